@@ -7,7 +7,7 @@ r_p bins, float64.  One *step* is one pass of the hot path over one batch of 10^
 parameter draws against the resident synthetic table (BASELINE configs[1]): one
 launch of predict_fused_kernel (occupations -> quadratic form -> results in a workgroup).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \\
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,13 +21,21 @@ step against its own replica of the table (the path shards over draws without an
 data-path collective); the results of all steps are collected on rank 0 by one RCCL
 gather over xGMI per block of --gather-every steps, on a second stream, overlapped with
 the following steps.  The SAME workload and payload for every N: (ngal, xi) of every draw,
-160 bytes; with --gpus > 1 the fused likelihood (``--gather chi2``: 16 bytes per draw, what
-an MCMC needs back) is timed as well, in a second region of the same run
+160 bytes; with --full and --gpus > 1 the fused likelihood (``--gather chi2``: 16 bytes per
+draw, what an MCMC needs back) is timed as well, in a second region of the same run
 (``second_payload``).  ``--workload interp5x5`` is BASELINE configs[3]: ``Interpolator.predict`` over a
 5 x 5 grid of such tables, 10^5 draws per step sharded round-robin over the ranks (strong
 scaling), gathered the same way.  PyTorch is only used for the gloo control plane.
 
-Rank 0 prints ONE short JSON line (< 4 KB) as the LAST line of stdout:
+A plain run sets up, settles the chip's power management (--settle-seconds), runs the W
+warm-up steps, times the K steps, writes the results of the last of them if
+``--dump-outputs DIR`` asks for them (rank 0's draws: ``ngal.npy`` and ``xi.npy`` --
+``chi2.npy`` with ``--gather chi2`` -- in float64; the inputs are seeded, the same from run
+to run) and prints ONE JSON line: metric, value, value_definition, unit, n_gpus, steps,
+warmup, ms_per_step (the time of one timed step), higher_is_better, scaling, vs_baseline,
+dtype, data, config.  Everything below is measured with ``--full`` only.
+
+With ``--full``, rank 0 prints ONE short JSON line (< 4 KB) as the LAST line of stdout:
 
   metric, value, unit, n_gpus, steps, warmup, ms_per_step, dtype, config, ...
   roofline       the kernel of the timed region.  ``frac`` = algorithmic flop of one step /
@@ -118,6 +126,48 @@ def headline(result, detail_path):
         line['roofline'].pop('launch_ms_source', None)
         text = json.dumps(line)
     return text
+
+
+def plain_headline(record):
+    """The line of a plain run (no --full): the headline keys and the configuration."""
+    line = {key: record[key] for key in HEADLINE_KEYS}
+    line['config'] = {key: record['config'][key] for key in CONFIG_KEYS
+                      if key in record['config']}
+    return json.dumps(line)
+
+
+def describe_workload(interp_mode, n_draws, world_size):
+    if interp_mode:
+        return ('BASELINE configs[3]: Interpolator.predict() over a 5 x 5 grid of '
+                'synthetic auto tables (each 50 mass bins x {cen,sat}, G=100, P=5050, 19 '
+                'rp bins), Zheng07, n_gauss_prim=10; %d draws per step sharded '
+                'round-robin over %d GPU(s), draws resident in HBM, results gathered on '
+                'rank 0' % (n_draws * world_size, world_size))
+    return ('BASELINE configs[1]: Zheng07 predict(), synthetic auto '
+            'table 50 mass bins x {cen,sat} (G=100, P=5050), 19 rp '
+            'bins, n_gauss_prim=10, batch of %d draws per GPU per '
+            'step, draws and results resident in HBM' % n_draws)
+
+
+DUMP_BYTES = 60 * 10**6     # (64 MB at most with the .npy headers)
+
+
+def dump_outputs(directory, dev, region, index, n_draws):
+    """--dump-outputs: the results of step `index` of `region` (this rank's draws) as a caller
+    of the device-resident entry point receives them -- ngal (n_draws) and xi (n_draws x n_r),
+    or ngal and chi2 -- in float64 .npy files.  Beyond DUMP_BYTES in all, the same rows of
+    every array: a sorted sample of the draws drawn with a fixed seed."""
+    host = dev.download(region.out_ptr(region.ring.slot(index)), region.n_out)
+    ngal = host[:n_draws]
+    second = host[n_draws:].reshape(n_draws, -1)
+    if region.n_out * 8 > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(
+            n_draws, DUMP_BYTES // (region.n_out // n_draws * 8), replace=False))
+        ngal, second = ngal[rows], second[rows]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, 'ngal.npy'), ngal)
+    np.save(os.path.join(directory, 'chi2.npy' if region.chi2_mode else 'xi.npy'),
+            second[:, 0] if region.chi2_mode else second)
 
 
 def check_gathered(region, comm, lib, _lib, dev, handle, interp_mode, chi2_mode, n_draws, n_r,
@@ -224,8 +274,8 @@ def main():
                              'payload is timed as well, in a second region of the same run '
                              '(`second_payload`)')
     parser.add_argument('--second-payload', type=int, default=None,
-                        help='time the other payload in a second region (default: 1 for '
-                             '--gpus > 1, else 0)')
+                        help='--full: time the other payload in a second region (default: 1 '
+                             'for --gpus > 1, else 0)')
     parser.add_argument('--gather-every', type=int, default=0,
                         help='multi-GPU: steps per RCCL gather of the results (default: 32, or '
                              'a quarter of --steps for short runs so that the gathers overlap '
@@ -238,21 +288,33 @@ def main():
     parser.add_argument('--settle-seconds', type=float, default=0.3,
                         help='untimed load before the warm-up steps (power management)')
     parser.add_argument('--cpu-seconds', type=float, default=12.0,
-                        help='budget of the CPU baseline sample (0: skip)')
+                        help='--full: budget of the CPU baseline sample (0: skip)')
     parser.add_argument('--cpu-all-cores', type=int, default=1,
-                        help='also time one independent CPU walker per host core')
+                        help='--full: also time one independent CPU walker per host core')
     parser.add_argument('--other-configs', type=int, default=1,
-                        help='measure BASELINE configs[2..4] as well (single GPU only)')
+                        help='--full: measure BASELINE configs[2..4] as well (single GPU only)')
     parser.add_argument('--detail', type=int, default=1,
-                        help='0 = headline only: skip the secondary legs (host-to-host, batch '
+                        help='--full: 0 skips the secondary legs (host-to-host, batch '
                              'sizes, un-batched calls, tabulation, other configurations)')
     parser.add_argument('--check-gather', type=int, default=1,
-                        help='multi-rank: rank 0 compares every gathered step with its own '
+                        help='--full, multi-rank: rank 0 compares every gathered step with its own '
                              'evaluation of the sending rank\'s draws, bit for bit (after the '
                              'timed region)')
     parser.add_argument('--only-config', choices=CONFIG_TAGS, default=None,
                         help='measure ONLY that configuration of other_configs and print its '
                              'record (for rocprofv3 runs: tools/profile_round.sh)')
+    parser.add_argument('--full', action='store_true',
+                        help='everything besides the headline as well: the serialised and '
+                             'per-launch kernel timings, the roofline record, the check against '
+                             'the CPU oracle, the CPU baselines, the secondary legs, the second '
+                             'payload and the gather check of multi-rank runs, the sidecar '
+                             'bench_detail.json.  Without it a run sets up, warms up, times '
+                             'the steps and prints the result line only')
+    parser.add_argument('--dump-outputs', metavar='DIR', default=None,
+                        help='after the timed steps, write what the last of them computed for '
+                             'rank 0\'s draws to DIR: ngal.npy and xi.npy (chi2.npy with '
+                             '--gather chi2), float64, at most 64 MB in all (a fixed sample of '
+                             'the draws beyond that)')
     args = parser.parse_args()
     interp_mode = args.workload == 'interp5x5'
     if args.gather is None:
@@ -274,7 +336,8 @@ def main():
     # The all-cores CPU baseline forks its workers, so it runs before this process
     # touches the GPU.
     cpu_all = None
-    if world_size == 1 and args.cpu_seconds > 0 and args.cpu_all_cores and not interp_mode:
+    if (args.full and world_size == 1 and args.cpu_seconds > 0 and args.cpu_all_cores
+            and not interp_mode):
         cpu_all = cpu_baseline_all_cores(args.cpu_seconds / 2)
     lib = _lib.load()
     _lib.require_device()
@@ -461,11 +524,12 @@ def main():
     # Before the timed region, in the state rocprofv3's serialised trace of this script sees
     # (profiles/*_kernel_stats_lanes1.csv): after the long pipelined region the chip is a few
     # per cent slower for a while (round 2: 38.7 us there against 37.5 here and 36.5 in the
-    # trace).  No collectives inside: every rank does the same on its own.
-    _lib.check(lib.tc_table_set_option(timer_handle, b'pipeline', 0))
-    isolated_ms, n_launch, serial_step_ms = kernel_time(
-        lib, _lib, timer_handle, lambda: predict(0), synchronize)
-    _lib.check(lib.tc_table_set_option(timer_handle, b'pipeline', 1))
+    # trace).  No collectives inside: every rank does the same on its own.  (--full only)
+    if args.full:
+        _lib.check(lib.tc_table_set_option(timer_handle, b'pipeline', 0))
+        isolated_ms, n_launch, serial_step_ms = kernel_time(
+            lib, _lib, timer_handle, lambda: predict(0), synchronize)
+        _lib.check(lib.tc_table_set_option(timer_handle, b'pipeline', 1))
 
     # Untimed: load the chip until its power management has settled (tools/archive/ramp.py: a
     # region started from idle runs 10-20 % slower for the first tens of milliseconds),
@@ -510,8 +574,9 @@ def main():
     # are created beforehand.  ONE launch in `lanes_used` carries a pair -- the launches of one
     # lane: a pair costs its launch ~1.5 us on the queue, and pairs on all 20 launches of the
     # driver's --steps 20 made that region 1.3-2.0 us per step longer than the same 20 steps
-    # without them (42.2 against 40.5 us, four runs each in alternation on one box).
-    events_in_region = args.steps <= 1024
+    # without them (42.2 against 40.5 us, four runs each in alternation on one box).  A plain
+    # run (no --full) carries none.
+    events_in_region = args.full and args.steps <= 1024
 
     def region_events(begin):
         if not events_in_region:
@@ -552,9 +617,58 @@ def main():
         drain()
         region_events(False)
     elapsed, breakdown, region_launches = timed(region)
+    if args.dump_outputs and comm.is_root:
+        dump_outputs(args.dump_outputs, dev, region, args.steps - 1, n_draws)
+
+    # ---- the record of the timed region: all that a plain run (no --full) prints ------------
+    n_bins = 2 * N_PRIM * N_SEC
+    n_pairs = n_bins * (n_bins + 1) // 2
+    config = {
+        'workload': describe_workload(interp_mode, n_draws, comm.world_size),
+        'draws_per_gpu_per_step': n_draws,
+        'n_bins': n_bins, 'n_pairs': n_pairs, 'n_r': N_R, 'n_tables': n_tables,
+        'parallelism': 'draws sharded over %d GPU(s), table%s replicated' %
+                       (comm.world_size, 's' if interp_mode else ''),
+        'gather': comm.gather_backend,
+        'rccl_ranks': comm.world_size if comm.comm is not None else 0,
+        'gather_payload': 'ngal + chi2 (16 B per draw)' if chi2_mode
+                          else 'ngal + xi (%d B per draw)' % (8 * (1 + N_R)),
+        'gather_payload_options': {
+            'chi2': '16 B per draw = %.2f MB per rank per gather' %
+                    (16e-6 * n_draws * every),
+            'full': '%d B per draw = %.2f MB per rank per gather' %
+                    (8 * (1 + N_R), 8e-6 * (1 + N_R) * n_draws * every)},
+        'gather_every_steps': every,
+        'lanes': lanes_used,
+    }
+    if comm.rccl_error:
+        config['rccl_error'] = comm.rccl_error
+    record = {
+        'metric': 'predict_calls_per_sec',
+        'value': comm.world_size * n_draws * args.steps / elapsed,
+        'value_definition': 'device-resident',
+        'unit': 'calls/s',
+        'n_gpus': comm.world_size,
+        'steps': args.steps,
+        'warmup': args.warmup,
+        'ms_per_step': elapsed / args.steps * 1e3,
+        'higher_is_better': True,
+        'scaling': 'strong' if interp_mode else 'weak',
+        'vs_baseline': None,
+        'dtype': 'f64',
+        'data': 'synthetic',
+        'config': config,
+    }
+    if not args.full:
+        if comm.is_root:
+            print(plain_headline(record), flush=True)
+        dev.free_all()
+        comm.barrier()
+        comm.close()
+        return
 
     # The other payload, same workload, same steps: a second region of the same run (default
-    # for --gpus > 1, where what travels to rank 0 is the difference between the two).
+    # for --gpus > 1 with --full, where what travels to rank 0 is the difference between the two).
     second = None
     want_second = (args.second_payload if args.second_payload is not None
                    else int(comm.world_size > 1))
@@ -586,8 +700,6 @@ def main():
                                       synthetic, interp, synchronize)
 
     # ---- dominant kernel: contraction, per-launch start / stop events -------------------
-    n_bins = 2 * N_PRIM * N_SEC
-    n_pairs = n_bins * (n_bins + 1) // 2
     flop_contract = n_draws * n_tables * pair_flops(n_bins, N_R)
     drain()
     # (the serialised pass ran before the timed region, see above) ... and stretched by the
@@ -680,55 +792,13 @@ def main():
         concurrency = launch_ms / (step_seconds * 1e3)
         # THE fraction: algorithmic flop of one step over the step time of the timed region
         achieved = flop_contract / step_seconds / 1e12
-        total_draws = comm.world_size * n_draws * args.steps
-        if interp_mode:
-            workload = ('BASELINE configs[3]: Interpolator.predict() over a 5 x 5 grid of '
-                        'synthetic auto tables (each 50 mass bins x {cen,sat}, G=100, P=5050, 19 '
-                        'rp bins), Zheng07, n_gauss_prim=10; %d draws per step sharded '
-                        'round-robin over %d GPU(s), draws resident in HBM, results gathered on '
-                        'rank 0' % (n_draws * comm.world_size, comm.world_size))
-        else:
-            workload = ('BASELINE configs[1]: Zheng07 predict(), synthetic auto '
-                        'table 50 mass bins x {cen,sat} (G=100, P=5050), 19 rp '
-                        'bins, n_gauss_prim=10, batch of %d draws per GPU per '
-                        'step, draws and results resident in HBM' % n_draws)
-        result = {
-            'metric': 'predict_calls_per_sec',
-            'value': total_draws / elapsed,
-            'value_definition': 'device-resident',
+        result = dict(record)
+        result.update({
             'value_is': 'device-resident rate (draws and results in HBM; multi-GPU: results '
                         'gathered on rank 0); the host-to-host rate of SURVEY.md 8d is '
                         'value_host_to_host (= host_to_host_pipelined.value)',
-            'unit': 'calls/s',
-            'n_gpus': comm.world_size,
-            'steps': args.steps,
-            'warmup': args.warmup,
             'settle_steps': settle_steps,
             'timed_region_breakdown_us': breakdown,
-            'ms_per_step': elapsed / args.steps * 1e3,
-            'higher_is_better': True,
-            'scaling': 'strong' if interp_mode else 'weak',
-            'vs_baseline': None,
-            'dtype': 'f64',
-            'data': 'synthetic',
-            'config': {
-                'workload': workload,
-                'draws_per_gpu_per_step': n_draws,
-                'n_bins': n_bins, 'n_pairs': n_pairs, 'n_r': N_R, 'n_tables': n_tables,
-                'parallelism': 'draws sharded over %d GPU(s), table%s replicated' %
-                               (comm.world_size, 's' if interp_mode else ''),
-                'gather': comm.gather_backend,
-                'rccl_ranks': comm.world_size if comm.comm is not None else 0,
-                'gather_payload': 'ngal + chi2 (16 B per draw)' if chi2_mode
-                                  else 'ngal + xi (%d B per draw)' % (8 * (1 + N_R)),
-                'gather_payload_options': {
-                    'chi2': '16 B per draw = %.2f MB per rank per gather' %
-                            (16e-6 * n_draws * every),
-                    'full': '%d B per draw = %.2f MB per rank per gather' %
-                            (8 * (1 + N_R), 8e-6 * (1 + N_R) * n_draws * every)},
-                'gather_every_steps': every,
-                'lanes': lanes_used,
-            },
             'roofline': {
                 'kernel': kernel_name,
                 'bound': 'mfma',
@@ -784,9 +854,7 @@ def main():
             },
             'parity_max_rel_vs_oracle': parity,
             'device': _lib.device_name(),
-        }
-        if comm.rccl_error:
-            result['config']['rccl_error'] = comm.rccl_error
+        })
         if gather_check is not None:
             result['gather_check'] = gather_check
         if second is not None:

@@ -476,8 +476,8 @@ def test_bench_under_torchrun_single_rank(mode):
     result = subprocess.run(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
          '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port',
-         str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '1', '--cpu-seconds', '0',
-         '--settle-seconds', '0.05', '--other-configs', '0'] + extra,
+         str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '1', '--full',
+         '--cpu-seconds', '0', '--settle-seconds', '0.05', '--other-configs', '0'] + extra,
         env=env, capture_output=True, text=True, timeout=900)
     assert result.returncode == 0, result.stdout[-2000:] + result.stderr[-2000:]
     # the record is the LAST line of stdout, short enough for the driver's parser, and its
@@ -537,8 +537,8 @@ def test_bench_with_two_ranks_on_one_device(workload):
     result = subprocess.run(
         [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
          '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port',
-         str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--cpu-seconds', '0',
-         '--settle-seconds', '0.05', '--other-configs', '0'] + extra,
+         str(_free_port()), os.path.join(REPO, 'bench.py'), '--gpus', '2', '--full',
+         '--cpu-seconds', '0', '--settle-seconds', '0.05', '--other-configs', '0'] + extra,
         env=env, capture_output=True, text=True, timeout=900)
     assert result.returncode == 0, result.stdout[-2000:] + result.stderr[-3000:]
     line = result.stdout.strip().splitlines()[-1]
@@ -561,6 +561,47 @@ def test_bench_with_two_ranks_on_one_device(workload):
     assert abs(record['value'] * record['ms_per_step'] * 1e-3 / per_step - 1) < 0.02, record
     # the second payload (default for more than one rank) ran in the same job
     assert '16 B' in record['second_payload']['gather_payload']
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the timed steps and the result line only, and --dump-outputs
+    writes what the last timed step computed -- the same bits in two runs with the same
+    arguments, the oracle's values for the first draws."""
+    import json
+    import subprocess
+    from util import REPO
+    from tabcorr_amd import synthetic
+    from oracle import tabcorr_oracle as oracle
+    from bench_legs import N_PRIM, N_SEC, N_R
+
+    def run(directory):
+        result = subprocess.run(
+            [sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '20',
+             '--warmup', '3', '--settle-seconds', '0.05', '--dump-outputs', str(directory)],
+            capture_output=True, text=True, timeout=600)
+        assert result.returncode == 0, result.stdout[-2000:] + result.stderr[-2000:]
+        lines = result.stdout.strip().splitlines()
+        assert not any(line.startswith('detail ') for line in lines), lines[:-1]
+        return json.loads(lines[-1])
+
+    record = run(tmp_path / 'a')
+    assert record['metric'] == 'predict_calls_per_sec' and record['unit'] == 'calls/s'
+    assert record['higher_is_better'] is True and record['dtype'] == 'f64'
+    assert record['steps'] == 20 and record['warmup'] == 3 and record['n_gpus'] == 1
+    assert abs(record['value'] * record['ms_per_step'] * 1e-3 / 10000 - 1) < 1e-9
+    for key in ('roofline', 'cpu_baseline', 'parity_max_rel_vs_oracle', 'detail'):
+        assert key not in record, key
+    ngal = np.load(tmp_path / 'a' / 'ngal.npy')
+    xi = np.load(tmp_path / 'a' / 'xi.npy')
+    assert ngal.dtype == xi.dtype == np.float64
+    assert ngal.shape == (10000, ) and xi.shape == (10000, N_R)
+    table = synthetic.synthetic_table(N_PRIM, N_SEC, (N_R, ), 'auto', seed=0)
+    expect = oracle.predict_zheng07_batch(table, synthetic.zheng07_draws(10000, seed=1)[:4])
+    assert_rel(ngal[:4], expect[0], RTOL)
+    assert_rel(xi[:4], expect[1], RTOL)
+    run(tmp_path / 'b')
+    assert np.array_equal(np.load(tmp_path / 'b' / 'ngal.npy'), ngal)
+    assert np.array_equal(np.load(tmp_path / 'b' / 'xi.npy'), xi)
 
 
 def test_read_hdf5_and_predict():

@@ -501,6 +501,53 @@ def test_result_ring_single_rank_bookkeeping():
         ResultRing(10, 0, 2, None)
 
 
+@pytest.mark.parametrize('chi2_mode', [False, True])
+def test_bench_dump_outputs_of_a_step(tmp_path, monkeypatch, chi2_mode):
+    """bench.py --dump-outputs: the slot the given step wrote, split as a caller receives it
+    (ngal | xi or ngal | chi2), float64; above the size limit the same fixed sample of rows
+    of every array."""
+    import bench
+    from tabcorr_amd.parallel import ResultRing
+    n_draws, n_r = 50, 3
+    n_out = n_draws * (2 if chi2_mode else 1 + n_r)
+
+    class Region:
+        ring = ResultRing(n_out, 2, 1, lambda *a: None, n_blocks=2)
+
+        def __init__(self):
+            self.n_out, self.chi2_mode = n_out, chi2_mode
+
+        def out_ptr(self, slot, offset=0):
+            return slot * n_out + offset
+
+    class Dev:
+        memory = np.arange(4 * n_out, dtype=np.float64)
+
+        def download(self, ptr, count):
+            return self.memory[ptr:ptr + count].copy()
+
+    bench.dump_outputs(str(tmp_path / 'all'), Dev(), Region(), 6, n_draws)   # (slot 2)
+    base = 2 * n_out
+    ngal = np.load(tmp_path / 'all' / 'ngal.npy')
+    second = np.load(tmp_path / 'all' / ('chi2.npy' if chi2_mode else 'xi.npy'))
+    assert ngal.dtype == second.dtype == np.float64
+    assert np.array_equal(ngal, base + np.arange(n_draws))
+    expect = base + n_draws + np.arange(n_out - n_draws)
+    assert np.array_equal(second, expect if chi2_mode else expect.reshape(n_draws, n_r))
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 8 * n_out // 5)
+    for name in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / name), Dev(), Region(), 6, n_draws)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert sum(os.path.getsize(tmp_path / 'a' / f) - 128 for f in files) <= 8 * n_out // 5
+    sample = np.load(tmp_path / 'a' / 'ngal.npy') - base
+    assert len(sample) == n_draws // 5 and np.all(np.diff(sample) > 0)
+    rows = np.load(tmp_path / 'a' / files[0 if chi2_mode else 1])
+    assert np.array_equal(rows, (expect if chi2_mode else expect.reshape(n_draws, n_r))[
+        sample.astype(int)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f))
+
+
 # -- HDF5 through the C library (no h5py / astropy) -------------------------------------
 
 def _need_hdf5():

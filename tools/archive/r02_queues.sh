@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TABCORR_AMD_LIBRARY=$PWD/build/ab/dev.so
 run() {
-  env "$@" python bench.py --cpu-seconds 0 --other-configs 0 --steps 6000 --warmup 300 2>/dev/null | python -c "
+  env "$@" python bench.py --full --cpu-seconds 0 --other-configs 0 --steps 6000 --warmup 300 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.readlines()[-1]); print('%-60s ms/step %.4f contract %.4f (overlapped %.4f)' % ('$*', d['ms_per_step'], d['roofline']['mean_launch_ms'], d['roofline']['overlapped_launch_ms']))"
 }
 run A=0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Developer sweep on one box: launch geometry of the occupation / finalisation kernels.
 cd "$GRAFT_REPO_ROOT" || exit 1
-run() { python bench.py --cpu-seconds 0 --other-configs 0 --steps 6000 --warmup 300 --settle-seconds 0.1 "$@" | python -c "
+run() { python bench.py --full --cpu-seconds 0 --other-configs 0 --steps 6000 --warmup 300 --settle-seconds 0.1 "$@" | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); r = d['roofline']
 print('%-70s %.4g calls/s  %.2f us/step  overlapped kernel %.2f' % ('$*', d['value'], d['ms_per_step'] * 1e3, r['overlapped_launch_ms'] * 1e3))"; }

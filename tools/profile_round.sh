@@ -12,7 +12,7 @@ WHAT=${1:-all}
 ROUND=${ROUND:-r06}
 OUT=gpurun_out/profile
 mkdir -p $OUT
-FAST="--cpu-seconds 0 --detail 0"
+FAST="--full --cpu-seconds 0 --detail 0"
 
 pmc_passes() {   # $1 = output stem, rest = bench arguments
   local stem=$1; shift
@@ -55,14 +55,14 @@ if [ $WHAT = main ] || [ $WHAT = all ]; then
   # predict_fused_kernel, bench.py's serialised pass the three kernels -- both are counted)
   pmc_passes pmc_summary --steps 50 --warmup 5 $FAST
   # (the last line of stdout is the record; everything else sits in the sidecar)
-  python bench.py > $OUT/bench.log 2> $OUT/bench.err
+  python bench.py --full > $OUT/bench.log 2> $OUT/bench.err
   tail -1 $OUT/bench.log > $OUT/bench.json
   cp bench_detail.json $OUT/bench_detail.json
   echo "default bench done"
   # the driver's own command (short timed region), three times
   : > $OUT/bench_driver_command.json
   for i in 1 2 3; do
-    python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 >> $OUT/bench_driver_command.json
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $OUT/bench_driver_command.json
   done
   # --lanes 1: every call alone on its lane = the three-kernel path, kernels serialised;
   # default lanes: predict_fused_kernel, one launch per step, four launches overlapping;

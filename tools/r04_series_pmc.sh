@@ -9,7 +9,7 @@ for on in 1 0; do
   rm -rf $OUT/pass
   rocprofv3 --pmc SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_SALU \
     --output-format csv -d $OUT/pass -- \
-    python3 bench.py --steps 50 --warmup 5 --cpu-seconds 0 --other-configs 0 --option series=$on \
+    python3 bench.py --full --steps 50 --warmup 5 --cpu-seconds 0 --other-configs 0 --option series=$on \
     > $OUT/log_$on.txt 2>&1
   echo "series=$on"
   python3 tools/pmc_summary.py $OUT/pass | grep predict_fused

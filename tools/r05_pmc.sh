@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/pmc_r05
 mkdir -p $OUT
 KERNEL=${KERNEL:-predict_fused}
-ARGS=${ARGS:---steps 50 --warmup 5 --cpu-seconds 0 --detail 0}
+ARGS=${ARGS:---full --steps 50 --warmup 5 --cpu-seconds 0 --detail 0}
 SETS=${SETS:-SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS|SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_BUSY_CU_CYCLES}
 NAME=${NAME:-r05_pmc}
 for spec in "$@"; do

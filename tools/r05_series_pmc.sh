@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/pmc_series
 mkdir -p $OUT
 KERNEL=${KERNEL:-predict_fused}
-ARGS=${ARGS:---steps 50 --warmup 5 --cpu-seconds 0 --detail 0}
+ARGS=${ARGS:---full --steps 50 --warmup 5 --cpu-seconds 0 --detail 0}
 for spec in "$@"; do
   name=${spec%%=*}; rest=${spec#*=}
   lib=${rest%%,*}; opts=""

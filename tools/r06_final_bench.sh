@@ -5,12 +5,12 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/profile
 mkdir -p $OUT
-python bench.py > $OUT/bench.log 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 tail -1 $OUT/bench.log > $OUT/bench.json
 cp bench_detail.json $OUT/bench_detail.json
 : > $OUT/bench_driver_command.json
 for i in 1 2 3; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 >> $OUT/bench_driver_command.json
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 >> $OUT/bench_driver_command.json
 done
 python tools/r06_latency.py > gpurun_out/r06_latency.log 2>&1
 python tools/r06_two_tables.py > gpurun_out/r06_two_tables.log 2>&1

@@ -4,7 +4,7 @@
 # 2: no matrix phase, 3: neither -- prologue, reductions and stores only).
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TABCORR_AMD_LIBRARY=build/ab/dev.so
-F="--cpu-seconds 0 --detail 0 --steps 2000 --warmup 200 --lanes 1 --option fused=2"
+F="--full --cpu-seconds 0 --detail 0 --steps 2000 --warmup 200 --lanes 1 --option fused=2"
 for draws in 40 64 32; do
   for skip in 0 1 2 3; do
     n=10000; [ $draws = 32 ] && n=8192
