@@ -305,24 +305,33 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *                 tc_table_synchronize (or gather with tc_comm_gather, which waits for every
  *                 lane); 1: their finalisations are chained so that results appear in call
  *                 order (0.3 - 3 us per 10^4-draw step).
- *   "fused"       1 (default): pipelined device-pointer and asynchronous calls that qualify
- *                 (mode auto, at most 20 r values; 104 bins, or 208 for the Zheng07 family with
- *                 n_gauss_prim = 10; total or separated by galaxy type) run as ONE launch per
- *                 batch, a workgroup carrying 64 (32) draws from the parameters to the results,
- *                 for batches of
+ *   "fused"       1 (default): calls that qualify (mode auto, at most 20 r values; 104 bins,
+ *                 or 208 for the Zheng07 family with n_gauss_prim = 10; total or separated by
+ *                 galaxy type) run as ONE launch per batch, a workgroup carrying 64, 40 or 32
+ *                 draws from the parameters to the results, where that form is estimated to be
+ *                 the faster one.  Pipelined device-pointer and asynchronous calls: batches of
  *                 "fused_min_draws" .. "fused_max_draws" draws (default 0 = chosen per table:
  *                 512 for small tables, ~7000 for 100 bins x 19 r values; 30720; asynchronous
- *                 calls: no upper bound); 0: always occupation, contraction, finalisation
- *                 kernels; 2: one launch also for calls that run alone on their lane and for
- *                 tables of 105 .. 248 bins (one 16-wave workgroup per CU: level with the
- *                 three kernels).
+ *                 calls: no upper bound).  Calls that run alone on their lane (host arrays, one
+ *                 lane, "pipeline" 0) take it by the same estimate from 2048 draws on, whatever
+ *                 "fused_min_draws" says: that option applies to pipelined calls only.  The
+ *                 last bits of a result depend on the form that produced it (see
+ *                 "deterministic").  0: always occupation, contraction, finalisation kernels;
+ *                 2: one launch for every call it can serve, and for tables of 105 .. 248 bins
+ *                 (one 16-wave workgroup per CU: level with the three kernels).
  *   "fused_waves" 0 (default): 8 waves per workgroup where two workgroups fit a CU; 8 / 16:
  *                 that many where the table fits.
  *   "fused_draws" 0 (default): workgroups of 32 draws (one tile, eight waves, two per CU) for
  *                 batches below 8192 draws of the Zheng07 family with n_gauss_prim = 10 --
  *                 a third faster there, and the one-launch form then pays from 12 draws per
  *                 bin on -- and for tables of 105 .. 208 bins, of 64 draws otherwise; 32 / 64:
- *                 forced.
+ *                 forced; 40: the latency form ("fused_spread") for every batch it serves.
+ *   "fused_spread" 1 (default): calls that have the chip to themselves (host arrays, one lane,
+ *                 "pipeline" 0) take the latency form of the one-launch kernel -- workgroups of
+ *                 40 draws, one per CU; undecorated Zheng07, n_gauss_prim = 10, total
+ *                 correlation function -- for batches of "fused_spread_min" draws (default
+ *                 8192) up to "fused_spread_rounds" (default 1, at most 64) workgroups per CU;
+ *                 0: never.
  *   "sync_chunks" synchronous host-array calls (tc_predict_zheng07_batch, tc_chi2_zheng07_batch
  *                 beyond the zero-copy size): 0 (default) batches of 2048 draws and more are cut
  *                 into 2 .. 8 chunks of draws (about a megabyte of results each) whose staging,

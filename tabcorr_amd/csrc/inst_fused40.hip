@@ -7,14 +7,13 @@
 namespace tc {
 namespace host {
 
-int launch_fused_instance_40(const FusedInstance& in, int device, int n_u, dim3 grid, dim3 block,
-                             int lds, hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
-                             const tc::FusedArgs& fa) {
+int launch_fused_instance_40(const FusedInstance& in, const FusedLaunch& l) {
   if (in.assembias || in.modulate || in.leauthaud || in.grouped || in.n_gauss != 10)
     return fail(TC_ERR_UNSUPPORTED, "internal: no 40-draw instance for these flags");
-  if (in.defer == 2) return launch_fused<10, false, false, false, 8, 40, false, 2>(TC_FUSED_ARGS);
-  if (in.defer == 1) return launch_fused<10, false, false, false, 8, 40, false, 1>(TC_FUSED_ARGS);
-  return launch_fused<10, false, false, false, 8, 40>(TC_FUSED_ARGS);
+  return with_int<1, 2>(
+      in.defer,
+      [&](auto sd) { return launch_fused<10, false, false, false, 8, 40, false, sd()>(l); },
+      [&] { return launch_fused<10, false, false, false, 8, 40>(l); });
 }
 
 }  // namespace host

@@ -2,6 +2,7 @@
 // kernels, the interpolator's coefficients and the likelihood: their launches, in a translation
 // unit of their own.
 #define TC_UNIT_QUAD
+#include "dispatch.h"
 #include "internal.h"
 #include "kernels.hip.h"
 
@@ -9,109 +10,72 @@ namespace tc {
 namespace host {
 
 // The occupation kernel of the three-kernel path for these flags (instances: Zheng07 family
-// with ten or any number of nodes, per bin or per group of bins; Leauthaud11).
+// with ten or any number of nodes, per bin or -- ten nodes -- per group of bins, each as an
+// (assembias, modulate) square; Leauthaud11, modulate or not).
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
                       int64_t grid_blocks, hipStream_t stream) {
   const dim3 grid((unsigned)grid_blocks), block(tc::kOccWaves * 64);
   const bool assembias = (flags & TC_FLAG_ASSEMBIAS) != 0;
   const bool modulate = (flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0;
-#define TC_OCC(NG, AB, MO)                                                           \
-  hipLaunchKernelGGL((tc::occ_zheng07_kernel<NG, AB, MO>), grid, block, 0, stream, oa)
-  if (flags & TC_FLAG_LEAUTHAUD11) {
-    if (modulate)
-      hipLaunchKernelGGL(tc::occ_leauthaud11_kernel<true>, grid, block, 0, stream, oa);
-    else
-      hipLaunchKernelGGL(tc::occ_leauthaud11_kernel<false>, grid, block, 0, stream, oa);
-  } else if (grouped) {
-#define TC_OCC_GROUPED(AB, MO)                                                        \
-  hipLaunchKernelGGL((tc::occ_zheng07_kernel<10, AB, MO, true>), grid, block, 0, stream, oa)
-    if (!assembias && !modulate) TC_OCC_GROUPED(false, false);
-    else if (!assembias) TC_OCC_GROUPED(false, true);
-    else if (!modulate) TC_OCC_GROUPED(true, false);
-    else TC_OCC_GROUPED(true, true);
-#undef TC_OCC_GROUPED
-  } else if (n_gauss == 10) {
-    if (!assembias && !modulate) TC_OCC(10, false, false);
-    else if (!assembias) TC_OCC(10, false, true);
-    else if (!modulate) TC_OCC(10, true, false);
-    else TC_OCC(10, true, true);
-  } else {
-    if (!assembias && !modulate) TC_OCC(0, false, false);
-    else if (!assembias) TC_OCC(0, false, true);
-    else if (!modulate) TC_OCC(0, true, false);
-    else TC_OCC(0, true, true);
-  }
-#undef TC_OCC
+  auto zheng07 = [&](auto ng, auto gr) {
+    return with_bools(
+        [&](auto ab, auto mo) {
+          hipLaunchKernelGGL((tc::occ_zheng07_kernel<ng(), ab(), mo(), gr()>), grid, block, 0,
+                             stream, oa);
+          return TC_OK;
+        },
+        assembias, modulate);
+  };
+  if (flags & TC_FLAG_LEAUTHAUD11)
+    with_bools(
+        [&](auto mo) {
+          hipLaunchKernelGGL(tc::occ_leauthaud11_kernel<mo()>, grid, block, 0, stream, oa);
+          return TC_OK;
+        },
+        modulate);
+  else if (grouped)
+    zheng07(int_c<10>{}, std::true_type{});
+  else if (n_gauss == 10)
+    zheng07(int_c<10>{}, std::false_type{});
+  else
+    zheng07(int_c<0>{}, std::false_type{});
   TC_HIP(hipGetLastError());
   return TC_OK;
 }
 
-int launch_contract_quad(int n_u, bool interp, const tc::QuadArgs& args, int lds_bytes,
+// Instances: contract_quad_kernel<1 .. 5, interp>, contract_quad_f32_kernel<1 .. 4, interp>.
+int launch_contract_quad(int n_u, int dtype, bool interp, const tc::QuadArgs& args, int lds_bytes,
                          hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
   const dim3 grid((unsigned)((args.n_waves + tc::kQuadWavesPerBlock - 1) /
                              tc::kQuadWavesPerBlock));
   const dim3 block(64 * tc::kQuadWavesPerBlock);
   if (args.n_waves == 0) return TC_OK;
-  switch (n_u) {
-#define TC_CASE(N)                                                                          \
-  case N:                                                                                   \
-    if (interp)                                                                             \
-      hipExtLaunchKernelGGL((tc::contract_quad_kernel<N, true>), grid, block, lds_bytes,  \
-                            stream, start, stop, 0, args);                                \
-    else                                                                                    \
-      hipExtLaunchKernelGGL((tc::contract_quad_kernel<N, false>), grid, block, lds_bytes, \
-                            stream, start, stop, 0, args);                                \
-    break;
-    TC_CASE(1) TC_CASE(2) TC_CASE(3) TC_CASE(4) TC_CASE(5)
-#undef TC_CASE
-    default:
-      return fail(TC_ERR_UNSUPPORTED, "no kernel for %d r sub-tiles", n_u);
-  }
-  TC_HIP(hipGetLastError());
-  return TC_OK;
-}
-
-int launch_contract_quad_f32_interp(int n_u, const tc::QuadArgs& args, int lds_bytes,
-                                    hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
-  const dim3 grid((unsigned)((args.n_waves + tc::kQuadWavesPerBlock - 1) /
-                             tc::kQuadWavesPerBlock));
-  const dim3 block(64 * tc::kQuadWavesPerBlock);
-  if (args.n_waves == 0) return TC_OK;
-  switch (n_u) {
-#define TC_CASE(N)                                                                          \
-  case N:                                                                                   \
-    hipExtLaunchKernelGGL((tc::contract_quad_f32_kernel<N, true>), grid, block, lds_bytes, \
-                          stream, start, stop, 0, args);                                  \
-    break;
-    TC_CASE(1) TC_CASE(2) TC_CASE(3) TC_CASE(4)
-#undef TC_CASE
-    default:
-      return fail(TC_ERR_UNSUPPORTED, "no float32 kernel for %d r sub-tiles", n_u);
-  }
-  TC_HIP(hipGetLastError());
-  return TC_OK;
-}
-
-int launch_contract_quad_f32(int n_u, const tc::QuadArgs& args, int lds_bytes,
-                             hipStream_t stream, hipEvent_t start, hipEvent_t stop) {
-  const dim3 grid((unsigned)((args.n_waves + tc::kQuadWavesPerBlock - 1) /
-                             tc::kQuadWavesPerBlock));
-  const dim3 block(64 * tc::kQuadWavesPerBlock);
-  if (args.n_waves == 0) return TC_OK;
-  switch (n_u) {
-#define TC_CASE(N)                                                                        \
-  case N:                                                                                 \
-    hipExtLaunchKernelGGL((tc::contract_quad_f32_kernel<N, false>), grid, block,          \
-                          lds_bytes,                                                      \
-                          stream, start, stop, 0, args);                                  \
-    break;
-    TC_CASE(1) TC_CASE(2) TC_CASE(3) TC_CASE(4)
-#undef TC_CASE
-    default:
-      return fail(TC_ERR_UNSUPPORTED, "no float32 kernel for %d r sub-tiles", n_u);
-  }
-  TC_HIP(hipGetLastError());
-  return TC_OK;
+  const bool f32 = dtype == TC_DTYPE_F32;
+  auto none = [&] {
+    return f32 ? fail(TC_ERR_UNSUPPORTED, "no float32 kernel for %d r sub-tiles", n_u)
+               : fail(TC_ERR_UNSUPPORTED, "no kernel for %d r sub-tiles", n_u);
+  };
+  return with_int<1, 2, 3, 4, 5>(
+      n_u,
+      [&](auto n) {
+        return with_bools(
+            [&](auto single, auto in) {
+              if constexpr (single() && n() == 5) {
+                return none();
+              } else {
+                if constexpr (single())
+                  hipExtLaunchKernelGGL((tc::contract_quad_f32_kernel<n(), in()>), grid, block,
+                                        lds_bytes, stream, start, stop, 0, args);
+                else
+                  hipExtLaunchKernelGGL((tc::contract_quad_kernel<n(), in()>), grid, block,
+                                        lds_bytes, stream, start, stop, 0, args);
+                TC_HIP(hipGetLastError());
+                return TC_OK;
+              }
+            },
+            f32, interp);
+      },
+      none);
 }
 
 int launch_finalize_quad(const tc::FinalizeQuadArgs& args, const Tuning& tuning,
@@ -146,69 +110,43 @@ int launch_finalize_quad(const tc::FinalizeQuadArgs& args, const Tuning& tuning,
   return TC_OK;
 }
 
-#define TC_RT_CASES                                                           \
-  TC_CASE(4) TC_CASE(8) TC_CASE(12) TC_CASE(16) TC_CASE(20) TC_CASE(24)       \
-  TC_CASE(28) TC_CASE(32)
-
-int launch_contract_rt(int rt, dim3 grid, dim3 block, int lds, hipStream_t stream,
+// Instances: contract_mfma_kernel<r tile, several tables> for r tiles of 4, 8, ..., 32.
+int launch_contract_rt(int rt, int device, dim3 grid, dim3 block, int lds, hipStream_t stream,
                        const tc::ContractArgs& args, hipEvent_t start, hipEvent_t stop) {
-  switch (rt) {
-#define TC_CASE(N)                                                            \
-  case N:                                                                     \
-    if (args.n_tables > 0)                                                    \
-      hipExtLaunchKernelGGL((tc::contract_mfma_kernel<N, true>), grid, block, \
-                            lds, stream, start, stop, 0, args);               \
-    else                                                                      \
-      hipExtLaunchKernelGGL((tc::contract_mfma_kernel<N, false>), grid, block, \
-                            lds, stream, start, stop, 0, args);               \
-    break;
-    TC_RT_CASES
-#undef TC_CASE
-    default:
-      return fail(TC_ERR_UNSUPPORTED, "no kernel for r tile %d", rt);
-  }
-  TC_HIP(hipGetLastError());
-  return TC_OK;
+  return with_int<4, 8, 12, 16, 20, 24, 28, 32>(
+      rt,
+      [&](auto n) {
+        return with_bools(
+            [&](auto tables) {
+              const auto kernel = tc::contract_mfma_kernel<n(), tables()>;
+              if (lds > 64 * 1024) {
+                const int status = ensure_lds_limit((const void*)kernel, device, lds);
+                if (status != TC_OK) return status;
+              }
+              hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, start, stop, 0, args);
+              TC_HIP(hipGetLastError());
+              return TC_OK;
+            },
+            args.n_tables > 0);
+      },
+      [&] { return fail(TC_ERR_UNSUPPORTED, "no kernel for r tile %d", rt); });
 }
 
 // float32 variant (one kernel for every r tile: always 32 wide)
-int launch_contract_f32(dim3 grid, dim3 block, int lds, hipStream_t stream,
+int launch_contract_f32(int device, dim3 grid, dim3 block, int lds, hipStream_t stream,
                         const tc::ContractArgs& args, hipEvent_t start, hipEvent_t stop) {
-  if (lds > 64 * 1024) {
-    TC_HIP(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&tc::contract_f32_kernel<false>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    TC_HIP(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&tc::contract_f32_kernel<true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  }
-  if (args.n_tables > 0)
-    hipExtLaunchKernelGGL(tc::contract_f32_kernel<true>, grid, block, lds, stream, start, stop,
-                          0, args);
-  else
-    hipExtLaunchKernelGGL(tc::contract_f32_kernel<false>, grid, block, lds, stream, start, stop,
-                          0, args);
-  TC_HIP(hipGetLastError());
-  return TC_OK;
-}
-
-int set_lds_limit_rt(int rt, int lds) {
-  switch (rt) {
-#define TC_CASE(N)                                                            \
-  case N:                                                                     \
-    TC_HIP(hipFuncSetAttribute(                                               \
-        reinterpret_cast<const void*>(&tc::contract_mfma_kernel<N, false>),   \
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds));                    \
-    TC_HIP(hipFuncSetAttribute(                                               \
-        reinterpret_cast<const void*>(&tc::contract_mfma_kernel<N, true>),    \
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds));                    \
-    break;
-    TC_RT_CASES
-#undef TC_CASE
-    default:
-      break;
-  }
-  return TC_OK;
+  return with_bools(
+      [&](auto tables) {
+        const auto kernel = tc::contract_f32_kernel<tables()>;
+        if (lds > 64 * 1024) {
+          const int status = ensure_lds_limit((const void*)kernel, device, lds);
+          if (status != TC_OK) return status;
+        }
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, start, stop, 0, args);
+        TC_HIP(hipGetLastError());
+        return TC_OK;
+      },
+      args.n_tables > 0);
 }
 
 int launch_finalize(const FinalizeArgs& args, const Tuning& tuning, hipStream_t stream) {

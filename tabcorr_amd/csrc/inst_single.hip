@@ -3,8 +3,6 @@
 // single_draw_kernel and resident_draw_kernel are two instances of one body, and with the
 // compiler's default (contraction across statements, decided per instance) the same draw came
 // out ~1e-14 apart depending on which of the two served it.
-#include <mutex>
-
 #define TC_UNIT_SINGLE
 #include "internal.h"
 #include "kernels.hip.h"
@@ -28,18 +26,9 @@ int launch_resident_kernel(int blocks, hipStream_t stream, const tc::SingleArgs&
 
 int launch_ensemble_kernel(int device, int grid, int lds_bytes, hipStream_t stream,
                            const tc::EnsembleArgs& ea) {
-  {
-    // (the attribute belongs to the function ON a device: once per device, and handles may
-    // be used from different threads)
-    static std::mutex attribute_mutex;
-    static bool attribute_set[64] = {};
-    std::lock_guard<std::mutex> lock(attribute_mutex);
-    if (!(device >= 0 && device < 64 && attribute_set[device])) {
-      TC_HIP(hipFuncSetAttribute((const void*)tc::resident_ensemble_kernel,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-      if (device >= 0 && device < 64) attribute_set[device] = true;
-    }
-  }
+  const int status =
+      ensure_lds_limit((const void*)tc::resident_ensemble_kernel, device, 150 * 1024);
+  if (status != TC_OK) return status;
   hipLaunchKernelGGL(tc::resident_ensemble_kernel, dim3((unsigned)grid),
                      dim3(tc::kEnsembleThreads), (size_t)lds_bytes, stream, ea);
   TC_HIP(hipGetLastError());

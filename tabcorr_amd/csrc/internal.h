@@ -647,11 +647,16 @@ int wave_slots(const tc_table* t, bool interp);
 int blocks_per_cu(int lds_bytes, int waves, int slots);
 int choose_chunking(tc_table* t, int64_t n_draws, int tables_per_block, DeviceChunking** out,
                     int* lds_bytes);
-int launch_contract_rt(int rt, dim3 grid, dim3 block, int lds, hipStream_t stream,
+// Raises the dynamic-LDS limit of `kernel` on `device` (the calling thread's current device:
+// the attribute belongs to the function ON a device) to at least `bytes`.  Thread-safe -- handles
+// may be used from different threads -- and the runtime is only asked when the largest limit set
+// so far is smaller (runtime.cpp).
+int ensure_lds_limit(const void* kernel, int device, int bytes);
+// (segment kernels: they raise their limit to `lds` where it exceeds 64 KiB)
+int launch_contract_rt(int rt, int device, dim3 grid, dim3 block, int lds, hipStream_t stream,
                        const ContractArgs& args, hipEvent_t start = nullptr,
                        hipEvent_t stop = nullptr);
-int set_lds_limit_rt(int rt, int lds);
-int launch_contract_f32(dim3 grid, dim3 block, int lds, hipStream_t stream,
+int launch_contract_f32(int device, dim3 grid, dim3 block, int lds, hipStream_t stream,
                         const ContractArgs& args, hipEvent_t start = nullptr,
                         hipEvent_t stop = nullptr);
 // Occupation kernel for a slab of draws: densities into (nbuf, ngal2) -- the current
@@ -702,14 +707,11 @@ int build_quad_table(tc_table* t, bool by_type, const void* matrix, int matrix_d
                      QuadTable* out);
 int get_quad_schedule(tc_table* t, QuadTable* q, int64_t n_tiles, int n_tables, bool separate,
                       DeviceQuadSchedule** out);
-int launch_contract_quad(int n_u, bool interp, const QuadArgs& args, int lds_bytes,
+// (dtype: TC_DTYPE_F64, or TC_DTYPE_F32 -- up to four r sub-tiles; interp: several tables)
+int launch_contract_quad(int n_u, int dtype, bool interp, const QuadArgs& args, int lds_bytes,
                          hipStream_t stream, hipEvent_t start, hipEvent_t stop);
 int launch_finalize_quad(const FinalizeQuadArgs& args, const Tuning& tuning, hipStream_t stream,
                          bool f32 = false);
-int launch_contract_quad_f32_interp(int n_u, const tc::QuadArgs& args, int lds_bytes,
-                                    hipStream_t stream, hipEvent_t start, hipEvent_t stop);
-int launch_contract_quad_f32(int n_u, const QuadArgs& args, int lds_bytes, hipStream_t stream,
-                             hipEvent_t start, hipEvent_t stop);
 // Stream an interpolator's work is queued on (interp.cpp).
 hipStream_t interp_stream(tc_interp* interp);
 int interp_join_lanes(tc_interp* interp, hipStream_t stream);

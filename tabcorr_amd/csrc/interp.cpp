@@ -214,10 +214,8 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
     hipEvent_t k0 = nullptr, k1 = nullptr;     // timed through the first table's timer
     status = next_kernel_events(t0, &k0, &k1);
     if (status != TC_OK) return status;
-    status = quad_f32 ? launch_contract_quad_f32_interp(tiling.n_u, qa, schedule->lds_bytes,
-                                                        L.stream, k0, k1)
-                      : launch_contract_quad(tiling.n_u, true, qa, schedule->lds_bytes,
-                                             L.stream, k0, k1);
+    status = launch_contract_quad(tiling.n_u, quad_f32 ? TC_DTYPE_F32 : TC_DTYPE_F64, true, qa,
+                                  schedule->lds_bytes, L.stream, k0, k1);
     if (status != TC_OK) return status;
     t0->last_workgroups = (schedule->n_waves + tc::kQuadWavesPerBlock - 1) / tc::kQuadWavesPerBlock;
     t0->last_waves = tc::kQuadWavesPerBlock;
@@ -317,13 +315,9 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
   if (status != TC_OK) return status;
   if (t0->compute_dtype == TC_DTYPE_F32) {
     ca.pos_ij = (const int32_t*)t0->d_pos_ij;
-    status = launch_contract_f32(grid, block, lds, L.stream, ca, k0, k1);
+    status = launch_contract_f32(t0->device, grid, block, lds, L.stream, ca, k0, k1);
   } else {
-    if (lds > 64 * 1024) {
-      status = set_lds_limit_rt(t0->rt, lds);
-      if (status != TC_OK) return status;
-    }
-    status = launch_contract_rt(t0->rt, grid, block, lds, L.stream, ca, k0, k1);
+    status = launch_contract_rt(t0->rt, t0->device, grid, block, lds, L.stream, ca, k0, k1);
   }
   if (status != TC_OK) return status;
   t0->last_workgroups = (int)(grid.x * grid.z);

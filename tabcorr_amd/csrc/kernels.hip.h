@@ -77,9 +77,20 @@ __device__ inline double heaviside_assembias(double n, double strength,
 // NaN strength stays NaN and propagates through the decoration by itself).
 constexpr int kBadCen = 1, kBadSat = 2, kTieCen = 4, kInfSat = 8;
 
-struct DrawSetup {
+// A draw as the occupation bodies read it (occ_bin_zheng07 and its kin); prepare_draw fills
+// the constants and `bad`.
+struct DrawParams {
   double log_m_min, inv_sigma, m0, log2_m1, sat_scale, alpha, a_cen, a_sat;
   int bad;
+  // wave-uniform: does any draw of the tile need the NaN fix-ups?  (draw_params; false for a
+  // single draw, whose kernels look at `bad`)
+  bool any_bad = false;
+  // The moment expansions (series.h).  A LANE adds as many terms as its own draw needs --
+  // inv_sigma_hi: high dword of the draw's |1 / sigma| (central bins); m0_hi: of its M0, or
+  // INT_MAX where the expansion does not apply to the draw (centrals to fix up; satellites: alpha
+  // outside [0, 4], any fix-up) -- so that a draw's result does not depend on its neighbours in
+  // the wave.  INT_MAX: off.
+  int inv_sigma_hi = 0x7fffffff, m0_hi = 0x7fffffff;
 };
 
 __device__ inline double clip_strength(double a) {
@@ -87,11 +98,11 @@ __device__ inline double clip_strength(double a) {
   return a < -1.0 ? -1.0 : a;
 }
 
-__device__ inline DrawSetup prepare_draw(const double* table, const fm::Consts& kc,
-                                         double log_m_min, double sigma, double log_m0,
-                                         double log_m1, double alpha, double a_cen,
-                                         double a_sat) {
-  DrawSetup d;
+__device__ inline DrawParams prepare_draw(const double* table, const fm::Consts& kc,
+                                          double log_m_min, double sigma, double log_m0,
+                                          double log_m1, double alpha, double a_cen,
+                                          double a_sat) {
+  DrawParams d;
   d.bad = 0;
   if (log_m_min != log_m_min || sigma != sigma ||
       (__builtin_isinf(log_m_min) && __builtin_isinf(sigma))) {
@@ -130,19 +141,16 @@ __device__ inline DrawSetup prepare_draw(const double* table, const fm::Consts& 
   return d;
 }
 
-// Mean occupation of bin g for the lane's draw (Zheng et al. 2007 eqs. 1 and 3 averaged over
-// the bin's quadrature nodes): the body shared by occ_zheng07_kernel and predict_fused_kernel.
-struct DrawParams {
-  double log_m_min, inv_sigma, m0, log2_m1, sat_scale, alpha, a_cen, a_sat;
-  int bad;
-  bool any_bad;    // wave-uniform: does any draw of the tile need the NaN fix-ups?
-  // The moment expansions (series.h).  A LANE adds as many terms as its own draw needs --
-  // inv_sigma_hi: high dword of the draw's |1 / sigma| (central bins); m0_hi: of its M0, or
-  // INT_MAX where the expansion does not apply to the draw (centrals to fix up; satellites: alpha
-  // outside [0, 4], any fix-up) -- so that a draw's result does not depend on its neighbours in
-  // the wave.  INT_MAX: off.
-  int inv_sigma_hi = 0x7fffffff, m0_hi = 0x7fffffff;
-};
+// The parameters of the lane's draw, one draw per lane of a wave, from its row `th` of theta
+// (the expansions' keys are series_setup's).
+template <bool ASSEMBIAS>
+__device__ __forceinline__ DrawParams draw_params(const double* table, const fm::Consts& kc,
+                                         const double* th) {
+  DrawParams dp = prepare_draw(table, kc, th[0], th[1], th[2], th[3], th[4],
+                               ASSEMBIAS ? th[5] : 0.0, ASSEMBIAS ? th[6] : 0.0);
+  dp.any_bad = __builtin_amdgcn_ballot_w64(dp.bad != 0) != 0;
+  return dp;
+}
 
 // Constants of the moment expansion (launch.hip: get_quadrature): per bin (or member, in group
 // order) series::kStride doubles and series::kThresholds int32.  consts == nullptr: off.
@@ -553,6 +561,14 @@ struct GroupConsts {
   sc_i32 member;               // (n_bins)
   SeriesConsts series;         // moment expansion, per member in group order (or off)
 };
+// ... from a kernel's GroupArgs (by value: a reference to the argument block keeps the compiler
+// from reading it as scalar kernel arguments)
+__device__ __forceinline__ GroupConsts group_consts(const GroupArgs g, int n_bins) {
+  return GroupConsts{(sc_f64)g.log_m, (sc_f64)g.m, (sc_f64)g.weight,
+                     (sc_f64)g.weight + n_bins * 10, (sc_f64)g.percentile, (sc_i32)g.member,
+                     SeriesConsts{(sc_f64)g.series, (sc_i32)g.series_thr, (sc_f64)g.sat_series,
+                                  (sc_i32)g.sat_series_thr}};
+}
 
 // Defer (predict_cross_fused_kernel, round 5): what happens to the lanes of a group that neither a
 // shortcut nor an expansion serves.  NoDefer: they run the node path here, under their part of
@@ -1034,8 +1050,8 @@ __global__ __launch_bounds__(kOccWaves * kLanes) void occ_zheng07_kernel(
     // per-draw quantities: computed by wave 0, shared with the other waves through LDS
     if (wave == 0) {
       const double* th = a.theta + b * a.n_theta;
-      const DrawSetup d = prepare_draw(table, kc, th[0], th[1], th[2], th[3], th[4],
-                                       assembias ? th[5] : 0.0, assembias ? th[6] : 0.0);
+      const DrawParams d = prepare_draw(table, kc, th[0], th[1], th[2], th[3], th[4],
+                                        assembias ? th[5] : 0.0, assembias ? th[6] : 0.0);
       prm[0][lane] = d.log_m_min;
       prm[1][lane] = d.inv_sigma;
       prm[2][lane] = d.m0;
@@ -1076,11 +1092,7 @@ __global__ __launch_bounds__(kOccWaves * kLanes) void occ_zheng07_kernel(
       if (GROUPED) {
         sc_i32 group_begin = (sc_i32)a.group.begin;
         sc_f64 n_h_m = (sc_f64)a.group.n_h;
-        const GroupConsts gq{(sc_f64)a.group.log_m, (sc_f64)a.group.m, (sc_f64)a.group.weight,
-                             (sc_f64)a.group.weight + a.n_bins * 10,
-                             (sc_f64)a.group.percentile, (sc_i32)a.group.member,
-                             SeriesConsts{(sc_f64)a.group.series, (sc_i32)a.group.series_thr,
-                                          (sc_f64)a.group.sat_series, (sc_i32)a.group.sat_series_thr}};
+        const GroupConsts gq = group_consts(a.group, a.n_bins);
         const bool central = g < a.n_central_groups;
         occ_group_zheng07<ASSEMBIAS, MODULATE>(
             table, kc, g, group_begin[g], group_begin[g + 1], central, gq, a.split, dp,
@@ -2559,21 +2571,8 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     // harmless finite numbers the compiler drops with the unused branch)
     LeauthaudDraw ld;
     if (LEAUTHAUD) ld = prepare_leauthaud(table, kc, th);
-    const DrawSetup d =
-        LEAUTHAUD ? prepare_draw(table, kc, 12.0, 1.0, 12.0, 13.0, 1.0, 0.0, 0.0)
-                  : prepare_draw(table, kc, th[0], th[1], th[2], th[3], th[4],
-                                 ASSEMBIAS ? th[5] : 0.0, ASSEMBIAS ? th[6] : 0.0);
-    DrawParams dp;
-    dp.log_m_min = d.log_m_min;
-    dp.inv_sigma = d.inv_sigma;
-    dp.m0 = d.m0;
-    dp.log2_m1 = d.log2_m1;
-    dp.sat_scale = d.sat_scale;
-    dp.alpha = d.alpha;
-    dp.a_cen = d.a_cen;
-    dp.a_sat = d.a_sat;
-    dp.bad = d.bad;
-    dp.any_bad = __builtin_amdgcn_ballot_w64(dp.bad != 0) != 0;
+    DrawParams dp = LEAUTHAUD ? prepare_draw(table, kc, 12.0, 1.0, 12.0, 13.0, 1.0, 0.0, 0.0)
+                              : draw_params<ASSEMBIAS>(table, kc, th);
     series_setup<MODULATE>(dp, (GROUPED ? a.group.series : a.series) != nullptr && DL != 32,
                            (GROUPED ? a.group.sat_series : a.sat_series) != nullptr && DL != 32);
     sc_f64 log_m = (sc_f64)a.log_m;
@@ -2588,11 +2587,14 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     if (GROUPED) {
       sc_i32 group_begin = (sc_i32)a.group.begin;
       sc_f64 n_h_m = (sc_f64)a.group.n_h;
+      // (group_consts spelled out: next to the halves' plain pointers below the helper's copy of
+      // a.group changes this kernel's register allocation)
       const GroupConsts gq{(sc_f64)a.group.log_m, (sc_f64)a.group.m, (sc_f64)a.group.weight,
                            (sc_f64)a.group.weight + a.n_bins * 10, (sc_f64)a.group.percentile,
                            (sc_i32)a.group.member,
-                             SeriesConsts{(sc_f64)a.group.series, (sc_i32)a.group.series_thr,
-                                          (sc_f64)a.group.sat_series, (sc_i32)a.group.sat_series_thr}};
+                           SeriesConsts{(sc_f64)a.group.series, (sc_i32)a.group.series_thr,
+                                        (sc_f64)a.group.sat_series,
+                                        (sc_i32)a.group.sat_series_thr}};
       for (int gr = wave; gr < a.n_groups; gr += W) {
         const bool central = gr < a.n_central_groups;
         auto emit = [&](int mi, int g, double acc) {
@@ -3267,28 +3269,13 @@ __global__ __launch_bounds__(64 * kCrossWaves, RW <= 8 ? 4 : 2) void predict_cro
   };
   {
     const double* th = a.theta + b * a.n_theta;
-    const DrawSetup d = prepare_draw(table, kc, th[0], th[1], th[2], th[3], th[4],
-                                     ASSEMBIAS ? th[5] : 0.0, ASSEMBIAS ? th[6] : 0.0);
-    dp.log_m_min = d.log_m_min;
-    dp.inv_sigma = d.inv_sigma;
-    dp.m0 = d.m0;
-    dp.log2_m1 = d.log2_m1;
-    dp.sat_scale = d.sat_scale;
-    dp.alpha = d.alpha;
-    dp.a_cen = d.a_cen;
-    dp.a_sat = d.a_sat;
-    dp.bad = d.bad;
-    dp.any_bad = __builtin_amdgcn_ballot_w64(dp.bad != 0) != 0;
+    dp = draw_params<ASSEMBIAS>(table, kc, th);
     series_setup<MODULATE>(dp, a.group.series != nullptr, a.group.sat_series != nullptr);
     sc_i32 group_begin = (sc_i32)a.group.begin;
     sc_i32 chunk_group = (sc_i32)a.chunk_group;
     sc_i32 chunk_block = (sc_i32)a.chunk_block;
     const MarkPairs<kDeferrable> mark{bitmap};
-    const GroupConsts gq{(sc_f64)a.group.log_m, (sc_f64)a.group.m, (sc_f64)a.group.weight,
-                         (sc_f64)a.group.weight + a.n_bins * 10, (sc_f64)a.group.percentile,
-                         (sc_i32)a.group.member,
-                             SeriesConsts{(sc_f64)a.group.series, (sc_i32)a.group.series_thr,
-                                          (sc_f64)a.group.sat_series, (sc_i32)a.group.sat_series_thr}};
+    const GroupConsts gq = group_consts(a.group, a.n_bins);
     if (a.separate && chunk_begin >= a.n_central_chunks) {
       // (a share without centrals: their sums are zero)
       double* res0 = cross_lds + a.lds_res0;
@@ -3624,18 +3611,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, DEFER ? 4 : 2) void predict_cross
   DrawParams dp;
   {
     const double* th = a.theta + b * a.n_theta;
-    const DrawSetup d = prepare_draw(table, kc, th[0], th[1], th[2], th[3], th[4],
-                                     ASSEMBIAS ? th[5] : 0.0, ASSEMBIAS ? th[6] : 0.0);
-    dp.log_m_min = d.log_m_min;
-    dp.inv_sigma = d.inv_sigma;
-    dp.m0 = d.m0;
-    dp.log2_m1 = d.log2_m1;
-    dp.sat_scale = d.sat_scale;
-    dp.alpha = d.alpha;
-    dp.a_cen = d.a_cen;
-    dp.a_sat = d.a_sat;
-    dp.bad = d.bad;
-    dp.any_bad = __builtin_amdgcn_ballot_w64(dp.bad != 0) != 0;
+    dp = draw_params<ASSEMBIAS>(table, kc, th);
     // (the decorated instances are compiled without the moment expansions: dp's keys stay at
     // INT_MAX there)
     if (kDeferrable)
@@ -3643,11 +3619,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, DEFER ? 4 : 2) void predict_cross
                              deferring && a.group.sat_series != nullptr);
     const MarkPairs<kDeferrable> mark{bitmap};
     sc_i32 group_begin = (sc_i32)a.group.begin;
-    const GroupConsts gq{(sc_f64)a.group.log_m, (sc_f64)a.group.m, (sc_f64)a.group.weight,
-                         (sc_f64)a.group.weight + a.n_bins * 10, (sc_f64)a.group.percentile,
-                         (sc_i32)a.group.member,
-                             SeriesConsts{(sc_f64)a.group.series, (sc_i32)a.group.series_thr,
-                                          (sc_f64)a.group.sat_series, (sc_i32)a.group.sat_series_thr}};
+    const GroupConsts gq = group_consts(a.group, a.n_bins);
     sc_f64 rows = (sc_f64)a.rows;
     auto emit = [&](int mi, int, double nbar) {
       sc_f64 coefficient = rows + (int64_t)mi * a.row_stride;
@@ -4027,10 +3999,10 @@ __device__ __forceinline__ void single_draw_body(SingleArgs a) {
   }
   // (made per call: the resident form would otherwise hold their registers while it waits)
   const fm::Consts kc = fm::make_consts();
-  const DrawSetup d = prepare_draw(table, kc, a.theta_value[0], a.theta_value[1],
-                                   a.theta_value[2], a.theta_value[3], a.theta_value[4],
-                                   assembias ? a.theta_value[5] : 0.0,
-                                   assembias ? a.theta_value[6] : 0.0);
+  const DrawParams d = prepare_draw(table, kc, a.theta_value[0], a.theta_value[1],
+                                    a.theta_value[2], a.theta_value[3], a.theta_value[4],
+                                    assembias ? a.theta_value[5] : 0.0,
+                                    assembias ? a.theta_value[6] : 0.0);
   const double log_m_min = d.log_m_min, inv_sigma = d.inv_sigma, m0 = d.m0;
   const double log2_m1 = d.log2_m1, sat_scale = d.sat_scale, alpha = d.alpha;
   const double a_cen = d.a_cen, a_sat = d.a_sat;
@@ -4391,9 +4363,9 @@ static __global__ __launch_bounds__(kEnsembleThreads) void resident_ensemble_ker
       if (tid_call == 0) __hip_atomic_store(a.flag_a + b, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else if (is_walker) {
       const fm::Consts kc = fm::make_consts();
-      const DrawSetup d = prepare_draw(table, kc, s_theta[0], s_theta[1], s_theta[2], s_theta[3],
-                                       s_theta[4], assembias ? s_theta[5] : 0.0,
-                                       assembias ? s_theta[6] : 0.0);
+      const DrawParams d = prepare_draw(table, kc, s_theta[0], s_theta[1], s_theta[2], s_theta[3],
+                                        s_theta[4], assembias ? s_theta[5] : 0.0,
+                                        assembias ? s_theta[6] : 0.0);
       const double f1 = (1.0 - a.split) / a.split, f2 = a.split / (1.0 - a.split);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {

@@ -613,8 +613,8 @@ static int run_contraction_quad(tc_table* t, int64_t n_draws, int64_t ldb, unsig
   hipEvent_t k0 = nullptr, k1 = nullptr;
   status = next_kernel_events(t, &k0, &k1);
   if (status != TC_OK) return status;
-  status = f32 ? launch_contract_quad_f32(tiling.n_u, qa, schedule->lds_bytes, stream, k0, k1)
-               : launch_contract_quad(tiling.n_u, false, qa, schedule->lds_bytes, stream, k0, k1);
+  status = launch_contract_quad(tiling.n_u, f32 ? TC_DTYPE_F32 : TC_DTYPE_F64, false, qa,
+                                schedule->lds_bytes, stream, k0, k1);
   if (status != TC_OK) return status;
   t->last_workgroups = (schedule->n_waves + tc::kQuadWavesPerBlock - 1) / tc::kQuadWavesPerBlock;
   t->last_waves = tc::kQuadWavesPerBlock;
@@ -730,19 +730,15 @@ int run_contraction(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
   const int padded_tiles = ca.xcd_map ? (n_tiles + 7) / 8 * 8 : n_tiles;
   dim3 grid((unsigned)(padded_tiles * n_groups), 1, (unsigned)t->n_rtiles);
   dim3 block(64 * c->host.waves_per_group);
-  if (lds > 64 * 1024) {
-    status = set_lds_limit_rt(t->rt, lds);
-    if (status != TC_OK) return status;
-  }
   hipEvent_t k0 = nullptr, k1 = nullptr;
   status = next_kernel_events(t, &k0, &k1);
   if (status != TC_OK) return status;
   if (t->compute_dtype == TC_DTYPE_F32) {
     ca.pos_ij = (const int32_t*)t->d_pos_ij;
-    status = launch_contract_f32(grid, block, lds, stream, ca, k0, k1);
+    status = launch_contract_f32(t->device, grid, block, lds, stream, ca, k0, k1);
     if (status != TC_OK) return status;
   } else {
-    status = launch_contract_rt(t->rt, grid, block, lds, stream, ca, k0, k1);
+    status = launch_contract_rt(t->rt, t->device, grid, block, lds, stream, ca, k0, k1);
     if (status != TC_OK) return status;
   }
   t->last_workgroups = n_tiles * n_groups * t->n_rtiles;

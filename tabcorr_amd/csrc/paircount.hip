@@ -821,9 +821,13 @@ int mass_in_cylinders(const double* objects, int64_t n_obj, const double* partic
   device.pointers.push_back(d_annuli);
   a.annuli = (double*)d_annuli;
   const size_t lds = (size_t)n_edges * kPairThreads * sizeof(double);
-  if (lds > 48 * 1024)
-    TC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&mass_in_cylinders_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  if (lds > 48 * 1024) {
+    int device = 0;
+    TC_HIP(hipGetDevice(&device));
+    status = ensure_lds_limit(reinterpret_cast<const void*>(&mass_in_cylinders_kernel), device,
+                              (int)lds);
+    if (status != TC_OK) return status;
+  }
   hipLaunchKernelGGL(mass_in_cylinders_kernel, dim3((unsigned)item_cell.size()),
                      dim3(kPairThreads), lds, nullptr, a);
   TC_HIP(hipGetLastError());

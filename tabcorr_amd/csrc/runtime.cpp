@@ -296,6 +296,17 @@ bool is_pinned(const void* ptr, size_t bytes, void** device_ptr) {
   return true;
 }
 
+int ensure_lds_limit(const void* kernel, int device, int bytes) {
+  static std::mutex mutex;
+  static std::map<std::pair<const void*, int>, int> limits;   // largest limit set so far
+  std::lock_guard<std::mutex> lock(mutex);
+  int& limit = limits[{kernel, device}];
+  if (bytes <= limit) return TC_OK;
+  TC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  limit = bytes;
+  return TC_OK;
+}
+
 }  // namespace host
 }  // namespace tc
 

@@ -40,6 +40,54 @@ def test_pinned_arrays():
     assert is_pinned(view)
 
 
+def test_concurrent_first_calls_raise_the_lds_limit():
+    """Two fresh handles make their first one-launch call from two threads at the same time --
+    how a multi-threaded sampler starts -- with a form that needs more than 64 KiB of dynamic
+    LDS, so that both raise the kernel's limit (internal.h: ensure_lds_limit); both results are
+    bit-equal to a third handle's, called from this thread.  74 bins, 4 r values: the smallest
+    table whose density rows alone (76 rows x 64 draws next to the 26 640 bytes of math table and
+    reduction scratch: 65 552 bytes) pass 65 536; the launch record says what the launch took."""
+    from tabcorr_amd import synthetic, _lib
+    lib = _lib.load()
+    table = synthetic.synthetic_table(37, 1, (4, ), 'auto', seed=41)
+    theta = synthetic.zheng07_draws(128, seed=42)
+
+    def handle():
+        halotab = make_tabcorr(table)
+        for name, value in ((b'fused', 2), (b'fused_min_draws', 1), (b'fused_draws', 64)):
+            _lib.check(lib.tc_table_set_option(halotab.to_device().handle, name, value))
+        return halotab
+
+    def lds_bytes(halotab):
+        values = [ctypes.c_int() for _ in range(4)]
+        _lib.check(lib.tc_table_last_launch(halotab.to_device().handle,
+                                            *[ctypes.byref(v) for v in values]))
+        assert values[2].value == 0, 'not the one-launch form'
+        return values[3].value
+
+    pair = [handle(), handle()]
+    results = [None, None]
+    barrier = threading.Barrier(2)
+
+    def first_call(i):
+        barrier.wait()
+        results[i] = pair[i].predict_batch(theta)
+
+    threads = [threading.Thread(target=first_call, args=(i, )) for i in range(2)]
+    for thread in threads:
+        thread.start()
+    for thread in threads:
+        thread.join()
+    third = handle()
+    ngal, xi = third.predict_batch(theta)
+    for halotab in pair + [third]:
+        assert lds_bytes(halotab) > 65536
+    for result in results:
+        assert result is not None, 'a thread raised'
+        assert np.array_equal(result[0], ngal) and np.array_equal(result[1], xi)
+    assert np.all(np.isfinite(xi))
+
+
 def test_async_matches_golden_and_sync():
     from tabcorr_amd import pinned_array, pinned_empty
     data = load_golden('synthetic_cfg2')
