@@ -185,6 +185,43 @@ int tc_chi2_zheng07_batch_device(tc_table* table, const double* theta_device, in
                                  const double* data, const double* precision,
                                  double* ngal_device, double* chi2_device);
 
+/* Analytic gradients (extension beyond the reference): the prediction of a batch of Zheng07
+ * draws together with its EXACT derivatives with respect to the five parameters (logMmin,
+ * sigma_logM, logM0, logM1, alpha) -- the derivative of the function the library computes (the
+ * Gauss-Legendre bin average of tabcorr.py:537-578 followed by tabcorr.py:623-650), not of the
+ * underlying integral.  n_theta must be 5; flags: 0 or TC_FLAG_MODULATE_WITH_CENOCC.  Outputs:
+ * ngal (n_draws), xi (n_draws, n_r), dngal (n_draws, 5), dxi (n_draws, 5, n_r).  One launch per
+ * batch; ngal and xi agree with tc_predict_zheng07_batch to parity (1e-10 relative), not
+ * necessarily to the bit.  A draw's results depend on the draw alone (batch-invariant by
+ * construction, whatever the option "deterministic" says).  Where the value's formula divides
+ * by zero (ngal = 0, sigma_logM = 0) the derivatives are what IEEE arithmetic gives (NaN or
+ * inf).  TC_ERR_UNSUPPORTED with a message: a float32 compute dtype, TC_FLAG_SEPARATE_GAL_TYPE,
+ * TC_FLAG_ASSEMBIAS, TC_FLAG_LEAUTHAUD11, tables whose rows do not fit the kernel's LDS (mode
+ * auto: about 3 n_centrals + 6 n_satellites <= 1270 rows, i.e. at least 280 bins split evenly;
+ * mode cross: any number of bins, n_r up to about 140). */
+int tc_predict_grad_zheng07_batch(tc_table* table, const double* theta, int n_theta,
+                                  int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                  double* ngal, double* xi, double* dngal, double* dxi);
+/* The same on device pointers: enqueues on one of the handle's lanes and returns. */
+int tc_predict_grad_zheng07_batch_device(tc_table* table, const double* theta_device,
+                                         int n_theta, int64_t n_draws, int n_gauss_prim,
+                                         unsigned flags, double* ngal_device,
+                                         double* xi_device, double* dngal_device,
+                                         double* dxi_device);
+/* chi2 = (xi - data)^T precision (xi - data) and dchi2 / dtheta_k = 2 (xi - data)^T P_sym
+ * dxi / dtheta_k with P_sym = (precision + precision^T) / 2, finished in the same launch: ngal
+ * (n_draws), chi2 (n_draws), dngal (n_draws, 5), dchi2 (n_draws, 5).  data / precision are host
+ * arrays in both forms (uploaded when they change). */
+int tc_chi2_grad_zheng07_batch(tc_table* table, const double* theta, int n_theta,
+                               int64_t n_draws, int n_gauss_prim, unsigned flags,
+                               const double* data, const double* precision, double* ngal,
+                               double* chi2, double* dngal, double* dchi2);
+int tc_chi2_grad_zheng07_batch_device(tc_table* table, const double* theta_device, int n_theta,
+                                      int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                      const double* data, const double* precision,
+                                      double* ngal_device, double* chi2_device,
+                                      double* dngal_device, double* dchi2_device);
+
 /* A handful of independent draws in ONE launch (the proposals of an ensemble sampler's step,
  * or the reference's un-batched predict(), README.md:72-75, for n_walkers = 1): every
  * workgroup evaluates the occupations of its draw itself, contracts its share of the table
@@ -466,6 +503,9 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *                 un-batched kernels give the same bits), so the same sequence of calls
  *                 returns the same bits in every run; the same DRAW in batches of different
  *                 sizes, or through different entry points, may differ in the last bits.
+ *                 The gradient entry points (tc_predict_grad_* / tc_chi2_grad_*) have ONE form
+ *                 each and are batch-invariant by construction at every value of this option:
+ *                 a draw's results depend on the draw alone, host arrays or device pointers.
  *                 1: the same, and "autotune" / "autotune_after" are refused (nothing
  *                 measured can enter the choice).
  *                 2: batch-invariant -- ONE form per (table, flags): the one-launch kernel

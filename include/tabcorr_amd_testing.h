@@ -17,8 +17,15 @@ extern "C" {
 
 /* Host evaluation of the table-driven FP64 functions the occupation kernel uses in place
  * of the device libm (tabcorr_amd/csrc/fastmath.h): kind 0 erf, 1 log2 (x > 0 normal),
- * 2 exp2, 3 exp10, 4 erf and 5 its derivative 2/sqrt(pi) exp(-x^2) from erf_gauss_fast. */
+ * 2 exp2, 3 exp10, 4 erf and 5 its derivative 2/sqrt(pi) exp(-x^2) from erf_gauss_fast,
+ * 6 the natural logarithm (x > 0 normal) of the gradient kernels. */
 int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y);
+
+/* The dense matrix-operand layout the gradient kernel of mode auto reads
+ * (tabcorr_amd/csrc/grad.h), built from packed (n_r, n_bins (n_bins + 1) / 2) lower triangles
+ * (p = i (i + 1) / 2 + j, j <= i) and read back lane by lane as the kernel addresses it:
+ * dense (n_r, n_bins, n_bins) = the symmetric matrices.  Fails if a padding entry is not zero. */
+int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* dense);
 
 /* The moment expansion of a central bin's node sum (tabcorr_amd/csrc/series.h) on the host,
  * next to the node loop it replaces: for one bin [log_min, log_max] with

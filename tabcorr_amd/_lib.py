@@ -58,6 +58,7 @@ SIGNATURES = {
     'tc_gauss_legendre': [ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_fastmath': [ctypes.c_int, ctypes.c_int64, c_double_p,
                           c_double_p],
+    'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_pair_indices': [ctypes.c_int, c_int32_p, c_int32_p, c_int32_p],
     'tc_spline_interpolation_matrix': [ctypes.c_int, c_double_p, c_double_p],
     'tc_plan_debug': [ctypes.c_int, ctypes.c_int, c_uint8_p, ctypes.c_int,
@@ -107,6 +108,22 @@ SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
         ctypes.c_void_p],
+    'tc_predict_grad_zheng07_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p],
+    'tc_predict_grad_zheng07_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p],
+    'tc_chi2_grad_zheng07_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p, c_double_p, c_double_p],
+    'tc_chi2_grad_zheng07_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'tc_predict_zheng07_many': [
         ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p],

@@ -184,6 +184,14 @@ TC_HD double log2_fast(const double* table, const Consts& k, double y) {
   return log2_fast_offset(table, k, y, 0.0);
 }
 
+// ln(y) from log2(y), and for a positive normal y (absolute error a few 1e-16 max(1, |log2 y|)):
+// the derivative of s^alpha with respect to alpha (grad_kernels.hip.h), whose kernel has log2(s)
+// at hand from the power itself.
+TC_HD double ln_from_log2(double log2_value) { return log2_value * kLn2; }
+TC_HD double log_fast(const double* table, const Consts& k, double y) {
+  return ln_from_log2(log2_fast(table, k, y));
+}
+
 // 2^z; with keep == false the result is exactly 0 (the scaling step does the masking).
 TC_HD double exp2_fast(const double* table, const Consts& k, double z, bool keep = true) {
   z = z < 1000.0 ? z : 1000.0;

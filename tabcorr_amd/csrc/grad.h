@@ -1,0 +1,96 @@
+// Analytic gradients of (ngal, xi, chi2) with respect to the five Zheng07 parameters: the
+// argument block of the gradient kernels (grad_kernels.hip.h), their LDS budget and the dense
+// matrix-operand layout of a mode-auto table.  Plain C++: the host-only units fill these in.
+//
+// With w = n_h <N> and S_r the symmetric matrix of one r bin, q_r = w^T S_r w and
+// dq_r / dtheta_k = 2 (dw / dtheta_k)^T (S_r w): ONE dense product U_r = S_r W per tile of draws
+// gives the value and all five derivatives by dot products.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace tc {
+
+constexpr int kGradParams = 5;        // logMmin, sigma_logM, logM0, logM1, alpha
+constexpr int kGradDraws = 16;        // draws per workgroup: the N of one v_mfma_f64_16x16x4_f64
+constexpr int kGradWaves = 4;
+constexpr int kGradThreads = 64 * kGradWaves;
+constexpr int kGradCrossSlab = 64;    // mode cross: bins whose w and dw one LDS slab holds
+
+struct GradArgs {
+  const double* theta;       // (n_draws, 5)
+  int64_t n_draws;
+  int n_bins;
+  int n_central;
+  int n_gauss;
+  int n_r;
+  int modulate;              // modulate_with_cenocc
+  const double* log_m;       // quadrature constants as in OccArgs (library bin order)
+  const double* m;
+  const double* weight;
+  const double* n_h;
+  const double* math_table;  // fastmath.h tables, read from global memory
+  // mode auto: the dense operand layout below; mode cross: (n_bins in library order, n_r)
+  const double* matrix;
+  int row_tiles;             // blocks of 16 matrix rows
+  int k_steps;               // steps of 4 matrix columns
+  double* ngal;              // (n_draws)
+  double* dngal;             // (n_draws, 5)
+  double* xi;                // (n_draws, n_r); NULL: the likelihood is finished in the launch
+  double* dxi;               // (n_draws, 5, n_r)
+  const double* chi2_data;   // data (n_r), then the precision matrix (n_r, n_r)
+  double* chi2;              // (n_draws)
+  double* dchi2;             // (n_draws, 5)
+};
+
+// ---- LDS of grad_auto_kernel ------------------------------------------------------------------
+// Rows of kGradDraws doubles.  A central bin keeps (w, dw/dlogMmin, dw/dsigma), a satellite bin
+// w and all five derivatives (three of them zero unless modulate_with_cenocc); one shared row of
+// zeros stands for everything else: the derivatives a central bin does not have and the padding
+// of the matrix up to whole tiles.
+constexpr int grad_auto_rows(int n_bins, int n_central) {
+  return 3 * n_central + 6 * (n_bins - n_central) + 1;
+}
+// ... then the totals (6, kGradDraws) and, for the likelihood, (6, n_r, kGradDraws) residuals
+// and derivatives
+constexpr size_t grad_auto_lds_bytes(int n_bins, int n_central, int n_r, bool chi2) {
+  return ((size_t)grad_auto_rows(n_bins, n_central) + 6 + (chi2 ? 6 * (size_t)n_r : 0)) *
+         kGradDraws * sizeof(double);
+}
+// grad_cross_kernel: one slab (6, kGradCrossSlab, kGradDraws), the products (6, n_r, kGradDraws)
+// and the totals
+constexpr size_t grad_cross_lds_bytes(int n_r) {
+  return (6 * (size_t)kGradCrossSlab + 6 * (size_t)n_r + 6) * kGradDraws * sizeof(double);
+}
+
+// ---- dense operand layout of a mode-auto table ------------------------------------------------
+// Per r bin, block of 16 rows and step of 4 columns 64 doubles: [l] = S_r[16 block + l % 16]
+// [4 step + l / 16], the A operand of v_mfma_f64_16x16x4_f64 in lane order (one coalesced
+// 512-byte load per instruction); zeros beyond the last bin.
+inline int grad_row_tiles(int n_bins) { return (n_bins + 15) / 16; }
+inline int grad_k_steps(int n_bins) { return (n_bins + 3) / 4; }
+inline size_t grad_operand_doubles(int n_bins, int n_r) {
+  return (size_t)n_r * grad_row_tiles(n_bins) * grad_k_steps(n_bins) * 64;
+}
+inline size_t grad_operand_index(int n_bins, int r, int i, int j) {
+  return (((size_t)r * grad_row_tiles(n_bins) + i / 16) * grad_k_steps(n_bins) + j / 4) * 64 +
+         (size_t)(j % 4) * 16 + i % 16;
+}
+// `packed`: (n_r, n_bins (n_bins + 1) / 2) lower triangles, p = i (i + 1) / 2 + j with j <= i
+// (tabcorr.py:770-806), WITHOUT the pair prefactor.
+inline void build_grad_operand(int n_bins, int n_r, const double* packed,
+                               std::vector<double>& out) {
+  const size_t n_pairs = (size_t)n_bins * (n_bins + 1) / 2;
+  out.assign(grad_operand_doubles(n_bins, n_r), 0.0);
+  for (int r = 0; r < n_r; ++r)
+    for (int i = 0; i < n_bins; ++i)
+      for (int j = 0; j <= i; ++j) {
+        const double value = packed[(size_t)r * n_pairs + (size_t)i * (i + 1) / 2 + j];
+        out[grad_operand_index(n_bins, r, i, j)] = value;
+        out[grad_operand_index(n_bins, r, j, i)] = value;
+      }
+}
+
+}  // namespace tc

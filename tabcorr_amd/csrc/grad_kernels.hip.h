@@ -1,0 +1,380 @@
+// Gradient kernels: (ngal, xi[, chi2]) of a batch of Zheng07 draws together with their exact
+// derivatives with respect to the five parameters, one launch per batch (grad.h: the argument
+// block, the LDS budget and the operand layout; launch.hip: run_grad).
+//
+// A workgroup of four waves carries kGradDraws = 16 draws from theta to the results:
+//   1  the node loops of every bin (tabcorr.py:537-578) for <N> and d<N>/dtheta_k, which share
+//      their erf / exp / pow; w = n_h <N> and dw stay in LDS;
+//   2  mode auto: per r bin U_r = S_r W on the FP64 matrix pipe (v_mfma_f64_16x16x4_f64: 16 rows
+//      of S_r x 4 columns x 16 draws per instruction, the A operand one coalesced load from the
+//      dense layout), then q_r = w . U_r and dq_r / dtheta_k = 2 dw_k . U_r; wave v takes the r
+//      bins v, v + 4, ...;  mode cross: six matrix-vector products per r bin, slab by slab;
+//   3  the chain rule (tabcorr.py:623-650) and, with a data vector, chi2 and its gradient.
+// There is ONE form: what a draw's results are made of -- the node sums in node order, the
+// matrix products in column order, the sums over rows in row order, the fixed tree over the four
+// row groups of a tile -- depends on the table alone, never on the batch or on the draw's
+// neighbours: the results are batch-invariant by construction.
+// Where the value's own formula divides by zero (ngal = 0, sigma_logM = 0) the derivatives are
+// whatever IEEE arithmetic makes of it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "fastmath.h"
+#include "grad.h"
+
+namespace tc {
+
+namespace grad {
+
+constexpr double kLn10 = 2.302585092994045684;
+constexpr double kLog2E = 1.4426950408889634074;
+constexpr double kTwoOverSqrtPi = 1.1283791670955125739;
+
+struct Draw {
+  double log_m_min, inv_sigma, m0, m0_ln10, inv_m1, alpha;
+};
+
+// <N_cen> and its derivatives with respect to logMmin and sigma_logM at one node:
+// N = (1 + erf x) / 2, dN/dlogMmin = -exp(-x^2) / (sigma sqrt(pi)), dN/dsigma = x dN/dlogMmin.
+// erf_gauss_fast counts the Gaussian as zero from |x| = 6 on; the derivative of a draw whose
+// every node lies out there is made of exactly these tails, so they are evaluated: exp(-x^2) =
+// 2^z with the rounding error of the product z = -x^2 log2 e carried along.
+__device__ __forceinline__ void central_node(const double* mt, const fm::Consts& k, const Draw& d,
+                                             double log_m, double* n, double* dn0, double* dn1) {
+  const double x = (log_m - d.log_m_min) * d.inv_sigma;
+  double gauss;
+  const double e = fm::erf_gauss_fast(mt, k, x, &gauss);
+  const double x2 = x * x;
+  const double zh = -x2 * kLog2E;
+  const double zl = fma(-x2, kLog2E, -zh) - fma(x, x, -x2) * kLog2E;
+  const double t = fm::exp2_fast(mt, k, zh, zh > -1000.0);
+  const double tail = kTwoOverSqrtPi * fma(t, zl * fm::kLn2, t);
+  gauss = fabs(x) < 6.0 ? gauss : tail;
+  *n = fma(0.5, e, 0.5);
+  *dn0 = -0.5 * gauss * d.inv_sigma;
+  *dn1 = *dn0 * x;
+}
+
+// w = n_h <N> of bin i (library order: the centrals first) and its five derivatives:
+// out[0] = w, out[1 + k] = dw / dtheta_k.
+__device__ __forceinline__ void bin_values(const GradArgs& a, const fm::Consts& k, const Draw& d,
+                                           int i, double out[6]) {
+  const double* mt = a.math_table;
+  const double* weight = a.weight + (size_t)i * a.n_gauss;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (i < a.n_central) {
+    const double* log_m = a.log_m + (size_t)i * a.n_gauss;
+    for (int node = 0; node < a.n_gauss; ++node) {
+      double n, dn0, dn1;
+      central_node(mt, k, d, log_m[node], &n, &dn0, &dn1);
+      const double wn = weight[node];
+      acc[0] = fma(wn, n, acc[0]);
+      acc[1] = fma(wn, dn0, acc[1]);
+      acc[2] = fma(wn, dn1, acc[2]);
+    }
+  } else {
+    const double* m = a.m + (size_t)i * a.n_gauss;
+    const double* log_m = a.log_m + (size_t)i * a.n_gauss;
+    for (int node = 0; node < a.n_gauss; ++node) {
+      // N = s^alpha with s = (M - M0) / M1 for M > M0, else 0 with zero derivatives (a node
+      // exactly at M0 included): dN/dlogM0 = -alpha s^(alpha - 1) M0 ln 10 / M1 =
+      // -alpha N M0 ln 10 / (M - M0), dN/dlogM1 = -alpha ln 10 N, dN/dalpha = N ln s
+      const double diff = m[node] - d.m0;
+      const bool use = diff > 0.0;
+      const double safe = use ? diff : 1.0;
+      const double s = use ? diff * d.inv_m1 : 1.0;
+      const double log2_s = fm::log2_fast(mt, k, s);
+      const double n = fm::exp2_fast(mt, k, d.alpha * log2_s, use);
+      double v[6];
+      v[0] = n;
+      v[1] = 0.0;
+      v[2] = 0.0;
+      v[3] = -d.alpha * n * d.m0_ln10 / safe;
+      v[4] = -d.alpha * kLn10 * n;
+      v[5] = n * fm::ln_from_log2(log2_s);
+      if (a.modulate) {
+        // product rule with <N_cen> at the satellites' node
+        double c, dc0, dc1;
+        central_node(mt, k, d, log_m[node], &c, &dc0, &dc1);
+        v[1] = n * dc0;
+        v[2] = n * dc1;
+        v[0] *= c;
+        v[3] *= c;
+        v[4] *= c;
+        v[5] *= c;
+      }
+      const double wn = weight[node];
+#pragma unroll
+      for (int p = 0; p < 6; ++p) acc[p] = fma(wn, v[p], acc[p]);
+    }
+  }
+  const double n_h = a.n_h[i];
+#pragma unroll
+  for (int p = 0; p < 6; ++p) out[p] = n_h * acc[p];
+}
+
+__device__ __forceinline__ Draw load_draw(const GradArgs& a, const fm::Consts& k, int64_t draw) {
+  // (the lanes beyond the batch repeat its last draw and store nothing)
+  const double* theta = a.theta + (draw < a.n_draws ? draw : a.n_draws - 1) * kGradParams;
+  Draw d;
+  d.log_m_min = theta[0];
+  d.inv_sigma = 1.0 / theta[1];
+  d.m0 = fm::exp10_fast(a.math_table, k, theta[2]);
+  d.m0_ln10 = d.m0 * kLn10;
+  d.inv_m1 = 1.0 / fm::exp10_fast(a.math_table, k, theta[3]);
+  d.alpha = theta[4];
+  return d;
+}
+
+// LDS row of (bin i, quantity p) in grad_auto_kernel (grad.h: grad_auto_rows)
+__device__ __forceinline__ int auto_row(int i, int p, int n_bins, int n_central, int zero_row) {
+  if (i >= n_bins) return zero_row;
+  if (i < n_central) return p < 3 ? 3 * i + p : zero_row;
+  return 3 * n_central + 6 * (i - n_central) + p;
+}
+
+// chi2 = e^T P e and dchi2 / dtheta_k = 2 e^T P_sym dxi_k with P_sym = (P + P^T) / 2, from the
+// residuals e (p = 0) and the derivatives (p = 1 .. 5) at stash[(p n_r + r) 16 + draw]; threads
+// 0 .. 95 = (p, draw).
+__device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* stash, int64_t draw0) {
+  const int t = threadIdx.x;
+  if (t >= 6 * kGradDraws) return;
+  const int p = t / kGradDraws, col = t % kGradDraws;
+  const int n_r = a.n_r;
+  const double* precision = a.chi2_data + n_r;
+  const double* e = stash + col;
+  const double* right = stash + (size_t)p * n_r * kGradDraws + col;
+  double sum = 0.0;
+  for (int r = 0; r < n_r; ++r) {
+    double row = 0.0;
+    if (p == 0) {
+      for (int s = 0; s < n_r; ++s) row = fma(precision[(size_t)r * n_r + s], e[s * kGradDraws], row);
+    } else {
+      for (int s = 0; s < n_r; ++s)
+        row = fma(precision[(size_t)r * n_r + s] + precision[(size_t)s * n_r + r],
+                  right[s * kGradDraws], row);
+    }
+    sum = fma(e[r * kGradDraws], row, sum);
+  }
+  const int64_t draw = draw0 + col;
+  if (draw >= a.n_draws) return;
+  if (p == 0)
+    a.chi2[draw] = sum;
+  else
+    a.dchi2[draw * kGradParams + (p - 1)] = sum;
+}
+
+}  // namespace grad
+
+// ---- mode auto ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs a) {
+  extern __shared__ double grad_lds[];
+  const int t = threadIdx.x;
+  const int col = t % kGradDraws;
+  const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
+  const int n_bins = a.n_bins, n_central = a.n_central, n_r = a.n_r;
+  const int zero_row = grad_auto_rows(n_bins, n_central) - 1;
+  double* w = grad_lds;                                       // (rows, 16)
+  double* total = w + (size_t)(zero_row + 1) * kGradDraws;    // (6, 16)
+  double* stash = total + 6 * kGradDraws;                     // (6, n_r, 16), likelihood only
+  const fm::Consts k = fm::make_consts();
+
+  // phase 1: thread = (bin i % 16, draw)
+  {
+    const grad::Draw d = grad::load_draw(a, k, draw0 + col);
+    if (t < kGradDraws) w[zero_row * kGradDraws + t] = 0.0;
+    for (int i = t / kGradDraws; i < n_bins; i += kGradThreads / kGradDraws) {
+      double out[6];
+      grad::bin_values(a, k, d, i, out);
+      const int base = grad::auto_row(i, 0, n_bins, n_central, zero_row);
+      const int count = i < n_central ? 3 : 6;
+#pragma unroll
+      for (int p = 0; p < 6; ++p)
+        if (p < count) w[(base + p) * kGradDraws + col] = out[p];
+    }
+  }
+  __syncthreads();
+  // totals over the bins in bin order: ngal and its derivatives
+  if (t < 6 * kGradDraws) {
+    const int p = t / kGradDraws;
+    double sum = 0.0;
+    for (int i = 0; i < n_bins; ++i)
+      sum += w[grad::auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col];
+    total[t] = sum;
+    const int64_t draw = draw0 + col;
+    if (draw < a.n_draws) {
+      if (p == 0)
+        a.ngal[draw] = sum;
+      else
+        a.dngal[draw * kGradParams + (p - 1)] = sum;
+    }
+  }
+  __syncthreads();
+
+  // phase 2: lane = (row group l / 16, draw l % 16); D[row = l / 16 + 4 v][draw] in register v
+  const int lane = t % 64, wave = t / 64;
+  const int group = lane / kGradDraws;
+  const int tiles = a.row_tiles, steps = a.k_steps;
+  const double ngal = total[col];
+  const double inv_ngal = 1.0 / ngal;
+  const double inv_ngal2 = 1.0 / (ngal * ngal);
+  typedef double f64x4 __attribute__((ext_vector_type(4)));
+  for (int r = wave; r < n_r; r += kGradWaves) {
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int tile = 0; tile < tiles; ++tile) {
+      const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
+      f64x4 u = {0.0, 0.0, 0.0, 0.0};
+      // four steps per round, the operands of the next round fetched ahead of this round's
+      // matrix instructions (a step beyond the last one repeats it and is not multiplied)
+      double a_now[4], a_next[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) a_now[s] = a_lane[(size_t)(s < steps ? s : steps - 1) * 64];
+      for (int step0 = 0; step0 < steps; step0 += 4) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int next = step0 + 4 + s;
+          a_next[s] = a_lane[(size_t)(next < steps ? next : steps - 1) * 64];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int step = step0 + s;
+          if (step < steps) {
+            const int j = 4 * step + group;
+            const double b = w[grad::auto_row(j, 0, n_bins, n_central, zero_row) * kGradDraws + col];
+            u = __builtin_amdgcn_mfma_f64_16x16x4f64(a_now[s], b, u, 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) a_now[s] = a_next[s];
+      }
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int i = 16 * tile + group + 4 * v;
+        const double uv = u[v];
+#pragma unroll
+        for (int p = 0; p < 6; ++p)
+          acc[p] = fma(w[grad::auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col], uv,
+                       acc[p]);
+      }
+    }
+    // the four row groups of a draw: (0 + 1) + (2 + 3), in every lane
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+      acc[p] += __shfl_xor(acc[p], 16);
+      acc[p] += __shfl_xor(acc[p], 32);
+    }
+    // xi = q / ngal^2, dxi_k = dq_k / ngal^2 - 2 xi dngal_k / ngal with dq_k = 2 dw_k . U
+    const double xi = acc[0] * inv_ngal2;
+    const int64_t draw = draw0 + col;
+    if (group == 0) {
+      if (a.xi != nullptr) {
+        if (draw < a.n_draws) a.xi[draw * n_r + r] = xi;
+      } else {
+        stash[(size_t)r * kGradDraws + col] = xi - a.chi2_data[r];
+      }
+    }
+#pragma unroll
+    for (int p = 1; p < 6; ++p) {
+      const double dxi =
+          2.0 * acc[p] * inv_ngal2 - 2.0 * xi * total[p * kGradDraws + col] * inv_ngal;
+      if (group == 0) {
+        if (a.xi != nullptr) {
+          if (draw < a.n_draws) a.dxi[(draw * kGradParams + (p - 1)) * n_r + r] = dxi;
+        } else {
+          stash[((size_t)p * n_r + r) * kGradDraws + col] = dxi;
+        }
+      }
+    }
+  }
+  if (a.xi == nullptr) {
+    __syncthreads();
+    grad::finish_chi2(a, stash, draw0);
+  }
+}
+
+// ---- mode cross ---------------------------------------------------------------------------------
+// xi_r = T_r . w / ngal (tabcorr.py:646-649): the bins in slabs of kGradCrossSlab, any number of
+// them; thread = (r, quantity, draw) items for the products, which it keeps in LDS.
+__global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs a) {
+  extern __shared__ double grad_lds[];
+  const int t = threadIdx.x;
+  const int col = t % kGradDraws;
+  const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
+  const int n_bins = a.n_bins, n_r = a.n_r;
+  double* w = grad_lds;                                               // (6, slab, 16)
+  double* y = w + 6 * kGradCrossSlab * kGradDraws;                    // (6, n_r, 16)
+  double* total = y + (size_t)6 * n_r * kGradDraws;                   // (6, 16)
+  const fm::Consts k = fm::make_consts();
+  const grad::Draw d = grad::load_draw(a, k, draw0 + col);
+  const int n_items = 6 * n_r * kGradDraws;
+  for (int item = t; item < n_items; item += kGradThreads) y[item] = 0.0;
+  double my_total = 0.0;
+  for (int slab0 = 0; slab0 < n_bins; slab0 += kGradCrossSlab) {
+    const int count = min(kGradCrossSlab, n_bins - slab0);
+    __syncthreads();
+    for (int li = t / kGradDraws; li < count; li += kGradThreads / kGradDraws) {
+      double out[6];
+      grad::bin_values(a, k, d, slab0 + li, out);
+#pragma unroll
+      for (int p = 0; p < 6; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
+    }
+    __syncthreads();
+    if (t < 6 * kGradDraws) {
+      const int p = t / kGradDraws;
+      for (int li = 0; li < count; ++li) my_total += w[(p * kGradCrossSlab + li) * kGradDraws + col];
+    }
+    for (int item = t; item < n_items; item += kGradThreads) {
+      const int r = item / (6 * kGradDraws), p = item / kGradDraws % 6;
+      const double* column = a.matrix + (size_t)slab0 * n_r + r;
+      const double* rows = w + (size_t)p * kGradCrossSlab * kGradDraws + col;
+      const size_t slot = ((size_t)p * n_r + r) * kGradDraws + col;
+      double sum = y[slot];
+      for (int li = 0; li < count; ++li)
+        sum = fma(column[(size_t)li * n_r], rows[li * kGradDraws], sum);
+      y[slot] = sum;
+    }
+  }
+  if (t < 6 * kGradDraws) {
+    total[t] = my_total;
+    const int p = t / kGradDraws;
+    const int64_t draw = draw0 + col;
+    if (draw < a.n_draws) {
+      if (p == 0)
+        a.ngal[draw] = my_total;
+      else
+        a.dngal[draw * kGradParams + (p - 1)] = my_total;
+    }
+  }
+  __syncthreads();
+  // xi = y_0 / ngal, dxi_k = (y_k - xi dngal_k) / ngal: first the derivatives (they read y_0),
+  // then the values
+  const double inv_ngal = 1.0 / total[col];
+  const int64_t draw = draw0 + col;
+  for (int item = t; item < n_items; item += kGradThreads) {
+    const int r = item / (6 * kGradDraws), p = item / kGradDraws % 6;
+    if (p == 0) continue;
+    const size_t slot = ((size_t)p * n_r + r) * kGradDraws + col;
+    const double xi = y[(size_t)r * kGradDraws + col] * inv_ngal;
+    const double dxi = (y[slot] - xi * total[p * kGradDraws + col]) * inv_ngal;
+    if (a.xi == nullptr)
+      y[slot] = dxi;
+    else if (draw < a.n_draws)
+      a.dxi[(draw * kGradParams + (p - 1)) * n_r + r] = dxi;
+  }
+  __syncthreads();
+  for (int item = t; item < n_r * kGradDraws; item += kGradThreads) {
+    const int r = item / kGradDraws;
+    const double xi = y[item] * inv_ngal;       // (item % 16 == col: 256 is a multiple of 16)
+    if (a.xi == nullptr)
+      y[item] = xi - a.chi2_data[r];
+    else if (draw < a.n_draws)
+      a.xi[draw * n_r + r] = xi;
+  }
+  if (a.xi == nullptr) {
+    __syncthreads();
+    grad::finish_chi2(a, y, draw0);
+  }
+}
+
+}  // namespace tc

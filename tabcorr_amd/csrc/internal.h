@@ -23,6 +23,7 @@
 #include "../../include/tabcorr_amd.h"
 #include "../../include/tabcorr_amd_testing.h"
 #include "fastmath.h"
+#include "grad.h"
 #include "hostmath.h"
 #include "kernel_args.h"
 
@@ -260,6 +261,18 @@ struct CrossFused {
   }
 };
 
+// The matrix as the gradient kernels read it (grad.h: the dense operand layout of mode auto, the
+// (bins, r) matrix of mode cross), built at the first gradient call (launch.hip: build_grad_table).
+struct GradTable {
+  bool tried = false;
+  void* d_matrix = nullptr;
+  void release() {
+    if (d_matrix != nullptr) (void)hipFree(d_matrix);
+    d_matrix = nullptr;
+    tried = false;
+  }
+};
+
 // Developer knobs.  The release build never reads the environment: tuning values are the
 // defaults of `Tuning` below (read once per handle in developer builds, -DTC_DEVELOPER_KNOBS,
 // so that parameter sweeps stay possible) and the few run-time options a caller may
@@ -487,6 +500,7 @@ struct tc_table {
   // the coefficient rows of predict_cross_fused_kernel (also those of interpolators)
   std::vector<double> cross_host;
   tc::host::CrossFused cross_fused, cross_fused_wide;
+  tc::host::GradTable grad;      // gradient entry points
   // Set while the chunks of a synchronous host call are queued (0 otherwise): the workgroups a
   // mode-cross launch should have at least, instead of Tuning::cross_target -- 512 / chunks, so
   // that a call that has the chip to itself fills it once with shares of tiles (the
@@ -687,6 +701,15 @@ int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_dr
               unsigned flags, double* ngal_device, double* xi_device);
 int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                        int n_gauss, unsigned flags);
+// Gradients (grad_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels do
+// not serve (TC_ERR_UNSUPPORTED with a message), the handle's copy of the matrix, the launch.
+// xi / dxi NULL: chi2 / dchi2 from chi2_data (data, then the precision matrix, on the device).
+int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
+                    int n_gauss, unsigned flags, bool chi2);
+int build_grad_table(tc_table* t);
+int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
+             unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
+             const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream);
 // Mode cross, one launch per batch (predict_cross_fused_kernel): the coefficient rows of one
 // table / K tables with common mass bins (cf->rows == 0 afterwards: not available), whether a
 // call takes that form, and the launch (`interp`: the spline part of the arguments, or NULL).
@@ -758,7 +781,8 @@ int launch_occ_from_array(tc_table* t, const double* occupation_device, int64_t 
 int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
                 const double* precision, double* chi2, hipStream_t stream);
 
-// ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip) ----
+// ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
+// inst_grad.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -780,6 +804,8 @@ int launch_fused_instance(const FusedInstance& instance, int device, int n_u, di
 int launch_cross_instance(bool assembias, bool modulate, bool defer, int device, int rows,
                           dim3 grid, dim3 block, int lds, hipStream_t stream, hipEvent_t k0,
                           hipEvent_t k1, const tc::CrossFusedArgs& ca);
+int launch_grad_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
+                         hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_resident_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_ensemble_kernel(int device, int grid, int lds_bytes, hipStream_t stream,

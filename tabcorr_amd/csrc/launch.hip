@@ -1292,6 +1292,132 @@ int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_dr
   return TC_OK;
 }
 
+// ---- gradients, one launch per batch (grad_kernels.hip.h) -------------------------------------
+
+int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
+                    int n_gauss, unsigned flags, bool chi2) {
+  TC_CHECK(t != nullptr, "table handle is NULL");
+  const unsigned unserved = flags & ~(unsigned)TC_FLAG_MODULATE_WITH_CENOCC;
+  if (unserved & TC_FLAG_SEPARATE_GAL_TYPE)
+    return fail(TC_ERR_UNSUPPORTED, "gradients are implemented for the total prediction only "
+                                    "(not separate_gal_type)");
+  if (unserved & TC_FLAG_ASSEMBIAS)
+    return fail(TC_ERR_UNSUPPORTED, "gradients are not implemented for assembly bias");
+  if (unserved & TC_FLAG_LEAUTHAUD11)
+    return fail(TC_ERR_UNSUPPORTED, "gradients are implemented for the Zheng07 family only");
+  if (unserved != 0) return fail(TC_ERR_UNSUPPORTED, "gradients: unknown flags 0x%x", unserved);
+  if (t->compute_dtype != TC_DTYPE_F64)
+    return fail(TC_ERR_UNSUPPORTED, "gradients need a float64 compute dtype");
+  TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
+  TC_CHECK(n_draws == 0 || theta != nullptr, "theta is NULL");
+  TC_CHECK(n_gauss >= 1 && n_gauss <= 4096, "n_gauss_prim must be in [1, 4096]");
+  TC_CHECK(n_theta == tc::kGradParams, "theta must have %d columns, got %d", tc::kGradParams,
+           n_theta);
+  const size_t lds = t->mode == TC_MODE_AUTO
+                         ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, chi2)
+                         : tc::grad_cross_lds_bytes(t->n_r);
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "gradients: a table of %d bins and %d correlation function bins needs %zu bytes "
+                "of LDS per workgroup, beyond the %d there are",
+                t->n_bins, t->n_r, lds, kMaxLdsBytes);
+  if (t->mode == TC_MODE_AUTO &&
+      tc::grad_operand_doubles(t->n_bins, t->n_r) * sizeof(double) > ((size_t)1 << 31))
+    return fail(TC_ERR_UNSUPPORTED, "gradients: the dense matrix of %d bins exceeds 2 GiB",
+                t->n_bins);
+  return TC_OK;
+}
+
+int build_grad_table(tc_table* t) {
+  if (t->grad.tried) return TC_OK;
+  // the matrix comes back from the handle's own copy on the device (tc_table_create: per r tile
+  // and position, the pair prefactor folded in -- a division by 1 or 2 is exact)
+  const int rt = t->rt, n_r = t->n_r, g = t->n_bins;
+  const int64_t n_positions = t->plan.n_positions;
+  std::vector<double> laid_out((size_t)t->n_rtiles * n_positions * rt);
+  TC_HIP(hipMemcpy(laid_out.data(), t->d_table, laid_out.size() * sizeof(double),
+                   hipMemcpyDeviceToHost));
+  const bool is_auto = t->mode == TC_MODE_AUTO;
+  const size_t n_pairs = is_auto ? (size_t)g * (g + 1) / 2 : (size_t)g;
+  // auto: (n_r, packed lower triangle) in library bin order; cross: (bins, n_r)
+  std::vector<double> matrix((size_t)n_r * n_pairs, 0.0);
+  for (int r = 0; r < n_r; ++r) {
+    const int tile = r / rt, rr = r % rt;
+    for (int64_t q = 0; q < n_positions; ++q) {
+      if (t->plan.column[q] < 0) continue;
+      const size_t index = ((size_t)tile * n_positions + q / 8 * 8) * rt +
+                           (((rr / 4) * 16 + (q % 4) * 4 + rr % 4) * 2 + (q / 4) % 2);
+      const double value = laid_out[index] / t->plan.prefactor[q];
+      const int i = t->plan.pos_i[q], j = t->plan.pos_j[q];
+      if (is_auto) {
+        const int hi = std::max(i, j), lo = std::min(i, j);
+        matrix[(size_t)r * n_pairs + (size_t)hi * (hi + 1) / 2 + lo] = value;
+      } else {
+        matrix[(size_t)j * n_r + r] = value;
+      }
+    }
+  }
+  int status = TC_OK;
+  if (is_auto) {
+    std::vector<double> operand;
+    tc::build_grad_operand(g, n_r, matrix.data(), operand);
+    status = upload(operand, &t->grad.d_matrix);
+  } else {
+    status = upload(matrix, &t->grad.d_matrix);
+  }
+  if (status != TC_OK) return status;
+  t->grad.tried = true;
+  return TC_OK;
+}
+
+int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
+             unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
+             const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream) {
+  Range range("gradients (one launch)");
+  Quadrature* q = nullptr;
+  int status = get_quadrature(t, n_gauss, &q);
+  if (status == TC_OK) status = build_grad_table(t);
+  if (status != TC_OK) return status;
+  tc::GradArgs ga{};
+  ga.theta = theta_device;
+  ga.n_draws = n_draws;
+  ga.n_bins = t->n_bins;
+  ga.n_central = t->plan.n_central;
+  ga.n_gauss = n_gauss;
+  ga.n_r = t->n_r;
+  ga.modulate = (flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0 ? 1 : 0;
+  ga.log_m = (const double*)q->log_m;
+  ga.m = (const double*)q->m;
+  ga.weight = (const double*)q->weight;
+  ga.n_h = (const double*)t->d_n_h;
+  ga.math_table = (const double*)t->d_math_table;
+  ga.matrix = (const double*)t->grad.d_matrix;
+  ga.row_tiles = tc::grad_row_tiles(t->n_bins);
+  ga.k_steps = tc::grad_k_steps(t->n_bins);
+  ga.ngal = ngal;
+  ga.dngal = dngal;
+  ga.xi = xi;
+  ga.dxi = dxi;
+  ga.chi2_data = chi2_data;
+  ga.chi2 = chi2;
+  ga.dchi2 = dchi2;
+  const bool with_chi2 = xi == nullptr;
+  const int lds = (int)(t->mode == TC_MODE_AUTO
+                            ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, with_chi2)
+                            : tc::grad_cross_lds_bytes(t->n_r));
+  const dim3 grid((unsigned)((n_draws + tc::kGradDraws - 1) / tc::kGradDraws));
+  hipEvent_t k0 = nullptr, k1 = nullptr;
+  status = next_kernel_events(t, &k0, &k1);
+  if (status != TC_OK) return status;
+  status = launch_grad_instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
+  if (status != TC_OK) return status;
+  t->last_workgroups = (int)grid.x;
+  t->last_waves = tc::kGradWaves;
+  t->last_splits = 0;
+  t->last_lds = lds;
+  return TC_OK;
+}
+
 // ---- mode cross, one launch per batch -----------------------------------------------------
 
 CrossFused* choose_cross_fused(tc_table* const* tables, int n_tables, CrossFused* narrow,

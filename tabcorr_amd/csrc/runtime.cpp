@@ -485,7 +485,7 @@ int tc_gauss_legendre(int n, double* x, double* w) {
 }
 
 int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y) {
-  TC_CHECK(kind >= 0 && kind <= 5 && n >= 0 && x && y, "invalid arguments");
+  TC_CHECK(kind >= 0 && kind <= 6 && n >= 0 && x && y, "invalid arguments");
   static std::vector<double> table;
   if (table.empty()) {
     table.resize(tc::fm::kTableDoubles);
@@ -497,12 +497,33 @@ int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y) {
     if (kind == 1) y[i] = tc::fm::log2_fast(table.data(), k, x[i]);
     if (kind == 2) y[i] = tc::fm::exp2_fast(table.data(), k, x[i]);
     if (kind == 3) y[i] = tc::fm::exp10_fast(table.data(), k, x[i]);
-    if (kind >= 4) {
+    if (kind == 6) y[i] = tc::fm::log_fast(table.data(), k, x[i]);
+    if (kind == 4 || kind == 5) {
       double gauss;
       const double value = tc::fm::erf_gauss_fast(table.data(), k, x[i], &gauss);
       y[i] = kind == 4 ? value : gauss;
     }
   }
+  return TC_OK;
+}
+
+int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* dense) {
+  TC_CHECK(n_bins >= 1 && n_r >= 1 && packed && dense, "invalid arguments");
+  std::vector<double> operand;
+  tc::build_grad_operand(n_bins, n_r, packed, operand);
+  // read back as the kernel's lanes address it: block of 16 rows, step of 4 columns, lane
+  const int tiles = tc::grad_row_tiles(n_bins), steps = tc::grad_k_steps(n_bins);
+  for (int r = 0; r < n_r; ++r)
+    for (int tile = 0; tile < tiles; ++tile)
+      for (int step = 0; step < steps; ++step)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int i = 16 * tile + lane % 16, j = 4 * step + lane / 16;
+          const double value = operand[(((size_t)r * tiles + tile) * steps + step) * 64 + lane];
+          if (i < n_bins && j < n_bins)
+            dense[((size_t)r * n_bins + i) * n_bins + j] = value;
+          else
+            TC_CHECK(value == 0.0, "padding of the operand layout is not zero");
+        }
   return TC_OK;
 }
 

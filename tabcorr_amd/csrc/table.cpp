@@ -259,6 +259,7 @@ int tc_table_destroy(tc_table* t) {
   t->quad_total.release();
   t->cross_fused.release();
   t->cross_fused_wide.release();
+  t->grad.release();
   for (DeviceBuffer* b : {&t->theta, &t->out_ngal, &t->out_xi, &t->occupation,
                           &t->trace, &t->wave_trace, &t->chi2_data})
     b->release();
@@ -1009,6 +1010,132 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   }
   return copy_out(&t->h_out, ngal, (size_t)n_draws, d_ngal, chi2, (size_t)n_draws,
                   d_chi2, t->stream);
+}
+
+// ---- gradients (launch.hip: run_grad) -----------------------------------------------------
+
+namespace {
+
+// The lane a device-pointer gradient call runs on (as tc_predict_zheng07_batch_device).
+int grad_lane(tc_table* t) {
+  if (t->force_lane >= 0)
+    t->cur = t->force_lane;
+  else
+    t->cur = t->tuning.pipeline ? (int)(t->device_calls++ % t->n_lanes) : 0;
+  return t->cur;
+}
+
+int grad_device(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
+                unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
+                const double* chi2_data, double* chi2, double* dchi2) {
+  TC_HIP(hipSetDevice(t->device));
+  int status = TC_OK;
+  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  tc_table::Lane& lane = t->lanes[grad_lane(t)];
+  const int64_t slab = max_slab(t);
+  const int64_t n_r = t->n_r;
+  for (int64_t begin = 0; begin < n_draws; begin += slab) {
+    const int64_t n = std::min(slab, n_draws - begin);
+    status = run_grad(t, theta_device + begin * tc::kGradParams, n, n_gauss, flags, ngal + begin,
+                      xi ? xi + begin * n_r : nullptr, dngal + begin * tc::kGradParams,
+                      dxi ? dxi + begin * tc::kGradParams * n_r : nullptr, chi2_data,
+                      chi2 ? chi2 + begin : nullptr,
+                      dchi2 ? dchi2 + begin * tc::kGradParams : nullptr, lane.stream);
+    if (status != TC_OK) return status;
+  }
+  t->prev = t->force_lane >= 0 ? -1 : t->cur;
+  return TC_OK;
+}
+
+// Host arrays: the draws go up and the four result arrays come down on lane 0; `wide` = doubles
+// per draw of the two large results (xi and dxi, or chi2 and dchi2).
+int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, unsigned flags,
+              const double* chi2_data, double* ngal, double* value, double* dngal,
+              double* dvalue) {
+  TC_HIP(hipSetDevice(t->device));
+  const bool chi2 = chi2_data != nullptr;
+  const size_t n = (size_t)n_draws, n_r = (size_t)t->n_r, np = tc::kGradParams;
+  const size_t value_count = chi2 ? n : n * n_r;
+  int status = t->theta.reserve(n * np * 8, t->stream);
+  if (status == TC_OK) status = t->out_ngal.reserve(n * (1 + np) * 8, t->stream);
+  if (status == TC_OK) status = t->out_xi.reserve(value_count * (1 + np) * 8, t->stream);
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(t->theta.ptr, theta, n * np * 8, hipMemcpyHostToDevice, t->stream));
+  double* d_ngal = (double*)t->out_ngal.ptr;
+  double* d_dngal = d_ngal + n;
+  double* d_value = (double*)t->out_xi.ptr;
+  double* d_dvalue = d_value + value_count;
+  t->force_lane = 0;
+  status = chi2 ? grad_device(t, (const double*)t->theta.ptr, n_draws, n_gauss, flags, d_ngal,
+                              nullptr, d_dngal, nullptr, chi2_data, d_value, d_dvalue)
+                : grad_device(t, (const double*)t->theta.ptr, n_draws, n_gauss, flags, d_ngal,
+                              d_value, d_dngal, d_dvalue, nullptr, nullptr, nullptr);
+  t->force_lane = -1;
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
+  TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * np * 8, hipMemcpyDeviceToHost, t->stream));
+  TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, t->stream));
+  TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * np * 8, hipMemcpyDeviceToHost,
+                        t->stream));
+  TC_HIP(hipStreamSynchronize(t->stream));
+  return TC_OK;
+}
+
+}  // namespace
+
+int tc_predict_grad_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                         int64_t n_draws, int n_gauss, unsigned flags,
+                                         double* ngal_device, double* xi_device,
+                                         double* dngal_device, double* dxi_device) {
+  const int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, false);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
+  return grad_device(t, theta_device, n_draws, n_gauss, flags, ngal_device, xi_device,
+                     dngal_device, dxi_device, nullptr, nullptr, nullptr);
+}
+
+int tc_predict_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta,
+                                  int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
+                                  double* xi, double* dngal, double* dxi) {
+  const int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, false);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
+  return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi);
+}
+
+int tc_chi2_grad_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                      int64_t n_draws, int n_gauss, unsigned flags,
+                                      const double* data, const double* precision,
+                                      double* ngal_device, double* chi2_device,
+                                      double* dngal_device, double* dchi2_device) {
+  int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, true);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(data && precision && ngal_device && chi2_device && dngal_device && dchi2_device,
+           "NULL pointer");
+  TC_HIP(hipSetDevice(t->device));
+  status = upload_chi2_data(t, data, precision);
+  if (status != TC_OK) return status;
+  return grad_device(t, theta_device, n_draws, n_gauss, flags, ngal_device, nullptr,
+                     dngal_device, nullptr, (const double*)t->chi2_data.ptr, chi2_device,
+                     dchi2_device);
+}
+
+int tc_chi2_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                               int n_gauss, unsigned flags, const double* data,
+                               const double* precision, double* ngal, double* chi2,
+                               double* dngal, double* dchi2) {
+  int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, true);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(data && precision && ngal && chi2 && dngal && dchi2, "NULL pointer");
+  TC_HIP(hipSetDevice(t->device));
+  status = upload_chi2_data(t, data, precision);
+  if (status != TC_OK) return status;
+  return grad_host(t, theta, n_draws, n_gauss, flags, (const double*)t->chi2_data.ptr, ngal,
+                   chi2, dngal, dchi2);
 }
 
 namespace {

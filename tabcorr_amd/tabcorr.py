@@ -26,7 +26,7 @@ import numpy as np
 from . import _lib
 from . import pinned
 from .galtable import GalTypeTable
-from .models import device_spec
+from .models import ZHENG07_KEYS, device_spec
 
 ATTR_KEYS = ['tpcf', 'mode', 'simname', 'redshift', 'Num_ptcl_requirement',
              'prim_haloprop_key', 'sec_haloprop_key']
@@ -719,6 +719,105 @@ class TabCorr:
                 _lib.as_double_p(ngal), _lib.as_double_p(chi2)))
         return ngal, chi2
 
+    # -- analytic gradients -----------------------------------------------------------
+
+    def predict_batch_grad(self, theta, n_gauss_prim=10,
+                           modulate_with_cenocc=False):
+        """`predict_batch` together with the exact derivatives of its results
+        with respect to the five Zheng07 parameters (`ZHENG07_KEYS` order), in
+        one kernel launch: what a best-fit search, a Fisher forecast or an
+        HMC sampler would otherwise difference `predict_batch` for.
+
+        It is the derivative of the function the library computes (the
+        Gauss-Legendre bin average followed by the contraction), not of the
+        underlying integral: <N_sat> has a kink at every quadrature node that
+        M0 crosses.  Where the value divides by zero (``ngal = 0``,
+        ``sigma_logM = 0``) the derivatives are NaN or inf.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )``
+        xi : ``(n_draws, ) + tpcf_shape``
+        dngal : ``(n_draws, 5)``
+        dxi : ``(n_draws, 5) + tpcf_shape``
+
+        Raises ``NotImplementedError`` for what the kernel does not serve
+        (float32 tables, very large mode-auto tables).
+        """
+        theta = _grad_theta(theta)
+        device = self.to_device()
+        n_draws = len(theta)
+        ngal = np.empty(n_draws)
+        xi = np.empty((n_draws, device.n_r))
+        dngal = np.empty((n_draws, 5))
+        dxi = np.empty((n_draws, 5, device.n_r))
+        with device.lock:
+            _lib.check(device.lib.tc_predict_grad_zheng07_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
+                _lib.as_double_p(ngal), _lib.as_double_p(xi),
+                _lib.as_double_p(dngal), _lib.as_double_p(dxi)))
+        shape = tuple(self.tpcf_shape)
+        return (ngal, xi.reshape((n_draws, ) + shape), dngal,
+                dxi.reshape((n_draws, 5) + shape))
+
+    def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
+                        modulate_with_cenocc=False):
+        """`chi2_batch` with its gradient: ``dchi2[:, k] = 2 (xi - data)^T P_sym
+        dxi / dtheta_k`` with ``P_sym = (precision + precision^T) / 2``,
+        finished on the device in the launch that computes ``xi``.
+
+        Returns
+        -------
+        ngal, chi2 : ``(n_draws, )``
+        dngal, dchi2 : ``(n_draws, 5)``
+        """
+        theta = _grad_theta(theta)
+        device = self.to_device()
+        data = _lib.contiguous(np.ravel(data))
+        precision = _lib.contiguous(precision)
+        if data.shape != (device.n_r, ) or precision.shape != (device.n_r,
+                                                               device.n_r):
+            raise ValueError('data must have {0} entries and precision shape '
+                             '({0}, {0}).'.format(device.n_r))
+        n_draws = len(theta)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal, dchi2 = np.empty((n_draws, 5)), np.empty((n_draws, 5))
+        with device.lock:
+            _lib.check(device.lib.tc_chi2_grad_zheng07_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
+                _lib.as_double_p(data), _lib.as_double_p(precision),
+                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
+                _lib.as_double_p(dngal), _lib.as_double_p(dchi2)))
+        return ngal, chi2, dngal, dchi2
+
+    def predict_grad(self, model, n_gauss_prim=10, check_consistency=True):
+        """Un-batched `predict_batch_grad` for a model object: a plain
+        `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model).
+
+        Returns
+        -------
+        ngal : float
+        xi : numpy.ndarray of shape ``tpcf_shape``
+        dngal : dict, `ZHENG07_KEYS` -> float
+        dxi : dict, `ZHENG07_KEYS` -> numpy.ndarray of shape ``tpcf_shape``
+        """
+        if check_consistency:
+            self._check_consistency_cached(model)
+        spec = device_spec(model)
+        if spec is None or spec.family != 'zheng07' or spec.assembias:
+            raise NotImplementedError(
+                'predict_grad needs a plain Zheng07 model (no assembly bias, '
+                'no other family).')
+        ngal, xi, dngal, dxi = self.predict_batch_grad(
+            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            n_gauss_prim=n_gauss_prim,
+            modulate_with_cenocc=spec.modulate_with_cenocc)
+        return (float(ngal[0]), xi[0],
+                {key: float(dngal[0, k]) for k, key in enumerate(ZHENG07_KEYS)},
+                {key: dxi[0, k] for k, key in enumerate(ZHENG07_KEYS)})
+
     def chi2_batch_async(self, theta, data, precision, n_gauss_prim=10,
                          modulate_with_cenocc=False, assembias=False,
                          family='zheng07', out=None):
@@ -790,6 +889,15 @@ def _flags(separate_gal_type=False, modulate_with_cenocc=False,
             (_lib.FLAG_MODULATE_WITH_CENOCC if modulate_with_cenocc else 0) |
             (_lib.FLAG_ASSEMBIAS if assembias else 0) |
             (_lib.FLAG_LEAUTHAUD11 if family == 'leauthaud11' else 0))
+
+
+def _grad_theta(theta):
+    """The ``(n_draws, 5)`` parameter array of the gradient calls."""
+    theta = _lib.contiguous(np.atleast_2d(theta))
+    if theta.ndim != 2 or theta.shape[1] != len(ZHENG07_KEYS):
+        raise ValueError('theta must have shape (n_draws, {}), got {}.'.format(
+            len(ZHENG07_KEYS), theta.shape))
+    return theta
 
 
 def _unbatch(ngal, xi):

@@ -1,0 +1,109 @@
+#!/usr/bin/env python3
+"""Cost of an analytic-gradient call next to the forward call it replaces several of.
+
+    python tools/grad_bench.py [--draws 10000] [--seconds 1.0] [--notes profiles/grad_notes.md]
+
+BASELINE configs[1] (50 x 2 bins, 19 r values, 10^4 draws, float64) and the shape of the
+reference's example table (30 x 2 bins, 19 r values), device-resident and pipelined over the
+handle's lanes as bench.py's timed region is: us per tc_predict_zheng07_batch_device call (the
+forward path), per tc_predict_grad_zheng07_batch_device call and per
+tc_chi2_grad_zheng07_batch_device call, from the same run.  The bar is what a user without
+gradients pays: one-sided differences cost 6 forward calls, central ones 11.  Prints one JSON
+line and, with --notes, appends the figures to that file.
+"""
+
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+from bench_legs import Device, sustained   # noqa: E402
+
+
+def measure(name, n_prim, n_sec, n_r, n_draws, seconds):
+    from tabcorr_amd import TabCorr, _lib, synthetic
+    table = synthetic.synthetic_table(n_prim, n_sec, (n_r, ), 'auto', seed=0)
+    halotab = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'], table['tpcf_shape'],
+                                  table['attrs'])
+    device = halotab.to_device()
+    lib, handle = device.lib, device.handle
+    memory = Device(lib, _lib)
+    theta = synthetic.zheng07_draws(n_draws, seed=1)
+    d_theta = memory.upload(theta)
+    d_ngal, d_xi = memory.malloc(n_draws), memory.malloc(n_draws * n_r)
+    d_dngal, d_dxi = memory.malloc(n_draws * 5), memory.malloc(n_draws * 5 * n_r)
+    d_chi2, d_dchi2 = memory.malloc(n_draws), memory.malloc(n_draws * 5)
+    rng = np.random.default_rng(3)
+    data = np.ascontiguousarray(rng.uniform(0.5, 1.5, n_r))
+    precision = np.ascontiguousarray(np.eye(n_r) + 0.01 * rng.normal(size=(n_r, n_r)))
+
+    def forward():
+        _lib.check(lib.tc_predict_zheng07_batch_device(handle, d_theta, 5, n_draws, 10, 0,
+                                                       d_ngal, d_xi))
+
+    def gradient():
+        _lib.check(lib.tc_predict_grad_zheng07_batch_device(handle, d_theta, 5, n_draws, 10, 0,
+                                                            d_ngal, d_xi, d_dngal, d_dxi))
+
+    def chi2_gradient():
+        _lib.check(lib.tc_chi2_grad_zheng07_batch_device(
+            handle, d_theta, 5, n_draws, 10, 0, _lib.as_double_p(data),
+            _lib.as_double_p(precision), d_ngal, d_chi2, d_dngal, d_dchi2))
+
+    def synchronize():
+        _lib.check(lib.tc_table_synchronize(handle))
+
+    try:
+        result = {'table': name, 'n_bins': 2 * n_prim * n_sec, 'n_r': n_r, 'n_draws': n_draws}
+        # forward, gradient, forward again: the two forward figures bracket the drift of the run
+        result['forward_us'] = sustained(forward, synchronize, seconds) * 1e6
+        result['grad_us'] = sustained(gradient, synchronize, seconds) * 1e6
+        result['chi2_grad_us'] = sustained(chi2_gradient, synchronize, seconds) * 1e6
+        result['forward_again_us'] = sustained(forward, synchronize, seconds) * 1e6
+        forward_us = 0.5 * (result['forward_us'] + result['forward_again_us'])
+        result['grad_over_forward'] = result['grad_us'] / forward_us
+        result['chi2_grad_over_forward'] = result['chi2_grad_us'] / forward_us
+        workgroups, waves, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        splits = ctypes.c_int()
+        gradient()
+        synchronize()
+        _lib.check(lib.tc_table_last_launch(handle, ctypes.byref(workgroups), ctypes.byref(waves),
+                                            ctypes.byref(splits), ctypes.byref(lds)))
+        result['grad_workgroups'] = workgroups.value
+        result['grad_lds_bytes'] = lds.value
+    finally:
+        synchronize()
+        memory.free_all()
+    return result
+
+
+def main():
+    parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    parser.add_argument('--draws', type=int, default=10000)
+    parser.add_argument('--seconds', type=float, default=1.0)
+    parser.add_argument('--notes', default=None, help='append the figures to this file')
+    args = parser.parse_args()
+    results = [measure('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
+               measure("reference example table's shape", 30, 1, 19, args.draws, args.seconds)]
+    print(json.dumps({'metric': 'us per call, device-resident, pipelined', 'results': results}))
+    if args.notes:
+        with open(args.notes, 'a') as notes:
+            notes.write('\n## tools/grad_bench.py, %d draws per call\n\n' % args.draws)
+            notes.write('| table | bins | forward us | gradient us | chi2 gradient us | '
+                        'gradient / forward | chi2 gradient / forward |\n')
+            notes.write('|---|---|---|---|---|---|---|\n')
+            for r in results:
+                notes.write('| %s | %d | %.1f (%.1f after) | %.1f | %.1f | %.2f | %.2f |\n' % (
+                    r['table'], r['n_bins'], r['forward_us'], r['forward_again_us'],
+                    r['grad_us'], r['chi2_grad_us'], r['grad_over_forward'],
+                    r['chi2_grad_over_forward']))
+
+
+if __name__ == '__main__':
+    main()
