@@ -773,13 +773,15 @@ class TabCorr:
         dngal, dchi2 : ``(n_draws, 5)``
         """
         theta = _grad_theta(theta)
-        device = self.to_device()
         data = _lib.contiguous(np.ravel(data))
         precision = _lib.contiguous(precision)
-        if data.shape != (device.n_r, ) or precision.shape != (device.n_r,
-                                                               device.n_r):
+        # (the rows of the table's own matrix: a wrong argument is refused
+        # before any device is touched, as a wrong theta is)
+        n_r = len(self.tpcf_matrix)
+        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
             raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(device.n_r))
+                             '({0}, {0}).'.format(n_r))
+        device = self.to_device()
         n_draws = len(theta)
         ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
         dngal, dchi2 = np.empty((n_draws, 5)), np.empty((n_draws, 5))

@@ -83,6 +83,11 @@ def jacobian_batch(table, theta, n_gauss_prim=10, modulate=False):
     return tuple(np.array([r[i] for r in results]) for i in range(5))
 
 
+def usable(reference):
+    """Whether every draw of a `jacobian_batch` result has galaxies and all of it is finite."""
+    return bool(np.all(reference[0] > 0.0) and all(np.all(np.isfinite(a)) for a in reference))
+
+
 def nodes_of(table, n_gauss_prim=10):
     """Sorted log10 masses of every quadrature node of the table (tabcorr.py:543-549)."""
     gal_type = table['gal_type']

@@ -76,10 +76,11 @@ def test_natural_log_accuracy_on_host(lib):
     assert np.max(np.abs(out - expect) / np.maximum(1.0, np.abs(expect))) < 4e-16
 
 
-@pytest.mark.parametrize('n_bins', [14, 36, 100])
+@pytest.mark.parametrize('n_bins', [2, 4, 14, 16, 32, 36, 64, 100])
 def test_dense_operand_layout_round_trips(lib, n_bins):
     """The matrix-operand layout the host builds for the gradient kernel, read back lane by lane,
-    is the symmetric expansion of the packed matrix (and its padding is zero)."""
+    is the symmetric expansion of the packed matrix (and its padding is zero).  2 and 4 bins are
+    a single step of four columns, 16, 32 and 64 whole tiles of 16 rows without padding."""
     from tabcorr_amd import _lib
     n_r = 3
     rng = np.random.default_rng(n_bins)
@@ -107,3 +108,38 @@ def test_gradient_calls_reject_a_wrong_theta_shape():
             halotab.predict_batch_grad(np.zeros((3, columns)))
         with pytest.raises(ValueError):
             halotab.chi2_grad_batch(np.zeros((3, columns)), np.zeros(5), np.eye(5))
+
+
+def test_chi2_gradient_calls_reject_wrong_data_and_precision_shapes(lib):
+    """A data vector or a precision matrix that does not fit the table's n_r is a ValueError of
+    `chi2_grad_batch` before any device is touched (the C entry points take bare pointers: the
+    shapes are the Python layer's to check), with tpcf_shape of one axis and of two.  Both C
+    entry points refuse a call without a handle before they read any other argument."""
+    from tabcorr_amd import TabCorr, _lib
+    theta = synthetic.zheng07_draws(3, seed=2)
+    for tpcf_shape in ((5, ), (3, 4)):
+        table = synthetic.synthetic_table(7, 1, tpcf_shape, 'auto', seed=3)
+        halotab = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'],
+                                      table['tpcf_shape'], table['attrs'])
+        n_r = int(np.prod(tpcf_shape))
+        good_data, good_precision = np.zeros(tpcf_shape), np.eye(n_r)
+        for data, precision in ((np.zeros(n_r + 1), good_precision),
+                                (np.zeros(n_r - 1), good_precision),
+                                (np.zeros((n_r, 2)), good_precision),
+                                (good_data, np.eye(n_r + 1)),
+                                (good_data, np.ones((n_r, n_r + 1))),
+                                (good_data, np.ones(n_r * n_r)),
+                                (good_data, np.ones((n_r, n_r, 1)))):
+            with pytest.raises(ValueError, match='precision'):
+                halotab.chi2_grad_batch(theta, data, precision)
+        assert halotab._device is None
+    empty = np.zeros(0)
+    status = lib.tc_chi2_grad_zheng07_batch(
+        None, _lib.as_double_p(theta), 5, 3, 10, 0, *[_lib.as_double_p(empty)] * 6)
+    assert status == _lib.TC_ERR_INVALID
+    with pytest.raises(ValueError):
+        _lib.check(status)
+    status = lib.tc_chi2_grad_zheng07_batch_device(
+        None, None, 5, 3, 10, 0, _lib.as_double_p(empty), _lib.as_double_p(empty),
+        None, None, None, None)
+    assert status == _lib.TC_ERR_INVALID
