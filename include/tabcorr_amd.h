@@ -343,7 +343,7 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *                 lane); 1: their finalisations are chained so that results appear in call
  *                 order (0.3 - 3 us per 10^4-draw step).
  *   "fused"       1 (default): calls that qualify (mode auto, at most 20 r values; 104 bins,
- *                 or 208 for the Zheng07 family with n_gauss_prim = 10; total or separated by
+ *                 or 212 for the Zheng07 family with n_gauss_prim = 10; total or separated by
  *                 galaxy type) run as ONE launch per batch, a workgroup carrying 64, 40 or 32
  *                 draws from the parameters to the results, where that form is estimated to be
  *                 the faster one.  Pipelined device-pointer and asynchronous calls: batches of
@@ -361,7 +361,7 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *   "fused_draws" 0 (default): workgroups of 32 draws (one tile, eight waves, two per CU) for
  *                 batches below 8192 draws of the Zheng07 family with n_gauss_prim = 10 --
  *                 a third faster there, and the one-launch form then pays from 12 draws per
- *                 bin on -- and for tables of 105 .. 208 bins, of 64 draws otherwise; 32 / 64:
+ *                 bin on -- and for tables of 105 .. 212 bins, of 64 draws otherwise; 32 / 64:
  *                 forced; 40: the latency form ("fused_spread") for every batch it serves.
  *   "fused_spread" 1 (default): calls that have the chip to themselves (host arrays, one lane,
  *                 "pipeline" 0) take the latency form of the one-launch kernel -- workgroups of

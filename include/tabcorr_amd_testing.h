@@ -78,6 +78,21 @@ int tc_debug_triangle_parts(int n_rb, int n_parts, int32_t* rb0, int32_t* cb0, i
 int tc_debug_node_groups(int n_bins, int n_central, const double* log_min,
                          const double* log_max, int32_t* begin, int32_t* member,
                          int* n_groups, int* n_central_groups);
+/* Which form a batched call of mode auto takes (tabcorr_amd/csrc/hostmath.h: choose_fused_form)
+ * on a float64 table of n_bins bins (the first n_central centrals) and n_r r values on a device
+ * with n_cus compute units -- no device needed: waves x draws per workgroup of the one launch
+ * (8 x 64, 16 x 64, 8 x 32, 8 x 40) and its dynamic LDS, or waves = draws = lds_bytes = 0: the
+ * three kernels.  call: bit 0 the call runs alone on its lane (host-buffer API, one lane,
+ * pipeline off), 1 asynchronous, 2 a chunk of a synchronous call that fits one round of 40-draw
+ * workgroups, 3 chained finalisations (option "ordered"), 4 developer timeline, 5 the fused
+ * likelihood is asked for.  options: the values of "fused", "fused_min_draws",
+ * "fused_max_draws", "fused_waves", "fused_draws", "fused_spread", "fused_spread_min",
+ * "fused_spread_rounds", "deterministic" (nine ints).  measured_forms (9) / measured_us (9 x 3):
+ * a measured choice as tc_table_autotune_result returns it, or both NULL. */
+int tc_debug_fused_form(int n_bins, int n_central, int n_r, int n_cus, int grouped,
+                        int64_t n_draws, int n_gauss, unsigned flags, unsigned call,
+                        const int* options, const int* measured_forms, const float* measured_us,
+                        int* waves, int* draws, int* lds_bytes);
 /* TEST INFRASTRUCTURE, never called by the product: executes the kernel's table layout,
  * schedule and slab grouping on the host, lane by lane, for densities (n_bins, ldb) given
  * in the reference's bin order; out (n_draws, 1 | 3, n_r) = sum_p c_p T[r][p] n_i n_j

@@ -74,6 +74,10 @@ SIGNATURES = {
                              c_int32_p, c_int32_p, c_int_p, c_int_p],
     'tc_debug_quad_schedule': [ctypes.c_int] * 10 + [c_int_p, c_int_p, c_int_p,
                                                      c_int64_p, c_int64_p],
+    'tc_debug_fused_form': [ctypes.c_int] * 5 + [ctypes.c_int64, ctypes.c_int, ctypes.c_uint,
+                                                 ctypes.c_uint, c_int_p, c_int_p,
+                                                 c_float_p, c_int_p, c_int_p,
+                                                 c_int_p],
     'tc_debug_quad_emulate': [ctypes.c_int, ctypes.c_int, c_double_p, c_uint8_p,
                               ctypes.c_int, ctypes.c_int, c_double_p,
                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -1,6 +1,7 @@
 // Host-side mathematics and work planning (see hostmath.h).
 #include "hostmath.h"
 #include "fastmath.h"
+#include "kernel_args.h"
 #include "series.h"
 
 #include <algorithm>
@@ -797,6 +798,209 @@ QuadTiling quad_tiling(int n_r) {
   tiling.r_per_tile = (n_r + tiling.n_rtiles - 1) / tiling.n_rtiles;
   tiling.n_u = (tiling.r_per_tile + 3) / 4;
   return tiling;
+}
+
+// ---- one launch per batch (predict_fused_kernel, mode auto): which calls take it ------------
+
+int fused_dens_rows(const QuadLayout& layout) {
+  int rows = 0;
+  for (const QuadComp& comp : layout.comps)
+    rows = std::max(rows, std::max(comp.i_bin0 + 4 * comp.n_rb, comp.j_bin0 + 4 * comp.n_cb));
+  return (rows + 3) / 4 * 4;
+}
+
+int fused_lds_bytes(int dens_rows, int waves, int draws) {
+  return (std::max(dens_rows * draws, fused_slot_doubles(waves, draws)) +
+          fused_scratch_doubles(waves)) * 8;
+}
+
+// One launch per slab of draws (predict_fused_kernel): float64 quadratic form with one r tile,
+// densities of a workgroup's draws within the LDS.  In order of precedence: what the kernel
+// does not serve; the latency form; option "deterministic" = 2; a measured choice; the rule for
+// calls that have the chip to themselves; the smallest batch that pays.
+FusedForm choose_fused_form(const FusedQuery& q) {
+  const FusedForm three_kernels{};
+  const bool separate = (q.flags & kFlagSeparate) != 0;
+  const bool modulate = (q.flags & kFlagModulate) != 0;
+  const bool assembias = (q.flags & kFlagAssembias) != 0;
+  const bool leauthaud = (q.flags & 16u) != 0;             // TC_FLAG_LEAUTHAUD11
+  const bool invariant = q.deterministic >= 2;             // (one form whatever the batch)
+  // (a measured choice -- option "autotune" -- knows where the one-launch form stops paying; it
+  // was measured with ten nodes and the default options)
+  const AutoChoice* measured =
+      q.n_gauss == 10 && q.fused == 1 && q.fused_min_draws == 0 ? q.measured : nullptr;
+
+  // ---- 1. refused outright --------------------------------------------------------------
+  // (no chained finalisations, no developer timeline)
+  if (q.fused == 0 || !q.servable || q.chain || q.trace || q.n_gauss < 1) return three_kernels;
+  // (asynchronous host calls: one command per call in the lane's chain pays for any size from
+  // the lower bound on -- 20 000 draws 93.7 -> 82.6 us, 40 000 176 -> 162 us per call)
+  if (q.n_draws > q.fused_max_draws && !q.async && measured == nullptr && !invariant)
+    return three_kernels;
+  // cen-cen | two halves of cen-sat | sat-sat on the four waves of a 32-draw tile: both
+  // galaxy types present (equal numbers of bins, as a TabCorr table has them, balance the
+  // waves to within a block row); no likelihood of separated components
+  if (separate && (!q.by_type_complete || q.likelihood)) return three_kernels;
+  // (the decorated variants are compiled for the reference's default n_gauss_prim only)
+  if (!leauthaud && (assembias || modulate) && q.n_gauss != 10) return three_kernels;
+
+  // ---- what fits: every LDS footprint once ------------------------------------------------
+  const int rows = separate ? q.rows_by_type : q.rows_total;
+  const int lds_8x64 = fused_lds_bytes(rows, 8, 64);
+  const bool fits_8x64 = lds_8x64 <= 80 * 1024;
+  const bool fits_16x64 = fused_lds_bytes(rows, 16, 64) <= 160 * 1024;
+  const bool fits_8x32 = fused_lds_bytes(rows, 8, 32) <= 80 * 1024;
+  // Two workgroups of 8 waves per CU (up to 80 KB of LDS each: 104 bins) or not at all: larger
+  // tables fit ONE workgroup per CU, whose phases no neighbour covers.  With 8 waves the three
+  // kernels are then 8-13 % ahead, with 16 waves (eight parts of the units per tile, four waves
+  // per SIMD again) level -- tools/archive/r03_fused_waves.py, 10^4 draws, us per step, three kernels /
+  // 8 waves / 16 waves: G = 112 51.8 / 55.6 / 51.5, 128 64.2 / 69.2 / 64.3, 200 137.0 / 150.9 /
+  // 138.7, 240 189.6 / 215.0 / 192.3; G = 100: 43.5 / 39.4 / 43.2 -- so beyond 104 bins the
+  // one-launch form (16 waves, up to 160 KB: 248 bins) is taken only when forced --
+  // or when the table has been measured with THESE flags (option "autotune"): that choice then
+  // decides; a measurement with other flags says nothing about this LDS footprint.
+  // Waves per workgroup of 64 draws: 8, 16, or 0 (does not fit).
+  const int waves_64 =
+      q.fused_waves == 8 && lds_8x64 <= 160 * 1024 ? 8
+      : q.fused_waves == 16 && fits_16x64          ? 16
+      : fits_8x64                                  ? 8
+      : fits_16x64 && (q.fused >= 2 || q.measured != nullptr || invariant) ? 16
+                                                                            : 0;
+  // Workgroups of ONE 32-draw tile and eight waves (eight parts of the units; up to 80 KB of LDS,
+  // two per CU), Zheng07 family with the default n_gauss_prim.
+  // * Tables of 105-208 bins, whose 64-draw workgroup does not fit half a CU: any batch size
+  //   (`wide`).
+  // * Batches below 8192 draws of tables up to 104 bins (`half`): a workgroup lasts a quarter as
+  //   long as the 64-draw one and a batch has twice as many -- what batches need that do not fill
+  //   the chip's 512 places with four launches of 64-draw workgroups (tools/archive/r03_fused_half.py, us per
+  //   step, three kernels / 64 draws x 8 waves / 32 x 4 / 32 x 8: G = 100: 1024 draws 12.8 / 23.4 /
+  //   19.3 / 15.1, 2048 19.0 / 29.0 / 21.7 / 16.0, 4096 23.9 / 30.2 / 22.3 / 16.9, 6144 31.6 / 31.1 /
+  //   26.2 / 25.1, 10^4 43.5 / 39.4 / 41.0 / 41.4; G = 60: 1024 10.2 / 12.3 / 9.7 / 7.4, 4096 15.3 /
+  //   13.4 / 11.0 / 8.2, 6144 18.6 / 14.2 / 12.2 / 11.9, 10^4 21.5 / 17.7 / 19.0 / 19.5): once the
+  //   chip is full the 64-draw form's fixed costs per draw win by 4-7 %.
+  const bool wide = q.n_gauss == 10 && q.fused_draws != 64 && q.fused_waves == 0 && !fits_8x64 &&
+                    fits_8x32;
+  const int measured_form =
+      q.fused_draws == 0 && measured != nullptr ? measured->form_for(q.n_draws) : 0;
+  const bool half_fits = q.n_gauss == 10 && (q.fused_waves == 0 || q.fused_waves == 8) && fits_8x32;
+  const bool half =
+      // (option "deterministic" = 2: the shape must not depend on the batch size -- 64 draws per
+      // workgroup unless 32 are forced)
+      invariant            ? q.fused_draws == 32 && half_fits
+      : measured_form != 0 ? measured_form == 32 && fits_8x32      // (option "autotune")
+      : q.fused_draws != 0 ? q.fused_draws != 64 && half_fits
+      // (a call that has the chip to itself: up to one 32-draw workgroup per CU INCLUSIVE --
+      // 8192 draws on 256 CUs take 41.9 us this way, 49.5 in the latency form, 55 as three
+      // kernels)
+      : (q.n_draws < 8192 || (q.alone && q.n_draws <= (int64_t)32 * q.n_cus)) && half_fits;
+  // the throughput form this call would take, if it takes one
+  const FusedForm throughput = wide || half ? FusedForm{8, 32} : FusedForm{waves_64, 64};
+
+  // ---- 2. the latency form ----------------------------------------------------------------
+  // predict_fused_kernel with 40 draws per workgroup, one workgroup per CU, v_mfma_f64_4x4x4:
+  // for a call that has the chip to itself.  The 64-draw workgroups of the throughput form put
+  // 10^4 draws on 157 of the 256 CUs (71 us alone on the chip, 0.37 of the FP64 peak -- four
+  // such launches in flight are what fills it); 250 workgroups of 40 draws reach every CU.
+  // Undecorated Zheng07 with ten nodes, total correlation function (or its likelihood), bins
+  // evaluated one by one; batches of up to one workgroup per CU.
+  if (q.fused_spread != 0 && q.n_gauss == 10 && !invariant &&
+      !(separate || assembias || modulate || leauthaud) && !q.grouped &&
+      (q.fused_draws == 0 || q.fused_draws == 40) &&
+      fused_lds_bytes(rows, 8, 40) <= 160 * 1024) {
+    if (q.fused_draws == 40) return {8, 40};          // (forced: any batch)
+    // alone on the chip, between fused_spread_min and one workgroup per CU (the three kernels
+    // spread smaller batches over the chip in less than a 40-draw workgroup's lifetime)
+    // (up to 32 draws per CU the 32-draw workgroups are shorter-lived)
+    const bool shorter_lived = !q.sync_spread && half && q.n_draws <= (int64_t)32 * q.n_cus;
+    if ((q.alone || q.sync_spread) && !shorter_lived && q.n_draws >= q.fused_spread_min &&
+        q.n_draws <= (int64_t)40 * q.n_cus * std::max(1, q.fused_spread_rounds))
+      return {8, 40};
+  }
+  if (!wide && waves_64 == 0) return three_kernels;       // (no throughput form fits)
+
+  // ---- 3. invariant -----------------------------------------------------------------------
+  // option "deterministic" = 2: every call the form covers takes it, alone on its lane or not,
+  // one draw or a million (Leauthaud11 with modulate_with_cenocc included)
+  if (invariant) return throughput;
+
+  // ---- 4. measured choice -----------------------------------------------------------------
+  // a measured choice for this table and these flags (option "autotune") replaces the formula
+  // below for the calls it was measured on: pipelined device-pointer and asynchronous calls
+  if (measured != nullptr && !q.alone)
+    return measured->form_for(q.n_draws) != 0 ? throughput : three_kernels;
+
+  // Estimated duration of a workgroup alone on its CU (us): 5 + 10 (G / 100) (n_gauss / 10)
+  // [occupations] + 60 (units / 325) (U / 5) [matrix work]: 75 for BASELINE configs[1]'s table,
+  // 33 for the reference's example table (G = 60), 27 for G = 100 with three r values.
+  const int64_t units = separate ? q.units_by_type : q.units_total;
+  const double estimate = (5.0 + 10.0 * (q.n_bins / 100.0) * (q.n_gauss / 10.0) +
+                           60.0 * ((double)units / 325.0) * (q.n_u / 5.0)) *
+                          8.0 / (wide ? 16 : waves_64);
+  // Leauthaud11 (a Newton inverse of the stellar-to-halo mass relation per central node: the
+  // occupations outweigh the matrix work and spread better over the chip as a kernel of their
+  // own): tools/archive/r03_fused_leauthaud.py, us per step, three kernels / one launch of 64-draw
+  // workgroups: G = 100: 4000 draws 57.3 / 88.7, 10^4 126.0 / 114.5; G = 60: 4000 38.4 / 49.9,
+  // 10^4 73.0 / 65.2 (32-draw workgroups below 8192 draws: further down); with
+  // modulate_with_cenocc (the inverse at the satellites' nodes too) never clearly ahead: 10^4
+  // draws 183.4 / 188.1 and 106.0 / 106.0, 4000 draws in 32-draw workgroups 80.2 / 80.6 and
+  // 51.5 / 45.9 -- only when forced.
+  if (leauthaud && modulate && q.fused < 2) return three_kernels;
+
+  // ---- 5. alone on the chip ---------------------------------------------------------------
+  // calls that run alone on their lane (host-buffer API, one lane, pipeline off); option
+  // "fused_min_draws" does not apply to them
+  if (q.alone && q.fused < 2) {
+    // A call that has the chip to itself (round 6).  The three kernels spread any batch over
+    // the whole chip -- on BASELINE configs[1]'s table 26 us for 1024 draws, 66 us for 10^4:
+    // ~22 us + 4.4 us per 1000 draws, scaled with the table's work per draw --, a one-launch
+    // form lasts as long as ONE workgroup whatever the batch (0.56 / 0.95 of the estimate for
+    // 32 / 64 draws: 42 and 71 us there) for as long as one round of workgroups covers it:
+    // 32-draw workgroups up to 32 draws per CU, 64-draw ones from 40 to 64 draws per CU
+    // (in between: the latency form above; tools/r06_latency.py: 4096 draws 36.8 / 41.7,
+    // 6144: 46.0 / 41.8, 8192: 55.5 / 41.8; 12288: 73.9 / 71.5, 16384: 90.7 / 71.7 us).
+    // (Leauthaud11: its occupations spread better as a kernel of their own; measured from 1024
+    // draws on: below, both ways are a few launches' worth of latency)
+    if (leauthaud || q.n_draws < 2048 || q.fused_draws != 0 || wide) return three_kernels;
+    const double three = 22.0 + 0.0044 * (double)q.n_draws * estimate / 75.0;
+    const bool one_round_of_32 = half && q.n_draws <= (int64_t)32 * q.n_cus;
+    const bool one_round_of_64 = waves_64 == 8 && q.n_draws > (int64_t)40 * q.n_cus &&
+                                 q.n_draws <= (int64_t)64 * q.n_cus;
+    return one_round_of_32   ? (0.56 * estimate < three ? throughput : three_kernels)
+           : one_round_of_64 ? (0.95 * estimate < three ? throughput : three_kernels)
+                             : three_kernels;
+  }
+
+  // ---- 6. smallest batch ------------------------------------------------------------------
+  // A launch lasts as long as one workgroup does, whatever the batch, so the one-launch form
+  // pays from the batch size on at which four lanes of such launches beat the three kernels
+  // (which spread any batch over the whole chip).  Measured crossovers
+  // (tools/archive/r03_fused_scan.py with N_PRIM / N_R): estimates up to 28 us win from 512 draws on
+  // (G = 40: 5.8 against 11.0 us per call at 512 draws; G = 100 with three r values: 8.5 /
+  // 12.0), longer workgroups from ~90 draws per estimated microsecond (G = 60: 3000-4000;
+  // G = 100, R = 8: 4096; G = 80: 5000; G = 100, R = 19: 6500-7000) -- below that both forms
+  // are bound by the host thread that queues them (10-13 us per call) and differ by noise.
+  // Wide tables (eight waves x 32 draws; tools/archive/r03_fused_wide.py, us per step, three kernels /
+  // one launch: G = 112: 1024 draws 14.9 / 18.6, 2048 21.4 / 19.1, 4096 27.2 / 20.3, 10^4 52.3 /
+  // 50.2, 20 000 98.6 / 99.0; G = 200: 2048 38.6 / 49.1, 4096 61.2 / 54.6, 6144 90.1 / 81.6,
+  // 10^4 137.3 / 134.8; separated + assembly bias: 4096 66.5 / 57.0, 10^4 146.9 / 140.8): from
+  // 15 draws per bin on.
+  const int64_t min_draws = q.fused_min_draws > 0 ? q.fused_min_draws
+                            : wide                ? 15 * (int64_t)q.n_bins
+                            // (Leauthaud11 in 32-draw workgroups, tools/archive/r03_fused_leauthaud.py,
+                            // three kernels / one launch: G = 60: 2000 draws 20.7 / 25.6, 4000
+                            // 37.4 / 28.7; G = 100: 2000 33.9 / 39.6, 4000 56.5 / 50.3)
+                            : leauthaud && half   ? 3000
+                            : half
+                                // (tools/archive/r03_fused_low.py, us per step, three kernels / one
+                                // launch: a step of small batches costs a fifth of the
+                                // estimate -- G = 40: 256 draws 14.0 / 5.6; G = 60: 256 8.7 /
+                                // 5.5, 1024 8.6 / 7.6; G = 100, R = 3: 256 13.4 / 6.3; G = 100,
+                                // R = 19: 1024 15.0 / 15.4, 1280 16.3 / 15.6, 2048 19.3 / 16.4)
+                                ? (estimate <= 50.0 ? 256 : 12 * (int64_t)q.n_bins)
+                            : leauthaud           ? 8192
+                            : estimate <= 28.0    ? 512
+                                                  : (int64_t)(90.0 * estimate);
+  return q.n_draws < min_draws ? three_kernels : throughput;
 }
 
 void fill_quad_table(const QuadLayout& layout, const std::vector<int32_t>& perm, int n_r,

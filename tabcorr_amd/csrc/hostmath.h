@@ -259,6 +259,81 @@ struct QuadTiling {
 };
 QuadTiling quad_tiling(int n_r);
 
+// ---- one launch per batch (predict_fused_kernel, mode auto): which calls take it ------------
+
+// Measured choice of the form a batch takes (option "autotune"; table.cpp: autotune): for a
+// grid of batch sizes the fastest of {three kernels, one launch with 64-draw workgroups, one
+// launch with 32-draw workgroups} in the pipelined regime, per combination of predict flags.
+// choose_fused_form asks it before its formula.
+struct AutoChoice {
+  static constexpr int kSizes = 9;
+  // batch sizes measured (geometric: a batch takes the choice of the nearest one)
+  static constexpr int64_t size(int i) { return (int64_t)256 << i; }      // 256 .. 65536
+  int form[kSizes] = {};         // 0 three kernels, 32 / 64 draws per workgroup of one launch
+  float us[kSizes][3] = {};      // measured us per call: three kernels, 64 draws, 32 draws
+  // The form for a batch of n draws: every form's time interpolated linearly between the two
+  // measured sizes around n (a form that is missing at either end is out; beyond the grid the
+  // nearest end decides), the fastest wins, a one-launch form only by 2 %.
+  int form_for(int64_t n_draws) const {
+    if (n_draws <= size(0)) return form[0];
+    if (n_draws >= size(kSizes - 1)) return form[kSizes - 1];
+    int i = 0;
+    while (size(i + 1) < n_draws) ++i;
+    const double w = (double)(n_draws - size(i)) / (double)(size(i + 1) - size(i));
+    static const int shape[3] = {0, 64, 32};
+    int best = 0;
+    double best_us = (1.0 - w) * us[i][0] + w * us[i + 1][0];
+    for (int k = 1; k < 3; ++k) {
+      if (us[i][k] <= 0.0f || us[i + 1][k] <= 0.0f) continue;
+      const double value = (1.0 - w) * us[i][k] + w * us[i + 1][k];
+      if (value < (best == 0 ? 0.98 : 1.0) * best_us) {
+        best_us = value;
+        best = shape[k];
+      }
+    }
+    return best;
+  }
+};
+
+// Rows of the kernel's LDS density array for a layout: whole blocks of four covering every row
+// a component reads; and the dynamic LDS of a workgroup of `waves` waves and `draws` draws.
+int fused_dens_rows(const QuadLayout& layout);
+int fused_lds_bytes(int dens_rows, int waves, int draws);
+
+// Everything the decision reads (launch.hip: fused_query fills it from a handle, nothing else
+// reads the handle for it; tc_debug_fused_form from plain numbers).
+struct FusedQuery {
+  // the table
+  int n_bins = 0, n_u = 0, n_cus = 256;   // (n_u: r sub-tiles of 4)
+  bool grouped = false;         // bins share their nodes (the GROUPED instances)
+  // what every one-launch form of mode auto needs: the float64 quadratic-form layout of the
+  // whole triangle as one component, one r tile, at most 20 r values
+  bool servable = false;
+  int64_t units_total = 0, units_by_type = 0;     // units of the two layouts
+  int rows_total = 0, rows_by_type = 0;           // ... and their fused_dens_rows
+  bool by_type_complete = false;   // the by-type layout is there with three non-empty components
+  // the call
+  int64_t n_draws = 0;
+  int n_gauss = 0;
+  unsigned flags = 0;           // TC_FLAG_*
+  bool alone = false;           // alone on its lane: host-buffer API, one lane, pipeline off
+  bool async = false;           // asynchronous host call (the chunks of a synchronous one too)
+  bool sync_spread = false;     // a chunk of a synchronous call that fits one round of 40-draw workgroups
+  bool chain = false, trace = false;   // chained finalisations; developer timeline
+  bool likelihood = false;      // the call asks for the fused likelihood
+  // options (internal.h: Tuning)
+  int fused = 1, fused_min_draws = 0, fused_max_draws = 30720, fused_waves = 0, fused_draws = 0;
+  int fused_spread = 1, fused_spread_min = 8192, fused_spread_rounds = 1, deterministic = 0;
+  const AutoChoice* measured = nullptr;   // option "autotune" for these flags, or none
+};
+
+// Waves per workgroup and draws per workgroup: 8 x 64, 16 x 64, 8 x 32, or 8 x 40 (the latency
+// form); waves == 0: the three kernels.
+struct FusedForm {
+  int waves = 0, draws = 0;
+};
+FusedForm choose_fused_form(const FusedQuery& query);
+
 // The re-laid-out matrix of a layout: (n_rtiles, n_units, (n_u + 1) / 2, 64 lanes, 2)
 // doubles with the pair prefactor folded in; `matrix` is the reference's (n_r, n_pairs)
 // tpcf_matrix in float64 or float32, `perm` the library's bin order.

@@ -371,14 +371,15 @@ struct Tuning {
                                 // one launch / three kernels: 256 draws 15.7 / 20.6, 1024 20.6 /
                                 // 26.0, 4096 35.1 / 68.1, 10^4 79.6 / 164.6)
   int fused = 1;
-  int fused_min_draws = 0;      // 0: chosen per table (launch.hip: fused_eligible)
+  int fused_min_draws = 0;      // 0: chosen per table (hostmath.cpp: choose_fused_form)
   int fused_max_draws = 30720;
   int fused_waves = 0;          // 0: 8 where two workgroups fit a CU, else 16; 8 / 16: forced
   int fused_draws = 0;          // draws per workgroup of the one-launch form: 0 = 32 for batches
                                 // below 8192 draws where that form applies, else 64
-                                // (launch.hip: fused_half_tiles); 32 / 64: forced
+                                // (hostmath.cpp: choose_fused_form); 32 / 64: forced; 40: the
+                                // latency form for every batch it serves
   // the latency form of the one-launch kernel (40 draws per workgroup, one workgroup per CU:
-  // launch.hip: fused_spread_eligible) for calls that run alone: 1 on; smallest batch; largest
+  // hostmath.cpp: choose_fused_form) for calls that run alone: 1 on; smallest batch; largest
   // batch in rounds of one workgroup per CU
   int fused_spread = 1, fused_spread_min = 8192, fused_spread_rounds = 1;
   int prio_fused = 1, prio_fused_occ = 2, prio_fused_out = 3;   // phases 2, 1, 3
@@ -424,39 +425,7 @@ struct Tuning {
 }  // namespace host
 }  // namespace tc
 
-// Measured choice of the form a batch takes (option "autotune"; table.cpp: autotune): for a
-// grid of batch sizes the fastest of {three kernels, one launch with 64-draw workgroups, one
-// launch with 32-draw workgroups} in the pipelined regime, per combination of predict flags.
-// launch.hip: fused_eligible / fused_half_tiles ask it before their formula.
-struct AutoChoice {
-  static constexpr int kSizes = 9;
-  // batch sizes measured (geometric: a batch takes the choice of the nearest one)
-  static constexpr int64_t size(int i) { return (int64_t)256 << i; }      // 256 .. 65536
-  int form[kSizes] = {};         // 0 three kernels, 32 / 64 draws per workgroup of one launch
-  float us[kSizes][3] = {};      // measured us per call: three kernels, 64 draws, 32 draws
-  // The form for a batch of n draws: every form's time interpolated linearly between the two
-  // measured sizes around n (a form that is missing at either end is out; beyond the grid the
-  // nearest end decides), the fastest wins, a one-launch form only by 2 %.
-  int form_for(int64_t n_draws) const {
-    if (n_draws <= size(0)) return form[0];
-    if (n_draws >= size(kSizes - 1)) return form[kSizes - 1];
-    int i = 0;
-    while (size(i + 1) < n_draws) ++i;
-    const double w = (double)(n_draws - size(i)) / (double)(size(i + 1) - size(i));
-    static const int shape[3] = {0, 64, 32};
-    int best = 0;
-    double best_us = (1.0 - w) * us[i][0] + w * us[i + 1][0];
-    for (int k = 1; k < 3; ++k) {
-      if (us[i][k] <= 0.0f || us[i + 1][k] <= 0.0f) continue;
-      const double value = (1.0 - w) * us[i][k] + w * us[i + 1][k];
-      if (value < (best == 0 ? 0.98 : 1.0) * best_us) {
-        best_us = value;
-        best = shape[k];
-      }
-    }
-    return best;
-  }
-};
+using tc::AutoChoice;      // (hostmath.h)
 
 struct tc_table {
   int device = 0;
@@ -510,7 +479,7 @@ struct tc_table {
   std::vector<hipEvent_t> chunk_events;    // ... between the chunks of a call with large results
   // ... and that the chunks of such a call have the chip to themselves: where the latency form
   // of the one-launch kernel serves the table, every chunk takes it when all chunks together
-  // have at most one workgroup of 40 draws per CU (launch.hip: fused_spread_eligible)
+  // have at most one workgroup of 40 draws per CU (hostmath.cpp: choose_fused_form)
   bool sync_spread = false;
   bool quad = false;
   tc::QuadTiling quad_tiling;
@@ -683,22 +652,19 @@ int run_occupation(tc_table* t, const double* theta_device, int n_theta, int64_t
 // Contraction + finalisation of draws whose densities are already in the current lane.
 int run_contraction(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
                     double* ngal_device, double* xi_device);
-// One launch per slab (predict_fused_kernel) for the calls it covers; ngal and xi (or the
-// likelihood, t->fuse_chi2_out) as run_contraction leaves them.
-bool fused_eligible(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags);
+// Alone on its lane: host-buffer entry points, a handle with one lane, option "pipeline" off.
+bool runs_alone(const tc_table* t);
+// One launch per slab (predict_fused_kernel) for the calls it covers: what hostmath.h:
+// choose_fused_form reads about a call, filled from the handle; the launch in the form it
+// returned -- ngal and xi (or the likelihood, t->fuse_chi2_out) as run_contraction leaves them.
+tc::FusedQuery fused_query(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags);
+int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n_theta,
+              int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
+              double* xi_device);
 // Option "deterministic" = 2: is there a one-launch form for this table and these flags (whose
 // bits do not depend on the batch)?  Every entry point then takes it for every batch size.
 bool batch_invariant_form(tc_table* t, int n_gauss, unsigned flags);
-int fused_dens_rows(const tc_table* t, bool separate);
-int fused_lds_bytes(const tc_table* t, bool separate, int waves, int draws);
-int fused_waves(const tc_table* t, bool separate, unsigned flags);
 int series_mask(const tc_table* t);
-bool fused_half_tiles(const tc_table* t, bool separate, int64_t n_draws, int n_gauss,
-                      unsigned flags);
-bool fused_wide_tables(const tc_table* t, bool separate, int n_gauss, unsigned flags);
-bool fused_spread_eligible(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags);
-int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_draws, int n_gauss,
-              unsigned flags, double* ngal_device, double* xi_device);
 int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                        int n_gauss, unsigned flags);
 // Gradients (grad_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels do

@@ -319,6 +319,16 @@ struct FinalizeQuadArgs {
 // over through memory.  Mode auto, total correlation function, one r tile.
 constexpr int kFusedWaves = 8;       // (default; 16 where one workgroup per CU is all that fits)
 constexpr int kFusedMaxParts = 8;    // parts of the units per 32-draw tile: waves / 2
+constexpr int kMathTableDoubles = 2306;        // = fm::kTableDoubles (fastmath.h)
+// Doubles of a workgroup's dynamic LDS besides the densities (hostmath.h: fused_lds_bytes adds
+// them up; W waves per workgroup: 8 = two 32-draw tiles x four parts of the units, two
+// workgroups per CU; 16 = eight parts per tile, one workgroup with up to 160 KB of LDS per CU)
+constexpr int fused_slot_doubles(int waves, int draws = 64) {
+  // (the waves' sums: per wave 4 U rows of one 32-draw tile, or -- 40 draws per workgroup --
+  // of all its draws)
+  return waves * 4 * kQuadMaxU * (draws == 40 ? 40 : kQuadTile);
+}
+constexpr int fused_scratch_doubles(int waves) { return kMathTableDoubles + 2 * waves * kLanes; }
 
 struct FusedArgs {
   const double* theta;       // (n_draws, n_theta)
@@ -378,7 +388,7 @@ constexpr int kCrossMaxRows = 128;   // K (R + 1) of the largest instance (16 ro
 // spline weights / norms (K, 64) and the results tile (rows out, 65) when they fit there | two
 // chunk buffers (kCrossChunkBins, 64), later the row sums (ROWS, 64) | separated by galaxy
 // type: the row sums of the centrals (ROWS, 64) | the tile when it does not fit the first part
-constexpr int kCrossTableDoubles = 2306;       // = fm::kTableDoubles (fastmath.h)
+constexpr int kCrossTableDoubles = kMathTableDoubles;
 // predict_cross_small_kernel (up to 16 rows, the sums in every wave's registers): math table |
 // stage (waves, 8 rows, 64): the waves' sums of half the rows, later the spline weights and the
 // results tile | sums (components, 16, 64)

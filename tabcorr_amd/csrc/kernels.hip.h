@@ -2227,11 +2227,7 @@ __global__ __launch_bounds__(1024) void finalize_quad_kernel(FinalizeQuadArgs a)
 // (W waves per workgroup: 8 = two 32-draw tiles x four parts of the units, two workgroups per
 // CU; 16 = eight parts per tile, one workgroup with up to 160 KB of LDS per CU -- tables of
 // more than 104 bins)
-constexpr int fused_slot_doubles(int waves, int draws = 64) {
-  // (the waves' sums: per wave 4 U rows of one 32-draw tile, or -- 40 draws per workgroup --
-  // of all its draws)
-  return waves * 4 * kQuadMaxU * (draws == 40 ? 40 : kQuadTile);
-}
+// (LDS besides the densities: kernel_args.h: fused_slot_doubles, fused_scratch_doubles)
 // 40 draws per workgroup (the latency form, below): where draw d of bin row `row` lies in the
 // LDS density array -- the ten draws d = 4 dg + j of one j side by side, so that a lane of
 // v_mfma_f64_4x4x4 (which wants dens[k][4 dg + j] for every dg) reads them as five 16-byte
@@ -2240,7 +2236,7 @@ constexpr int fused_slot_doubles(int waves, int draws = 64) {
 __device__ __forceinline__ constexpr int dens40(int row, int draw) {
   return row * 40 + (draw & 3) * 10 + (draw >> 2);
 }
-constexpr int fused_scratch_doubles(int waves) { return fm::kTableDoubles + 2 * waves * kLanes; }
+static_assert(fm::kTableDoubles == kMathTableDoubles, "kernel_args.h");
 static_assert(kFusedWaves == 8 && kFusedMaxParts == 8, "8 or 16 waves: 4 or 8 parts per tile");
 static_assert(20 * (kLanes + 1) + 20 * 21 <= fm::kTableDoubles,
               "results tile + likelihood data in the place of the math table");

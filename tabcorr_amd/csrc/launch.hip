@@ -818,7 +818,7 @@ int run_occupation(tc_table* t, const double* theta_device, int n_theta,
         // that run alone on their lane (host-buffer API, pipeline off) wait for this kernel:
         // twice as many, shorter items (10^4 draws: 25 -> 20 us, host-to-host 158 -> 149 us;
         // in the pipeline they cost 0.7 us per step)
-        const bool alone = t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
+        const bool alone = runs_alone(t);
         splits = trial;
         grid_blocks = (int)std::min<int64_t>(items, slots);
         if (items >= (alone ? 2 : 1) * (int64_t)n_cus) break;
@@ -891,133 +891,52 @@ int run_occupation(tc_table* t, const double* theta_device, int n_theta,
   return launch_occupation(oa, flags, n_gauss, grouped, grid_blocks, stream);
 }
 
-// One launch per slab of draws (predict_fused_kernel): float64 quadratic form with one r tile,
-// densities of 64 draws within the LDS.
-bool fused_eligible(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags) {
-  // (asynchronous host calls: one command per call in the lane's chain pays for any size from
-  // the lower bound on -- 20 000 draws 93.7 -> 82.6 us, 40 000 176 -> 162 us per call)
-  if (t->tuning.fused == 0) return false;
-  // (a measured choice -- option "autotune" -- knows where the one-launch form stops paying)
-  const bool tuned_flags = n_gauss == 10 && t->tuning.fused == 1 &&
-                           t->tuning.fused_min_draws == 0 && t->autotuned.count(flags) != 0;
-  const bool invariant = t->tuning.deterministic >= 2;     // (one form whatever the batch)
-  if (n_draws > t->tuning.fused_max_draws && t->async_lane < 0 && !tuned_flags && !invariant)
-    return false;
-  if (!t->quad || t->compute_dtype != TC_DTYPE_F64 || t->quad_total.d_table == nullptr)
-    return false;
-  if (t->quad_tiling.n_rtiles != 1 || t->n_r > 20 || t->chain || t->tuning.trace) return false;
-  const bool leauthaud = (flags & TC_FLAG_LEAUTHAUD11) != 0;
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  if (separate) {
-    // cen-cen | two halves of cen-sat | sat-sat on the four waves of a 32-draw tile: both
-    // galaxy types present (equal numbers of bins, as a TabCorr table has them, balance the
-    // waves to within a block row); no likelihood of separated components
-    const tc::QuadLayout& layout = t->quad_by_type.layout;
-    if (t->quad_by_type.d_table == nullptr || layout.comps.size() != 3 ||
-        t->fuse_chi2_out != nullptr)
-      return false;
-    for (const tc::QuadComp& comp : layout.comps)
-      if (comp.n_units <= 0) return false;
-  }
-  // (the decorated variants are compiled for the reference's default n_gauss_prim only)
-  if (!leauthaud && (flags & (TC_FLAG_ASSEMBIAS | TC_FLAG_MODULATE_WITH_CENOCC)) && n_gauss != 10)
-    return false;
-  if (t->quad_total.layout.comps.size() != 1 || !t->quad_total.layout.comps[0].triangular)
-    return false;
-  // Two workgroups of 8 waves per CU (up to 80 KB of LDS each: 104 bins) or not at all: larger
-  // tables fit ONE workgroup per CU, whose phases no neighbour covers.  With 8 waves the three
-  // kernels are then 8-13 % ahead, with 16 waves (eight parts of the units per tile, four waves
-  // per SIMD again) level -- tools/archive/r03_fused_waves.py, 10^4 draws, us per step, three kernels /
-  // 8 waves / 16 waves: G = 112 51.8 / 55.6 / 51.5, 128 64.2 / 69.2 / 64.3, 200 137.0 / 150.9 /
-  // 138.7, 240 189.6 / 215.0 / 192.3; G = 100: 43.5 / 39.4 / 43.2 -- so beyond 104 bins the
-  // one-launch form (16 waves, up to 160 KB: 248 bins) is taken only when forced.
-  // the latency form for calls that have the chip to themselves (fused_spread_eligible)
-  if (!invariant && fused_spread_eligible(t, n_draws, n_gauss, flags)) return true;
-  const bool wide = fused_wide_tables(t, separate, n_gauss, flags);
-  if (n_gauss < 1 || (!wide && fused_waves(t, separate, flags) == 0)) return false;
-  // option "deterministic" = 2: every call the form covers takes it, alone on its lane or not,
-  // one draw or a million (Leauthaud11 with modulate_with_cenocc included)
-  if (invariant) return true;
-  // a measured choice for this table and these flags (option "autotune") replaces the formula
-  // below for the calls it was measured on: pipelined device-pointer and asynchronous calls
-  if (n_gauss == 10 && t->tuning.fused == 1 && t->tuning.fused_min_draws == 0) {
-    auto tuned = t->autotuned.find(flags);
-    const bool alone = t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
-    if (tuned != t->autotuned.end() && !alone) return tuned->second.form_for(n_draws) != 0;
-  }
-  // Smallest batch: a launch lasts as long as one workgroup does, whatever the batch, so the
-  // one-launch form pays from the batch size on at which four lanes of such launches beat the
-  // three kernels (which spread any batch over the whole chip).  Estimated duration of a
-  // workgroup alone on its CU (us): 5 + 10 (G / 100) (n_gauss / 10) [occupations] + 60 (units /
-  // 325) (U / 5) [matrix work]: 75 for BASELINE configs[1]'s table, 33 for the reference's
-  // example table (G = 60), 27 for G = 100 with three r values.  Measured crossovers
-  // (tools/archive/r03_fused_scan.py with N_PRIM / N_R): estimates up to 28 us win from 512 draws on
-  // (G = 40: 5.8 against 11.0 us per call at 512 draws; G = 100 with three r values: 8.5 /
-  // 12.0), longer workgroups from ~90 draws per estimated microsecond (G = 60: 3000-4000;
-  // G = 100, R = 8: 4096; G = 80: 5000; G = 100, R = 19: 6500-7000) -- below that both forms
-  // are bound by the host thread that queues them (10-13 us per call) and differ by noise.
-  // calls that run alone on their lane (host-buffer API, one lane, pipeline off)
-  const bool alone = t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
-  {
-    const tc::QuadLayout& layout = separate ? t->quad_by_type.layout : t->quad_total.layout;
-    const double estimate = (5.0 + 10.0 * (t->n_bins / 100.0) * (n_gauss / 10.0) +
-                             60.0 * ((double)layout.n_units / 325.0) * (t->quad_tiling.n_u / 5.0)) *
-                            8.0 / (wide ? 16 : fused_waves(t, separate, flags));
-    // Leauthaud11 (a Newton inverse of the stellar-to-halo mass relation per central node: the
-    // occupations outweigh the matrix work and spread better over the chip as a kernel of their
-    // own): tools/archive/r03_fused_leauthaud.py, us per step, three kernels / one launch of 64-draw
-    // workgroups: G = 100: 4000 draws 57.3 / 88.7, 10^4 126.0 / 114.5; G = 60: 4000 38.4 / 49.9,
-    // 10^4 73.0 / 65.2 (32-draw workgroups below 8192 draws: further down); with
-    // modulate_with_cenocc (the inverse at the satellites' nodes too) never clearly ahead: 10^4
-    // draws 183.4 / 188.1 and 106.0 / 106.0, 4000 draws in 32-draw workgroups 80.2 / 80.6 and
-    // 51.5 / 45.9 -- only when forced.
-    if (leauthaud && (flags & TC_FLAG_MODULATE_WITH_CENOCC) && t->tuning.fused < 2) return false;
-    // Wide tables (eight waves x 32 draws; tools/archive/r03_fused_wide.py, us per step, three kernels /
-    // one launch: G = 112: 1024 draws 14.9 / 18.6, 2048 21.4 / 19.1, 4096 27.2 / 20.3, 10^4 52.3 /
-    // 50.2, 20 000 98.6 / 99.0; G = 200: 2048 38.6 / 49.1, 4096 61.2 / 54.6, 6144 90.1 / 81.6,
-    // 10^4 137.3 / 134.8; separated + assembly bias: 4096 66.5 / 57.0, 10^4 146.9 / 140.8): from
-    // 15 draws per bin on.
-    const int64_t min_draws = t->tuning.fused_min_draws > 0 ? t->tuning.fused_min_draws
-                              : wide                        ? 15 * (int64_t)t->n_bins
-                              // (Leauthaud11 in 32-draw workgroups, tools/archive/r03_fused_leauthaud.py,
-                              // three kernels / one launch: G = 60: 2000 draws 20.7 / 25.6, 4000
-                              // 37.4 / 28.7; G = 100: 2000 33.9 / 39.6, 4000 56.5 / 50.3)
-                              : leauthaud && fused_half_tiles(t, separate, n_draws, n_gauss, flags)
-                                  ? 3000
-                              : fused_half_tiles(t, separate, n_draws, n_gauss, flags)
-                                  // (tools/archive/r03_fused_low.py, us per step, three kernels / one
-                                  // launch: a step of small batches costs a fifth of the
-                                  // estimate -- G = 40: 256 draws 14.0 / 5.6; G = 60: 256 8.7 /
-                                  // 5.5, 1024 8.6 / 7.6; G = 100, R = 3: 256 13.4 / 6.3; G = 100,
-                                  // R = 19: 1024 15.0 / 15.4, 1280 16.3 / 15.6, 2048 19.3 / 16.4)
-                                  ? (estimate <= 50.0 ? 256 : 12 * (int64_t)t->n_bins)
-                              : leauthaud                   ? 8192
-                              : estimate <= 28.0            ? 512
-                                                            : (int64_t)(90.0 * estimate);
-    if (alone && t->tuning.fused < 2) {
-      // A call that has the chip to itself (round 6).  The three kernels spread any batch over
-      // the whole chip -- on BASELINE configs[1]'s table 26 us for 1024 draws, 66 us for 10^4:
-      // ~22 us + 4.4 us per 1000 draws, scaled with the table's work per draw --, a one-launch
-      // form lasts as long as ONE workgroup whatever the batch (0.56 / 0.95 of the estimate for
-      // 32 / 64 draws: 42 and 71 us there) for as long as one round of workgroups covers it:
-      // 32-draw workgroups up to 32 draws per CU, 64-draw ones from 40 to 64 draws per CU
-      // (in between: the latency form above; tools/r06_latency.py: 4096 draws 36.8 / 41.7,
-      // 6144: 46.0 / 41.8, 8192: 55.5 / 41.8; 12288: 73.9 / 71.5, 16384: 90.7 / 71.7 us).
-      if (leauthaud) return false;      // (its occupations spread better as a kernel of their own)
-      // (measured from 1024 draws on; below, both ways are a few launches' worth of latency)
-      if (n_draws < 2048) return false;
-      const double three = 22.0 + 0.0044 * (double)n_draws * estimate / 75.0;
-      if (n_draws <= (int64_t)32 * t->n_cus && t->tuning.fused_draws == 0 && !wide &&
-          fused_half_tiles(t, separate, n_draws, n_gauss, flags))
-        return 0.56 * estimate < three;
-      if (n_draws > (int64_t)40 * t->n_cus && n_draws <= (int64_t)64 * t->n_cus && !wide &&
-          t->tuning.fused_draws == 0 && fused_waves(t, separate, flags) == 8)
-        return 0.95 * estimate < three;
-      return false;
-    }
-    if (n_draws < min_draws) return false;
-  }
-  return true;
+// Alone on its lane: host-buffer entry points, a handle with one lane, option "pipeline" off.
+bool runs_alone(const tc_table* t) {
+  return t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
+}
+
+// Everything hostmath.h: choose_fused_form reads about a call of n_draws on this handle -- the
+// one place that reads the handle for it (no allocation: every un-batched call with option
+// "deterministic" = 2 comes through here).
+tc::FusedQuery fused_query(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags) {
+  const tc::QuadLayout& total = t->quad_total.layout;
+  const tc::QuadLayout& by_type = t->quad_by_type.layout;
+  tc::FusedQuery q;
+  q.n_bins = t->n_bins;
+  q.n_u = t->quad_tiling.n_u;
+  q.n_cus = t->n_cus;
+  q.grouped = t->grouped;
+  q.servable = t->quad && t->compute_dtype == TC_DTYPE_F64 && t->quad_total.d_table != nullptr &&
+               t->quad_tiling.n_rtiles == 1 && t->n_r <= 20 && total.comps.size() == 1 &&
+               total.comps[0].triangular;
+  q.units_total = total.n_units;
+  q.units_by_type = by_type.n_units;
+  q.rows_total = tc::fused_dens_rows(total);
+  q.rows_by_type = tc::fused_dens_rows(by_type);
+  q.by_type_complete = t->quad_by_type.d_table != nullptr && by_type.comps.size() == 3;
+  for (const tc::QuadComp& comp : by_type.comps) q.by_type_complete &= comp.n_units > 0;
+  q.n_draws = n_draws;
+  q.n_gauss = n_gauss;
+  q.flags = flags;
+  q.alone = runs_alone(t);
+  q.async = t->async_lane >= 0;
+  q.sync_spread = t->sync_spread;
+  q.chain = t->chain;
+  q.trace = t->tuning.trace != 0;
+  q.likelihood = t->fuse_chi2_out != nullptr;
+  q.fused = t->tuning.fused;
+  q.fused_min_draws = t->tuning.fused_min_draws;
+  q.fused_max_draws = t->tuning.fused_max_draws;
+  q.fused_waves = t->tuning.fused_waves;
+  q.fused_draws = t->tuning.fused_draws;
+  q.fused_spread = t->tuning.fused_spread;
+  q.fused_spread_min = t->tuning.fused_spread_min;
+  q.fused_spread_rounds = t->tuning.fused_spread_rounds;
+  q.deterministic = t->tuning.deterministic;
+  auto measured = t->autotuned.find(flags);
+  q.measured = measured != t->autotuned.end() ? &measured->second : nullptr;
+  return q;
 }
 
 bool batch_invariant_form(tc_table* t, int n_gauss, unsigned flags) {
@@ -1029,118 +948,13 @@ bool batch_invariant_form(tc_table* t, int n_gauss, unsigned flags) {
         *choose_cross_fused(&self, 1, &t->cross_fused, &t->cross_fused_wide, 1, flags, &status);
     return status == TC_OK && cross_fused_eligible(t, cf, 1, n_gauss, flags, true);
   }
-  return fused_eligible(t, 1, n_gauss, flags);
+  return tc::choose_fused_form(fused_query(t, 1, n_gauss, flags)).waves != 0;
 }
 
-// Rows of the LDS density array: whole blocks of four covering every row a component reads.
-int fused_dens_rows(const tc_table* t, bool separate) {
-  if (!separate) return 4 * t->quad_total.layout.comps[0].n_rb;
-  int rows = 0;
-  for (const tc::QuadComp& comp : t->quad_by_type.layout.comps)
-    rows = std::max(rows, std::max(comp.i_bin0 + 4 * comp.n_rb, comp.j_bin0 + 4 * comp.n_cb));
-  return (rows + 3) / 4 * 4;
-}
 
-int fused_lds_bytes(const tc_table* t, bool separate, int waves, int draws) {
-  const int dens_rows = fused_dens_rows(t, separate);
-  return (std::max(dens_rows * draws, tc::fused_slot_doubles(waves, draws)) +
-          tc::fused_scratch_doubles(waves)) * 8;
-}
-
-// The latency form (predict_fused_kernel with 40 draws per workgroup, one workgroup per CU,
-// v_mfma_f64_4x4x4): for a call that has the chip to itself.  The 64-draw workgroups of the
-// throughput form put 10^4 draws on 157 of the 256 CUs (71 us alone on the chip, 0.37 of the
-// FP64 peak -- four such launches in flight are what fills it); 250 workgroups of 40 draws reach
-// every CU.  Undecorated Zheng07 with ten nodes, total correlation function (or its likelihood),
-// bins evaluated one by one; batches of up to one workgroup per CU.
-bool fused_spread_eligible(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags) {
-  if (t->tuning.fused_spread == 0 || n_gauss != 10 || t->tuning.deterministic >= 2) return false;
-  // (what every one-launch form of mode auto needs: the float64 quadratic-form layout of the
-  // whole triangle, one r tile, no chained finalisations, no developer timeline)
-  if (t->tuning.fused == 0 || !t->quad || t->compute_dtype != TC_DTYPE_F64 ||
-      t->quad_total.d_table == nullptr || t->quad_tiling.n_rtiles != 1 || t->n_r > 20 ||
-      t->chain || t->tuning.trace || t->quad_total.layout.comps.size() != 1 ||
-      !t->quad_total.layout.comps[0].triangular)
-    return false;
-  if (flags & (TC_FLAG_SEPARATE_GAL_TYPE | TC_FLAG_ASSEMBIAS | TC_FLAG_MODULATE_WITH_CENOCC |
-               TC_FLAG_LEAUTHAUD11))
-    return false;
-  if (t->grouped) return false;
-  if (t->tuning.fused_draws != 0 && t->tuning.fused_draws != 40) return false;
-  if (fused_lds_bytes(t, false, 8, 40) > kMaxLdsBytes) return false;
-  if (t->tuning.fused_draws == 40) return true;          // (forced: any batch)
-  // alone on the chip, between fused_spread_min and one workgroup per CU (the three kernels
-  // spread smaller batches over the chip in less than a 40-draw workgroup's lifetime)
-  const bool alone = t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1 ||
-                     t->sync_spread;
-  // (up to 32 draws per CU the 32-draw workgroups are shorter-lived)
-  if (alone && !t->sync_spread && n_draws <= (int64_t)32 * t->n_cus &&
-      t->tuning.fused_draws == 0 && fused_half_tiles(t, false, n_draws, n_gauss, flags))
-    return false;
-  return alone && n_draws >= t->tuning.fused_spread_min &&
-         n_draws <= (int64_t)40 * t->n_cus * std::max(1, t->tuning.fused_spread_rounds);
-}
-
-// Workgroups of ONE 32-draw tile and eight waves (eight parts of the units; up to 80 KB of LDS,
-// two per CU), Zheng07 family with the default n_gauss_prim.
-// * Batches below 8192 draws of tables up to 104 bins: a workgroup lasts a quarter as long as
-//   the 64-draw one and a batch has twice as many -- what batches need that do not fill the
-//   chip's 512 places with four launches of 64-draw workgroups (tools/archive/r03_fused_half.py, us per
-//   step, three kernels / 64 draws x 8 waves / 32 x 4 / 32 x 8: G = 100: 1024 draws 12.8 / 23.4 /
-//   19.3 / 15.1, 2048 19.0 / 29.0 / 21.7 / 16.0, 4096 23.9 / 30.2 / 22.3 / 16.9, 6144 31.6 / 31.1 /
-//   26.2 / 25.1, 10^4 43.5 / 39.4 / 41.0 / 41.4; G = 60: 1024 10.2 / 12.3 / 9.7 / 7.4, 4096 15.3 /
-//   13.4 / 11.0 / 8.2, 6144 18.6 / 14.2 / 12.2 / 11.9, 10^4 21.5 / 17.7 / 19.0 / 19.5): once the
-//   chip is full the 64-draw form's fixed costs per draw win by 4-7 %.
-// * Tables of 105-208 bins, whose 64-draw workgroup does not fit half a CU: any batch size.
-bool fused_half_tiles(const tc_table* t, bool separate, int64_t n_draws, int n_gauss,
-                      unsigned flags) {
-  // (option "deterministic" = 2: the shape must not depend on the batch size -- 64 draws per
-  // workgroup unless 32 are forced)
-  if (t->tuning.deterministic >= 2)
-    return t->tuning.fused_draws == 32 && n_gauss == 10 &&
-           (t->tuning.fused_waves == 0 || t->tuning.fused_waves == 8) &&
-           fused_lds_bytes(t, separate, 8, 32) <= 80 * 1024;
-  if (t->tuning.fused_draws == 0 && n_gauss == 10 && t->tuning.fused == 1 &&
-      t->tuning.fused_min_draws == 0) {
-    auto tuned = t->autotuned.find(flags);      // (measured: option "autotune")
-    if (tuned != t->autotuned.end() && tuned->second.form_for(n_draws) != 0)
-      return tuned->second.form_for(n_draws) == 32 &&
-             fused_lds_bytes(t, separate, 8, 32) <= 80 * 1024;
-  }
-  // (a call that has the chip to itself: up to one 32-draw workgroup per CU INCLUSIVE -- 8192
-  // draws on 256 CUs take 41.9 us this way, 49.5 in the latency form, 55 as three kernels)
-  const bool alone = t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
-  if (t->tuning.fused_draws == 64 ||
-      (t->tuning.fused_draws == 0 && n_draws >= 8192 && !(alone && n_draws <= (int64_t)32 * t->n_cus)))
-    return false;
-  if (n_gauss != 10) return false;
-  if (t->tuning.fused_waves != 0 && t->tuning.fused_waves != 8) return false;
-  return fused_lds_bytes(t, separate, 8, 32) <= 80 * 1024;
-}
-
-bool fused_wide_tables(const tc_table* t, bool separate, int n_gauss, unsigned flags) {
-  if (n_gauss != 10) return false;
-  if (t->tuning.fused_draws == 64 || t->tuning.fused_waves != 0) return false;
-  return fused_lds_bytes(t, separate, 8, 64) > 80 * 1024 &&
-         fused_lds_bytes(t, separate, 8, 32) <= 80 * 1024;
-}
-
-// Waves per workgroup of the one-launch form for this table: 8, 16, or 0 (does not fit).
-int fused_waves(const tc_table* t, bool separate, unsigned flags) {
-  const bool fits8 = fused_lds_bytes(t, separate, 8, 64) <= 80 * 1024;
-  const bool fits16 = fused_lds_bytes(t, separate, 16, 64) <= 160 * 1024;
-  if (t->tuning.fused_waves == 8 && fused_lds_bytes(t, separate, 8, 64) <= 160 * 1024) return 8;
-  if (t->tuning.fused_waves == 16 && fits16) return 16;
-  // (16 waves: level with the three kernels on the shapes swept by hand, so only when forced --
-  // or when the table has been measured with THESE flags (option "autotune"): that choice then
-  // decides; a measurement with other flags says nothing about this LDS footprint)
-  return fits8 ? 8
-               : (fits16 && (t->tuning.fused >= 2 || t->autotuned.count(flags) != 0 ||
-                             t->tuning.deterministic >= 2)) ? 16 : 0;
-}
-
-int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_draws,
-              int n_gauss, unsigned flags, double* ngal_device, double* xi_device) {
+int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n_theta,
+              int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
+              double* xi_device) {
   Range range("occupation + contraction + finalisation (one launch)");
   tc_table::Lane& lane = t->lanes[t->cur];
   hipStream_t stream = lane.stream;
@@ -1155,14 +969,10 @@ int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_dr
   fa.n_bins = t->n_bins;
   fa.n_central = t->plan.n_central;
   fa.n_gauss = n_gauss;
-  fa.dens_rows = fused_dens_rows(t, separate);
+  fa.dens_rows = tc::fused_dens_rows(q_table.layout);
   fa.separate = separate ? 1 : 0;
-  const bool spread = fused_spread_eligible(t, n_draws, n_gauss, flags);
-  const bool wide = !spread && fused_wide_tables(t, separate, n_gauss, flags);
-  const bool half_tiles = !spread && !wide && fused_half_tiles(t, separate, n_draws, n_gauss, flags);
-  const int waves = spread || wide || half_tiles ? 8 : fused_waves(t, separate, flags);
-  const int draws = spread ? 40 : wide || half_tiles ? 32 : 64;
-  const int n_parts = spread ? 8 : waves * 32 / draws;
+  const int waves = form.waves, draws = form.draws;
+  const int n_parts = draws == 40 ? 8 : waves * 32 / draws;
   if (!separate) {
     const tc::QuadComp& comp = q_table.layout.comps[0];
     tc::triangle_parts(comp.n_rb, n_parts, fa.part_rb0, fa.part_cb0, fa.part_count);
@@ -1235,7 +1045,7 @@ int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_dr
     fa.xi = nullptr;
     t->chi2_fused = true;
   }
-  const int lds = fused_lds_bytes(t, separate, waves, draws);
+  const int lds = tc::fused_lds_bytes(fa.dens_rows, waves, draws);
   const dim3 grid((unsigned)((n_draws + draws - 1) / draws)), block(64 * waves);
 #ifdef TC_DEVELOPER_KNOBS
   if (fa.chi2 == nullptr && env_int_early("TC_FUSED_STAMPS", 0) != 0) {
@@ -1259,8 +1069,8 @@ int run_fused(tc_table* t, const double* theta_device, int n_theta, int64_t n_dr
   // or not the centrals take theirs (the reference's example table, bins 0.15 dex wide: 18.2 ->
   // 17.5 us per 10^4 draws); option "series" = 0 switches every expansion off
   const bool sat_defer = t->tuning.fused_defer != 0 && !assembias && !modulate &&
-                         !(flags & TC_FLAG_LEAUTHAUD11) && n_gauss == 10 && !wide &&
-                         !half_tiles && waves == 8 && t->n_bins <= 256 &&
+                         !(flags & TC_FLAG_LEAUTHAUD11) && n_gauss == 10 && draws != 32 &&
+                         waves == 8 && t->n_bins <= 256 &&
                          !(t->grouped && n_gauss == 10) && t->tuning.series != 0 &&
                          q->sat_series != nullptr && q->sat_records != nullptr;
   if (sat_defer) fa.sat_series = (const double*)q->sat_series;

@@ -749,6 +749,68 @@ int tc_debug_triangle_parts(int n_rb, int n_parts, int32_t* rb0, int32_t* cb0, i
   return TC_OK;
 }
 
+int tc_debug_fused_form(int n_bins, int n_central, int n_r, int n_cus, int grouped,
+                        int64_t n_draws, int n_gauss, unsigned flags, unsigned call,
+                        const int* options, const int* measured_forms, const float* measured_us,
+                        int* waves, int* draws, int* lds_bytes) {
+  TC_CHECK(n_bins >= 1 && n_central >= 0 && n_central <= n_bins && n_r >= 1 && n_cus >= 1 &&
+               options && waves && draws && lds_bytes && (!measured_forms == !measured_us),
+           "invalid arguments");
+  // the layouts a float64 handle of mode auto holds (table.cpp: tc_table_create)
+  const tc::QuadTiling tiling = tc::quad_tiling(n_r);
+  tc::QuadLayout by_type, total;
+  tc::build_quad_layout(n_bins, n_central, true, by_type);
+  const bool fusable = tiling.n_rtiles == 1 && n_r <= 20 && n_bins <= 248;
+  const bool has_total = (n_central % 4 != 0 && n_central < n_bins) || fusable;
+  if (has_total) tc::build_quad_layout(n_bins, n_central, false, total);
+  tc::FusedQuery q;
+  q.n_bins = n_bins;
+  q.n_u = tiling.n_u;
+  q.n_cus = n_cus;
+  q.grouped = grouped != 0;
+  q.servable = has_total && tiling.n_rtiles == 1 && n_r <= 20;
+  q.units_total = total.n_units;
+  q.units_by_type = by_type.n_units;
+  q.rows_total = tc::fused_dens_rows(total);
+  q.rows_by_type = tc::fused_dens_rows(by_type);
+  q.by_type_complete = true;
+  for (const tc::QuadComp& comp : by_type.comps) q.by_type_complete &= comp.n_units > 0;
+  q.n_draws = n_draws;
+  q.n_gauss = n_gauss;
+  q.flags = flags;
+  q.alone = (call & 1) != 0;
+  q.async = (call & 2) != 0;
+  q.sync_spread = (call & 4) != 0;
+  q.chain = (call & 8) != 0;
+  q.trace = (call & 16) != 0;
+  q.likelihood = (call & 32) != 0;
+  q.fused = options[0];
+  q.fused_min_draws = options[1];
+  q.fused_max_draws = options[2];
+  q.fused_waves = options[3];
+  q.fused_draws = options[4];
+  q.fused_spread = options[5];
+  q.fused_spread_min = options[6];
+  q.fused_spread_rounds = options[7];
+  q.deterministic = options[8];
+  tc::AutoChoice choice;
+  if (measured_forms != nullptr) {
+    for (int i = 0; i < tc::AutoChoice::kSizes; ++i) {
+      choice.form[i] = measured_forms[i];
+      for (int k = 0; k < 3; ++k) choice.us[i][k] = measured_us[3 * i + k];
+    }
+    q.measured = &choice;
+  }
+  const tc::FusedForm form = tc::choose_fused_form(q);
+  *waves = form.waves;
+  *draws = form.draws;
+  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
+  *lds_bytes = form.waves == 0 ? 0
+                               : tc::fused_lds_bytes(separate ? q.rows_by_type : q.rows_total,
+                                                     form.waves, form.draws);
+  return TC_OK;
+}
+
 int tc_debug_quad_schedule(int n_bins, int n_central, int by_type, int n_tiles, int n_rtiles,
                            int n_tables, int separate, int max_waves, int min_units, int order,
                            int* n_waves, int* n_runs, int* n_slabs, int64_t* units_min,

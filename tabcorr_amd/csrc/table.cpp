@@ -216,7 +216,7 @@ int tc_table_create(int mode, int n_bins, int n_r, int64_t n_pairs,
     const int n_central = t->plan.n_central;
     // (... and for every float64 table with a single r tile: predict_fused_kernel walks the
     // whole triangle as one component)
-    // (only where that kernel can ever take the table -- launch.hip: fused_eligible --: up to
+    // (only where that kernel can ever take the table -- hostmath.cpp: choose_fused_form --: up to
     // 20 r values, up to 248 bins; a second copy of the matrix otherwise serves nobody)
     const bool fusable = !quad_f32 && quad_tiling.n_rtiles == 1 && n_r <= 20 && n_bins <= 248;
     if (status == TC_OK && ((n_central % 4 != 0 && n_central < n_bins) || fusable))
@@ -316,7 +316,7 @@ int tc_table_info(const tc_table* t, int* mode, int* n_bins, int* n_r,
 namespace {
 int autotune(tc_table* t, unsigned flags);
 
-// The built-in estimate of which form serves a batch (launch.hip: fused_eligible) was fitted on
+// The built-in estimate of which form serves a batch (hostmath.cpp: choose_fused_form) was fitted on
 // a handful of table shapes and is up to 1.4 x behind the best form elsewhere (VERDICT r04 item
 // 5).  So a handle that sees a LOOP of pipelined or asynchronous calls measures: the
 // autotune_after-th such call with one combination of flags runs option "autotune" for it.
@@ -389,8 +389,7 @@ int tc_predict_zheng07_batch_device(tc_table* t, const double* theta_device,
       const CrossFused& cf = *choose_cross_fused(&self, 1, &t->cross_fused, &t->cross_fused_wide,
                                                  n, flags, &status);
       if (status != TC_OK) return status;
-      const bool alone = t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
-      if (cross_fused_eligible(t, cf, n, n_gauss, flags, alone)) {
+      if (cross_fused_eligible(t, cf, n, n_gauss, flags, runs_alone(t))) {
         status = run_cross_fused(t, cf, nullptr, theta_device + begin * n_theta,
                                  n_theta, n, flags, ngal_device + begin * (separate ? 2 : 1),
                                  xi_device + begin * n_comp * t->n_r, t->lanes[t->cur].stream,
@@ -400,8 +399,9 @@ int tc_predict_zheng07_batch_device(tc_table* t, const double* theta_device,
         continue;
       }
     }
-    if (fused_eligible(t, n, n_gauss, flags)) {
-      status = run_fused(t, theta_device + begin * n_theta, n_theta, n, n_gauss, flags,
+    const tc::FusedForm form = tc::choose_fused_form(fused_query(t, n, n_gauss, flags));
+    if (form.waves != 0) {
+      status = run_fused(t, form, theta_device + begin * n_theta, n_theta, n, n_gauss, flags,
                          ngal_device + begin * (separate ? 2 : 1),
                          xi_device + begin * n_comp * t->n_r);
       if (status != TC_OK) return status;
@@ -770,7 +770,9 @@ int predict_chunked(tc_table* t, const double* theta, int n_theta, int64_t n_dra
   // the chunks' launches then fill the chip together)
   t->sync_spread = n_draws >= t->tuning.fused_spread_min &&
                    (n_draws + 39) / 40 + n_chunks <= (int64_t)t->n_cus;
-  const bool spread = t->sync_spread && fused_spread_eligible(t, n_draws, n_gauss, flags);
+  tc::FusedQuery whole = fused_query(t, n_draws, n_gauss, flags);
+  whole.async = true;                      // (as its chunks will run)
+  const bool spread = t->sync_spread && tc::choose_fused_form(whole).draws == 40;
   t->sync_spread = spread;
   const int saved_draws = t->tuning.fused_draws, saved_min = t->tuning.fused_min_draws;
   if (spread) {
@@ -1491,11 +1493,8 @@ int autotune(tc_table* t, unsigned flags) {
       t->tuning.fused = 2;
       t->tuning.fused_draws = shapes[k];
       choice.us[i][1 + k] = 0.0f;
-      if (!fused_eligible(t, n, 10, flags)) continue;
       // (the shape asked for is the one that would run?)
-      const bool half = fused_wide_tables(t, separate, 10, flags) ||
-                        fused_half_tiles(t, separate, n, 10, flags);
-      if (half != (shapes[k] == 32)) continue;
+      if (tc::choose_fused_form(fused_query(t, n, 10, flags)).draws != shapes[k]) continue;
       status = time_form(n, &choice.us[i][1 + k]);
       if (status != TC_OK) return status;
       // (a one-launch form must win by 2 %: ties go to the three kernels)
@@ -1578,7 +1577,7 @@ int tc_table_set_option(tc_table* t, const char* name, int value) {
     t->tuning.autotune_after = value;
   } else if (key == "autotune") {
     // value = the predict flags to tune for (TC_FLAG_*; n_gauss_prim = 10), or -1: forget
-    // every measured choice (back to the formula of launch.hip: fused_eligible)
+    // every measured choice (back to the formula of hostmath.cpp: choose_fused_form)
     if (value < 0) {
       t->autotuned.clear();
       return TC_OK;
@@ -1736,7 +1735,7 @@ int tc_table_set_option(tc_table* t, const char* name, int value) {
     if (status != TC_OK) return status;
     t->resident.idle_us = value;
   } else if (key == "fused_draws") {
-    // (40: the latency form -- launch.hip: fused_spread_eligible -- for every batch it serves)
+    // (40: the latency form -- hostmath.cpp: choose_fused_form -- for every batch it serves)
     TC_CHECK(value == 0 || value == 32 || value == 40 || value == 64,
              "fused_draws must be 0, 32, 40 or 64");
     t->tuning.fused_draws = value;

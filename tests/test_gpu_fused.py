@@ -1041,3 +1041,209 @@ def test_latency_form_with_entries_that_are_not_finite():
     assert np.array_equal(xi[:, others], xi_c[:, others])
     good = np.isfinite(xi_3)
     assert_rel(xi[good], xi_3[good], 1e-12)
+
+
+# ---- the form a call takes is the one the host-side decision returns -------------------------
+
+FORM_SIZES = (64, 2048, 8192, 10000, 16384)
+FORM_ENTRIES = ('host', 'device', 'async', 'chi2', 'invariant')
+FORM_N_R = 3
+FORM_CUS = 256                      # compute units of an MI355X
+FORM_OPTIONS = dict(fused=1, fused_min_draws=0, fused_max_draws=30720, fused_waves=0,
+                    fused_draws=0, fused_spread=1, fused_spread_min=8192, fused_spread_rounds=1,
+                    deterministic=0)
+ALONE, ASYNC, SYNC_SPREAD, CHAIN, TRACE, LIKELIHOOD = 1, 2, 4, 8, 16, 32
+
+
+def observed_forms(n_bins):
+    """Every entry point x batch size on a synthetic table of n_bins bins and three r values
+    (default options; un-batched kernels off, host arrays in one chunk): {(entry, n_draws):
+    (last launch, ngal and xi | chi2 of the first 64 draws)}, and the oracle's for those draws."""
+    import ctypes
+    from tabcorr_amd import _lib, pinned_array, pinned_empty, synthetic
+    from oracle import tabcorr_oracle as oracle
+    lib = _lib.load()
+    table = synthetic.synthetic_table(n_bins // 2, 1, (FORM_N_R, ), 'auto', seed=n_bins)
+    halotab = make_tabcorr(table)
+    handle = halotab.to_device().handle
+    set_option(halotab, 'single_draw', 0)
+    set_option(halotab, 'sync_chunks', 1)
+    n_max = max(FORM_SIZES)
+    theta = synthetic.zheng07_draws(n_max, seed=5)
+    expect = oracle.predict_zheng07_batch(table, theta[:64])
+    precision = np.diag(np.arange(1.0, FORM_N_R + 1.0))
+    data = np.zeros(FORM_N_R)
+    pointers = [ctypes.c_void_p() for _ in range(3)]
+    for ptr, count in zip(pointers, (theta.size, n_max, n_max * FORM_N_R)):
+        _lib.check(lib.tc_device_malloc(ctypes.byref(ptr), count * 8))
+    d_theta, d_ngal, d_xi = pointers
+    _lib.check(lib.tc_memcpy_h2d(d_theta, theta.ctypes.data_as(ctypes.c_void_p), theta.nbytes))
+    pinned_theta = pinned_array(theta)
+    seen = {}
+    try:
+        for n in FORM_SIZES:
+            seen['host', n] = (halotab.predict_batch(theta[:n]), last_launch(halotab))
+            _lib.check(lib.tc_predict_zheng07_batch_device(handle, d_theta, 5, n, 10, 0, d_ngal,
+                                                           d_xi))
+            _lib.check(lib.tc_table_synchronize(handle))
+            launch = last_launch(halotab)
+            ngal, xi = np.empty(64), np.empty((64, FORM_N_R))
+            _lib.check(lib.tc_memcpy_d2h(ngal.ctypes.data_as(ctypes.c_void_p), d_ngal, ngal.nbytes))
+            _lib.check(lib.tc_memcpy_d2h(xi.ctypes.data_as(ctypes.c_void_p), d_xi, xi.nbytes))
+            seen['device', n] = ((ngal, xi), launch)
+            out = (pinned_empty(n), pinned_empty((n, FORM_N_R)))
+            got = halotab.predict_batch_async(pinned_theta[:n], out=out).wait()
+            seen['async', n] = (got, last_launch(halotab))
+            seen['chi2', n] = (halotab.chi2_batch(theta[:n], data, precision),
+                               last_launch(halotab))
+            set_option(halotab, 'deterministic', 2)
+            seen['invariant', n] = (halotab.predict_batch(theta[:n]), last_launch(halotab))
+            set_option(halotab, 'deterministic', 0)
+    finally:
+        for ptr in pointers:
+            _lib.check(lib.tc_device_free(ptr))
+    return {key: (launch, np.asarray(ngal)[:64], np.asarray(second)[:64])
+            for key, ((ngal, second), launch) in seen.items()}, expect
+
+
+def decided_form(n_bins, n_draws, call, **options):
+    """(waves, draws, LDS bytes) of tc_debug_fused_form for the synthetic table of n_bins bins
+    (half of them centrals, nothing grouped), ten nodes, no flags."""
+    import ctypes
+    from tabcorr_amd import _lib
+    lib = _lib.load()
+    values = dict(FORM_OPTIONS, **options)
+    packed = (ctypes.c_int * len(FORM_OPTIONS))(*[values[name] for name in FORM_OPTIONS])
+    out = [ctypes.c_int() for _ in range(3)]
+    _lib.check(lib.tc_debug_fused_form(n_bins, n_bins // 2, FORM_N_R, FORM_CUS, 0, n_draws, 10, 0,
+                                       call, packed, None, None, *[ctypes.byref(v) for v in out]))
+    return tuple(v.value for v in out)
+
+
+def matching_form(n_bins, entry, n):
+    """The query that matches a call of observed_forms (table.cpp: which lane an entry point's
+    launch runs on, and what the one chunk of a host-array call sets for it)."""
+    if entry == 'device':
+        return decided_form(n_bins, n, 0)
+    if entry == 'async':
+        return decided_form(n_bins, n, ASYNC)
+    if entry == 'chi2':
+        return decided_form(n_bins, n, ALONE | LIKELIHOOD)
+    options = {'deterministic': 2} if entry == 'invariant' else {}
+    # host arrays: draws and results of up to 512 KB are addressed in page-locked memory by a
+    # launch alone on lane 0; larger calls run as one asynchronous chunk -- in the latency form
+    # where the whole call fits one round of its workgroups, else with 32 draws per workgroup
+    if n * (5 + 1 + FORM_N_R) * 8 <= 512 * 1024:
+        return decided_form(n_bins, n, ALONE, **options)
+    fits = n >= FORM_OPTIONS['fused_spread_min'] and (n + 39) // 40 + 1 <= FORM_CUS
+    if fits and decided_form(n_bins, n, ASYNC | SYNC_SPREAD, **options)[1] == 40:
+        return decided_form(n_bins, n, ASYNC | SYNC_SPREAD, fused_draws=40, **options)
+    if entry == 'invariant':
+        return decided_form(n_bins, n, ASYNC, **options)
+    return decided_form(n_bins, n, ASYNC, fused_draws=32, fused_min_draws=1)
+
+
+# (workgroups, waves, LDS bytes) of the one launch, None: three kernels -- as the library took
+# them before the decision moved into choose_fused_form (recorded on an MI355X)
+FORMS_BEFORE = {
+    (12, 'host', 64): None,
+    (12, 'host', 2048): (64, 8, 67600),
+    (12, 'host', 8192): (205, 8, 77840),
+    (12, 'host', 10000): (250, 8, 77840),
+    (12, 'host', 16384): (512, 8, 67600),
+    (12, 'device', 64): None,
+    (12, 'device', 2048): (64, 8, 67600),
+    (12, 'device', 8192): (128, 8, 67600),
+    (12, 'device', 10000): (157, 8, 67600),
+    (12, 'device', 16384): (256, 8, 67600),
+    (12, 'async', 64): None,
+    (12, 'async', 2048): (64, 8, 67600),
+    (12, 'async', 8192): (128, 8, 67600),
+    (12, 'async', 10000): (157, 8, 67600),
+    (12, 'async', 16384): (256, 8, 67600),
+    (12, 'chi2', 64): None,
+    (12, 'chi2', 2048): (64, 8, 67600),
+    (12, 'chi2', 8192): (256, 8, 67600),
+    (12, 'chi2', 10000): (250, 8, 77840),
+    (12, 'chi2', 16384): (256, 8, 67600),
+    (12, 'invariant', 64): (1, 8, 67600),
+    (12, 'invariant', 2048): (32, 8, 67600),
+    (12, 'invariant', 8192): (128, 8, 67600),
+    (12, 'invariant', 10000): (157, 8, 67600),
+    (12, 'invariant', 16384): (256, 8, 67600),
+    (40, 'host', 64): None,
+    (40, 'host', 2048): (64, 8, 67600),
+    (40, 'host', 8192): (205, 8, 77840),
+    (40, 'host', 10000): (250, 8, 77840),
+    (40, 'host', 16384): (512, 8, 67600),
+    (40, 'device', 64): None,
+    (40, 'device', 2048): (64, 8, 67600),
+    (40, 'device', 8192): (128, 8, 67600),
+    (40, 'device', 10000): (157, 8, 67600),
+    (40, 'device', 16384): (256, 8, 67600),
+    (40, 'async', 64): None,
+    (40, 'async', 2048): (64, 8, 67600),
+    (40, 'async', 8192): (128, 8, 67600),
+    (40, 'async', 10000): (157, 8, 67600),
+    (40, 'async', 16384): (256, 8, 67600),
+    (40, 'chi2', 64): None,
+    (40, 'chi2', 2048): (64, 8, 67600),
+    (40, 'chi2', 8192): (256, 8, 67600),
+    (40, 'chi2', 10000): (250, 8, 77840),
+    (40, 'chi2', 16384): (256, 8, 67600),
+    (40, 'invariant', 64): (1, 8, 67600),
+    (40, 'invariant', 2048): (32, 8, 67600),
+    (40, 'invariant', 8192): (128, 8, 67600),
+    (40, 'invariant', 10000): (157, 8, 67600),
+    (40, 'invariant', 16384): (256, 8, 67600),
+    (112, 'host', 64): None,
+    (112, 'host', 2048): None,
+    (112, 'host', 8192): (205, 8, 77840),
+    (112, 'host', 10000): (250, 8, 77840),
+    (112, 'host', 16384): (512, 8, 67600),
+    (112, 'device', 64): None,
+    (112, 'device', 2048): (64, 8, 67600),
+    (112, 'device', 8192): (256, 8, 67600),
+    (112, 'device', 10000): (313, 8, 67600),
+    (112, 'device', 16384): (512, 8, 67600),
+    (112, 'async', 64): None,
+    (112, 'async', 2048): (64, 8, 67600),
+    (112, 'async', 8192): (256, 8, 67600),
+    (112, 'async', 10000): (313, 8, 67600),
+    (112, 'async', 16384): (512, 8, 67600),
+    (112, 'chi2', 64): None,
+    (112, 'chi2', 2048): None,
+    (112, 'chi2', 8192): None,
+    (112, 'chi2', 10000): (250, 8, 77840),
+    (112, 'chi2', 16384): None,
+    (112, 'invariant', 64): (2, 8, 67600),
+    (112, 'invariant', 2048): (64, 8, 67600),
+    (112, 'invariant', 8192): (256, 8, 67600),
+    (112, 'invariant', 10000): (313, 8, 67600),
+    (112, 'invariant', 16384): (512, 8, 67600),
+}
+
+
+@pytest.mark.parametrize('n_bins', [12, 40, 112])
+def test_every_entry_point_takes_the_form_the_host_decision_returns(n_bins):
+    """tc_table_last_launch after host-array, device-pointer, asynchronous, likelihood and
+    batch-invariant calls of 64 .. 16384 draws: what the library launched before the decision
+    became hostmath.h: choose_fused_form, and what tc_debug_fused_form returns for the query
+    that launch.hip: fused_query fills for that call; the oracle's values on the first 64 draws
+    (tabcorr.py:537-650)."""
+    seen, expect = observed_forms(n_bins)
+    for entry in FORM_ENTRIES:
+        for n in FORM_SIZES:
+            (workgroups, waves, slabs, lds), ngal, second = seen[entry, n]
+            launched = (workgroups, waves, lds) if slabs == 0 else None
+            print(n_bins, entry, n, launched)
+            assert launched == FORMS_BEFORE[n_bins, entry, n], (entry, n)
+            want_waves, want_draws, want_lds = matching_form(n_bins, entry, n)
+            decided = ((n + want_draws - 1) // want_draws, want_waves, want_lds) if want_waves else None
+            assert launched == decided, (entry, n, decided)
+            assert_rel(ngal, expect[0], RTOL, 'ngal %s %d' % (entry, n))
+            if entry == 'chi2':
+                want = np.einsum('bi,ij,bj->b', expect[1], np.diag(np.arange(1.0, 4.0)), expect[1])
+                assert_rel(second, want, RTOL, 'chi2 %d' % n)
+            else:
+                assert_rel(second, expect[1], RTOL, 'xi %s %d' % (entry, n))

@@ -834,6 +834,87 @@ def test_host_logic_under_address_and_undefined_sanitizers(tmp_path):
     assert 'all checks passed' in run.stdout
 
 
+# ---- which batched calls run as one launch, and in which workgroup shape (no GPU needed) ----
+
+FUSED_OPTIONS = ('fused', 'fused_min_draws', 'fused_max_draws', 'fused_waves', 'fused_draws',
+                 'fused_spread', 'fused_spread_min', 'fused_spread_rounds', 'deterministic')
+
+
+def fused_form(lib, n_bins, n_central, n_r, n_cus, grouped, n_draws, n_gauss, flags, call,
+               options, measured=None):
+    """(waves, draws, LDS bytes) of tc_debug_fused_form; options in FUSED_OPTIONS order,
+    measured = (forms[9], us[9][3]) or None."""
+    from tabcorr_amd import _lib
+    packed = (ctypes.c_int * 9)(*options)
+    forms = us = None
+    if measured is not None:
+        forms = (ctypes.c_int * 9)(*measured[0])
+        us = (ctypes.c_float * 27)(*measured[1])
+    out = [ctypes.c_int() for _ in range(3)]
+    _lib.check(lib.tc_debug_fused_form(n_bins, n_central, n_r, n_cus, grouped, n_draws, n_gauss,
+                                       flags, call, packed, forms, us,
+                                       *[ctypes.byref(v) for v in out]))
+    return tuple(v.value for v in out)
+
+
+def test_fused_form_is_what_the_five_predicates_decided(lib):
+    """hostmath.h: choose_fused_form against tests/golden/fused_form_cases.txt: 2748 queries
+    (table shape, call, options, measured choice) with the answers of the five predicates it
+    replaced (fused_eligible, fused_spread_eligible, fused_half_tiles, fused_wide_tables,
+    fused_waves and run_fused's derivation of the shape), recorded from that code."""
+    choices, cases = [None], []
+    for line in open(os.path.join(REPO, 'tests', 'golden', 'fused_form_cases.txt')):
+        fields = line.split()
+        if line.startswith('choice'):
+            choices.append(([int(v) for v in fields[1:10]], [float(v) for v in fields[10:37]]))
+        elif not line.startswith('#'):
+            cases.append([int(v) for v in fields])
+    assert len(choices) == 4 and 2000 <= len(cases) <= 5000
+    outcomes = {}
+    for case in cases:
+        table, (n_draws, n_gauss, flags, call), options = case[:5], case[5:9], case[9:18]
+        want = tuple(case[19:22])
+        got = fused_form(lib, *table, n_draws, n_gauss, flags, call, options, choices[case[18]])
+        assert got == want, (case, got)
+        outcomes[want[:2]] = outcomes.get(want[:2], 0) + 1
+    # three kernels, 8 x 64, 16 x 64, 8 x 32 and the latency form
+    assert set(outcomes) == {(0, 0), (8, 64), (16, 64), (8, 32), (8, 40)}
+    assert min(outcomes.values()) >= 50, outcomes
+
+
+def test_fused_form_changes_where_the_lds_footprint_says(lib):
+    """(densities of the draws | the waves' sums) + math table + reduction scratch, in bytes:
+    two workgroups of 8 waves per CU up to 80 KB each -- 104 bins with 64 draws, 212 with 32 --,
+    one of 16 waves up to 160 KB -- 248 bins; pipelined calls of 10^4 draws, 19 r values."""
+    def form(n_bins, **options):
+        values = dict(zip(FUSED_OPTIONS, (1, 0, 30720, 0, 0, 1, 8192, 1, 0)), **options)
+        return fused_form(lib, n_bins, n_bins // 2, 19, 256, 0, 10000, 10, 0, 0,
+                          [values[name] for name in FUSED_OPTIONS])
+    def lds(rows, waves, draws):
+        # the draws' densities or -- in their place later -- the waves' sums (4 x 5 rows of a
+        # 32-draw tile, or of all 40 draws, per wave); the math table; two rows per wave
+        sums = waves * 20 * (40 if draws == 40 else 32)
+        return (max(rows * draws, sums) + 2306 + 2 * waves * 64) * 8
+    assert lds(104, 8, 64) == 79888 and lds(108, 8, 64) == 81936       # 80 KB = 81920
+    # (32 draws: four more rows are 1 KB more, so 212 bins still fit and 216 are the first that
+    # do not)
+    assert lds(208, 8, 32) == 79888 and lds(212, 8, 32) == 80912 and lds(216, 8, 32) == 81936
+    assert lds(248, 16, 64) == 161808 and lds(252, 16, 64) == 163856   # 160 KB = 163840
+    assert form(104) == (8, 64, 79888)
+    assert form(108) == (8, 32, lds(108, 8, 32))
+    assert form(208) == (8, 32, 79888)
+    assert form(212) == (8, 32, 80912)
+    assert form(216) == (0, 0, 0)                     # (16 waves: only when forced or measured)
+    assert form(216, fused=2, fused_min_draws=1) == (16, 64, lds(216, 16, 64))
+    assert form(248, fused=2, fused_min_draws=1) == (16, 64, 161808)
+    assert form(252, fused=2, fused_min_draws=1) == (0, 0, 0)
+    assert form(248, deterministic=2) == (16, 64, 161808)
+    assert form(252, deterministic=2) == (0, 0, 0)
+    # a call alone on the chip: the latency form, 40 draws per workgroup
+    values = fused_form(lib, 12, 6, 3, 256, 0, 10000, 10, 0, 1, (1, 0, 30720, 0, 0, 1, 8192, 1, 0))
+    assert values == (8, 40, lds(12, 8, 40)) and values[2] == 77840
+
+
 # ---- quadratic-form contraction: layout, equal-share schedule, merge (no GPU needed) --------
 
 @pytest.mark.parametrize(

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The form a batch takes -- three kernels, one launch with 64-draw or 32-draw workgroups --
-as chosen by the built-in estimate (launch.hip: fused_eligible) and by the measured choice of
+as chosen by the built-in estimate (hostmath.cpp: choose_fused_form) and by the measured choice of
 option "autotune", against the best forced form, over a grid of table shapes and batch sizes
 (device-resident pipelined calls, us per call).  Prints every point where a choice is more than
 5 % behind the best forced form, and the worst ratios."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The form a batch takes -- three kernels, one launch with 64-draw or 32-draw workgroups --
-as chosen by the built-in estimate (launch.hip: fused_eligible: what the first 255 pipelined
+as chosen by the built-in estimate (hostmath.cpp: choose_fused_form: what the first 255 pipelined
 calls get) and by the library's DEFAULT behaviour from the 256th pipelined call on (it measures
 by itself: option "autotune_after"; nobody calls autotune() here), against the best forced form,
 over a grid of table shapes and batch sizes (device-resident pipelined calls, us per call).

@@ -2,8 +2,9 @@
 // (SURVEY.md section 5): g++ -fsanitize=address,undefined on hostmath.cpp + this file, no
 // HIP.  Walks the same entry points the C ABI uses (bin permutation and segmentation,
 // chunking, the quadratic-form layout / schedule / table fill / emulation, spline
-// matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort) over a
-// sweep of shapes and checks the results against direct evaluations.  Exit status 0 = all
+// matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort, the choice of
+// the one-launch form) over a sweep of shapes and checks the results against direct
+// evaluations.  Exit status 0 = all
 // checks passed and no sanitizer report (-fno-sanitize-recover aborts on the first).
 //
 //   make -C tools/sanitize && tools/sanitize/host_driver
@@ -317,6 +318,80 @@ static void check_cells() {
     }
 }
 
+// hostmath.h: choose_fused_form over a few thousand queries, degenerate ones included (zero
+// draws, no nodes, tables without centrals or satellites, no layouts at all): a form the
+// instances exist for, an LDS footprint within the CU's, and the same answer twice.
+static void check_fused_form() {
+  std::mt19937_64 rng(5);
+  auto pick = [&](std::initializer_list<int> values) {
+    return *(values.begin() + rng() % values.size());
+  };
+  tc::AutoChoice choice;
+  for (int i = 0; i < tc::AutoChoice::kSizes; ++i) {
+    choice.form[i] = pick({0, 32, 64});
+    for (int k = 0; k < 3; ++k) choice.us[i][k] = (float)(rng() % 4) * 7.5f;
+  }
+  int one_launch = 0;
+  for (int n = 0; n < 6000; ++n) {
+    const int n_bins = pick({1, 3, 8, 60, 100, 104, 108, 208, 212, 248, 252, 440});
+    const int n_central = pick({0, n_bins / 2, n_bins / 2, n_bins / 2 + 1, n_bins});
+    const int n_r = pick({1, 3, 19, 20, 21, 45});
+    const tc::QuadTiling tiling = tc::quad_tiling(n_r);
+    tc::QuadLayout total, by_type;
+    tc::FusedQuery q;
+    if (n % 17 != 0) {                  // (else: a handle without the quadratic-form layouts)
+      tc::build_quad_layout(n_bins, std::min(n_central, n_bins), true, by_type);
+      tc::build_quad_layout(n_bins, std::min(n_central, n_bins), false, total);
+      q.servable = tiling.n_rtiles == 1 && n_r <= 20;
+    }
+    q.n_bins = n_bins;
+    q.n_u = tiling.n_u;
+    q.n_cus = pick({256, 64, 1});
+    q.grouped = rng() % 4 == 0;
+    q.units_total = total.n_units;
+    q.units_by_type = by_type.n_units;
+    q.rows_total = tc::fused_dens_rows(total);
+    q.rows_by_type = tc::fused_dens_rows(by_type);
+    q.by_type_complete = by_type.comps.size() == 3;
+    for (const tc::QuadComp& comp : by_type.comps) q.by_type_complete &= comp.n_units > 0;
+    q.n_draws = pick({0, 1, 255, 2048, 8192, 10000, 16384, 30721, 1 << 30});
+    q.n_gauss = pick({0, 1, 10, 10, 10, 12});
+    q.flags = (unsigned)pick({0, 0, 1, 2, 4, 16, 18, 23, 31});
+    q.alone = rng() % 2;
+    q.async = rng() % 3 == 0;
+    q.sync_spread = rng() % 4 == 0;
+    q.chain = rng() % 16 == 0;
+    q.trace = rng() % 16 == 0;
+    q.likelihood = rng() % 4 == 0;
+    q.fused = pick({0, 1, 1, 2});
+    q.fused_min_draws = pick({0, 0, 1, 5000});
+    q.fused_max_draws = pick({30720, 0, 1 << 30});
+    q.fused_waves = pick({0, 0, 8, 16});
+    q.fused_draws = pick({0, 0, 32, 40, 64});
+    q.fused_spread = rng() % 4 != 0;
+    q.fused_spread_min = pick({8192, 0, 1});
+    q.fused_spread_rounds = pick({1, 2, 0, -1});
+    q.deterministic = pick({0, 0, 1, 2});
+    q.measured = rng() % 3 == 0 ? &choice : nullptr;
+    const tc::FusedForm form = tc::choose_fused_form(q);
+    const tc::FusedForm again = tc::choose_fused_form(q);
+    EXPECT(form.waves == again.waves && form.draws == again.draws, "the decision is not a function");
+    if (form.waves == 0) {
+      EXPECT(form.draws == 0, "three kernels with %d draws per workgroup", form.draws);
+      continue;
+    }
+    ++one_launch;
+    EXPECT(q.servable && q.fused != 0 && q.n_gauss >= 1, "one launch for a table it cannot serve");
+    EXPECT((form.waves == 8 && (form.draws == 64 || form.draws == 32 || form.draws == 40)) ||
+               (form.waves == 16 && form.draws == 64),
+           "no instance of %d waves x %d draws", form.waves, form.draws);
+    const int rows = (q.flags & tc::kFlagSeparate) ? q.rows_by_type : q.rows_total;
+    const int lds = tc::fused_lds_bytes(rows, form.waves, form.draws);
+    EXPECT(rows >= n_bins && lds <= 160 * 1024, "%d bins: %d rows, %d bytes of LDS", n_bins, rows, lds);
+  }
+  EXPECT(one_launch > 300, "only %d queries took a one-launch form", one_launch);
+}
+
 int main() {
   check_quadrature();
   check_splines();
@@ -324,6 +399,7 @@ int main() {
   check_quad();
   check_fastmath();
   check_cells();
+  check_fused_form();
   if (g_failures != 0) {
     printf("%d check(s) failed\n", g_failures);
     return 1;
