@@ -116,6 +116,14 @@ int tc_pair_indices(int n_bins, int32_t* index_1, int32_t* index_2, int32_t* pre
 /* Not-a-knot cubic spline matrix a[(n-1)][4][n] of interpolator.py:219-272. */
 int tc_spline_interpolation_matrix(int n, const double* xp, double* a);
 
+/* Weights of one axis of that spline at x: the spline through (xp, y) is sum_j weight[j] y[j] and
+ * its derivative with respect to x sum_j dweight[j] y[j]; `a` is the matrix above.  *segment (may
+ * be NULL) receives the segment whose polynomial is evaluated: np.digitize(x, xp) - 1 with
+ * x == xp[n - 1] in the last one, clamped to [0, n - 2] -- beyond the grid the outermost
+ * polynomial continues.  Pure host code: the text the interpolator's gradient kernels run. */
+int tc_spline_weights(int n, const double* xp, const double* a, double x, double* weight,
+                      double* dweight, int* segment);
+
 /* ---- one tabulated table (replaces the state of a `TabCorr` instance) ----------------
  *
  * tc_table_create uploads everything predict() needs from a TabCorr object
@@ -317,6 +325,40 @@ int tc_interp_chi2_zheng07_batch_device(tc_interp* interp, const double* theta_d
                                         int n_gauss_prim, unsigned flags, const double* data,
                                         const double* precision, double* ngal_device,
                                         double* chi2_device);
+
+/* Analytic gradients behind Interpolator.predict (extension, as tc_predict_grad_zheng07_batch):
+ * the interpolated prediction of a batch of draws (theta, x) with its exact derivatives with
+ * respect to the five Zheng07 parameters and the D = n_dim extra parameters, in one launch per
+ * batch.  Derivative columns: the five Zheng07 parameters, then the extra parameters in axis
+ * order: ngal (n_draws), xi (n_draws, n_r), dngal (n_draws, 5 + D), dxi (n_draws, 5 + D, n_r).
+ * The spline is C2, so the results have no kink in x; a clamped x (beyond the grid) gets the
+ * derivative of the outermost polynomial.  n_theta must be 5; flags 0 or
+ * TC_FLAG_MODULATE_WITH_CENOCC.  TC_ERR_UNSUPPORTED as for a table (float32 tables,
+ * TC_FLAG_SEPARATE_GAL_TYPE, TC_FLAG_ASSEMBIAS, TC_FLAG_LEAUTHAUD11) and for a grid whose rows do
+ * not fit the kernel's LDS: a table's rows plus 64 D rows of weights and (6 + D) n_r rows of
+ * accumulators (twice those in mode cross) within 160 KiB.  Batch-invariant by construction.
+ * Host arrays run on lane 0; the `_device` forms enqueue on the next lane and return. */
+int tc_interp_predict_grad_zheng07_batch(tc_interp* interp, const double* theta, int n_theta,
+                                         const double* x, int64_t n_draws, int n_gauss_prim,
+                                         unsigned flags, double* ngal, double* xi, double* dngal,
+                                         double* dxi);
+int tc_interp_predict_grad_zheng07_batch_device(tc_interp* interp, const double* theta_device,
+                                                int n_theta, const double* x_device,
+                                                int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                                double* ngal_device, double* xi_device,
+                                                double* dngal_device, double* dxi_device);
+/* ... and of the likelihood (tc_chi2_grad_zheng07_batch): ngal, chi2 (n_draws), dngal, dchi2
+ * (n_draws, 5 + D); data / precision are host arrays in both forms. */
+int tc_interp_chi2_grad_zheng07_batch(tc_interp* interp, const double* theta, int n_theta,
+                                      const double* x, int64_t n_draws, int n_gauss_prim,
+                                      unsigned flags, const double* data, const double* precision,
+                                      double* ngal, double* chi2, double* dngal, double* dchi2);
+int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* interp, const double* theta_device,
+                                             int n_theta, const double* x_device, int64_t n_draws,
+                                             int n_gauss_prim, unsigned flags, const double* data,
+                                             const double* precision, double* ngal_device,
+                                             double* chi2_device, double* dngal_device,
+                                             double* dchi2_device);
 
 /* Asynchronous host-to-host forms (page-locked theta, x, outputs; see
  * tc_predict_zheng07_batch_async): upload, kernels and download of a call on one of the

@@ -61,6 +61,8 @@ SIGNATURES = {
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_pair_indices': [ctypes.c_int, c_int32_p, c_int32_p, c_int32_p],
     'tc_spline_interpolation_matrix': [ctypes.c_int, c_double_p, c_double_p],
+    'tc_spline_weights': [ctypes.c_int, c_double_p, c_double_p, ctypes.c_double, c_double_p,
+                          c_double_p, c_int_p],
     'tc_plan_debug': [ctypes.c_int, ctypes.c_int, c_uint8_p, ctypes.c_int,
                       c_int64_p, c_int32_p, c_int32_p, c_int32_p],
     'tc_debug_triangle_parts': [ctypes.c_int, ctypes.c_int, c_int_p, c_int_p, c_int_p],
@@ -177,6 +179,22 @@ SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
         ctypes.c_void_p, ctypes.c_void_p],
+    'tc_interp_predict_grad_zheng07_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        c_double_p, c_double_p],
+    'tc_interp_predict_grad_zheng07_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    'tc_interp_chi2_grad_zheng07_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_interp_chi2_grad_zheng07_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'tc_table_set_option': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int],
     'tc_table_timer_begin': [ctypes.c_void_p, ctypes.c_int],
     'tc_table_timer_end': [ctypes.c_void_p, c_float_p],

@@ -1,6 +1,7 @@
 // Analytic gradients of (ngal, xi, chi2) with respect to the five Zheng07 parameters: the
 // argument block of the gradient kernels (grad_kernels.hip.h), their LDS budget and the dense
-// matrix-operand layout of a mode-auto table.  Plain C++: the host-only units fill these in.
+// matrix-operand layout of a mode-auto table.  Plain C++ for the host-only units that fill these
+// in, but for spline_weights, which hipcc also compiles for the device.
 //
 // With w = n_h <N> and S_r the symmetric matrix of one r bin, q_r = w^T S_r w and
 // dq_r / dtheta_k = 2 (dw / dtheta_k)^T (S_r w): ONE dense product U_r = S_r W per tile of draws
@@ -10,6 +11,8 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+
+#include "kernel_args.h"
 
 namespace tc {
 
@@ -91,6 +94,89 @@ inline void build_grad_operand(int n_bins, int n_r, const double* packed,
         out[grad_operand_index(n_bins, r, i, j)] = value;
         out[grad_operand_index(n_bins, r, j, i)] = value;
       }
+}
+
+// ---- gradients of an interpolator (grad_interp_kernels.hip.h) -----------------------------------
+// The interpolated result is linear in the per-table results: with c_t(x) the tensor-product
+// spline weight of table t, d/dtheta_k = sum_t c_t d(ngal_t, xi_t)/dtheta_k and d/dx_d =
+// sum_t (dc_t/dx_d) (ngal_t, xi_t).  One launch per batch walks the tables class by class.
+
+#if defined(__HIPCC__)
+#define TC_GRAD_HOST_DEVICE __host__ __device__
+#else
+#define TC_GRAD_HOST_DEVICE
+#endif
+
+// Weights of one axis: the spline through (xp, y) at x is sum_j weight[j] y[j] and its derivative
+// sum_j dweight[j] y[j], for the nodes j = first, first + step, ... < n, stored `stride` doubles
+// apart.  `a`: the (n - 1, 4, n) matrix of spline_interpolation_matrix.  Segment as
+// interpolator.py:275-331: np.digitize with the right edge special-cased, clamped to the outermost
+// segments -- an x beyond the grid gets that segment's polynomial and its derivative.  Returns
+// the segment.
+TC_GRAD_HOST_DEVICE inline int spline_weights(int n, const double* xp, const double* a,
+                                              double x, int first, int step, int stride,
+                                              double* weight, double* dweight) {
+  int seg = -1;
+  for (int i = 0; i < n; ++i) seg += xp[i] <= x ? 1 : 0;   // np.digitize(x, xp) - 1
+  if (x == xp[n - 1]) seg = n - 2;
+  seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
+  const double* m = a + (size_t)seg * 4 * n;
+  const double x2 = x * x, x3 = x2 * x;
+  for (int j = first; j < n; j += step) {
+    weight[(size_t)j * stride] = m[j] + m[n + j] * x + m[2 * n + j] * x2 + m[3 * n + j] * x3;
+    dweight[(size_t)j * stride] = m[n + j] + 2.0 * m[2 * n + j] * x + 3.0 * m[3 * n + j] * x2;
+  }
+  return seg;
+}
+#undef TC_GRAD_HOST_DEVICE
+
+// what tc_interp_create admits (kernel_args.h) sizes the argument arrays and the weight rows
+constexpr int kGradMaxDim = kMaxInterpDim;
+constexpr int kGradMaxAxis = kMaxInterpAxis;
+
+struct GradInterpArgs {
+  // theta, the sizes, the flags, math_table, row_tiles / k_steps and the result arrays as for one
+  // table: dngal (n_draws, 5 + n_dim), dxi (n_draws, 5 + n_dim, n_r), dchi2 (n_draws, 5 + n_dim),
+  // the five Zheng07 parameters first.  log_m, m, weight, n_h and matrix are set per class and
+  // per table by the kernel.
+  GradArgs table;
+  const double* x;                    // (n_draws, n_dim)
+  int n_dim;
+  int n_classes;
+  int n_axis[kGradMaxDim];
+  int axis_offset[kGradMaxDim];       // offset of xp_d in xp
+  int a_offset[kGradMaxDim];          // offset of a_d in a
+  const double* xp;
+  const double* a;
+  // the walk: the tables class by class, inside a class in list order -- fixed by the
+  // interpolator; class v is walk[class_begin[v] .. class_begin[v + 1])
+  const int32_t* class_begin;         // (n_classes + 1)
+  const int32_t* walk_node;           // (K, n_dim) grid node of every table, in walk order
+  const double* const* matrices;      // (K) GradArgs::matrix of every table, in walk order
+  const double* const* class_log_m;   // (n_classes) quadrature constants and n_h of every class
+  const double* const* class_m;
+  const double* const* class_weight;
+  const double* const* class_n_h;
+};
+
+// LDS rows of kGradDraws doubles that both interpolator kernels keep: the weights and derivative
+// weights of every axis, and the (6 + n_dim) accumulators of xi per r bin.  The likelihood is
+// finished in the accumulators themselves (`chi2` costs nothing).
+constexpr size_t grad_interp_common_rows(int n_r, int n_dim) {
+  return 2 * (size_t)n_dim * kGradMaxAxis + (size_t)(6 + n_dim) * n_r;
+}
+// grad_interp_auto_kernel: the rows of grad_auto_kernel for one class at a time, its totals.
+constexpr size_t grad_interp_auto_lds_bytes(int n_bins, int n_central, int n_r, int n_dim,
+                                            bool /* chi2 */) {
+  return ((size_t)grad_auto_rows(n_bins, n_central) + 6 + grad_interp_common_rows(n_r, n_dim)) *
+         kGradDraws * sizeof(double);
+}
+// grad_interp_cross_kernel: one slab, the totals and the weighted products (6 + n_dim, n_r) of
+// the class in flight.
+constexpr size_t grad_interp_cross_lds_bytes(int n_r, int n_dim, bool /* chi2 */) {
+  return (6 * (size_t)kGradCrossSlab + 6 + (size_t)(6 + n_dim) * n_r +
+          grad_interp_common_rows(n_r, n_dim)) *
+         kGradDraws * sizeof(double);
 }
 
 }  // namespace tc

@@ -135,11 +135,13 @@ __device__ __forceinline__ int auto_row(int i, int p, int n_bins, int n_central,
 }
 
 // chi2 = e^T P e and dchi2 / dtheta_k = 2 e^T P_sym dxi_k with P_sym = (P + P^T) / 2, from the
-// residuals e (p = 0) and the derivatives (p = 1 .. 5) at stash[(p n_r + r) 16 + draw]; threads
-// 0 .. 95 = (p, draw).
-__device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* stash, int64_t draw0) {
+// residuals e (p = 0) and the derivatives (p = 1 .. n_quantities - 1: five for a table, 5 + n_dim
+// for an interpolator) at stash[(p n_r + r) 16 + draw]; threads 0 .. 16 n_quantities - 1 =
+// (p, draw).
+__device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* stash, int64_t draw0,
+                                            int n_quantities) {
   const int t = threadIdx.x;
-  if (t >= 6 * kGradDraws) return;
+  if (t >= n_quantities * kGradDraws) return;
   const int p = t / kGradDraws, col = t % kGradDraws;
   const int n_r = a.n_r;
   const double* precision = a.chi2_data + n_r;
@@ -162,7 +164,128 @@ __device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* sta
   if (p == 0)
     a.chi2[draw] = sum;
   else
-    a.dchi2[draw * kGradParams + (p - 1)] = sum;
+    a.dchi2[draw * (n_quantities - 1) + (p - 1)] = sum;
+}
+
+// ---- the pieces of grad_auto_kernel (grad_interp_auto_kernel runs them per class and table) -----
+
+// Phase 1: thread = (bin i % 16, draw) writes w and dw of its bins, and the row of zeros.
+__device__ __forceinline__ void auto_node_loops(const GradArgs& a, const fm::Consts& k,
+                                                const Draw& d, double* w, int zero_row) {
+  const int t = threadIdx.x;
+  const int col = t % kGradDraws;
+  const int n_bins = a.n_bins, n_central = a.n_central;
+  if (t < kGradDraws) w[zero_row * kGradDraws + t] = 0.0;
+  for (int i = t / kGradDraws; i < n_bins; i += kGradThreads / kGradDraws) {
+    double out[6];
+    bin_values(a, k, d, i, out);
+    const int base = auto_row(i, 0, n_bins, n_central, zero_row);
+    const int count = i < n_central ? 3 : 6;
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+      if (p < count) w[(base + p) * kGradDraws + col] = out[p];
+  }
+}
+
+// Total of quantity p over the bins in bin order: ngal (p = 0) or dngal / dtheta_(p - 1).
+__device__ __forceinline__ double auto_total(const double* w, int p, int col, int n_bins,
+                                             int n_central, int zero_row) {
+  double sum = 0.0;
+  for (int i = 0; i < n_bins; ++i)
+    sum += w[auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col];
+  return sum;
+}
+
+// Phase 2 of one r bin, one wave: U_r = S_r W on the matrix pipe against a.matrix, then acc[0] =
+// w . U_r and acc[p] = dw_p . U_r, complete in every lane.  lane = (row group l / 16, draw
+// l % 16); D[row = l / 16 + 4 v][draw] in register v.
+__device__ __forceinline__ void auto_products(const GradArgs& a, const double* w, int r,
+                                              int zero_row, double acc[6]) {
+  const int lane = threadIdx.x % 64;
+  const int group = lane / kGradDraws, col = lane % kGradDraws;
+  const int n_bins = a.n_bins, n_central = a.n_central;
+  const int tiles = a.row_tiles, steps = a.k_steps;
+  typedef double f64x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+  for (int p = 0; p < 6; ++p) acc[p] = 0.0;
+  for (int tile = 0; tile < tiles; ++tile) {
+    const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
+    f64x4 u = {0.0, 0.0, 0.0, 0.0};
+    // four steps per round, the operands of the next round fetched ahead of this round's
+    // matrix instructions (a step beyond the last one repeats it and is not multiplied)
+    double a_now[4], a_next[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) a_now[s] = a_lane[(size_t)(s < steps ? s : steps - 1) * 64];
+    for (int step0 = 0; step0 < steps; step0 += 4) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int next = step0 + 4 + s;
+        a_next[s] = a_lane[(size_t)(next < steps ? next : steps - 1) * 64];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int step = step0 + s;
+        if (step < steps) {
+          const int j = 4 * step + group;
+          const double b = w[auto_row(j, 0, n_bins, n_central, zero_row) * kGradDraws + col];
+          u = __builtin_amdgcn_mfma_f64_16x16x4f64(a_now[s], b, u, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) a_now[s] = a_next[s];
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int i = 16 * tile + group + 4 * v;
+      const double uv = u[v];
+#pragma unroll
+      for (int p = 0; p < 6; ++p)
+        acc[p] = fma(w[auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col], uv, acc[p]);
+    }
+  }
+  // the four row groups of a draw: (0 + 1) + (2 + 3), in every lane
+#pragma unroll
+  for (int p = 0; p < 6; ++p) {
+    acc[p] += __shfl_xor(acc[p], 16);
+    acc[p] += __shfl_xor(acc[p], 32);
+  }
+}
+
+// Phase 3, mode auto: xi = q / ngal^2 and dxi_k = dq_k / ngal^2 - 2 xi dngal_k / ngal with dq_k =
+// 2 dw_k . U, from the products and the totals (6, 16) of the draw's column.
+__device__ __forceinline__ double auto_xi(const double acc[6], double inv_ngal2) {
+  return acc[0] * inv_ngal2;
+}
+__device__ __forceinline__ double auto_dxi(const double acc[6], int p, double xi,
+                                           const double* total, int col, double inv_ngal,
+                                           double inv_ngal2) {
+  return 2.0 * acc[p] * inv_ngal2 - 2.0 * xi * total[p * kGradDraws + col] * inv_ngal;
+}
+
+// ---- the pieces of grad_cross_kernel ------------------------------------------------------------
+
+// w and dw of the bins slab0 .. slab0 + count - 1 into the slab (6, kGradCrossSlab, 16).
+__device__ __forceinline__ void cross_node_loops(const GradArgs& a, const fm::Consts& k,
+                                                 const Draw& d, int slab0, int count, double* w) {
+  const int t = threadIdx.x;
+  const int col = t % kGradDraws;
+  for (int li = t / kGradDraws; li < count; li += kGradThreads / kGradDraws) {
+    double out[6];
+    bin_values(a, k, d, slab0 + li, out);
+#pragma unroll
+    for (int p = 0; p < 6; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
+  }
+}
+
+// sum + T_r[slab] . (quantity p of the slab) for one draw, in bin order.
+__device__ __forceinline__ double cross_slab_product(const double* matrix, int n_r, int r,
+                                                     int slab0, int count, const double* w, int p,
+                                                     int col, double sum) {
+  const double* column = matrix + (size_t)slab0 * n_r + r;
+  const double* rows = w + (size_t)p * kGradCrossSlab * kGradDraws + col;
+  for (int li = 0; li < count; ++li)
+    sum = fma(column[(size_t)li * n_r], rows[li * kGradDraws], sum);
+  return sum;
 }
 
 }  // namespace grad
@@ -183,24 +306,13 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   // phase 1: thread = (bin i % 16, draw)
   {
     const grad::Draw d = grad::load_draw(a, k, draw0 + col);
-    if (t < kGradDraws) w[zero_row * kGradDraws + t] = 0.0;
-    for (int i = t / kGradDraws; i < n_bins; i += kGradThreads / kGradDraws) {
-      double out[6];
-      grad::bin_values(a, k, d, i, out);
-      const int base = grad::auto_row(i, 0, n_bins, n_central, zero_row);
-      const int count = i < n_central ? 3 : 6;
-#pragma unroll
-      for (int p = 0; p < 6; ++p)
-        if (p < count) w[(base + p) * kGradDraws + col] = out[p];
-    }
+    grad::auto_node_loops(a, k, d, w, zero_row);
   }
   __syncthreads();
   // totals over the bins in bin order: ngal and its derivatives
   if (t < 6 * kGradDraws) {
     const int p = t / kGradDraws;
-    double sum = 0.0;
-    for (int i = 0; i < n_bins; ++i)
-      sum += w[grad::auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col];
+    const double sum = grad::auto_total(w, p, col, n_bins, n_central, zero_row);
     total[t] = sum;
     const int64_t draw = draw0 + col;
     if (draw < a.n_draws) {
@@ -212,60 +324,16 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   }
   __syncthreads();
 
-  // phase 2: lane = (row group l / 16, draw l % 16); D[row = l / 16 + 4 v][draw] in register v
+  // phase 2: wave v takes the r bins v, v + 4, ...
   const int lane = t % 64, wave = t / 64;
   const int group = lane / kGradDraws;
-  const int tiles = a.row_tiles, steps = a.k_steps;
   const double ngal = total[col];
   const double inv_ngal = 1.0 / ngal;
   const double inv_ngal2 = 1.0 / (ngal * ngal);
-  typedef double f64x4 __attribute__((ext_vector_type(4)));
   for (int r = wave; r < n_r; r += kGradWaves) {
-    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int tile = 0; tile < tiles; ++tile) {
-      const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
-      f64x4 u = {0.0, 0.0, 0.0, 0.0};
-      // four steps per round, the operands of the next round fetched ahead of this round's
-      // matrix instructions (a step beyond the last one repeats it and is not multiplied)
-      double a_now[4], a_next[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) a_now[s] = a_lane[(size_t)(s < steps ? s : steps - 1) * 64];
-      for (int step0 = 0; step0 < steps; step0 += 4) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int next = step0 + 4 + s;
-          a_next[s] = a_lane[(size_t)(next < steps ? next : steps - 1) * 64];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int step = step0 + s;
-          if (step < steps) {
-            const int j = 4 * step + group;
-            const double b = w[grad::auto_row(j, 0, n_bins, n_central, zero_row) * kGradDraws + col];
-            u = __builtin_amdgcn_mfma_f64_16x16x4f64(a_now[s], b, u, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) a_now[s] = a_next[s];
-      }
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int i = 16 * tile + group + 4 * v;
-        const double uv = u[v];
-#pragma unroll
-        for (int p = 0; p < 6; ++p)
-          acc[p] = fma(w[grad::auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col], uv,
-                       acc[p]);
-      }
-    }
-    // the four row groups of a draw: (0 + 1) + (2 + 3), in every lane
-#pragma unroll
-    for (int p = 0; p < 6; ++p) {
-      acc[p] += __shfl_xor(acc[p], 16);
-      acc[p] += __shfl_xor(acc[p], 32);
-    }
-    // xi = q / ngal^2, dxi_k = dq_k / ngal^2 - 2 xi dngal_k / ngal with dq_k = 2 dw_k . U
-    const double xi = acc[0] * inv_ngal2;
+    double acc[6];
+    grad::auto_products(a, w, r, zero_row, acc);
+    const double xi = grad::auto_xi(acc, inv_ngal2);
     const int64_t draw = draw0 + col;
     if (group == 0) {
       if (a.xi != nullptr) {
@@ -276,8 +344,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
     }
 #pragma unroll
     for (int p = 1; p < 6; ++p) {
-      const double dxi =
-          2.0 * acc[p] * inv_ngal2 - 2.0 * xi * total[p * kGradDraws + col] * inv_ngal;
+      const double dxi = grad::auto_dxi(acc, p, xi, total, col, inv_ngal, inv_ngal2);
       if (group == 0) {
         if (a.xi != nullptr) {
           if (draw < a.n_draws) a.dxi[(draw * kGradParams + (p - 1)) * n_r + r] = dxi;
@@ -289,7 +356,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   }
   if (a.xi == nullptr) {
     __syncthreads();
-    grad::finish_chi2(a, stash, draw0);
+    grad::finish_chi2(a, stash, draw0, 6);
   }
 }
 
@@ -313,12 +380,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   for (int slab0 = 0; slab0 < n_bins; slab0 += kGradCrossSlab) {
     const int count = min(kGradCrossSlab, n_bins - slab0);
     __syncthreads();
-    for (int li = t / kGradDraws; li < count; li += kGradThreads / kGradDraws) {
-      double out[6];
-      grad::bin_values(a, k, d, slab0 + li, out);
-#pragma unroll
-      for (int p = 0; p < 6; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
-    }
+    grad::cross_node_loops(a, k, d, slab0, count, w);
     __syncthreads();
     if (t < 6 * kGradDraws) {
       const int p = t / kGradDraws;
@@ -326,13 +388,8 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
     }
     for (int item = t; item < n_items; item += kGradThreads) {
       const int r = item / (6 * kGradDraws), p = item / kGradDraws % 6;
-      const double* column = a.matrix + (size_t)slab0 * n_r + r;
-      const double* rows = w + (size_t)p * kGradCrossSlab * kGradDraws + col;
       const size_t slot = ((size_t)p * n_r + r) * kGradDraws + col;
-      double sum = y[slot];
-      for (int li = 0; li < count; ++li)
-        sum = fma(column[(size_t)li * n_r], rows[li * kGradDraws], sum);
-      y[slot] = sum;
+      y[slot] = grad::cross_slab_product(a.matrix, n_r, r, slab0, count, w, p, col, y[slot]);
     }
   }
   if (t < 6 * kGradDraws) {
@@ -373,7 +430,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   }
   if (a.xi == nullptr) {
     __syncthreads();
-    grad::finish_chi2(a, y, draw0);
+    grad::finish_chi2(a, y, draw0, 6);
   }
 }
 

@@ -772,6 +772,8 @@ int launch_cross_instance(bool assembias, bool modulate, bool defer, int device,
                           hipEvent_t k1, const tc::CrossFusedArgs& ca);
 int launch_grad_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                          hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
+int launch_grad_interp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
+                                hipEvent_t k0, hipEvent_t k1, const tc::GradInterpArgs& ga);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_resident_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_ensemble_kernel(int device, int grid, int lds_bytes, hipStream_t stream,

@@ -32,6 +32,16 @@ struct tc_interp {
     void* percentile = nullptr;
   };
   std::map<int, SinglePointers> single_pointers;
+  // gradients (grad_interp_kernels.hip.h), built at the first gradient call: the walk over the
+  // tables -- class by class, inside a class in list order -- as the grid node and the gradient
+  // matrix (launch.hip: build_grad_table) of every table in walk order
+  struct GradWalk {
+    bool built = false;
+    void* class_begin = nullptr;              // (classes + 1)
+    void* node = nullptr;                     // (K, D)
+    void* matrices = nullptr;                 // (K) device pointers
+  };
+  GradWalk grad_walk;
   // Lanes (stream + workspaces), as for a table handle: consecutive device-pointer and
   // asynchronous calls alternate between them, so that the occupation / spline-weight /
   // finalisation kernels and the ramps of one call's contraction hide behind the
@@ -79,6 +89,27 @@ bool same_bins(const tc_table* a, const tc_table* b) {
   return a->n_h == b->n_h && a->log_min == b->log_min && a->log_max == b->log_max &&
          a->percentile == b->percentile && a->dist_index == b->dist_index &&
          a->legacy == b->legacy;
+}
+
+// Data vector and precision matrix of a likelihood: uploaded when they differ from the last upload.
+int upload_chi2_data(tc_interp* it, const double* data, const double* precision) {
+  const int n_r = it->tables[0]->n_r;
+  const size_t data_count = (size_t)(n_r + 1) * n_r;
+  int status = it->chi2_data.reserve(data_count * 8, it->stream);
+  if (status != TC_OK) return status;
+  if (it->chi2_host.size() != data_count ||
+      memcmp(it->chi2_host.data(), data, (size_t)n_r * 8) != 0 ||
+      memcmp(it->chi2_host.data() + n_r, precision, (size_t)n_r * n_r * 8) != 0) {
+    // (earlier kernels of any lane may still read the old ones)
+    status = tc_interp_synchronize(it);
+    if (status != TC_OK) return status;
+    it->chi2_host.assign(data, data + n_r);
+    it->chi2_host.insert(it->chi2_host.end(), precision, precision + (size_t)n_r * n_r);
+    TC_HIP(hipMemcpyAsync(it->chi2_data.ptr, it->chi2_host.data(), data_count * 8,
+                          hipMemcpyHostToDevice, it->stream));
+    TC_HIP(hipStreamSynchronize(it->stream));
+  }
+  return TC_OK;
 }
 
 int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta,
@@ -508,6 +539,8 @@ int tc_interp_destroy(tc_interp* it) {
     for (void* p : {kv.second.log_m, kv.second.m, kv.second.weight, kv.second.n_h,
                     kv.second.percentile})
       if (p) (void)hipFree(p);
+  for (void* p : {it->grad_walk.class_begin, it->grad_walk.node, it->grad_walk.matrices})
+    if (p) (void)hipFree(p);
   for (tc_interp::Lane& lane : it->lanes) {
     for (void* p : {lane.d_nbufs, lane.d_nbufs32, lane.d_ngal_parts})
       if (p) (void)hipFree(p);
@@ -580,21 +613,14 @@ int tc_interp_predict_zheng07_batch_device(tc_interp* it, const double* theta_de
 
 namespace {
 
-// Un-batched Interpolator.predict: ONE launch evaluates every table (single_draw_kernel
-// with grid = tables x workgroups per table, each workgroup computing the occupations of
-// its table's class itself), the partial sums land in page-locked host memory, and the
-// host normalises each table, forms the tensor-product spline weights
-// (interpolator.py:275-331) and adds the tables in list order.  No device-side
-// combination, no second launch: ~25 us against ~70 us for the four-launch batched path.
-int interp_predict_one(tc_interp* it, const double* theta, int n_theta, const double* x,
-                       int n_gauss, unsigned flags, double* ngal, double* xi) {
-  tc_table* t0 = it->tables[0];
-  const int n_classes = (int)it->class_table.size();
+// Per class the device pointers of its quadrature constants for n_gauss nodes, n_h and
+// percentiles, as device arrays (made once per n_gauss).
+int class_pointers(tc_interp* it, int n_gauss, const tc_interp::SinglePointers** out) {
   auto found = it->single_pointers.find(n_gauss);
   if (found == it->single_pointers.end()) {
     std::vector<void*> log_m, m, weight, n_h, percentile;
-    for (int v = 0; v < n_classes; ++v) {
-      tc_table* t = it->tables[it->class_table[v]];
+    for (int table : it->class_table) {
+      tc_table* t = it->tables[table];
       Quadrature* q = nullptr;
       int status = get_quadrature(t, n_gauss, &q);
       if (status != TC_OK) return status;
@@ -613,7 +639,23 @@ int interp_predict_one(tc_interp* it, const double* theta, int n_theta, const do
     if (status != TC_OK) return status;
     found = it->single_pointers.emplace(n_gauss, p).first;
   }
-  const tc_interp::SinglePointers& p = found->second;
+  *out = &found->second;
+  return TC_OK;
+}
+
+// Un-batched Interpolator.predict: ONE launch evaluates every table (single_draw_kernel
+// with grid = tables x workgroups per table, each workgroup computing the occupations of
+// its table's class itself), the partial sums land in page-locked host memory, and the
+// host normalises each table, forms the tensor-product spline weights
+// (interpolator.py:275-331) and adds the tables in list order.  No device-side
+// combination, no second launch: ~25 us against ~70 us for the four-launch batched path.
+int interp_predict_one(tc_interp* it, const double* theta, int n_theta, const double* x,
+                       int n_gauss, unsigned flags, double* ngal, double* xi) {
+  tc_table* t0 = it->tables[0];
+  const tc_interp::SinglePointers* pointers = nullptr;
+  int status = class_pointers(it, n_gauss, &pointers);
+  if (status != TC_OK) return status;
+  const tc_interp::SinglePointers& p = *pointers;
   const int rt = t0->rt, n_tables = it->n_tables;
   // One workgroup of 1024 threads per CU at a time (16 of the 24 wave slots its registers
   // allow): all tables' workgroups in ONE round where that leaves each of them at most four
@@ -626,7 +668,7 @@ int interp_predict_one(tc_interp* it, const double* theta, int n_theta, const do
   if (t0->tuning.single_round && one_round >= 1 && one_round < blocks && 4 * one_round >= blocks)
     blocks = one_round;
   SingleWorkspace& workspace = it->single_ws;
-  int status = workspace.prepare(n_tables, blocks, rt, 0);
+  status = workspace.prepare(n_tables, blocks, rt, 0);
   if (status != TC_OK) return status;
   double* ws = workspace.ngal();
   tc::SingleArgs sa{};
@@ -868,22 +910,8 @@ int tc_interp_chi2_zheng07_batch_device(tc_interp* it, const double* theta_devic
                          : t0->tuning.pipeline ? (int)(it->device_calls % it->n_lanes)
                                                : 0;
   tc_interp::Lane& L = it->lanes[lane_index];
-  // data vector and precision matrix: uploaded when they differ from the last upload
-  const size_t data_count = (size_t)(n_r + 1) * n_r;
-  int status = it->chi2_data.reserve(data_count * 8, it->stream);
+  int status = upload_chi2_data(it, data, precision);
   if (status != TC_OK) return status;
-  if (it->chi2_host.size() != data_count ||
-      memcmp(it->chi2_host.data(), data, (size_t)n_r * 8) != 0 ||
-      memcmp(it->chi2_host.data() + n_r, precision, (size_t)n_r * n_r * 8) != 0) {
-    // (earlier kernels of any lane may still read the old ones)
-    status = tc_interp_synchronize(it);
-    if (status != TC_OK) return status;
-    it->chi2_host.assign(data, data + n_r);
-    it->chi2_host.insert(it->chi2_host.end(), precision, precision + (size_t)n_r * n_r);
-    TC_HIP(hipMemcpyAsync(it->chi2_data.ptr, it->chi2_host.data(), data_count * 8,
-                          hipMemcpyHostToDevice, it->stream));
-    TC_HIP(hipStreamSynchronize(it->stream));
-  }
   status = L.chi2_xi.reserve((size_t)n_draws * n_r * 8, L.stream);
   if (status != TC_OK) return status;
   const double* d_data = (const double*)it->chi2_data.ptr;
@@ -1015,6 +1043,244 @@ int tc_interp_chi2_zheng07_batch_async(tc_interp* it, const double* theta, int n
                                        int64_t* ticket) {
   return interp_async(it, theta, n_theta, x, n_draws, n_gauss, flags, data, precision, ngal,
                       chi2, true, ticket, false);
+}
+
+// ---- gradients (grad_interp_kernels.hip.h) ------------------------------------------------
+
+namespace {
+
+size_t interp_grad_lds(const tc_interp* it, bool chi2) {
+  const tc_table* t0 = it->tables[0];
+  return t0->mode == TC_MODE_AUTO
+             ? tc::grad_interp_auto_lds_bytes(t0->n_bins, t0->plan.n_central, t0->n_r, it->n_dim,
+                                              chi2)
+             : tc::grad_interp_cross_lds_bytes(t0->n_r, it->n_dim, chi2);
+}
+
+// What the table entry points refuse (check_grad_args on the first table: flags, float32, the
+// shape of theta) and a grid that does not fit the LDS of a workgroup.
+int check_interp_grad_args(const tc_interp* it, const void* theta, int n_theta, int64_t n_draws,
+                           int n_gauss, unsigned flags, bool chi2) {
+  TC_CHECK(it != nullptr, "interp handle is NULL");
+  const tc_table* t0 = it->tables[0];
+  const int status = check_grad_args(t0, theta, n_theta, n_draws, n_gauss, flags, chi2);
+  if (status != TC_OK) return status;
+  const size_t lds = interp_grad_lds(it, chi2);
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "gradients: a grid of %d dimensions over tables of %d bins and %d correlation "
+                "function bins needs %zu bytes of LDS per workgroup, beyond the %d there are",
+                it->n_dim, t0->n_bins, t0->n_r, lds, kMaxLdsBytes);
+  return TC_OK;
+}
+
+int build_grad_walk(tc_interp* it) {
+  if (it->grad_walk.built) return TC_OK;
+  const int n_classes = (int)it->class_table.size();
+  std::vector<int32_t> class_begin(1, 0), node;
+  std::vector<void*> matrices;
+  for (int v = 0; v < n_classes; ++v) {
+    for (int k = 0; k < it->n_tables; ++k) {
+      if (it->table_class[k] != v) continue;
+      const int status = build_grad_table(it->tables[k]);
+      if (status != TC_OK) return status;
+      matrices.push_back(it->tables[k]->grad.d_matrix);
+      node.insert(node.end(), it->table_node.begin() + (size_t)k * it->n_dim,
+                  it->table_node.begin() + (size_t)(k + 1) * it->n_dim);
+    }
+    class_begin.push_back((int32_t)matrices.size());
+  }
+  // (into locals: a failure half-way leaves nothing behind)
+  void* uploaded[3] = {nullptr, nullptr, nullptr};
+  int status = upload(class_begin, &uploaded[0]);
+  if (status == TC_OK) status = upload(node, &uploaded[1]);
+  if (status == TC_OK) status = upload(matrices, &uploaded[2]);
+  if (status != TC_OK) {
+    for (void* p : uploaded)
+      if (p) (void)hipFree(p);
+    return status;
+  }
+  it->grad_walk.class_begin = uploaded[0];
+  it->grad_walk.node = uploaded[1];
+  it->grad_walk.matrices = uploaded[2];
+  it->grad_walk.built = true;
+  return TC_OK;
+}
+
+// One launch per slab of draws on the call's lane.  xi / dxi NULL: chi2 / dchi2 from chi2_data.
+int interp_grad_device(tc_interp* it, const double* theta_device, const double* x_device,
+                       int64_t n_draws, int n_gauss, unsigned flags, double* ngal, double* xi,
+                       double* dngal, double* dxi, const double* chi2_data, double* chi2,
+                       double* dchi2) {
+  TC_HIP(hipSetDevice(it->device));
+  tc_table* t0 = it->tables[0];
+  int status = TC_OK;
+  for (tc_table* t : it->tables)
+    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  const tc_interp::SinglePointers* pointers = nullptr;
+  status = class_pointers(it, n_gauss, &pointers);
+  if (status == TC_OK) status = build_grad_walk(it);
+  if (status != TC_OK) return status;
+  it->cur = it->force_lane >= 0 ? it->force_lane
+            : t0->tuning.pipeline ? (int)(it->device_calls++ % it->n_lanes)
+                                  : 0;
+  tc_interp::Lane& L = it->lanes[it->cur];
+  const bool with_chi2 = xi == nullptr;
+  const int n_r = t0->n_r, n_dim = it->n_dim, n_cols = tc::kGradParams + n_dim;
+  tc::GradInterpArgs ga{};
+  ga.table.n_bins = t0->n_bins;
+  ga.table.n_central = t0->plan.n_central;
+  ga.table.n_gauss = n_gauss;
+  ga.table.n_r = n_r;
+  ga.table.modulate = (flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0 ? 1 : 0;
+  ga.table.math_table = (const double*)t0->d_math_table;
+  ga.table.row_tiles = tc::grad_row_tiles(t0->n_bins);
+  ga.table.k_steps = tc::grad_k_steps(t0->n_bins);
+  ga.table.chi2_data = chi2_data;
+  ga.n_dim = n_dim;
+  ga.n_classes = (int)it->class_table.size();
+  for (int d = 0; d < n_dim; ++d) {
+    ga.n_axis[d] = (int)it->xp[d].size();
+    ga.axis_offset[d] = it->axis_offset[d];
+    ga.a_offset[d] = it->a_offset[d];
+  }
+  ga.xp = (const double*)it->d_xp;
+  ga.a = (const double*)it->d_a;
+  ga.class_begin = (const int32_t*)it->grad_walk.class_begin;
+  ga.walk_node = (const int32_t*)it->grad_walk.node;
+  ga.matrices = (const double* const*)it->grad_walk.matrices;
+  ga.class_log_m = (const double* const*)pointers->log_m;
+  ga.class_m = (const double* const*)pointers->m;
+  ga.class_weight = (const double* const*)pointers->weight;
+  ga.class_n_h = (const double* const*)pointers->n_h;
+  const int lds = (int)interp_grad_lds(it, with_chi2);
+  const int64_t slab = max_slab(t0);
+  for (int64_t begin = 0; begin < n_draws; begin += slab) {
+    const int64_t n = std::min(slab, n_draws - begin);
+    Range range("interpolator gradients (one launch)");
+    ga.table.theta = theta_device + begin * tc::kGradParams;
+    ga.x = x_device + begin * n_dim;
+    ga.table.n_draws = n;
+    ga.table.ngal = ngal + begin;
+    ga.table.dngal = dngal + begin * n_cols;
+    ga.table.xi = xi ? xi + begin * n_r : nullptr;
+    ga.table.dxi = dxi ? dxi + begin * n_cols * n_r : nullptr;
+    ga.table.chi2 = chi2 ? chi2 + begin : nullptr;
+    ga.table.dchi2 = dchi2 ? dchi2 + begin * n_cols : nullptr;
+    const dim3 grid((unsigned)((n + tc::kGradDraws - 1) / tc::kGradDraws));
+    hipEvent_t k0 = nullptr, k1 = nullptr;       // timed through the first table's timer
+    status = next_kernel_events(t0, &k0, &k1);
+    if (status != TC_OK) return status;
+    status = launch_grad_interp_instance(t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
+    if (status != TC_OK) return status;
+    t0->last_workgroups = (int)grid.x;
+    t0->last_waves = tc::kGradWaves;
+    t0->last_splits = 0;
+    t0->last_lds = lds;
+  }
+  return TC_OK;
+}
+
+// Host arrays: the draws go up and the four result arrays come down on lane 0; `value` / `dvalue`
+// are xi and dxi, or (chi2_data given) chi2 and dchi2.
+int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_t n_draws,
+                     int n_gauss, unsigned flags, const double* chi2_data, double* ngal,
+                     double* value, double* dngal, double* dvalue) {
+  TC_HIP(hipSetDevice(it->device));
+  const bool chi2 = chi2_data != nullptr;
+  const size_t n = (size_t)n_draws, n_r = (size_t)it->tables[0]->n_r;
+  const size_t np = tc::kGradParams, n_cols = np + it->n_dim;
+  const size_t value_count = chi2 ? n : n * n_r;
+  int status = it->theta.reserve(n * np * 8, it->stream);
+  if (status == TC_OK) status = it->x.reserve(n * it->n_dim * 8, it->stream);
+  if (status == TC_OK) status = it->out_ngal.reserve(n * (1 + n_cols) * 8, it->stream);
+  if (status == TC_OK) status = it->out_xi.reserve(value_count * (1 + n_cols) * 8, it->stream);
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, n * np * 8, hipMemcpyHostToDevice, it->stream));
+  TC_HIP(hipMemcpyAsync(it->x.ptr, x, n * it->n_dim * 8, hipMemcpyHostToDevice, it->stream));
+  double* d_ngal = (double*)it->out_ngal.ptr;
+  double* d_dngal = d_ngal + n;
+  double* d_value = (double*)it->out_xi.ptr;
+  double* d_dvalue = d_value + value_count;
+  it->force_lane = 0;
+  status = chi2 ? interp_grad_device(it, (const double*)it->theta.ptr, (const double*)it->x.ptr,
+                                     n_draws, n_gauss, flags, d_ngal, nullptr, d_dngal, nullptr,
+                                     chi2_data, d_value, d_dvalue)
+                : interp_grad_device(it, (const double*)it->theta.ptr, (const double*)it->x.ptr,
+                                     n_draws, n_gauss, flags, d_ngal, d_value, d_dngal, d_dvalue,
+                                     nullptr, nullptr, nullptr);
+  it->force_lane = -1;
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, it->stream));
+  TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * n_cols * 8, hipMemcpyDeviceToHost, it->stream));
+  TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, it->stream));
+  TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * n_cols * 8, hipMemcpyDeviceToHost,
+                        it->stream));
+  TC_HIP(hipStreamSynchronize(it->stream));
+  return TC_OK;
+}
+
+}  // namespace
+
+int tc_interp_predict_grad_zheng07_batch_device(tc_interp* it, const double* theta_device,
+                                                int n_theta, const double* x_device,
+                                                int64_t n_draws, int n_gauss, unsigned flags,
+                                                double* ngal_device, double* xi_device,
+                                                double* dngal_device, double* dxi_device) {
+  const int status =
+      check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, false);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x_device && ngal_device && xi_device && dngal_device && dxi_device, "NULL pointer");
+  return interp_grad_device(it, theta_device, x_device, n_draws, n_gauss, flags, ngal_device,
+                            xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr);
+}
+
+int tc_interp_predict_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
+                                         const double* x, int64_t n_draws, int n_gauss,
+                                         unsigned flags, double* ngal, double* xi, double* dngal,
+                                         double* dxi) {
+  const int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, false);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x && ngal && xi && dngal && dxi, "NULL pointer");
+  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi);
+}
+
+int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* it, const double* theta_device,
+                                             int n_theta, const double* x_device,
+                                             int64_t n_draws, int n_gauss, unsigned flags,
+                                             const double* data, const double* precision,
+                                             double* ngal_device, double* chi2_device,
+                                             double* dngal_device, double* dchi2_device) {
+  int status = check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, true);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x_device && data && precision && ngal_device && chi2_device && dngal_device &&
+               dchi2_device,
+           "NULL pointer");
+  TC_HIP(hipSetDevice(it->device));
+  status = upload_chi2_data(it, data, precision);
+  if (status != TC_OK) return status;
+  return interp_grad_device(it, theta_device, x_device, n_draws, n_gauss, flags, ngal_device,
+                            nullptr, dngal_device, nullptr, (const double*)it->chi2_data.ptr,
+                            chi2_device, dchi2_device);
+}
+
+int tc_interp_chi2_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
+                                      const double* x, int64_t n_draws, int n_gauss,
+                                      unsigned flags, const double* data,
+                                      const double* precision, double* ngal, double* chi2,
+                                      double* dngal, double* dchi2) {
+  int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, true);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x && data && precision && ngal && chi2 && dngal && dchi2, "NULL pointer");
+  TC_HIP(hipSetDevice(it->device));
+  status = upload_chi2_data(it, data, precision);
+  if (status != TC_OK) return status;
+  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags,
+                          (const double*)it->chi2_data.ptr, ngal, chi2, dngal, dchi2);
 }
 
 int tc_interp_wait(tc_interp* it, int64_t ticket) {

@@ -606,6 +606,16 @@ int tc_spline_interpolation_matrix(int n, const double* xp, double* a) {
   return TC_OK;
 }
 
+int tc_spline_weights(int n, const double* xp, const double* a, double x, double* weight,
+                      double* dweight, int* segment) {
+  TC_CHECK(xp != nullptr && a != nullptr && weight != nullptr && dweight != nullptr,
+           "invalid arguments");
+  TC_CHECK(n >= 4, "Cannot perform spline interpolation with less than 4 values.");
+  const int seg = tc::spline_weights(n, xp, a, x, 0, 1, 1, weight, dweight);
+  if (segment != nullptr) *segment = seg;
+  return TC_OK;
+}
+
 int tc_debug_node_groups(int n_bins, int n_central, const double* log_min,
                          const double* log_max, int32_t* begin, int32_t* member,
                          int* n_groups, int* n_central_groups) {

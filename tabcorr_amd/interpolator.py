@@ -23,7 +23,9 @@ from . import _lib
 from . import pinned
 from .galtable import GalTypeTable
 from .models import device_spec
-from .tabcorr import TabCorr, XI_KEYS, NGAL_KEYS, _flags, _unbatch
+from .models import ZHENG07_KEYS
+from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _flags, _grad_theta,
+                      _unbatch)
 
 OUT_OF_RANGE = ('The x-coordinates are outside of the interpolation ' +
                 'range and extrapolation is turned off.')
@@ -438,6 +440,131 @@ class Interpolator:
                 _lib.as_double_p(data), _lib.as_double_p(precision),
                 _lib.as_double_p(ngal), _lib.as_double_p(chi2)))
         return ngal, chi2
+
+    # -- analytic gradients ----------------------------------------------------------
+
+    def _grad_inputs(self, theta, x, extrapolate):
+        """``theta (n, 5)`` and ``x (n, D)`` of the gradient calls, checked
+        before any device is touched."""
+        theta = _grad_theta(theta)
+        x = _lib.contiguous(np.atleast_2d(x))
+        if x.shape != (len(theta), len(self.keys)):
+            raise ValueError('x must have shape (n_draws, {}).'.format(
+                len(self.keys)))
+        self._check_range(x, extrapolate)
+        return theta, x
+
+    def predict_batch_grad(self, theta, x, n_gauss_prim=10, extrapolate=False,
+                           modulate_with_cenocc=False):
+        """`predict_batch` together with the exact derivatives of its results
+        with respect to the five Zheng07 parameters and the ``D`` extra
+        parameters (columns: `ZHENG07_KEYS`, then ``self.keys``), in one
+        kernel launch: what a best-fit search, a Fisher forecast or an HMC
+        sampler over ``(theta, x)`` would otherwise difference `predict_batch`
+        ``2 (5 + D)`` times for.
+
+        The interpolated result is linear in the tables' results, so the
+        derivative with respect to ``theta`` is the interpolated table
+        gradient (`TabCorr.predict_batch_grad`, with its kinks in ``logM0``)
+        and the one with respect to ``x`` the derivative of the spline
+        weights.  The not-a-knot spline is C2: there is no kink in ``x``; an
+        ``x`` outside the grid (``extrapolate=True``) gets the derivative of
+        the outermost polynomial.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )``
+        xi : ``(n_draws, ) + tpcf_shape``
+        dngal : ``(n_draws, 5 + D)``
+        dxi : ``(n_draws, 5 + D) + tpcf_shape``
+
+        Raises ``NotImplementedError`` for what the kernel does not serve
+        (float32 tables, grids whose rows do not fit the LDS of a workgroup).
+        """
+        theta, x = self._grad_inputs(theta, x, extrapolate)
+        device = self.to_device()
+        n_draws, n_r = len(theta), device.tables[0].n_r
+        n_cols = len(ZHENG07_KEYS) + len(self.keys)
+        ngal = np.empty(n_draws)
+        xi = np.empty((n_draws, n_r))
+        dngal = np.empty((n_draws, n_cols))
+        dxi = np.empty((n_draws, n_cols, n_r))
+        with device.lock:
+            _lib.check(device.lib.tc_interp_predict_grad_zheng07_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                _lib.as_double_p(x), n_draws, n_gauss_prim,
+                _flags(False, modulate_with_cenocc), _lib.as_double_p(ngal),
+                _lib.as_double_p(xi), _lib.as_double_p(dngal),
+                _lib.as_double_p(dxi)))
+        shape = tuple(self.tabcorr_list[0].tpcf_shape)
+        return (ngal, xi.reshape((n_draws, ) + shape), dngal,
+                dxi.reshape((n_draws, n_cols) + shape))
+
+    def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
+                        extrapolate=False, modulate_with_cenocc=False):
+        """`chi2_batch` with its gradient with respect to ``(theta, x)``:
+        ``dchi2[:, k] = 2 (xi - data)^T P_sym dxi_k`` with ``P_sym =
+        (precision + precision^T) / 2``, finished on the device in the launch
+        that computes ``xi``.
+
+        Returns
+        -------
+        ngal, chi2 : ``(n_draws, )``
+        dngal, dchi2 : ``(n_draws, 5 + D)``
+        """
+        theta, x = self._grad_inputs(theta, x, extrapolate)
+        data = _lib.contiguous(np.ravel(data))
+        precision = _lib.contiguous(precision)
+        n_r = len(self.tabcorr_list[0].tpcf_matrix)
+        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
+            raise ValueError('data must have {0} entries and precision shape '
+                             '({0}, {0}).'.format(n_r))
+        device = self.to_device()
+        n_draws = len(theta)
+        n_cols = len(ZHENG07_KEYS) + len(self.keys)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal = np.empty((n_draws, n_cols))
+        dchi2 = np.empty((n_draws, n_cols))
+        with device.lock:
+            _lib.check(device.lib.tc_interp_chi2_grad_zheng07_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                _lib.as_double_p(x), n_draws, n_gauss_prim,
+                _flags(False, modulate_with_cenocc), _lib.as_double_p(data),
+                _lib.as_double_p(precision), _lib.as_double_p(ngal),
+                _lib.as_double_p(chi2), _lib.as_double_p(dngal),
+                _lib.as_double_p(dchi2)))
+        return ngal, chi2, dngal, dchi2
+
+    def predict_grad(self, model, n_gauss_prim=10, extrapolate=False,
+                     check_consistency=True):
+        """Un-batched `predict_batch_grad` for a model object: a plain
+        `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model)
+        whose ``param_dict`` holds the extra parameters.
+
+        Returns
+        -------
+        ngal : float
+        xi : numpy.ndarray of shape ``tpcf_shape``
+        dngal : dict, ``ZHENG07_KEYS + tuple(self.keys)`` -> float
+        dxi : dict, the same keys -> numpy.ndarray of shape ``tpcf_shape``
+        """
+        x = self._x_model(model)
+        if check_consistency:
+            for halotab in self.tabcorr_list:
+                halotab._check_consistency_cached(model)
+        spec = device_spec(model)
+        if spec is None or spec.family != 'zheng07' or spec.assembias:
+            raise NotImplementedError(
+                'predict_grad needs a plain Zheng07 model (no assembly bias, '
+                'no other family).')
+        ngal, xi, dngal, dxi = self.predict_batch_grad(
+            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            x[np.newaxis], n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
+            modulate_with_cenocc=spec.modulate_with_cenocc)
+        keys = tuple(ZHENG07_KEYS) + tuple(self.keys)
+        return (float(ngal[0]), xi[0],
+                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
+                {key: dxi[0, k] for k, key in enumerate(keys)})
 
     # -- generic models: host callbacks + device contraction per table -----------------
 

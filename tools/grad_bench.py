@@ -8,8 +8,15 @@ reference's example table (30 x 2 bins, 19 r values), device-resident and pipeli
 handle's lanes as bench.py's timed region is: us per tc_predict_zheng07_batch_device call (the
 forward path), per tc_predict_grad_zheng07_batch_device call and per
 tc_chi2_grad_zheng07_batch_device call, from the same run.  The bar is what a user without
-gradients pays: one-sided differences cost 6 forward calls, central ones 11.  Prints one JSON
-line and, with --notes, appends the figures to that file.
+gradients pays: one-sided differences cost 6 forward calls, central ones 11.
+
+The interpolator leg times Interpolator.chi2_grad_batch (host arrays in and out) against what a
+user pays today for the same derivatives with respect to (theta, x): 2 (5 + D) calls of
+Interpolator.chi2_batch, the forward path, timed in the same run -- on a 5 x 5 grid of 100-bin
+tables in mode auto and on the mode-cross shape of the reference's AbacusSummit interpolator (4
+tables over one axis, 1104 bins, 13 r values).
+
+Prints one JSON line and, with --notes, appends the figures to that file.
 """
 
 import argparse
@@ -23,7 +30,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from bench_legs import Device, sustained   # noqa: E402
+from bench_legs import Device, sustained, time_calls   # noqa: E402
 
 
 def measure(name, n_prim, n_sec, n_r, n_draws, seconds):
@@ -83,6 +90,50 @@ def measure(name, n_prim, n_sec, n_r, n_draws, seconds):
     return result
 
 
+def measure_interpolator(name, grid, n_prim, n_sec, n_r, mode, n_draws, seconds):
+    from tabcorr_amd import Interpolator, TabCorr, synthetic
+    tables, keys, points = synthetic.synthetic_interpolator(grid, n_prim, n_sec, (n_r, ), mode,
+                                                            seed=0)
+    interp = Interpolator(
+        [TabCorr.from_arrays(t['gal_type'], t['tpcf_matrix'], t['tpcf_shape'], t['attrs'])
+         for t in tables], {key: points[:, d] for d, key in enumerate(keys)})
+    theta = synthetic.zheng07_draws(n_draws, seed=1)
+    rng = np.random.default_rng(3)
+    x = rng.uniform(points.min(axis=0), points.max(axis=0), size=(n_draws, len(keys)))
+    data = np.ascontiguousarray(rng.uniform(0.5, 1.5, n_r))
+    precision = np.ascontiguousarray(np.eye(n_r) + 0.01 * rng.normal(size=(n_r, n_r)))
+    n_columns = 5 + len(keys)
+
+    def forward():
+        interp.chi2_batch(theta, x, data, precision)
+
+    def gradient():
+        interp.chi2_grad_batch(theta, x, data, precision)
+
+    result = {'interpolator': name, 'grid': list(grid), 'mode': mode,
+              'n_bins': len(tables[0]['gal_type']), 'n_r': n_r, 'n_draws': n_draws,
+              'forward_calls_replaced': 2 * n_columns}
+    # forward, gradient, forward again: the two forward figures bracket the drift of the run
+    result['chi2_us'] = time_calls(forward, seconds) * 1e6
+    result['chi2_grad_us'] = time_calls(gradient, seconds) * 1e6
+    result['chi2_again_us'] = time_calls(forward, seconds) * 1e6
+    forward_us = 0.5 * (result['chi2_us'] + result['chi2_again_us'])
+    result['differences_us'] = 2 * n_columns * forward_us
+    result['chi2_grad_over_chi2'] = result['chi2_grad_us'] / forward_us
+    result['differences_over_chi2_grad'] = result['differences_us'] / result['chi2_grad_us']
+    device = interp.to_device()
+    gradient()                      # (the launch tc_table_last_launch reports)
+    workgroups, waves, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    splits = ctypes.c_int()
+    from tabcorr_amd import _lib
+    _lib.check(device.lib.tc_table_last_launch(
+        device.tables[0].handle, ctypes.byref(workgroups), ctypes.byref(waves),
+        ctypes.byref(splits), ctypes.byref(lds)))
+    result['chi2_grad_workgroups'] = workgroups.value
+    result['chi2_grad_lds_bytes'] = lds.value
+    return result
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     parser.add_argument('--draws', type=int, default=10000)
@@ -91,7 +142,14 @@ def main():
     args = parser.parse_args()
     results = [measure('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
                measure("reference example table's shape", 30, 1, 19, args.draws, args.seconds)]
-    print(json.dumps({'metric': 'us per call, device-resident, pipelined', 'results': results}))
+    interpolators = [
+        measure_interpolator('5 x 5 grid of 100-bin tables', (5, 5), 50, 1, 19, 'auto', args.draws,
+                             args.seconds),
+        measure_interpolator("AbacusSummit interpolator's shape", (4, ), 276, 2, 13, 'cross',
+                             args.draws, args.seconds)]
+    print(json.dumps({'metric': 'us per call, device-resident, pipelined', 'results': results,
+                      'interpolator_metric': 'us per call, host arrays in and out',
+                      'interpolators': interpolators}))
     if args.notes:
         with open(args.notes, 'a') as notes:
             notes.write('\n## tools/grad_bench.py, %d draws per call\n\n' % args.draws)
@@ -103,6 +161,19 @@ def main():
                     r['table'], r['n_bins'], r['forward_us'], r['forward_again_us'],
                     r['grad_us'], r['chi2_grad_us'], r['grad_over_forward'],
                     r['chi2_grad_over_forward']))
+            notes.write('\nInterpolator.chi2_grad_batch against 2 (5 + D) calls of '
+                        'Interpolator.chi2_batch, host arrays in and out:\n\n')
+            notes.write('| interpolator | bins | chi2_batch us | chi2_grad_batch us | '
+                        '2 (5 + D) chi2_batch us | gradient / forward | differences / gradient | '
+                        'LDS bytes |\n')
+            notes.write('|---|---|---|---|---|---|---|---|\n')
+            for r in interpolators:
+                notes.write('| %s | %d | %.1f (%.1f after) | %.1f | %.1f (%d calls) | %.2f | %.2f '
+                            '| %d |\n' % (
+                                r['interpolator'], r['n_bins'], r['chi2_us'], r['chi2_again_us'],
+                                r['chi2_grad_us'], r['differences_us'],
+                                r['forward_calls_replaced'], r['chi2_grad_over_chi2'],
+                                r['differences_over_chi2_grad'], r['chi2_grad_lds_bytes']))
 
 
 if __name__ == '__main__':
