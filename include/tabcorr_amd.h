@@ -282,6 +282,41 @@ int tc_predict_occupation_batch(tc_table* table, const double* occupation,
                                 int64_t n_draws, unsigned flags, double* ngal,
                                 double* xi);
 
+/* Reverse-mode derivative at that seam (extension beyond the reference): the vector-Jacobian
+ * product of (ngal, xi) = predict(occupation) with respect to the occupation array, for every
+ * occupation model at once -- the caller contracts g_occupation with its own d<N>/dtheta.  With
+ * w = occupation . n_h and the cotangents g_ngal (n_draws, or NULL = 0) and g_xi (n_draws, n_r):
+ *   auto:  g_occ_i = n_h_i [g_ngal + (2 / ngal^2) sum_r g_r (S_r w)_i - (2 / ngal) sum_r g_r xi_r]
+ *   cross: g_occ_i = n_h_i [g_ngal + (1 / ngal) sum_r g_r T_ri - (1 / ngal) sum_r g_r xi_r]
+ * Outputs: ngal (n_draws), xi (n_draws, n_r), g_occupation (n_draws, n_bins) in the row order of
+ * `occupation`.  One launch per batch (host arrays: per slab of draws); ngal and xi agree with
+ * tc_predict_occupation_batch to parity (1e-10 relative), not necessarily to the bit.  A draw's
+ * results depend on the draw alone.  Where ngal = 0 the results are what IEEE arithmetic gives
+ * (NaN or inf).  flags must be 0.  TC_ERR_UNSUPPORTED with a message: TC_FLAG_SEPARATE_GAL_TYPE,
+ * a float32 compute dtype, tables whose rows do not fit the kernel's LDS (mode auto: 2 n_bins +
+ * 6 n_r + 3 <= 1280 rows of 128 bytes; mode cross: any number of bins, 3 n_r + 66 <= 1280). */
+int tc_predict_occupation_vjp_batch(tc_table* table, const double* occupation, int64_t n_draws,
+                                    unsigned flags, const double* g_ngal, const double* g_xi,
+                                    double* ngal, double* xi, double* g_occupation);
+/* The same on device pointers: enqueues on the next lane of the handle and returns. */
+int tc_predict_occupation_vjp_batch_device(tc_table* table, const double* occupation_device,
+                                           int64_t n_draws, unsigned flags,
+                                           const double* g_ngal_device,
+                                           const double* g_xi_device, double* ngal_device,
+                                           double* xi_device, double* g_occupation_device);
+/* The likelihood form: chi2 = (xi - data)^T precision (xi - data) and dchi2 / docc, i.e. the VJP
+ * with g_xi = 2 P_sym (xi - data), P_sym = (precision + precision^T) / 2, and g_ngal = 0, formed
+ * in the same launch from its own xi (mode auto runs the matrix product twice; nothing leaves
+ * the device in between).  ngal, chi2 (n_draws), dchi2_docc (n_draws, n_bins); dngal / docc is
+ * n_h.  data / precision are host arrays in both forms (uploaded when they change). */
+int tc_chi2_occupation_grad_batch(tc_table* table, const double* occupation, int64_t n_draws,
+                                  unsigned flags, const double* data, const double* precision,
+                                  double* ngal, double* chi2, double* dchi2_docc);
+int tc_chi2_occupation_grad_batch_device(tc_table* table, const double* occupation_device,
+                                         int64_t n_draws, unsigned flags, const double* data,
+                                         const double* precision, double* ngal_device,
+                                         double* chi2_device, double* dchi2_docc_device);
+
 /* ---- interpolation over a grid of tables (replaces `Interpolator`) -------------------
  *
  * tables: K handles in tabcorr_list order.  points: (K, n_dim) extra-parameter values

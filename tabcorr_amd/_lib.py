@@ -158,6 +158,20 @@ SIGNATURES = {
     'tc_predict_occupation_batch': [
         ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_uint,
         c_double_p, c_double_p],
+    'tc_predict_occupation_vjp_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_uint,
+        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_predict_occupation_vjp_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p],
+    'tc_chi2_occupation_grad_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_uint,
+        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_chi2_occupation_grad_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint,
+        c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p],
     'tc_interp_create': [c_void_pp, ctypes.c_int, ctypes.c_int, c_double_p,
                          c_void_pp],
     'tc_interp_destroy': [ctypes.c_void_p],

@@ -24,6 +24,7 @@
 #include "../../include/tabcorr_amd_testing.h"
 #include "fastmath.h"
 #include "grad.h"
+#include "vjp.h"
 #include "hostmath.h"
 #include "kernel_args.h"
 
@@ -676,6 +677,13 @@ int build_grad_table(tc_table* t);
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
              const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream);
+// Occupation VJP (vjp_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels
+// do not serve (TC_ERR_UNSUPPORTED with a message), then the launch against the gradient table.
+// g_xi NULL: the likelihood form -- chi2 and dchi2 / docc from chi2_data (on the device).
+int check_vjp_args(const tc_table* t, int64_t n_draws, unsigned flags);
+int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const double* g_ngal,
+            const double* g_xi, const double* chi2_data, double* ngal, double* xi, double* chi2,
+            double* g_occupation, hipStream_t stream);
 // Mode cross, one launch per batch (predict_cross_fused_kernel): the coefficient rows of one
 // table / K tables with common mass bins (cf->rows == 0 afterwards: not available), whether a
 // call takes that form, and the launch (`interp`: the spline part of the arguments, or NULL).
@@ -748,7 +756,7 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
                 const double* precision, double* chi2, hipStream_t stream);
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
-// inst_grad.hip) ----
+// inst_grad.hip, inst_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -774,6 +782,8 @@ int launch_grad_instance(int mode, int device, dim3 grid, int lds, hipStream_t s
                          hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
 int launch_grad_interp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                                 hipEvent_t k0, hipEvent_t k1, const tc::GradInterpArgs& ga);
+int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
+                        hipEvent_t k0, hipEvent_t k1, const tc::VjpArgs& va);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_resident_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_ensemble_kernel(int device, int grid, int lds_bytes, hipStream_t stream,

@@ -1228,6 +1228,69 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
   return TC_OK;
 }
 
+// ---- occupation VJP, one launch per batch (vjp_kernels.hip.h) ---------------------------------
+
+int check_vjp_args(const tc_table* t, int64_t n_draws, unsigned flags) {
+  TC_CHECK(t != nullptr, "table handle is NULL");
+  if (flags & TC_FLAG_SEPARATE_GAL_TYPE)
+    return fail(TC_ERR_UNSUPPORTED, "the occupation VJP is implemented for the total prediction "
+                                    "only (not separate_gal_type)");
+  if (flags != 0) return fail(TC_ERR_UNSUPPORTED, "occupation VJP: flags must be 0, got 0x%x", flags);
+  if (t->compute_dtype != TC_DTYPE_F64)
+    return fail(TC_ERR_UNSUPPORTED, "the occupation VJP needs a float64 compute dtype");
+  TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
+  const size_t lds = t->mode == TC_MODE_AUTO ? tc::vjp_auto_lds_bytes(t->n_bins, t->n_r)
+                                             : tc::vjp_cross_lds_bytes(t->n_r);
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "occupation VJP: a table of %d bins and %d correlation function bins needs %zu "
+                "bytes of LDS per workgroup, beyond the %d there are",
+                t->n_bins, t->n_r, lds, kMaxLdsBytes);
+  if (t->mode == TC_MODE_AUTO &&
+      tc::grad_operand_doubles(t->n_bins, t->n_r) * sizeof(double) > ((size_t)1 << 31))
+    return fail(TC_ERR_UNSUPPORTED, "occupation VJP: the dense matrix of %d bins exceeds 2 GiB",
+                t->n_bins);
+  return TC_OK;
+}
+
+int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const double* g_ngal,
+            const double* g_xi, const double* chi2_data, double* ngal, double* xi, double* chi2,
+            double* g_occupation, hipStream_t stream) {
+  Range range("occupation VJP (one launch)");
+  int status = build_grad_table(t);
+  if (status != TC_OK) return status;
+  tc::VjpArgs va{};
+  va.occupation = occupation_device;
+  va.n_draws = n_draws;
+  va.n_bins = t->n_bins;
+  va.n_r = t->n_r;
+  va.perm = (const int32_t*)t->d_perm;
+  va.n_h = (const double*)t->d_n_h;
+  va.matrix = (const double*)t->grad.d_matrix;
+  va.row_tiles = tc::grad_row_tiles(t->n_bins);
+  va.k_steps = tc::grad_k_steps(t->n_bins);
+  va.g_ngal = g_ngal;
+  va.g_xi = g_xi;
+  va.chi2_data = chi2_data;
+  va.ngal = ngal;
+  va.xi = xi;
+  va.chi2 = chi2;
+  va.g_occupation = g_occupation;
+  const int lds = (int)(t->mode == TC_MODE_AUTO ? tc::vjp_auto_lds_bytes(t->n_bins, t->n_r)
+                                                : tc::vjp_cross_lds_bytes(t->n_r));
+  const dim3 grid((unsigned)((n_draws + tc::kGradDraws - 1) / tc::kGradDraws));
+  hipEvent_t k0 = nullptr, k1 = nullptr;
+  status = next_kernel_events(t, &k0, &k1);
+  if (status != TC_OK) return status;
+  status = launch_vjp_instance(t->mode, t->device, grid, lds, stream, k0, k1, va);
+  if (status != TC_OK) return status;
+  t->last_workgroups = (int)grid.x;
+  t->last_waves = tc::kGradWaves;
+  t->last_splits = 0;
+  t->last_lds = lds;
+  return TC_OK;
+}
+
 // ---- mode cross, one launch per batch -----------------------------------------------------
 
 CrossFused* choose_cross_fused(tc_table* const* tables, int n_tables, CrossFused* narrow,

@@ -1140,6 +1140,138 @@ int tc_chi2_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta, in
                    chi2, dngal, dchi2);
 }
 
+// ---- occupation VJP (launch.hip: run_vjp) -------------------------------------------------
+
+namespace {
+
+// Device pointers, the slabs of a batch one launch each on the next lane (as grad_device).
+int vjp_device(tc_table* t, const double* occupation, int64_t n_draws, const double* g_ngal,
+               const double* g_xi, const double* chi2_data, double* ngal, double* xi,
+               double* chi2, double* g_occupation) {
+  TC_HIP(hipSetDevice(t->device));
+  int status = TC_OK;
+  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  tc_table::Lane& lane = t->lanes[grad_lane(t)];
+  const int64_t slab = max_slab(t);
+  const int64_t n_r = t->n_r, n_bins = t->n_bins;
+  for (int64_t begin = 0; begin < n_draws; begin += slab) {
+    const int64_t n = std::min(slab, n_draws - begin);
+    status = run_vjp(t, occupation + begin * n_bins, n, g_ngal ? g_ngal + begin : nullptr,
+                     g_xi ? g_xi + begin * n_r : nullptr, chi2_data, ngal + begin,
+                     xi ? xi + begin * n_r : nullptr, chi2 ? chi2 + begin : nullptr,
+                     g_occupation + begin * n_bins, lane.stream);
+    if (status != TC_OK) return status;
+  }
+  t->prev = t->force_lane >= 0 ? -1 : t->cur;
+  return TC_OK;
+}
+
+// Host arrays, slab by slab on lane 0: the occupations and the cotangents go up in one workspace,
+// the results come down from another.  `value`: xi (n_draws, n_r), or chi2 (n_draws) with
+// chi2_data.
+int vjp_host(tc_table* t, const double* occupation, int64_t n_draws, const double* g_ngal,
+             const double* g_xi, const double* chi2_data, double* ngal, double* value,
+             double* g_occupation) {
+  TC_HIP(hipSetDevice(t->device));
+  int status = TC_OK;
+  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  const bool chi2 = chi2_data != nullptr;
+  const size_t n_r = (size_t)t->n_r, n_bins = (size_t)t->n_bins;
+  const int64_t slab = max_slab(t);
+  for (int64_t begin = 0; begin < n_draws; begin += slab) {
+    const size_t n = (size_t)std::min(slab, n_draws - begin);
+    const size_t value_count = chi2 ? n : n * n_r;
+    status = t->occupation.reserve(n * (n_bins + n_r + 1) * 8, t->stream);
+    if (status == TC_OK) status = t->out_ngal.reserve(n * 8, t->stream);
+    if (status == TC_OK) status = t->out_xi.reserve((n * n_bins + value_count) * 8, t->stream);
+    if (status != TC_OK) return status;
+    double* d_occupation = (double*)t->occupation.ptr;
+    double* d_g_xi = d_occupation + n * n_bins;
+    double* d_g_ngal = d_g_xi + n * n_r;
+    double* d_ngal = (double*)t->out_ngal.ptr;
+    double* d_g_occupation = (double*)t->out_xi.ptr;
+    double* d_value = d_g_occupation + n * n_bins;
+    TC_HIP(hipMemcpyAsync(d_occupation, occupation + (size_t)begin * n_bins, n * n_bins * 8,
+                          hipMemcpyHostToDevice, t->stream));
+    if (!chi2)
+      TC_HIP(hipMemcpyAsync(d_g_xi, g_xi + (size_t)begin * n_r, n * n_r * 8,
+                            hipMemcpyHostToDevice, t->stream));
+    if (!chi2 && g_ngal != nullptr)
+      TC_HIP(hipMemcpyAsync(d_g_ngal, g_ngal + begin, n * 8, hipMemcpyHostToDevice, t->stream));
+    t->force_lane = 0;
+    status = vjp_device(t, d_occupation, (int64_t)n, !chi2 && g_ngal != nullptr ? d_g_ngal : nullptr,
+                        chi2 ? nullptr : d_g_xi, chi2_data, d_ngal, chi2 ? nullptr : d_value,
+                        chi2 ? d_value : nullptr, d_g_occupation);
+    t->force_lane = -1;
+    if (status != TC_OK) return status;
+    TC_HIP(hipMemcpyAsync(ngal + begin, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
+    TC_HIP(hipMemcpyAsync(value + (size_t)begin * (chi2 ? 1 : n_r), d_value, value_count * 8,
+                          hipMemcpyDeviceToHost, t->stream));
+    TC_HIP(hipMemcpyAsync(g_occupation + (size_t)begin * n_bins, d_g_occupation, n * n_bins * 8,
+                          hipMemcpyDeviceToHost, t->stream));
+    TC_HIP(hipStreamSynchronize(t->stream));
+  }
+  return TC_OK;
+}
+
+}  // namespace
+
+int tc_predict_occupation_vjp_batch_device(tc_table* t, const double* occupation_device,
+                                           int64_t n_draws, unsigned flags,
+                                           const double* g_ngal_device, const double* g_xi_device,
+                                           double* ngal_device, double* xi_device,
+                                           double* g_occupation_device) {
+  const int status = check_vjp_args(t, n_draws, flags);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(occupation_device && g_xi_device && ngal_device && xi_device && g_occupation_device,
+           "NULL pointer");
+  return vjp_device(t, occupation_device, n_draws, g_ngal_device, g_xi_device, nullptr,
+                    ngal_device, xi_device, nullptr, g_occupation_device);
+}
+
+int tc_predict_occupation_vjp_batch(tc_table* t, const double* occupation, int64_t n_draws,
+                                    unsigned flags, const double* g_ngal, const double* g_xi,
+                                    double* ngal, double* xi, double* g_occupation) {
+  const int status = check_vjp_args(t, n_draws, flags);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(occupation && g_xi && ngal && xi && g_occupation, "NULL pointer");
+  return vjp_host(t, occupation, n_draws, g_ngal, g_xi, nullptr, ngal, xi, g_occupation);
+}
+
+int tc_chi2_occupation_grad_batch_device(tc_table* t, const double* occupation_device,
+                                         int64_t n_draws, unsigned flags, const double* data,
+                                         const double* precision, double* ngal_device,
+                                         double* chi2_device, double* dchi2_docc_device) {
+  int status = check_vjp_args(t, n_draws, flags);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(occupation_device && data && precision && ngal_device && chi2_device &&
+               dchi2_docc_device,
+           "NULL pointer");
+  TC_HIP(hipSetDevice(t->device));
+  status = upload_chi2_data(t, data, precision);
+  if (status != TC_OK) return status;
+  return vjp_device(t, occupation_device, n_draws, nullptr, nullptr,
+                    (const double*)t->chi2_data.ptr, ngal_device, nullptr, chi2_device,
+                    dchi2_docc_device);
+}
+
+int tc_chi2_occupation_grad_batch(tc_table* t, const double* occupation, int64_t n_draws,
+                                  unsigned flags, const double* data, const double* precision,
+                                  double* ngal, double* chi2, double* dchi2_docc) {
+  int status = check_vjp_args(t, n_draws, flags);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(occupation && data && precision && ngal && chi2 && dchi2_docc, "NULL pointer");
+  TC_HIP(hipSetDevice(t->device));
+  status = upload_chi2_data(t, data, precision);
+  if (status != TC_OK) return status;
+  return vjp_host(t, occupation, n_draws, nullptr, nullptr, (const double*)t->chi2_data.ptr,
+                  ngal, chi2, dchi2_docc);
+}
+
 namespace {
 
 // Next ticket of the handle: its event (created on first use of the slot) and its number.

@@ -820,6 +820,114 @@ class TabCorr:
                 {key: float(dngal[0, k]) for k, key in enumerate(ZHENG07_KEYS)},
                 {key: dxi[0, k] for k, key in enumerate(ZHENG07_KEYS)})
 
+    # -- reverse mode at the occupation seam ---------------------------------------------
+
+    def _vjp_occupation(self, occupation):
+        """The 2-D contiguous occupation array of the VJP calls and whether
+        the caller's was batched; a wrong number of columns is refused before
+        any device is touched."""
+        occupation = np.asarray(occupation, dtype=np.float64)
+        batched = occupation.ndim == 2
+        occupation = _lib.contiguous(np.atleast_2d(occupation))
+        n_bins = len(self.gal_type)
+        if occupation.ndim != 2 or occupation.shape[1] != n_bins:
+            raise ValueError(
+                'The mean occupation array must have shape (n_draws, {0}) or '
+                '({0}, ), got {1}.'.format(n_bins, occupation.shape))
+        return occupation, batched
+
+    def predict_vjp(self, occupation, g_xi, g_ngal=None):
+        """``predict(occupation)`` together with its vector-Jacobian product
+        with respect to the occupation array: for cotangents ``g_ngal`` and
+        ``g_xi`` of the results, ``g_occupation[d, i] = g_ngal[d] dngal[d] /
+        dn[d, i] + sum_r g_xi[d, r] dxi[d, r] / dn[d, i]``, in one kernel
+        launch.  Contracted with the caller's own ``d<N>/dtheta`` (``n_bins``
+        numbers per parameter, e.g. from differenced `mean_occupation_batch`
+        calls) it is the gradient of any scalar of ``(ngal, xi)`` for EVERY
+        occupation model -- decorated, Leauthaud11 or custom -- whatever the
+        number of parameters.
+
+        Parameters
+        ----------
+        occupation : ``(n_draws, n_bins)`` or ``(n_bins, )`` (un-batched)
+        g_xi : ``(n_draws, ) + tpcf_shape`` (``tpcf_shape`` when un-batched)
+        g_ngal : ``(n_draws, )`` (a scalar when un-batched), or None = 0
+
+        Returns
+        -------
+        ngal : ``(n_draws, )``
+        xi : ``(n_draws, ) + tpcf_shape``
+        g_occupation : ``(n_draws, n_bins)``, in the row order of ``gal_type``
+
+        Where ``ngal = 0`` the results are NaN or inf.  Raises
+        ``NotImplementedError`` for what the kernel does not serve (float32
+        tables, very large mode-auto tables).
+        """
+        occupation, batched = self._vjp_occupation(occupation)
+        n_draws = len(occupation)
+        n_r = len(self.tpcf_matrix)
+        shape = tuple(self.tpcf_shape)
+        g_xi = np.asarray(g_xi, dtype=np.float64)
+        if g_xi.shape != ((n_draws, ) if batched else ()) + shape:
+            raise ValueError('g_xi must have shape {}, got {}.'.format(
+                ((n_draws, ) if batched else ()) + shape, g_xi.shape))
+        g_xi = _lib.contiguous(g_xi.reshape(n_draws, n_r))
+        if g_ngal is not None:
+            g_ngal = np.asarray(g_ngal, dtype=np.float64)
+            if g_ngal.shape != ((n_draws, ) if batched else ()):
+                raise ValueError('g_ngal must have shape {}, got {}.'.format(
+                    (n_draws, ) if batched else (), g_ngal.shape))
+            g_ngal = _lib.contiguous(g_ngal.reshape(n_draws))
+        device = self.to_device()
+        ngal = np.empty(n_draws)
+        xi = np.empty((n_draws, n_r))
+        g_occupation = np.empty_like(occupation)
+        with device.lock:
+            _lib.check(device.lib.tc_predict_occupation_vjp_batch(
+                device.handle, _lib.as_double_p(occupation), n_draws, 0,
+                None if g_ngal is None else _lib.as_double_p(g_ngal),
+                _lib.as_double_p(g_xi), _lib.as_double_p(ngal),
+                _lib.as_double_p(xi), _lib.as_double_p(g_occupation)))
+        xi = xi.reshape((n_draws, ) + shape)
+        if not batched:
+            return ngal[0], xi[0], g_occupation[0]
+        return ngal, xi, g_occupation
+
+    def chi2_grad_occupation(self, occupation, data, precision):
+        """``chi2 = (xi - data)^T precision (xi - data)`` of
+        ``predict(occupation)`` and its gradient with respect to the
+        occupation array -- `predict_vjp` with ``g_xi = 2 P_sym (xi - data)``,
+        ``P_sym = (precision + precision^T) / 2``, and ``g_ngal = 0``, formed
+        on the device in the same launch.  The number density needs no call:
+        ``dngal/dn = n_h`` (``gal_type['n_h']``), for a likelihood with an
+        ``ngal`` term.
+
+        Returns
+        -------
+        ngal, chi2 : ``(n_draws, )`` (scalars for a 1-D occupation)
+        dchi2_docc : ``(n_draws, n_bins)``, in the row order of ``gal_type``
+        """
+        occupation, batched = self._vjp_occupation(occupation)
+        data = _lib.contiguous(np.ravel(data))
+        precision = _lib.contiguous(precision)
+        n_r = len(self.tpcf_matrix)
+        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
+            raise ValueError('data must have {0} entries and precision shape '
+                             '({0}, {0}).'.format(n_r))
+        device = self.to_device()
+        n_draws = len(occupation)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dchi2 = np.empty_like(occupation)
+        with device.lock:
+            _lib.check(device.lib.tc_chi2_occupation_grad_batch(
+                device.handle, _lib.as_double_p(occupation), n_draws, 0,
+                _lib.as_double_p(data), _lib.as_double_p(precision),
+                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
+                _lib.as_double_p(dchi2)))
+        if not batched:
+            return ngal[0], chi2[0], dchi2[0]
+        return ngal, chi2, dchi2
+
     def chi2_batch_async(self, theta, data, precision, n_gauss_prim=10,
                          modulate_with_cenocc=False, assembias=False,
                          family='zheng07', out=None):

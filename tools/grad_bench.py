@@ -16,7 +16,12 @@ Interpolator.chi2_batch, the forward path, timed in the same run -- on a 5 x 5 g
 tables in mode auto and on the mode-cross shape of the reference's AbacusSummit interpolator (4
 tables over one axis, 1104 bins, 13 r values).
 
-Prints one JSON line and, with --notes, appends the figures to that file.
+The occupation-VJP leg times TabCorr.predict_vjp and TabCorr.chi2_grad_occupation (host arrays
+in and out) against predict(ndarray) on the same occupations -- the forward seam they
+differentiate -- and against predict_batch_grad, on the two table shapes above.
+
+Prints one JSON line and, with --notes, appends the figures to that file.  --only vjp: that leg
+alone.
 """
 
 import argparse
@@ -134,12 +139,83 @@ def measure_interpolator(name, grid, n_prim, n_sec, n_r, mode, n_draws, seconds)
     return result
 
 
+def measure_occupation_vjp(name, n_prim, n_sec, n_r, n_draws, seconds):
+    from tabcorr_amd import TabCorr, synthetic
+    table = synthetic.synthetic_table(n_prim, n_sec, (n_r, ), 'auto', seed=0)
+    halotab = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'], table['tpcf_shape'],
+                                  table['attrs'])
+    theta = synthetic.zheng07_draws(n_draws, seed=1)
+    occupation = halotab.mean_occupation_batch(theta)
+    rng = np.random.default_rng(3)
+    g_xi, g_ngal = rng.normal(size=(n_draws, n_r)), rng.normal(size=n_draws)
+    data = np.ascontiguousarray(rng.uniform(0.5, 1.5, n_r))
+    precision = np.ascontiguousarray(np.eye(n_r) + 0.01 * rng.normal(size=(n_r, n_r)))
+    calls = [('predict_occupation_us', lambda: halotab.predict(occupation)),
+             ('predict_vjp_us', lambda: halotab.predict_vjp(occupation, g_xi, g_ngal)),
+             ('chi2_grad_occupation_us',
+              lambda: halotab.chi2_grad_occupation(occupation, data, precision)),
+             ('predict_batch_grad_us', lambda: halotab.predict_batch_grad(theta)),
+             # the forward figure again: the two bracket the drift of the run
+             ('predict_occupation_again_us', lambda: halotab.predict(occupation))]
+    result = {'table': name, 'n_bins': occupation.shape[1], 'n_r': n_r, 'n_draws': n_draws}
+    for key, call in calls:
+        result[key] = time_calls(call, seconds) * 1e6
+    forward_us = 0.5 * (result['predict_occupation_us'] + result['predict_occupation_again_us'])
+    result['vjp_over_forward'] = result['predict_vjp_us'] / forward_us
+    result['chi2_grad_over_forward'] = result['chi2_grad_occupation_us'] / forward_us
+    result['vjp_over_batch_grad'] = result['predict_vjp_us'] / result['predict_batch_grad_us']
+    # the main kernel alone (the forward path: its contraction kernel), from the launches' own
+    # events
+    from tabcorr_amd import _lib
+    device = halotab.to_device()
+    for key, call in calls[:3]:
+        milliseconds, mean, count = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+        with device.lock:
+            _lib.check(device.lib.tc_table_timer_begin(device.handle, 1))
+        call()
+        with device.lock:
+            _lib.check(device.lib.tc_table_timer_end(device.handle, ctypes.byref(milliseconds)))
+            _lib.check(device.lib.tc_table_kernel_time(device.handle, ctypes.byref(count),
+                                                       ctypes.byref(mean)))
+        result[key.replace('_us', '_kernels_us')] = count.value * mean.value * 1e3
+    return result
+
+
+def write_vjp_notes(notes, results, n_draws):
+    notes.write('\n## tools/grad_bench.py, occupation VJP, %d draws per call, host arrays in '
+                'and out\n\n' % n_draws)
+    notes.write('| table | bins | predict(ndarray) us | predict_vjp us | chi2_grad_occupation us | '
+                'predict_batch_grad us | VJP / forward | chi2 gradient / forward | '
+                'main kernel alone: forward, VJP, chi2 gradient us |\n')
+    notes.write('|---|---|---|---|---|---|---|---|---|\n')
+    for r in results:
+        notes.write('| %s | %d | %.1f (%.1f after) | %.1f | %.1f | %.1f | %.2f | %.2f | '
+                    '%.1f, %.1f, %.1f |\n' % (
+                        r['table'], r['n_bins'], r['predict_occupation_us'],
+                        r['predict_occupation_again_us'], r['predict_vjp_us'],
+                        r['chi2_grad_occupation_us'], r['predict_batch_grad_us'],
+                        r['vjp_over_forward'], r['chi2_grad_over_forward'],
+                        r['predict_occupation_kernels_us'], r['predict_vjp_kernels_us'],
+                        r['chi2_grad_occupation_kernels_us']))
+
+
 def main():
     parser = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     parser.add_argument('--draws', type=int, default=10000)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--notes', default=None, help='append the figures to this file')
+    parser.add_argument('--only', choices=['vjp'], default=None, help='one leg alone')
     args = parser.parse_args()
+    vjp = [measure_occupation_vjp('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
+           measure_occupation_vjp("reference example table's shape", 30, 1, 19, args.draws,
+                                  args.seconds)]
+    if args.only == 'vjp':
+        print(json.dumps({'occupation_vjp_metric': 'us per call, host arrays in and out',
+                          'occupation_vjp': vjp}))
+        if args.notes:
+            with open(args.notes, 'a') as notes:
+                write_vjp_notes(notes, vjp, args.draws)
+        return
     results = [measure('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
                measure("reference example table's shape", 30, 1, 19, args.draws, args.seconds)]
     interpolators = [
@@ -149,7 +225,9 @@ def main():
                              args.draws, args.seconds)]
     print(json.dumps({'metric': 'us per call, device-resident, pipelined', 'results': results,
                       'interpolator_metric': 'us per call, host arrays in and out',
-                      'interpolators': interpolators}))
+                      'interpolators': interpolators,
+                      'occupation_vjp_metric': 'us per call, host arrays in and out',
+                      'occupation_vjp': vjp}))
     if args.notes:
         with open(args.notes, 'a') as notes:
             notes.write('\n## tools/grad_bench.py, %d draws per call\n\n' % args.draws)
@@ -174,6 +252,7 @@ def main():
                                 r['chi2_grad_us'], r['differences_us'],
                                 r['forward_calls_replaced'], r['chi2_grad_over_chi2'],
                                 r['differences_over_chi2_grad'], r['chi2_grad_lds_bytes']))
+            write_vjp_notes(notes, vjp, args.draws)
 
 
 if __name__ == '__main__':
