@@ -31,8 +31,7 @@ __device__ __forceinline__ void interp_weights(const GradInterpArgs& ia, int64_t
                                                double* weights) {
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
-  const int64_t n_draws = ia.table.n_draws;
-  const int64_t draw = draw0 + col < n_draws ? draw0 + col : n_draws - 1;
+  const int64_t draw = clamp_draw(draw0 + col, ia.table.n_draws);
   double* dweights = weights + (size_t)ia.n_dim * kGradMaxAxis * kGradDraws;
   for (int d = 0; d < ia.n_dim; ++d)
     spline_weights(ia.n_axis[d], ia.xp + ia.axis_offset[d], ia.a + ia.a_offset[d],

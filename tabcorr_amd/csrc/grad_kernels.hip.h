@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fastmath.h"
-#include "grad.h"
+#include "grad_device.hip.h"
 
 namespace tc {
 
@@ -115,8 +115,7 @@ __device__ __forceinline__ void bin_values(const GradArgs& a, const fm::Consts& 
 }
 
 __device__ __forceinline__ Draw load_draw(const GradArgs& a, const fm::Consts& k, int64_t draw) {
-  // (the lanes beyond the batch repeat its last draw and store nothing)
-  const double* theta = a.theta + (draw < a.n_draws ? draw : a.n_draws - 1) * kGradParams;
+  const double* theta = a.theta + clamp_draw(draw, a.n_draws) * kGradParams;
   Draw d;
   d.log_m_min = theta[0];
   d.inv_sigma = 1.0 / theta[1];
@@ -205,35 +204,13 @@ __device__ __forceinline__ void auto_products(const GradArgs& a, const double* w
   const int group = lane / kGradDraws, col = lane % kGradDraws;
   const int n_bins = a.n_bins, n_central = a.n_central;
   const int tiles = a.row_tiles, steps = a.k_steps;
-  typedef double f64x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int p = 0; p < 6; ++p) acc[p] = 0.0;
   for (int tile = 0; tile < tiles; ++tile) {
     const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
-    f64x4 u = {0.0, 0.0, 0.0, 0.0};
-    // four steps per round, the operands of the next round fetched ahead of this round's
-    // matrix instructions (a step beyond the last one repeats it and is not multiplied)
-    double a_now[4], a_next[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) a_now[s] = a_lane[(size_t)(s < steps ? s : steps - 1) * 64];
-    for (int step0 = 0; step0 < steps; step0 += 4) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int next = step0 + 4 + s;
-        a_next[s] = a_lane[(size_t)(next < steps ? next : steps - 1) * 64];
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int step = step0 + s;
-        if (step < steps) {
-          const int j = 4 * step + group;
-          const double b = w[auto_row(j, 0, n_bins, n_central, zero_row) * kGradDraws + col];
-          u = __builtin_amdgcn_mfma_f64_16x16x4f64(a_now[s], b, u, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) a_now[s] = a_next[s];
-    }
+    const f64x4 u = dense_tile_product(a_lane, steps, w, group, col, [=](int j) {
+      return auto_row(j, 0, n_bins, n_central, zero_row);
+    });
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       const int i = 16 * tile + group + 4 * v;
@@ -243,12 +220,8 @@ __device__ __forceinline__ void auto_products(const GradArgs& a, const double* w
         acc[p] = fma(w[auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col], uv, acc[p]);
     }
   }
-  // the four row groups of a draw: (0 + 1) + (2 + 3), in every lane
 #pragma unroll
-  for (int p = 0; p < 6; ++p) {
-    acc[p] += __shfl_xor(acc[p], 16);
-    acc[p] += __shfl_xor(acc[p], 32);
-  }
+  for (int p = 0; p < 6; ++p) acc[p] = sum_row_groups(acc[p]);
 }
 
 // Phase 3, mode auto: xi = q / ngal^2 and dxi_k = dq_k / ngal^2 - 2 xi dngal_k / ngal with dq_k =
@@ -275,17 +248,6 @@ __device__ __forceinline__ void cross_node_loops(const GradArgs& a, const fm::Co
 #pragma unroll
     for (int p = 0; p < 6; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
   }
-}
-
-// sum + T_r[slab] . (quantity p of the slab) for one draw, in bin order.
-__device__ __forceinline__ double cross_slab_product(const double* matrix, int n_r, int r,
-                                                     int slab0, int count, const double* w, int p,
-                                                     int col, double sum) {
-  const double* column = matrix + (size_t)slab0 * n_r + r;
-  const double* rows = w + (size_t)p * kGradCrossSlab * kGradDraws + col;
-  for (int li = 0; li < count; ++li)
-    sum = fma(column[(size_t)li * n_r], rows[li * kGradDraws], sum);
-  return sum;
 }
 
 }  // namespace grad

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -674,6 +675,16 @@ int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                     int n_gauss, unsigned flags, bool chi2);
 int build_grad_table(tc_table* t);
+// The lane a derivative call asks for: lane 0, pinned (the host-array entry points stage their
+// copies on it), or the next lane of the handle's rotation (the device-pointer entry points).
+enum class GradLane { kPinned, kNext };
+// The table-shape fields of the argument block: n_bins, n_central, n_gauss, n_r, modulate,
+// math_table, row_tiles and k_steps.
+void fill_grad_shape(const tc_table* t, int n_gauss, unsigned flags, tc::GradArgs* ga);
+// One launch of a derivative kernel for n_draws draws: the grid of kGradDraws draws per
+// workgroup, the table's timing events, `launch`, then what the handle reports of its last launch.
+int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
+                      const std::function<int(dim3, hipEvent_t, hipEvent_t)>& launch);
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
              const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream);
@@ -718,6 +729,15 @@ int next_kernel_events(tc_table* t, hipEvent_t* start, hipEvent_t* stop);
 // Largest number of draws one slab may hold (workspaces bounded; 32-bit scalar offsets of
 // the quadratic-form kernel: n_bins * ldb * 8 < 2^32).
 int64_t max_slab(const tc_table* t);
+// fn(begin, n) for the draws of a batch in slabs of at most `slab`, until one fails.
+template <typename Fn>
+int for_each_slab(int64_t n_draws, int64_t slab, Fn fn) {
+  for (int64_t begin = 0; begin < n_draws; begin += slab) {
+    const int status = fn(begin, std::min(slab, n_draws - begin));
+    if (status != TC_OK) return status;
+  }
+  return TC_OK;
+}
 bool single_draw_eligible(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags);
 constexpr int kSingleMaxBlocks = 64;
 constexpr int kSingleMaxWalkers = 64;

@@ -1108,10 +1108,10 @@ int build_grad_walk(tc_interp* it) {
 }
 
 // One launch per slab of draws on the call's lane.  xi / dxi NULL: chi2 / dchi2 from chi2_data.
-int interp_grad_device(tc_interp* it, const double* theta_device, const double* x_device,
-                       int64_t n_draws, int n_gauss, unsigned flags, double* ngal, double* xi,
-                       double* dngal, double* dxi, const double* chi2_data, double* chi2,
-                       double* dchi2) {
+int interp_grad_device(tc_interp* it, GradLane request, const double* theta_device,
+                       const double* x_device, int64_t n_draws, int n_gauss, unsigned flags,
+                       double* ngal, double* xi, double* dngal, double* dxi,
+                       const double* chi2_data, double* chi2, double* dchi2) {
   TC_HIP(hipSetDevice(it->device));
   tc_table* t0 = it->tables[0];
   int status = TC_OK;
@@ -1121,21 +1121,14 @@ int interp_grad_device(tc_interp* it, const double* theta_device, const double* 
   status = class_pointers(it, n_gauss, &pointers);
   if (status == TC_OK) status = build_grad_walk(it);
   if (status != TC_OK) return status;
-  it->cur = it->force_lane >= 0 ? it->force_lane
-            : t0->tuning.pipeline ? (int)(it->device_calls++ % it->n_lanes)
-                                  : 0;
+  it->cur = request == GradLane::kPinned || !t0->tuning.pipeline
+                ? 0
+                : (int)(it->device_calls++ % it->n_lanes);
   tc_interp::Lane& L = it->lanes[it->cur];
   const bool with_chi2 = xi == nullptr;
   const int n_r = t0->n_r, n_dim = it->n_dim, n_cols = tc::kGradParams + n_dim;
   tc::GradInterpArgs ga{};
-  ga.table.n_bins = t0->n_bins;
-  ga.table.n_central = t0->plan.n_central;
-  ga.table.n_gauss = n_gauss;
-  ga.table.n_r = n_r;
-  ga.table.modulate = (flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0 ? 1 : 0;
-  ga.table.math_table = (const double*)t0->d_math_table;
-  ga.table.row_tiles = tc::grad_row_tiles(t0->n_bins);
-  ga.table.k_steps = tc::grad_k_steps(t0->n_bins);
+  fill_grad_shape(t0, n_gauss, flags, &ga.table);
   ga.table.chi2_data = chi2_data;
   ga.n_dim = n_dim;
   ga.n_classes = (int)it->class_table.size();
@@ -1154,9 +1147,7 @@ int interp_grad_device(tc_interp* it, const double* theta_device, const double* 
   ga.class_weight = (const double* const*)pointers->weight;
   ga.class_n_h = (const double* const*)pointers->n_h;
   const int lds = (int)interp_grad_lds(it, with_chi2);
-  const int64_t slab = max_slab(t0);
-  for (int64_t begin = 0; begin < n_draws; begin += slab) {
-    const int64_t n = std::min(slab, n_draws - begin);
+  return for_each_slab(n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
     Range range("interpolator gradients (one launch)");
     ga.table.theta = theta_device + begin * tc::kGradParams;
     ga.x = x_device + begin * n_dim;
@@ -1167,18 +1158,11 @@ int interp_grad_device(tc_interp* it, const double* theta_device, const double* 
     ga.table.dxi = dxi ? dxi + begin * n_cols * n_r : nullptr;
     ga.table.chi2 = chi2 ? chi2 + begin : nullptr;
     ga.table.dchi2 = dchi2 ? dchi2 + begin * n_cols : nullptr;
-    const dim3 grid((unsigned)((n + tc::kGradDraws - 1) / tc::kGradDraws));
-    hipEvent_t k0 = nullptr, k1 = nullptr;       // timed through the first table's timer
-    status = next_kernel_events(t0, &k0, &k1);
-    if (status != TC_OK) return status;
-    status = launch_grad_interp_instance(t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
-    if (status != TC_OK) return status;
-    t0->last_workgroups = (int)grid.x;
-    t0->last_waves = tc::kGradWaves;
-    t0->last_splits = 0;
-    t0->last_lds = lds;
-  }
-  return TC_OK;
+    // (timed through the first table's timer)
+    return launch_grad_batch(t0, n, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+      return launch_grad_interp_instance(t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
+    });
+  });
 }
 
 // Host arrays: the draws go up and the four result arrays come down on lane 0; `value` / `dvalue`
@@ -1202,14 +1186,10 @@ int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_
   double* d_dngal = d_ngal + n;
   double* d_value = (double*)it->out_xi.ptr;
   double* d_dvalue = d_value + value_count;
-  it->force_lane = 0;
-  status = chi2 ? interp_grad_device(it, (const double*)it->theta.ptr, (const double*)it->x.ptr,
-                                     n_draws, n_gauss, flags, d_ngal, nullptr, d_dngal, nullptr,
-                                     chi2_data, d_value, d_dvalue)
-                : interp_grad_device(it, (const double*)it->theta.ptr, (const double*)it->x.ptr,
-                                     n_draws, n_gauss, flags, d_ngal, d_value, d_dngal, d_dvalue,
-                                     nullptr, nullptr, nullptr);
-  it->force_lane = -1;
+  status = interp_grad_device(it, GradLane::kPinned, (const double*)it->theta.ptr,
+                              (const double*)it->x.ptr, n_draws, n_gauss, flags, d_ngal,
+                              chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
+                              chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * n_cols * 8, hipMemcpyDeviceToHost, it->stream));
@@ -1232,8 +1212,9 @@ int tc_interp_predict_grad_zheng07_batch_device(tc_interp* it, const double* the
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(x_device && ngal_device && xi_device && dngal_device && dxi_device, "NULL pointer");
-  return interp_grad_device(it, theta_device, x_device, n_draws, n_gauss, flags, ngal_device,
-                            xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr);
+  return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
+                            flags, ngal_device, xi_device, dngal_device, dxi_device, nullptr,
+                            nullptr, nullptr);
 }
 
 int tc_interp_predict_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -1262,9 +1243,9 @@ int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* it, const double* theta_
   TC_HIP(hipSetDevice(it->device));
   status = upload_chi2_data(it, data, precision);
   if (status != TC_OK) return status;
-  return interp_grad_device(it, theta_device, x_device, n_draws, n_gauss, flags, ngal_device,
-                            nullptr, dngal_device, nullptr, (const double*)it->chi2_data.ptr,
-                            chi2_device, dchi2_device);
+  return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
+                            flags, ngal_device, nullptr, dngal_device, nullptr,
+                            (const double*)it->chi2_data.ptr, chi2_device, dchi2_device);
 }
 
 int tc_interp_chi2_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,

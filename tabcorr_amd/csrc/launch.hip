@@ -1104,6 +1104,32 @@ int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n
 
 // ---- gradients, one launch per batch (grad_kernels.hip.h) -------------------------------------
 
+// What neither derivative family serves: a workgroup beyond the LDS of a CU, a dense operand
+// beyond 2 GiB.  `what`: the leading words of the message.
+static int check_grad_fit(const tc_table* t, const char* what, size_t lds) {
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "%s: a table of %d bins and %d correlation function bins needs %zu bytes "
+                "of LDS per workgroup, beyond the %d there are",
+                what, t->n_bins, t->n_r, lds, kMaxLdsBytes);
+  if (t->mode == TC_MODE_AUTO &&
+      tc::grad_operand_doubles(t->n_bins, t->n_r) * sizeof(double) > ((size_t)1 << 31))
+    return fail(TC_ERR_UNSUPPORTED, "%s: the dense matrix of %d bins exceeds 2 GiB", what,
+                t->n_bins);
+  return TC_OK;
+}
+
+static size_t grad_lds(const tc_table* t, bool chi2) {
+  return t->mode == TC_MODE_AUTO
+             ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, chi2)
+             : tc::grad_cross_lds_bytes(t->n_r);
+}
+
+static size_t vjp_lds(const tc_table* t) {
+  return t->mode == TC_MODE_AUTO ? tc::vjp_auto_lds_bytes(t->n_bins, t->n_r)
+                                 : tc::vjp_cross_lds_bytes(t->n_r);
+}
+
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                     int n_gauss, unsigned flags, bool chi2) {
   TC_CHECK(t != nullptr, "table handle is NULL");
@@ -1123,19 +1149,7 @@ int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n
   TC_CHECK(n_gauss >= 1 && n_gauss <= 4096, "n_gauss_prim must be in [1, 4096]");
   TC_CHECK(n_theta == tc::kGradParams, "theta must have %d columns, got %d", tc::kGradParams,
            n_theta);
-  const size_t lds = t->mode == TC_MODE_AUTO
-                         ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, chi2)
-                         : tc::grad_cross_lds_bytes(t->n_r);
-  if (lds > (size_t)kMaxLdsBytes)
-    return fail(TC_ERR_UNSUPPORTED,
-                "gradients: a table of %d bins and %d correlation function bins needs %zu bytes "
-                "of LDS per workgroup, beyond the %d there are",
-                t->n_bins, t->n_r, lds, kMaxLdsBytes);
-  if (t->mode == TC_MODE_AUTO &&
-      tc::grad_operand_doubles(t->n_bins, t->n_r) * sizeof(double) > ((size_t)1 << 31))
-    return fail(TC_ERR_UNSUPPORTED, "gradients: the dense matrix of %d bins exceeds 2 GiB",
-                t->n_bins);
-  return TC_OK;
+  return check_grad_fit(t, "gradients", grad_lds(t, chi2));
 }
 
 int build_grad_table(tc_table* t) {
@@ -1180,6 +1194,32 @@ int build_grad_table(tc_table* t) {
   return TC_OK;
 }
 
+void fill_grad_shape(const tc_table* t, int n_gauss, unsigned flags, tc::GradArgs* ga) {
+  ga->n_bins = t->n_bins;
+  ga->n_central = t->plan.n_central;
+  ga->n_gauss = n_gauss;
+  ga->n_r = t->n_r;
+  ga->modulate = (flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0 ? 1 : 0;
+  ga->math_table = (const double*)t->d_math_table;
+  ga->row_tiles = tc::grad_row_tiles(t->n_bins);
+  ga->k_steps = tc::grad_k_steps(t->n_bins);
+}
+
+int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
+                      const std::function<int(dim3, hipEvent_t, hipEvent_t)>& launch) {
+  const dim3 grid((unsigned)((n_draws + tc::kGradDraws - 1) / tc::kGradDraws));
+  hipEvent_t k0 = nullptr, k1 = nullptr;
+  int status = next_kernel_events(t, &k0, &k1);
+  if (status != TC_OK) return status;
+  status = launch(grid, k0, k1);
+  if (status != TC_OK) return status;
+  t->last_workgroups = (int)grid.x;
+  t->last_waves = tc::kGradWaves;
+  t->last_splits = 0;
+  t->last_lds = lds;
+  return TC_OK;
+}
+
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
              const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream) {
@@ -1189,21 +1229,14 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
   if (status == TC_OK) status = build_grad_table(t);
   if (status != TC_OK) return status;
   tc::GradArgs ga{};
+  fill_grad_shape(t, n_gauss, flags, &ga);
   ga.theta = theta_device;
   ga.n_draws = n_draws;
-  ga.n_bins = t->n_bins;
-  ga.n_central = t->plan.n_central;
-  ga.n_gauss = n_gauss;
-  ga.n_r = t->n_r;
-  ga.modulate = (flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0 ? 1 : 0;
   ga.log_m = (const double*)q->log_m;
   ga.m = (const double*)q->m;
   ga.weight = (const double*)q->weight;
   ga.n_h = (const double*)t->d_n_h;
-  ga.math_table = (const double*)t->d_math_table;
   ga.matrix = (const double*)t->grad.d_matrix;
-  ga.row_tiles = tc::grad_row_tiles(t->n_bins);
-  ga.k_steps = tc::grad_k_steps(t->n_bins);
   ga.ngal = ngal;
   ga.dngal = dngal;
   ga.xi = xi;
@@ -1211,21 +1244,10 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
   ga.chi2_data = chi2_data;
   ga.chi2 = chi2;
   ga.dchi2 = dchi2;
-  const bool with_chi2 = xi == nullptr;
-  const int lds = (int)(t->mode == TC_MODE_AUTO
-                            ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, with_chi2)
-                            : tc::grad_cross_lds_bytes(t->n_r));
-  const dim3 grid((unsigned)((n_draws + tc::kGradDraws - 1) / tc::kGradDraws));
-  hipEvent_t k0 = nullptr, k1 = nullptr;
-  status = next_kernel_events(t, &k0, &k1);
-  if (status != TC_OK) return status;
-  status = launch_grad_instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
-  if (status != TC_OK) return status;
-  t->last_workgroups = (int)grid.x;
-  t->last_waves = tc::kGradWaves;
-  t->last_splits = 0;
-  t->last_lds = lds;
-  return TC_OK;
+  const int lds = (int)grad_lds(t, xi == nullptr);
+  return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+    return launch_grad_instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
+  });
 }
 
 // ---- occupation VJP, one launch per batch (vjp_kernels.hip.h) ---------------------------------
@@ -1239,18 +1261,7 @@ int check_vjp_args(const tc_table* t, int64_t n_draws, unsigned flags) {
   if (t->compute_dtype != TC_DTYPE_F64)
     return fail(TC_ERR_UNSUPPORTED, "the occupation VJP needs a float64 compute dtype");
   TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
-  const size_t lds = t->mode == TC_MODE_AUTO ? tc::vjp_auto_lds_bytes(t->n_bins, t->n_r)
-                                             : tc::vjp_cross_lds_bytes(t->n_r);
-  if (lds > (size_t)kMaxLdsBytes)
-    return fail(TC_ERR_UNSUPPORTED,
-                "occupation VJP: a table of %d bins and %d correlation function bins needs %zu "
-                "bytes of LDS per workgroup, beyond the %d there are",
-                t->n_bins, t->n_r, lds, kMaxLdsBytes);
-  if (t->mode == TC_MODE_AUTO &&
-      tc::grad_operand_doubles(t->n_bins, t->n_r) * sizeof(double) > ((size_t)1 << 31))
-    return fail(TC_ERR_UNSUPPORTED, "occupation VJP: the dense matrix of %d bins exceeds 2 GiB",
-                t->n_bins);
-  return TC_OK;
+  return check_grad_fit(t, "occupation VJP", vjp_lds(t));
 }
 
 int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const double* g_ngal,
@@ -1276,19 +1287,10 @@ int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const
   va.xi = xi;
   va.chi2 = chi2;
   va.g_occupation = g_occupation;
-  const int lds = (int)(t->mode == TC_MODE_AUTO ? tc::vjp_auto_lds_bytes(t->n_bins, t->n_r)
-                                                : tc::vjp_cross_lds_bytes(t->n_r));
-  const dim3 grid((unsigned)((n_draws + tc::kGradDraws - 1) / tc::kGradDraws));
-  hipEvent_t k0 = nullptr, k1 = nullptr;
-  status = next_kernel_events(t, &k0, &k1);
-  if (status != TC_OK) return status;
-  status = launch_vjp_instance(t->mode, t->device, grid, lds, stream, k0, k1, va);
-  if (status != TC_OK) return status;
-  t->last_workgroups = (int)grid.x;
-  t->last_waves = tc::kGradWaves;
-  t->last_splits = 0;
-  t->last_lds = lds;
-  return TC_OK;
+  const int lds = (int)vjp_lds(t);
+  return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+    return launch_vjp_instance(t->mode, t->device, grid, lds, stream, k0, k1, va);
+  });
 }
 
 // ---- mode cross, one launch per batch -----------------------------------------------------

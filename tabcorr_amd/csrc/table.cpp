@@ -1018,35 +1018,35 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
 
 namespace {
 
-// The lane a device-pointer gradient call runs on (as tc_predict_zheng07_batch_device).
-int grad_lane(tc_table* t) {
-  if (t->force_lane >= 0)
-    t->cur = t->force_lane;
-  else
-    t->cur = t->tuning.pipeline ? (int)(t->device_calls++ % t->n_lanes) : 0;
-  return t->cur;
-}
-
-int grad_device(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
-                unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-                const double* chi2_data, double* chi2, double* dchi2) {
+// A derivative call on device pointers: run(begin, n, stream) for every slab of the batch, one
+// launch each, on lane 0 (pinned) or on the next lane of the rotation (as
+// tc_predict_zheng07_batch_device).
+extern "C++" template <typename Run>
+int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
   TC_HIP(hipSetDevice(t->device));
   int status = TC_OK;
   if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  tc_table::Lane& lane = t->lanes[grad_lane(t)];
-  const int64_t slab = max_slab(t);
-  const int64_t n_r = t->n_r;
-  for (int64_t begin = 0; begin < n_draws; begin += slab) {
-    const int64_t n = std::min(slab, n_draws - begin);
-    status = run_grad(t, theta_device + begin * tc::kGradParams, n, n_gauss, flags, ngal + begin,
-                      xi ? xi + begin * n_r : nullptr, dngal + begin * tc::kGradParams,
-                      dxi ? dxi + begin * tc::kGradParams * n_r : nullptr, chi2_data,
-                      chi2 ? chi2 + begin : nullptr,
-                      dchi2 ? dchi2 + begin * tc::kGradParams : nullptr, lane.stream);
-    if (status != TC_OK) return status;
-  }
-  t->prev = t->force_lane >= 0 ? -1 : t->cur;
+  const bool pinned = request == GradLane::kPinned;
+  t->cur = pinned || !t->tuning.pipeline ? 0 : (int)(t->device_calls++ % t->n_lanes);
+  hipStream_t stream = t->lanes[t->cur].stream;
+  status = for_each_slab(n_draws, max_slab(t),
+                         [&](int64_t begin, int64_t n) { return run(begin, n, stream); });
+  if (status != TC_OK) return status;
+  t->prev = pinned ? -1 : t->cur;
   return TC_OK;
+}
+
+int grad_device(tc_table* t, GradLane request, const double* theta_device, int64_t n_draws,
+                int n_gauss, unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
+                const double* chi2_data, double* chi2, double* dchi2) {
+  const int64_t n_r = t->n_r;
+  return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
+    return run_grad(t, theta_device + begin * tc::kGradParams, n, n_gauss, flags, ngal + begin,
+                    xi ? xi + begin * n_r : nullptr, dngal + begin * tc::kGradParams,
+                    dxi ? dxi + begin * tc::kGradParams * n_r : nullptr, chi2_data,
+                    chi2 ? chi2 + begin : nullptr,
+                    dchi2 ? dchi2 + begin * tc::kGradParams : nullptr, stream);
+  });
 }
 
 // Host arrays: the draws go up and the four result arrays come down on lane 0; `wide` = doubles
@@ -1067,12 +1067,9 @@ int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, un
   double* d_dngal = d_ngal + n;
   double* d_value = (double*)t->out_xi.ptr;
   double* d_dvalue = d_value + value_count;
-  t->force_lane = 0;
-  status = chi2 ? grad_device(t, (const double*)t->theta.ptr, n_draws, n_gauss, flags, d_ngal,
-                              nullptr, d_dngal, nullptr, chi2_data, d_value, d_dvalue)
-                : grad_device(t, (const double*)t->theta.ptr, n_draws, n_gauss, flags, d_ngal,
-                              d_value, d_dngal, d_dvalue, nullptr, nullptr, nullptr);
-  t->force_lane = -1;
+  status = grad_device(t, GradLane::kPinned, (const double*)t->theta.ptr, n_draws, n_gauss, flags,
+                       d_ngal, chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
+                       chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
   TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * np * 8, hipMemcpyDeviceToHost, t->stream));
@@ -1093,8 +1090,8 @@ int tc_predict_grad_zheng07_batch_device(tc_table* t, const double* theta_device
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
-  return grad_device(t, theta_device, n_draws, n_gauss, flags, ngal_device, xi_device,
-                     dngal_device, dxi_device, nullptr, nullptr, nullptr);
+  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
+                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr);
 }
 
 int tc_predict_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta,
@@ -1120,8 +1117,8 @@ int tc_chi2_grad_zheng07_batch_device(tc_table* t, const double* theta_device, i
   TC_HIP(hipSetDevice(t->device));
   status = upload_chi2_data(t, data, precision);
   if (status != TC_OK) return status;
-  return grad_device(t, theta_device, n_draws, n_gauss, flags, ngal_device, nullptr,
-                     dngal_device, nullptr, (const double*)t->chi2_data.ptr, chi2_device,
+  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
+                     nullptr, dngal_device, nullptr, (const double*)t->chi2_data.ptr, chi2_device,
                      dchi2_device);
 }
 
@@ -1144,26 +1141,16 @@ int tc_chi2_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta, in
 
 namespace {
 
-// Device pointers, the slabs of a batch one launch each on the next lane (as grad_device).
-int vjp_device(tc_table* t, const double* occupation, int64_t n_draws, const double* g_ngal,
-               const double* g_xi, const double* chi2_data, double* ngal, double* xi,
-               double* chi2, double* g_occupation) {
-  TC_HIP(hipSetDevice(t->device));
-  int status = TC_OK;
-  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  tc_table::Lane& lane = t->lanes[grad_lane(t)];
-  const int64_t slab = max_slab(t);
+int vjp_device(tc_table* t, GradLane request, const double* occupation, int64_t n_draws,
+               const double* g_ngal, const double* g_xi, const double* chi2_data, double* ngal,
+               double* xi, double* chi2, double* g_occupation) {
   const int64_t n_r = t->n_r, n_bins = t->n_bins;
-  for (int64_t begin = 0; begin < n_draws; begin += slab) {
-    const int64_t n = std::min(slab, n_draws - begin);
-    status = run_vjp(t, occupation + begin * n_bins, n, g_ngal ? g_ngal + begin : nullptr,
-                     g_xi ? g_xi + begin * n_r : nullptr, chi2_data, ngal + begin,
-                     xi ? xi + begin * n_r : nullptr, chi2 ? chi2 + begin : nullptr,
-                     g_occupation + begin * n_bins, lane.stream);
-    if (status != TC_OK) return status;
-  }
-  t->prev = t->force_lane >= 0 ? -1 : t->cur;
-  return TC_OK;
+  return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
+    return run_vjp(t, occupation + begin * n_bins, n, g_ngal ? g_ngal + begin : nullptr,
+                   g_xi ? g_xi + begin * n_r : nullptr, chi2_data, ngal + begin,
+                   xi ? xi + begin * n_r : nullptr, chi2 ? chi2 + begin : nullptr,
+                   g_occupation + begin * n_bins, stream);
+  });
 }
 
 // Host arrays, slab by slab on lane 0: the occupations and the cotangents go up in one workspace,
@@ -1177,11 +1164,10 @@ int vjp_host(tc_table* t, const double* occupation, int64_t n_draws, const doubl
   if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
   const bool chi2 = chi2_data != nullptr;
   const size_t n_r = (size_t)t->n_r, n_bins = (size_t)t->n_bins;
-  const int64_t slab = max_slab(t);
-  for (int64_t begin = 0; begin < n_draws; begin += slab) {
-    const size_t n = (size_t)std::min(slab, n_draws - begin);
+  return for_each_slab(n_draws, max_slab(t), [&](int64_t begin, int64_t n_slab) {
+    const size_t n = (size_t)n_slab;
     const size_t value_count = chi2 ? n : n * n_r;
-    status = t->occupation.reserve(n * (n_bins + n_r + 1) * 8, t->stream);
+    int status = t->occupation.reserve(n * (n_bins + n_r + 1) * 8, t->stream);
     if (status == TC_OK) status = t->out_ngal.reserve(n * 8, t->stream);
     if (status == TC_OK) status = t->out_xi.reserve((n * n_bins + value_count) * 8, t->stream);
     if (status != TC_OK) return status;
@@ -1198,11 +1184,10 @@ int vjp_host(tc_table* t, const double* occupation, int64_t n_draws, const doubl
                             hipMemcpyHostToDevice, t->stream));
     if (!chi2 && g_ngal != nullptr)
       TC_HIP(hipMemcpyAsync(d_g_ngal, g_ngal + begin, n * 8, hipMemcpyHostToDevice, t->stream));
-    t->force_lane = 0;
-    status = vjp_device(t, d_occupation, (int64_t)n, !chi2 && g_ngal != nullptr ? d_g_ngal : nullptr,
-                        chi2 ? nullptr : d_g_xi, chi2_data, d_ngal, chi2 ? nullptr : d_value,
-                        chi2 ? d_value : nullptr, d_g_occupation);
-    t->force_lane = -1;
+    status = vjp_device(t, GradLane::kPinned, d_occupation, n_slab,
+                        !chi2 && g_ngal != nullptr ? d_g_ngal : nullptr, chi2 ? nullptr : d_g_xi,
+                        chi2_data, d_ngal, chi2 ? nullptr : d_value, chi2 ? d_value : nullptr,
+                        d_g_occupation);
     if (status != TC_OK) return status;
     TC_HIP(hipMemcpyAsync(ngal + begin, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
     TC_HIP(hipMemcpyAsync(value + (size_t)begin * (chi2 ? 1 : n_r), d_value, value_count * 8,
@@ -1210,8 +1195,8 @@ int vjp_host(tc_table* t, const double* occupation, int64_t n_draws, const doubl
     TC_HIP(hipMemcpyAsync(g_occupation + (size_t)begin * n_bins, d_g_occupation, n * n_bins * 8,
                           hipMemcpyDeviceToHost, t->stream));
     TC_HIP(hipStreamSynchronize(t->stream));
-  }
-  return TC_OK;
+    return (int)TC_OK;
+  });
 }
 
 }  // namespace
@@ -1226,8 +1211,8 @@ int tc_predict_occupation_vjp_batch_device(tc_table* t, const double* occupation
   if (n_draws == 0) return TC_OK;
   TC_CHECK(occupation_device && g_xi_device && ngal_device && xi_device && g_occupation_device,
            "NULL pointer");
-  return vjp_device(t, occupation_device, n_draws, g_ngal_device, g_xi_device, nullptr,
-                    ngal_device, xi_device, nullptr, g_occupation_device);
+  return vjp_device(t, GradLane::kNext, occupation_device, n_draws, g_ngal_device, g_xi_device,
+                    nullptr, ngal_device, xi_device, nullptr, g_occupation_device);
 }
 
 int tc_predict_occupation_vjp_batch(tc_table* t, const double* occupation, int64_t n_draws,
@@ -1253,7 +1238,7 @@ int tc_chi2_occupation_grad_batch_device(tc_table* t, const double* occupation_d
   TC_HIP(hipSetDevice(t->device));
   status = upload_chi2_data(t, data, precision);
   if (status != TC_OK) return status;
-  return vjp_device(t, occupation_device, n_draws, nullptr, nullptr,
+  return vjp_device(t, GradLane::kNext, occupation_device, n_draws, nullptr, nullptr,
                     (const double*)t->chi2_data.ptr, ngal_device, nullptr, chi2_device,
                     dchi2_docc_device);
 }

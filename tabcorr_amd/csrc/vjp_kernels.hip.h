@@ -24,16 +24,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include "grad_device.hip.h"
 #include "vjp.h"
 
 namespace tc {
 
 namespace vjp {
-
-// The draw a column reads: the columns beyond the batch repeat its last draw and store nothing.
-__device__ __forceinline__ int64_t read_draw(const VjpArgs& a, int64_t draw) {
-  return draw < a.n_draws ? draw : a.n_draws - 1;
-}
 
 // One pass of mode auto over the row tiles of this wave.  with_q: qpart[(r 4 + wave), col] +=
 // the tiles' share of w . U_r (qpart starts at zero); with_g: gsum[i, col] = sum_r g_r U_ri for
@@ -46,7 +42,7 @@ __device__ __forceinline__ void auto_pass(const VjpArgs& a, const double* w, con
   const int group = lane / kGradDraws, col = lane % kGradDraws;
   const int n_bins = a.n_bins, n_r = a.n_r;
   const int tiles = a.row_tiles, steps = a.k_steps;
-  typedef double f64x4 __attribute__((ext_vector_type(4)));
+  using grad::f64x4;
   for (int tile = wave; tile < tiles; tile += kGradWaves) {
     double w_row[4];
 #pragma unroll
@@ -57,37 +53,14 @@ __device__ __forceinline__ void auto_pass(const VjpArgs& a, const double* w, con
     f64x4 g = {0.0, 0.0, 0.0, 0.0};
     for (int r = 0; r < n_r; ++r) {
       const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
-      f64x4 u = {0.0, 0.0, 0.0, 0.0};
-      // four steps per round, the operands of the next round fetched ahead of this round's
-      // matrix instructions (a step beyond the last one repeats it and is not multiplied)
-      double a_now[4], a_next[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) a_now[s] = a_lane[(size_t)(s < steps ? s : steps - 1) * 64];
-      for (int step0 = 0; step0 < steps; step0 += 4) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int next = step0 + 4 + s;
-          a_next[s] = a_lane[(size_t)(next < steps ? next : steps - 1) * 64];
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int step = step0 + s;
-          if (step < steps) {
-            const int j = 4 * step + group;
-            const double b = w[(j < n_bins ? j : zero_row) * kGradDraws + col];
-            u = __builtin_amdgcn_mfma_f64_16x16x4f64(a_now[s], b, u, 0, 0, 0);
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) a_now[s] = a_next[s];
-      }
+      const f64x4 u = grad::dense_tile_product(a_lane, steps, w, group, col, [=](int j) {
+        return j < n_bins ? j : zero_row;
+      });
       if (with_q) {
         double q = 0.0;
 #pragma unroll
         for (int v = 0; v < 4; ++v) q = fma(w_row[v], u[v], q);
-        // the four row groups of a draw: (0 + 1) + (2 + 3), in every lane
-        q += __shfl_xor(q, 16);
-        q += __shfl_xor(q, 32);
+        q = grad::sum_row_groups(q);
         if (group == 0) qpart[(r * kGradWaves + wave) * kGradDraws + col] += q;
       }
       if (with_g) {
@@ -152,7 +125,7 @@ __global__ __launch_bounds__(kGradThreads) void vjp_auto_kernel(const VjpArgs a)
   const int col = t % kGradDraws;
   const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
   const int64_t draw = draw0 + col;
-  const int64_t source = vjp::read_draw(a, draw);
+  const int64_t source = grad::clamp_draw(draw, a.n_draws);
   const int n_bins = a.n_bins, n_r = a.n_r;
   const bool likelihood = a.g_xi == nullptr;
   const int zero_row = n_bins;
@@ -228,7 +201,7 @@ __global__ __launch_bounds__(kGradThreads) void vjp_cross_kernel(const VjpArgs a
   const int col = t % kGradDraws;
   const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
   const int64_t draw = draw0 + col;
-  const int64_t source = vjp::read_draw(a, draw);
+  const int64_t source = grad::clamp_draw(draw, a.n_draws);
   const int n_bins = a.n_bins, n_r = a.n_r;
   const bool likelihood = a.g_xi == nullptr;
   double* w = vjp_lds;                                              // (slab, 16)
@@ -255,12 +228,8 @@ __global__ __launch_bounds__(kGradThreads) void vjp_cross_kernel(const VjpArgs a
     if (t < kGradDraws)
       for (int li = 0; li < count; ++li) my_total += w[li * kGradDraws + t];
     for (int item = t; item < n_items; item += kGradThreads) {
-      const int r = item / kGradDraws;
-      const double* column = a.matrix + (size_t)slab0 * n_r + r;
-      double sum = y[item];
-      for (int li = 0; li < count; ++li)
-        sum = fma(column[(size_t)li * n_r], w[li * kGradDraws + col], sum);
-      y[item] = sum;
+      y[item] = grad::cross_slab_product(a.matrix, n_r, item / kGradDraws, slab0, count, w, 0, col,
+                                         y[item]);
     }
   }
   if (t < kGradDraws) {

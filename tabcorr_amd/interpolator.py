@@ -24,8 +24,8 @@ from . import pinned
 from .galtable import GalTypeTable
 from .models import device_spec
 from .models import ZHENG07_KEYS
-from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _flags, _grad_theta,
-                      _unbatch)
+from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _chi2_operands, _flags,
+                      _grad_theta, _unbatch)
 
 OUT_OF_RANGE = ('The x-coordinates are outside of the interpolation ' +
                 'range and extrapolation is turned off.')
@@ -513,12 +513,8 @@ class Interpolator:
         dngal, dchi2 : ``(n_draws, 5 + D)``
         """
         theta, x = self._grad_inputs(theta, x, extrapolate)
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
-        n_r = len(self.tabcorr_list[0].tpcf_matrix)
-        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(n_r))
+        data, precision = _chi2_operands(
+            data, precision, len(self.tabcorr_list[0].tpcf_matrix))
         device = self.to_device()
         n_draws = len(theta)
         n_cols = len(ZHENG07_KEYS) + len(self.keys)

@@ -773,14 +773,10 @@ class TabCorr:
         dngal, dchi2 : ``(n_draws, 5)``
         """
         theta = _grad_theta(theta)
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
         # (the rows of the table's own matrix: a wrong argument is refused
         # before any device is touched, as a wrong theta is)
-        n_r = len(self.tpcf_matrix)
-        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(n_r))
+        data, precision = _chi2_operands(data, precision,
+                                         len(self.tpcf_matrix))
         device = self.to_device()
         n_draws = len(theta)
         ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
@@ -908,12 +904,8 @@ class TabCorr:
         dchi2_docc : ``(n_draws, n_bins)``, in the row order of ``gal_type``
         """
         occupation, batched = self._vjp_occupation(occupation)
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
-        n_r = len(self.tpcf_matrix)
-        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(n_r))
+        data, precision = _chi2_operands(data, precision,
+                                         len(self.tpcf_matrix))
         device = self.to_device()
         n_draws = len(occupation)
         ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
@@ -1008,6 +1000,17 @@ def _grad_theta(theta):
         raise ValueError('theta must have shape (n_draws, {}), got {}.'.format(
             len(ZHENG07_KEYS), theta.shape))
     return theta
+
+
+def _chi2_operands(data, precision, n_r):
+    """The data vector and the precision matrix of the likelihood gradient
+    calls, contiguous, or a ValueError where they do not fit ``n_r``."""
+    data = _lib.contiguous(np.ravel(data))
+    precision = _lib.contiguous(precision)
+    if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
+        raise ValueError('data must have {0} entries and precision shape '
+                         '({0}, {0}).'.format(n_r))
+    return data, precision
 
 
 def _unbatch(ngal, xi):

@@ -7,7 +7,6 @@ the size of the terms that cancel in it (grad_reference.jacobian: scale) -- the 
 to those terms.  Every case prints its largest error in units of that allowance.
 """
 
-import ctypes
 import os
 import sys
 
@@ -18,12 +17,13 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import grad_reference  # noqa: E402
 from oracle import tabcorr_oracle as oracle  # noqa: E402
 from tabcorr_amd import synthetic  # noqa: E402
+from derivative_kit import (  # noqa: E402
+    D, LDS_LIMIT, RTOL, check_refused, check_still_serves, chi2_data, device_call, largest,
+    same_bits)
 from util import assert_rel, load_golden, table_from_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-10
-D = 16                               # draws per workgroup of the gradient kernels (grad.h)
 DRAW_COUNTS = [1, D - 1, D, D + 1, 2 * D + 3]
 N_MAX = max(DRAW_COUNTS)
 
@@ -164,13 +164,7 @@ def test_gradient_at_the_edges_of_the_loops(case, n_draws, modulate):
 def chi2_inputs(shape, mode, modulate, symmetric, usable=False):
     """theta, the reference, a data vector near draw 3's xi and a precision matrix."""
     theta, reference, _ = get_reference(shape, mode, modulate, 10, usable=usable)
-    n_r = shape[2]
-    rng = np.random.default_rng(11)
-    a = rng.normal(size=(n_r, n_r))
-    precision = a @ a.T + n_r * np.eye(n_r)
-    if not symmetric:
-        precision = precision + rng.normal(size=(n_r, n_r))
-    data = reference[1][3] * (1.0 + 0.05 * rng.normal(size=n_r))
+    data, precision = chi2_data(reference[1][3], symmetric)
     return theta, reference, data, precision
 
 
@@ -242,67 +236,26 @@ def test_chi2_gradient_edges(shape, mode, n_draws, modulate):
     check_chi2_gradient(shape, mode, False, modulate, n_draws, usable=True)
 
 
-def device_call(halotab, theta, n_gauss=10, flags=0):
-    """tc_predict_grad_zheng07_batch_device on freshly allocated device arrays."""
-    from tabcorr_amd import _lib
+def device_grad(halotab, theta, n_gauss=10, flags=0):
+    """tc_predict_grad_zheng07_batch_device: ngal, xi, dngal, dxi."""
     device = halotab.to_device()
-    lib = device.lib
     n, n_r = len(theta), device.n_r
-    outputs = [np.empty(n), np.empty((n, n_r)), np.empty((n, 5)), np.empty((n, 5, n_r))]
-    theta = np.ascontiguousarray(theta)
-    pointers = []
-    for array in [theta] + outputs:
-        ptr = ctypes.c_void_p()
-        _lib.check(lib.tc_device_malloc(ctypes.byref(ptr), array.nbytes))
-        pointers.append(ptr)
-    try:
-        with device.lock:
-            _lib.check(lib.tc_memcpy_h2d(pointers[0], theta.ctypes.data_as(ctypes.c_void_p),
-                                         theta.nbytes))
-            _lib.check(lib.tc_predict_grad_zheng07_batch_device(
-                device.handle, pointers[0], 5, n, n_gauss, flags, *pointers[1:]))
-            _lib.check(lib.tc_table_synchronize(device.handle))
-            for array, ptr in zip(outputs, pointers[1:]):
-                _lib.check(lib.tc_memcpy_d2h(array.ctypes.data_as(ctypes.c_void_p), ptr,
-                                             array.nbytes))
-    finally:
-        for ptr in pointers:
-            lib.tc_device_free(ptr)
-    return outputs
+    return device_call(device, 'tc_predict_grad_zheng07_batch_device',
+                       [theta, 5, n, n_gauss, flags], [n, (n, n_r), (n, 5), (n, 5, n_r)])
 
 
-def device_chi2_call(halotab, theta, data, precision, n_gauss=10, flags=0):
-    """tc_chi2_grad_zheng07_batch_device on freshly allocated device arrays (the data vector and
-    the precision matrix are host arrays there too): ngal, chi2, dngal, dchi2."""
+def device_chi2_grad(halotab, theta, data, precision, n_gauss=10, flags=0):
+    """tc_chi2_grad_zheng07_batch_device (the data vector and the precision matrix are host
+    arrays there too): ngal, chi2, dngal, dchi2."""
     from tabcorr_amd import _lib
     device = halotab.to_device()
-    lib = device.lib
     n = len(theta)
-    outputs = [np.empty(n), np.empty(n), np.empty((n, 5)), np.empty((n, 5))]
-    theta = np.ascontiguousarray(theta)
     data = _lib.contiguous(np.ravel(data))
     precision = _lib.contiguous(precision)
     assert data.shape == (device.n_r, ) and precision.shape == (device.n_r, device.n_r)
-    pointers = []
-    try:
-        for array in [theta] + outputs:
-            ptr = ctypes.c_void_p()
-            _lib.check(lib.tc_device_malloc(ctypes.byref(ptr), array.nbytes))
-            pointers.append(ptr)
-        with device.lock:
-            _lib.check(lib.tc_memcpy_h2d(pointers[0], theta.ctypes.data_as(ctypes.c_void_p),
-                                         theta.nbytes))
-            _lib.check(lib.tc_chi2_grad_zheng07_batch_device(
-                device.handle, pointers[0], 5, n, n_gauss, flags, _lib.as_double_p(data),
-                _lib.as_double_p(precision), *pointers[1:]))
-            _lib.check(lib.tc_table_synchronize(device.handle))
-            for array, ptr in zip(outputs, pointers[1:]):
-                _lib.check(lib.tc_memcpy_d2h(array.ctypes.data_as(ctypes.c_void_p), ptr,
-                                             array.nbytes))
-    finally:
-        for ptr in pointers:
-            lib.tc_device_free(ptr)
-    return outputs
+    return device_call(device, 'tc_chi2_grad_zheng07_batch_device',
+                       [theta, 5, n, n_gauss, flags, _lib.as_double_p(data),
+                        _lib.as_double_p(precision)], [n, n, (n, 5), (n, 5)])
 
 
 @pytest.mark.parametrize('shape,mode', [((50, 1, 19), 'auto'), ((7, 1, 5), 'auto'),
@@ -314,16 +267,11 @@ def test_batch_invariance(shape, mode):
     theta, _, _ = get_reference(shape, mode, False, 10)
     full = halotab.predict_batch_grad(theta)
     for n in (1, D + 1):
-        part = halotab.predict_batch_grad(theta[:n])
-        for a, b in zip(part, full):
-            assert np.array_equal(a, b[:n], equal_nan=True)
+        assert same_bits(halotab.predict_batch_grad(theta[:n]), [b[:n] for b in full])
     # the last draw alone, and in the middle of another batch
-    alone = halotab.predict_batch_grad(theta[-1:])
-    for a, b in zip(alone, full):
-        assert np.array_equal(a[0], b[-1], equal_nan=True)
+    assert same_bits(halotab.predict_batch_grad(theta[-1:]), [b[-1:] for b in full])
     for n in (1, D + 1, N_MAX):
-        for a, b in zip(device_call(halotab, theta[:n]), full):
-            assert np.array_equal(a.reshape(b[:n].shape), b[:n], equal_nan=True)
+        assert same_bits(device_grad(halotab, theta[:n]), [b[:n] for b in full], reshape=True)
 
 
 @pytest.mark.parametrize('shape,mode', [((16, 1, 17), 'auto'), ((50, 1, 19), 'auto'),
@@ -339,22 +287,17 @@ def test_chi2_batch_invariance_and_device_entry(shape, mode):
     assert all(np.all(np.isfinite(a)) for a in full)
     for n in (1, D + 1, N_MAX):
         host = halotab.chi2_grad_batch(theta[:n], data, precision)
-        device = device_chi2_call(halotab, theta[:n], data, precision)
-        for a, b, c in zip(host, device, full):
-            assert a.shape == b.shape == c[:n].shape
-            assert np.array_equal(a, c[:n])
-            assert np.array_equal(b, a)
+        device = device_chi2_grad(halotab, theta[:n], data, precision)
+        assert same_bits(host, [c[:n] for c in full]) and same_bits(device, host)
     # the last draw alone (column 0 of its workgroup instead of column 2)
-    alone = halotab.chi2_grad_batch(theta[-1:], data, precision)
-    for a, c in zip(alone, full):
-        assert np.array_equal(a[0], c[-1])
+    assert same_bits(halotab.chi2_grad_batch(theta[-1:], data, precision),
+                     [c[-1:] for c in full])
     # modulate_with_cenocc through the flags of the device entry
     from tabcorr_amd import _lib
     host = halotab.chi2_grad_batch(theta[:D + 1], data, precision, modulate_with_cenocc=True)
-    device = device_chi2_call(halotab, theta[:D + 1], data, precision,
+    device = device_chi2_grad(halotab, theta[:D + 1], data, precision,
                               flags=_lib.FLAG_MODULATE_WITH_CENOCC)
-    for a, b in zip(host, device):
-        assert np.array_equal(a, b)
+    assert same_bits(device, host)
     assert not np.array_equal(host[1], full[1][:D + 1])
 
 
@@ -362,8 +305,7 @@ def test_chi2_batch_invariance_and_device_entry(shape, mode):
 # The documented budget of the two kernels (csrc/grad.h), in rows of D doubles.  Mode auto: three
 # rows per central bin, six per satellite bin, one row of zeros, six rows of totals and, for the
 # likelihood, six rows per r bin.  Mode cross: six slabs of 64 bins, six rows per r bin, six rows
-# of totals, the same for the likelihood.  A workgroup has 160 KiB.
-LDS_LIMIT = 160 * 1024
+# of totals, the same for the likelihood.
 CROSS_SLAB = 64
 
 
@@ -374,15 +316,6 @@ def auto_lds_bytes(n_bins, n_central, n_r, chi2):
 
 def cross_lds_bytes(n_r):
     return (6 * CROSS_SLAB + 6 * n_r + 6) * D * 8
-
-
-def largest(served):
-    """The largest size that `served` accepts (sizes are served up to a limit)."""
-    size = 1
-    while served(size + 1):
-        size += 1
-    assert served(size) and not served(size + 1)
-    return size
 
 
 def lds_limit_case(shape, mode, tpcf_shape=None):
@@ -402,17 +335,6 @@ def check_against_reference(halotab, theta, reference, what):
     assert_rel(ngal, reference[0], RTOL, what + ' ngal')
     assert_rel(xi, reference[1], RTOL, what + ' xi')
     check_derivatives(dngal, dxi, reference, what)
-
-
-def check_refused(halotab, table, call):
-    """`call` raises NotImplementedError and the handle goes on serving predict_batch."""
-    theta = synthetic.zheng07_draws(5, seed=2)
-    with pytest.raises(NotImplementedError, match='LDS'):
-        call(theta)
-    expect = oracle.predict_zheng07_batch(table, theta)
-    ngal, xi = halotab.predict_batch(theta)
-    assert_rel(ngal, expect[0], RTOL)
-    assert_rel(xi, expect[1], RTOL)
 
 
 def test_lds_limit_auto():
@@ -500,18 +422,10 @@ def test_unsupported_requests_leave_the_handle_usable():
     from tabcorr_amd import TabCorr, _lib
     table = synthetic.synthetic_table(9, 2, (5, ), 'auto', seed=3)
     theta = synthetic.zheng07_draws(5, seed=2)
-    expect = oracle.predict_zheng07_batch(table, theta)
-
-    def still_works(halotab, rtol):
-        ngal, xi = halotab.predict_batch(theta)
-        assert_rel(ngal, expect[0], rtol)
-        assert_rel(xi, expect[1], rtol)
-
     single = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'], table['tpcf_shape'],
                                  table['attrs'], compute_dtype='float32')
-    with pytest.raises(NotImplementedError, match='float64'):
-        single.predict_batch_grad(theta)
-    still_works(single, 1e-5)         # the float32 path's stated tolerance
+    # (1e-5: the float32 path's stated tolerance)
+    check_refused(single, table, single.predict_batch_grad, 'float64', 1e-5)
 
     halotab = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'], table['tpcf_shape'],
                                   table['attrs'])
@@ -527,7 +441,7 @@ def test_unsupported_requests_leave_the_handle_usable():
         assert status == _lib.TC_ERR_UNSUPPORTED
         with pytest.raises(NotImplementedError):
             _lib.check(status)
-        still_works(halotab, RTOL)
+        check_still_serves(halotab, table)
     # and the gradient call itself still serves the handle
     reference = grad_reference.jacobian_batch(
         table, grad_reference.centre_log_m0(theta.copy(), grad_reference.nodes_of(table)))

@@ -8,7 +8,6 @@ in units of that allowance.  Logical logM0 values sit at node midpoints over the
 tables (grad_reference.centre_log_m0).
 """
 
-import ctypes
 import os
 import sys
 
@@ -20,12 +19,12 @@ import grad_reference  # noqa: E402
 import interp_grad_reference as reference  # noqa: E402
 from oracle import tabcorr_oracle as oracle  # noqa: E402
 from tabcorr_amd import synthetic  # noqa: E402
+from derivative_kit import (  # noqa: E402
+    D, LDS_LIMIT, RTOL, chi2_data, device_call, largest, same_bits)
 from util import assert_rel  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-10
-D = 16                               # draws per workgroup of the gradient kernels (grad.h)
 DRAW_COUNTS = [1, D + 1, 2 * D + 3]
 N_MAX = max(DRAW_COUNTS)
 
@@ -236,15 +235,7 @@ def test_grid_of_identical_tables():
 
 def chi2_inputs(case, symmetric):
     """A data vector near draw 3's xi and a precision matrix."""
-    xi = case['reference']['xi']
-    n_r = int(np.prod(xi.shape[1:]))
-    rng = np.random.default_rng(11)
-    a = rng.normal(size=(n_r, n_r))
-    precision = a @ a.T + n_r * np.eye(n_r)
-    if not symmetric:
-        precision = precision + rng.normal(size=(n_r, n_r))
-    data = xi[3].ravel() * (1.0 + 0.05 * rng.normal(size=n_r))
-    return data, precision
+    return chi2_data(case['reference']['xi'][3].ravel(), symmetric)
 
 
 def check_chi2_values(got, expect, data, precision, what):
@@ -301,46 +292,20 @@ def test_chi2_gradient(entry, n_draws, symmetric):
                                          modulate_with_cenocc=modulate)[1], RTOL)
 
 
-def device_call(interp, theta, x, data=None, precision=None, n_gauss=10, flags=0):
-    """tc_interp_predict_grad_zheng07_batch_device (or, with data, the chi2 entry) on freshly
-    allocated device arrays."""
+def device_grad(interp, theta, x, data=None, precision=None, n_gauss=10, flags=0):
+    """tc_interp_predict_grad_zheng07_batch_device or, with data, the chi2 entry."""
     from tabcorr_amd import _lib
     device = interp.to_device()
-    lib = device.lib
     n, n_r, n_cols = len(theta), device.tables[0].n_r, 5 + x.shape[1]
+    arguments = [theta, 5, x, n, n_gauss, flags]
     if data is None:
-        outputs = [np.empty(n), np.empty((n, n_r)), np.empty((n, n_cols)),
-                   np.empty((n, n_cols, n_r))]
-    else:
-        outputs = [np.empty(n), np.empty(n), np.empty((n, n_cols)), np.empty((n, n_cols))]
-    inputs = [np.ascontiguousarray(theta), np.ascontiguousarray(x)]
-    pointers = []
-    try:
-        for array in inputs + outputs:
-            ptr = ctypes.c_void_p()
-            _lib.check(lib.tc_device_malloc(ctypes.byref(ptr), array.nbytes))
-            pointers.append(ptr)
-        with device.lock:
-            for array, ptr in zip(inputs, pointers):
-                _lib.check(lib.tc_memcpy_h2d(ptr, array.ctypes.data_as(ctypes.c_void_p),
-                                             array.nbytes))
-            if data is None:
-                _lib.check(lib.tc_interp_predict_grad_zheng07_batch_device(
-                    device.handle, pointers[0], 5, pointers[1], n, n_gauss, flags, *pointers[2:]))
-            else:
-                data = _lib.contiguous(np.ravel(data))
-                precision = _lib.contiguous(precision)
-                _lib.check(lib.tc_interp_chi2_grad_zheng07_batch_device(
-                    device.handle, pointers[0], 5, pointers[1], n, n_gauss, flags,
-                    _lib.as_double_p(data), _lib.as_double_p(precision), *pointers[2:]))
-            _lib.check(lib.tc_interp_synchronize(device.handle))
-            for array, ptr in zip(outputs, pointers[2:]):
-                _lib.check(lib.tc_memcpy_d2h(array.ctypes.data_as(ctypes.c_void_p), ptr,
-                                             array.nbytes))
-    finally:
-        for ptr in pointers:
-            lib.tc_device_free(ptr)
-    return outputs
+        return device_call(device, 'tc_interp_predict_grad_zheng07_batch_device', arguments,
+                           [n, (n, n_r), (n, n_cols), (n, n_cols, n_r)], 'tc_interp_synchronize')
+    data = _lib.contiguous(np.ravel(data))
+    precision = _lib.contiguous(precision)
+    return device_call(device, 'tc_interp_chi2_grad_zheng07_batch_device',
+                       arguments + [_lib.as_double_p(data), _lib.as_double_p(precision)],
+                       [n, n, (n, n_cols), (n, n_cols)], 'tc_interp_synchronize')
 
 
 @pytest.mark.parametrize('entry', [((4, 5), 7, 2, (5, ), 'auto'), ((4, 5), 33, 1, (3, 4), 'cross'),
@@ -361,21 +326,15 @@ def test_batch_invariance_and_device_entries(entry):
     assert all(np.all(np.isfinite(a)) for a in full + full_chi2)
     for n in DRAW_COUNTS:
         part = interp.predict_batch_grad(theta[:n], x[:n])
-        device = device_call(interp, theta[:n], x[:n])
-        for a, b, c in zip(part, device, full):
-            assert np.array_equal(a, c[:n])
-            assert np.array_equal(b.reshape(a.shape), a)
+        device = device_grad(interp, theta[:n], x[:n])
+        assert same_bits(part, [c[:n] for c in full]) and same_bits(device, part, reshape=True)
         part = interp.chi2_grad_batch(theta[:n], x[:n], data, precision)
-        device = device_call(interp, theta[:n], x[:n], data, precision)
-        for a, b, c in zip(part, device, full_chi2):
-            assert a.shape == b.shape == c[:n].shape
-            assert np.array_equal(a, c[:n])
-            assert np.array_equal(b, a)
+        device = device_grad(interp, theta[:n], x[:n], data, precision)
+        assert same_bits(part, [c[:n] for c in full_chi2]) and same_bits(device, part)
     # the last draw alone (column 0 of its workgroup instead of column 2)
     for alone, whole in ((interp.predict_batch_grad(theta[-1:], x[-1:]), full),
                          (interp.chi2_grad_batch(theta[-1:], x[-1:], data, precision), full_chi2)):
-        for a, c in zip(alone, whole):
-            assert np.array_equal(a[0], c[-1])
+        assert same_bits(alone, [c[-1:] for c in whole])
 
 
 def test_predict_grad_of_a_model():
@@ -402,8 +361,7 @@ def test_predict_grad_of_a_model():
 # The documented budget of grad_interp_auto_kernel (csrc/grad.h), in rows of D doubles: the rows
 # of a table (three per central bin, six per satellite bin, one of zeros), six rows of totals, the
 # weights and derivative weights of every axis (2 x 32 rows per dimension) and 6 + n_dim
-# accumulators per r bin; the likelihood is finished in the accumulators.  A workgroup has 160 KiB.
-LDS_LIMIT = 160 * 1024
+# accumulators per r bin; the likelihood is finished in the accumulators.
 
 
 # (a restatement of grad_interp_auto_lds_bytes, which is not exported: keep it in step with
@@ -418,9 +376,7 @@ def test_lds_limit_auto():
     bytes and are served, by both calls, and match the reference; one primary bin more (164 736
     bytes) is refused by both, and the interpolator goes on serving predict_batch."""
     n_r, n_dim = 4, 1
-    n_prim = 1
-    while auto_lds_bytes(2 * (n_prim + 1), n_prim + 1, n_r, n_dim, False) <= LDS_LIMIT:
-        n_prim += 1
+    n_prim = largest(lambda n: auto_lds_bytes(2 * n, n, n_r, n_dim, False) <= LDS_LIMIT)
     assert n_prim == 131 and auto_lds_bytes(2 * n_prim, n_prim, n_r, n_dim, False) == 163584
     assert auto_lds_bytes(2 * n_prim + 2, n_prim + 1, n_r, n_dim, True) == 164736
     case = get_case((4, ), n_prim, 1, (n_r, ), 'auto')

@@ -7,7 +7,6 @@ applied to the value and to the terms that cancel in it (vjp_reference: scale); 
 1e-10 relative.  Every case prints its largest error in units of that allowance.
 """
 
-import ctypes
 import os
 import sys
 
@@ -19,13 +18,14 @@ import grad_reference  # noqa: E402
 import vjp_reference  # noqa: E402
 from oracle import tabcorr_oracle as oracle  # noqa: E402
 from tabcorr_amd import synthetic  # noqa: E402
+from derivative_kit import (  # noqa: E402
+    D, LDS_LIMIT, RTOL, check_refused, check_still_serves, chi2_data, device_call, largest,
+    same_bits)
 from util import assert_rel, load_golden, table_from_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-10
 EPS = np.finfo(np.float64).eps
-D = 16                               # draws per workgroup of the VJP kernels (grad.h)
 DRAW_COUNTS = [1, D + 1, 2 * D + 3]
 N_MAX = max(DRAW_COUNTS)
 KINDS = ['zheng07', 'decorated', 'random']
@@ -194,14 +194,7 @@ def chi2_inputs(case, kind, symmetric):
     """Occupations, a data vector near draw 3's xi and a precision matrix."""
     table, _ = get_table(case)
     occupation = get_occupations(case, kind)
-    n_r = int(np.prod(case[2]))
-    rng = np.random.default_rng(11)
-    a = rng.normal(size=(n_r, n_r))
-    precision = a @ a.T + n_r * np.eye(n_r)
-    if not symmetric:
-        precision = precision + rng.normal(size=(n_r, n_r))
-    xi3 = oracle.predict(table, occupation[3])[1]
-    data = xi3 * (1.0 + 0.05 * rng.normal(size=xi3.shape))
+    data, precision = chi2_data(oracle.predict(table, occupation[3])[1], symmetric)
     return occupation, data, precision
 
 
@@ -248,58 +241,19 @@ def test_chi2_gradient_matches_reference(case, symmetric):
 
 # ---- batch invariance, host and device entry points -------------------------------------------
 
-def device_arrays(lib, arrays):
-    from tabcorr_amd import _lib
-    pointers = []
-    for array in arrays:
-        ptr = ctypes.c_void_p()
-        _lib.check(lib.tc_device_malloc(ctypes.byref(ptr), max(array.nbytes, 8)))
-        pointers.append(ptr)
-    return pointers
-
-
-def device_call(halotab, occupation, g_xi=None, g_ngal=None, data=None, precision=None, flags=0):
+def device_vjp(halotab, occupation, g_xi=None, g_ngal=None, data=None, precision=None, flags=0):
     """tc_predict_occupation_vjp_batch_device (with g_xi) or tc_chi2_occupation_grad_batch_device
-    (with data and precision) on freshly allocated device arrays."""
+    (with data and precision)."""
     from tabcorr_amd import _lib
     device = halotab.to_device()
-    lib = device.lib
     n, n_r = len(occupation), device.n_r
-    occupation = np.ascontiguousarray(occupation)
-    likelihood = g_xi is None
-    inputs = [occupation] if likelihood else [occupation, np.ascontiguousarray(g_xi)]
-    if g_ngal is not None:
-        inputs.append(np.ascontiguousarray(g_ngal))
-    outputs = [np.empty(n), np.empty(n) if likelihood else np.empty((n, n_r)),
-               np.empty_like(occupation)]
-    pointers = []
-    try:
-        pointers = device_arrays(lib, inputs + outputs)
-        ins, outs = pointers[:len(inputs)], pointers[len(inputs):]
-        with device.lock:
-            for array, ptr in zip(inputs, ins):
-                _lib.check(lib.tc_memcpy_h2d(ptr, array.ctypes.data_as(ctypes.c_void_p),
-                                             array.nbytes))
-            if likelihood:
-                _lib.check(lib.tc_chi2_occupation_grad_batch_device(
-                    device.handle, ins[0], n, flags, _lib.as_double_p(_lib.contiguous(np.ravel(data))),
-                    _lib.as_double_p(_lib.contiguous(precision)), *outs))
-            else:
-                _lib.check(lib.tc_predict_occupation_vjp_batch_device(
-                    device.handle, ins[0], n, flags, ins[2] if g_ngal is not None else None,
-                    ins[1], *outs))
-            _lib.check(lib.tc_table_synchronize(device.handle))
-            for array, ptr in zip(outputs, outs):
-                _lib.check(lib.tc_memcpy_d2h(array.ctypes.data_as(ctypes.c_void_p), ptr,
-                                             array.nbytes))
-    finally:
-        for ptr in pointers:
-            lib.tc_device_free(ptr)
-    return outputs
-
-
-def same_bits(a, b):
-    return all(np.array_equal(np.reshape(x, np.shape(y)), y, equal_nan=True) for x, y in zip(a, b))
+    if g_xi is None:
+        data, precision = _lib.contiguous(np.ravel(data)), _lib.contiguous(precision)
+        return device_call(device, 'tc_chi2_occupation_grad_batch_device',
+                           [occupation, n, flags, _lib.as_double_p(data),
+                            _lib.as_double_p(precision)], [n, n, occupation.shape])
+    return device_call(device, 'tc_predict_occupation_vjp_batch_device',
+                       [occupation, n, flags, g_ngal, g_xi], [n, (n, n_r), occupation.shape])
 
 
 @pytest.mark.parametrize('case', [(50, 1, (19, ), 'auto'), (9, 2, (5, ), 'auto'),
@@ -318,13 +272,13 @@ def test_batch_invariance(case):
 
     def predict(rows, device=False):
         if device:
-            return device_call(halotab, occupation[rows], g_xi.reshape(N_MAX, -1)[rows],
+            return device_vjp(halotab, occupation[rows], g_xi.reshape(N_MAX, -1)[rows],
                                g_ngal[rows])
         return halotab.predict_vjp(occupation[rows], g_xi[rows], g_ngal[rows])
 
     def likelihood(rows, device=False):
         if device:
-            return device_call(halotab, occupation[rows], data=data, precision=precision)
+            return device_vjp(halotab, occupation[rows], data=data, precision=precision)
         return halotab.chi2_grad_occupation(occupation[rows], data, precision)
 
     for call in (predict, likelihood):
@@ -335,10 +289,10 @@ def test_batch_invariance(case):
                      slice(N_MAX - 1, N_MAX), slice(4, 5), slice(5, 6), slice(6, 7)):
             assert same_bits(call(rows), [a[rows] for a in full]), (call.__name__, rows)
         for n in DRAW_COUNTS:
-            assert same_bits(call(slice(0, n), device=True), [a[:n] for a in full])
+            assert same_bits(call(slice(0, n), device=True), [a[:n] for a in full], reshape=True)
     # g_ngal = NULL through the device entry point
-    assert same_bits(device_call(halotab, occupation, g_xi.reshape(N_MAX, -1)),
-                     halotab.predict_vjp(occupation, g_xi))
+    assert same_bits(device_vjp(halotab, occupation, g_xi.reshape(N_MAX, -1)),
+                     halotab.predict_vjp(occupation, g_xi), reshape=True)
 
 
 # ---- the chain rule, end to end ---------------------------------------------------------------
@@ -401,28 +355,11 @@ def test_chain_rule_against_central_differences_of_the_oracle(mode):
 # ---- what is refused --------------------------------------------------------------------------
 # The documented budget of vjp_auto_kernel (csrc/vjp.h), in rows of D doubles: w of every bin and
 # one row of zeros, sum_r g_r U_ri of every bin, per r bin four partial q_r, the cotangent and xi,
-# and two rows for ngal and sum_r g_r xi_r.  A workgroup has 160 KiB.
-LDS_LIMIT = 160 * 1024
+# and two rows for ngal and sum_r g_r xi_r.
 
 
 def vjp_auto_lds_bytes(n_bins, n_r):
     return (2 * n_bins + 1 + 6 * n_r + 2) * D * 8
-
-
-def largest(served):
-    size = 1
-    while served(size + 1):
-        size += 1
-    assert served(size) and not served(size + 1)
-    return size
-
-
-def check_still_serves(halotab, table, rtol=RTOL):
-    theta = synthetic.zheng07_draws(5, seed=2)
-    expect = oracle.predict_zheng07_batch(table, theta)
-    ngal, xi = halotab.predict_batch(theta)
-    assert_rel(ngal, expect[0], rtol)
-    assert_rel(xi, expect[1], rtol)
 
 
 def check_served_case(case, what):
@@ -448,11 +385,9 @@ def test_lds_limit_auto(n_r):
                what + ' chi2')
     table, halotab = make_table(n_prim + 1, 1, (n_r, ), 'auto')
     occupation = np.ones((3, 2 * n_prim + 2))
-    with pytest.raises(NotImplementedError, match='LDS'):
-        halotab.predict_vjp(occupation, np.ones((3, n_r)))
-    with pytest.raises(NotImplementedError, match='LDS'):
-        halotab.chi2_grad_occupation(occupation, np.ones(n_r), np.eye(n_r))
-    check_still_serves(halotab, table)
+    check_refused(halotab, table, lambda _: halotab.predict_vjp(occupation, np.ones((3, n_r))))
+    check_refused(halotab, table,
+                  lambda _: halotab.chi2_grad_occupation(occupation, np.ones(n_r), np.eye(n_r)))
     check_served_case((9, 2, (5, ), 'auto'), 'after the LDS refusal')
 
 
@@ -462,11 +397,12 @@ def test_unsupported_requests_leave_the_handle_usable():
     table, halotab = get_table(case)
     _, single = make_table(*case, compute_dtype='float32')
     occupation = np.array(get_occupations(case, 'random')[:5])
-    with pytest.raises(NotImplementedError, match='float64'):
-        single.predict_vjp(occupation, np.ones((5, 5)))
-    with pytest.raises(NotImplementedError, match='float64'):
-        single.chi2_grad_occupation(occupation, np.ones(5), np.eye(5))
-    check_still_serves(single, table, 1e-5)      # the float32 path's stated tolerance
+    # (1e-5: the float32 path's stated tolerance)
+    check_refused(single, table, lambda _: single.predict_vjp(occupation, np.ones((5, 5))),
+                  'float64', 1e-5)
+    check_refused(single, table,
+                  lambda _: single.chi2_grad_occupation(occupation, np.ones(5), np.eye(5)),
+                  'float64', 1e-5)
     check_served_case(case, 'after the float32 refusal')
 
     device = halotab.to_device()
