@@ -229,6 +229,28 @@ int tc_chi2_grad_zheng07_batch_device(tc_table* table, const double* theta_devic
                                       const double* data, const double* precision,
                                       double* ngal_device, double* chi2_device,
                                       double* dngal_device, double* dchi2_device);
+/* The same with the Fisher matrix of the likelihood, from the derivatives the launch already
+ * holds: with dxi_k the Jacobian column of parameter k (k, l = 0 .. 4 in the order above),
+ *   fisher[k][l] = 1/2 sum_r dxi_k[r] (sum_s (precision[r][s] + precision[s][r]) dxi_l[s])
+ *                = dxi_k^T P_sym dxi_l,
+ * the Gauss-Newton normal matrix: 2 fisher is the Gauss-Newton Hessian of chi2.  A likelihood's
+ * ngal term stays the caller's: dngal is returned next to it, and an outer product completes the
+ * matrix.  fisher (n_draws, 5, 5): the full matrix, every pair k <= l computed once and stored to
+ * both positions (bit-symmetric); the sums run over s ascending inside r ascending, so a draw's
+ * matrix does not depend on its batch.  It does not depend on `data`.  Where the value's formula
+ * divides by zero the entries are what IEEE arithmetic gives.  The other outputs are those of
+ * tc_chi2_grad_zheng07_batch, bit for bit; arguments are checked and calls refused exactly as
+ * there. */
+int tc_chi2_fisher_zheng07_batch(tc_table* table, const double* theta, int n_theta,
+                                 int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                 const double* data, const double* precision, double* ngal,
+                                 double* chi2, double* dngal, double* dchi2, double* fisher);
+int tc_chi2_fisher_zheng07_batch_device(tc_table* table, const double* theta_device, int n_theta,
+                                        int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                        const double* data, const double* precision,
+                                        double* ngal_device, double* chi2_device,
+                                        double* dngal_device, double* dchi2_device,
+                                        double* fisher_device);
 
 /* A handful of independent draws in ONE launch (the proposals of an ensemble sampler's step,
  * or the reference's un-batched predict(), README.md:72-75, for n_walkers = 1): every
@@ -394,6 +416,23 @@ int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* interp, const double* th
                                              const double* precision, double* ngal_device,
                                              double* chi2_device, double* dngal_device,
                                              double* dchi2_device);
+/* ... with the Fisher matrix of the likelihood (tc_chi2_fisher_zheng07_batch: the same
+ * definition, fisher[k][l] = dxi_k^T P_sym dxi_l) over the 5 + D differentiated quantities, the
+ * five Zheng07 parameters first, then the extra parameters in axis order: fisher (n_draws, 5 + D,
+ * 5 + D).  The other outputs are those of tc_interp_chi2_grad_zheng07_batch, bit for bit;
+ * arguments are checked and calls refused exactly as there. */
+int tc_interp_chi2_fisher_zheng07_batch(tc_interp* interp, const double* theta, int n_theta,
+                                        const double* x, int64_t n_draws, int n_gauss_prim,
+                                        unsigned flags, const double* data,
+                                        const double* precision, double* ngal, double* chi2,
+                                        double* dngal, double* dchi2, double* fisher);
+int tc_interp_chi2_fisher_zheng07_batch_device(tc_interp* interp, const double* theta_device,
+                                               int n_theta, const double* x_device,
+                                               int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                               const double* data, const double* precision,
+                                               double* ngal_device, double* chi2_device,
+                                               double* dngal_device, double* dchi2_device,
+                                               double* fisher_device);
 
 /* Asynchronous host-to-host forms (page-locked theta, x, outputs; see
  * tc_predict_zheng07_batch_async): upload, kernels and download of a call on one of the

@@ -46,6 +46,10 @@ struct GradArgs {
   const double* chi2_data;   // data (n_r), then the precision matrix (n_r, n_r)
   double* chi2;              // (n_draws)
   double* dchi2;             // (n_draws, 5)
+  // Fisher matrix of the likelihood, fisher[k][l] = dxi_k^T P_sym dxi_l over the differentiated
+  // quantities (n_draws, 5, 5) -- (n_draws, 5 + n_dim, 5 + n_dim) for an interpolator; NULL: not
+  // asked for.  Only with the likelihood (xi NULL): grad_kernels.hip.h: finish_fisher
+  double* fisher;
 };
 
 // ---- LDS of grad_auto_kernel ------------------------------------------------------------------

@@ -14,7 +14,8 @@
 //      grad_kernels.hip.h once per CLASS, the matrix products once per TABLE, every table's
 //      results added with c_t (value, five theta derivatives) and dc_t/dx_d (n_dim more) into
 //      6 + n_dim accumulators per (r, draw) in LDS;
-//   3  the stores or, with a data vector, chi2 and its 5 + n_dim derivatives.
+//   3  the stores or, with a data vector, chi2, its 5 + n_dim derivatives and, where asked for,
+//      the Fisher matrix over the same 5 + n_dim quantities.
 // The order of every sum -- tables, rows, slabs -- is fixed by the interpolator: a draw's results
 // do not depend on the batch or on the draw's neighbours.
 #pragma once
@@ -66,7 +67,7 @@ __device__ __forceinline__ void set_class(GradArgs& a, const GradInterpArgs& ia,
 }
 
 // ngal and its 5 + n_dim derivatives (thread = (q, draw)), then xi and its derivatives from the
-// accumulators (n_q, n_r, 16) -- or chi2 and its derivatives.
+// accumulators (n_q, n_r, 16) -- or chi2, its derivatives and, where asked for, the Fisher matrix.
 __device__ __forceinline__ void interp_finish(const GradArgs& a, int n_q, double my_ngal,
                                               double* sums, int64_t draw0) {
   const int t = threadIdx.x;
@@ -95,6 +96,7 @@ __device__ __forceinline__ void interp_finish(const GradArgs& a, int n_q, double
     sums[item] -= a.chi2_data[item / kGradDraws];
   __syncthreads();
   finish_chi2(a, sums, draw0, n_q);
+  finish_fisher(a, sums, draw0, n_q);
 }
 
 }  // namespace grad

@@ -9,7 +9,8 @@
 //      of S_r x 4 columns x 16 draws per instruction, the A operand one coalesced load from the
 //      dense layout), then q_r = w . U_r and dq_r / dtheta_k = 2 dw_k . U_r; wave v takes the r
 //      bins v, v + 4, ...;  mode cross: six matrix-vector products per r bin, slab by slab;
-//   3  the chain rule (tabcorr.py:623-650) and, with a data vector, chi2 and its gradient.
+//   3  the chain rule (tabcorr.py:623-650) and, with a data vector, chi2, its gradient and, where
+//      asked for, the Fisher matrix dxi_k^T P_sym dxi_l of the draw.
 // There is ONE form: what a draw's results are made of -- the node sums in node order, the
 // matrix products in column order, the sums over rows in row order, the fixed tree over the four
 // row groups of a tile -- depends on the table alone, never on the batch or on the draw's
@@ -166,6 +167,46 @@ __device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* sta
     a.dchi2[draw * (n_quantities - 1) + (p - 1)] = sum;
 }
 
+// Fisher matrix of the likelihood, where a.fisher is given: fisher[k][l] = dxi_k^T P_sym dxi_l =
+// 1/2 sum_r dxi_k[r] (sum_s (P[r][s] + P[s][r]) dxi_l[s]) over the n = n_quantities - 1
+// differentiated quantities, from the rows p = 1 .. n of the stash that finish_chi2 reads (and
+// leaves as they are: no barrier between the two).  Items (pair k <= l, draw), n (n + 1) / 2 x 16
+// of them (240 for a table, up to 1456 for an interpolator of kGradMaxDim axes), walked by the
+// workgroup; s ascending inside r ascending, one fma chain each, as in finish_chi2: a draw's
+// matrix depends on the draw alone.  Every pair is computed once and stored to both positions of
+// the full (n, n) matrix, which is therefore bit-symmetric.
+__device__ __forceinline__ void finish_fisher(const GradArgs& a, const double* stash,
+                                              int64_t draw0, int n_quantities) {
+  if (a.fisher == nullptr) return;
+  const int n = n_quantities - 1;
+  const int n_r = a.n_r;
+  const double* precision = a.chi2_data + n_r;
+  const int n_items = n * (n + 1) / 2 * kGradDraws;
+  for (int item = threadIdx.x; item < n_items; item += kGradThreads) {
+    const int pair = item / kGradDraws, col = item % kGradDraws;
+    // pair = l (l + 1) / 2 + k with k <= l
+    int l = 0;
+    while ((l + 1) * (l + 2) / 2 <= pair) ++l;
+    const int k = pair - l * (l + 1) / 2;
+    const double* left = stash + (size_t)(k + 1) * n_r * kGradDraws + col;
+    const double* right = stash + (size_t)(l + 1) * n_r * kGradDraws + col;
+    double sum = 0.0;
+    for (int r = 0; r < n_r; ++r) {
+      double row = 0.0;
+      for (int s = 0; s < n_r; ++s)
+        row = fma(precision[(size_t)r * n_r + s] + precision[(size_t)s * n_r + r],
+                  right[s * kGradDraws], row);
+      sum = fma(left[r * kGradDraws], row, sum);
+    }
+    sum *= 0.5;
+    const int64_t draw = draw0 + col;
+    if (draw >= a.n_draws) continue;
+    double* out = a.fisher + draw * n * n;
+    out[k * n + l] = sum;
+    out[l * n + k] = sum;
+  }
+}
+
 // ---- the pieces of grad_auto_kernel (grad_interp_auto_kernel runs them per class and table) -----
 
 // Phase 1: thread = (bin i % 16, draw) writes w and dw of its bins, and the row of zeros.
@@ -319,6 +360,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   if (a.xi == nullptr) {
     __syncthreads();
     grad::finish_chi2(a, stash, draw0, 6);
+    grad::finish_fisher(a, stash, draw0, 6);
   }
 }
 
@@ -393,6 +435,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   if (a.xi == nullptr) {
     __syncthreads();
     grad::finish_chi2(a, y, draw0, 6);
+    grad::finish_fisher(a, y, draw0, 6);
   }
 }
 

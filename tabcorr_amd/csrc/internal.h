@@ -671,7 +671,8 @@ int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_
                        int n_gauss, unsigned flags);
 // Gradients (grad_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels do
 // not serve (TC_ERR_UNSUPPORTED with a message), the handle's copy of the matrix, the launch.
-// xi / dxi NULL: chi2 / dchi2 from chi2_data (data, then the precision matrix, on the device).
+// xi / dxi NULL: chi2 / dchi2 from chi2_data (data, then the precision matrix, on the device) and,
+// where `fisher` is given, the Fisher matrix (n_draws, 5, 5) of the likelihood.
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                     int n_gauss, unsigned flags, bool chi2);
 int build_grad_table(tc_table* t);
@@ -687,7 +688,8 @@ int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
                       const std::function<int(dim3, hipEvent_t, hipEvent_t)>& launch);
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-             const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream);
+             const double* chi2_data, double* chi2, double* dchi2, double* fisher,
+             hipStream_t stream);
 // Occupation VJP (vjp_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels
 // do not serve (TC_ERR_UNSUPPORTED with a message), then the launch against the gradient table.
 // g_xi NULL: the likelihood form -- chi2 and dchi2 / docc from chi2_data (on the device).

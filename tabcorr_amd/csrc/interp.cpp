@@ -1107,11 +1107,12 @@ int build_grad_walk(tc_interp* it) {
   return TC_OK;
 }
 
-// One launch per slab of draws on the call's lane.  xi / dxi NULL: chi2 / dchi2 from chi2_data.
+// One launch per slab of draws on the call's lane.  xi / dxi NULL: chi2 / dchi2 from chi2_data
+// and, where `fisher` is given, the Fisher matrix (n_draws, 5 + n_dim, 5 + n_dim).
 int interp_grad_device(tc_interp* it, GradLane request, const double* theta_device,
                        const double* x_device, int64_t n_draws, int n_gauss, unsigned flags,
                        double* ngal, double* xi, double* dngal, double* dxi,
-                       const double* chi2_data, double* chi2, double* dchi2) {
+                       const double* chi2_data, double* chi2, double* dchi2, double* fisher) {
   TC_HIP(hipSetDevice(it->device));
   tc_table* t0 = it->tables[0];
   int status = TC_OK;
@@ -1158,6 +1159,7 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
     ga.table.dxi = dxi ? dxi + begin * n_cols * n_r : nullptr;
     ga.table.chi2 = chi2 ? chi2 + begin : nullptr;
     ga.table.dchi2 = dchi2 ? dchi2 + begin * n_cols : nullptr;
+    ga.table.fisher = fisher ? fisher + begin * n_cols * n_cols : nullptr;
     // (timed through the first table's timer)
     return launch_grad_batch(t0, n, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
       return launch_grad_interp_instance(t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
@@ -1166,10 +1168,11 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
 }
 
 // Host arrays: the draws go up and the four result arrays come down on lane 0; `value` / `dvalue`
-// are xi and dxi, or (chi2_data given) chi2 and dchi2.
+// are xi and dxi, or (chi2_data given) chi2 and dchi2.  `fisher` (with chi2_data only, or NULL):
+// one array more comes down, from behind the other two.
 int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_t n_draws,
                      int n_gauss, unsigned flags, const double* chi2_data, double* ngal,
-                     double* value, double* dngal, double* dvalue) {
+                     double* value, double* dngal, double* dvalue, double* fisher = nullptr) {
   TC_HIP(hipSetDevice(it->device));
   const bool chi2 = chi2_data != nullptr;
   const size_t n = (size_t)n_draws, n_r = (size_t)it->tables[0]->n_r;
@@ -1178,7 +1181,9 @@ int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_
   int status = it->theta.reserve(n * np * 8, it->stream);
   if (status == TC_OK) status = it->x.reserve(n * it->n_dim * 8, it->stream);
   if (status == TC_OK) status = it->out_ngal.reserve(n * (1 + n_cols) * 8, it->stream);
-  if (status == TC_OK) status = it->out_xi.reserve(value_count * (1 + n_cols) * 8, it->stream);
+  const size_t fisher_count = fisher ? n * n_cols * n_cols : 0;
+  if (status == TC_OK)
+    status = it->out_xi.reserve((value_count * (1 + n_cols) + fisher_count) * 8, it->stream);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, n * np * 8, hipMemcpyHostToDevice, it->stream));
   TC_HIP(hipMemcpyAsync(it->x.ptr, x, n * it->n_dim * 8, hipMemcpyHostToDevice, it->stream));
@@ -1186,16 +1191,20 @@ int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_
   double* d_dngal = d_ngal + n;
   double* d_value = (double*)it->out_xi.ptr;
   double* d_dvalue = d_value + value_count;
+  double* d_fisher = fisher ? d_dvalue + value_count * n_cols : nullptr;
   status = interp_grad_device(it, GradLane::kPinned, (const double*)it->theta.ptr,
                               (const double*)it->x.ptr, n_draws, n_gauss, flags, d_ngal,
                               chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                              chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr);
+                              chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr,
+                              d_fisher);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * n_cols * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * n_cols * 8, hipMemcpyDeviceToHost,
                         it->stream));
+  if (fisher)
+    TC_HIP(hipMemcpyAsync(fisher, d_fisher, fisher_count * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipStreamSynchronize(it->stream));
   return TC_OK;
 }
@@ -1214,7 +1223,7 @@ int tc_interp_predict_grad_zheng07_batch_device(tc_interp* it, const double* the
   TC_CHECK(x_device && ngal_device && xi_device && dngal_device && dxi_device, "NULL pointer");
   return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
                             flags, ngal_device, xi_device, dngal_device, dxi_device, nullptr,
-                            nullptr, nullptr);
+                            nullptr, nullptr, nullptr);
 }
 
 int tc_interp_predict_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -1228,24 +1237,58 @@ int tc_interp_predict_grad_zheng07_batch(tc_interp* it, const double* theta, int
   return interp_grad_host(it, theta, x, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi);
 }
 
-int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* it, const double* theta_device,
-                                             int n_theta, const double* x_device,
-                                             int64_t n_draws, int n_gauss, unsigned flags,
-                                             const double* data, const double* precision,
-                                             double* ngal_device, double* chi2_device,
-                                             double* dngal_device, double* dchi2_device) {
+namespace {
+
+// The likelihood entries on device pointers and on host arrays; `want_fisher`: the entry has a
+// Fisher matrix among its outputs (the tc_interp_chi2_fisher_* entries), which then must not be
+// NULL.
+int interp_chi2_grad_device_entry(tc_interp* it, const double* theta_device, int n_theta,
+                                  const double* x_device, int64_t n_draws, int n_gauss,
+                                  unsigned flags, const double* data, const double* precision,
+                                  double* ngal_device, double* chi2_device, double* dngal_device,
+                                  double* dchi2_device, bool want_fisher, double* fisher_device) {
   int status = check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, true);
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(x_device && data && precision && ngal_device && chi2_device && dngal_device &&
-               dchi2_device,
+               dchi2_device && (!want_fisher || fisher_device),
            "NULL pointer");
   TC_HIP(hipSetDevice(it->device));
   status = upload_chi2_data(it, data, precision);
   if (status != TC_OK) return status;
   return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
                             flags, ngal_device, nullptr, dngal_device, nullptr,
-                            (const double*)it->chi2_data.ptr, chi2_device, dchi2_device);
+                            (const double*)it->chi2_data.ptr, chi2_device, dchi2_device,
+                            fisher_device);
+}
+
+int interp_chi2_grad_host_entry(tc_interp* it, const double* theta, int n_theta, const double* x,
+                                int64_t n_draws, int n_gauss, unsigned flags, const double* data,
+                                const double* precision, double* ngal, double* chi2,
+                                double* dngal, double* dchi2, bool want_fisher, double* fisher) {
+  int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, true);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x && data && precision && ngal && chi2 && dngal && dchi2 && (!want_fisher || fisher),
+           "NULL pointer");
+  TC_HIP(hipSetDevice(it->device));
+  status = upload_chi2_data(it, data, precision);
+  if (status != TC_OK) return status;
+  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags,
+                          (const double*)it->chi2_data.ptr, ngal, chi2, dngal, dchi2, fisher);
+}
+
+}  // namespace
+
+int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* it, const double* theta_device,
+                                             int n_theta, const double* x_device,
+                                             int64_t n_draws, int n_gauss, unsigned flags,
+                                             const double* data, const double* precision,
+                                             double* ngal_device, double* chi2_device,
+                                             double* dngal_device, double* dchi2_device) {
+  return interp_chi2_grad_device_entry(it, theta_device, n_theta, x_device, n_draws, n_gauss,
+                                       flags, data, precision, ngal_device, chi2_device,
+                                       dngal_device, dchi2_device, false, nullptr);
 }
 
 int tc_interp_chi2_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -1253,15 +1296,29 @@ int tc_interp_chi2_grad_zheng07_batch(tc_interp* it, const double* theta, int n_
                                       unsigned flags, const double* data,
                                       const double* precision, double* ngal, double* chi2,
                                       double* dngal, double* dchi2) {
-  int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, true);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x && data && precision && ngal && chi2 && dngal && dchi2, "NULL pointer");
-  TC_HIP(hipSetDevice(it->device));
-  status = upload_chi2_data(it, data, precision);
-  if (status != TC_OK) return status;
-  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags,
-                          (const double*)it->chi2_data.ptr, ngal, chi2, dngal, dchi2);
+  return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
+                                     precision, ngal, chi2, dngal, dchi2, false, nullptr);
+}
+
+int tc_interp_chi2_fisher_zheng07_batch_device(tc_interp* it, const double* theta_device,
+                                               int n_theta, const double* x_device,
+                                               int64_t n_draws, int n_gauss, unsigned flags,
+                                               const double* data, const double* precision,
+                                               double* ngal_device, double* chi2_device,
+                                               double* dngal_device, double* dchi2_device,
+                                               double* fisher_device) {
+  return interp_chi2_grad_device_entry(it, theta_device, n_theta, x_device, n_draws, n_gauss,
+                                       flags, data, precision, ngal_device, chi2_device,
+                                       dngal_device, dchi2_device, true, fisher_device);
+}
+
+int tc_interp_chi2_fisher_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
+                                        const double* x, int64_t n_draws, int n_gauss,
+                                        unsigned flags, const double* data,
+                                        const double* precision, double* ngal, double* chi2,
+                                        double* dngal, double* dchi2, double* fisher) {
+  return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
+                                     precision, ngal, chi2, dngal, dchi2, true, fisher);
 }
 
 int tc_interp_wait(tc_interp* it, int64_t ticket) {

@@ -1222,7 +1222,8 @@ int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
 
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-             const double* chi2_data, double* chi2, double* dchi2, hipStream_t stream) {
+             const double* chi2_data, double* chi2, double* dchi2, double* fisher,
+             hipStream_t stream) {
   Range range("gradients (one launch)");
   Quadrature* q = nullptr;
   int status = get_quadrature(t, n_gauss, &q);
@@ -1244,6 +1245,7 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
   ga.chi2_data = chi2_data;
   ga.chi2 = chi2;
   ga.dchi2 = dchi2;
+  ga.fisher = fisher;
   const int lds = (int)grad_lds(t, xi == nullptr);
   return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
     return launch_grad_instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);

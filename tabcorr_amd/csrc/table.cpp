@@ -1038,44 +1038,52 @@ int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
 
 int grad_device(tc_table* t, GradLane request, const double* theta_device, int64_t n_draws,
                 int n_gauss, unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-                const double* chi2_data, double* chi2, double* dchi2) {
+                const double* chi2_data, double* chi2, double* dchi2, double* fisher) {
   const int64_t n_r = t->n_r;
+  const int64_t np2 = tc::kGradParams * tc::kGradParams;
   return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
     return run_grad(t, theta_device + begin * tc::kGradParams, n, n_gauss, flags, ngal + begin,
                     xi ? xi + begin * n_r : nullptr, dngal + begin * tc::kGradParams,
                     dxi ? dxi + begin * tc::kGradParams * n_r : nullptr, chi2_data,
                     chi2 ? chi2 + begin : nullptr,
-                    dchi2 ? dchi2 + begin * tc::kGradParams : nullptr, stream);
+                    dchi2 ? dchi2 + begin * tc::kGradParams : nullptr,
+                    fisher ? fisher + begin * np2 : nullptr, stream);
   });
 }
 
 // Host arrays: the draws go up and the four result arrays come down on lane 0; `wide` = doubles
-// per draw of the two large results (xi and dxi, or chi2 and dchi2).
+// per draw of the two large results (xi and dxi, or chi2 and dchi2).  `fisher` (with chi2_data
+// only, or NULL): one array more comes down, from behind the other two.
 int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, unsigned flags,
               const double* chi2_data, double* ngal, double* value, double* dngal,
-              double* dvalue) {
+              double* dvalue, double* fisher = nullptr) {
   TC_HIP(hipSetDevice(t->device));
   const bool chi2 = chi2_data != nullptr;
   const size_t n = (size_t)n_draws, n_r = (size_t)t->n_r, np = tc::kGradParams;
   const size_t value_count = chi2 ? n : n * n_r;
   int status = t->theta.reserve(n * np * 8, t->stream);
   if (status == TC_OK) status = t->out_ngal.reserve(n * (1 + np) * 8, t->stream);
-  if (status == TC_OK) status = t->out_xi.reserve(value_count * (1 + np) * 8, t->stream);
+  const size_t fisher_count = fisher ? n * np * np : 0;
+  if (status == TC_OK)
+    status = t->out_xi.reserve((value_count * (1 + np) + fisher_count) * 8, t->stream);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(t->theta.ptr, theta, n * np * 8, hipMemcpyHostToDevice, t->stream));
   double* d_ngal = (double*)t->out_ngal.ptr;
   double* d_dngal = d_ngal + n;
   double* d_value = (double*)t->out_xi.ptr;
   double* d_dvalue = d_value + value_count;
+  double* d_fisher = fisher ? d_dvalue + value_count * np : nullptr;
   status = grad_device(t, GradLane::kPinned, (const double*)t->theta.ptr, n_draws, n_gauss, flags,
                        d_ngal, chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                       chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr);
+                       chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr, d_fisher);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
   TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * np * 8, hipMemcpyDeviceToHost, t->stream));
   TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, t->stream));
   TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * np * 8, hipMemcpyDeviceToHost,
                         t->stream));
+  if (fisher)
+    TC_HIP(hipMemcpyAsync(fisher, d_fisher, fisher_count * 8, hipMemcpyDeviceToHost, t->stream));
   TC_HIP(hipStreamSynchronize(t->stream));
   return TC_OK;
 }
@@ -1091,7 +1099,7 @@ int tc_predict_grad_zheng07_batch_device(tc_table* t, const double* theta_device
   if (n_draws == 0) return TC_OK;
   TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
   return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr);
+                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr);
 }
 
 int tc_predict_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta,
@@ -1104,37 +1112,82 @@ int tc_predict_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi);
 }
 
-int tc_chi2_grad_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
-                                      int64_t n_draws, int n_gauss, unsigned flags,
-                                      const double* data, const double* precision,
-                                      double* ngal_device, double* chi2_device,
-                                      double* dngal_device, double* dchi2_device) {
+namespace {
+
+// The likelihood entries on device pointers and on host arrays; `want_fisher`: the entry has a
+// Fisher matrix among its outputs (the tc_chi2_fisher_* entries), which then must not be NULL.
+int chi2_grad_device_entry(tc_table* t, const double* theta_device, int n_theta, int64_t n_draws,
+                           int n_gauss, unsigned flags, const double* data,
+                           const double* precision, double* ngal_device, double* chi2_device,
+                           double* dngal_device, double* dchi2_device, bool want_fisher,
+                           double* fisher_device) {
   int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, true);
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
-  TC_CHECK(data && precision && ngal_device && chi2_device && dngal_device && dchi2_device,
+  TC_CHECK(data && precision && ngal_device && chi2_device && dngal_device && dchi2_device &&
+               (!want_fisher || fisher_device),
            "NULL pointer");
   TC_HIP(hipSetDevice(t->device));
   status = upload_chi2_data(t, data, precision);
   if (status != TC_OK) return status;
   return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
                      nullptr, dngal_device, nullptr, (const double*)t->chi2_data.ptr, chi2_device,
-                     dchi2_device);
+                     dchi2_device, fisher_device);
+}
+
+int chi2_grad_host_entry(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                         int n_gauss, unsigned flags, const double* data, const double* precision,
+                         double* ngal, double* chi2, double* dngal, double* dchi2,
+                         bool want_fisher, double* fisher) {
+  int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, true);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(data && precision && ngal && chi2 && dngal && dchi2 && (!want_fisher || fisher),
+           "NULL pointer");
+  TC_HIP(hipSetDevice(t->device));
+  status = upload_chi2_data(t, data, precision);
+  if (status != TC_OK) return status;
+  return grad_host(t, theta, n_draws, n_gauss, flags, (const double*)t->chi2_data.ptr, ngal,
+                   chi2, dngal, dchi2, fisher);
+}
+
+}  // namespace
+
+int tc_chi2_grad_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                      int64_t n_draws, int n_gauss, unsigned flags,
+                                      const double* data, const double* precision,
+                                      double* ngal_device, double* chi2_device,
+                                      double* dngal_device, double* dchi2_device) {
+  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
+                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
+                                false, nullptr);
 }
 
 int tc_chi2_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
                                int n_gauss, unsigned flags, const double* data,
                                const double* precision, double* ngal, double* chi2,
                                double* dngal, double* dchi2) {
-  int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, true);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(data && precision && ngal && chi2 && dngal && dchi2, "NULL pointer");
-  TC_HIP(hipSetDevice(t->device));
-  status = upload_chi2_data(t, data, precision);
-  if (status != TC_OK) return status;
-  return grad_host(t, theta, n_draws, n_gauss, flags, (const double*)t->chi2_data.ptr, ngal,
-                   chi2, dngal, dchi2);
+  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
+                              chi2, dngal, dchi2, false, nullptr);
+}
+
+int tc_chi2_fisher_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                        int64_t n_draws, int n_gauss, unsigned flags,
+                                        const double* data, const double* precision,
+                                        double* ngal_device, double* chi2_device,
+                                        double* dngal_device, double* dchi2_device,
+                                        double* fisher_device) {
+  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
+                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
+                                true, fisher_device);
+}
+
+int tc_chi2_fisher_zheng07_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                                 int n_gauss, unsigned flags, const double* data,
+                                 const double* precision, double* ngal, double* chi2,
+                                 double* dngal, double* dchi2, double* fisher) {
+  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
+                              chi2, dngal, dchi2, true, fisher);
 }
 
 // ---- occupation VJP (launch.hip: run_vjp) -------------------------------------------------

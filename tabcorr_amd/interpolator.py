@@ -562,6 +562,104 @@ class Interpolator:
                 {key: float(dngal[0, k]) for k, key in enumerate(keys)},
                 {key: dxi[0, k] for k, key in enumerate(keys)})
 
+    # -- Fisher matrix of the likelihood ------------------------------------------------
+
+    def chi2_fisher_batch(self, theta, x, data, precision, n_gauss_prim=10,
+                          extrapolate=False, modulate_with_cenocc=False):
+        """`chi2_grad_batch` with the Fisher matrix of the likelihood over
+        ``(theta, x)``, from the same launch: with ``dxi_k`` the Jacobian
+        column of quantity ``k`` (`ZHENG07_KEYS`, then ``self.keys``),
+
+            ``fisher[:, k, l] = 1/2 sum_r dxi_k[r] (sum_s (P[r, s] + P[s, r])
+            dxi_l[s]) = dxi_k^T P_sym dxi_l``
+
+        with ``P_sym = (precision + precision^T) / 2`` (see
+        `TabCorr.chi2_fisher_batch`).  The Gauss-Newton Hessian of chi2 is
+        ``2 fisher``.  The ``ngal`` part of a likelihood stays the caller's:
+        ``dngal`` is returned next to ``fisher``, and an outer product
+        completes it.  The matrix is symmetric to the bit; a draw's matrix
+        does not depend on its batch, and not on ``data``.
+
+        Returns
+        -------
+        ngal, chi2 : ``(n_draws, )``
+        dngal, dchi2 : ``(n_draws, 5 + D)`` -- those of `chi2_grad_batch`, bit
+            for bit
+        fisher : ``(n_draws, 5 + D, 5 + D)``
+        """
+        theta, x = self._grad_inputs(theta, x, extrapolate)
+        data, precision = _chi2_operands(
+            data, precision, len(self.tabcorr_list[0].tpcf_matrix))
+        device = self.to_device()
+        n_draws = len(theta)
+        n_cols = len(ZHENG07_KEYS) + len(self.keys)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal = np.empty((n_draws, n_cols))
+        dchi2 = np.empty((n_draws, n_cols))
+        fisher = np.empty((n_draws, n_cols, n_cols))
+        with device.lock:
+            _lib.check(device.lib.tc_interp_chi2_fisher_zheng07_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                _lib.as_double_p(x), n_draws, n_gauss_prim,
+                _flags(False, modulate_with_cenocc), _lib.as_double_p(data),
+                _lib.as_double_p(precision), _lib.as_double_p(ngal),
+                _lib.as_double_p(chi2), _lib.as_double_p(dngal),
+                _lib.as_double_p(dchi2), _lib.as_double_p(fisher)))
+        return ngal, chi2, dngal, dchi2, fisher
+
+    def fisher_batch(self, theta, x, precision, n_gauss_prim=10,
+                     extrapolate=False, modulate_with_cenocc=False):
+        """The forecast form of `chi2_fisher_batch`, which needs no data: the
+        same launch with a zero data vector, without ``chi2`` and ``dchi2``.
+        The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal`` part of
+        a likelihood is the caller's, from ``dngal`` by an outer product.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )``
+        dngal : ``(n_draws, 5 + D)``
+        fisher : ``(n_draws, 5 + D, 5 + D)``
+        """
+        ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
+            theta, x, np.zeros(len(self.tabcorr_list[0].tpcf_matrix)),
+            precision, n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
+            modulate_with_cenocc=modulate_with_cenocc)
+        return ngal, dngal, fisher
+
+    def fisher(self, model, precision, n_gauss_prim=10, extrapolate=False,
+               check_consistency=True):
+        """Un-batched `fisher_batch` for a model object: a plain
+        `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model)
+        whose ``param_dict`` holds the extra parameters, as `predict_grad`
+        takes.  The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal``
+        part of a likelihood is the caller's, from ``dngal`` by an outer
+        product.
+
+        Returns
+        -------
+        ngal : float
+        dngal : dict, ``ZHENG07_KEYS + tuple(self.keys)`` -> float
+        fisher : numpy.ndarray of shape ``(5 + D, 5 + D)`` in that key order
+        """
+        x = self._x_model(model)
+        if check_consistency:
+            for halotab in self.tabcorr_list:
+                halotab._check_consistency_cached(model)
+        spec = device_spec(model)
+        if spec is None or spec.family != 'zheng07' or spec.assembias:
+            raise NotImplementedError(
+                'fisher needs a plain Zheng07 model (no assembly bias, no '
+                'other family).')
+        ngal, dngal, fisher = self.fisher_batch(
+            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            x[np.newaxis], precision, n_gauss_prim=n_gauss_prim,
+            extrapolate=extrapolate,
+            modulate_with_cenocc=spec.modulate_with_cenocc)
+        keys = tuple(ZHENG07_KEYS) + tuple(self.keys)
+        return (float(ngal[0]),
+                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
+                fisher[0])
+
     # -- generic models: host callbacks + device contraction per table -----------------
 
     def _spline_matrices(self):

@@ -816,6 +816,105 @@ class TabCorr:
                 {key: float(dngal[0, k]) for k, key in enumerate(ZHENG07_KEYS)},
                 {key: dxi[0, k] for k, key in enumerate(ZHENG07_KEYS)})
 
+    # -- Fisher matrix of the likelihood ---------------------------------------------------
+
+    def chi2_fisher_batch(self, theta, data, precision, n_gauss_prim=10,
+                          modulate_with_cenocc=False):
+        """`chi2_grad_batch` with the Fisher matrix of the likelihood, from
+        the same launch: with ``dxi_k`` the Jacobian column of parameter ``k``
+        (`ZHENG07_KEYS` order),
+
+            ``fisher[:, k, l] = 1/2 sum_r dxi_k[r] (sum_s (P[r, s] + P[s, r])
+            dxi_l[s]) = dxi_k^T P_sym dxi_l``
+
+        with ``P_sym = (precision + precision^T) / 2`` as in `chi2_grad_batch`:
+        the Gauss-Newton normal matrix that a Levenberg-Marquardt step or a
+        Fisher forecast would otherwise form from the whole Jacobian of
+        `predict_batch_grad` on the host.  The Gauss-Newton Hessian of chi2 is
+        ``2 fisher``.  The ``ngal`` part of a likelihood stays the caller's:
+        ``dngal`` is returned next to ``fisher``, and an outer product
+        (``dngal[:, :, None] * dngal[:, None, :] / sigma_ngal**2``) completes
+        it.
+
+        Every pair ``k <= l`` is computed once and stored to both positions:
+        the matrix is symmetric to the bit.  A draw's matrix does not depend
+        on its batch, and not on ``data``.  Where the value divides by zero
+        (``ngal = 0``, ``sigma_logM = 0``) the entries are NaN or inf, as the
+        gradients are.
+
+        Returns
+        -------
+        ngal, chi2 : ``(n_draws, )``
+        dngal, dchi2 : ``(n_draws, 5)`` -- those of `chi2_grad_batch`, bit for bit
+        fisher : ``(n_draws, 5, 5)``
+        """
+        theta = _grad_theta(theta)
+        data, precision = _chi2_operands(data, precision,
+                                         len(self.tpcf_matrix))
+        device = self.to_device()
+        n_draws = len(theta)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal, dchi2 = np.empty((n_draws, 5)), np.empty((n_draws, 5))
+        fisher = np.empty((n_draws, 5, 5))
+        with device.lock:
+            _lib.check(device.lib.tc_chi2_fisher_zheng07_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
+                _lib.as_double_p(data), _lib.as_double_p(precision),
+                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
+                _lib.as_double_p(dngal), _lib.as_double_p(dchi2),
+                _lib.as_double_p(fisher)))
+        return ngal, chi2, dngal, dchi2, fisher
+
+    def fisher_batch(self, theta, precision, n_gauss_prim=10,
+                     modulate_with_cenocc=False):
+        """The forecast form of `chi2_fisher_batch`, which needs no data: the
+        same launch with a zero data vector, without ``chi2`` and ``dchi2``.
+        The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal`` part of
+        a likelihood is the caller's, from ``dngal`` by an outer product.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )``
+        dngal : ``(n_draws, 5)``
+        fisher : ``(n_draws, 5, 5)``, ``fisher[:, k, l] = dxi_k^T P_sym dxi_l``
+        """
+        ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
+            theta, np.zeros(len(self.tpcf_matrix)), precision,
+            n_gauss_prim=n_gauss_prim,
+            modulate_with_cenocc=modulate_with_cenocc)
+        return ngal, dngal, fisher
+
+    def fisher(self, model, precision, n_gauss_prim=10,
+               check_consistency=True):
+        """Un-batched `fisher_batch` for a model object: a plain
+        `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model),
+        as `predict_grad` takes.  The Gauss-Newton Hessian of chi2 is
+        ``2 fisher``; the ``ngal`` part of a likelihood is the caller's, from
+        ``dngal`` by an outer product.
+
+        Returns
+        -------
+        ngal : float
+        dngal : dict, `ZHENG07_KEYS` -> float
+        fisher : numpy.ndarray of shape ``(5, 5)`` in `ZHENG07_KEYS` order,
+            ``fisher[k, l] = dxi_k^T P_sym dxi_l``
+        """
+        if check_consistency:
+            self._check_consistency_cached(model)
+        spec = device_spec(model)
+        if spec is None or spec.family != 'zheng07' or spec.assembias:
+            raise NotImplementedError(
+                'fisher needs a plain Zheng07 model (no assembly bias, no '
+                'other family).')
+        ngal, dngal, fisher = self.fisher_batch(
+            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            precision, n_gauss_prim=n_gauss_prim,
+            modulate_with_cenocc=spec.modulate_with_cenocc)
+        return (float(ngal[0]),
+                {key: float(dngal[0, k]) for k, key in enumerate(ZHENG07_KEYS)},
+                fisher[0])
+
     # -- reverse mode at the occupation seam ---------------------------------------------
 
     def _vjp_occupation(self, occupation):

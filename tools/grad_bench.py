@@ -20,8 +20,16 @@ The occupation-VJP leg times TabCorr.predict_vjp and TabCorr.chi2_grad_occupatio
 in and out) against predict(ndarray) on the same occupations -- the forward seam they
 differentiate -- and against predict_batch_grad, on the two table shapes above.
 
-Prints one JSON line and, with --notes, appends the figures to that file.  --only vjp: that leg
-alone.
+The Fisher leg (--only fisher; not part of the default run) times chi2_fisher_batch -- chi2, its
+gradient and the Fisher matrix of every draw from one launch -- next to chi2_grad_batch and next
+to what a user pays for the same matrix without it: predict_batch_grad plus the NumPy einsum over
+the Jacobian it brings back (jacobian_route_us).  Host arrays in and out, on the two table shapes
+and the two interpolator shapes above and on a mode-cross table with the 148 r bins of the LDS
+limit (where the n_r^2 terms of an entry are most); for the tables also the two device-pointer
+entries, device-resident and pipelined, where the kernel's own increase shows.
+
+Prints one JSON line and, with --notes, appends the figures to that file.  --only vjp, --only
+fisher: that leg alone.
 """
 
 import argparse
@@ -181,6 +189,117 @@ def measure_occupation_vjp(name, n_prim, n_sec, n_r, n_draws, seconds):
     return result
 
 
+def fisher_calls(target, theta, x, n_r, seconds):
+    """The three host-array figures of the Fisher leg for a table (x None) or an interpolator."""
+    rng = np.random.default_rng(3)
+    data = np.ascontiguousarray(rng.uniform(0.5, 1.5, n_r))
+    precision = np.ascontiguousarray(np.eye(n_r) + 0.01 * rng.normal(size=(n_r, n_r)))
+    p_sym = 0.5 * (precision + precision.T)
+    draws = (theta, ) if x is None else (theta, x)
+
+    def jacobian_route():
+        dxi = target.predict_batch_grad(*draws)[3]
+        return np.einsum('nkr,rs,nls->nkl', dxi, p_sym, dxi, optimize=True)
+
+    calls = [('chi2_grad_us', lambda: target.chi2_grad_batch(*draws, data, precision)),
+             ('chi2_fisher_us', lambda: target.chi2_fisher_batch(*draws, data, precision)),
+             ('jacobian_route_us', jacobian_route),
+             # the first figure again: the two bracket the drift of the run
+             ('chi2_grad_again_us', lambda: target.chi2_grad_batch(*draws, data, precision))]
+    result = {key: time_calls(call, seconds) * 1e6 for key, call in calls}
+    # the two routes give the same matrix (to rounding: the orders of the sums differ)
+    fisher = target.chi2_fisher_batch(*draws, data, precision)[4]
+    expect = jacobian_route()
+    finite = np.isfinite(expect) & np.isfinite(fisher)
+    result['routes_max_difference'] = float(np.max(
+        np.abs(fisher - expect)[finite] / np.max(np.abs(expect[finite]))))
+    chi2_grad_us = 0.5 * (result['chi2_grad_us'] + result['chi2_grad_again_us'])
+    result['chi2_fisher_over_chi2_grad'] = result['chi2_fisher_us'] / chi2_grad_us
+    result['jacobian_route_over_chi2_fisher'] = (result['jacobian_route_us'] /
+                                                 result['chi2_fisher_us'])
+    return result, data, precision
+
+
+def measure_fisher(name, n_prim, n_sec, n_r, n_draws, seconds, mode='auto'):
+    from tabcorr_amd import TabCorr, _lib, synthetic
+    table = synthetic.synthetic_table(n_prim, n_sec, (n_r, ), mode, seed=0)
+    halotab = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'], table['tpcf_shape'],
+                                  table['attrs'])
+    theta = synthetic.zheng07_draws(n_draws, seed=1)
+    result = {'table': name, 'n_bins': 2 * n_prim * n_sec, 'n_r': n_r, 'n_draws': n_draws}
+    figures, data, precision = fisher_calls(halotab, theta, None, n_r, seconds)
+    result.update(figures)
+    # the device-pointer entries, device-resident and pipelined over the handle's lanes
+    device = halotab.to_device()
+    lib, handle = device.lib, device.handle
+    memory = Device(lib, _lib)
+    d_theta = memory.upload(theta)
+    d_ngal, d_chi2 = memory.malloc(n_draws), memory.malloc(n_draws)
+    d_dngal, d_dchi2 = memory.malloc(n_draws * 5), memory.malloc(n_draws * 5)
+    d_fisher = memory.malloc(n_draws * 25)
+    operands = (_lib.as_double_p(data), _lib.as_double_p(precision))
+
+    def chi2_gradient():
+        _lib.check(lib.tc_chi2_grad_zheng07_batch_device(
+            handle, d_theta, 5, n_draws, 10, 0, *operands, d_ngal, d_chi2, d_dngal, d_dchi2))
+
+    def chi2_fisher():
+        _lib.check(lib.tc_chi2_fisher_zheng07_batch_device(
+            handle, d_theta, 5, n_draws, 10, 0, *operands, d_ngal, d_chi2, d_dngal, d_dchi2,
+            d_fisher))
+
+    def synchronize():
+        _lib.check(lib.tc_table_synchronize(handle))
+
+    try:
+        result['chi2_grad_device_us'] = sustained(chi2_gradient, synchronize, seconds) * 1e6
+        result['chi2_fisher_device_us'] = sustained(chi2_fisher, synchronize, seconds) * 1e6
+        result['chi2_grad_device_again_us'] = sustained(chi2_gradient, synchronize, seconds) * 1e6
+        result['chi2_fisher_over_chi2_grad_device'] = result['chi2_fisher_device_us'] / (
+            0.5 * (result['chi2_grad_device_us'] + result['chi2_grad_device_again_us']))
+    finally:
+        synchronize()
+        memory.free_all()
+    return result
+
+
+def measure_fisher_interpolator(name, grid, n_prim, n_sec, n_r, mode, n_draws, seconds):
+    from tabcorr_amd import Interpolator, TabCorr, synthetic
+    tables, keys, points = synthetic.synthetic_interpolator(grid, n_prim, n_sec, (n_r, ), mode,
+                                                            seed=0)
+    interp = Interpolator(
+        [TabCorr.from_arrays(t['gal_type'], t['tpcf_matrix'], t['tpcf_shape'], t['attrs'])
+         for t in tables], {key: points[:, d] for d, key in enumerate(keys)})
+    theta = synthetic.zheng07_draws(n_draws, seed=1)
+    x = np.random.default_rng(3).uniform(points.min(axis=0), points.max(axis=0),
+                                         size=(n_draws, len(keys)))
+    result = {'interpolator': name, 'grid': list(grid), 'mode': mode,
+              'n_bins': len(tables[0]['gal_type']), 'n_r': n_r, 'n_draws': n_draws,
+              'n_columns': 5 + len(keys)}
+    result.update(fisher_calls(interp, theta, x, n_r, seconds)[0])
+    return result
+
+
+def write_fisher_notes(notes, tables, interpolators, n_draws):
+    notes.write('\n## tools/grad_bench.py --only fisher, %d draws per call, host arrays in and '
+                'out\n\n' % n_draws)
+    notes.write('| shape | bins | Q | chi2_grad us | chi2_fisher us | jacobian route us | '
+                'chi2_fisher / chi2_grad | jacobian route / chi2_fisher | '
+                'device-pointer entries: chi2_grad, chi2_fisher us (ratio) |\n')
+    notes.write('|---|---|---|---|---|---|---|---|---|\n')
+    for r in tables + interpolators:
+        device = '-'
+        if 'chi2_fisher_device_us' in r:
+            device = '%.1f (%.1f after), %.1f (%.3f)' % (
+                r['chi2_grad_device_us'], r['chi2_grad_device_again_us'],
+                r['chi2_fisher_device_us'], r['chi2_fisher_over_chi2_grad_device'])
+        notes.write('| %s | %d | %d | %.1f (%.1f after) | %.1f | %.1f | %.3f | %.2f | %s |\n' % (
+            r.get('table', r.get('interpolator')), r['n_bins'], r.get('n_columns', 5),
+            r['chi2_grad_us'], r['chi2_grad_again_us'], r['chi2_fisher_us'],
+            r['jacobian_route_us'], r['chi2_fisher_over_chi2_grad'],
+            r['jacobian_route_over_chi2_fisher'], device))
+
+
 def write_vjp_notes(notes, results, n_draws):
     notes.write('\n## tools/grad_bench.py, occupation VJP, %d draws per call, host arrays in '
                 'and out\n\n' % n_draws)
@@ -204,8 +323,27 @@ def main():
     parser.add_argument('--draws', type=int, default=10000)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--notes', default=None, help='append the figures to this file')
-    parser.add_argument('--only', choices=['vjp'], default=None, help='one leg alone')
+    parser.add_argument('--only', choices=['vjp', 'fisher'], default=None, help='one leg alone')
     args = parser.parse_args()
+    if args.only == 'fisher':
+        tables = [measure_fisher('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
+                  measure_fisher("reference example table's shape", 30, 1, 19, args.draws,
+                                 args.seconds),
+                  # where the n_r^2 terms of an entry are most: the r bins of the LDS limit
+                  measure_fisher('mode cross, 148 r bins (the LDS limit)', 9, 2, 148, args.draws,
+                                 args.seconds, mode='cross')]
+        interpolators = [
+            measure_fisher_interpolator('5 x 5 grid of 100-bin tables', (5, 5), 50, 1, 19, 'auto',
+                                        args.draws, args.seconds),
+            measure_fisher_interpolator("AbacusSummit interpolator's shape", (4, ), 276, 2, 13,
+                                        'cross', args.draws, args.seconds)]
+        print(json.dumps({'fisher_metric': 'us per call, host arrays in and out; *_device_us: '
+                                           'device-resident, pipelined',
+                          'fisher_tables': tables, 'fisher_interpolators': interpolators}))
+        if args.notes:
+            with open(args.notes, 'a') as notes:
+                write_fisher_notes(notes, tables, interpolators, args.draws)
+        return
     vjp = [measure_occupation_vjp('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
            measure_occupation_vjp("reference example table's shape", 30, 1, 19, args.draws,
                                   args.seconds)]
