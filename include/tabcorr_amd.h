@@ -251,6 +251,39 @@ int tc_chi2_fisher_zheng07_batch_device(tc_table* table, const double* theta_dev
                                         double* ngal_device, double* chi2_device,
                                         double* dngal_device, double* dchi2_device,
                                         double* fisher_device);
+/* The gradients of the model decorated with Heaviside assembly bias at the median split (what
+ * TC_FLAG_ASSEMBIAS predicts): n_theta must be 7, the five Zheng07 parameters, then the strengths
+ * of the centrals' and the satellites' assembly bias, and there are 7 wherever 5 stands above:
+ * dngal (n_draws, 7), dxi (n_draws, 7, n_r), dchi2 (n_draws, 7), fisher (n_draws, 7, 7).  With c
+ * the clip of a strength to [-1, 1] and s_b = +1 for a bin whose sec_haloprop_percentile lies
+ * above 0.5, else -1: <N_cen>' = N + s_b c(A_cen) min(N, 1 - N) per quadrature node and <N_sat>'
+ * = (1 + s_b c(A_sat)) N, N the plain occupations (with TC_FLAG_MODULATE_WITH_CENOCC the
+ * satellites' N holds the PLAIN <N_cen>).  The derivative is that of the function computed: the
+ * column of a strength beyond [-1, 1] is exactly zero, at +-1 it is the one facing inside, and
+ * min(N, 1 - N) takes the branch N <= 1 - N at a tie.  flags: 0 or
+ * TC_FLAG_MODULATE_WITH_CENOCC (the decoration is implied; TC_FLAG_ASSEMBIAS and every other
+ * flag is TC_ERR_UNSUPPORTED).  Otherwise as the plain calls: one launch per batch, a draw's
+ * results depend on the draw alone, float32 tables and tables beyond the LDS budget (8 for 6
+ * quantities, 4 rows per central and 7 per satellite bin) are refused.  The likelihood calls take
+ * a trailing `fisher`, which may be NULL: not asked for. */
+int tc_predict_grad_assembias_batch(tc_table* table, const double* theta, int n_theta,
+                                    int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                    double* ngal, double* xi, double* dngal, double* dxi);
+int tc_predict_grad_assembias_batch_device(tc_table* table, const double* theta_device,
+                                           int n_theta, int64_t n_draws, int n_gauss_prim,
+                                           unsigned flags, double* ngal_device,
+                                           double* xi_device, double* dngal_device,
+                                           double* dxi_device);
+int tc_chi2_grad_assembias_batch(tc_table* table, const double* theta, int n_theta,
+                                 int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                 const double* data, const double* precision, double* ngal,
+                                 double* chi2, double* dngal, double* dchi2, double* fisher);
+int tc_chi2_grad_assembias_batch_device(tc_table* table, const double* theta_device, int n_theta,
+                                        int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                        const double* data, const double* precision,
+                                        double* ngal_device, double* chi2_device,
+                                        double* dngal_device, double* dchi2_device,
+                                        double* fisher_device);
 
 /* A handful of independent draws in ONE launch (the proposals of an ensemble sampler's step,
  * or the reference's un-batched predict(), README.md:72-75, for n_walkers = 1): every
@@ -427,6 +460,32 @@ int tc_interp_chi2_fisher_zheng07_batch(tc_interp* interp, const double* theta, 
                                         const double* precision, double* ngal, double* chi2,
                                         double* dngal, double* dchi2, double* fisher);
 int tc_interp_chi2_fisher_zheng07_batch_device(tc_interp* interp, const double* theta_device,
+                                               int n_theta, const double* x_device,
+                                               int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                               const double* data, const double* precision,
+                                               double* ngal_device, double* chi2_device,
+                                               double* dngal_device, double* dchi2_device,
+                                               double* fisher_device);
+/* The interpolator's gradients for the model decorated with assembly bias (as
+ * tc_predict_grad_assembias_batch: n_theta must be 7, flags 0 or TC_FLAG_MODULATE_WITH_CENOCC):
+ * 7 + D columns, the seven model parameters first -- dngal (n_draws, 7 + D), dxi (n_draws, 7 + D,
+ * n_r), dchi2 (n_draws, 7 + D), fisher (n_draws, 7 + D, 7 + D), which may be NULL. */
+int tc_interp_predict_grad_assembias_batch(tc_interp* interp, const double* theta, int n_theta,
+                                           const double* x, int64_t n_draws, int n_gauss_prim,
+                                           unsigned flags, double* ngal, double* xi,
+                                           double* dngal, double* dxi);
+int tc_interp_predict_grad_assembias_batch_device(tc_interp* interp, const double* theta_device,
+                                                  int n_theta, const double* x_device,
+                                                  int64_t n_draws, int n_gauss_prim,
+                                                  unsigned flags, double* ngal_device,
+                                                  double* xi_device, double* dngal_device,
+                                                  double* dxi_device);
+int tc_interp_chi2_grad_assembias_batch(tc_interp* interp, const double* theta, int n_theta,
+                                        const double* x, int64_t n_draws, int n_gauss_prim,
+                                        unsigned flags, const double* data,
+                                        const double* precision, double* ngal, double* chi2,
+                                        double* dngal, double* dchi2, double* fisher);
+int tc_interp_chi2_grad_assembias_batch_device(tc_interp* interp, const double* theta_device,
                                                int n_theta, const double* x_device,
                                                int64_t n_draws, int n_gauss_prim, unsigned flags,
                                                const double* data, const double* precision,

@@ -18,7 +18,9 @@ extern "C" {
 /* Host evaluation of the table-driven FP64 functions the occupation kernel uses in place
  * of the device libm (tabcorr_amd/csrc/fastmath.h): kind 0 erf, 1 log2 (x > 0 normal),
  * 2 exp2, 3 exp10, 4 erf and 5 its derivative 2/sqrt(pi) exp(-x^2) from erf_gauss_fast,
- * 6 the natural logarithm (x > 0 normal) of the gradient kernels. */
+ * 6 the natural logarithm (x > 0 normal) of the gradient kernels, 7 erfc(|x|) / 2 for |x| >= 2.5
+ * as the assembly-bias gradient kernels form it from the Gaussian of kind 5 (half_erfc_from_gauss;
+ * from |x| = 6 on, where kind 5 is zero, from the libm Gaussian). */
 int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y);
 
 /* The dense matrix-operand layout the gradient kernel of mode auto reads
@@ -26,6 +28,14 @@ int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y);
  * (p = i (i + 1) / 2 + j, j <= i) and read back lane by lane as the kernel addresses it:
  * dense (n_r, n_bins, n_bins) = the symmetric matrices.  Fails if a padding entry is not zero. */
 int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* dense);
+
+/* The LDS bytes per workgroup that the launch layer asks for and refuses by
+ * (tabcorr_amd/csrc/grad.h): kernel 0 grad_auto_kernel, 1 grad_cross_kernel, 2
+ * grad_interp_auto_kernel, 3 grad_interp_cross_kernel; n_params 5 (plain Zheng07) or 7 (decorated
+ * with assembly bias); chi2: the likelihood is finished in the launch; n_dim: the interpolator's
+ * axes (ignored by kernels 0 and 1, as n_bins and n_central are by 1 and 3). */
+int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n_r, int n_dim,
+                      int chi2, int64_t* bytes);
 
 /* The moment expansion of a central bin's node sum (tabcorr_amd/csrc/series.h) on the host,
  * next to the node loop it replaces: for one bin [log_min, log_max] with

@@ -59,6 +59,7 @@ SIGNATURES = {
     'tc_debug_fastmath': [ctypes.c_int, ctypes.c_int64, c_double_p,
                           c_double_p],
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
+    'tc_debug_grad_lds': [ctypes.c_int] * 7 + [c_int64_p],
     'tc_pair_indices': [ctypes.c_int, c_int32_p, c_int32_p, c_int32_p],
     'tc_spline_interpolation_matrix': [ctypes.c_int, c_double_p, c_double_p],
     'tc_spline_weights': [ctypes.c_int, c_double_p, c_double_p, ctypes.c_double, c_double_p,
@@ -135,6 +136,23 @@ SIGNATURES = {
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
         c_double_p, c_double_p, c_double_p, c_double_p],
     'tc_chi2_fisher_zheng07_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    # (decorated with assembly bias: 7 columns; the trailing fisher may be None)
+    'tc_predict_grad_assembias_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p],
+    'tc_predict_grad_assembias_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p],
+    'tc_chi2_grad_assembias_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_chi2_grad_assembias_batch_device': [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
@@ -222,6 +240,23 @@ SIGNATURES = {
         ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
         c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
     'tc_interp_chi2_fisher_zheng07_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p],
+    'tc_interp_predict_grad_assembias_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        c_double_p, c_double_p],
+    'tc_interp_predict_grad_assembias_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    'tc_interp_chi2_grad_assembias_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_interp_chi2_grad_assembias_batch_device': [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -20,7 +20,8 @@ LIBRARY = os.path.join(HERE, 'libtabcorr_hip.so')
 # compile in parallel, the longest first), paircount.hip the tabulation kernels; launch.hip and
 # the .cpp units are host code
 SOURCES = ['inst_fused.hip', 'inst_fused32.hip', 'inst_fused16.hip', 'inst_fused40.hip',
-           'inst_cross.hip', 'inst_quad.hip', 'inst_single.hip', 'inst_grad.hip', 'inst_vjp.hip',
+           'inst_cross.hip', 'inst_quad.hip', 'inst_single.hip', 'inst_grad.hip',
+           'inst_grad_assembias.hip', 'inst_vjp.hip',
            'launch.hip', 'paircount.hip',
            'table.cpp', 'interp.cpp', 'comm.cpp', 'runtime.cpp', 'hostmath.cpp']
 # per-unit flags (inst_single.hip: see its header)

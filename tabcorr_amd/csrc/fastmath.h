@@ -149,6 +149,38 @@ TC_HD double erf_gauss_fast(const double* table, const Consts& k, double x, doub
   return copysign(fma(g * h, s, row[0]), x);
 }
 
+// erfc(|x|) / 2 for |x| >= kErfcFrom from the Gaussian g = 2/sqrt(pi) exp(-x^2) the caller has at
+// hand: erfc(x) = exp(-x^2) erfcx(x), and x erfcx(x) is a polynomial of degree 14 in t = 1 / x^2
+// on 0 <= t <= 1 / kErfcFrom^2 (a Chebyshev fit rewritten in u = 2 t kErfcFrom^2 - 1; 4e-14
+// relative).  For min(N, 1 - N) of the decorated centrals' A_cen column (grad_kernels.hip.h),
+// where 1 - N carries the absolute rounding of N.  x_abs = inf gives 0.
+constexpr double kErfcFrom = 2.5;
+TC_HD double half_erfc_from_gauss(double x_abs, double gauss) {
+  constexpr double c[15] = {
+      0.5439016215198279,
+      -0.018351285411052486,
+      0.0016592352017971237,
+      -0.00022669009504947842,
+      3.9755978152344944e-05,
+      -8.292149581150471e-06,
+      1.969342781200889e-06,
+      -5.175773405844965e-07,
+      1.4778217679377117e-07,
+      -4.6197825227755686e-08,
+      1.5218126073604054e-08,
+      -3.987232667916014e-09,
+      1.267643139910619e-09,
+      -1.2793517979072261e-09,
+      5.397997306082776e-10};
+  const double inv = 1.0 / x_abs;
+  const double u = fma(inv * inv, 2.0 * kErfcFrom * kErfcFrom, -1.0);
+  double p = c[14];
+#pragma unroll
+  for (int i = 13; i >= 0; --i) p = fma(p, u, c[i]);
+  // gauss sqrt(pi) / 2 = exp(-x^2); half of erfc
+  return gauss * 0.44311346272637900682 * (p * inv);
+}
+
 // log2(y) - offset for a positive normal y.
 TC_HD double log2_fast_offset(const double* table, const Consts& k, double y,
                               double offset) {

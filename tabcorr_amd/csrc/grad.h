@@ -1,4 +1,6 @@
-// Analytic gradients of (ngal, xi, chi2) with respect to the five Zheng07 parameters: the
+// Analytic gradients of (ngal, xi, chi2) with respect to the five Zheng07 parameters -- or, for
+// the model decorated with Heaviside assembly bias at the median split, those and the two
+// strengths (`n_params` = 5 or 7 below, a template parameter of the kernels) --: the
 // argument block of the gradient kernels (grad_kernels.hip.h), their LDS budget and the dense
 // matrix-operand layout of a mode-auto table.  Plain C++ for the host-only units that fill these
 // in, but for spline_weights, which hipcc also compiles for the device.
@@ -17,13 +19,17 @@
 namespace tc {
 
 constexpr int kGradParams = 5;        // logMmin, sigma_logM, logM0, logM1, alpha
+// ... and the strengths of the centrals' and the satellites' assembly bias (the decorated model):
+// N_cen' = N + s_b c(A_cen) min(N, 1 - N) per node and N_sat' = (1 + s_b c(A_sat)) N with c the
+// clip to [-1, 1] and s_b = +1 for a bin whose secondary percentile lies above 0.5, else -1
+constexpr int kGradParamsAssembias = 7;
 constexpr int kGradDraws = 16;        // draws per workgroup: the N of one v_mfma_f64_16x16x4_f64
 constexpr int kGradWaves = 4;
 constexpr int kGradThreads = 64 * kGradWaves;
 constexpr int kGradCrossSlab = 64;    // mode cross: bins whose w and dw one LDS slab holds
 
 struct GradArgs {
-  const double* theta;       // (n_draws, 5)
+  const double* theta;       // (n_draws, 5) -- 7 wherever 5 stands below, decorated
   int64_t n_draws;
   int n_bins;
   int n_central;
@@ -50,26 +56,34 @@ struct GradArgs {
   // quantities (n_draws, 5, 5) -- (n_draws, 5 + n_dim, 5 + n_dim) for an interpolator; NULL: not
   // asked for.  Only with the likelihood (xi NULL): grad_kernels.hip.h: finish_fisher
   double* fisher;
+  const double* percentile;  // (n_bins) sec_haloprop_percentile, library bin order; decorated only
 };
 
 // ---- LDS of grad_auto_kernel ------------------------------------------------------------------
 // Rows of kGradDraws doubles.  A central bin keeps (w, dw/dlogMmin, dw/dsigma), a satellite bin
 // w and all five derivatives (three of them zero unless modulate_with_cenocc); one shared row of
 // zeros stands for everything else: the derivatives a central bin does not have and the padding
-// of the matrix up to whole tiles.
-constexpr int grad_auto_rows(int n_bins, int n_central) {
-  return 3 * n_central + 6 * (n_bins - n_central) + 1;
+// of the matrix up to whole tiles.  Decorated (n_params = 7): a central bin keeps a fourth row,
+// dw/dA_cen, a satellite bin a seventh, dw/dA_sat.
+constexpr int grad_central_rows(int n_params) { return n_params == kGradParams ? 3 : 4; }
+constexpr int grad_satellite_rows(int n_params) { return n_params == kGradParams ? 6 : 7; }
+constexpr int grad_auto_rows(int n_bins, int n_central, int n_params = kGradParams) {
+  return grad_central_rows(n_params) * n_central +
+         grad_satellite_rows(n_params) * (n_bins - n_central) + 1;
 }
 // ... then the totals (6, kGradDraws) and, for the likelihood, (6, n_r, kGradDraws) residuals
-// and derivatives
-constexpr size_t grad_auto_lds_bytes(int n_bins, int n_central, int n_r, bool chi2) {
-  return ((size_t)grad_auto_rows(n_bins, n_central) + 6 + (chi2 ? 6 * (size_t)n_r : 0)) *
+// and derivatives -- 8 for 6 where decorated, here and below
+constexpr size_t grad_auto_lds_bytes(int n_bins, int n_central, int n_r, bool chi2,
+                                     int n_params = kGradParams) {
+  return ((size_t)grad_auto_rows(n_bins, n_central, n_params) + (n_params + 1) +
+          (chi2 ? (n_params + 1) * (size_t)n_r : 0)) *
          kGradDraws * sizeof(double);
 }
 // grad_cross_kernel: one slab (6, kGradCrossSlab, kGradDraws), the products (6, n_r, kGradDraws)
 // and the totals
-constexpr size_t grad_cross_lds_bytes(int n_r) {
-  return (6 * (size_t)kGradCrossSlab + 6 * (size_t)n_r + 6) * kGradDraws * sizeof(double);
+constexpr size_t grad_cross_lds_bytes(int n_r, int n_params = kGradParams) {
+  return (size_t)(n_params + 1) * ((size_t)kGradCrossSlab + (size_t)n_r + 1) * kGradDraws *
+         sizeof(double);
 }
 
 // ---- dense operand layout of a mode-auto table ------------------------------------------------
@@ -161,25 +175,28 @@ struct GradInterpArgs {
   const double* const* class_m;
   const double* const* class_weight;
   const double* const* class_n_h;
+  const double* const* class_percentile;   // decorated only
 };
 
 // LDS rows of kGradDraws doubles that both interpolator kernels keep: the weights and derivative
-// weights of every axis, and the (6 + n_dim) accumulators of xi per r bin.  The likelihood is
-// finished in the accumulators themselves (`chi2` costs nothing).
-constexpr size_t grad_interp_common_rows(int n_r, int n_dim) {
-  return 2 * (size_t)n_dim * kGradMaxAxis + (size_t)(6 + n_dim) * n_r;
+// weights of every axis, and the (6 + n_dim) accumulators of xi per r bin ((8 + n_dim) where
+// decorated).  The likelihood is finished in the accumulators themselves (`chi2` costs nothing).
+constexpr size_t grad_interp_common_rows(int n_r, int n_dim, int n_params = kGradParams) {
+  return 2 * (size_t)n_dim * kGradMaxAxis + (size_t)(n_params + 1 + n_dim) * n_r;
 }
 // grad_interp_auto_kernel: the rows of grad_auto_kernel for one class at a time, its totals.
 constexpr size_t grad_interp_auto_lds_bytes(int n_bins, int n_central, int n_r, int n_dim,
-                                            bool /* chi2 */) {
-  return ((size_t)grad_auto_rows(n_bins, n_central) + 6 + grad_interp_common_rows(n_r, n_dim)) *
+                                            bool /* chi2 */, int n_params = kGradParams) {
+  return ((size_t)grad_auto_rows(n_bins, n_central, n_params) + (n_params + 1) +
+          grad_interp_common_rows(n_r, n_dim, n_params)) *
          kGradDraws * sizeof(double);
 }
 // grad_interp_cross_kernel: one slab, the totals and the weighted products (6 + n_dim, n_r) of
 // the class in flight.
-constexpr size_t grad_interp_cross_lds_bytes(int n_r, int n_dim, bool /* chi2 */) {
-  return (6 * (size_t)kGradCrossSlab + 6 + (size_t)(6 + n_dim) * n_r +
-          grad_interp_common_rows(n_r, n_dim)) *
+constexpr size_t grad_interp_cross_lds_bytes(int n_r, int n_dim, bool /* chi2 */,
+                                             int n_params = kGradParams) {
+  return ((size_t)(n_params + 1) * ((size_t)kGradCrossSlab + 1) +
+          (size_t)(n_params + 1 + n_dim) * n_r + grad_interp_common_rows(n_r, n_dim, n_params)) *
          kGradDraws * sizeof(double);
 }
 

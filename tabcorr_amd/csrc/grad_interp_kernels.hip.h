@@ -18,6 +18,7 @@
 //      the Fisher matrix over the same 5 + n_dim quantities.
 // The order of every sum -- tables, rows, slabs -- is fixed by the interpolator: a draw's results
 // do not depend on the batch or on the draw's neighbours.
+// NP as in grad_kernels.hip.h: 5, or 7 for the decorated model, where "6" reads 8 and "5" 7.
 #pragma once
 
 #include "grad_kernels.hip.h"
@@ -56,14 +57,17 @@ __device__ __forceinline__ double interp_coef(const GradInterpArgs& ia, const do
 
 // Accumulator q = 0 .. 5 takes c_t times quantity q of the table, q = 6 + d takes dc_t/dx_d times
 // its value (quantity 0).
-__device__ __forceinline__ int interp_which(int q) { return q < 6 ? 0 : q - 5; }
-__device__ __forceinline__ int interp_quantity(int q) { return q < 6 ? q : 0; }
+template <int NP>
+__device__ __forceinline__ int interp_which(int q) { return q < NP + 1 ? 0 : q - NP; }
+template <int NP>
+__device__ __forceinline__ int interp_quantity(int q) { return q < NP + 1 ? q : 0; }
 
 __device__ __forceinline__ void set_class(GradArgs& a, const GradInterpArgs& ia, int v) {
   a.log_m = ia.class_log_m[v];
   a.m = ia.class_m[v];
   a.weight = ia.class_weight[v];
   a.n_h = ia.class_n_h[v];
+  a.percentile = ia.class_percentile != nullptr ? ia.class_percentile[v] : nullptr;
 }
 
 // ngal and its 5 + n_dim derivatives (thread = (q, draw)), then xi and its derivatives from the
@@ -102,18 +106,20 @@ __device__ __forceinline__ void interp_finish(const GradArgs& a, int n_q, double
 }  // namespace grad
 
 // ---- mode auto ----------------------------------------------------------------------------------
+template <int NP>
 __global__ __launch_bounds__(kGradThreads) void grad_interp_auto_kernel(const GradInterpArgs ia) {
+  constexpr int NQ = NP + 1;
   extern __shared__ double grad_lds[];
   GradArgs a = ia.table;
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
   const int n_bins = a.n_bins, n_central = a.n_central, n_r = a.n_r, n_dim = ia.n_dim;
-  const int n_q = 6 + n_dim;
-  const int zero_row = grad_auto_rows(n_bins, n_central) - 1;
+  const int n_q = NQ + n_dim;
+  const int zero_row = grad_auto_rows(n_bins, n_central, NP) - 1;
   double* w = grad_lds;                                               // (rows, 16), one class
   double* total = w + (size_t)(zero_row + 1) * kGradDraws;            // (6, 16), one class
-  double* weights = total + 6 * kGradDraws;                           // (2, n_dim, 32, 16)
+  double* weights = total + NQ * kGradDraws;                           // (2, n_dim, 32, 16)
   double* sums = weights + (size_t)2 * n_dim * kGradMaxAxis * kGradDraws;   // (n_q, n_r, 16)
   const fm::Consts k = fm::make_consts();
   grad::interp_weights(ia, draw0, weights);
@@ -124,12 +130,12 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_auto_kernel(const Gr
     grad::set_class(a, ia, v);
     __syncthreads();
     {
-      const grad::Draw d = grad::load_draw(a, k, draw0 + col);
-      grad::auto_node_loops(a, k, d, w, zero_row);
+      const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+      grad::auto_node_loops<NP>(a, k, d, w, zero_row);
     }
     __syncthreads();
-    if (t < 6 * kGradDraws)
-      total[t] = grad::auto_total(w, t / kGradDraws, col, n_bins, n_central, zero_row);
+    if (t < NQ * kGradDraws)
+      total[t] = grad::auto_total<NP>(w, t / kGradDraws, col, n_bins, n_central, zero_row);
     __syncthreads();
     const double ngal = total[col];
     const double inv_ngal = 1.0 / ngal;
@@ -138,26 +144,26 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_auto_kernel(const Gr
       const int32_t* node = ia.walk_node + (size_t)s * n_dim;
       if (t < n_q * kGradDraws) {
         const int q = t / kGradDraws;
-        my_ngal = fma(grad::interp_coef(ia, weights, node, grad::interp_which(q), col),
-                      total[grad::interp_quantity(q) * kGradDraws + col], my_ngal);
+        my_ngal = fma(grad::interp_coef(ia, weights, node, grad::interp_which<NP>(q), col),
+                      total[grad::interp_quantity<NP>(q) * kGradDraws + col], my_ngal);
       }
       a.matrix = ia.matrices[s];
       const double c = grad::interp_coef(ia, weights, node, 0, col);
       for (int r = wave; r < n_r; r += kGradWaves) {
-        double acc[6];
-        grad::auto_products(a, w, r, zero_row, acc);
+        double acc[NQ];
+        grad::auto_products<NP>(a, w, r, zero_row, acc);
         const double xi = grad::auto_xi(acc, inv_ngal2);
         if (group == 0) {
           double* slot = sums + (size_t)r * kGradDraws + col;
           const size_t stride = (size_t)n_r * kGradDraws;
           slot[0] = fma(c, xi, slot[0]);
 #pragma unroll
-          for (int p = 1; p < 6; ++p)
+          for (int p = 1; p < NQ; ++p)
             slot[p * stride] = fma(c, grad::auto_dxi(acc, p, xi, total, col, inv_ngal, inv_ngal2),
                                    slot[p * stride]);
           for (int d = 0; d < n_dim; ++d)
-            slot[(6 + d) * stride] = fma(grad::interp_coef(ia, weights, node, 1 + d, col), xi,
-                                         slot[(6 + d) * stride]);
+            slot[(NQ + d) * stride] = fma(grad::interp_coef(ia, weights, node, 1 + d, col), xi,
+                                         slot[(NQ + d) * stride]);
         }
       }
     }
@@ -170,22 +176,24 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_auto_kernel(const Gr
 // Inside a class xi_t = T_t . w / ngal shares w and ngal, so the class is linear in the slab
 // products: Y_q = sum_t coef_{t,q} T_t . (w or dw_q) accumulates over slabs and tables, the chain
 // rule of grad_cross_kernel is applied once per class and the class added to the accumulators.
+template <int NP>
 __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const GradInterpArgs ia) {
+  constexpr int NQ = NP + 1;
   extern __shared__ double grad_lds[];
   GradArgs a = ia.table;
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
   const int n_bins = a.n_bins, n_r = a.n_r, n_dim = ia.n_dim;
-  const int n_q = 6 + n_dim;
+  const int n_q = NQ + n_dim;
   const int n_items = n_q * n_r * kGradDraws;
   double* w = grad_lds;                                               // (6, slab, 16)
-  double* total = w + 6 * kGradCrossSlab * kGradDraws;                // (6, 16), one class
-  double* weights = total + 6 * kGradDraws;                           // (2, n_dim, 32, 16)
+  double* total = w + NQ * kGradCrossSlab * kGradDraws;                // (6, 16), one class
+  double* weights = total + NQ * kGradDraws;                           // (2, n_dim, 32, 16)
   double* y = weights + (size_t)2 * n_dim * kGradMaxAxis * kGradDraws;      // (n_q, n_r, 16), one class
   double* sums = y + n_items;                                         // (n_q, n_r, 16)
   const fm::Consts k = fm::make_consts();
-  const grad::Draw d = grad::load_draw(a, k, draw0 + col);
+  const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
   grad::interp_weights(ia, draw0, weights);
   for (int item = t; item < n_items; item += kGradThreads) sums[item] = 0.0;
   double my_ngal = 0.0;                                               // thread = (q, draw)
@@ -198,9 +206,9 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
     for (int slab0 = 0; slab0 < n_bins; slab0 += kGradCrossSlab) {
       const int count = min(kGradCrossSlab, n_bins - slab0);
       __syncthreads();
-      grad::cross_node_loops(a, k, d, slab0, count, w);
+      grad::cross_node_loops<NP>(a, k, d, slab0, count, w);
       __syncthreads();
-      if (t < 6 * kGradDraws) {
+      if (t < NQ * kGradDraws) {
         const int p = t / kGradDraws;
         for (int li = 0; li < count; ++li) my_total += w[(p * kGradCrossSlab + li) * kGradDraws + col];
       }
@@ -209,8 +217,8 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
         const double* matrix = ia.matrices[s];
         // item = (r, quantity p, draw) as in grad_cross_kernel: one product each; the value's
         // product (p = 0) also feeds the n_dim accumulators of d/dx
-        for (int item = t; item < 6 * n_r * kGradDraws; item += kGradThreads) {
-          const int r = item / (6 * kGradDraws), p = item / kGradDraws % 6;
+        for (int item = t; item < NQ * n_r * kGradDraws; item += kGradThreads) {
+          const int r = item / (NQ * kGradDraws), p = item / kGradDraws % NQ;
           const double product =
               grad::cross_slab_product(matrix, n_r, r, slab0, count, w, p, col, 0.0);
           const size_t stride = (size_t)n_r * kGradDraws;
@@ -219,19 +227,19 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
                                  slot[p * stride]);
           if (p == 0)
             for (int e = 0; e < n_dim; ++e)
-              slot[(6 + e) * stride] = fma(grad::interp_coef(ia, weights, node, 1 + e, col),
-                                           product, slot[(6 + e) * stride]);
+              slot[(NQ + e) * stride] = fma(grad::interp_coef(ia, weights, node, 1 + e, col),
+                                           product, slot[(NQ + e) * stride]);
         }
       }
     }
-    if (t < 6 * kGradDraws) total[t] = my_total;
+    if (t < NQ * kGradDraws) total[t] = my_total;
     __syncthreads();
     if (t < n_q * kGradDraws) {
       const int q = t / kGradDraws;
       for (int s = s_begin; s < s_end; ++s)
         my_ngal = fma(grad::interp_coef(ia, weights, ia.walk_node + (size_t)s * n_dim,
-                                        grad::interp_which(q), col),
-                      total[grad::interp_quantity(q) * kGradDraws + col], my_ngal);
+                                        grad::interp_which<NP>(q), col),
+                      total[grad::interp_quantity<NP>(q) * kGradDraws + col], my_ngal);
     }
     // xi = Y_0 / ngal, dxi_k = (Y_k - xi dngal_k) / ngal, d/dx_d = Y_(6 + d) / ngal
     const double inv_ngal = 1.0 / total[col];
@@ -240,7 +248,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
       const size_t slot = ((size_t)q * n_r + r) * kGradDraws + col;
       const double xi = y[(size_t)r * kGradDraws + col] * inv_ngal;
       double value = xi;
-      if (q >= 6)
+      if (q >= NQ)
         value = y[slot] * inv_ngal;
       else if (q > 0)
         value = (y[slot] - xi * total[q * kGradDraws + col]) * inv_ngal;

@@ -1,6 +1,8 @@
 // Gradient kernels: (ngal, xi[, chi2]) of a batch of Zheng07 draws together with their exact
 // derivatives with respect to the five parameters, one launch per batch (grad.h: the argument
-// block, the LDS budget and the operand layout; launch.hip: run_grad).
+// block, the LDS budget and the operand layout; launch.hip: run_grad).  NP, a template parameter
+// of every kernel and piece, is the number of differentiated parameters: 5, or 7 for the model
+// decorated with assembly bias (the two strengths last); "6" below reads NP + 1 there.
 //
 // A workgroup of four waves carries kGradDraws = 16 draws from theta to the results:
 //   1  the node loops of every bin (tabcorr.py:537-578) for <N> and d<N>/dtheta_k, which share
@@ -34,15 +36,23 @@ constexpr double kTwoOverSqrtPi = 1.1283791670955125739;
 
 struct Draw {
   double log_m_min, inv_sigma, m0, m0_ln10, inv_m1, alpha;
+  // decorated: the clipped strengths c(A_cen), c(A_sat) and the clip's derivatives (1 inside
+  // [-1, 1], 0 beyond, NaN for a NaN strength)
+  double a_cen, da_cen, a_sat, da_sat;
 };
+
+constexpr bool decorated(int np) { return np == kGradParamsAssembias; }
 
 // <N_cen> and its derivatives with respect to logMmin and sigma_logM at one node:
 // N = (1 + erf x) / 2, dN/dlogMmin = -exp(-x^2) / (sigma sqrt(pi)), dN/dsigma = x dN/dlogMmin.
 // erf_gauss_fast counts the Gaussian as zero from |x| = 6 on; the derivative of a draw whose
 // every node lies out there is made of exactly these tails, so they are evaluated: exp(-x^2) =
 // 2^z with the rounding error of the product z = -x^2 log2 e carried along.
+// x_abs, gauss_out: |x| and 2/sqrt(pi) exp(-x^2), for the decorated centrals.
 __device__ __forceinline__ void central_node(const double* mt, const fm::Consts& k, const Draw& d,
-                                             double log_m, double* n, double* dn0, double* dn1) {
+                                             double log_m, double* n, double* dn0, double* dn1,
+                                             double* x_abs = nullptr,
+                                             double* gauss_out = nullptr) {
   const double x = (log_m - d.log_m_min) * d.inv_sigma;
   double gauss;
   const double e = fm::erf_gauss_fast(mt, k, x, &gauss);
@@ -55,25 +65,53 @@ __device__ __forceinline__ void central_node(const double* mt, const fm::Consts&
   *n = fma(0.5, e, 0.5);
   *dn0 = -0.5 * gauss * d.inv_sigma;
   *dn1 = *dn0 * x;
+  if (x_abs != nullptr) *x_abs = fabs(x);
+  if (gauss_out != nullptr) *gauss_out = gauss;
 }
 
-// w = n_h <N> of bin i (library order: the centrals first) and its five derivatives:
+// w = n_h <N> of bin i (library order: the centrals first) and its NP derivatives:
 // out[0] = w, out[1 + k] = dw / dtheta_k.
+// Decorated, with s = +-c(A) above / below the split as the forward kernels have it
+// (kernels.hip.h: occ_nodes_zheng07, `median`): per central node N' = N + s_cen min(N, 1 - N),
+// so dN'/dtheta_k = (1 + s_cen tau) dN/dtheta_k with tau = +-1 the branch fmin takes, and
+// dN'/dA_cen = +-c'(A_cen) min(N, 1 - N); a satellite bin's sums take the factor 1 + s_sat
+// (`modulate` multiplies by the PLAIN <N_cen>) and dN'/dA_sat = +-c'(A_sat) N.
+// For the A_cen column min(N, 1 - N) = erfc(|x|) / 2 comes from the node's Gaussian once |x| >=
+// fm::kErfcFrom (fastmath.h: half_erfc_from_gauss): as fmin(n, 1 - n) it carries the absolute
+// rounding of n, 1e-16, which is 1e-8 of it at |x| = 4 -- nothing in the value N', where it
+// stands next to n, but everything in a column that a draw with a narrow sigma_logM makes of
+// such terms alone.  Below kErfcFrom it is at least 2e-4 and fmin's 5e-13 relative do.
+template <int NP>
 __device__ __forceinline__ void bin_values(const GradArgs& a, const fm::Consts& k, const Draw& d,
-                                           int i, double out[6]) {
+                                           int i, double out[NP + 1]) {
   const double* mt = a.math_table;
   const double* weight = a.weight + (size_t)i * a.n_gauss;
-  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  double acc[NP + 1];
+#pragma unroll
+  for (int p = 0; p < NP + 1; ++p) acc[p] = 0.0;
+  const bool above = decorated(NP) ? a.percentile[i] > 0.5 : false;
   if (i < a.n_central) {
     const double* log_m = a.log_m + (size_t)i * a.n_gauss;
+    const double s_cen = above ? d.a_cen : -d.a_cen;
     for (int node = 0; node < a.n_gauss; ++node) {
-      double n, dn0, dn1;
-      central_node(mt, k, d, log_m[node], &n, &dn0, &dn1);
+      double n, dn0, dn1, x_abs, gauss;
+      central_node(mt, k, d, log_m[node], &n, &dn0, &dn1, &x_abs, &gauss);
       const double wn = weight[node];
+      if (decorated(NP)) {
+        const double rest = 1.0 - n;
+        const double least = fmin(n, rest);
+        const double factor = n <= rest ? 1.0 + s_cen : 1.0 - s_cen;
+        n = fma(s_cen, least, n);
+        dn0 *= factor;
+        dn1 *= factor;
+        const double tail = fm::half_erfc_from_gauss(x_abs, gauss);
+        acc[NP - 1] = fma(wn, x_abs >= fm::kErfcFrom ? tail : least, acc[NP - 1]);
+      }
       acc[0] = fma(wn, n, acc[0]);
       acc[1] = fma(wn, dn0, acc[1]);
       acc[2] = fma(wn, dn1, acc[2]);
     }
+    if (decorated(NP)) acc[NP - 1] *= above ? d.da_cen : -d.da_cen;
   } else {
     const double* m = a.m + (size_t)i * a.n_gauss;
     const double* log_m = a.log_m + (size_t)i * a.n_gauss;
@@ -109,14 +147,28 @@ __device__ __forceinline__ void bin_values(const GradArgs& a, const fm::Consts& 
 #pragma unroll
       for (int p = 0; p < 6; ++p) acc[p] = fma(wn, v[p], acc[p]);
     }
+    if (decorated(NP)) {
+      const double s_sat = above ? d.a_sat : -d.a_sat;
+      acc[NP] = (above ? d.da_sat : -d.da_sat) * acc[0];
+#pragma unroll
+      for (int p = 0; p < 6; ++p) acc[p] = fma(s_sat, acc[p], acc[p]);
+    }
   }
   const double n_h = a.n_h[i];
 #pragma unroll
-  for (int p = 0; p < 6; ++p) out[p] = n_h * acc[p];
+  for (int p = 0; p < NP + 1; ++p) out[p] = n_h * acc[p];
 }
 
+// The clip of a strength to [-1, 1] as the forward kernels apply it (kernels.hip.h:
+// clip_strength; NaN stays NaN) and its derivative, at the boundary the one facing inside.
+__device__ __forceinline__ void clip_strength_grad(double a, double* c, double* dc) {
+  *c = a > 1.0 ? 1.0 : (a < -1.0 ? -1.0 : a);
+  *dc = a != a ? a : (fabs(a) <= 1.0 ? 1.0 : 0.0);
+}
+
+template <int NP>
 __device__ __forceinline__ Draw load_draw(const GradArgs& a, const fm::Consts& k, int64_t draw) {
-  const double* theta = a.theta + clamp_draw(draw, a.n_draws) * kGradParams;
+  const double* theta = a.theta + clamp_draw(draw, a.n_draws) * NP;
   Draw d;
   d.log_m_min = theta[0];
   d.inv_sigma = 1.0 / theta[1];
@@ -124,18 +176,30 @@ __device__ __forceinline__ Draw load_draw(const GradArgs& a, const fm::Consts& k
   d.m0_ln10 = d.m0 * kLn10;
   d.inv_m1 = 1.0 / fm::exp10_fast(a.math_table, k, theta[3]);
   d.alpha = theta[4];
+  d.a_cen = d.da_cen = d.a_sat = d.da_sat = 0.0;
+  if (decorated(NP)) {
+    clip_strength_grad(theta[NP - 2], &d.a_cen, &d.da_cen);
+    clip_strength_grad(theta[NP - 1], &d.a_sat, &d.da_sat);
+  }
   return d;
 }
 
-// LDS row of (bin i, quantity p) in grad_auto_kernel (grad.h: grad_auto_rows)
+// LDS row of (bin i, quantity p) in grad_auto_kernel (grad.h: grad_auto_rows).  Decorated: a
+// central bin's fourth row is p = 6 (A_cen), a satellite bin's seventh p = 7 (A_sat).
+template <int NP>
 __device__ __forceinline__ int auto_row(int i, int p, int n_bins, int n_central, int zero_row) {
   if (i >= n_bins) return zero_row;
-  if (i < n_central) return p < 3 ? 3 * i + p : zero_row;
-  return 3 * n_central + 6 * (i - n_central) + p;
+  if (!decorated(NP)) {
+    if (i < n_central) return p < 3 ? 3 * i + p : zero_row;
+    return 3 * n_central + 6 * (i - n_central) + p;
+  }
+  if (i < n_central) return p < 3 ? 4 * i + p : (p == NP - 1 ? 4 * i + 3 : zero_row);
+  if (p == NP - 1) return zero_row;
+  return 4 * n_central + NP * (i - n_central) + (p == NP ? NP - 1 : p);
 }
 
 // chi2 = e^T P e and dchi2 / dtheta_k = 2 e^T P_sym dxi_k with P_sym = (P + P^T) / 2, from the
-// residuals e (p = 0) and the derivatives (p = 1 .. n_quantities - 1: five for a table, 5 + n_dim
+// residuals e (p = 0) and the derivatives (p = 1 .. n_quantities - 1: NP for a table, NP + n_dim
 // for an interpolator) at stash[(p n_r + r) 16 + draw]; threads 0 .. 16 n_quantities - 1 =
 // (p, draw).
 __device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* stash, int64_t draw0,
@@ -171,7 +235,8 @@ __device__ __forceinline__ void finish_chi2(const GradArgs& a, const double* sta
 // 1/2 sum_r dxi_k[r] (sum_s (P[r][s] + P[s][r]) dxi_l[s]) over the n = n_quantities - 1
 // differentiated quantities, from the rows p = 1 .. n of the stash that finish_chi2 reads (and
 // leaves as they are: no barrier between the two).  Items (pair k <= l, draw), n (n + 1) / 2 x 16
-// of them (240 for a table, up to 1456 for an interpolator of kGradMaxDim axes), walked by the
+// of them (240 for a table, up to 1456 for an interpolator of kGradMaxDim axes; 448 and 1920
+// where decorated), walked by the
 // workgroup; s ascending inside r ascending, one fma chain each, as in finish_chi2: a draw's
 // matrix depends on the draw alone.  Every pair is computed once and stored to both positions of
 // the full (n, n) matrix, which is therefore bit-symmetric.
@@ -210,6 +275,7 @@ __device__ __forceinline__ void finish_fisher(const GradArgs& a, const double* s
 // ---- the pieces of grad_auto_kernel (grad_interp_auto_kernel runs them per class and table) -----
 
 // Phase 1: thread = (bin i % 16, draw) writes w and dw of its bins, and the row of zeros.
+template <int NP>
 __device__ __forceinline__ void auto_node_loops(const GradArgs& a, const fm::Consts& k,
                                                 const Draw& d, double* w, int zero_row) {
   const int t = threadIdx.x;
@@ -217,60 +283,72 @@ __device__ __forceinline__ void auto_node_loops(const GradArgs& a, const fm::Con
   const int n_bins = a.n_bins, n_central = a.n_central;
   if (t < kGradDraws) w[zero_row * kGradDraws + t] = 0.0;
   for (int i = t / kGradDraws; i < n_bins; i += kGradThreads / kGradDraws) {
-    double out[6];
-    bin_values(a, k, d, i, out);
-    const int base = auto_row(i, 0, n_bins, n_central, zero_row);
-    const int count = i < n_central ? 3 : 6;
+    double out[NP + 1];
+    bin_values<NP>(a, k, d, i, out);
+    if (!decorated(NP)) {
+      const int base = auto_row<NP>(i, 0, n_bins, n_central, zero_row);
+      const int count = i < n_central ? 3 : 6;
 #pragma unroll
-    for (int p = 0; p < 6; ++p)
-      if (p < count) w[(base + p) * kGradDraws + col] = out[p];
+      for (int p = 0; p < 6; ++p)
+        if (p < count) w[(base + p) * kGradDraws + col] = out[p];
+    } else {
+      // (the rows a bin does not have are the row of zeros: not written)
+#pragma unroll
+      for (int p = 0; p < NP + 1; ++p) {
+        const int row = auto_row<NP>(i, p, n_bins, n_central, zero_row);
+        if (row != zero_row) w[row * kGradDraws + col] = out[p];
+      }
+    }
   }
 }
 
 // Total of quantity p over the bins in bin order: ngal (p = 0) or dngal / dtheta_(p - 1).
+template <int NP>
 __device__ __forceinline__ double auto_total(const double* w, int p, int col, int n_bins,
                                              int n_central, int zero_row) {
   double sum = 0.0;
   for (int i = 0; i < n_bins; ++i)
-    sum += w[auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col];
+    sum += w[auto_row<NP>(i, p, n_bins, n_central, zero_row) * kGradDraws + col];
   return sum;
 }
 
 // Phase 2 of one r bin, one wave: U_r = S_r W on the matrix pipe against a.matrix, then acc[0] =
 // w . U_r and acc[p] = dw_p . U_r, complete in every lane.  lane = (row group l / 16, draw
 // l % 16); D[row = l / 16 + 4 v][draw] in register v.
+template <int NP>
 __device__ __forceinline__ void auto_products(const GradArgs& a, const double* w, int r,
-                                              int zero_row, double acc[6]) {
+                                              int zero_row, double acc[NP + 1]) {
   const int lane = threadIdx.x % 64;
   const int group = lane / kGradDraws, col = lane % kGradDraws;
   const int n_bins = a.n_bins, n_central = a.n_central;
   const int tiles = a.row_tiles, steps = a.k_steps;
 #pragma unroll
-  for (int p = 0; p < 6; ++p) acc[p] = 0.0;
+  for (int p = 0; p < NP + 1; ++p) acc[p] = 0.0;
   for (int tile = 0; tile < tiles; ++tile) {
     const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
     const f64x4 u = dense_tile_product(a_lane, steps, w, group, col, [=](int j) {
-      return auto_row(j, 0, n_bins, n_central, zero_row);
+      return auto_row<NP>(j, 0, n_bins, n_central, zero_row);
     });
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       const int i = 16 * tile + group + 4 * v;
       const double uv = u[v];
 #pragma unroll
-      for (int p = 0; p < 6; ++p)
-        acc[p] = fma(w[auto_row(i, p, n_bins, n_central, zero_row) * kGradDraws + col], uv, acc[p]);
+      for (int p = 0; p < NP + 1; ++p)
+        acc[p] = fma(w[auto_row<NP>(i, p, n_bins, n_central, zero_row) * kGradDraws + col], uv,
+                     acc[p]);
     }
   }
 #pragma unroll
-  for (int p = 0; p < 6; ++p) acc[p] = sum_row_groups(acc[p]);
+  for (int p = 0; p < NP + 1; ++p) acc[p] = sum_row_groups(acc[p]);
 }
 
 // Phase 3, mode auto: xi = q / ngal^2 and dxi_k = dq_k / ngal^2 - 2 xi dngal_k / ngal with dq_k =
 // 2 dw_k . U, from the products and the totals (6, 16) of the draw's column.
-__device__ __forceinline__ double auto_xi(const double acc[6], double inv_ngal2) {
+__device__ __forceinline__ double auto_xi(const double* acc, double inv_ngal2) {
   return acc[0] * inv_ngal2;
 }
-__device__ __forceinline__ double auto_dxi(const double acc[6], int p, double xi,
+__device__ __forceinline__ double auto_dxi(const double* acc, int p, double xi,
                                            const double* total, int col, double inv_ngal,
                                            double inv_ngal2) {
   return 2.0 * acc[p] * inv_ngal2 - 2.0 * xi * total[p * kGradDraws + col] * inv_ngal;
@@ -279,50 +357,53 @@ __device__ __forceinline__ double auto_dxi(const double acc[6], int p, double xi
 // ---- the pieces of grad_cross_kernel ------------------------------------------------------------
 
 // w and dw of the bins slab0 .. slab0 + count - 1 into the slab (6, kGradCrossSlab, 16).
+template <int NP>
 __device__ __forceinline__ void cross_node_loops(const GradArgs& a, const fm::Consts& k,
                                                  const Draw& d, int slab0, int count, double* w) {
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   for (int li = t / kGradDraws; li < count; li += kGradThreads / kGradDraws) {
-    double out[6];
-    bin_values(a, k, d, slab0 + li, out);
+    double out[NP + 1];
+    bin_values<NP>(a, k, d, slab0 + li, out);
 #pragma unroll
-    for (int p = 0; p < 6; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
+    for (int p = 0; p < NP + 1; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
   }
 }
 
 }  // namespace grad
 
 // ---- mode auto ----------------------------------------------------------------------------------
+template <int NP>
 __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs a) {
+  constexpr int NQ = NP + 1;
   extern __shared__ double grad_lds[];
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
   const int n_bins = a.n_bins, n_central = a.n_central, n_r = a.n_r;
-  const int zero_row = grad_auto_rows(n_bins, n_central) - 1;
+  const int zero_row = grad_auto_rows(n_bins, n_central, NP) - 1;
   double* w = grad_lds;                                       // (rows, 16)
   double* total = w + (size_t)(zero_row + 1) * kGradDraws;    // (6, 16)
-  double* stash = total + 6 * kGradDraws;                     // (6, n_r, 16), likelihood only
+  double* stash = total + NQ * kGradDraws;                     // (6, n_r, 16), likelihood only
   const fm::Consts k = fm::make_consts();
 
   // phase 1: thread = (bin i % 16, draw)
   {
-    const grad::Draw d = grad::load_draw(a, k, draw0 + col);
-    grad::auto_node_loops(a, k, d, w, zero_row);
+    const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+    grad::auto_node_loops<NP>(a, k, d, w, zero_row);
   }
   __syncthreads();
   // totals over the bins in bin order: ngal and its derivatives
-  if (t < 6 * kGradDraws) {
+  if (t < NQ * kGradDraws) {
     const int p = t / kGradDraws;
-    const double sum = grad::auto_total(w, p, col, n_bins, n_central, zero_row);
+    const double sum = grad::auto_total<NP>(w, p, col, n_bins, n_central, zero_row);
     total[t] = sum;
     const int64_t draw = draw0 + col;
     if (draw < a.n_draws) {
       if (p == 0)
         a.ngal[draw] = sum;
       else
-        a.dngal[draw * kGradParams + (p - 1)] = sum;
+        a.dngal[draw * NP + (p - 1)] = sum;
     }
   }
   __syncthreads();
@@ -334,8 +415,8 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   const double inv_ngal = 1.0 / ngal;
   const double inv_ngal2 = 1.0 / (ngal * ngal);
   for (int r = wave; r < n_r; r += kGradWaves) {
-    double acc[6];
-    grad::auto_products(a, w, r, zero_row, acc);
+    double acc[NQ];
+    grad::auto_products<NP>(a, w, r, zero_row, acc);
     const double xi = grad::auto_xi(acc, inv_ngal2);
     const int64_t draw = draw0 + col;
     if (group == 0) {
@@ -346,11 +427,11 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
       }
     }
 #pragma unroll
-    for (int p = 1; p < 6; ++p) {
+    for (int p = 1; p < NQ; ++p) {
       const double dxi = grad::auto_dxi(acc, p, xi, total, col, inv_ngal, inv_ngal2);
       if (group == 0) {
         if (a.xi != nullptr) {
-          if (draw < a.n_draws) a.dxi[(draw * kGradParams + (p - 1)) * n_r + r] = dxi;
+          if (draw < a.n_draws) a.dxi[(draw * NP + (p - 1)) * n_r + r] = dxi;
         } else {
           stash[((size_t)p * n_r + r) * kGradDraws + col] = dxi;
         }
@@ -359,44 +440,46 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   }
   if (a.xi == nullptr) {
     __syncthreads();
-    grad::finish_chi2(a, stash, draw0, 6);
-    grad::finish_fisher(a, stash, draw0, 6);
+    grad::finish_chi2(a, stash, draw0, NQ);
+    grad::finish_fisher(a, stash, draw0, NQ);
   }
 }
 
 // ---- mode cross ---------------------------------------------------------------------------------
 // xi_r = T_r . w / ngal (tabcorr.py:646-649): the bins in slabs of kGradCrossSlab, any number of
 // them; thread = (r, quantity, draw) items for the products, which it keeps in LDS.
+template <int NP>
 __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs a) {
+  constexpr int NQ = NP + 1;
   extern __shared__ double grad_lds[];
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   const int64_t draw0 = (int64_t)blockIdx.x * kGradDraws;
   const int n_bins = a.n_bins, n_r = a.n_r;
   double* w = grad_lds;                                               // (6, slab, 16)
-  double* y = w + 6 * kGradCrossSlab * kGradDraws;                    // (6, n_r, 16)
-  double* total = y + (size_t)6 * n_r * kGradDraws;                   // (6, 16)
+  double* y = w + NQ * kGradCrossSlab * kGradDraws;                    // (6, n_r, 16)
+  double* total = y + (size_t)NQ * n_r * kGradDraws;                   // (6, 16)
   const fm::Consts k = fm::make_consts();
-  const grad::Draw d = grad::load_draw(a, k, draw0 + col);
-  const int n_items = 6 * n_r * kGradDraws;
+  const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+  const int n_items = NQ * n_r * kGradDraws;
   for (int item = t; item < n_items; item += kGradThreads) y[item] = 0.0;
   double my_total = 0.0;
   for (int slab0 = 0; slab0 < n_bins; slab0 += kGradCrossSlab) {
     const int count = min(kGradCrossSlab, n_bins - slab0);
     __syncthreads();
-    grad::cross_node_loops(a, k, d, slab0, count, w);
+    grad::cross_node_loops<NP>(a, k, d, slab0, count, w);
     __syncthreads();
-    if (t < 6 * kGradDraws) {
+    if (t < NQ * kGradDraws) {
       const int p = t / kGradDraws;
       for (int li = 0; li < count; ++li) my_total += w[(p * kGradCrossSlab + li) * kGradDraws + col];
     }
     for (int item = t; item < n_items; item += kGradThreads) {
-      const int r = item / (6 * kGradDraws), p = item / kGradDraws % 6;
+      const int r = item / (NQ * kGradDraws), p = item / kGradDraws % NQ;
       const size_t slot = ((size_t)p * n_r + r) * kGradDraws + col;
       y[slot] = grad::cross_slab_product(a.matrix, n_r, r, slab0, count, w, p, col, y[slot]);
     }
   }
-  if (t < 6 * kGradDraws) {
+  if (t < NQ * kGradDraws) {
     total[t] = my_total;
     const int p = t / kGradDraws;
     const int64_t draw = draw0 + col;
@@ -404,7 +487,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
       if (p == 0)
         a.ngal[draw] = my_total;
       else
-        a.dngal[draw * kGradParams + (p - 1)] = my_total;
+        a.dngal[draw * NP + (p - 1)] = my_total;
     }
   }
   __syncthreads();
@@ -413,7 +496,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   const double inv_ngal = 1.0 / total[col];
   const int64_t draw = draw0 + col;
   for (int item = t; item < n_items; item += kGradThreads) {
-    const int r = item / (6 * kGradDraws), p = item / kGradDraws % 6;
+    const int r = item / (NQ * kGradDraws), p = item / kGradDraws % NQ;
     if (p == 0) continue;
     const size_t slot = ((size_t)p * n_r + r) * kGradDraws + col;
     const double xi = y[(size_t)r * kGradDraws + col] * inv_ngal;
@@ -421,7 +504,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
     if (a.xi == nullptr)
       y[slot] = dxi;
     else if (draw < a.n_draws)
-      a.dxi[(draw * kGradParams + (p - 1)) * n_r + r] = dxi;
+      a.dxi[(draw * NP + (p - 1)) * n_r + r] = dxi;
   }
   __syncthreads();
   for (int item = t; item < n_r * kGradDraws; item += kGradThreads) {
@@ -434,8 +517,8 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   }
   if (a.xi == nullptr) {
     __syncthreads();
-    grad::finish_chi2(a, y, draw0, 6);
-    grad::finish_fisher(a, y, draw0, 6);
+    grad::finish_chi2(a, y, draw0, NQ);
+    grad::finish_fisher(a, y, draw0, NQ);
   }
 }
 

@@ -672,9 +672,10 @@ int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_
 // Gradients (grad_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels do
 // not serve (TC_ERR_UNSUPPORTED with a message), the handle's copy of the matrix, the launch.
 // xi / dxi NULL: chi2 / dchi2 from chi2_data (data, then the precision matrix, on the device) and,
-// where `fisher` is given, the Fisher matrix (n_draws, 5, 5) of the likelihood.
+// where `fisher` is given, the Fisher matrix (n_draws, 5, 5) of the likelihood.  n_params:
+// tc::kGradParams, or tc::kGradParamsAssembias for the decorated model (7 wherever 5 stands).
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
-                    int n_gauss, unsigned flags, bool chi2);
+                    int n_gauss, unsigned flags, bool chi2, int n_params = tc::kGradParams);
 int build_grad_table(tc_table* t);
 // The lane a derivative call asks for: lane 0, pinned (the host-array entry points stage their
 // copies on it), or the next lane of the handle's rotation (the device-pointer entry points).
@@ -689,7 +690,7 @@ int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
              const double* chi2_data, double* chi2, double* dchi2, double* fisher,
-             hipStream_t stream);
+             hipStream_t stream, int n_params = tc::kGradParams);
 // Occupation VJP (vjp_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels
 // do not serve (TC_ERR_UNSUPPORTED with a message), then the launch against the gradient table.
 // g_xi NULL: the likelihood form -- chi2 and dchi2 / docc from chi2_data (on the device).
@@ -778,7 +779,7 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
                 const double* precision, double* chi2, hipStream_t stream);
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
-// inst_grad.hip, inst_vjp.hip) ----
+// inst_grad.hip, inst_grad_assembias.hip, inst_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -804,6 +805,11 @@ int launch_grad_instance(int mode, int device, dim3 grid, int lds, hipStream_t s
                          hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
 int launch_grad_interp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                                 hipEvent_t k0, hipEvent_t k1, const tc::GradInterpArgs& ga);
+int launch_grad_assembias_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
+                                   hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
+int launch_grad_interp_assembias_instance(int mode, int device, dim3 grid, int lds,
+                                          hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
+                                          const tc::GradInterpArgs& ga);
 int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                         hipEvent_t k0, hipEvent_t k1, const tc::VjpArgs& va);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);

@@ -1049,23 +1049,25 @@ int tc_interp_chi2_zheng07_batch_async(tc_interp* it, const double* theta, int n
 
 namespace {
 
-size_t interp_grad_lds(const tc_interp* it, bool chi2) {
+size_t interp_grad_lds(const tc_interp* it, bool chi2, int n_params) {
   const tc_table* t0 = it->tables[0];
   return t0->mode == TC_MODE_AUTO
              ? tc::grad_interp_auto_lds_bytes(t0->n_bins, t0->plan.n_central, t0->n_r, it->n_dim,
-                                              chi2)
-             : tc::grad_interp_cross_lds_bytes(t0->n_r, it->n_dim, chi2);
+                                              chi2, n_params)
+             : tc::grad_interp_cross_lds_bytes(t0->n_r, it->n_dim, chi2, n_params);
 }
 
 // What the table entry points refuse (check_grad_args on the first table: flags, float32, the
 // shape of theta) and a grid that does not fit the LDS of a workgroup.
 int check_interp_grad_args(const tc_interp* it, const void* theta, int n_theta, int64_t n_draws,
-                           int n_gauss, unsigned flags, bool chi2) {
+                           int n_gauss, unsigned flags, bool chi2,
+                           int n_params = tc::kGradParams) {
   TC_CHECK(it != nullptr, "interp handle is NULL");
   const tc_table* t0 = it->tables[0];
-  const int status = check_grad_args(t0, theta, n_theta, n_draws, n_gauss, flags, chi2);
+  const int status =
+      check_grad_args(t0, theta, n_theta, n_draws, n_gauss, flags, chi2, n_params);
   if (status != TC_OK) return status;
-  const size_t lds = interp_grad_lds(it, chi2);
+  const size_t lds = interp_grad_lds(it, chi2, n_params);
   if (lds > (size_t)kMaxLdsBytes)
     return fail(TC_ERR_UNSUPPORTED,
                 "gradients: a grid of %d dimensions over tables of %d bins and %d correlation "
@@ -1108,11 +1110,13 @@ int build_grad_walk(tc_interp* it) {
 }
 
 // One launch per slab of draws on the call's lane.  xi / dxi NULL: chi2 / dchi2 from chi2_data
-// and, where `fisher` is given, the Fisher matrix (n_draws, 5 + n_dim, 5 + n_dim).
+// and, where `fisher` is given, the Fisher matrix (n_draws, 5 + n_dim, 5 + n_dim).  n_params:
+// tc::kGradParams, or tc::kGradParamsAssembias for the decorated model (7 wherever 5 stands).
 int interp_grad_device(tc_interp* it, GradLane request, const double* theta_device,
                        const double* x_device, int64_t n_draws, int n_gauss, unsigned flags,
                        double* ngal, double* xi, double* dngal, double* dxi,
-                       const double* chi2_data, double* chi2, double* dchi2, double* fisher) {
+                       const double* chi2_data, double* chi2, double* dchi2, double* fisher,
+                       int n_params = tc::kGradParams) {
   TC_HIP(hipSetDevice(it->device));
   tc_table* t0 = it->tables[0];
   int status = TC_OK;
@@ -1127,7 +1131,8 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
                 : (int)(it->device_calls++ % it->n_lanes);
   tc_interp::Lane& L = it->lanes[it->cur];
   const bool with_chi2 = xi == nullptr;
-  const int n_r = t0->n_r, n_dim = it->n_dim, n_cols = tc::kGradParams + n_dim;
+  const bool decorated = n_params == tc::kGradParamsAssembias;
+  const int n_r = t0->n_r, n_dim = it->n_dim, n_cols = n_params + n_dim;
   tc::GradInterpArgs ga{};
   fill_grad_shape(t0, n_gauss, flags, &ga.table);
   ga.table.chi2_data = chi2_data;
@@ -1147,10 +1152,11 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
   ga.class_m = (const double* const*)pointers->m;
   ga.class_weight = (const double* const*)pointers->weight;
   ga.class_n_h = (const double* const*)pointers->n_h;
-  const int lds = (int)interp_grad_lds(it, with_chi2);
+  ga.class_percentile = decorated ? (const double* const*)pointers->percentile : nullptr;
+  const int lds = (int)interp_grad_lds(it, with_chi2, n_params);
   return for_each_slab(n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
     Range range("interpolator gradients (one launch)");
-    ga.table.theta = theta_device + begin * tc::kGradParams;
+    ga.table.theta = theta_device + begin * n_params;
     ga.x = x_device + begin * n_dim;
     ga.table.n_draws = n;
     ga.table.ngal = ngal + begin;
@@ -1162,7 +1168,8 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
     ga.table.fisher = fisher ? fisher + begin * n_cols * n_cols : nullptr;
     // (timed through the first table's timer)
     return launch_grad_batch(t0, n, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-      return launch_grad_interp_instance(t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
+      return (decorated ? launch_grad_interp_assembias_instance : launch_grad_interp_instance)(
+          t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
     });
   });
 }
@@ -1172,11 +1179,12 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
 // one array more comes down, from behind the other two.
 int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_t n_draws,
                      int n_gauss, unsigned flags, const double* chi2_data, double* ngal,
-                     double* value, double* dngal, double* dvalue, double* fisher = nullptr) {
+                     double* value, double* dngal, double* dvalue, double* fisher = nullptr,
+                     int n_params = tc::kGradParams) {
   TC_HIP(hipSetDevice(it->device));
   const bool chi2 = chi2_data != nullptr;
   const size_t n = (size_t)n_draws, n_r = (size_t)it->tables[0]->n_r;
-  const size_t np = tc::kGradParams, n_cols = np + it->n_dim;
+  const size_t np = (size_t)n_params, n_cols = np + it->n_dim;
   const size_t value_count = chi2 ? n : n * n_r;
   int status = it->theta.reserve(n * np * 8, it->stream);
   if (status == TC_OK) status = it->x.reserve(n * it->n_dim * 8, it->stream);
@@ -1196,7 +1204,7 @@ int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_
                               (const double*)it->x.ptr, n_draws, n_gauss, flags, d_ngal,
                               chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
                               chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr,
-                              d_fisher);
+                              d_fisher, n_params);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * n_cols * 8, hipMemcpyDeviceToHost, it->stream));
@@ -1246,8 +1254,10 @@ int interp_chi2_grad_device_entry(tc_interp* it, const double* theta_device, int
                                   const double* x_device, int64_t n_draws, int n_gauss,
                                   unsigned flags, const double* data, const double* precision,
                                   double* ngal_device, double* chi2_device, double* dngal_device,
-                                  double* dchi2_device, bool want_fisher, double* fisher_device) {
-  int status = check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, true);
+                                  double* dchi2_device, bool want_fisher, double* fisher_device,
+                                  int n_params = tc::kGradParams) {
+  int status =
+      check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, true, n_params);
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(x_device && data && precision && ngal_device && chi2_device && dngal_device &&
@@ -1259,14 +1269,15 @@ int interp_chi2_grad_device_entry(tc_interp* it, const double* theta_device, int
   return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
                             flags, ngal_device, nullptr, dngal_device, nullptr,
                             (const double*)it->chi2_data.ptr, chi2_device, dchi2_device,
-                            fisher_device);
+                            fisher_device, n_params);
 }
 
 int interp_chi2_grad_host_entry(tc_interp* it, const double* theta, int n_theta, const double* x,
                                 int64_t n_draws, int n_gauss, unsigned flags, const double* data,
                                 const double* precision, double* ngal, double* chi2,
-                                double* dngal, double* dchi2, bool want_fisher, double* fisher) {
-  int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, true);
+                                double* dngal, double* dchi2, bool want_fisher, double* fisher,
+                                int n_params = tc::kGradParams) {
+  int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, true, n_params);
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(x && data && precision && ngal && chi2 && dngal && dchi2 && (!want_fisher || fisher),
@@ -1275,7 +1286,8 @@ int interp_chi2_grad_host_entry(tc_interp* it, const double* theta, int n_theta,
   status = upload_chi2_data(it, data, precision);
   if (status != TC_OK) return status;
   return interp_grad_host(it, theta, x, n_draws, n_gauss, flags,
-                          (const double*)it->chi2_data.ptr, ngal, chi2, dngal, dchi2, fisher);
+                          (const double*)it->chi2_data.ptr, ngal, chi2, dngal, dchi2, fisher,
+                          n_params);
 }
 
 }  // namespace
@@ -1319,6 +1331,62 @@ int tc_interp_chi2_fisher_zheng07_batch(tc_interp* it, const double* theta, int 
                                         double* dngal, double* dchi2, double* fisher) {
   return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
                                      precision, ngal, chi2, dngal, dchi2, true, fisher);
+}
+
+// ---- gradients of the model decorated with assembly bias: seven columns of theta, the
+// strengths last, then the n_dim extra parameters; `fisher` may be NULL ----
+
+int tc_interp_predict_grad_assembias_batch_device(tc_interp* it, const double* theta_device,
+                                                  int n_theta, const double* x_device,
+                                                  int64_t n_draws, int n_gauss, unsigned flags,
+                                                  double* ngal_device, double* xi_device,
+                                                  double* dngal_device, double* dxi_device) {
+  const int np = tc::kGradParamsAssembias;
+  const int status =
+      check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, false, np);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x_device && ngal_device && xi_device && dngal_device && dxi_device, "NULL pointer");
+  return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
+                            flags, ngal_device, xi_device, dngal_device, dxi_device, nullptr,
+                            nullptr, nullptr, nullptr, np);
+}
+
+int tc_interp_predict_grad_assembias_batch(tc_interp* it, const double* theta, int n_theta,
+                                           const double* x, int64_t n_draws, int n_gauss,
+                                           unsigned flags, double* ngal, double* xi,
+                                           double* dngal, double* dxi) {
+  const int np = tc::kGradParamsAssembias;
+  const int status =
+      check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, false, np);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(x && ngal && xi && dngal && dxi, "NULL pointer");
+  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi,
+                          nullptr, np);
+}
+
+int tc_interp_chi2_grad_assembias_batch_device(tc_interp* it, const double* theta_device,
+                                               int n_theta, const double* x_device,
+                                               int64_t n_draws, int n_gauss, unsigned flags,
+                                               const double* data, const double* precision,
+                                               double* ngal_device, double* chi2_device,
+                                               double* dngal_device, double* dchi2_device,
+                                               double* fisher_device) {
+  return interp_chi2_grad_device_entry(it, theta_device, n_theta, x_device, n_draws, n_gauss,
+                                       flags, data, precision, ngal_device, chi2_device,
+                                       dngal_device, dchi2_device, false, fisher_device,
+                                       tc::kGradParamsAssembias);
+}
+
+int tc_interp_chi2_grad_assembias_batch(tc_interp* it, const double* theta, int n_theta,
+                                        const double* x, int64_t n_draws, int n_gauss,
+                                        unsigned flags, const double* data,
+                                        const double* precision, double* ngal, double* chi2,
+                                        double* dngal, double* dchi2, double* fisher) {
+  return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
+                                     precision, ngal, chi2, dngal, dchi2, false, fisher,
+                                     tc::kGradParamsAssembias);
 }
 
 int tc_interp_wait(tc_interp* it, int64_t ticket) {

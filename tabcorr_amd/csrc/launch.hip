@@ -1119,10 +1119,10 @@ static int check_grad_fit(const tc_table* t, const char* what, size_t lds) {
   return TC_OK;
 }
 
-static size_t grad_lds(const tc_table* t, bool chi2) {
+static size_t grad_lds(const tc_table* t, bool chi2, int n_params) {
   return t->mode == TC_MODE_AUTO
-             ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, chi2)
-             : tc::grad_cross_lds_bytes(t->n_r);
+             ? tc::grad_auto_lds_bytes(t->n_bins, t->plan.n_central, t->n_r, chi2, n_params)
+             : tc::grad_cross_lds_bytes(t->n_r, n_params);
 }
 
 static size_t vjp_lds(const tc_table* t) {
@@ -1131,14 +1131,19 @@ static size_t vjp_lds(const tc_table* t) {
 }
 
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
-                    int n_gauss, unsigned flags, bool chi2) {
+                    int n_gauss, unsigned flags, bool chi2, int n_params) {
   TC_CHECK(t != nullptr, "table handle is NULL");
+  const bool decorated = n_params == tc::kGradParamsAssembias;
   const unsigned unserved = flags & ~(unsigned)TC_FLAG_MODULATE_WITH_CENOCC;
   if (unserved & TC_FLAG_SEPARATE_GAL_TYPE)
     return fail(TC_ERR_UNSUPPORTED, "gradients are implemented for the total prediction only "
                                     "(not separate_gal_type)");
   if (unserved & TC_FLAG_ASSEMBIAS)
-    return fail(TC_ERR_UNSUPPORTED, "gradients are not implemented for assembly bias");
+    return fail(TC_ERR_UNSUPPORTED,
+                decorated ? "the assembly-bias gradient entry points are decorated as they are: "
+                            "flags may hold TC_FLAG_MODULATE_WITH_CENOCC only"
+                          : "gradients are not implemented for assembly bias by this entry "
+                            "point (see the *_grad_assembias_* ones)");
   if (unserved & TC_FLAG_LEAUTHAUD11)
     return fail(TC_ERR_UNSUPPORTED, "gradients are implemented for the Zheng07 family only");
   if (unserved != 0) return fail(TC_ERR_UNSUPPORTED, "gradients: unknown flags 0x%x", unserved);
@@ -1147,9 +1152,8 @@ int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n
   TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
   TC_CHECK(n_draws == 0 || theta != nullptr, "theta is NULL");
   TC_CHECK(n_gauss >= 1 && n_gauss <= 4096, "n_gauss_prim must be in [1, 4096]");
-  TC_CHECK(n_theta == tc::kGradParams, "theta must have %d columns, got %d", tc::kGradParams,
-           n_theta);
-  return check_grad_fit(t, "gradients", grad_lds(t, chi2));
+  TC_CHECK(n_theta == n_params, "theta must have %d columns, got %d", n_params, n_theta);
+  return check_grad_fit(t, "gradients", grad_lds(t, chi2, n_params));
 }
 
 int build_grad_table(tc_table* t) {
@@ -1223,8 +1227,9 @@ int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
 int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
              unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
              const double* chi2_data, double* chi2, double* dchi2, double* fisher,
-             hipStream_t stream) {
+             hipStream_t stream, int n_params) {
   Range range("gradients (one launch)");
+  const bool decorated = n_params == tc::kGradParamsAssembias;
   Quadrature* q = nullptr;
   int status = get_quadrature(t, n_gauss, &q);
   if (status == TC_OK) status = build_grad_table(t);
@@ -1246,9 +1251,11 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
   ga.chi2 = chi2;
   ga.dchi2 = dchi2;
   ga.fisher = fisher;
-  const int lds = (int)grad_lds(t, xi == nullptr);
+  ga.percentile = decorated ? (const double*)t->d_percentile : nullptr;
+  const int lds = (int)grad_lds(t, xi == nullptr, n_params);
   return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-    return launch_grad_instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
+    return (decorated ? launch_grad_assembias_instance : launch_grad_instance)(
+        t->mode, t->device, grid, lds, stream, k0, k1, ga);
   });
 }
 

@@ -485,7 +485,7 @@ int tc_gauss_legendre(int n, double* x, double* w) {
 }
 
 int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y) {
-  TC_CHECK(kind >= 0 && kind <= 6 && n >= 0 && x && y, "invalid arguments");
+  TC_CHECK(kind >= 0 && kind <= 7 && n >= 0 && x && y, "invalid arguments");
   static std::vector<double> table;
   if (table.empty()) {
     table.resize(tc::fm::kTableDoubles);
@@ -502,6 +502,12 @@ int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y) {
       double gauss;
       const double value = tc::fm::erf_gauss_fast(table.data(), k, x[i], &gauss);
       y[i] = kind == 4 ? value : gauss;
+    }
+    if (kind == 7) {
+      double gauss;
+      (void)tc::fm::erf_gauss_fast(table.data(), k, x[i], &gauss);
+      if (std::fabs(x[i]) >= 6.0) gauss = 1.1283791670955125739 * std::exp(-x[i] * x[i]);
+      y[i] = tc::fm::half_erfc_from_gauss(std::fabs(x[i]), gauss);
     }
   }
   return TC_OK;
@@ -524,6 +530,21 @@ int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* den
           else
             TC_CHECK(value == 0.0, "padding of the operand layout is not zero");
         }
+  return TC_OK;
+}
+
+int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n_r, int n_dim,
+                      int chi2, int64_t* bytes) {
+  TC_CHECK(kernel >= 0 && kernel <= 3 && bytes, "invalid arguments");
+  TC_CHECK(n_params == tc::kGradParams || n_params == tc::kGradParamsAssembias,
+           "n_params must be %d or %d", tc::kGradParams, tc::kGradParamsAssembias);
+  TC_CHECK(n_bins >= n_central && n_central >= 0 && n_r >= 0 && n_dim >= 0, "invalid sizes");
+  const size_t sizes[4] = {
+      tc::grad_auto_lds_bytes(n_bins, n_central, n_r, chi2 != 0, n_params),
+      tc::grad_cross_lds_bytes(n_r, n_params),
+      tc::grad_interp_auto_lds_bytes(n_bins, n_central, n_r, n_dim, chi2 != 0, n_params),
+      tc::grad_interp_cross_lds_bytes(n_r, n_dim, chi2 != 0, n_params)};
+  *bytes = (int64_t)sizes[kernel];
   return TC_OK;
 }
 

@@ -1036,18 +1036,18 @@ int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
   return TC_OK;
 }
 
+// (n_params: tc::kGradParams, or tc::kGradParamsAssembias for the decorated model)
 int grad_device(tc_table* t, GradLane request, const double* theta_device, int64_t n_draws,
                 int n_gauss, unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-                const double* chi2_data, double* chi2, double* dchi2, double* fisher) {
-  const int64_t n_r = t->n_r;
-  const int64_t np2 = tc::kGradParams * tc::kGradParams;
+                const double* chi2_data, double* chi2, double* dchi2, double* fisher,
+                int n_params = tc::kGradParams) {
+  const int64_t n_r = t->n_r, np = n_params;
   return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
-    return run_grad(t, theta_device + begin * tc::kGradParams, n, n_gauss, flags, ngal + begin,
-                    xi ? xi + begin * n_r : nullptr, dngal + begin * tc::kGradParams,
-                    dxi ? dxi + begin * tc::kGradParams * n_r : nullptr, chi2_data,
-                    chi2 ? chi2 + begin : nullptr,
-                    dchi2 ? dchi2 + begin * tc::kGradParams : nullptr,
-                    fisher ? fisher + begin * np2 : nullptr, stream);
+    return run_grad(t, theta_device + begin * np, n, n_gauss, flags, ngal + begin,
+                    xi ? xi + begin * n_r : nullptr, dngal + begin * np,
+                    dxi ? dxi + begin * np * n_r : nullptr, chi2_data,
+                    chi2 ? chi2 + begin : nullptr, dchi2 ? dchi2 + begin * np : nullptr,
+                    fisher ? fisher + begin * np * np : nullptr, stream, n_params);
   });
 }
 
@@ -1056,10 +1056,10 @@ int grad_device(tc_table* t, GradLane request, const double* theta_device, int64
 // only, or NULL): one array more comes down, from behind the other two.
 int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, unsigned flags,
               const double* chi2_data, double* ngal, double* value, double* dngal,
-              double* dvalue, double* fisher = nullptr) {
+              double* dvalue, double* fisher = nullptr, int n_params = tc::kGradParams) {
   TC_HIP(hipSetDevice(t->device));
   const bool chi2 = chi2_data != nullptr;
-  const size_t n = (size_t)n_draws, n_r = (size_t)t->n_r, np = tc::kGradParams;
+  const size_t n = (size_t)n_draws, n_r = (size_t)t->n_r, np = (size_t)n_params;
   const size_t value_count = chi2 ? n : n * n_r;
   int status = t->theta.reserve(n * np * 8, t->stream);
   if (status == TC_OK) status = t->out_ngal.reserve(n * (1 + np) * 8, t->stream);
@@ -1075,7 +1075,8 @@ int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, un
   double* d_fisher = fisher ? d_dvalue + value_count * np : nullptr;
   status = grad_device(t, GradLane::kPinned, (const double*)t->theta.ptr, n_draws, n_gauss, flags,
                        d_ngal, chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                       chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr, d_fisher);
+                       chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr, d_fisher,
+                       n_params);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
   TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * np * 8, hipMemcpyDeviceToHost, t->stream));
@@ -1120,8 +1121,9 @@ int chi2_grad_device_entry(tc_table* t, const double* theta_device, int n_theta,
                            int n_gauss, unsigned flags, const double* data,
                            const double* precision, double* ngal_device, double* chi2_device,
                            double* dngal_device, double* dchi2_device, bool want_fisher,
-                           double* fisher_device) {
-  int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, true);
+                           double* fisher_device, int n_params = tc::kGradParams) {
+  int status =
+      check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, true, n_params);
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(data && precision && ngal_device && chi2_device && dngal_device && dchi2_device &&
@@ -1132,14 +1134,14 @@ int chi2_grad_device_entry(tc_table* t, const double* theta_device, int n_theta,
   if (status != TC_OK) return status;
   return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
                      nullptr, dngal_device, nullptr, (const double*)t->chi2_data.ptr, chi2_device,
-                     dchi2_device, fisher_device);
+                     dchi2_device, fisher_device, n_params);
 }
 
 int chi2_grad_host_entry(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
                          int n_gauss, unsigned flags, const double* data, const double* precision,
                          double* ngal, double* chi2, double* dngal, double* dchi2,
-                         bool want_fisher, double* fisher) {
-  int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, true);
+                         bool want_fisher, double* fisher, int n_params = tc::kGradParams) {
+  int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, true, n_params);
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(data && precision && ngal && chi2 && dngal && dchi2 && (!want_fisher || fisher),
@@ -1148,7 +1150,7 @@ int chi2_grad_host_entry(tc_table* t, const double* theta, int n_theta, int64_t 
   status = upload_chi2_data(t, data, precision);
   if (status != TC_OK) return status;
   return grad_host(t, theta, n_draws, n_gauss, flags, (const double*)t->chi2_data.ptr, ngal,
-                   chi2, dngal, dchi2, fisher);
+                   chi2, dngal, dchi2, fisher, n_params);
 }
 
 }  // namespace
@@ -1188,6 +1190,52 @@ int tc_chi2_fisher_zheng07_batch(tc_table* t, const double* theta, int n_theta, 
                                  double* dngal, double* dchi2, double* fisher) {
   return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
                               chi2, dngal, dchi2, true, fisher);
+}
+
+// ---- gradients of the model decorated with assembly bias: seven columns, the strengths last;
+// `fisher` may be NULL ----
+
+int tc_predict_grad_assembias_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                           int64_t n_draws, int n_gauss, unsigned flags,
+                                           double* ngal_device, double* xi_device,
+                                           double* dngal_device, double* dxi_device) {
+  const int np = tc::kGradParamsAssembias;
+  const int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, false, np);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
+  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
+                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr, np);
+}
+
+int tc_predict_grad_assembias_batch(tc_table* t, const double* theta, int n_theta,
+                                    int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
+                                    double* xi, double* dngal, double* dxi) {
+  const int np = tc::kGradParamsAssembias;
+  const int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, false, np);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
+  return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi, nullptr, np);
+}
+
+int tc_chi2_grad_assembias_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                        int64_t n_draws, int n_gauss, unsigned flags,
+                                        const double* data, const double* precision,
+                                        double* ngal_device, double* chi2_device,
+                                        double* dngal_device, double* dchi2_device,
+                                        double* fisher_device) {
+  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
+                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
+                                false, fisher_device, tc::kGradParamsAssembias);
+}
+
+int tc_chi2_grad_assembias_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                                 int n_gauss, unsigned flags, const double* data,
+                                 const double* precision, double* ngal, double* chi2,
+                                 double* dngal, double* dchi2, double* fisher) {
+  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
+                              chi2, dngal, dchi2, false, fisher, tc::kGradParamsAssembias);
 }
 
 // ---- occupation VJP (launch.hip: run_vjp) -------------------------------------------------

@@ -25,7 +25,7 @@ from .galtable import GalTypeTable
 from .models import device_spec
 from .models import ZHENG07_KEYS
 from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _chi2_operands, _flags,
-                      _grad_theta, _unbatch)
+                      _grad_keys, _grad_spec, _grad_theta, _unbatch)
 
 OUT_OF_RANGE = ('The x-coordinates are outside of the interpolation ' +
                 'range and extrapolation is turned off.')
@@ -443,10 +443,11 @@ class Interpolator:
 
     # -- analytic gradients ----------------------------------------------------------
 
-    def _grad_inputs(self, theta, x, extrapolate):
-        """``theta (n, 5)`` and ``x (n, D)`` of the gradient calls, checked
+    def _grad_inputs(self, theta, x, extrapolate, assembias=False):
+        """``theta (n, 5)`` -- ``(n, 7)`` for the model decorated with
+        assembly bias -- and ``x (n, D)`` of the gradient calls, checked
         before any device is touched."""
-        theta = _grad_theta(theta)
+        theta = _grad_theta(theta, assembias)
         x = _lib.contiguous(np.atleast_2d(x))
         if x.shape != (len(theta), len(self.keys)):
             raise ValueError('x must have shape (n_draws, {}).'.format(
@@ -455,7 +456,7 @@ class Interpolator:
         return theta, x
 
     def predict_batch_grad(self, theta, x, n_gauss_prim=10, extrapolate=False,
-                           modulate_with_cenocc=False):
+                           modulate_with_cenocc=False, assembias=False):
         """`predict_batch` together with the exact derivatives of its results
         with respect to the five Zheng07 parameters and the ``D`` extra
         parameters (columns: `ZHENG07_KEYS`, then ``self.keys``), in one
@@ -471,6 +472,11 @@ class Interpolator:
         ``x`` outside the grid (``extrapolate=True``) gets the derivative of
         the outermost polynomial.
 
+        ``assembias=True``: the model decorated with assembly bias, as
+        `TabCorr.predict_batch_grad` has it: ``theta`` and the derivatives
+        carry the 7 columns of `ZHENG07_ASSEMBIAS_KEYS` (7 wherever 5 stands
+        below), then ``self.keys``.
+
         Returns
         -------
         ngal : ``(n_draws, )``
@@ -481,16 +487,19 @@ class Interpolator:
         Raises ``NotImplementedError`` for what the kernel does not serve
         (float32 tables, grids whose rows do not fit the LDS of a workgroup).
         """
-        theta, x = self._grad_inputs(theta, x, extrapolate)
+        theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
         device = self.to_device()
         n_draws, n_r = len(theta), device.tables[0].n_r
-        n_cols = len(ZHENG07_KEYS) + len(self.keys)
+        n_cols = theta.shape[1] + len(self.keys)
         ngal = np.empty(n_draws)
         xi = np.empty((n_draws, n_r))
         dngal = np.empty((n_draws, n_cols))
         dxi = np.empty((n_draws, n_cols, n_r))
+        entry = (device.lib.tc_interp_predict_grad_assembias_batch
+                 if assembias
+                 else device.lib.tc_interp_predict_grad_zheng07_batch)
         with device.lock:
-            _lib.check(device.lib.tc_interp_predict_grad_zheng07_batch(
+            _lib.check(entry(
                 device.handle, _lib.as_double_p(theta), theta.shape[1],
                 _lib.as_double_p(x), n_draws, n_gauss_prim,
                 _flags(False, modulate_with_cenocc), _lib.as_double_p(ngal),
@@ -501,17 +510,23 @@ class Interpolator:
                 dxi.reshape((n_draws, n_cols) + shape))
 
     def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
-                        extrapolate=False, modulate_with_cenocc=False):
+                        extrapolate=False, modulate_with_cenocc=False,
+                        assembias=False):
         """`chi2_batch` with its gradient with respect to ``(theta, x)``:
         ``dchi2[:, k] = 2 (xi - data)^T P_sym dxi_k`` with ``P_sym =
         (precision + precision^T) / 2``, finished on the device in the launch
-        that computes ``xi``.
+        that computes ``xi``.  ``assembias=True``: ``7 + D`` columns, as in
+        `predict_batch_grad`.
 
         Returns
         -------
         ngal, chi2 : ``(n_draws, )``
         dngal, dchi2 : ``(n_draws, 5 + D)``
         """
+        if assembias:
+            return self._chi2_grad_assembias(
+                theta, x, data, precision, n_gauss_prim, extrapolate,
+                modulate_with_cenocc, False)[:4]
         theta, x = self._grad_inputs(theta, x, extrapolate)
         data, precision = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
@@ -531,11 +546,38 @@ class Interpolator:
                 _lib.as_double_p(dchi2)))
         return ngal, chi2, dngal, dchi2
 
+    def _chi2_grad_assembias(self, theta, x, data, precision, n_gauss_prim,
+                             extrapolate, modulate_with_cenocc, want_fisher):
+        """The likelihood gradient of the decorated model, with or without
+        its Fisher matrix: one entry point serves both."""
+        theta, x = self._grad_inputs(theta, x, extrapolate, True)
+        data, precision = _chi2_operands(
+            data, precision, len(self.tabcorr_list[0].tpcf_matrix))
+        device = self.to_device()
+        n_draws = len(theta)
+        n_cols = theta.shape[1] + len(self.keys)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal = np.empty((n_draws, n_cols))
+        dchi2 = np.empty((n_draws, n_cols))
+        fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
+        with device.lock:
+            _lib.check(device.lib.tc_interp_chi2_grad_assembias_batch(
+                device.handle, _lib.as_double_p(theta), theta.shape[1],
+                _lib.as_double_p(x), n_draws, n_gauss_prim,
+                _flags(False, modulate_with_cenocc), _lib.as_double_p(data),
+                _lib.as_double_p(precision), _lib.as_double_p(ngal),
+                _lib.as_double_p(chi2), _lib.as_double_p(dngal),
+                _lib.as_double_p(dchi2),
+                _lib.as_double_p(fisher) if want_fisher else None))
+        return ngal, chi2, dngal, dchi2, fisher
+
     def predict_grad(self, model, n_gauss_prim=10, extrapolate=False,
-                     check_consistency=True):
+                     check_consistency=True, assembias=False):
         """Un-batched `predict_batch_grad` for a model object: a plain
         `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model)
-        whose ``param_dict`` holds the extra parameters.
+        whose ``param_dict`` holds the extra parameters; with
+        ``assembias=True`` a decorated one, the dicts then keyed by
+        ``ZHENG07_ASSEMBIAS_KEYS + tuple(self.keys)``.
 
         Returns
         -------
@@ -548,16 +590,15 @@ class Interpolator:
         if check_consistency:
             for halotab in self.tabcorr_list:
                 halotab._check_consistency_cached(model)
-        spec = device_spec(model)
-        if spec is None or spec.family != 'zheng07' or spec.assembias:
-            raise NotImplementedError(
-                'predict_grad needs a plain Zheng07 model (no assembly bias, '
-                'no other family).')
+        spec = _grad_spec(model, assembias, 'predict_grad')
+        model_keys = tuple(_grad_keys(assembias))
         ngal, xi, dngal, dxi = self.predict_batch_grad(
-            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            np.asarray(spec.theta,
+                       dtype=np.float64)[np.newaxis, :len(model_keys)],
             x[np.newaxis], n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-            modulate_with_cenocc=spec.modulate_with_cenocc)
-        keys = tuple(ZHENG07_KEYS) + tuple(self.keys)
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
+        keys = model_keys + tuple(self.keys)
         return (float(ngal[0]), xi[0],
                 {key: float(dngal[0, k]) for k, key in enumerate(keys)},
                 {key: dxi[0, k] for k, key in enumerate(keys)})
@@ -565,7 +606,8 @@ class Interpolator:
     # -- Fisher matrix of the likelihood ------------------------------------------------
 
     def chi2_fisher_batch(self, theta, x, data, precision, n_gauss_prim=10,
-                          extrapolate=False, modulate_with_cenocc=False):
+                          extrapolate=False, modulate_with_cenocc=False,
+                          assembias=False):
         """`chi2_grad_batch` with the Fisher matrix of the likelihood over
         ``(theta, x)``, from the same launch: with ``dxi_k`` the Jacobian
         column of quantity ``k`` (`ZHENG07_KEYS`, then ``self.keys``),
@@ -579,6 +621,7 @@ class Interpolator:
         ``dngal`` is returned next to ``fisher``, and an outer product
         completes it.  The matrix is symmetric to the bit; a draw's matrix
         does not depend on its batch, and not on ``data``.
+        ``assembias=True``: ``7 + D`` columns, as in `predict_batch_grad`.
 
         Returns
         -------
@@ -587,6 +630,10 @@ class Interpolator:
             for bit
         fisher : ``(n_draws, 5 + D, 5 + D)``
         """
+        if assembias:
+            return self._chi2_grad_assembias(
+                theta, x, data, precision, n_gauss_prim, extrapolate,
+                modulate_with_cenocc, True)
         theta, x = self._grad_inputs(theta, x, extrapolate)
         data, precision = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
@@ -608,7 +655,8 @@ class Interpolator:
         return ngal, chi2, dngal, dchi2, fisher
 
     def fisher_batch(self, theta, x, precision, n_gauss_prim=10,
-                     extrapolate=False, modulate_with_cenocc=False):
+                     extrapolate=False, modulate_with_cenocc=False,
+                     assembias=False):
         """The forecast form of `chi2_fisher_batch`, which needs no data: the
         same launch with a zero data vector, without ``chi2`` and ``dchi2``.
         The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal`` part of
@@ -623,17 +671,18 @@ class Interpolator:
         ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
             theta, x, np.zeros(len(self.tabcorr_list[0].tpcf_matrix)),
             precision, n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-            modulate_with_cenocc=modulate_with_cenocc)
+            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias)
         return ngal, dngal, fisher
 
     def fisher(self, model, precision, n_gauss_prim=10, extrapolate=False,
-               check_consistency=True):
+               check_consistency=True, assembias=False):
         """Un-batched `fisher_batch` for a model object: a plain
         `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model)
         whose ``param_dict`` holds the extra parameters, as `predict_grad`
         takes.  The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal``
         part of a likelihood is the caller's, from ``dngal`` by an outer
-        product.
+        product.  ``assembias=True``: a decorated model and
+        ``ZHENG07_ASSEMBIAS_KEYS + tuple(self.keys)``.
 
         Returns
         -------
@@ -645,17 +694,16 @@ class Interpolator:
         if check_consistency:
             for halotab in self.tabcorr_list:
                 halotab._check_consistency_cached(model)
-        spec = device_spec(model)
-        if spec is None or spec.family != 'zheng07' or spec.assembias:
-            raise NotImplementedError(
-                'fisher needs a plain Zheng07 model (no assembly bias, no '
-                'other family).')
+        spec = _grad_spec(model, assembias, 'fisher')
+        model_keys = tuple(_grad_keys(assembias))
         ngal, dngal, fisher = self.fisher_batch(
-            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            np.asarray(spec.theta,
+                       dtype=np.float64)[np.newaxis, :len(model_keys)],
             x[np.newaxis], precision, n_gauss_prim=n_gauss_prim,
             extrapolate=extrapolate,
-            modulate_with_cenocc=spec.modulate_with_cenocc)
-        keys = tuple(ZHENG07_KEYS) + tuple(self.keys)
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
+        keys = model_keys + tuple(self.keys)
         return (float(ngal[0]),
                 {key: float(dngal[0, k]) for k, key in enumerate(keys)},
                 fisher[0])

@@ -25,6 +25,8 @@ import numpy as np
 ZHENG07_KEYS = ('logMmin', 'sigma_logM', 'logM0', 'logM1', 'alpha')
 ASSEMBIAS_KEYS = ('mean_occupation_centrals_assembias_param1',
                   'mean_occupation_satellites_assembias_param1')
+# the columns of the decorated model's draws and of its gradients (`assembias=True`)
+ZHENG07_ASSEMBIAS_KEYS = ZHENG07_KEYS + ASSEMBIAS_KEYS
 
 try:
     from scipy.special import erf as _erf

@@ -26,7 +26,7 @@ import numpy as np
 from . import _lib
 from . import pinned
 from .galtable import GalTypeTable
-from .models import ZHENG07_KEYS, device_spec
+from .models import ZHENG07_ASSEMBIAS_KEYS, ZHENG07_KEYS, device_spec
 
 ATTR_KEYS = ['tpcf', 'mode', 'simname', 'redshift', 'Num_ptcl_requirement',
              'prim_haloprop_key', 'sec_haloprop_key']
@@ -722,7 +722,7 @@ class TabCorr:
     # -- analytic gradients -----------------------------------------------------------
 
     def predict_batch_grad(self, theta, n_gauss_prim=10,
-                           modulate_with_cenocc=False):
+                           modulate_with_cenocc=False, assembias=False):
         """`predict_batch` together with the exact derivatives of its results
         with respect to the five Zheng07 parameters (`ZHENG07_KEYS` order), in
         one kernel launch: what a best-fit search, a Fisher forecast or an
@@ -734,6 +734,13 @@ class TabCorr:
         M0 crosses.  Where the value divides by zero (``ngal = 0``,
         ``sigma_logM = 0``) the derivatives are NaN or inf.
 
+        ``assembias=True``: the model decorated with Heaviside assembly bias
+        at the median split (what ``predict_batch(..., assembias=True)``
+        predicts).  ``theta`` has the 7 columns of `ZHENG07_ASSEMBIAS_KEYS`
+        and so has every derivative: 7 stands wherever 5 does below.  It is
+        the derivative of the function computed: a strength beyond
+        ``[-1, 1]`` is clipped, its column is exactly zero.
+
         Returns
         -------
         ngal : ``(n_draws, )``
@@ -744,34 +751,41 @@ class TabCorr:
         Raises ``NotImplementedError`` for what the kernel does not serve
         (float32 tables, very large mode-auto tables).
         """
-        theta = _grad_theta(theta)
+        theta = _grad_theta(theta, assembias)
         device = self.to_device()
-        n_draws = len(theta)
+        n_draws, n_cols = theta.shape
         ngal = np.empty(n_draws)
         xi = np.empty((n_draws, device.n_r))
-        dngal = np.empty((n_draws, 5))
-        dxi = np.empty((n_draws, 5, device.n_r))
+        dngal = np.empty((n_draws, n_cols))
+        dxi = np.empty((n_draws, n_cols, device.n_r))
+        entry = (device.lib.tc_predict_grad_assembias_batch if assembias
+                 else device.lib.tc_predict_grad_zheng07_batch)
         with device.lock:
-            _lib.check(device.lib.tc_predict_grad_zheng07_batch(
+            _lib.check(entry(
                 device.handle, _lib.as_double_p(theta), theta.shape[1],
                 n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
                 _lib.as_double_p(ngal), _lib.as_double_p(xi),
                 _lib.as_double_p(dngal), _lib.as_double_p(dxi)))
         shape = tuple(self.tpcf_shape)
         return (ngal, xi.reshape((n_draws, ) + shape), dngal,
-                dxi.reshape((n_draws, 5) + shape))
+                dxi.reshape((n_draws, n_cols) + shape))
 
     def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
-                        modulate_with_cenocc=False):
+                        modulate_with_cenocc=False, assembias=False):
         """`chi2_batch` with its gradient: ``dchi2[:, k] = 2 (xi - data)^T P_sym
         dxi / dtheta_k`` with ``P_sym = (precision + precision^T) / 2``,
         finished on the device in the launch that computes ``xi``.
+        ``assembias=True``: 7 columns, as in `predict_batch_grad`.
 
         Returns
         -------
         ngal, chi2 : ``(n_draws, )``
         dngal, dchi2 : ``(n_draws, 5)``
         """
+        if assembias:
+            return self._chi2_grad_assembias(
+                theta, data, precision, n_gauss_prim, modulate_with_cenocc,
+                False)[:4]
         theta = _grad_theta(theta)
         # (the rows of the table's own matrix: a wrong argument is refused
         # before any device is touched, as a wrong theta is)
@@ -790,9 +804,36 @@ class TabCorr:
                 _lib.as_double_p(dngal), _lib.as_double_p(dchi2)))
         return ngal, chi2, dngal, dchi2
 
-    def predict_grad(self, model, n_gauss_prim=10, check_consistency=True):
+    def _chi2_grad_assembias(self, theta, data, precision, n_gauss_prim,
+                             modulate_with_cenocc, want_fisher):
+        """The likelihood gradient of the decorated model, with or without
+        its Fisher matrix: one entry point serves both."""
+        theta = _grad_theta(theta, True)
+        data, precision = _chi2_operands(data, precision,
+                                         len(self.tpcf_matrix))
+        device = self.to_device()
+        n_draws, n_cols = theta.shape
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal = np.empty((n_draws, n_cols))
+        dchi2 = np.empty((n_draws, n_cols))
+        fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
+        with device.lock:
+            _lib.check(device.lib.tc_chi2_grad_assembias_batch(
+                device.handle, _lib.as_double_p(theta), n_cols, n_draws,
+                n_gauss_prim, _flags(False, modulate_with_cenocc),
+                _lib.as_double_p(data), _lib.as_double_p(precision),
+                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
+                _lib.as_double_p(dngal), _lib.as_double_p(dchi2),
+                _lib.as_double_p(fisher) if want_fisher else None))
+        return ngal, chi2, dngal, dchi2, fisher
+
+    def predict_grad(self, model, n_gauss_prim=10, check_consistency=True,
+                     assembias=False):
         """Un-batched `predict_batch_grad` for a model object: a plain
-        `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model).
+        `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model);
+        with ``assembias=True`` a decorated one (`tabcorr_amd.Zheng07Model`
+        with a ``sec_haloprop_key``), the dicts then keyed by
+        `ZHENG07_ASSEMBIAS_KEYS`.
 
         Returns
         -------
@@ -803,23 +844,21 @@ class TabCorr:
         """
         if check_consistency:
             self._check_consistency_cached(model)
-        spec = device_spec(model)
-        if spec is None or spec.family != 'zheng07' or spec.assembias:
-            raise NotImplementedError(
-                'predict_grad needs a plain Zheng07 model (no assembly bias, '
-                'no other family).')
+        spec = _grad_spec(model, assembias, 'predict_grad')
+        keys = _grad_keys(assembias)
         ngal, xi, dngal, dxi = self.predict_batch_grad(
-            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
             n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=spec.modulate_with_cenocc)
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
         return (float(ngal[0]), xi[0],
-                {key: float(dngal[0, k]) for k, key in enumerate(ZHENG07_KEYS)},
-                {key: dxi[0, k] for k, key in enumerate(ZHENG07_KEYS)})
+                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
+                {key: dxi[0, k] for k, key in enumerate(keys)})
 
     # -- Fisher matrix of the likelihood ---------------------------------------------------
 
     def chi2_fisher_batch(self, theta, data, precision, n_gauss_prim=10,
-                          modulate_with_cenocc=False):
+                          modulate_with_cenocc=False, assembias=False):
         """`chi2_grad_batch` with the Fisher matrix of the likelihood, from
         the same launch: with ``dxi_k`` the Jacobian column of parameter ``k``
         (`ZHENG07_KEYS` order),
@@ -840,7 +879,8 @@ class TabCorr:
         the matrix is symmetric to the bit.  A draw's matrix does not depend
         on its batch, and not on ``data``.  Where the value divides by zero
         (``ngal = 0``, ``sigma_logM = 0``) the entries are NaN or inf, as the
-        gradients are.
+        gradients are.  ``assembias=True``: 7 columns, as in
+        `predict_batch_grad`, and a ``(7, 7)`` matrix.
 
         Returns
         -------
@@ -848,6 +888,10 @@ class TabCorr:
         dngal, dchi2 : ``(n_draws, 5)`` -- those of `chi2_grad_batch`, bit for bit
         fisher : ``(n_draws, 5, 5)``
         """
+        if assembias:
+            return self._chi2_grad_assembias(
+                theta, data, precision, n_gauss_prim, modulate_with_cenocc,
+                True)
         theta = _grad_theta(theta)
         data, precision = _chi2_operands(data, precision,
                                          len(self.tpcf_matrix))
@@ -867,7 +911,7 @@ class TabCorr:
         return ngal, chi2, dngal, dchi2, fisher
 
     def fisher_batch(self, theta, precision, n_gauss_prim=10,
-                     modulate_with_cenocc=False):
+                     modulate_with_cenocc=False, assembias=False):
         """The forecast form of `chi2_fisher_batch`, which needs no data: the
         same launch with a zero data vector, without ``chi2`` and ``dchi2``.
         The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal`` part of
@@ -882,16 +926,17 @@ class TabCorr:
         ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
             theta, np.zeros(len(self.tpcf_matrix)), precision,
             n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=modulate_with_cenocc)
+            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias)
         return ngal, dngal, fisher
 
     def fisher(self, model, precision, n_gauss_prim=10,
-               check_consistency=True):
+               check_consistency=True, assembias=False):
         """Un-batched `fisher_batch` for a model object: a plain
         `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model),
         as `predict_grad` takes.  The Gauss-Newton Hessian of chi2 is
         ``2 fisher``; the ``ngal`` part of a likelihood is the caller's, from
-        ``dngal`` by an outer product.
+        ``dngal`` by an outer product.  ``assembias=True``: a decorated
+        model, `ZHENG07_ASSEMBIAS_KEYS` and a ``(7, 7)`` matrix.
 
         Returns
         -------
@@ -902,17 +947,15 @@ class TabCorr:
         """
         if check_consistency:
             self._check_consistency_cached(model)
-        spec = device_spec(model)
-        if spec is None or spec.family != 'zheng07' or spec.assembias:
-            raise NotImplementedError(
-                'fisher needs a plain Zheng07 model (no assembly bias, no '
-                'other family).')
+        spec = _grad_spec(model, assembias, 'fisher')
+        keys = _grad_keys(assembias)
         ngal, dngal, fisher = self.fisher_batch(
-            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :5],
+            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
             precision, n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=spec.modulate_with_cenocc)
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
         return (float(ngal[0]),
-                {key: float(dngal[0, k]) for k, key in enumerate(ZHENG07_KEYS)},
+                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
                 fisher[0])
 
     # -- reverse mode at the occupation seam ---------------------------------------------
@@ -1092,13 +1135,36 @@ def _flags(separate_gal_type=False, modulate_with_cenocc=False,
             (_lib.FLAG_LEAUTHAUD11 if family == 'leauthaud11' else 0))
 
 
-def _grad_theta(theta):
-    """The ``(n_draws, 5)`` parameter array of the gradient calls."""
+def _grad_keys(assembias=False):
+    """The differentiated model parameters, in column order."""
+    return ZHENG07_ASSEMBIAS_KEYS if assembias else ZHENG07_KEYS
+
+
+def _grad_theta(theta, assembias=False):
+    """The ``(n_draws, 5)`` parameter array of the gradient calls --
+    ``(n_draws, 7)`` for the model decorated with assembly bias."""
     theta = _lib.contiguous(np.atleast_2d(theta))
-    if theta.ndim != 2 or theta.shape[1] != len(ZHENG07_KEYS):
+    n_cols = len(_grad_keys(assembias))
+    if theta.ndim != 2 or theta.shape[1] != n_cols:
         raise ValueError('theta must have shape (n_draws, {}), got {}.'.format(
-            len(ZHENG07_KEYS), theta.shape))
+            n_cols, theta.shape))
     return theta
+
+
+def _grad_spec(model, assembias, what):
+    """The device spec of the model of an un-batched gradient call: plain
+    Zheng07 -- with ``assembias`` Zheng07 decorated with assembly bias."""
+    spec = device_spec(model)
+    if not assembias:
+        if spec is None or spec.family != 'zheng07' or spec.assembias:
+            raise NotImplementedError(
+                '{} needs a plain Zheng07 model (no assembly bias, no other '
+                'family).'.format(what))
+    elif spec is None or spec.family != 'zheng07' or not spec.assembias:
+        raise ValueError(
+            '{} with assembias=True needs a Zheng07 model decorated with '
+            'assembly bias.'.format(what))
+    return spec
 
 
 def _chi2_operands(data, precision, n_r):

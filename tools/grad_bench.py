@@ -28,8 +28,16 @@ and the two interpolator shapes above and on a mode-cross table with the 148 r b
 limit (where the n_r^2 terms of an entry are most); for the tables also the two device-pointer
 entries, device-resident and pipelined, where the kernel's own increase shows.
 
+The assembly-bias leg (--only assembias; not part of the default run) times the gradients of the
+decorated model, predict_batch_grad(assembias=True) and chi2_grad_batch(assembias=True), on
+two-percentile tables of 100 and 60 bins next to the plain predict_batch_grad on the same table
+and next to what they replace: 14 calls of predict_batch(assembias=True), the central
+differences over seven parameters.  Device-resident and pipelined, as the first leg, and through
+the host-array methods.  The expectation is about 8/6 of the plain gradient -- eight quantities
+for six in the dot products and the LDS rows, the matrix stream unchanged.
+
 Prints one JSON line and, with --notes, appends the figures to that file.  --only vjp, --only
-fisher: that leg alone.
+fisher, --only assembias: that leg alone.
 """
 
 import argparse
@@ -101,6 +109,92 @@ def measure(name, n_prim, n_sec, n_r, n_draws, seconds):
         synchronize()
         memory.free_all()
     return result
+
+
+def measure_assembias(name, n_prim, n_r, n_draws, seconds):
+    from tabcorr_amd import TabCorr, _lib, synthetic
+    table = synthetic.synthetic_table(n_prim, 2, (n_r, ), 'auto', seed=0)
+    halotab = TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'], table['tpcf_shape'],
+                                  table['attrs'])
+    device = halotab.to_device()
+    lib, handle = device.lib, device.handle
+    memory = Device(lib, _lib)
+    rng = np.random.default_rng(3)
+    plain = synthetic.zheng07_draws(n_draws, seed=1)
+    theta = np.ascontiguousarray(np.hstack([plain, rng.uniform(-1.0, 1.0, (n_draws, 2))]))
+    d_theta, d_plain = memory.upload(theta), memory.upload(plain)
+    d_ngal, d_xi = memory.malloc(n_draws), memory.malloc(n_draws * n_r)
+    d_dngal, d_dxi = memory.malloc(n_draws * 7), memory.malloc(n_draws * 7 * n_r)
+    d_chi2, d_dchi2 = memory.malloc(n_draws), memory.malloc(n_draws * 7)
+    data = np.ascontiguousarray(rng.uniform(0.5, 1.5, n_r))
+    precision = np.ascontiguousarray(np.eye(n_r) + 0.01 * rng.normal(size=(n_r, n_r)))
+    operands = (_lib.as_double_p(data), _lib.as_double_p(precision))
+
+    def forward():
+        _lib.check(lib.tc_predict_zheng07_batch_device(handle, d_theta, 7, n_draws, 10,
+                                                       _lib.FLAG_ASSEMBIAS, d_ngal, d_xi))
+
+    def gradient():
+        _lib.check(lib.tc_predict_grad_assembias_batch_device(handle, d_theta, 7, n_draws, 10, 0,
+                                                              d_ngal, d_xi, d_dngal, d_dxi))
+
+    def chi2_gradient():
+        _lib.check(lib.tc_chi2_grad_assembias_batch_device(
+            handle, d_theta, 7, n_draws, 10, 0, *operands, d_ngal, d_chi2, d_dngal, d_dchi2,
+            None))
+
+    def plain_gradient():
+        _lib.check(lib.tc_predict_grad_zheng07_batch_device(handle, d_plain, 5, n_draws, 10, 0,
+                                                            d_ngal, d_xi, d_dngal, d_dxi))
+
+    def synchronize():
+        _lib.check(lib.tc_table_synchronize(handle))
+
+    result = {'table': name, 'n_bins': 4 * n_prim, 'n_r': n_r, 'n_draws': n_draws}
+    try:
+        # forward first and last: the two figures bracket the drift of the run
+        for key, call in (('forward_us', forward), ('grad_us', gradient),
+                          ('chi2_grad_us', chi2_gradient), ('plain_grad_us', plain_gradient),
+                          ('forward_again_us', forward)):
+            result[key] = sustained(call, synchronize, seconds) * 1e6
+    finally:
+        synchronize()
+        memory.free_all()
+    forward_us = 0.5 * (result['forward_us'] + result['forward_again_us'])
+    result['differences_us'] = 14 * forward_us
+    result['grad_over_plain_grad'] = result['grad_us'] / result['plain_grad_us']
+    result['differences_over_grad'] = result['differences_us'] / result['grad_us']
+    # the same through the methods, host arrays in and out
+    host = [('host_forward_us', lambda: halotab.predict_batch(theta, assembias=True)),
+            ('host_grad_us', lambda: halotab.predict_batch_grad(theta, assembias=True)),
+            ('host_chi2_grad_us',
+             lambda: halotab.chi2_grad_batch(theta, data, precision, assembias=True)),
+            ('host_plain_grad_us', lambda: halotab.predict_batch_grad(plain)),
+            ('host_forward_again_us', lambda: halotab.predict_batch(theta, assembias=True))]
+    for key, call in host:
+        result[key] = time_calls(call, seconds) * 1e6
+    result['host_differences_us'] = 7 * (result['host_forward_us'] +
+                                         result['host_forward_again_us'])
+    return result
+
+
+def write_assembias_notes(notes, results, n_draws):
+    notes.write('\n## tools/grad_bench.py --only assembias, %d draws per call\n\n' % n_draws)
+    notes.write('Device-resident, pipelined (host arrays in and out in brackets), us per call; '
+                'expectation: decorated / plain gradient about 8/6 = 1.33.\n\n')
+    notes.write('| table | bins | forward(assembias) us | gradient(assembias) us | '
+                'chi2 gradient(assembias) us | plain gradient us | 14 forward calls us | '
+                'decorated / plain gradient | 14 forward / gradient |\n')
+    notes.write('|---|---|---|---|---|---|---|---|---|\n')
+    for r in results:
+        notes.write('| %s | %d | %.1f, %.1f after [%.1f, %.1f after] | %.1f [%.1f] | %.1f [%.1f] '
+                    '| %.1f [%.1f] | %.1f [%.1f] | %.3f | %.2f |\n' % (
+                        r['table'], r['n_bins'], r['forward_us'], r['forward_again_us'],
+                        r['host_forward_us'], r['host_forward_again_us'], r['grad_us'],
+                        r['host_grad_us'], r['chi2_grad_us'], r['host_chi2_grad_us'],
+                        r['plain_grad_us'], r['host_plain_grad_us'], r['differences_us'],
+                        r['host_differences_us'], r['grad_over_plain_grad'],
+                        r['differences_over_grad']))
 
 
 def measure_interpolator(name, grid, n_prim, n_sec, n_r, mode, n_draws, seconds):
@@ -323,8 +417,21 @@ def main():
     parser.add_argument('--draws', type=int, default=10000)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--notes', default=None, help='append the figures to this file')
-    parser.add_argument('--only', choices=['vjp', 'fisher'], default=None, help='one leg alone')
+    parser.add_argument('--only', choices=['vjp', 'fisher', 'assembias'], default=None,
+                        help='one leg alone')
     args = parser.parse_args()
+    if args.only == 'assembias':
+        results = [measure_assembias('two percentiles, 100 bins', 25, 19, args.draws,
+                                     args.seconds),
+                   measure_assembias('two percentiles, 60 bins', 15, 19, args.draws,
+                                     args.seconds)]
+        print(json.dumps({'assembias_metric': 'us per call, device-resident, pipelined; host_*: '
+                                              'host arrays in and out',
+                          'assembias': results}))
+        if args.notes:
+            with open(args.notes, 'a') as notes:
+                write_assembias_notes(notes, results, args.draws)
+        return
     if args.only == 'fisher':
         tables = [measure_fisher('BASELINE configs[1]', 50, 1, 19, args.draws, args.seconds),
                   measure_fisher("reference example table's shape", 30, 1, 19, args.draws,
