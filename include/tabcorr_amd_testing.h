@@ -103,6 +103,19 @@ int tc_debug_fused_form(int n_bins, int n_central, int n_r, int n_cus, int group
                         int64_t n_draws, int n_gauss, unsigned flags, unsigned call,
                         const int* options, const int* measured_forms, const float* measured_us,
                         int* waves, int* draws, int* lds_bytes);
+/* What the pair counter (tabcorr_amd/csrc/paircount.hip: pair_count) plans for a periodic box,
+ * a reach in the plane (r_p,max or s_max) and along the line of sight (pi_max or s_max), the
+ * larger of the two samples' point counts, n_bin = n_rp (labelled r_p counts), n_rp n_pi or
+ * n_s n_mu bins and n_labels labels -- no device needed: cells and neighbour cells per side
+ * (2, 1, or 0 for a single cell) along x, y, z (tabcorr_amd/csrc/hostmath.h: make_cell_grid),
+ * the labels per block of sample 1 and of sample 2 and the number of blocks on either side
+ * (plan_label_blocks), and the dynamic LDS bytes per workgroup the launch asks for.
+ * n_labels == 0: the unlabelled count (blocks reported as 0).  Fails as the count itself
+ * would where the bins exceed what a workgroup's LDS counters take. */
+int tc_debug_pair_plan(const double* boxsize, double reach_xy, double reach_z,
+                       int64_t n_points, int n_bin, int n_labels, int32_t* cells,
+                       int32_t* neighbours, int32_t* labels_per_block, int32_t* n_blocks,
+                       int64_t* lds_bytes);
 /* TEST INFRASTRUCTURE, never called by the product: executes the kernel's table layout,
  * schedule and slab grouping on the host, lane by lane, for densities (n_bins, ldb) given
  * in the reference's bin order; out (n_draws, 1 | 3, n_r) = sum_p c_p T[r][p] n_i n_j

@@ -81,20 +81,45 @@ def pair_count_rppi(pos1, pos2, boxsize, rp_bins, pi_max, n_pi=None,
     return counts.reshape(n_rp, n_pi)
 
 
-def pair_count_smu(pos1, pos2, boxsize, s_bins, n_mu, chunk=512):
+def pair_count_smu(pos1, pos2, boxsize, s_bins, n_mu, chunk=512, label1=None,
+                   label2=None, n_labels=0):
     """Ordered pair counts ``(n_s, n_mu)`` in bins of the separation ``s`` and
     of ``mu = |dz| / s`` on ``[0, 1)`` -- ``Corrfunc.theory.DDsmu`` as called at
     ``tabcorr/corrfunc.py:141-155``: ``s_bins[0]^2 <= s^2 < s_bins[-1]^2`` with
     ``s^2 = (dx^2 + dy^2) + dz^2``, ``mu < 1``, mu bin ``int(mu n_mu)``; a pair at
-    zero separation (self-pairs when ``s_bins[0] == 0``) goes to mu bin 0."""
+    zero separation (self-pairs when ``s_bins[0] == 0``) goes to mu bin 0.
+    With labels (as `pair_count_rppi` takes them): ``(n_s, n_mu, n_labels,
+    n_labels)``, the counts between the points of every pair of labels."""
     pos1 = np.asarray(pos1, dtype=np.float64).reshape(-1, 3)
     if pos2 is None:
-        pos2 = pos1
+        pos2, label2 = pos1, label1
     pos2 = np.asarray(pos2, dtype=np.float64).reshape(-1, 3)
     boxsize = np.broadcast_to(np.asarray(boxsize, dtype=np.float64), (3, ))
     s_bins = np.asarray(s_bins, dtype=np.float64)
     n_s = len(s_bins) - 1
     edge_sqr = s_bins * s_bins
+    labelled = n_labels > 0
+    if labelled:
+        label1 = np.asarray(label1, dtype=np.int64)
+        label2 = np.asarray(label2, dtype=np.int64)
+        counts = np.zeros(n_s * n_mu * n_labels * n_labels, dtype=np.uint64)
+        for begin in range(0, len(pos1), chunk):
+            a = pos1[begin:begin + chunk]
+            dz = np.abs(_min_image(a[:, None, 2] - pos2[None, :, 2], boxsize[2]))
+            dx = _min_image(a[:, None, 0] - pos2[None, :, 0], boxsize[0])
+            dy = _min_image(a[:, None, 1] - pos2[None, :, 1], boxsize[1])
+            s_sqr = (dx * dx + dy * dy) + dz * dz
+            i, j = np.nonzero((s_sqr >= edge_sqr[0]) & (s_sqr < edge_sqr[-1]))
+            s_sqr, dz = s_sqr[i, j], dz[i, j]
+            with np.errstate(invalid='ignore', divide='ignore'):
+                mu = np.where(s_sqr > 0, dz / np.sqrt(s_sqr), 0.0)
+            mu_bin = (mu * float(n_mu)).astype(np.int64)
+            ok = (mu < 1.0) & (mu_bin < n_mu)
+            s_bin = np.searchsorted(edge_sqr, s_sqr[ok], side='right') - 1
+            flat = ((s_bin * n_mu + mu_bin[ok]) * n_labels +
+                    label1[begin + i[ok]]) * n_labels + label2[j[ok]]
+            counts += np.bincount(flat, minlength=len(counts)).astype(np.uint64)
+        return counts.reshape(n_s, n_mu, n_labels, n_labels)
     counts = np.zeros(n_s * n_mu, dtype=np.uint64)
     for begin in range(0, len(pos1), chunk):
         a = pos1[begin:begin + chunk]

@@ -81,6 +81,9 @@ SIGNATURES = {
                                                  ctypes.c_uint, c_int_p, c_int_p,
                                                  c_float_p, c_int_p, c_int_p,
                                                  c_int_p],
+    'tc_debug_pair_plan': [c_double_p, ctypes.c_double, ctypes.c_double, ctypes.c_int64,
+                           ctypes.c_int, ctypes.c_int, c_int32_p, c_int32_p, c_int32_p,
+                           c_int32_p, c_int64_p],
     'tc_debug_quad_emulate': [ctypes.c_int, ctypes.c_int, c_double_p, c_uint8_p,
                               ctypes.c_int, ctypes.c_int, c_double_p,
                               ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -1447,6 +1447,18 @@ void sort_cells_by_label(CellSort& cells) {
   cells = std::move(sorted);
 }
 
+LabelBlockPlan plan_label_blocks(int n_bin, int n_labels, int budget, int limit) {
+  const int64_t bins = n_bin;     // (products in 64 bits, whatever the caller's bounds)
+  int b1 = n_labels, b2 = std::min(n_labels, 8);
+  while (bins * b1 * b2 > budget && b2 > 2) --b2;
+  while (bins * b1 * b2 > budget && b1 > 1) b1 = (b1 + 1) / 2;
+  while (bins * b1 * b2 > limit && b2 > 1) --b2;
+  LabelBlockPlan plan;
+  plan.block1 = b1;
+  plan.block2 = b2;
+  return plan;
+}
+
 void build_label_blocks(const CellSort& cells, int n_labels, int block, LabelBlocks& out) {
   out.block = std::max(1, block);
   out.n_blocks = std::max(1, (n_labels + out.block - 1) / out.block);

@@ -397,6 +397,18 @@ struct LabelBlocks {
 };
 void build_label_blocks(const CellSort& cells, int n_labels, int block, LabelBlocks& out);
 
+// Labels per block of set 1 and of set 2 for n_bin (separation [, mu]) bins, in LDS counters
+// of 32 bits: n_bin * block1 * block2 stays within `budget` (what keeps several workgroups on
+// a CU) while block1 > 1 or block2 > 2, and within `limit` (what one workgroup can have)
+// always; the caller has checked n_bin <= limit.  Set 1 keeps all its labels while that fits;
+// set 2 starts from 8.  Pure: paircount.hip calls it with its budget, tests with any.
+constexpr int kPairLdsLimit = 60 * 1024 / 4;      // counters one workgroup may ask for
+constexpr int kPairLdsBudgetKB = 30;              // default budget (TC_PAIR_LDS_KB)
+struct LabelBlockPlan {
+  int block1 = 1, block2 = 1;
+};
+LabelBlockPlan plan_label_blocks(int n_bin, int n_labels, int budget, int limit);
+
 // Work units of that kernel: (set-1 label block, set-2 label block, range of cells), the cell
 // ranges cut so that every unit holds about the same number of candidate pairs (points of a
 // cell x points in the cells around it) and all blocks together give ~`target_units` units.

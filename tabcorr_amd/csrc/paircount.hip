@@ -349,6 +349,8 @@ __global__ __launch_bounds__(kPairThreads) void pair_count_blocks_kernel(
     __syncthreads();
     const int total = nb_prefix[128];
     pending += (unsigned long long)(p_end - p_begin) * (unsigned long long)total;
+    // (no test reaches this flush, nor the launch's refusal at 4e9 candidates in one cell: both
+    // need ~5e4 coincident points per pair of label blocks, minutes of brute-force oracle)
     if (pending >= (1ull << 31)) {
       flush();
       pending = (unsigned long long)(p_end - p_begin) * (unsigned long long)total;
@@ -536,6 +538,12 @@ struct DeviceArrays {
   }
 };
 
+// LDS counters a workgroup of the labelled kernel should stay within (hostmath.h:
+// plan_label_blocks; TC_PAIR_LDS_KB: developer builds)
+int pair_lds_budget() {
+  return env_int("TC_PAIR_LDS_KB", kPairLdsBudgetKB) * 1024 / (int)sizeof(unsigned);
+}
+
 // smu: rp_bins are the s bins, n_pi the number of mu bins on [0, 1), pi_max is ignored (the
 // line-of-sight reach is the largest s).
 int pair_count(const double* pos1, const int32_t* label1, int64_t n1, const double* pos2,
@@ -605,13 +613,11 @@ int pair_count(const double* pos1, const int32_t* label1, int64_t n1, const doub
     // keep five workgroups on a CU, which the scalar-load latency of the inner loop needs
     // (19 bins x 100 labels, 10^6 points: 8 labels of set 2 = 60 KB 276 ms, 4 = 30 KB 180 ms,
     // 2 = 15 KB 190 ms: tools/archive/r03_pc_knobs.sh); set 1 keeps all its labels while that fits
-    const int limit = 60 * 1024 / (int)sizeof(unsigned);
-    const int budget = env_int("TC_PAIR_LDS_KB", 30) * 1024 / (int)sizeof(unsigned);
+    // (hostmath.h: plan_label_blocks)
+    const int limit = kPairLdsLimit;
     TC_CHECK(n_bin <= limit, "at most %d (separation, mu) bins are supported", limit);
-    int b1 = n_labels, b2 = std::min(n_labels, 8);
-    while (n_bin * b1 * b2 > budget && b2 > 2) --b2;
-    while (n_bin * b1 * b2 > budget && b1 > 1) b1 = (b1 + 1) / 2;
-    while (n_bin * b1 * b2 > limit && b2 > 1) --b2;
+    const LabelBlockPlan plan = plan_label_blocks(n_bin, n_labels, pair_lds_budget(), limit);
+    const int b1 = plan.block1, b2 = plan.block2;
     sort_cells_by_label(set1);
     if (!autocorr) sort_cells_by_label(set2);
     build_label_blocks(set1, n_labels, b1, blocks1);
@@ -726,6 +732,8 @@ int pair_count(const double* pos1, const int32_t* label1, int64_t n1, const doub
     const dim3 grid_dim((unsigned)units.block1.size());
     if (grid_dim.x == 0) return TC_OK;
     const int unroll = env_int("TC_PAIR_UNROLL", 8);                  // (developer builds)
+    // (up to 60 KB of counters next to 11 KB of static LDS: the runtime serves such launches
+    // without a raised limit -- tests/test_gpu_paircount_plans.py, cases S3 and S5)
 #define TC_LAUNCH(SMU, U)                                                                     \
   hipLaunchKernelGGL((pair_count_blocks_kernel<SMU, U>), grid_dim, block, lds, nullptr, a,  \
                      a.x1, a.y1, a.z1, a.label1)
@@ -849,6 +857,44 @@ int mass_in_cylinders(const double* objects, int64_t n_obj, const double* partic
 }  // namespace tc
 
 extern "C" {
+
+// include/tabcorr_amd_testing.h: the grid and the label blocks pair_count() would plan (no
+// device is touched)
+int tc_debug_pair_plan(const double* boxsize, double reach_xy, double reach_z, int64_t n_points,
+                       int n_bin, int n_labels, int32_t* cells, int32_t* neighbours,
+                       int32_t* labels_per_block, int32_t* n_blocks, int64_t* lds_bytes) {
+  using tc::host::fail;
+  TC_CHECK(boxsize && cells && neighbours && labels_per_block && n_blocks && lds_bytes,
+           "NULL argument");
+  TC_CHECK(boxsize[0] > 0 && boxsize[1] > 0 && boxsize[2] > 0 && reach_xy > 0 && reach_z > 0,
+           "box size and reach must be positive");
+  TC_CHECK(n_points >= 0 && n_bin >= 1 && n_labels >= 0 && n_labels <= 4096,
+           "invalid point, bin or label count");
+  const tc::CellGrid grid = tc::make_cell_grid(boxsize, reach_xy, reach_z, n_points, true);
+  cells[0] = grid.nx;
+  cells[1] = grid.ny;
+  cells[2] = grid.nz;
+  neighbours[0] = grid.reach_x;
+  neighbours[1] = grid.reach_y;
+  neighbours[2] = grid.reach_z;
+  if (n_labels == 0) {
+    *lds_bytes = (int64_t)n_bin * (int64_t)sizeof(unsigned);
+    TC_CHECK(*lds_bytes <= 48 * 1024, "at most %d two-dimensional bins are supported",
+             48 * 1024 / 4);
+    labels_per_block[0] = labels_per_block[1] = n_blocks[0] = n_blocks[1] = 0;
+    return TC_OK;
+  }
+  TC_CHECK(n_bin <= tc::kPairLdsLimit, "at most %d (separation, mu) bins are supported",
+           tc::kPairLdsLimit);
+  const tc::LabelBlockPlan plan =
+      tc::plan_label_blocks(n_bin, n_labels, tc::host::pair_lds_budget(), tc::kPairLdsLimit);
+  labels_per_block[0] = plan.block1;
+  labels_per_block[1] = plan.block2;
+  n_blocks[0] = (n_labels + plan.block1 - 1) / plan.block1;
+  n_blocks[1] = (n_labels + plan.block2 - 1) / plan.block2;
+  *lds_bytes = (int64_t)n_bin * plan.block1 * plan.block2 * (int64_t)sizeof(unsigned);
+  return TC_OK;
+}
 
 int tc_mass_in_cylinders(const double* objects, int64_t n_objects, const double* particles,
                          int64_t n_particles, const double* masses, const double* boxsize,

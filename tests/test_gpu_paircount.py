@@ -119,7 +119,9 @@ def test_wp_and_the_tabulation_matrix():
 def test_labelled_counts_at_tabulation_scale():
     """2 x 10^5 halos in 100 bins (the shape of BASELINE configs[1]'s table): properties that
     do not need the O(N^2) oracle -- symmetry, even diagonal, the sum over bin pairs equals
-    the unlabelled count, invariance under a relabelling -- plus the oracle on a sub-box."""
+    the unlabelled count, invariance under a relabelling.  The oracle on this plan (all labels of
+    sample 1 in one block, blocks of a few labels of sample 2) at a size it can count: case L1 of
+    tests/test_gpu_paircount_plans.py."""
     from tabcorr_amd import corrfunc
     rng = np.random.default_rng(3)
     box = 250.0

@@ -120,6 +120,44 @@ def test_s_mu_counts():
         oracle.s_mu_tpcf(pos1, s_bins, np.array([0.0, 0.3, 1.0]), period=box)
 
 
+def test_labelled_s_mu_counts_are_the_per_label_pair_counts():
+    """pair_count_smu with labels: block (a, b) of the (n_s, n_mu, L, L) result is the
+    unlabelled count between the points of label a and those of label b, auto and cross;
+    one label has no points, a first edge of 0 puts the self pairs on the diagonal."""
+    rng = np.random.default_rng(31)
+    box = np.array([40.0, 50.0, 45.0])
+    pos1 = rng.uniform(0, 1, (600, 3)) * box
+    pos1[:150] = np.mod(pos1[0] + rng.normal(0, 1.0, (150, 3)), box)    # a clump
+    pos2 = rng.uniform(0, 1, (400, 3)) * box
+    label1 = rng.choice([0, 1, 2, 4], len(pos1))                        # label 3 is empty
+    label2 = rng.integers(0, 5, len(pos2))
+    for s_bins in (np.logspace(-0.3, 1.2, 6), np.array([0.0, 1.0, 4.0, 12.0])):
+        auto = oracle.pair_count_smu(pos1, None, box, s_bins, 7, label1=label1, n_labels=5)
+        assert auto.shape == (len(s_bins) - 1, 7, 5, 5) and auto.dtype == np.uint64
+        assert np.array_equal(auto, auto.transpose(0, 1, 3, 2))
+        assert np.array_equal(auto.sum(axis=(2, 3)),
+                              oracle.pair_count_smu(pos1, None, box, s_bins, 7))
+        cross = oracle.pair_count_smu(pos1, pos2, box, s_bins, 7, label1=label1,
+                                      label2=label2, n_labels=5)
+        assert np.array_equal(cross.sum(axis=(2, 3)),
+                              oracle.pair_count_smu(pos1, pos2, box, s_bins, 7))
+        for a in range(5):
+            for b in range(5):
+                sub = oracle.pair_count_smu(pos1[label1 == a],
+                                            None if a == b else pos1[label1 == b], box,
+                                            s_bins, 7)
+                assert np.array_equal(auto[:, :, a, b], sub), (a, b)
+                sub = oracle.pair_count_smu(pos1[label1 == a], pos2[label2 == b], box,
+                                            s_bins, 7)
+                assert np.array_equal(cross[:, :, a, b], sub), (a, b)
+        assert auto[:, :, 3].sum() == 0 and cross[:, :, 3].sum() == 0
+        assert cross.sum() > 1000
+    # a small chunk changes nothing (the label of point i is looked up across chunks)
+    assert np.array_equal(
+        oracle.pair_count_smu(pos1, pos2, box, s_bins, 7, chunk=64, label1=label1,
+                              label2=label2, n_labels=5), cross)
+
+
 def test_s_mu_matrix_matches_pairwise_calls():
     """compute_tpcf_matrix_smu (tabcorr/tabcorr.py:846-922 with tpcf = s_mu_tpcf): symmetric,
     zero rows for empty bins, entries equal to the single-pair calls, flattened as

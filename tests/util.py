@@ -59,3 +59,35 @@ def assert_rel(actual, desired, rtol, what='', floor=1e-14):
     scale = np.max(np.abs(desired)) if desired.size else 0.0
     np.testing.assert_allclose(actual, desired, rtol=rtol,
                                atol=floor * scale, err_msg=what)
+
+
+def pair_plan(boxsize, reach_xy, reach_z, n_points, n_bin, n_labels=0):
+    """tc_debug_pair_plan (no device needed): what the pair counter plans for a box, the
+    reach in the plane and along the line of sight, the larger sample's point count,
+    ``n_bin`` bins and ``n_labels`` labels (0: the unlabelled count) -- a dict with ``cells``
+    and ``neighbours`` (per axis), ``plan`` = (labels per block of sample 1, of sample 2,
+    blocks of sample 1, of sample 2) and ``lds_bytes``."""
+    import ctypes
+    from tabcorr_amd import _lib
+    lib = _lib.load()
+    box = np.ascontiguousarray(np.broadcast_to(np.asarray(boxsize, dtype=np.float64), (3, )))
+    cells, neighbours = (ctypes.c_int32 * 3)(), (ctypes.c_int32 * 3)()
+    per_block, n_blocks = (ctypes.c_int32 * 2)(), (ctypes.c_int32 * 2)()
+    lds = ctypes.c_int64(-1)
+    _lib.check(lib.tc_debug_pair_plan(
+        box.ctypes.data_as(_lib.c_double_p), float(reach_xy), float(reach_z), int(n_points),
+        int(n_bin), int(n_labels), cells, neighbours, per_block, n_blocks, ctypes.byref(lds)))
+    return {'cells': tuple(cells), 'neighbours': tuple(neighbours),
+            'plan': (per_block[0], per_block[1], n_blocks[0], n_blocks[1]),
+            'lds_bytes': lds.value}
+
+
+def cell_occupancy(pos, boxsize, cells):
+    """Points per cell of the pair counter's grid, (nx, ny, nz): a point belongs to cell
+    ``min(n - 1, int(x / L n))`` along every axis (hostmath.cpp: sort_into_cells)."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    box = np.broadcast_to(np.asarray(boxsize, dtype=np.float64), (3, ))
+    cells = np.asarray(cells)
+    index = np.minimum(cells - 1, (pos / box * cells).astype(np.int64))
+    flat = (index[:, 0] * cells[1] + index[:, 1]) * cells[2] + index[:, 2]
+    return np.bincount(flat, minlength=int(np.prod(cells))).reshape(tuple(cells))

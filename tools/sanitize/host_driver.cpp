@@ -2,8 +2,8 @@
 // (SURVEY.md section 5): g++ -fsanitize=address,undefined on hostmath.cpp + this file, no
 // HIP.  Walks the same entry points the C ABI uses (bin permutation and segmentation,
 // chunking, the quadratic-form layout / schedule / table fill / emulation, spline
-// matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort, the choice of
-// the one-launch form) over a sweep of shapes and checks the results against direct
+// matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort and label-block
+// plan, the choice of the one-launch form) over a sweep of shapes and checks the results against direct
 // evaluations.  Exit status 0 = all
 // checks passed and no sanitizer report (-fno-sanitize-recover aborts on the first).
 //
@@ -318,6 +318,65 @@ static void check_cells() {
     }
 }
 
+// hostmath.h: plan_label_blocks over bins up to the limit and labels up to the C ABI's 4096:
+// blocks that cover the labels, counters within the limit always and within the budget until
+// nothing is left to shrink, and a cell sort cut by the planned blocks.
+static void check_label_block_plan() {
+  const int limit = tc::kPairLdsLimit;
+  std::vector<int> bins;
+  for (double b = 1.0; b < limit; b *= 1.37) bins.push_back((int)b);
+  for (int b : {19, 64, 80, 3840, 6782, 6783, 7200, 7680, 7681, 7744, 13564, 13565, 15359, 15360})
+    bins.push_back(b);
+  for (int budget_kb : {30, 8, 60})
+    for (int n_bin : bins)
+      for (int n_labels : {1, 2, 3, 7, 8, 9, 50, 51, 70, 71, 100, 4096}) {
+        const int budget = budget_kb * 1024 / 4;
+        const tc::LabelBlockPlan plan = tc::plan_label_blocks(n_bin, n_labels, budget, limit);
+        const int64_t counters = (int64_t)n_bin * plan.block1 * plan.block2;
+        EXPECT(plan.block1 >= 1 && plan.block1 <= n_labels && plan.block2 >= 1 &&
+                   plan.block2 <= std::min(n_labels, 8),
+               "%d bins, %d labels: blocks of %d and %d labels", n_bin, n_labels, plan.block1,
+               plan.block2);
+        EXPECT(counters <= limit, "%d bins, %d labels: %lld counters", n_bin, n_labels,
+               (long long)counters);
+        EXPECT(counters <= budget || (plan.block1 == 1 && plan.block2 <= 2),
+               "%d bins, %d labels: %lld counters over the budget with blocks of %d and %d", n_bin,
+               n_labels, (long long)counters, plan.block1, plan.block2);
+      }
+  // the planned blocks cut a sorted point set: every label in exactly one block per side
+  std::mt19937_64 rng(6);
+  std::uniform_real_distribution<double> uniform(0.0, 1.0);
+  const double box[3] = {100.0, 100.0, 100.0};
+  for (int n_labels : {3, 51, 71}) {
+    const int64_t n = 2000;
+    std::vector<double> pos((size_t)n * 3);
+    std::vector<int32_t> label((size_t)n);
+    for (int64_t p = 0; p < n; ++p) {
+      for (int d = 0; d < 3; ++d) pos[3 * p + d] = uniform(rng) * box[d];
+      label[p] = (int32_t)(rng() % n_labels);
+    }
+    const tc::CellGrid grid = tc::make_cell_grid(box, 20.0, 20.0, n);
+    tc::CellSort sorted;
+    EXPECT(tc::sort_into_cells(grid, pos.data(), label.data(), n, sorted) == -1, "outside");
+    tc::sort_cells_by_label(sorted);
+    for (int n_bin : {64, 80, 7200, 7744}) {
+      const tc::LabelBlockPlan plan =
+          tc::plan_label_blocks(n_bin, n_labels, tc::kPairLdsBudgetKB * 1024 / 4, limit);
+      for (int block : {plan.block1, plan.block2}) {
+        tc::LabelBlocks blocks;
+        tc::build_label_blocks(sorted, n_labels, block, blocks);
+        EXPECT(blocks.n_blocks * block >= n_labels && (blocks.n_blocks - 1) * block < n_labels,
+               "%d blocks of %d labels for %d labels", blocks.n_blocks, block, n_labels);
+        const size_t stride = (size_t)blocks.n_blocks + 1;
+        for (int c = 0; c < grid.n_cells(); ++c)
+          for (int k = 0; k < blocks.n_blocks; ++k)
+            for (int32_t p = blocks.start[c * stride + k]; p < blocks.start[c * stride + k + 1]; ++p)
+              EXPECT(sorted.label[p] / block == k, "point in the wrong label block");
+      }
+    }
+  }
+}
+
 // hostmath.h: choose_fused_form over a few thousand queries, degenerate ones included (zero
 // draws, no nodes, tables without centrals or satellites, no layouts at all): a form the
 // instances exist for, an LDS footprint within the CU's, and the same answer twice.
@@ -399,6 +458,7 @@ int main() {
   check_quad();
   check_fastmath();
   check_cells();
+  check_label_block_plan();
   check_fused_form();
   if (g_failures != 0) {
     printf("%d check(s) failed\n", g_failures);
