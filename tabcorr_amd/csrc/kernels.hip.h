@@ -14,6 +14,7 @@
 #include <utility>
 
 #include "fastmath.h"
+#include "fused_walk.h"
 #include "hostmath.h"
 #include "kernel_args.h"
 #include "series.h"
@@ -2213,7 +2214,7 @@ __global__ __launch_bounds__(1024) void finalize_quad_kernel(FinalizeQuadArgs a)
 //   1. evaluates the occupations of its 64 draws (lane = draw, bins strided over the waves,
 //      occ_bin_zheng07 as in occ_zheng07_kernel) into an LDS array dens[bin][64],
 //   2. contracts: wave w takes the 32-draw tile w / 4 and quarter w % 4 of the triangle's
-//      units -- the loop of contract_quad_kernel with the density operands read from LDS (the
+//      units (the second tile's waves half a turn on: quarter (w + 2) % 4) -- the loop of contract_quad_kernel with the density operands read from LDS (the
 //      matrix still streams from the L2 through buffer loads), walked once per PAIR of r
 //      sub-tiles: 32 accumulator registers instead of 80, so that four waves per SIMD fit
 //      (two workgroups per CU: whatever phase the neighbour is in, a SIMD has two waves
@@ -2241,83 +2242,63 @@ static_assert(kFusedWaves == 8 && kFusedMaxParts == 8, "8 or 16 waves: 4 or 8 pa
 static_assert(20 * (kLanes + 1) + 20 * 21 <= fm::kTableDoubles,
               "results tile + likelihood data in the place of the math table");
 
-// One pass over `count` units from block (rb, cb) on: UU (1 or 2) r sub-tiles whose table
-// operands are the pair at lane offset off_a; F[uu][set] += ... as in contract_quad_kernel.
+// One pass over a wave's part of the units (fused_walk.h: the order of the units, and which of
+// the two operand stages a unit takes): UU (1 or 2) r sub-tiles whose table operands are the
+// pair at lane offset off_a; F[uu][set] += ... as in contract_quad_kernel.
+// (No scheduling barriers between the requests and the matrix instructions: the compiler's own
+// interleaving is 0.55 us per step ahead of loads-then-products, profiles/walk_notes.md.)
 template <int UU, int DL>
 __device__ __forceinline__ void fused_quad_pass(__amdgpu_buffer_rsrc_t rs_t, unsigned off_a,
                                                 unsigned unit_bytes, const double* dens_b,
-                                                const double* dens_e, int rb, int cb, int left,
-                                                bool triangular, int n_cb, unsigned unit_base,
+                                                const double* dens_e, const FusedPart& part,
                                                 double (&F)[2][2]) {
-  unsigned ua = (unit_base + (unsigned)(triangular ? rb * (rb + 1) / 2 + cb : rb * n_cb + cb)) *
-                unit_bytes;
-  f64x2 t0, t1, b0, b1;
+  f64x2 t[2], b[2];
   f64x4 D[UU][2];
-  auto fetch = [&](f64x2& t, f64x2& b, int column) {
-    t = buffer_load16<0>(rs_t, off_a, ua);
-    b = *(const f64x2*)(dens_b + 4 * column * DL);
-    ua += unit_bytes;
-  };
-  auto mma = [&](const f64x2& t, const f64x2& b, bool first) {
-    if (first) {
-      const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
+  f64x2 e[4];
+  fused_walk(
+      part,
+      [&](auto stage, unsigned unit, int column, bool) {
+        constexpr int kStage = decltype(stage)::value;
+        t[kStage] = buffer_load16<0>(rs_t, off_a, unit * unit_bytes);
+        b[kStage] = *(const f64x2*)(dens_b + 4 * column * DL);
+      },
+      [&](int rb) {
 #pragma unroll
-      for (int u = 0; u < UU; ++u) {
-        const double av = u ? t.y : t.x;
-        D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.x, zero, 0, 0, 0);
-        D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.y, zero, 0, 0, 0);
-      }
-    } else {
+        for (int v = 0; v < 4; ++v) e[v] = *(const f64x2*)(dens_e + (4 * rb + v) * DL);
+      },
+      [&](auto stage, bool first, int, int) {
+        constexpr int kStage = decltype(stage)::value;
+        // (the first unit of a block row starts the sums: C = 0)
+        if (first) {
+          const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-      for (int u = 0; u < UU; ++u) {
-        const double av = u ? t.y : t.x;
-        D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.x, D[u][0], 0, 0, 0);
-        D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.y, D[u][1], 0, 0, 0);
-      }
-    }
-  };
-  fetch(t0, b0, cb);
-  while (left > 0) {
-    const int row_length = triangular ? rb + 1 : n_cb;
-    const int n = row_length - cb < left ? row_length - cb : left;
-    left -= n;
-    f64x2 e[4];
+          for (int u = 0; u < UU; ++u) {
+            const double av = u ? t[kStage].y : t[kStage].x;
+            D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].x, zero, 0, 0, 0);
+            D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].y, zero, 0, 0, 0);
+          }
+        } else {
 #pragma unroll
-    for (int v = 0; v < 4; ++v) e[v] = *(const f64x2*)(dens_e + (4 * rb + v) * DL);
-    fetch(t1, b1, n > 1 ? cb + 1 : 0);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(t0, b0, true);
-    __builtin_amdgcn_sched_barrier(0);
-    int t = 1;
-    for (; t + 1 < n; t += 2) {
-      fetch(t0, b0, cb + t + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(t1, b1, false);
-      __builtin_amdgcn_sched_barrier(0);
-      fetch(t1, b1, t + 2 < n ? cb + t + 2 : 0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(t0, b0, false);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if (t < n) {
-      fetch(t0, b0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(t1, b1, false);
-      __builtin_amdgcn_sched_barrier(0);
-    } else {
-      t0 = t1;
-      b0 = b1;
-    }
+          for (int u = 0; u < UU; ++u) {
+            const double av = u ? t[kStage].y : t[kStage].x;
+            D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].x, D[u][0], 0, 0, 0);
+            D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].y, D[u][1], 0, 0, 0);
+          }
+        }
+      },
+      [&]() {
+        t[0] = t[1];
+        b[0] = b[1];
+      },
+      [&](int) {
 #pragma unroll
-    for (int u = 0; u < UU; ++u)
+        for (int u = 0; u < UU; ++u)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        F[u][0] = fma(D[u][0][v], e[v].x, F[u][0]);
-        F[u][1] = fma(D[u][1][v], e[v].y, F[u][1]);
-      }
-    ++rb;
-    cb = 0;
-  }
+          for (int v = 0; v < 4; ++v) {
+            F[u][0] = fma(D[u][0][v], e[v].x, F[u][0]);
+            F[u][1] = fma(D[u][1][v], e[v].y, F[u][1]);
+          }
+      });
 }
 
 // Inclusive prefix sum of `value` over the 64 lanes: inside the rows of 16 lanes by shifts, then
@@ -2784,6 +2765,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
   // (sub-tile, four draws) pairs per lane in either pass)
   constexpr int UA = DL == 40 ? (U > 3 ? 3 : U) : 1, UB = DL == 40 && U > 3 ? U - 3 : 1;
   double F40a[UA][10], F40b[UB][10];
+  int slot = wave;       // where the wave's sums go
   if (DL == 40) {
     const int part = wave;
     // (the unit's lane 16 k + 4 i + r for the wave's lane 16 k + 4 r + i: fused_quad_pass40)
@@ -2820,7 +2802,12 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
       fused_quad_pass40<(U > 3 ? 3 : 0), UB>(rs_t, off_a, unit_bytes, dens_b, dens_e, rb, cb,
                                              count, triangular, n_cb, first_unit, F40b);
   } else {
-    const int sub = wave / PARTS, part = wave % PARTS;
+    // (the two waves of a SIMD, w and w + 4 of eight, belong to the two tiles: the second
+    // tile's waves take the parts half a turn on, so that the pair does not reach its row ends
+    // and waits in the same cycle)
+    const int sub = wave / PARTS;
+    const int part = (wave % PARTS + sub * (PARTS / 2)) % PARTS;
+    slot = sub * PARTS + part;
     const unsigned off_a = lane * 16;
     // (the component's columns are density rows j_row0 ..., its rows i_row0 ...)
     const double* dens_b =
@@ -2828,20 +2815,17 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     const double* dens_e = dens + a.part_i_row0[part] * DL + sub * kQuadTile + 2 * c;
     const __amdgpu_buffer_rsrc_t rs_t =
         __builtin_amdgcn_make_buffer_rsrc((void*)a.table, 0, a.table_bytes, kBufferFlags);
-    const int rb = a.part_rb0[part], cb = a.part_cb0[part], count = a.part_count[part];
-    const bool triangular = a.part_triangular[part] != 0;
-    const int n_cb = a.part_n_cb[part];
-    const unsigned unit_base = (unsigned)a.part_unit_base[part];
+    const FusedPart walk = {a.part_rb0[part],        a.part_cb0[part],
+                            a.part_count[part],      a.part_triangular[part],
+                            a.part_n_cb[part],       (unsigned)a.part_unit_base[part]};
 #pragma unroll
     for (int p = 0; p < UP; ++p) {
       F[p][0][0] = F[p][0][1] = F[p][1][0] = F[p][1][1] = 0.0;
       if (skip & 2) continue;
       if (2 * p + 1 < U)
-        fused_quad_pass<2, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, rb, cb, count,
-                               triangular, n_cb, unit_base, F[p]);
+        fused_quad_pass<2, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk, F[p]);
       else
-        fused_quad_pass<1, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, rb, cb, count,
-                               triangular, n_cb, unit_base, F[p]);
+        fused_quad_pass<1, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk, F[p]);
     }
   }
   stamp(5);
@@ -2891,7 +2875,8 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     }
   } else {
     // r = 4 u + l / 16, draws 2 c and 2 c + 1 of the wave's tile
-    double* out = dens + (wave * (4 * U) + kq) * kQuadTile + 2 * c;
+    // (the slot of (tile, part): phase 3 adds a tile's parts in part order)
+    double* out = dens + (slot * (4 * U) + kq) * kQuadTile + 2 * c;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const f64x2 value = {F[u >> 1][u & 1][0], F[u >> 1][u & 1][1]};
