@@ -1,20 +1,30 @@
-// The walk of one wave of predict_fused_kernel (64-draw and 32-draw forms) over its part of a
-// component's matrix units, for host and device: kernels.hip.h (fused_quad_pass) passes the
-// loads and matrix instructions as callbacks, tests/test_fused_walk_cpu.py compiles this header
-// into a host program that records the same calls.
+// The walk of one wave over its part of a component's matrix units, for host and device.  Three
+// users in kernels.hip.h pass their loads and matrix instructions as callbacks:
+//   fused_quad_pass            predict_fused_kernel, 64 and 32 draws per workgroup
+//   contract_quad_kernel       the three-kernel path, float64: one walk per run of a wave
+//   contract_quad_f32_kernel   the same on float32 tables
+// The two contract kernels fence their consume callback (a scheduling barrier as its first and
+// as its last statement: requests, barrier, products, barrier, requests, ...); the fused one does
+// not, and leaves the interleaving to the compiler (profiles/walk_notes.md).
+// (fused_quad_pass40, the latency form of predict_fused_kernel, makes the same requests, products
+// and moves in the same order from a loop written out by hand: through this header it measured
+// 0.4 us per 10^4 draws behind, profiles/walk_notes.md section 5.)
+// tests/test_fused_walk_cpu.py compiles this header into a host program that records the same
+// calls.
 //
 // A part is `count` units of a component from block (rb0, cb0) on, row by row: block row rb of a
 // triangular component holds the block columns 0 .. rb, of a rectangular one 0 .. n_cb - 1.  The
 // units of a component lie in the table in this order, so the walk's units are consecutive:
 // unit_base + rb (rb + 1) / 2 + cb, or unit_base + rb n_cb + cb.
 //
-// The operands of a unit (16 bytes of the matrix per lane, the densities of its block column)
-// are requested one unit ahead into the other of two statically named stages, across row ends;
-// the loop of a row's units is unrolled by the two stages and every row begins in stage 0, so a
-// row with an even number of units ends with a move of the requested operands from stage 1 to
-// stage 0.  The request behind the part's last unit has no consumer: it asks for the unit behind
-// the part -- the next part's, or the one behind the table, which the bounds check of the
-// table's buffer resource answers with zeros -- with block column 0.
+// The operands of a unit (the matrix words of its lanes, the densities of its block column) are
+// requested one unit ahead into the other of two statically named stages, across row ends; the
+// loop of a row's units is unrolled by the two stages and every row begins in stage 0, so a row
+// in which the part has an odd number of units (n = 1, 3, 5, ...) ends with a move of the
+// requested operands from stage 1 to stage 0.  The request behind the part's last unit has no
+// consumer: it asks for the unit behind the part -- the next part's, or the one behind the
+// table, which the bounds check of the table's buffer resource answers with zeros -- with block
+// column 0.
 // (Deeper rings without the move were built on this header and measured: profiles/
 // walk_notes.md.)
 #pragma once

@@ -1682,7 +1682,13 @@ __global__ __launch_bounds__(512) void contract_mfma_kernel(ContractArgs a) {
 // unit) space is cut into equal contiguous ranges, one per resident wave (hostmath.h:
 // QuadSchedule), so every SIMD retires the same number of matrix instructions whatever
 // the batch size; a wave writes its sums to a slab of the partial buffer whenever it
-// leaves an output group, finalize_quad_kernel adds the slabs in fixed order.
+// leaves an output group (quad_flush, quad_merge), finalize_quad_kernel adds the slabs in fixed
+// order.
+// A run of a wave -- `count` units of one component from block (rb0, cb0) on, of one draw tile,
+// r tile and table -- is a FusedPart, walked by fused_walk (fused_walk.h: the order of the units
+// across row ends, the two operand stages requested one unit ahead, the move at a row's end, the
+// dead request behind the run); the kernel supplies the loads, the matrix instructions between
+// two scheduling barriers and the row's outer factor.
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1696,6 +1702,48 @@ __device__ inline f64x2 buffer_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned lane
                                       unsigned wave_offset) {
   return __builtin_bit_cast(
       f64x2, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane_offset + IMM, wave_offset, 0));
+}
+
+// What a wave of the two contract kernels does when it leaves an output group: its sums F (r =
+// 4 u + l / 16, the lane's TILE / 16 draws of the tile as one vector V) go to a slab of the
+// partial buffer, or to an LDS slot of the workgroup that quad_merge adds to its neighbours, and
+// start again at zero.
+template <typename V, int TILE, int U, typename T>
+__device__ __forceinline__ void quad_flush(T (&F)[U][TILE / 16], T* partial, T* stage, int slab,
+                                           int kq, int c) {
+  constexpr int N = TILE / 16;
+  T* out = slab >= 0 ? partial + ((int64_t)slab * (4 * U) + kq) * TILE + N * c
+                     : stage + ((-2 - slab) * (4 * U) + kq) * TILE + N * c;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    V value;
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      value[s] = F[u][s];
+      F[u][s] = 0;
+    }
+    *(V*)(out + (4 * u) * TILE) = value;
+  }
+}
+
+// Workgroup-level merge (hostmath.h: QuadMergePlan): the waves of a workgroup mostly end and
+// start inside the same output group; their sums are added here, in slot order, and leave as
+// ONE slab -- a third of the partial-buffer traffic of one slab per wave.
+template <typename V, int TILE, int U, typename T>
+__device__ __forceinline__ void quad_merge(T* partial, const T* stage, sc_i32 merges, int begin,
+                                           int end, int wave_in_block, int kq, int c) {
+  constexpr int N = TILE / 16;
+  for (int e = begin + wave_in_block; e < end; e += kQuadWavesPerBlock) {
+    const int slab = merges[4 * e], first = merges[4 * e + 1], count = merges[4 * e + 2];
+    T* out = partial + ((int64_t)slab * (4 * U) + kq) * TILE + N * c;
+    const T* in = stage + (first * (4 * U) + kq) * TILE + N * c;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      V sum = *(const V*)(in + (4 * u) * TILE);
+      for (int s = 1; s < count; ++s) sum += *(const V*)(in + (s * (4 * U) + 4 * u) * TILE);
+      *(V*)(out + (4 * u) * TILE) = sum;
+    }
+  }
 }
 
 template <int U, bool INTERP>
@@ -1757,121 +1805,81 @@ __global__ __launch_bounds__(64 * kQuadWavesPerBlock, 2) void contract_quad_kern
       cf = *(const __attribute__((address_space(1))) f64x2*)(
           a.coef + (int64_t)table * a.ldb + (int64_t)tile * kQuadTile + 2 * c);
 
-    int rb = rb0, cb = cb0, left = count;
-    unsigned ua = (unit_base + (unsigned)(triangular ? rb * (rb + 1) / 2 + cb : rb * n_cb + cb)) *
-                  (UP * 1024);
-    f64x2 t0[UP], t1[UP], b0, b1;
+    const FusedPart part = {rb0, cb0, count, triangular, n_cb, unit_base};
+    f64x2 t[2][UP], b[2], e[4];
     f64x4 D[U][2];
-    // Operands of the unit at table offset `ua` and block column `col`.  Unconditional
-    // (one basic block per phase keeps every prefetch where it is written); at worst a
-    // wave reads one unit nobody uses.
-    auto fetch = [&](f64x2 (&t)[UP], f64x2& b, int col) {
-      t[0] = buffer_load16<0>(rs_t, off_a, ua);
-      if (UP > 1) t[1] = buffer_load16<1024>(rs_t, off_a, ua);
-      if (UP > 2) t[2] = buffer_load16<2048>(rs_t, off_a, ua);
-      b = buffer_load16<0>(rs_n, off_b, (unsigned)(j_bin0 + 4 * col) * row_bytes);
-      ua += UP * 1024;
-    };
-    auto mma = [&](const f64x2 (&t)[UP], const f64x2& b, bool first) {
-      if (first) {
-        const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
+    fused_walk(
+        part,
+        // Operands of table unit `unit`, block column `column`.  Unconditional (one basic
+        // block per phase keeps every prefetch where it is written); at worst a wave reads
+        // one unit nobody uses.
+        [&](auto stage, unsigned unit, int column, bool) {
+          constexpr int kStage = decltype(stage)::value;
+          const unsigned ua = unit * (UP * 1024);
+          t[kStage][0] = buffer_load16<0>(rs_t, off_a, ua);
+          if constexpr (UP > 1) t[kStage][1] = buffer_load16<1024>(rs_t, off_a, ua);
+          if constexpr (UP > 2) t[kStage][2] = buffer_load16<2048>(rs_t, off_a, ua);
+          b[kStage] = buffer_load16<0>(rs_n, off_b, (unsigned)(j_bin0 + 4 * column) * row_bytes);
+        },
+        [&](int rb) {
+          if (TC_TRACE(a.stamps) && ri == run_begin && rb == rb0) {
+            // (waits for the first operands: reading them forces the loads to land)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            t_first = __builtin_amdgcn_s_memrealtime();
+            c_first = __builtin_amdgcn_s_memtime();
+          }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const double av = (u & 1) ? t[u >> 1].y : t[u >> 1].x;
-          D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.x, zero, 0, 0, 0);
-          D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.y, zero, 0, 0, 0);
-        }
-      } else {
+          for (int v = 0; v < 4; ++v)
+            e[v] = buffer_load16<0>(rs_n, off_e, (unsigned)(i_bin0 + 4 * rb + v) * row_bytes);
+        },
+        // (the scheduling barriers keep the compiler from sinking a request next to its use:
+        // the loads of unit t + 1 are in flight while unit t runs on the matrix core)
+        [&](auto stage, bool first, int, int) {
+          constexpr int kStage = decltype(stage)::value;
+          __builtin_amdgcn_sched_barrier(0);
+          if (first) {
+            const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const double av = (u & 1) ? t[u >> 1].y : t[u >> 1].x;
-          D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.x, D[u][0], 0, 0, 0);
-          D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b.y, D[u][1], 0, 0, 0);
-        }
-      }
-    };
-    fetch(t0, b0, cb);
-    if (TC_TRACE(a.stamps) && ri == run_begin) {
-      // (waits for the first operands: reading them forces the loads to land)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      t_first = __builtin_amdgcn_s_memrealtime();
-      c_first = __builtin_amdgcn_s_memtime();
-    }
-    while (left > 0) {
-      // the units of one block row inside this run: n >= 1; on entry the first one is
-      // in (t0, b0)
-      const int row_length = triangular ? rb + 1 : n_cb;
-      const int n = row_length - cb < left ? row_length - cb : left;
-      left -= n;
-      f64x2 e[4];
+            for (int u = 0; u < U; ++u) {
+              const double av = (u & 1) ? t[kStage][u >> 1].y : t[kStage][u >> 1].x;
+              D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].x, zero, 0, 0, 0);
+              D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].y, zero, 0, 0, 0);
+            }
+          } else {
 #pragma unroll
-      for (int v = 0; v < 4; ++v)
-        e[v] = buffer_load16<0>(rs_n, off_e, (unsigned)(i_bin0 + 4 * rb + v) * row_bytes);
-      // (the scheduling barriers keep the compiler from sinking a prefetch next to its
-      // use: the loads of unit t + 1 are in flight while unit t runs on the matrix core)
-      fetch(t1, b1, n > 1 ? cb + 1 : 0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(t0, b0, true);
-      __builtin_amdgcn_sched_barrier(0);
-      int t = 1;
-      for (; t + 1 < n; t += 2) {
-        fetch(t0, b0, cb + t + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(t1, b1, false);
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(t1, b1, t + 2 < n ? cb + t + 2 : 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(t0, b0, false);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (t < n) {
-        // one unit left, in (t1, b1); the next row's first unit goes to (t0, b0)
-        fetch(t0, b0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(t1, b1, false);
-        __builtin_amdgcn_sched_barrier(0);
-      } else {
-        // the next row's first unit sits in (t1, b1)
+            for (int u = 0; u < U; ++u) {
+              const double av = (u & 1) ? t[kStage][u >> 1].y : t[kStage][u >> 1].x;
+              D[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].x, D[u][0], 0, 0, 0);
+              D[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b[kStage].y, D[u][1], 0, 0, 0);
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        },
+        [&]() {
 #pragma unroll
-        for (int p = 0; p < UP; ++p) t0[p] = t1[p];
-        b0 = b1;
-      }
-      // the row's outer factor: F += D n_i (x the table's spline weight)
-      if (interp) {
+          for (int p = 0; p < UP; ++p) t[0][p] = t[1][p];
+          b[0] = b[1];
+        },
+        // the row's outer factor: F += D n_i (x the table's spline weight)
+        [&](int) {
+          if (interp) {
 #pragma unroll
-        for (int v = 0; v < 4; ++v) e[v] *= cf;
-      }
+            for (int v = 0; v < 4; ++v) e[v] *= cf;
+          }
 #pragma unroll
-      for (int u = 0; u < U; ++u)
+          for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          F[u][0] = fma(D[u][0][v], e[v].x, F[u][0]);
-          F[u][1] = fma(D[u][1][v], e[v].y, F[u][1]);
-        }
-      ++rb;
-      cb = 0;
-    }
+            for (int v = 0; v < 4; ++v) {
+              F[u][0] = fma(D[u][0][v], e[v].x, F[u][0]);
+              F[u][1] = fma(D[u][1][v], e[v].y, F[u][1]);
+            }
+        });
     if (TC_TRACE(a.stamps)) {
       t_main = __builtin_amdgcn_s_memrealtime();
       c_main = __builtin_amdgcn_s_memtime();
     }
-    if (slab != -1) {
-      // r = 4 u + l / 16, draws 2 c and 2 c + 1 of the tile: to a slab of the partial buffer,
-      // or to an LDS slot of the workgroup that is merged with its neighbours below
-      double* out = slab >= 0
-                        ? (double*)a.partial + ((int64_t)slab * (4 * U) + kq) * kQuadTile + 2 * c
-                        : stage + ((-2 - slab) * (4 * U) + kq) * kQuadTile + 2 * c;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const f64x2 value = {F[u][0], F[u][1]};
-        *(f64x2*)(out + (4 * u) * kQuadTile) = value;
-        F[u][0] = F[u][1] = 0.0;
-      }
-    }
+    if (slab != -1) quad_flush<f64x2, kQuadTile>(F, (double*)a.partial, stage, slab, kq, c);
   }
-  // Workgroup-level merge (hostmath.h: QuadMergePlan): the waves of a workgroup mostly end
-  // and start inside the same output group; their sums are added here, in slot order, and
-  // leave as ONE slab -- a third of the partial-buffer traffic of one slab per wave.
   if (TC_TRACE(a.stamps)) t_flushed = __builtin_amdgcn_s_memrealtime();
   auto write_stamps = [&]() {
     if (TC_TRACE(a.stamps) && lane == 0 && wave < a.n_waves) {
@@ -1891,19 +1899,8 @@ __global__ __launch_bounds__(64 * kQuadWavesPerBlock, 2) void contract_quad_kern
     return;
   }
   __syncthreads();
-  sc_i32 merges = (sc_i32)a.merges;
-  for (int e = merge_begin + wave_in_block; e < merge_end; e += kQuadWavesPerBlock) {
-    const int slab = merges[4 * e], first = merges[4 * e + 1], count = merges[4 * e + 2];
-    double* out = (double*)a.partial + ((int64_t)slab * (4 * U) + kq) * kQuadTile + 2 * c;
-    const double* in = stage + (first * (4 * U) + kq) * kQuadTile + 2 * c;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      f64x2 sum = *(const f64x2*)(in + (4 * u) * kQuadTile);
-      for (int s = 1; s < count; ++s)
-        sum += *(const f64x2*)(in + (s * (4 * U) + 4 * u) * kQuadTile);
-      *(f64x2*)(out + (4 * u) * kQuadTile) = sum;
-    }
-  }
+  quad_merge<f64x2, kQuadTile, U>((double*)a.partial, stage, (sc_i32)a.merges, merge_begin,
+                                  merge_end, wave_in_block, kq, c);
   write_stamps();
 }
 
@@ -1917,7 +1914,8 @@ __global__ __launch_bounds__(64 * kQuadWavesPerBlock, 2) void contract_quad_kern
 // column sets: draws 4 c + s of its tile, one 16-byte density load per lane serves all four)
 // and an r tile holds 16 values (four sub-tiles in ONE 16-byte table load per lane): 16
 // matrix instructions per two loads.  Densities arrive as floats (the occupation kernel
-// writes a float copy), sums stay in float, slabs are (4 U, 64) floats.
+// writes a float copy), sums stay in float, slabs are (4 U, 64) floats.  The runs are walked by
+// fused_walk with fenced products, flushed and merged by quad_flush / quad_merge, as in float64.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int IMM>
@@ -1978,102 +1976,59 @@ __global__ __launch_bounds__(64 * kQuadWavesPerBlock, 2) void contract_quad_f32_
     const __amdgpu_buffer_rsrc_t rs_t =
         __builtin_amdgcn_make_buffer_rsrc((void*)matrix, 0, a.rtile_bytes, kBufferFlags);
 
-    int rb = rb0, cb = cb0, left = count;
-    unsigned ua = (unit_base + (unsigned)(triangular ? rb * (rb + 1) / 2 + cb : rb * n_cb + cb)) *
-                  1024u;
-    f32x4 t0, t1, b0, b1;
+    const FusedPart part = {rb0, cb0, count, triangular, n_cb, unit_base};
+    f32x4 t[2], b[2], e[4];
     f32x4 D[U][4];
-    auto fetch = [&](f32x4& t, f32x4& b, int col) {
-      t = buffer_load16f<0>(rs_t, off_a, ua);
-      b = buffer_load16f<0>(rs_n, off_b, (unsigned)(j_bin0 + 4 * col) * row_bytes);
-      ua += 1024u;
-    };
-    auto mma = [&](const f32x4& t, const f32x4& b, bool first) {
-      const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    fused_walk(
+        part,
+        [&](auto stage, unsigned unit, int column, bool) {
+          constexpr int kStage = decltype(stage)::value;
+          t[kStage] = buffer_load16f<0>(rs_t, off_a, unit * 1024u);
+          b[kStage] = buffer_load16f<0>(rs_n, off_b, (unsigned)(j_bin0 + 4 * column) * row_bytes);
+        },
+        [&](int rb) {
 #pragma unroll
-      for (int u = 0; u < U; ++u)
+          for (int v = 0; v < 4; ++v)
+            e[v] = buffer_load16f<0>(rs_n, off_e, (unsigned)(i_bin0 + 4 * rb + v) * row_bytes);
+        },
+        // (fenced, as in contract_quad_kernel)
+        [&](auto stage, bool first, int, int) {
+          constexpr int kStage = decltype(stage)::value;
+          const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-          D[u][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(t[u], b[s], first ? zero : D[u][s], 0, 0, 0);
-    };
-    fetch(t0, b0, cb);
-    while (left > 0) {
-      const int row_length = triangular ? rb + 1 : n_cb;
-      const int n = row_length - cb < left ? row_length - cb : left;
-      left -= n;
-      f32x4 e[4];
+          for (int u = 0; u < U; ++u)
 #pragma unroll
-      for (int v = 0; v < 4; ++v)
-        e[v] = buffer_load16f<0>(rs_n, off_e, (unsigned)(i_bin0 + 4 * rb + v) * row_bytes);
-      fetch(t1, b1, n > 1 ? cb + 1 : 0);
-      __builtin_amdgcn_sched_barrier(0);
-      mma(t0, b0, true);
-      __builtin_amdgcn_sched_barrier(0);
-      int t = 1;
-      for (; t + 1 < n; t += 2) {
-        fetch(t0, b0, cb + t + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(t1, b1, false);
-        __builtin_amdgcn_sched_barrier(0);
-        fetch(t1, b1, t + 2 < n ? cb + t + 2 : 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(t0, b0, false);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (t < n) {
-        fetch(t0, b0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(t1, b1, false);
-        __builtin_amdgcn_sched_barrier(0);
-      } else {
-        t0 = t1;
-        b0 = b1;
-      }
-      // the row's outer factor: F += D n_i (x the table's spline weight)
-      if (interp) {
+            for (int s = 0; s < 4; ++s)
+              D[u][s] = __builtin_amdgcn_mfma_f32_16x16x4f32(t[kStage][u], b[kStage][s],
+                                                             first ? zero : D[u][s], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        },
+        [&]() {
+          t[0] = t[1];
+          b[0] = b[1];
+        },
+        // the row's outer factor: F += D n_i (x the table's spline weight)
+        [&](int) {
+          if (interp) {
 #pragma unroll
-        for (int v = 0; v < 4; ++v) e[v] *= cf;
-      }
+            for (int v = 0; v < 4; ++v) e[v] *= cf;
+          }
 #pragma unroll
-      for (int u = 0; u < U; ++u)
+          for (int u = 0; u < U; ++u)
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
+            for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int v = 0; v < 4; ++v) F[u][s] = fmaf(D[u][s][v], e[v][s], F[u][s]);
-      ++rb;
-      cb = 0;
-    }
-    if (slab != -1) {
-      // r = 4 u + l / 16, draws 4 c .. 4 c + 3 of the tile
-      float* out = slab >= 0
-                       ? (float*)a.partial + ((int64_t)slab * (4 * U) + kq) * kQuadTileF32 + 4 * c
-                       : stage32 + ((-2 - slab) * (4 * U) + kq) * kQuadTileF32 + 4 * c;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const f32x4 value = {F[u][0], F[u][1], F[u][2], F[u][3]};
-        *(f32x4*)(out + (4 * u) * kQuadTileF32) = value;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) F[u][s] = 0.0f;
-      }
-    }
+              for (int v = 0; v < 4; ++v) F[u][s] = fmaf(D[u][s][v], e[v][s], F[u][s]);
+        });
+    if (slab != -1) quad_flush<f32x4, kQuadTileF32>(F, (float*)a.partial, stage32, slab, kq, c);
   }
   sc_i32 merge_range = (sc_i32)a.merge_range;
   const int merge_begin = merge_range[2 * blockIdx.x], merge_end = merge_range[2 * blockIdx.x + 1];
   if (merge_begin == merge_end) return;          // (uniform over the workgroup)
   __syncthreads();
-  sc_i32 merges = (sc_i32)a.merges;
-  for (int e = merge_begin + wave_in_block; e < merge_end; e += kQuadWavesPerBlock) {
-    const int slab = merges[4 * e], first = merges[4 * e + 1], n_slots = merges[4 * e + 2];
-    float* out = (float*)a.partial + ((int64_t)slab * (4 * U) + kq) * kQuadTileF32 + 4 * c;
-    const float* in = stage32 + (first * (4 * U) + kq) * kQuadTileF32 + 4 * c;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      f32x4 sum = *(const f32x4*)(in + (4 * u) * kQuadTileF32);
-      for (int s = 1; s < n_slots; ++s)
-        sum += *(const f32x4*)(in + (s * (4 * U) + 4 * u) * kQuadTileF32);
-      *(f32x4*)(out + (4 * u) * kQuadTileF32) = sum;
-    }
-  }
+  quad_merge<f32x4, kQuadTileF32, U>((float*)a.partial, stage32, (sc_i32)a.merges, merge_begin,
+                                     merge_end, wave_in_block, kq, c);
 }
 
 // Sums the slabs of every output group in slab order, normalises and writes the results
@@ -2337,6 +2292,10 @@ __device__ __forceinline__ double fused_quad_rows40(double select, double value,
 // mfma_map.hip), which times dens[4 rb + i][4 dg + j] is the lane's share of F[r][draw]: the four
 // i of a (r, j) -- lanes 16 apart, the k index of a B operand -- are added once, after the walk,
 // on the matrix pipe as well (fused_quad_rows40: A = a row of ones).  F[s][dg] += ... per lane.
+// (The loop below is fused_walk's schedule written out by hand, its first two units peeled
+// differently: the same requests, products and moves in the same order.  As callbacks of
+// fused_walk the pass measured 0.4 us per 10^4 draws behind this loop -- the requested operands
+// were copied at the row ends behind a full wait --, so it stays: profiles/walk_notes.md.)
 template <int S0, int NS>
 __device__ __forceinline__ void fused_quad_pass40(__amdgpu_buffer_rsrc_t rs_t, unsigned off_a,
                                                   unsigned unit_bytes, const double* dens_b,

@@ -1,7 +1,7 @@
-"""csrc/fused_walk.h -- the walk of a wave of predict_fused_kernel over its part of the matrix
-units, and the ring of operand stages it keeps ahead of itself -- stepped through on the host:
-tests/fused_walk_host.cpp compiles the header the kernel includes into a program that prints
-the callbacks' calls.  No device.
+"""csrc/fused_walk.h -- the walk of a wave of predict_fused_kernel, contract_quad_kernel or
+contract_quad_f32_kernel over its part of the matrix units, and the ring of operand stages it
+keeps ahead of itself -- stepped through on the host: tests/fused_walk_host.cpp compiles the
+header the kernels include into a program that prints the callbacks' calls.  No device.
 
 (The program stands alone: `c++ -std=c++17 -fsanitize=address,undefined -I tabcorr_amd/csrc
 tests/fused_walk_host.cpp` and the parts on its standard input check it under the sanitizers.)
@@ -58,17 +58,38 @@ def rectangle_parts(n_rb, n_cb, n_parts):
     return parts
 
 
+def every_cut(triangular, n_rb, n_cb):
+    """hostmath.h: QuadSchedule gives every resident wave an equal contiguous range of the unit
+    space, so a run of contract_quad_kernel starts and ends anywhere in a row and can span a
+    whole component: every (first unit, count >= 1) of the component."""
+    blocks = [(rb, cb) for rb in range(n_rb) for cb in range(rb + 1 if triangular else n_cb)]
+    return [blocks[first] + (count, ) for first in range(len(blocks))
+            for count in range(1, len(blocks) - first + 1)]
+
+
+BASES = ((0, 0), (7, 0), (3, 40))         # (unit_base, units behind the component)
+
+
 def all_parts():
     """(rb0, cb0, count, triangular, n_cb, unit_base, table_units) of every case: the component
     alone in its table, last in a longer one, and followed by others."""
     out = []
+    shapes = [(1, n_rb, n_rb, n_rb * (n_rb + 1) // 2, every_cut(1, n_rb, n_rb))
+              for n_rb in (1, 2, 3, 4, 5)]
+    shapes += [(0, n_rb, n_cb, n_rb * n_cb, every_cut(0, n_rb, n_cb))
+               for n_rb, n_cb in ((3, 1), (2, 7), (3, 4))]
+    for triangular, n_rb, n_cb, n_units, parts in shapes:
+        for unit_base, behind in BASES:
+            for rb0, cb0, count in parts:
+                out.append((rb0, cb0, count, triangular, n_cb, unit_base,
+                            unit_base + n_units + behind))
     for n_parts in (4, 8, 16):
         shapes = [(1, n_rb, n_rb, n_rb * (n_rb + 1) // 2, triangle_parts(n_rb, n_parts))
                   for n_rb in (1, 2, 3, 5, 9, 25)]
         shapes += [(0, n_rb, n_cb, n_rb * n_cb, rectangle_parts(n_rb, n_cb, n_parts))
                    for n_rb, n_cb in ((1, 1), (1, 13), (13, 12))]
         for triangular, n_rb, n_cb, n_units, parts in shapes:
-            for unit_base, behind in ((0, 0), (7, 0), (3, 40)):
+            for unit_base, behind in BASES:
                 for rb0, cb0, count in parts:
                     out.append((rb0, cb0, count, triangular, n_cb, unit_base,
                                 unit_base + n_units + behind))
@@ -178,6 +199,9 @@ def test_walk_visits_the_parents_units_through_the_ring(program):
     assert {0, 1, 2, 3} <= {p[2] for p in parts}
     assert any(p[1] > 0 and p[2] > 1 for p in parts), 'a part that starts inside a row'
     assert any(p[3] and p[0] == 0 and p[2] >= 3 for p in parts), 'rows of one unit'
+    # ... and every cut of the quadratic-form schedule's small components
+    assert {(0, 0, 15, 1, 5), (4, 4, 1, 1, 5), (1, 6, 1, 0, 7), (0, 3, 9, 0, 4)} <= {
+        p[:5] for p in parts}
     depth, logs = run(program, parts)
     assert depth == 2
     for part, log in zip(parts, logs):
