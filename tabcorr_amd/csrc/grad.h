@@ -3,7 +3,7 @@
 // strengths (`n_params` = 5 or 7 below, a template parameter of the kernels) --: the
 // argument block of the gradient kernels (grad_kernels.hip.h), their LDS budget and the dense
 // matrix-operand layout of a mode-auto table.  Plain C++ for the host-only units that fill these
-// in, but for spline_weights, which hipcc also compiles for the device.
+// in (spline.h, which it includes, is compiled for the device too).
 //
 // With w = n_h <N> and S_r the symmetric matrix of one r bin, q_r = w^T S_r w and
 // dq_r / dtheta_k = 2 (dw / dtheta_k)^T (S_r w): ONE dense product U_r = S_r W per tile of draws
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kernel_args.h"
+#include "spline.h"
 
 namespace tc {
 
@@ -119,34 +120,7 @@ inline void build_grad_operand(int n_bins, int n_r, const double* packed,
 // spline weight of table t, d/dtheta_k = sum_t c_t d(ngal_t, xi_t)/dtheta_k and d/dx_d =
 // sum_t (dc_t/dx_d) (ngal_t, xi_t).  One launch per batch walks the tables class by class.
 
-#if defined(__HIPCC__)
-#define TC_GRAD_HOST_DEVICE __host__ __device__
-#else
-#define TC_GRAD_HOST_DEVICE
-#endif
-
-// Weights of one axis: the spline through (xp, y) at x is sum_j weight[j] y[j] and its derivative
-// sum_j dweight[j] y[j], for the nodes j = first, first + step, ... < n, stored `stride` doubles
-// apart.  `a`: the (n - 1, 4, n) matrix of spline_interpolation_matrix.  Segment as
-// interpolator.py:275-331: np.digitize with the right edge special-cased, clamped to the outermost
-// segments -- an x beyond the grid gets that segment's polynomial and its derivative.  Returns
-// the segment.
-TC_GRAD_HOST_DEVICE inline int spline_weights(int n, const double* xp, const double* a,
-                                              double x, int first, int step, int stride,
-                                              double* weight, double* dweight) {
-  int seg = -1;
-  for (int i = 0; i < n; ++i) seg += xp[i] <= x ? 1 : 0;   // np.digitize(x, xp) - 1
-  if (x == xp[n - 1]) seg = n - 2;
-  seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
-  const double* m = a + (size_t)seg * 4 * n;
-  const double x2 = x * x, x3 = x2 * x;
-  for (int j = first; j < n; j += step) {
-    weight[(size_t)j * stride] = m[j] + m[n + j] * x + m[2 * n + j] * x2 + m[3 * n + j] * x3;
-    dweight[(size_t)j * stride] = m[n + j] + 2.0 * m[2 * n + j] * x + 3.0 * m[3 * n + j] * x2;
-  }
-  return seg;
-}
-#undef TC_GRAD_HOST_DEVICE
+// (the spline weights c_t and dc_t/dx_d of an axis: spline.h: spline_weights)
 
 // what tc_interp_create admits (kernel_args.h) sizes the argument arrays and the weight rows
 constexpr int kGradMaxDim = kMaxInterpDim;

@@ -2,6 +2,7 @@
 // interpolation over a grid of tables, evaluated as one contraction over all tables
 // (tabcorr/interpolator.py:136-219).
 #include "internal.h"
+#include "spline.h"
 
 using namespace tc::host;
 
@@ -707,14 +708,10 @@ int interp_predict_one(tc_interp* it, const double* theta, int n_theta, const do
     const std::vector<double>& xp = it->xp[d];
     const int n = (int)xp.size();
     const double xv = x[d];
-    int seg = -1;
-    for (int i = 0; i < n; ++i) seg += xp[i] <= xv ? 1 : 0;   // np.digitize(x, xp) - 1
-    if (xv == xp[n - 1]) seg = n - 2;
-    seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
-    const double* m = it->a_host.data() + it->a_offset[d] + (size_t)seg * 4 * n;
+    const double* m = it->a_host.data() + it->a_offset[d] +
+                      (size_t)tc::spline_segment(n, xp.data(), xv) * 4 * n;
     const double x2 = xv * xv, x3 = x2 * xv;
-    for (int j = 0; j < n; ++j)
-      weight[d][j] = m[j] + m[n + j] * xv + m[2 * n + j] * x2 + m[3 * n + j] * x3;
+    for (int j = 0; j < n; ++j) weight[d][j] = tc::spline_node_weight(n, m, j, xv, x2, x3);
   }
   status = wait_single_done(&workspace, it->stream, t0->tuning.poll_done != 0);
   if (status != TC_OK) return status;

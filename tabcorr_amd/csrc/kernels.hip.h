@@ -13,11 +13,13 @@
 #include <cstdint>
 #include <utility>
 
+#include "epilogue.h"
 #include "fastmath.h"
 #include "fused_walk.h"
 #include "hostmath.h"
 #include "kernel_args.h"
 #include "series.h"
+#include "spline.h"
 
 // Developer timelines (per-workgroup / per-wave time stamps behind tc_table_set_option
 // "trace") exist only in developer builds (-DTC_DEVELOPER_KNOBS, tools/build_dev.sh); the
@@ -2036,52 +2038,8 @@ __global__ __launch_bounds__(64 * kQuadWavesPerBlock, 2) void contract_quad_f32_
 // One block per 64 draws (two 32-draw tiles, each with its own slab lists).
 template <typename P, int TILE>
 __global__ __launch_bounds__(1024) void finalize_quad_kernel(FinalizeQuadArgs a) {
-  __shared__ double tile[kFinalizeRows][kLanes + 1];
-  __shared__ double part_sum[16][kLanes];
-  __shared__ double norm_inv[kLanes];
-  // fused likelihood: the data vector and the weight matrix, staged once per workgroup
-  __shared__ double chi2_lds[kFinalizeRows * (kFinalizeRows + 1)];
   set_priority(a.priority);
-  if (a.chi2 != nullptr) {
-    const int count = a.n_r * (a.n_r + 1);
-    for (int idx = threadIdx.x; idx < count; idx += blockDim.x) chi2_lds[idx] = a.chi2_data[idx];
-  }
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t col = (int64_t)blockIdx.x * kLanes;
-  const int64_t n_valid = a.n_draws - col < kLanes ? a.n_draws - col : kLanes;
-
-  if (wave == 0 && a.ngal_part == nullptr) norm_inv[lane] = 1.0;
-  if (wave == 0 && a.ngal_part != nullptr) {
-    double n_cen = 0.0, n_sat = 0.0;
-    for (int p = 0; p < a.n_ngal_parts; ++p) {
-      n_cen += a.ngal_part[((int64_t)p * 2 + 0) * a.ldb + col + lane];
-      n_sat += a.ngal_part[((int64_t)p * 2 + 1) * a.ldb + col + lane];
-    }
-    const double total = n_cen + n_sat;
-    norm_inv[lane] = a.mode == 0 ? total * total : total;
-    if (lane < n_valid && blockIdx.y == 0) {
-      if (a.n_comp == 1) {
-        a.ngal[col + lane] = total;
-      } else {
-        a.ngal[2 * (col + lane)] = n_cen;
-        a.ngal[2 * (col + lane) + 1] = n_sat;
-      }
-    }
-  }
-  __syncthreads();
-  const double norm = norm_inv[lane];
-  // Separated by galaxy type the reference forms every term / sum first and masks
-  // afterwards (tabcorr.py:653-681): with a non-finite sum some term is inf / inf = NaN
-  // and NaN x False = NaN reaches every component.
-  const bool poisoned = a.n_comp > 1 && !(fabs(norm) <= 1.79769313486231570815e308);
-  auto normalise = [&](double sum) { return poisoned ? __builtin_nan("") : sum / norm; };
-
-  const int n_rows = a.n_comp * a.n_r;
-  const int n_waves = blockDim.x >> 6;
-  const int rows_per_block = (n_rows + gridDim.y - 1) / gridDim.y;
-  const int row_begin = blockIdx.y * rows_per_block;
-  const int row_end = row_begin + rows_per_block < n_rows ? row_begin + rows_per_block : n_rows;
   // (a block serves 64 draws: two tiles of 32, or one of 64)
   const int64_t tile32 = TILE == 32 ? (int64_t)blockIdx.x * 2 + (lane >> 5) : (int64_t)blockIdx.x;
   const int64_t slab_stride = (int64_t)a.rt * TILE;
@@ -2107,55 +2065,9 @@ __global__ __launch_bounds__(1024) void finalize_quad_kernel(FinalizeQuadArgs a)
     }
     return sum;
   };
-  for (int row0 = row_begin; row0 < row_end; row0 += kFinalizeRows) {
-    const int rows = row_end - row0 < kFinalizeRows ? row_end - row0 : kFinalizeRows;
-    if (rows * 2 <= n_waves) {
-      // few rows (small batches, split over row blocks; an un-batched interpolator call
-      // leaves ~1000 slabs per row): several waves per row, each over a contiguous range
-      // of slabs, combined in fixed order
-      const int parts = n_waves / rows;
-      const int rr = wave / parts, part = wave % parts;
-      if (rr < rows) part_sum[wave][lane] = sum_slabs(row0 + rr, part, parts);
-      __syncthreads();
-      if (wave < rows) {
-        double sum = 0.0;
-        for (int p = 0; p < parts; ++p) sum += part_sum[wave * parts + p][lane];
-        tile[wave][lane] = normalise(sum);
-      }
-    } else {
-      for (int rr = wave; rr < rows; rr += n_waves)
-        tile[rr][lane] = normalise(sum_slabs(row0 + rr, 0, 1));
-    }
-    __syncthreads();
-    if (a.chi2 != nullptr) {
-      // (host side: every row of the draws is in `tile` now -- one pass, one row block)
-      // wave w sums the rows i = w, w + n_waves, ... of delta_i (P delta)_i for its lane's
-      // draw; the matrix from LDS (every lane reads the same word: a broadcast)
-      const double* data = chi2_lds;
-      const double* matrix = chi2_lds + rows;
-      double part = 0.0;
-      for (int i = wave; i < rows; i += n_waves) {
-        double inner = 0.0;
-        for (int j = 0; j < rows; ++j)
-          inner = fma(matrix[i * rows + j], tile[j][lane] - data[j], inner);
-        part = fma(tile[i][lane] - data[i], inner, part);
-      }
-      part_sum[wave][lane] = part;
-      __syncthreads();
-      if (wave == 0 && lane < n_valid) {
-        double total = 0.0;
-        for (int w = 0; w < n_waves; ++w) total += part_sum[w][lane];
-        a.chi2[col + lane] = total;
-      }
-      __syncthreads();
-      continue;
-    }
-    for (int idx = threadIdx.x; idx < rows * kLanes; idx += blockDim.x) {
-      const int d = idx / rows, rr = idx % rows;
-      if (d < n_valid) a.xi[(col + d) * (int64_t)n_rows + row0 + rr] = tile[rr][d];
-    }
-    __syncthreads();
-  }
+  finalize_body<true>(a, sum_slabs, [](double sum, double norm, bool poisoned) {
+    return poisoned ? __builtin_nan("") : sum / norm;
+  });
 }
 
 // ---- one launch per batch: theta -> (ngal, xi[, chi2]) inside a workgroup ------------------
@@ -2902,7 +2814,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
   stamp(6);
   const int64_t n_valid = a.n_draws - col < DL ? a.n_draws - col : DL;
   if (a.chi2 != nullptr) {
-    // chi2 = delta^T P delta for the lane's draw (finalize_quad_kernel's fused likelihood)
+    // chi2 = delta^T P delta for the lane's draw (as epilogue.h: finalize_body)
     const int rows = a.n_r;
     const double* data = chi2_lds;
     const double* matrix = chi2_lds + rows;
@@ -3168,12 +3080,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, RW <= 8 ? 4 : 2) void predict_cro
   set_priority(a.priority & 3);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  {
-    typedef double __attribute__((ext_vector_type(2))) double2v;
-    const double2v* src = (const double2v*)a.math_table;
-    double2v* dst = (double2v*)table;
-    for (int i = threadIdx.x; i < fm::kTableDoubles / 2; i += blockDim.x) dst[i] = src[i];
-  }
+  stage_math_table(table, a.math_table);
   // (the deferred pairs: instances of their own -- undecorated, up to 64 rows)
   static_assert(!DEFER || (!ASSEMBIAS && !MODULATE && ROWS <= 64), "deferred pairs");
   constexpr bool kDeferrable = DEFER;
@@ -3414,16 +3321,11 @@ __global__ __launch_bounds__(64 * kCrossWaves, RW <= 8 ? 4 : 2) void predict_cro
       if (a.interp) {
         for (int dim = 0; dim < a.n_dim; ++dim) {
           const int n = a.n_axis[dim];
-          const double* xp = a.xp + a.axis_offset[dim];
           const double x = a.x[b_end * a.n_dim + dim];
-          int seg = -1;
-          for (int i = 0; i < n; ++i) seg += xp[i] <= x ? 1 : 0;   // np.digitize(x, xp) - 1
-          if (x == xp[n - 1]) seg = n - 2;
-          seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
+          const int seg = spline_segment(n, a.xp + a.axis_offset[dim], x);
           const double* m = a.a + a.a_offset[dim] + (int64_t)seg * 4 * n;
-          const int j = a.table_node[k * a.n_dim + dim];
           const double x2 = x * x, x3 = x2 * x;
-          c *= m[j] + m[n + j] * x + m[2 * n + j] * x2 + m[3 * n + j] * x3;
+          c *= spline_node_weight(n, m, a.table_node[k * a.n_dim + dim], x, x2, x3);
         }
       }
       const double cen = res0[(k * per_table + a.n_r) * kLanes + lane];
@@ -3459,7 +3361,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, RW <= 8 ? 4 : 2) void predict_cro
   __syncthreads();
   const int64_t n_valid = a.n_draws - col < kLanes ? a.n_draws - col : kLanes;
   if (a.chi2 != nullptr) {
-    // chi2 = delta^T P delta for the lane's draw (total prediction; finalize_quad_kernel)
+    // chi2 = delta^T P delta for the lane's draw (total prediction; as epilogue.h: finalize_body)
     const int rows_r = a.n_r;
     const double* data = a.chi2_data;
     const double* matrix = a.chi2_data + rows_r;
@@ -3479,10 +3381,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, RW <= 8 ? 4 : 2) void predict_cro
     }
     return;
   }
-  for (int idx = threadIdx.x; idx < n_rows * kLanes; idx += blockDim.x) {
-    const int dd = idx / n_rows, row = idx % n_rows;
-    if (dd < n_valid) a.xi[(col + dd) * (int64_t)n_rows + row] = tile[row * (kLanes + 1) + dd];
-  }
+  tile_write_xi(tile, n_rows, kLanes, n_valid, a.xi + col * (int64_t)n_rows, n_rows, 0);
   stamp(6);
 #ifdef TC_DEVELOPER_KNOBS
   if (stamps != nullptr && threadIdx.x == 0) {
@@ -3680,16 +3579,11 @@ __global__ __launch_bounds__(64 * kCrossWaves, DEFER ? 4 : 2) void predict_cross
       if (a.interp) {
         for (int dim = 0; dim < a.n_dim; ++dim) {
           const int n = a.n_axis[dim];
-          const double* xp = a.xp + a.axis_offset[dim];
           const double x = a.x[b_end * a.n_dim + dim];
-          int seg = -1;
-          for (int i = 0; i < n; ++i) seg += xp[i] <= x ? 1 : 0;   // np.digitize(x, xp) - 1
-          if (x == xp[n - 1]) seg = n - 2;
-          seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
+          const int seg = spline_segment(n, a.xp + a.axis_offset[dim], x);
           const double* m = a.a + a.a_offset[dim] + (int64_t)seg * 4 * n;
-          const int j = a.table_node[k * a.n_dim + dim];
           const double x2 = x * x, x3 = x2 * x;
-          c *= m[j] + m[n + j] * x + m[2 * n + j] * x2 + m[3 * n + j] * x3;
+          c *= spline_node_weight(n, m, a.table_node[k * a.n_dim + dim], x, x2, x3);
         }
       }
       const double cen = res[(k * per_table + a.n_r) * kLanes + lane];
@@ -3724,7 +3618,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, DEFER ? 4 : 2) void predict_cross
   __syncthreads();
   const int64_t n_valid = a.n_draws - col < kLanes ? a.n_draws - col : kLanes;
   if (a.chi2 != nullptr) {
-    // chi2 = delta^T P delta for the lane's draw (total prediction; finalize_quad_kernel)
+    // chi2 = delta^T P delta for the lane's draw (total prediction; as epilogue.h: finalize_body)
     const int rows_r = a.n_r;
     const double* data = a.chi2_data;
     const double* matrix = a.chi2_data + rows_r;
@@ -3744,10 +3638,7 @@ __global__ __launch_bounds__(64 * kCrossWaves, DEFER ? 4 : 2) void predict_cross
     }
     return;
   }
-  for (int idx = threadIdx.x; idx < n_rows * kLanes; idx += blockDim.x) {
-    const int dd = idx / n_rows, row = idx % n_rows;
-    if (dd < n_valid) a.xi[(col + dd) * (int64_t)n_rows + row] = tile[row * (kLanes + 1) + dd];
-  }
+  tile_write_xi(tile, n_rows, kLanes, n_valid, a.xi + col * (int64_t)n_rows, n_rows, 0);
 }
 
 // ---- un-batched predict(): one draw, one launch ---------------------------------------
@@ -3819,12 +3710,7 @@ __device__ __forceinline__ void single_draw_body(SingleArgs a) {
     a.ngal += 2 * walker;
     a.partial += (int64_t)walker * a.blocks_per_table * a.rt;
   }
-  {
-    typedef double __attribute__((ext_vector_type(2))) double2v;
-    const double2v* src = (const double2v*)a.math_table;
-    double2v* dst = (double2v*)table;
-    for (int i = tid; i < fm::kTableDoubles / 2; i += kSingleThreads) dst[i] = src[i];
-  }
+  stage_math_table(table, a.math_table, tid, kSingleThreads);
   __syncthreads();
   stamp(1);
   // Resident form: the rest of the body once per call, the calls taken from the mailbox.
@@ -4156,12 +4042,7 @@ static __global__ __launch_bounds__(kEnsembleThreads) void resident_ensemble_ker
   const int n_nodes = a.n_bins * a.n_gauss;
 
   // once per launch: the math tables, this slice's positions, this thread's two nodes
-  {
-    typedef double __attribute__((ext_vector_type(2))) double2v;
-    const double2v* src = (const double2v*)a.math_table;
-    double2v* dst = (double2v*)table;
-    for (int i = tid; i < fm::kTableDoubles / 2; i += kEnsembleThreads) dst[i] = src[i];
-  }
+  stage_math_table(table, a.math_table, tid, kEnsembleThreads);
   const int64_t slice_begin = (int64_t)slice * 4 * pq;
   for (int idx = tid; idx < 4 * pq * 32; idx += kEnsembleThreads) {
     const int pl = idx >> 5, r = idx & 31;
@@ -4779,51 +4660,16 @@ __global__ __launch_bounds__(512) void contract_f32_kernel(ContractArgs a) {
 // goes through LDS.
 #ifdef TC_UNIT_QUAD   // (emitted by the unit that launches it, which defines the macro)
 static __global__ __launch_bounds__(1024) void finalize_kernel(FinalizeArgs a) {
-  __shared__ double tile[kFinalizeRows][kLanes + 1];
-  __shared__ double part_sum[16][kLanes];
-  __shared__ double norm_inv[kLanes];
   __builtin_amdgcn_s_setprio(3);
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t col = (int64_t)blockIdx.x * kLanes;
-  const int64_t n_valid = a.n_draws - col < kLanes ? a.n_draws - col : kLanes;
-
-  if (wave == 0 && a.ngal_part == nullptr) norm_inv[lane] = 1.0;
-  if (wave == 0 && a.ngal_part != nullptr) {
-    double n_cen = 0.0, n_sat = 0.0;
-    for (int p = 0; p < a.n_ngal_parts; ++p) {
-      n_cen += a.ngal_part[((int64_t)p * 2 + 0) * a.ldb + col + lane];
-      n_sat += a.ngal_part[((int64_t)p * 2 + 1) * a.ldb + col + lane];
-    }
-    const double total = n_cen + n_sat;
-    norm_inv[lane] = a.mode == 0 ? total * total : total;
-    if (lane < n_valid && blockIdx.y == 0) {
-      if (a.n_comp == 1) {
-        a.ngal[col + lane] = total;
-      } else {
-        a.ngal[2 * (col + lane)] = n_cen;
-        a.ngal[2 * (col + lane) + 1] = n_sat;
-      }
-    }
-  }
-  __syncthreads();
-  // (separated by galaxy type a non-finite sum poisons every component: see
-  // finalize_quad_kernel)
-  const double norm = a.n_comp > 1 && !(fabs(norm_inv[lane]) <= 1.79769313486231570815e308)
-                          ? __builtin_nan("")
-                          : norm_inv[lane];
-
-  const int n_rows = a.n_comp * a.n_r;
-  const int n_waves = blockDim.x >> 6;
   const int n_slabs = a.n_groups * a.k_splits;
-  // rows of this block (grid.y row blocks; one for large batches)
-  const int rows_per_block = (n_rows + gridDim.y - 1) / gridDim.y;
-  const int row_begin = blockIdx.y * rows_per_block;
-  const int row_end = row_begin + rows_per_block < n_rows ? row_begin + rows_per_block : n_rows;
   const int64_t slab = (int64_t)a.r_stride * a.ldb;
-  // sum of the slabs [g_begin, g_end) of one row, eight independent loads in flight, the
-  // additions in slab order
-  auto sum_slabs = [&](int row, int g_begin, int g_end) {
+  // sum of part `part` of `parts` equal ranges of the slabs of one row, eight independent loads
+  // in flight, the additions in slab order
+  auto sum_slabs = [&](int row, int part, int parts) {
+    const int g_begin = (int)((int64_t)n_slabs * part / parts);
+    const int g_end = (int)((int64_t)n_slabs * (part + 1) / parts);
     const int c = row / a.n_r, r = row % a.n_r;
     const double* src = a.partial + (int64_t)r * a.ldb + col + lane;
     double sum = 0.0;
@@ -4841,37 +4687,9 @@ static __global__ __launch_bounds__(1024) void finalize_kernel(FinalizeArgs a) {
     }
     return sum;
   };
-  for (int row0 = row_begin; row0 < row_end; row0 += kFinalizeRows) {
-    const int rows = row_end - row0 < kFinalizeRows ? row_end - row0 : kFinalizeRows;
-    if (rows * 2 <= n_waves) {
-      // few rows (small batches, split over row blocks): several waves per row, each
-      // over a contiguous range of slabs, combined in fixed order
-      const int parts = n_waves / rows;
-      const int rr = wave / parts, part = wave % parts;
-      if (rr < rows) {
-        const int g_begin = (int)((int64_t)n_slabs * part / parts);
-        const int g_end = (int)((int64_t)n_slabs * (part + 1) / parts);
-        part_sum[wave][lane] = sum_slabs(row0 + rr, g_begin, g_end);
-      }
-      __syncthreads();
-      if (wave < rows) {
-        double sum = 0.0;
-        for (int p = 0; p < parts; ++p) sum += part_sum[wave * parts + p][lane];
-        tile[wave][lane] = sum / norm;
-      }
-    } else {
-      for (int rr = wave; rr < rows; rr += n_waves)
-        tile[rr][lane] = sum_slabs(row0 + rr, 0, n_slabs) / norm;
-    }
-    __syncthreads();
-    // out[(col + d) * n_rows + row0 + rr]
-    for (int idx = threadIdx.x; idx < rows * kLanes; idx += blockDim.x) {
-      const int d = idx / rows, rr = idx % rows;
-      if (d < n_valid)
-        a.xi[(col + d) * (int64_t)n_rows + row0 + rr] = tile[rr][d];
-    }
-    __syncthreads();
-  }
+  finalize_body<false>(a, sum_slabs, [](double sum, double norm, bool poisoned) {
+    return sum / (poisoned ? __builtin_nan("") : norm);
+  });
 }
 #endif
 
@@ -4890,14 +4708,9 @@ static __global__ __launch_bounds__(64) void interp_coef_kernel(InterpArgs a) {
     const int n = a.n_axis[d];
     const double* xp = a.xp + a.axis_offset[d];
     const double x = a.x[b * a.n_dim + d];
-    int seg = -1;
-    for (int i = 0; i < n; ++i) seg += xp[i] <= x ? 1 : 0;   // np.digitize(x, xp) - 1
-    if (x == xp[n - 1]) seg = n - 2;
-    seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
-    const double* m = a.a + a.a_offset[d] + (int64_t)seg * 4 * n;
+    const double* m = a.a + a.a_offset[d] + (int64_t)spline_segment(n, xp, x) * 4 * n;
     const double x2 = x * x, x3 = x2 * x;
-    for (int j = 0; j < n; ++j)
-      weight[d][j][lane] = m[j] + m[n + j] * x + m[2 * n + j] * x2 + m[3 * n + j] * x3;
+    for (int j = 0; j < n; ++j) weight[d][j][lane] = spline_node_weight(n, m, j, x, x2, x3);
   }
   double n_cen = 0.0, n_sat = 0.0;
   int summed_class = -1;
@@ -4951,14 +4764,9 @@ static __global__ __launch_bounds__(64) void interp_coef_small_kernel(InterpArgs
     const int n = a.n_axis[d];
     const double* xp = a.xp + a.axis_offset[d];
     const double x = a.x[b * a.n_dim + d];
-    int seg = -1;
-    for (int i = 0; i < n; ++i) seg += xp[i] <= x ? 1 : 0;   // np.digitize(x, xp) - 1
-    if (x == xp[n - 1]) seg = n - 2;
-    seg = seg < 0 ? 0 : (seg > n - 2 ? n - 2 : seg);
-    const double* m = a.a + a.a_offset[d] + (int64_t)seg * 4 * n;
+    const double* m = a.a + a.a_offset[d] + (int64_t)spline_segment(n, xp, x) * 4 * n;
     const double x2 = x * x, x3 = x2 * x;
-    if (lane < n)
-      weight[d][lane] = m[lane] + m[n + lane] * x + m[2 * n + lane] * x2 + m[3 * n + lane] * x3;
+    if (lane < n) weight[d][lane] = spline_node_weight(n, m, lane, x, x2, x3);
   }
   __syncthreads();
   for (int k = lane; k < a.n_tables; k += kLanes) {

@@ -1593,18 +1593,6 @@ int run_cross_fused(tc_table* t0, const CrossFused& cf, const tc::CrossFusedArgs
     ca.split_all[0] = 0;
     ca.split_all[n_splits] = ca.n_groups;
     ca.n_splits = n_splits;
-    if (n_splits > 1) {
-      const size_t count = (size_t)(separate ? 2 : 1) * tc::kCrossSmallRows * 64;
-      status = partial->reserve((size_t)n_tiles * n_splits * count * sizeof(double), stream);
-      if (status != TC_OK) return status;
-      const size_t had = counters->bytes;
-      status = counters->reserve((size_t)n_tiles * sizeof(int), stream);
-      if (status != TC_OK) return status;
-      // (zero once: the last workgroup of a tile resets its counter)
-      if (counters->bytes != had) TC_HIP(hipMemsetAsync(counters->ptr, 0, counters->bytes, stream));
-      ca.partial = (double*)partial->ptr;
-      ca.counters = (int*)counters->ptr;
-    }
   } else {
     // the chunked form likewise: ranges of chunks of about equal cost (per group a node
     // evaluation, per member bin its row FMAs)
@@ -1631,16 +1619,21 @@ int run_cross_fused(tc_table* t0, const CrossFused& cf, const tc::CrossFusedArgs
       }
       ca.split_all[n_splits] = cf.n_chunks;
       ca.n_splits = n_splits;
-      const size_t count = (size_t)(separate ? 2 : 1) * cf.rows * 64;
-      status = partial->reserve((size_t)n_tiles * n_splits * count * sizeof(double), stream);
-      if (status != TC_OK) return status;
-      const size_t had = counters->bytes;
-      status = counters->reserve((size_t)n_tiles * sizeof(int), stream);
-      if (status != TC_OK) return status;
-      if (counters->bytes != had) TC_HIP(hipMemsetAsync(counters->ptr, 0, counters->bytes, stream));
-      ca.partial = (double*)partial->ptr;
-      ca.counters = (int*)counters->ptr;
     }
+  }
+  if (n_splits > 1) {
+    // a slot per (tile, split) for the shares -- (components, rows of the instance, 64) sums
+    // each -- and a counter per tile
+    const size_t count = (size_t)(separate ? 2 : 1) * cf.rows * 64;
+    status = partial->reserve((size_t)n_tiles * n_splits * count * sizeof(double), stream);
+    if (status != TC_OK) return status;
+    const size_t had = counters->bytes;
+    status = counters->reserve((size_t)n_tiles * sizeof(int), stream);
+    if (status != TC_OK) return status;
+    // (zero once: the last workgroup of a tile resets its counter)
+    if (counters->bytes != had) TC_HIP(hipMemsetAsync(counters->ptr, 0, counters->bytes, stream));
+    ca.partial = (double*)partial->ptr;
+    ca.counters = (int*)counters->ptr;
   }
   const dim3 grid((unsigned)(n_tiles * n_splits)), block(64 * tc::kCrossWaves);
 #ifdef TC_DEVELOPER_KNOBS
