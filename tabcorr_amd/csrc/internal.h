@@ -472,17 +472,8 @@ struct tc_table {
   std::vector<double> cross_host;
   tc::host::CrossFused cross_fused, cross_fused_wide;
   tc::host::GradTable grad;      // gradient entry points
-  // Set while the chunks of a synchronous host call are queued (0 otherwise): the workgroups a
-  // mode-cross launch should have at least, instead of Tuning::cross_target -- 512 / chunks, so
-  // that a call that has the chip to itself fills it once with shares of tiles (the
-  // AbacusSummit interpolator, one chunk: 242 -> 200 us per 10^4 draws host to host; its single
-  // table, two chunks: 149 -> 139; pipelined launches keep 160: they share the chip anyway).
-  int sync_cross_target = 0;
-  std::vector<hipEvent_t> chunk_events;    // ... between the chunks of a call with large results
-  // ... and that the chunks of such a call have the chip to themselves: where the latency form
-  // of the one-launch kernel serves the table, every chunk takes it when all chunks together
-  // have at most one workgroup of 40 draws per CU (hostmath.cpp: choose_fused_form)
-  bool sync_spread = false;
+  std::vector<hipEvent_t> chunk_events;    // between the chunks of a synchronous host call with
+                                           // large results (table.cpp: predict_chunked)
   bool quad = false;
   tc::QuadTiling quad_tiling;
   tc::host::QuadTable quad_by_type, quad_total;
@@ -502,7 +493,8 @@ struct tc_table {
   // device-pointer predict calls alternate between them, so that the occupation kernel of batch k + 1
   // overlaps the contraction of batch k (both are FP64-issue bound and the contraction
   // leaves issue slots free at its ramp-down); results are still produced in call order
-  // (the finalisation kernels are chained by events).  Host-buffer calls use lane 0.
+  // (the finalisation kernels are chained by events).  Host-buffer calls use lane 0.  Which lane
+  // a call runs on is the call's own (tc::host::Call below); the handle keeps what outlives it:
   struct Lane {
     hipStream_t stream = nullptr;
     hipEvent_t finished = nullptr;   // recorded after the lane's last finalisation
@@ -516,10 +508,9 @@ struct tc_table {
   static constexpr int kMaxLanes = 8;
   Lane lanes[kMaxLanes];
   int n_lanes = 2;
-  int prev = -1;                     // lane of the previous finalisation
-  int cur = 0;                       // lane of the current / last predict call
-  int force_lane = -1;               // host-buffer entry points pin lane 0
-  int async_lane = -1;               // asynchronous host calls: the lane already chosen
+  int prev = -1;                     // lane of the previous finalisation (-1: nobody chains to it)
+  int cur = 0;                       // lane of the last call, written once per call by its entry
+                                     // point (tc_comm_gather queues behind it)
   // Option "ordered": the finalisations of consecutive device-pointer calls are chained by
   // events so that their results appear in call order.  Off by default: every call only orders
   // its own kernels, tc_table_synchronize / tc_comm_gather wait for every lane (the chain
@@ -535,12 +526,7 @@ struct tc_table {
   static constexpr int kMaxTickets = 64;
   Ticket tickets[kMaxTickets];
   int64_t next_ticket = 0;
-  // chi2 calls: where the finalisation may put the fused likelihood (data | precision on
-  // the device, output); run_contraction sets chi2_fused when it did
-  const double* fuse_chi2_data = nullptr;
-  double* fuse_chi2_out = nullptr;
-  bool chi2_fused = false;
-  uint64_t device_calls = 0;
+  uint64_t device_calls = 0;         // calls that took a lane of the rotation (next_lane)
   tc::host::DeviceBuffer theta, out_ngal, out_xi, occupation, trace, wave_trace;
   tc::host::DeviceBuffer chi2_data;          // data vector + precision matrix of chi2 calls
   std::vector<double> chi2_host;             // host copy of what chi2_data holds
@@ -622,6 +608,62 @@ constexpr int kMaxLdsBytes = 160 * 1024;
 // Draws are processed in slabs so that the workspaces stay bounded.
 constexpr int64_t kMaxSlab = 1 << 18;
 
+// What one call carries from its entry point down to the launches.  The entry point fills it
+// once, everything below reads it; nothing of it is written on a handle, so a call leaves no
+// trace for the next one and an interpolator's call none on the tables it shares.
+struct Call {
+  int lane = 0;              // the lane it runs on, chosen once (next_lane)
+  bool pinned = false;       // a host-array entry point: lane 0, synchronised before it returns,
+                             // so nobody chains to its finalisation (prev = -1)
+  bool async = false;        // an asynchronous host call (tc_*_async), or a chunk of a synchronous one
+  bool alone = false;        // alone on its lane: pinned, option "pipeline" off, or a single lane
+  bool chain = false;        // option "ordered" as this call sees it: off for asynchronous calls
+  // The likelihood target: data | precision on the device and where chi2 goes.  NULL for a
+  // prediction, and for a batch of more than one slab.  A launch that writes chi2 itself says so
+  // through its `chi2_written` argument; otherwise launch_chi2 follows the prediction.
+  const double* chi2_data = nullptr;
+  double* chi2_out = nullptr;
+  // A chunk of a synchronous host call.  cross_target: the workgroups a mode-cross launch should
+  // have at least, instead of Tuning::cross_target (0) -- 512 / chunks, so that a call that has
+  // the chip to itself fills it once with shares of tiles (the AbacusSummit interpolator, one
+  // chunk: 242 -> 200 us per 10^4 draws host to host; its single table, two chunks: 149 -> 139;
+  // pipelined launches keep 160: they share the chip anyway).  sync_spread: the chunks have the
+  // chip to themselves -- where the latency form of the one-launch kernel serves the table, every
+  // chunk takes it when all chunks together have at most one workgroup of 40 draws per CU
+  // (hostmath.cpp: choose_fused_form).
+  int cross_target = 0;
+  bool sync_spread = false;
+  // options "fused_draws" and "fused_min_draws" as this call sees them (the chunks of a
+  // synchronous call take one form whatever their size: table.cpp, predict_chunked)
+  int fused_draws = 0, fused_min_draws = 0;
+};
+// The one rule for a call's lane: lane 0 for a pinned call and with option "pipeline" off, else
+// the next of the handle's `n_lanes` in rotation -- `device_calls` counts the calls that took one.
+inline int next_lane(bool pinned, bool pipeline, int n_lanes, uint64_t* device_calls) {
+  return pinned || !pipeline ? 0 : (int)((*device_calls)++ % n_lanes);
+}
+// A call on `lane` of a handle with `n_lanes` lanes whose options are `t`'s (an interpolator's
+// are its first table's), as they stand now.
+inline Call make_call(const tc_table* t, int lane, bool pinned, int n_lanes) {
+  Call call;
+  call.lane = lane;
+  call.pinned = pinned;
+  call.alone = pinned || !t->tuning.pipeline || n_lanes == 1;
+  call.chain = t->chain;
+  call.fused_draws = t->tuning.fused_draws;
+  call.fused_min_draws = t->tuning.fused_min_draws;
+  return call;
+}
+// ... of a table handle, on its next lane
+inline Call make_call(tc_table* t, bool pinned) {
+  return make_call(t, next_lane(pinned, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls),
+                   pinned, t->n_lanes);
+}
+// ... and what a device-pointer call WOULD carry, taking no lane (questions about forms)
+inline Call probe_call(const tc_table* t, bool pinned = false) {
+  return make_call(t, 0, pinned, t->n_lanes);
+}
+
 // ---- launch layer (launch.hip) --------------------------------------------------------
 int get_quadrature(tc_table* t, int n_gauss, Quadrature** out);
 // The GroupArgs of a table's groups of bins (n_gauss = 10).
@@ -644,25 +686,26 @@ int launch_contract_rt(int rt, int device, dim3 grid, dim3 block, int lds, hipSt
 int launch_contract_f32(int device, dim3 grid, dim3 block, int lds, hipStream_t stream,
                         const ContractArgs& args, hipEvent_t start = nullptr,
                         hipEvent_t stop = nullptr);
-// Occupation kernel for a slab of draws: densities into (nbuf, ngal2) -- the current
-// lane's by default -- and optionally the occupations in reference order.
-int run_occupation(tc_table* t, const double* theta_device, int n_theta, int64_t n_draws,
-                   int64_t ldb, int n_gauss, unsigned flags, double* occupation_device,
-                   DeviceBuffer* nbuf = nullptr, DeviceBuffer* ngal2 = nullptr,
-                   hipStream_t stream = nullptr, int* ngal_parts = nullptr,
-                   DeviceBuffer* nbuf32 = nullptr);
-// Contraction + finalisation of draws whose densities are already in the current lane.
-int run_contraction(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
-                    double* ngal_device, double* xi_device);
-// Alone on its lane: host-buffer entry points, a handle with one lane, option "pipeline" off.
-bool runs_alone(const tc_table* t);
+// Occupation kernel for a slab of draws: densities into (nbuf, ngal2) -- those of the call's
+// lane by default -- and optionally the occupations in reference order.
+int run_occupation(tc_table* t, const Call& call, const double* theta_device, int n_theta,
+                   int64_t n_draws, int64_t ldb, int n_gauss, unsigned flags,
+                   double* occupation_device, DeviceBuffer* nbuf = nullptr,
+                   DeviceBuffer* ngal2 = nullptr, hipStream_t stream = nullptr,
+                   int* ngal_parts = nullptr, DeviceBuffer* nbuf32 = nullptr);
+// Contraction + finalisation of draws whose densities are already in the call's lane.
+// *chi2_written = true where the finalisation wrote the call's likelihood itself.
+int run_contraction(tc_table* t, const Call& call, int64_t n_draws, int64_t ldb, unsigned flags,
+                    double* ngal_device, double* xi_device, bool* chi2_written = nullptr);
 // One launch per slab (predict_fused_kernel) for the calls it covers: what hostmath.h:
-// choose_fused_form reads about a call, filled from the handle; the launch in the form it
-// returned -- ngal and xi (or the likelihood, t->fuse_chi2_out) as run_contraction leaves them.
-tc::FusedQuery fused_query(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags);
-int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n_theta,
-              int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
-              double* xi_device);
+// choose_fused_form reads about a call -- the table's shape and options from the handle, the
+// rest from the call; the launch in the form it returned -- ngal and xi (or the call's
+// likelihood: *chi2_written = true) as run_contraction leaves them.
+tc::FusedQuery fused_query(const tc_table* t, const Call& call, int64_t n_draws, int n_gauss,
+                           unsigned flags);
+int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* theta_device,
+              int n_theta, int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
+              double* xi_device, bool* chi2_written = nullptr);
 // Option "deterministic" = 2: is there a one-launch form for this table and these flags (whose
 // bits do not depend on the batch)?  Every entry point then takes it for every batch size.
 bool batch_invariant_form(tc_table* t, int n_gauss, unsigned flags);
@@ -706,12 +749,13 @@ int build_cross_fused(tc_table* const* tables, int n_tables, CrossFused* cf, boo
 // for) or, for tables of up to 16 rows, `wide` (32 rows: the chunk form) -- built on first use.
 CrossFused* choose_cross_fused(tc_table* const* tables, int n_tables, CrossFused* narrow,
                                CrossFused* wide, int64_t n_draws, unsigned flags, int* status);
-bool cross_fused_eligible(const tc_table* t0, const CrossFused& cf, int64_t n_draws, int n_gauss,
-                          unsigned flags, bool alone);
-int run_cross_fused(tc_table* t0, const CrossFused& cf, const tc::CrossFusedArgs* interp,
-                    const double* theta_device, int n_theta, int64_t n_draws, unsigned flags,
-                    double* ngal_device, double* xi_device, hipStream_t stream,
-                    DeviceBuffer* partial, DeviceBuffer* counters);
+bool cross_fused_eligible(const tc_table* t0, const Call& call, const CrossFused& cf,
+                          int64_t n_draws, int n_gauss, unsigned flags);
+int run_cross_fused(tc_table* t0, const Call& call, const CrossFused& cf,
+                    const tc::CrossFusedArgs* interp, const double* theta_device, int n_theta,
+                    int64_t n_draws, unsigned flags, double* ngal_device, double* xi_device,
+                    hipStream_t stream, DeviceBuffer* partial, DeviceBuffer* counters,
+                    bool* chi2_written = nullptr);
 int launch_finalize(const FinalizeArgs& args, const Tuning& tuning, hipStream_t stream);
 // Quadratic-form path: layout upload, schedules, launches.
 int build_quad_table(tc_table* t, bool by_type, const void* matrix, int matrix_dtype,

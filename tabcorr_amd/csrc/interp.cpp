@@ -68,8 +68,7 @@ struct tc_interp {
   // draws and only several launches in flight fill the CUs (the reference's AbacusSummit
   // interpolator, 10^4 draws per call: 143 us per call with two lanes)
   int n_lanes = 2;
-  int force_lane = -1;                        // host-buffer entry points pin lane 0
-  int cur = 0;                                // lane of the current / last call
+  int cur = 0;                                // lane of the last call (tc_comm_gather_interp)
   uint64_t device_calls = 0;
   hipStream_t stream = nullptr;               // = lanes[0].stream
   DeviceBuffer theta, x, out_ngal, out_xi;  // host-buffer calls
@@ -113,11 +112,14 @@ int upload_chi2_data(tc_interp* it, const double* data, const double* precision)
   return TC_OK;
 }
 
-int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta,
-                          const double* x_device, int64_t n_draws, int n_gauss,
-                          unsigned flags, double* ngal_device, double* xi_device) {
+// One slab of an interpolated prediction as `call` describes it (internal.h: its lane is one of
+// the interpolator's, its options the first table's).
+int interp_predict_slab(tc_interp* it, const Call& call, const double* theta_device, int n_theta,
+                        const double* x_device, int64_t n_draws, int n_gauss,
+                        unsigned flags, double* ngal_device, double* xi_device,
+                        bool* chi2_written) {
   tc_table* t0 = it->tables[0];
-  tc_interp::Lane& L = it->lanes[it->cur];
+  tc_interp::Lane& L = it->lanes[call.lane];
   const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
   const int n_comp = separate ? t0->plan.n_components : 1;
   const int n_classes = (int)it->class_table.size();
@@ -130,8 +132,7 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
         *choose_cross_fused(it->tables.data(), it->n_tables, &it->cross_fused,
                             &it->cross_fused_wide, n_draws, flags, &status);
     if (status != TC_OK) return status;
-    const bool alone = it->force_lane >= 0 || !t0->tuning.pipeline;
-    if (cross_fused_eligible(t0, cf, n_draws, n_gauss, flags, alone)) {
+    if (cross_fused_eligible(t0, call, cf, n_draws, n_gauss, flags)) {
       tc::CrossFusedArgs ca{};
       ca.n_dim = it->n_dim;
       for (int d = 0; d < it->n_dim; ++d) {
@@ -143,8 +144,8 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
       ca.a = (const double*)it->d_a;
       ca.table_node = (const int32_t*)it->d_table_node;
       ca.x = x_device;
-      return run_cross_fused(t0, cf, &ca, theta_device, n_theta, n_draws, flags,
-                             ngal_device, xi_device, L.stream, &L.partial, &L.cross_counters);
+      return run_cross_fused(t0, call, cf, &ca, theta_device, n_theta, n_draws, flags, ngal_device,
+                             xi_device, L.stream, &L.partial, &L.cross_counters, chi2_written);
     }
   }
 
@@ -152,9 +153,10 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
   int ngal_parts = 1;
   const bool quad_f32 = t0->quad && t0->compute_dtype == TC_DTYPE_F32;
   for (int v = 0; v < n_classes; ++v) {
-    status = run_occupation(it->tables[it->class_table[v]], theta_device, n_theta,
-                            n_draws, ldb, n_gauss, flags, nullptr, &L.nbuf[v],
-                            &L.ngal2[v], L.stream, &ngal_parts,
+    // (the shape of a class's occupation launch follows that table's own options, not the call's)
+    tc_table* t = it->tables[it->class_table[v]];
+    status = run_occupation(t, probe_call(t), theta_device, n_theta, n_draws, ldb, n_gauss, flags,
+                            nullptr, &L.nbuf[v], &L.ngal2[v], L.stream, &ngal_parts,
                             quad_f32 ? &L.nbuf32[v] : nullptr);
     if (status != TC_OK) return status;
   }
@@ -270,13 +272,12 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
     fq.n_draws = n_draws;
     fq.ngal = ngal_device;
     fq.xi = xi_device;
-    t0->chi2_fused = false;
-    if (t0->fuse_chi2_out != nullptr && !separate && t0->n_r <= tc::kFinalizeRows) {
+    if (call.chi2_out != nullptr && !separate && t0->n_r <= tc::kFinalizeRows) {
       // (launch.hip, run_contraction_quad: the likelihood from the finalisation's LDS tile)
-      fq.chi2_data = t0->fuse_chi2_data;
-      fq.chi2 = t0->fuse_chi2_out;
+      fq.chi2_data = call.chi2_data;
+      fq.chi2 = call.chi2_out;
       fq.xi = nullptr;
-      t0->chi2_fused = true;
+      *chi2_written = true;
     }
     return launch_finalize_quad(fq, t0->tuning, L.stream, quad_f32);
   }
@@ -373,6 +374,57 @@ int interp_predict_device(tc_interp* it, const double* theta_device, int n_theta
   fa.ngal = ngal_device;
   fa.xi = xi_device;
   return launch_finalize(fa, t0->tuning, L.stream);
+}
+
+// A call of the interpolator on its next lane (internal.h: make_call), the options its first
+// table's.
+Call interp_call(tc_interp* it, bool pinned) {
+  const tc_table* t0 = it->tables[0];
+  return make_call(t0, next_lane(pinned, t0->tuning.pipeline != 0, it->n_lanes,
+                                 &it->device_calls), pinned, it->n_lanes);
+}
+
+// A prediction of n_draws > 0 draws on device pointers as `call` describes it (the arguments are
+// checked): tc_interp_predict_zheng07_batch_device, and the host-array and asynchronous entry
+// points underneath.  *chi2_written: the launch wrote the call's likelihood itself.
+int interp_predict_device(tc_interp* it, const Call& call, const double* theta_device,
+                          int n_theta, const double* x_device, int64_t n_draws, int n_gauss,
+                          unsigned flags, double* ngal_device, double* xi_device,
+                          bool* chi2_written = nullptr) {
+  TC_HIP(hipSetDevice(it->device));
+  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
+  const int n_comp = separate ? it->tables[0]->plan.n_components : 1;
+  it->cur = call.lane;
+  return for_each_slab(n_draws, max_slab(it->tables[0]), [&](int64_t begin, int64_t n) {
+    return interp_predict_slab(it, call, theta_device + begin * n_theta, n_theta,
+                               x_device + begin * it->n_dim, n, n_gauss, flags,
+                               ngal_device + begin * (separate ? 2 : 1),
+                               xi_device + begin * n_comp * it->tables[0]->n_r, chi2_written);
+  });
+}
+
+// A likelihood of n_draws > 0 draws on device pointers as `call` describes it (the arguments are
+// checked): tc_interp_chi2_zheng07_batch_device and the entry points underneath.
+int interp_chi2_device(tc_interp* it, Call call, const double* theta_device, int n_theta,
+                       const double* x_device, int64_t n_draws, int n_gauss, unsigned flags,
+                       const double* data, const double* precision, double* ngal_device,
+                       double* chi2_device) {
+  TC_HIP(hipSetDevice(it->device));
+  tc_table* t0 = it->tables[0];
+  const int n_r = t0->n_r;
+  tc_interp::Lane& L = it->lanes[call.lane];
+  int status = upload_chi2_data(it, data, precision);
+  if (status != TC_OK) return status;
+  status = L.chi2_xi.reserve((size_t)n_draws * n_r * 8, L.stream);
+  if (status != TC_OK) return status;
+  call.chi2_data = (const double*)it->chi2_data.ptr;
+  call.chi2_out = n_draws <= max_slab(t0) ? chi2_device : nullptr;   // (one slab)
+  bool written = false;
+  status = interp_predict_device(it, call, theta_device, n_theta, x_device, n_draws, n_gauss,
+                                 flags, ngal_device, (double*)L.chi2_xi.ptr, &written);
+  if (status != TC_OK || written) return status;
+  return launch_chi2((const double*)L.chi2_xi.ptr, n_draws, n_r, call.chi2_data,
+                     call.chi2_data + n_r, chi2_device, L.stream);
 }
 
 }  // namespace
@@ -594,22 +646,8 @@ int tc_interp_predict_zheng07_batch_device(tc_interp* it, const double* theta_de
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(x_device && ngal_device && xi_device, "NULL pointer");
-  TC_HIP(hipSetDevice(it->device));
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  const int n_comp = separate ? it->tables[0]->plan.n_components : 1;
-  it->cur = it->force_lane >= 0 ? it->force_lane
-            : it->tables[0]->tuning.pipeline ? (int)(it->device_calls++ % it->n_lanes)
-                                             : 0;
-  const int64_t slab = max_slab(it->tables[0]);
-  for (int64_t begin = 0; begin < n_draws; begin += slab) {
-    const int64_t n = std::min(slab, n_draws - begin);
-    status = interp_predict_device(
-        it, theta_device + begin * n_theta, n_theta, x_device + begin * it->n_dim, n,
-        n_gauss, flags, ngal_device + begin * (separate ? 2 : 1),
-        xi_device + begin * n_comp * it->tables[0]->n_r);
-    if (status != TC_OK) return status;
-  }
-  return TC_OK;
+  return interp_predict_device(it, interp_call(it, /*pinned=*/false), theta_device, n_theta,
+                               x_device, n_draws, n_gauss, flags, ngal_device, xi_device);
 }
 
 namespace {
@@ -743,7 +781,7 @@ namespace {
 int interp_async(tc_interp* it, const double* theta, int n_theta, const double* x,
                  int64_t n_draws, int n_gauss, unsigned flags, const double* data,
                  const double* precision, double* ngal, double* second, bool chi2,
-                 int64_t* ticket_out, bool staging);
+                 int64_t* ticket_out, int cross_target = -1);
 
 // A synchronous host-array call as overlapping chunks of draws (table.cpp: predict_chunked has
 // the reasoning): chunk k's draws and extra parameters are staged and queued on lane k % lanes
@@ -767,7 +805,6 @@ int interp_chunked(tc_interp* it, const double* theta, int n_theta, const double
   int64_t tickets[64];
   double* h_in = (double*)it->h_in.ptr;
   double* h_out = (double*)it->h_out.ptr;
-  it->tables[0]->sync_cross_target = 512 / n_chunks;       // (internal.h)
   for (int k = 0; k < n_chunks && status == TC_OK; ++k) {
     const int64_t begin = k * chunk, n = std::min(chunk, n_draws - begin);
     double* in = h_in + begin * in_cols;          // [theta | x] of the chunk
@@ -775,10 +812,9 @@ int interp_chunked(tc_interp* it, const double* theta, int n_theta, const double
     memcpy(in + n * n_theta, x + begin * it->n_dim, (size_t)n * it->n_dim * 8);
     double* out = h_out + begin * (ngal_cols + xi_cols);
     status = interp_async(it, in, n_theta, in + n * n_theta, n, n_gauss, flags, nullptr, nullptr,
-                          out, out + n * ngal_cols, false, &tickets[k], true);
+                          out, out + n * ngal_cols, false, &tickets[k], 512 / n_chunks);
     if (status != TC_OK) n_chunks = k;
   }
-  it->tables[0]->sync_cross_target = 0;
   for (int k = 0; k < n_chunks; ++k) {
     const int64_t begin = k * chunk, n = std::min(chunk, n_draws - begin);
     const int waited = tc_interp_wait(it, tickets[k]);
@@ -812,7 +848,8 @@ int tc_interp_predict_zheng07_batch(tc_interp* it, const double* theta, int n_th
     const CrossFused& cf = *choose_cross_fused(it->tables.data(), it->n_tables, &it->cross_fused,
                                                &it->cross_fused_wide, n_draws, flags, &status);
     if (status != TC_OK) return status;
-    invariant = cross_fused_eligible(it->tables[0], cf, n_draws, n_gauss, flags, true);
+    invariant = cross_fused_eligible(it->tables[0], probe_call(it->tables[0], /*pinned=*/true), cf,
+                                     n_draws, n_gauss, flags);
   }
   if (!invariant && single_draw_eligible(it->tables[0], n_draws, n_gauss, flags) &&
       (int64_t)it->n_tables * single_draw_blocks(it->tables[0]) <= 8192)
@@ -831,11 +868,9 @@ int tc_interp_predict_zheng07_batch(tc_interp* it, const double* theta, int n_th
     double* out = (double*)it->h_out.ptr;
     memcpy(in, theta, theta_count * 8);
     memcpy(in + theta_count, x, x_count * 8);
-    it->force_lane = 0;
-    status = tc_interp_predict_zheng07_batch_device(it, in, n_theta, in + theta_count,
-                                                    n_draws, n_gauss, flags, out,
-                                                    out + ngal_count);
-    it->force_lane = -1;
+    status = interp_predict_device(it, interp_call(it, /*pinned=*/true), in, n_theta,
+                                   in + theta_count, n_draws, n_gauss, flags, out,
+                                   out + ngal_count);
     if (status != TC_OK) return status;
     TC_HIP(hipStreamSynchronize(it->stream));
     memcpy(ngal, out, ngal_count * 8);
@@ -875,11 +910,10 @@ int tc_interp_predict_zheng07_batch(tc_interp* it, const double* theta, int n_th
                         hipMemcpyHostToDevice, it->stream));
   TC_HIP(hipMemcpyAsync(it->x.ptr, x, (size_t)n_draws * it->n_dim * 8,
                         hipMemcpyHostToDevice, it->stream));
-  it->force_lane = 0;
-  status = tc_interp_predict_zheng07_batch_device(
-      it, (const double*)it->theta.ptr, n_theta, (const double*)it->x.ptr, n_draws,
-      n_gauss, flags, (double*)it->out_ngal.ptr, (double*)it->out_xi.ptr);
-  it->force_lane = -1;
+  status = interp_predict_device(it, interp_call(it, /*pinned=*/true),
+                                 (const double*)it->theta.ptr, n_theta, (const double*)it->x.ptr,
+                                 n_draws, n_gauss, flags, (double*)it->out_ngal.ptr,
+                                 (double*)it->out_xi.ptr);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, it->out_ngal.ptr, ngal_count * 8, hipMemcpyDeviceToHost,
                         it->stream));
@@ -899,31 +933,11 @@ int tc_interp_chi2_zheng07_batch_device(tc_interp* it, const double* theta_devic
            "chi2 is defined for the total correlation function only");
   if (n_draws == 0) return TC_OK;
   TC_CHECK(data && precision && ngal_device && chi2_device, "NULL pointer");
-  TC_HIP(hipSetDevice(it->device));
-  const int n_r = it->tables[0]->n_r;
-  tc_table* t0 = it->tables[0];
-  // the lane tc_interp_predict_zheng07_batch_device is about to pick
-  const int lane_index = it->force_lane >= 0 ? it->force_lane
-                         : t0->tuning.pipeline ? (int)(it->device_calls % it->n_lanes)
-                                               : 0;
-  tc_interp::Lane& L = it->lanes[lane_index];
-  int status = upload_chi2_data(it, data, precision);
+  int status = check_predict_args(it->tables[0], theta_device, n_theta, n_draws, n_gauss, flags);
   if (status != TC_OK) return status;
-  status = L.chi2_xi.reserve((size_t)n_draws * n_r * 8, L.stream);
-  if (status != TC_OK) return status;
-  const double* d_data = (const double*)it->chi2_data.ptr;
-  t0->chi2_fused = false;
-  t0->fuse_chi2_data = d_data;
-  t0->fuse_chi2_out = n_draws <= max_slab(t0) ? chi2_device : nullptr;   // (one slab)
-  status = tc_interp_predict_zheng07_batch_device(it, theta_device, n_theta, x_device, n_draws,
-                                                  n_gauss, flags, ngal_device,
-                                                  (double*)L.chi2_xi.ptr);
-  const bool fused = t0->fuse_chi2_out != nullptr && t0->chi2_fused;
-  t0->fuse_chi2_out = nullptr;
-  if (status != TC_OK) return status;
-  if (fused) return TC_OK;
-  return launch_chi2((const double*)L.chi2_xi.ptr, n_draws, n_r, d_data, d_data + n_r,
-                     chi2_device, L.stream);
+  TC_CHECK(x_device != nullptr, "NULL pointer");
+  return interp_chi2_device(it, interp_call(it, /*pinned=*/false), theta_device, n_theta, x_device,
+                            n_draws, n_gauss, flags, data, precision, ngal_device, chi2_device);
 }
 
 int tc_interp_chi2_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -946,11 +960,11 @@ int tc_interp_chi2_zheng07_batch(tc_interp* it, const double* theta, int n_theta
   TC_HIP(hipMemcpyAsync(it->x.ptr, x, x_bytes, hipMemcpyHostToDevice, it->stream));
   double* d_ngal = (double*)it->out_ngal.ptr;
   double* d_chi2 = d_ngal + n_draws;
-  it->force_lane = 0;
-  status = tc_interp_chi2_zheng07_batch_device(it, (const double*)it->theta.ptr, n_theta,
-                                               (const double*)it->x.ptr, n_draws, n_gauss,
-                                               flags, data, precision, d_ngal, d_chi2);
-  it->force_lane = -1;
+  TC_CHECK(!(flags & TC_FLAG_SEPARATE_GAL_TYPE),
+           "chi2 is defined for the total correlation function only");
+  status = interp_chi2_device(it, interp_call(it, /*pinned=*/true), (const double*)it->theta.ptr,
+                              n_theta, (const double*)it->x.ptr, n_draws, n_gauss, flags, data,
+                              precision, d_ngal, d_chi2);
   if (status != TC_OK) return status;
   TC_HIP(hipMemcpyAsync(ngal, d_ngal, (size_t)n_draws * 8, hipMemcpyDeviceToHost, it->stream));
   TC_HIP(hipMemcpyAsync(chi2, d_chi2, (size_t)n_draws * 8, hipMemcpyDeviceToHost, it->stream));
@@ -963,7 +977,7 @@ namespace {
 int interp_async(tc_interp* it, const double* theta, int n_theta, const double* x,
                  int64_t n_draws, int n_gauss, unsigned flags, const double* data,
                  const double* precision, double* ngal, double* second, bool chi2,
-                 int64_t* ticket_out, bool staging) {
+                 int64_t* ticket_out, int cross_target) {
   TC_CHECK(it != nullptr, "interp handle is NULL");
   tc_table* t0 = it->tables[0];
   int status = check_predict_args(t0, theta, n_theta, n_draws, n_gauss, flags);
@@ -977,17 +991,18 @@ int interp_async(tc_interp* it, const double* theta, int n_theta, const double* 
   const size_t ngal_count = (size_t)n_draws * (separate ? 2 : 1);
   const size_t second_count = chi2 ? (size_t)n_draws : (size_t)n_draws * n_comp * t0->n_r;
   const size_t theta_count = (size_t)n_draws * n_theta, x_count = (size_t)n_draws * it->n_dim;
-  // (staging: the library's own page-locked staging areas -- the chunks of a synchronous call)
-  TC_CHECK(n_draws == 0 || staging ||
+  // (cross_target >= 0: a chunk of a synchronous call -- Call::cross_target -- in the library's
+  // own page-locked staging areas)
+  TC_CHECK(n_draws == 0 || cross_target >= 0 ||
                (is_pinned(theta, theta_count * 8) && is_pinned(x, x_count * 8) &&
                 is_pinned(ngal, ngal_count * 8) && is_pinned(second, second_count * 8)),
            "asynchronous calls need page-locked buffers (tc_host_alloc / tc_host_register)");
   TC_HIP(hipSetDevice(it->device));
   // everything of a call -- upload, kernels, download, the ticket's event -- on the next lane's
   // stream: the lanes overlap each other's transfers and kernels
-  const int lane_index =
-      t0->tuning.pipeline ? (int)(it->device_calls % it->n_lanes) : 0;
-  tc_interp::Lane& L = it->lanes[lane_index];
+  Call call = interp_call(it, /*pinned=*/false);
+  call.cross_target = std::max(0, cross_target);
+  tc_interp::Lane& L = it->lanes[call.lane];
   hipStream_t last = L.stream;
   if (n_draws > 0) {
     status = L.stage_out.reserve((ngal_count + second_count) * 8, L.stream);
@@ -1002,17 +1017,14 @@ int interp_async(tc_interp* it, const double* theta, int n_theta, const double* 
       TC_HIP(hipMemcpyAsync(d_theta, theta, theta_count * 8, hipMemcpyHostToDevice, L.stream));
       TC_HIP(hipMemcpyAsync(d_x, x, x_count * 8, hipMemcpyHostToDevice, L.stream));
     }
-    status = chi2 ? tc_interp_chi2_zheng07_batch_device(it, d_theta, n_theta, d_x, n_draws,
-                                                        n_gauss, flags, data, precision, d_ngal,
-                                                        d_second)
-                  : tc_interp_predict_zheng07_batch_device(it, d_theta, n_theta, d_x, n_draws,
-                                                           n_gauss, flags, d_ngal, d_second);
+    status = chi2 ? interp_chi2_device(it, call, d_theta, n_theta, d_x, n_draws, n_gauss, flags,
+                                       data, precision, d_ngal, d_second)
+                  : interp_predict_device(it, call, d_theta, n_theta, d_x, n_draws, n_gauss,
+                                          flags, d_ngal, d_second);
     if (status != TC_OK) return status;
     Range range("download");
     TC_HIP(hipMemcpyAsync(ngal, d_ngal, ngal_count * 8, hipMemcpyDeviceToHost, L.stream));
     TC_HIP(hipMemcpyAsync(second, d_second, second_count * 8, hipMemcpyDeviceToHost, L.stream));
-  } else if (t0->tuning.pipeline) {
-    ++it->device_calls;
   }
   tc_table::Ticket& slot = it->tickets[it->next_ticket % tc_table::kMaxTickets];
   if (slot.done == nullptr)
@@ -1030,7 +1042,7 @@ int tc_interp_predict_zheng07_batch_async(tc_interp* it, const double* theta, in
                                           unsigned flags, double* ngal, double* xi,
                                           int64_t* ticket) {
   return interp_async(it, theta, n_theta, x, n_draws, n_gauss, flags, nullptr, nullptr, ngal, xi,
-                      false, ticket, false);
+                      false, ticket);
 }
 
 int tc_interp_chi2_zheng07_batch_async(tc_interp* it, const double* theta, int n_theta,
@@ -1039,7 +1051,7 @@ int tc_interp_chi2_zheng07_batch_async(tc_interp* it, const double* theta, int n
                                        const double* precision, double* ngal, double* chi2,
                                        int64_t* ticket) {
   return interp_async(it, theta, n_theta, x, n_draws, n_gauss, flags, data, precision, ngal,
-                      chi2, true, ticket, false);
+                      chi2, true, ticket);
 }
 
 // ---- gradients (grad_interp_kernels.hip.h) ------------------------------------------------
@@ -1123,9 +1135,8 @@ int interp_grad_device(tc_interp* it, GradLane request, const double* theta_devi
   status = class_pointers(it, n_gauss, &pointers);
   if (status == TC_OK) status = build_grad_walk(it);
   if (status != TC_OK) return status;
-  it->cur = request == GradLane::kPinned || !t0->tuning.pipeline
-                ? 0
-                : (int)(it->device_calls++ % it->n_lanes);
+  it->cur = next_lane(request == GradLane::kPinned, t0->tuning.pipeline != 0, it->n_lanes,
+                      &it->device_calls);
   tc_interp::Lane& L = it->lanes[it->cur];
   const bool with_chi2 = xi == nullptr;
   const bool decorated = n_params == tc::kGradParamsAssembias;

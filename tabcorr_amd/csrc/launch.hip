@@ -559,9 +559,28 @@ int next_kernel_events(tc_table* t, hipEvent_t* start, hipEvent_t* stop) {
   return TC_OK;
 }
 
+// Option "ordered", before a finalisation: results appear in call order -- wait for the previous
+// call's (host-array calls synchronise before returning and leave nothing to wait for) ...
+static int chain_wait(tc_table* t, const Call& call, hipStream_t stream) {
+  if (call.chain && t->prev >= 0 && t->prev != call.lane)
+    TC_HIP(hipStreamWaitEvent(stream, t->lanes[t->prev].finished, 0));
+  return TC_OK;
+}
+// ... and behind it: the lane's `finished` event orders the next lane's finalisation behind this
+// one.  (With unordered finalisations nobody waits for it -- tc_comm_gather records its own --
+// and the marker would only put a 7-25 us bubble between this finalisation and the lane's next
+// occupation kernel: profiles/r03_notes.md)
+static int chain_record(tc_table* t, const Call& call) {
+  if (!call.pinned && call.chain)
+    TC_HIP(hipEventRecord(t->lanes[call.lane].finished, t->lanes[call.lane].stream));
+  t->prev = call.pinned ? -1 : call.lane;
+  return TC_OK;
+}
+
 // Contraction + finalisation through the quadratic-form kernel (mode auto, float64).
-static int run_contraction_quad(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
-                                double* ngal_device, double* xi_device) {
+static int run_contraction_quad(tc_table* t, const Call& call, int64_t n_draws, int64_t ldb,
+                                unsigned flags, double* ngal_device, double* xi_device,
+                                bool* chi2_written) {
   Range range("contraction + finalisation");
   const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
   QuadTable* q = separate || t->quad_total.d_table == nullptr ? &t->quad_by_type
@@ -572,7 +591,7 @@ static int run_contraction_quad(tc_table* t, int64_t n_draws, int64_t ldb, unsig
   int status = get_quad_schedule(t, q, ldb / (f32 ? tc::kQuadTileF32 : tc::kQuadTile), 1,
                                  separate, &schedule);
   if (status != TC_OK) return status;
-  tc_table::Lane& lane = t->lanes[t->cur];
+  tc_table::Lane& lane = t->lanes[call.lane];
   hipStream_t stream = lane.stream;
   const int rt = 4 * tiling.n_u;
   status = lane.partial.reserve(
@@ -638,36 +657,27 @@ static int run_contraction_quad(tc_table* t, int64_t n_draws, int64_t ldb, unsig
   fa.n_draws = n_draws;
   fa.ngal = ngal_device;
   fa.xi = xi_device;
-  t->chi2_fused = false;
-  if (t->fuse_chi2_out != nullptr && !separate && t->n_r <= tc::kFinalizeRows) {
+  if (call.chi2_out != nullptr && !separate && t->n_r <= tc::kFinalizeRows) {
     // the likelihood straight from the finalisation's LDS tile: no xi round trip, one
     // launch (and one gap in the lane's chain) less
-    fa.chi2_data = t->fuse_chi2_data;
-    fa.chi2 = t->fuse_chi2_out;
+    fa.chi2_data = call.chi2_data;
+    fa.chi2 = call.chi2_out;
     fa.xi = nullptr;
-    t->chi2_fused = true;
+    *chi2_written = true;
   }
-  if (t->chain && t->prev >= 0 && t->prev != t->cur)
-    TC_HIP(hipStreamWaitEvent(stream, t->lanes[t->prev].finished, 0));
+  status = chain_wait(t, call, stream);
+  if (status != TC_OK) return status;
   if (!t->tuning.skip_finalize) status = launch_finalize_quad(fa, t->tuning, stream, f32);
   if (status != TC_OK) return status;
-  if (t->force_lane >= 0) {
-    t->prev = -1;
-  } else {
-    // (the lane's `finished` event orders the next lane's finalisation behind this one; with
-    // unordered finalisations nobody waits for it -- tc_comm_gather records its own -- and the
-    // marker would only put a 7-25 us bubble between this finalisation and the lane's next
-    // occupation kernel: profiles/r03_notes.md)
-    if (t->chain) TC_HIP(hipEventRecord(lane.finished, stream));
-    t->prev = t->cur;
-  }
-  return TC_OK;
+  return chain_record(t, call);
 }
 
 // Contraction + finalisation of draws whose densities are already in nbuf / ngal2.
-int run_contraction(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
-                    double* ngal_device, double* xi_device) {
-  if (t->quad) return run_contraction_quad(t, n_draws, ldb, flags, ngal_device, xi_device);
+int run_contraction(tc_table* t, const Call& call, int64_t n_draws, int64_t ldb, unsigned flags,
+                    double* ngal_device, double* xi_device, bool* chi2_written) {
+  if (t->quad)
+    return run_contraction_quad(t, call, n_draws, ldb, flags, ngal_device, xi_device,
+                                chi2_written);
   Range range("contraction + finalisation");
   const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
   const int n_comp = separate ? t->plan.n_components : 1;
@@ -675,7 +685,7 @@ int run_contraction(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
   int lds = 0;
   int status = choose_chunking(t, n_draws, 1, &c, &lds);
   if (status != TC_OK) return status;
-  tc_table::Lane& lane = t->lanes[t->cur];
+  tc_table::Lane& lane = t->lanes[call.lane];
   hipStream_t stream = lane.stream;
   const int n_groups = (int)c->host.groups.size();
   const int r_stride = t->rt * t->n_rtiles;
@@ -761,31 +771,19 @@ int run_contraction(tc_table* t, int64_t n_draws, int64_t ldb, unsigned flags,
   fa.n_draws = n_draws;
   fa.ngal = ngal_device;
   fa.xi = xi_device;
-  // results appear in call order: wait for the previous call's finalisation
-  // (host-buffer calls synchronise before returning and need no chaining)
-  if (t->chain && t->prev >= 0 && t->prev != t->cur)
-    TC_HIP(hipStreamWaitEvent(stream, t->lanes[t->prev].finished, 0));
+  status = chain_wait(t, call, stream);
+  if (status != TC_OK) return status;
   if (!t->tuning.skip_finalize) status = launch_finalize(fa, t->tuning, stream);
   if (status != TC_OK) return status;
-  if (t->force_lane >= 0) {
-    t->prev = -1;
-  } else {
-    // (the lane's `finished` event orders the next lane's finalisation behind this one; with
-    // unordered finalisations nobody waits for it -- tc_comm_gather records its own -- and the
-    // marker would only put a 7-25 us bubble between this finalisation and the lane's next
-    // occupation kernel: profiles/r03_notes.md)
-    if (t->chain) TC_HIP(hipEventRecord(lane.finished, stream));
-    t->prev = t->cur;
-  }
-  return TC_OK;
+  return chain_record(t, call);
 }
 
-int run_occupation(tc_table* t, const double* theta_device, int n_theta,
+int run_occupation(tc_table* t, const Call& call, const double* theta_device, int n_theta,
                    int64_t n_draws, int64_t ldb, int n_gauss, unsigned flags,
                    double* occupation_device, DeviceBuffer* nbuf, DeviceBuffer* ngal2,
                    hipStream_t stream, int* ngal_parts, DeviceBuffer* nbuf32) {
   Range range("occupation");
-  tc_table::Lane& lane = t->lanes[t->cur];
+  tc_table::Lane& lane = t->lanes[call.lane];
   if (nbuf == nullptr) nbuf = &lane.nbuf;
   if (ngal2 == nullptr) ngal2 = &lane.ngal2;
   if (stream == nullptr) stream = lane.stream;
@@ -818,10 +816,9 @@ int run_occupation(tc_table* t, const double* theta_device, int n_theta,
         // that run alone on their lane (host-buffer API, pipeline off) wait for this kernel:
         // twice as many, shorter items (10^4 draws: 25 -> 20 us, host-to-host 158 -> 149 us;
         // in the pipeline they cost 0.7 us per step)
-        const bool alone = runs_alone(t);
         splits = trial;
         grid_blocks = (int)std::min<int64_t>(items, slots);
-        if (items >= (alone ? 2 : 1) * (int64_t)n_cus) break;
+        if (items >= (call.alone ? 2 : 1) * (int64_t)n_cus) break;
         continue;
       }
       const int64_t rounds = (items + slots - 1) / slots;
@@ -891,15 +888,11 @@ int run_occupation(tc_table* t, const double* theta_device, int n_theta,
   return launch_occupation(oa, flags, n_gauss, grouped, grid_blocks, stream);
 }
 
-// Alone on its lane: host-buffer entry points, a handle with one lane, option "pipeline" off.
-bool runs_alone(const tc_table* t) {
-  return t->force_lane >= 0 || !t->tuning.pipeline || t->n_lanes == 1;
-}
-
 // Everything hostmath.h: choose_fused_form reads about a call of n_draws on this handle -- the
-// one place that reads the handle for it (no allocation: every un-batched call with option
-// "deterministic" = 2 comes through here).
-tc::FusedQuery fused_query(const tc_table* t, int64_t n_draws, int n_gauss, unsigned flags) {
+// one place that puts the handle's state and the call's side by side for it (no allocation:
+// every un-batched call with option "deterministic" = 2 comes through here).
+tc::FusedQuery fused_query(const tc_table* t, const Call& call, int64_t n_draws, int n_gauss,
+                           unsigned flags) {
   const tc::QuadLayout& total = t->quad_total.layout;
   const tc::QuadLayout& by_type = t->quad_by_type.layout;
   tc::FusedQuery q;
@@ -919,17 +912,17 @@ tc::FusedQuery fused_query(const tc_table* t, int64_t n_draws, int n_gauss, unsi
   q.n_draws = n_draws;
   q.n_gauss = n_gauss;
   q.flags = flags;
-  q.alone = runs_alone(t);
-  q.async = t->async_lane >= 0;
-  q.sync_spread = t->sync_spread;
-  q.chain = t->chain;
+  q.alone = call.alone;
+  q.async = call.async;
+  q.sync_spread = call.sync_spread;
+  q.chain = call.chain;
   q.trace = t->tuning.trace != 0;
-  q.likelihood = t->fuse_chi2_out != nullptr;
+  q.likelihood = call.chi2_out != nullptr;
   q.fused = t->tuning.fused;
-  q.fused_min_draws = t->tuning.fused_min_draws;
+  q.fused_min_draws = call.fused_min_draws;
   q.fused_max_draws = t->tuning.fused_max_draws;
   q.fused_waves = t->tuning.fused_waves;
-  q.fused_draws = t->tuning.fused_draws;
+  q.fused_draws = call.fused_draws;
   q.fused_spread = t->tuning.fused_spread;
   q.fused_spread_min = t->tuning.fused_spread_min;
   q.fused_spread_rounds = t->tuning.fused_spread_rounds;
@@ -946,17 +939,18 @@ bool batch_invariant_form(tc_table* t, int n_gauss, unsigned flags) {
     tc_table* self = t;
     const CrossFused& cf =
         *choose_cross_fused(&self, 1, &t->cross_fused, &t->cross_fused_wide, 1, flags, &status);
-    return status == TC_OK && cross_fused_eligible(t, cf, 1, n_gauss, flags, true);
+    return status == TC_OK &&
+           cross_fused_eligible(t, probe_call(t, /*pinned=*/true), cf, 1, n_gauss, flags);
   }
-  return tc::choose_fused_form(fused_query(t, 1, n_gauss, flags)).waves != 0;
+  return tc::choose_fused_form(fused_query(t, probe_call(t), 1, n_gauss, flags)).waves != 0;
 }
 
 
-int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n_theta,
-              int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
-              double* xi_device) {
+int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* theta_device,
+              int n_theta, int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
+              double* xi_device, bool* chi2_written) {
   Range range("occupation + contraction + finalisation (one launch)");
-  tc_table::Lane& lane = t->lanes[t->cur];
+  tc_table::Lane& lane = t->lanes[call.lane];
   hipStream_t stream = lane.stream;
   Quadrature* q = nullptr;
   int status = get_quadrature(t, n_gauss, &q);
@@ -1038,12 +1032,11 @@ int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n
       (uint32_t)((size_t)q_table.layout.n_units * (size_t)((t->quad_tiling.n_u + 1) / 2) * 1024);
   fa.ngal = ngal_device;
   fa.xi = xi_device;
-  t->chi2_fused = false;
-  if (t->fuse_chi2_out != nullptr) {
-    fa.chi2_data = t->fuse_chi2_data;
-    fa.chi2 = t->fuse_chi2_out;
+  if (call.chi2_out != nullptr) {
+    fa.chi2_data = call.chi2_data;
+    fa.chi2 = call.chi2_out;
     fa.xi = nullptr;
-    t->chi2_fused = true;
+    *chi2_written = true;
   }
   const int lds = tc::fused_lds_bytes(fa.dens_rows, waves, draws);
   const dim3 grid((unsigned)((n_draws + draws - 1) / draws)), block(64 * waves);
@@ -1098,7 +1091,7 @@ int run_fused(tc_table* t, tc::FusedForm form, const double* theta_device, int n
   t->last_waves = waves;
   t->last_splits = 0;
   t->last_lds = lds;
-  t->prev = t->force_lane >= 0 ? -1 : t->cur;
+  t->prev = call.pinned ? -1 : call.lane;
   return TC_OK;
 }
 
@@ -1447,20 +1440,20 @@ CrossLds cross_lds_layout(const CrossFused& cf, int n_r, bool separate, int defe
 }
 }  // namespace
 
-bool cross_fused_eligible(const tc_table* t0, const CrossFused& cf, int64_t n_draws, int n_gauss,
-                          unsigned flags, bool alone) {
-  if (cf.rows == 0 || t0->tuning.fused == 0 || n_gauss != 10 || t0->chain || t0->tuning.trace)
+bool cross_fused_eligible(const tc_table* t0, const Call& call, const CrossFused& cf,
+                          int64_t n_draws, int n_gauss, unsigned flags) {
+  if (cf.rows == 0 || t0->tuning.fused == 0 || n_gauss != 10 || call.chain || t0->tuning.trace)
     return false;
   if (flags & TC_FLAG_LEAUTHAUD11) return false;
   const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
   const tc::NodeGroups& groups = t0->node_groups;
   if (separate && (groups.n_central_groups == 0 || groups.n_central_groups == groups.n_groups ||
-                   t0->fuse_chi2_out != nullptr))
+                   call.chi2_out != nullptr))
     return false;
   if (cf.rows > tc::kCrossSmallRows &&
       cross_lds_layout(cf, t0->n_r, separate).bytes > kMaxLdsBytes - 256)
     return false;
-  if (t0->fuse_chi2_out != nullptr && t0->n_r > 32) return false;
+  if (call.chi2_out != nullptr && t0->n_r > 32) return false;
   // A workgroup carries 64 draws through the bins; batches of few tiles get several workgroups
   // per tile (run_cross_fused), so that the one-launch forms pay from a few hundred draws on.
   // (tools/r04_cross_scan.py, the reference's AbacusSummit table, us per step one launch / three
@@ -1469,17 +1462,18 @@ bool cross_fused_eligible(const tc_table* t0, const CrossFused& cf, int64_t n_dr
   // from the smallest batches on (256 draws 8.7 us against 13.4 for the three kernels, 1024: 9.3 /
   // 19.4, 4096: 25.6 / 55.7).
   if (t0->tuning.deterministic >= 2) return true;        // (one form whatever the batch)
-  const int64_t min_draws = t0->tuning.fused_min_draws > 0 ? t0->tuning.fused_min_draws
+  const int64_t min_draws = call.fused_min_draws > 0 ? call.fused_min_draws
                             : cf.rows <= tc::kCrossSmallRows ? 192
                                                              : t0->tuning.cross_min_draws;
   if (n_draws < min_draws) return false;
-  return t0->tuning.fused >= 2 || !alone;
+  return t0->tuning.fused >= 2 || !call.alone;
 }
 
-int run_cross_fused(tc_table* t0, const CrossFused& cf, const tc::CrossFusedArgs* interp,
-                    const double* theta_device, int n_theta, int64_t n_draws, unsigned flags,
-                    double* ngal_device, double* xi_device, hipStream_t stream,
-                    DeviceBuffer* partial, DeviceBuffer* counters) {
+int run_cross_fused(tc_table* t0, const Call& call, const CrossFused& cf,
+                    const tc::CrossFusedArgs* interp, const double* theta_device, int n_theta,
+                    int64_t n_draws, unsigned flags, double* ngal_device, double* xi_device,
+                    hipStream_t stream, DeviceBuffer* partial, DeviceBuffer* counters,
+                    bool* chi2_written) {
   Range range("occupation + contraction + finalisation (mode cross, one launch)");
   Quadrature* q = nullptr;
   int status = get_quadrature(t0, 10, &q);
@@ -1551,12 +1545,11 @@ int run_cross_fused(tc_table* t0, const CrossFused& cf, const tc::CrossFusedArgs
   ca.priority = (t0->tuning.prio_fused_occ & 3) | ((t0->tuning.prio_fused_out & 3) << 4);
   ca.ngal = ngal_device;
   ca.xi = xi_device;
-  t0->chi2_fused = false;
-  if (t0->fuse_chi2_out != nullptr) {
-    ca.chi2_data = t0->fuse_chi2_data;
-    ca.chi2 = t0->fuse_chi2_out;
+  if (call.chi2_out != nullptr) {
+    ca.chi2_data = call.chi2_data;
+    ca.chi2 = call.chi2_out;
     ca.xi = nullptr;
-    t0->chi2_fused = true;
+    *chi2_written = true;
   }
   const int lds = layout.bytes;
   const int64_t n_tiles = (n_draws + 63) / 64;
@@ -1567,7 +1560,7 @@ int run_cross_fused(tc_table* t0, const CrossFused& cf, const tc::CrossFusedArgs
   // (option "deterministic" = 2: ONE workgroup per tile whatever the batch -- the shares of a
   // tile's groups, and with them the order of a draw's sums, follow the number of tiles)
   const int cross_target = t0->tuning.deterministic >= 2 ? 0
-                           : t0->sync_cross_target > 0   ? t0->sync_cross_target
+                           : call.cross_target > 0       ? call.cross_target
                                                          : t0->tuning.cross_target;
   int n_splits = 1;
   if (cf.rows <= tc::kCrossSmallRows) {

@@ -320,36 +320,87 @@ int autotune(tc_table* t, unsigned flags);
 // a handful of table shapes and is up to 1.4 x behind the best form elsewhere (VERDICT r04 item
 // 5).  So a handle that sees a LOOP of pipelined or asynchronous calls measures: the
 // autotune_after-th such call with one combination of flags runs option "autotune" for it.
-int maybe_autotune(tc_table* t, int n_gauss, unsigned flags) {
+int maybe_autotune(tc_table* t, const Call& call, int n_gauss, unsigned flags) {
+  // (the chunks of a synchronous call come with their form: no measurement inside one)
   if (t->autotuning || t->tuning.autotune_after <= 0 || t->tuning.deterministic != 0 ||
       n_gauss != 10 || t->tuning.fused != 1 ||
-      t->tuning.fused_min_draws != 0 || t->tuning.fused_draws != 0 || t->tuning.fused_waves != 0)
+      call.fused_min_draws != 0 || call.fused_draws != 0 || t->tuning.fused_waves != 0)
     return TC_OK;
-  const bool pipelined = t->async_lane >= 0 || (t->force_lane < 0 && t->tuning.pipeline &&
-                                                t->n_lanes > 1);
+  const bool pipelined = call.async || (!call.pinned && t->tuning.pipeline && t->n_lanes > 1);
   // (only where the one-launch forms can serve the table at all)
   if (!pipelined || !t->quad || t->compute_dtype != TC_DTYPE_F64 || t->mode != TC_MODE_AUTO ||
-      t->quad_tiling.n_rtiles != 1 || t->n_r > 20 || t->chain || t->tuning.trace ||
-      t->fuse_chi2_out != nullptr)
+      t->quad_tiling.n_rtiles != 1 || t->n_r > 20 || call.chain || t->tuning.trace ||
+      call.chi2_out != nullptr)
     return TC_OK;
   const unsigned key = flags & (TC_FLAG_SEPARATE_GAL_TYPE | TC_FLAG_MODULATE_WITH_CENOCC |
                                 TC_FLAG_ASSEMBIAS | TC_FLAG_LEAUTHAUD11);
   if (t->autotuned.count(key) != 0) return TC_OK;
   if (++t->pipelined_calls[key] < t->tuning.autotune_after) return TC_OK;
   t->pipelined_calls[key] = 0;
-  // (the measurement calls this entry point itself, with its own lanes and options)
-  const int saved_force = t->force_lane, saved_async = t->async_lane, saved_cur = t->cur;
+  // (the measurement makes device-pointer calls of its own, on the lanes of the rotation)
   t->autotuning = true;
-  t->force_lane = t->async_lane = -1;
   const int status = autotune(t, key);
   t->autotuning = false;
-  t->force_lane = saved_force;
-  t->async_lane = saved_async;
-  t->cur = saved_cur;
   if (status != TC_OK) {
     // (a table the measurement cannot serve: keep the estimate, do not try again)
     t->tuning.autotune_after = 0;
     (void)tc_table_synchronize(t);
+  }
+  return TC_OK;
+}
+
+// A prediction of n_draws > 0 draws on device pointers as `call` describes it (the arguments
+// are checked): what tc_predict_zheng07_batch_device does, and every host-array and
+// asynchronous entry point underneath.  *chi2_written: the form that ran wrote the call's
+// likelihood (call.chi2_out) itself and left xi alone.
+int predict_device(tc_table* t, const Call& call, const double* theta_device, int n_theta,
+                   int64_t n_draws, int n_gauss, unsigned flags, double* ngal_device,
+                   double* xi_device, bool* chi2_written = nullptr) {
+  TC_HIP(hipSetDevice(t->device));
+  int status = TC_OK;
+  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
+  const int n_comp = separate ? t->plan.n_components : 1;
+  // a loop of pipelined / asynchronous calls: its autotune_after-th call measures which form
+  // serves which batch size on this table (about half a second, once per combination of flags)
+  if ((status = maybe_autotune(t, call, n_gauss, flags)) != TC_OK) return status;
+  t->cur = call.lane;
+  tc_table::Lane& lane = t->lanes[call.lane];
+  const int64_t slab = max_slab(t);
+  for (int64_t begin = 0; begin < n_draws; begin += slab) {
+    const int64_t n = std::min(slab, n_draws - begin);
+    const int64_t ldb = (n + 63) / 64 * 64;
+    if (t->mode == TC_MODE_CROSS && !t->cross_host.empty() && t->tuning.fused != 0) {
+      // mode cross: one launch per batch where it pays (launch.hip)
+      tc_table* self = t;
+      const CrossFused& cf = *choose_cross_fused(&self, 1, &t->cross_fused, &t->cross_fused_wide,
+                                                 n, flags, &status);
+      if (status != TC_OK) return status;
+      if (cross_fused_eligible(t, call, cf, n, n_gauss, flags)) {
+        status = run_cross_fused(t, call, cf, nullptr, theta_device + begin * n_theta,
+                                 n_theta, n, flags, ngal_device + begin * (separate ? 2 : 1),
+                                 xi_device + begin * n_comp * t->n_r, lane.stream,
+                                 &lane.partial, &lane.cross_counters, chi2_written);
+        if (status != TC_OK) return status;
+        t->prev = call.pinned ? -1 : call.lane;
+        continue;
+      }
+    }
+    const tc::FusedForm form = tc::choose_fused_form(fused_query(t, call, n, n_gauss, flags));
+    if (form.waves != 0) {
+      status = run_fused(t, call, form, theta_device + begin * n_theta, n_theta, n, n_gauss,
+                         flags, ngal_device + begin * (separate ? 2 : 1),
+                         xi_device + begin * n_comp * t->n_r, chi2_written);
+      if (status != TC_OK) return status;
+      continue;
+    }
+    status = run_occupation(t, call, theta_device + begin * n_theta, n_theta, n, ldb,
+                            n_gauss, flags, nullptr);
+    if (status != TC_OK) return status;
+    status = run_contraction(t, call, n, ldb, flags,
+                             ngal_device + begin * (separate ? 2 : 1),
+                             xi_device + begin * n_comp * t->n_r, chi2_written);
+    if (status != TC_OK) return status;
   }
   return TC_OK;
 }
@@ -365,57 +416,8 @@ int tc_predict_zheng07_batch_device(tc_table* t, const double* theta_device,
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(ngal_device && xi_device, "output pointer is NULL");
-  TC_HIP(hipSetDevice(t->device));
-  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  const int n_comp = separate ? t->plan.n_components : 1;
-  t->chi2_fused = false;     // (set by whichever form writes the likelihood itself)
-  if (t->force_lane >= 0)
-    t->cur = t->force_lane;
-  else if (t->async_lane >= 0)
-    t->cur = t->async_lane;
-  else
-    t->cur = t->tuning.pipeline ? (int)(t->device_calls++ % t->n_lanes) : 0;
-  // a loop of pipelined / asynchronous calls: its autotune_after-th call measures which form
-  // serves which batch size on this table (about half a second, once per combination of flags)
-  if ((status = maybe_autotune(t, n_gauss, flags)) != TC_OK) return status;
-  const int64_t slab = max_slab(t);
-  for (int64_t begin = 0; begin < n_draws; begin += slab) {
-    const int64_t n = std::min(slab, n_draws - begin);
-    const int64_t ldb = (n + 63) / 64 * 64;
-    if (t->mode == TC_MODE_CROSS && !t->cross_host.empty() && t->tuning.fused != 0) {
-      // mode cross: one launch per batch where it pays (launch.hip)
-      tc_table* self = t;
-      const CrossFused& cf = *choose_cross_fused(&self, 1, &t->cross_fused, &t->cross_fused_wide,
-                                                 n, flags, &status);
-      if (status != TC_OK) return status;
-      if (cross_fused_eligible(t, cf, n, n_gauss, flags, runs_alone(t))) {
-        status = run_cross_fused(t, cf, nullptr, theta_device + begin * n_theta,
-                                 n_theta, n, flags, ngal_device + begin * (separate ? 2 : 1),
-                                 xi_device + begin * n_comp * t->n_r, t->lanes[t->cur].stream,
-                                 &t->lanes[t->cur].partial, &t->lanes[t->cur].cross_counters);
-        if (status != TC_OK) return status;
-        t->prev = t->force_lane >= 0 ? -1 : t->cur;
-        continue;
-      }
-    }
-    const tc::FusedForm form = tc::choose_fused_form(fused_query(t, n, n_gauss, flags));
-    if (form.waves != 0) {
-      status = run_fused(t, form, theta_device + begin * n_theta, n_theta, n, n_gauss, flags,
-                         ngal_device + begin * (separate ? 2 : 1),
-                         xi_device + begin * n_comp * t->n_r);
-      if (status != TC_OK) return status;
-      continue;
-    }
-    status = run_occupation(t, theta_device + begin * n_theta, n_theta, n, ldb,
-                            n_gauss, flags, nullptr);
-    if (status != TC_OK) return status;
-    status = run_contraction(t, n, ldb, flags,
-                             ngal_device + begin * (separate ? 2 : 1),
-                             xi_device + begin * n_comp * t->n_r);
-    if (status != TC_OK) return status;
-  }
-  return TC_OK;
+  return predict_device(t, make_call(t, /*pinned=*/false), theta_device, n_theta, n_draws,
+                        n_gauss, flags, ngal_device, xi_device);
 }
 
 }  // extern "C"
@@ -498,6 +500,19 @@ void resident_auto_served(tc_table* t, bool relaunched) {
   }
   r.auto_window = r.auto_relaunches = 0;
 }
+
+// Nobody asked for the resident kernel: whatever went wrong with it (it keeps leaving before it
+// answers, its mailbox or aperture cannot be allocated, ...) is not the caller's business.  Stop
+// it, stay away from it for a while -- for good after three such failures -- and let the caller
+// serve THIS call by a launch.
+void resident_auto_failed(tc_table* t) {
+  (void)resident_stop(t);
+  (void)hipGetLastError();
+  tc_table::Resident& r = t->resident;
+  r.auto_backoff = r.auto_backoff_calls;
+  r.auto_streak = r.auto_window = r.auto_relaunches = 0;
+  if (++r.auto_failures >= 3) r.auto_mode = false;
+}
 }  // namespace
 
 extern "C" {
@@ -531,16 +546,7 @@ int tc_predict_zheng07_many(tc_table* t, const double* theta, int n_theta, int n
       resident_auto_served(t, t->resident.relaunches != before);
       return status;
     }
-    // Nobody asked for the resident kernel: whatever went wrong with it (it keeps leaving
-    // before it answers, its mailbox or aperture cannot be allocated, ...) is not the caller's
-    // business.  Stop it, stay away from it for a while -- for good after three such failures
-    // -- and serve THIS call by a launch.
-    (void)resident_stop(t);
-    (void)hipGetLastError();
-    tc_table::Resident& r = t->resident;
-    r.auto_backoff = r.auto_backoff_calls;
-    r.auto_streak = r.auto_window = r.auto_relaunches = 0;
-    if (++r.auto_failures >= 3) r.auto_mode = false;
+    resident_auto_failed(t);     // (and serve this call by a launch)
   }
   if (t->resident.enabled && ensemble_eligible(t, n_walkers, n_gauss, flags)) {
     status = ensemble_predict(t, theta, n_theta, n_walkers, n_gauss, flags, ngal, xi);
@@ -616,13 +622,7 @@ int tc_predict_zheng07_joint(tc_table* const* tables, int n_tables, const double
         n_tables = k;             // (collect what was posted, then report)
         break;
       }
-      // (nobody asked for the resident kernel: tc_predict_zheng07_many's fallback)
-      (void)resident_stop(t);
-      (void)hipGetLastError();
-      tc_table::Resident& r = t->resident;
-      r.auto_backoff = r.auto_backoff_calls;
-      r.auto_streak = r.auto_window = r.auto_relaunches = 0;
-      if (++r.auto_failures >= 3) r.auto_mode = false;
+      resident_auto_failed(t);    // (tc_predict_zheng07_many's fallback)
       route[k] = kLaunched;
     }
     int status = TC_OK;
@@ -647,13 +647,7 @@ int tc_predict_zheng07_joint(tc_table* const* tables, int n_tables, const double
       if (status == TC_OK && automatic[k])
         resident_auto_served(t, t->resident.relaunches != relaunches[k]);
       if (status != TC_OK && automatic[k]) {
-        // (as above: stop, back off, serve this table by a launch)
-        (void)resident_stop(t);
-        (void)hipGetLastError();
-        tc_table::Resident& r = t->resident;
-        r.auto_backoff = r.auto_backoff_calls;
-        r.auto_streak = r.auto_window = r.auto_relaunches = 0;
-        if (++r.auto_failures >= 3) r.auto_mode = false;
+        resident_auto_failed(t);  // (as above: serve this table by a launch)
         status = launch_single_draw(t, theta, n_theta, 1, n_gauss, flags, &t->single_ws,
                                     t->stream);
         if (status == TC_OK)
@@ -673,7 +667,7 @@ int tc_predict_zheng07_joint(tc_table* const* tables, int n_tables, const double
 namespace {
 int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws, int n_gauss,
                   unsigned flags, const double* data, const double* precision, double* ngal,
-                  double* second, bool chi2, int64_t* ticket_out, bool staging,
+                  double* second, bool chi2, int64_t* ticket_out, const Call* chunk,
                   hipEvent_t wait_for = nullptr, hipEvent_t kernels_done = nullptr);
 
 // How many chunks a synchronous host call of n_draws with out_bytes of results is cut into
@@ -764,23 +758,23 @@ int predict_chunked(tc_table* t, const double* theta, int n_theta, int64_t n_dra
   // (one form for every chunk size: the one-launch form with sync_form draws per workgroup
   // wherever it serves the table at all, not only from the batch size on where it pays)
   // (mode cross: the workgroups of ALL chunks together should fill the chip once -- see
-  // tc_table::sync_cross_target)
-  t->sync_cross_target = 512 / n_chunks;
+  // Call::cross_target)
+  Call hints = probe_call(t);
+  hints.async = true;                      // (as the chunks will run)
+  hints.chain = false;
+  hints.cross_target = 512 / n_chunks;
   // (the latency form for every chunk when the whole call fits one round of 40-draw workgroups:
   // the chunks' launches then fill the chip together)
-  t->sync_spread = n_draws >= t->tuning.fused_spread_min &&
-                   (n_draws + 39) / 40 + n_chunks <= (int64_t)t->n_cus;
-  tc::FusedQuery whole = fused_query(t, n_draws, n_gauss, flags);
-  whole.async = true;                      // (as its chunks will run)
-  const bool spread = t->sync_spread && tc::choose_fused_form(whole).draws == 40;
-  t->sync_spread = spread;
-  const int saved_draws = t->tuning.fused_draws, saved_min = t->tuning.fused_min_draws;
-  if (spread) {
-    t->tuning.fused_draws = 40;
-  } else if (t->tuning.sync_form != 0 && saved_draws == 0 && t->tuning.fused == 1 &&
-      t->tuning.deterministic < 2) {
-    t->tuning.fused_draws = t->tuning.sync_form;
-    if (saved_min == 0) t->tuning.fused_min_draws = 1;
+  hints.sync_spread = n_draws >= t->tuning.fused_spread_min &&
+                      (n_draws + 39) / 40 + n_chunks <= (int64_t)t->n_cus;
+  hints.sync_spread = hints.sync_spread &&
+      tc::choose_fused_form(fused_query(t, hints, n_draws, n_gauss, flags)).draws == 40;
+  if (hints.sync_spread) {
+    hints.fused_draws = 40;
+  } else if (t->tuning.sync_form != 0 && hints.fused_draws == 0 && t->tuning.fused == 1 &&
+             t->tuning.deterministic < 2) {
+    hints.fused_draws = t->tuning.sync_form;
+    if (hints.fused_min_draws == 0) hints.fused_min_draws = 1;
   }
   for (int k = 0; k < n_chunks && status == TC_OK; ++k) {
     const int64_t begin = begins[k], n = begins[k + 1] - begin;
@@ -788,15 +782,11 @@ int predict_chunked(tc_table* t, const double* theta, int n_theta, int64_t n_dra
     // (the chunk's results side by side in the staging area: [ngal | xi] -- one copy command)
     double* out = h_out + begin * (ngal_cols + second_cols);
     status = predict_async(t, h_theta + begin * n_theta, n_theta, n, n_gauss, flags, data,
-                           precision, out, out + n * ngal_cols, chi2, &tickets[k], true,
+                           precision, out, out + n * ngal_cols, chi2, &tickets[k], &hints,
                            staggered && k > 0 ? t->chunk_events[k - 1] : nullptr,
                            staggered ? t->chunk_events[k] : nullptr);
     if (status != TC_OK) n_chunks = k;       // (wait for what was queued, then report)
   }
-  t->tuning.fused_draws = saved_draws;
-  t->tuning.fused_min_draws = saved_min;
-  t->sync_cross_target = 0;
-  t->sync_spread = false;
   for (int k = 0; k < n_chunks; ++k) {
     const int64_t begin = begins[k], n = begins[k + 1] - begin;
     const int waited = tc_table_wait(t, tickets[k]);
@@ -851,10 +841,8 @@ int tc_predict_zheng07_batch(tc_table* t, const double* theta, int n_theta,
       t->h_out.reserve(out_bytes) == TC_OK) {
     memcpy(t->h_in.ptr, theta, theta_bytes);
     double* h = (double*)t->h_out.ptr;
-    t->force_lane = 0;
-    status = tc_predict_zheng07_batch_device(t, (const double*)t->h_in.ptr, n_theta,
-                                             n_draws, n_gauss, flags, h, h + ngal_count);
-    t->force_lane = -1;
+    status = predict_device(t, make_call(t, /*pinned=*/true), (const double*)t->h_in.ptr,
+                            n_theta, n_draws, n_gauss, flags, h, h + ngal_count);
     if (status != TC_OK) return status;
     TC_HIP(hipStreamSynchronize(t->stream));
     memcpy(ngal, h, ngal_count * 8);
@@ -870,11 +858,9 @@ int tc_predict_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   if (status != TC_OK) return status;
   status = copy_in(&t->h_in, t->theta.ptr, theta, theta_bytes, t->stream);
   if (status != TC_OK) return status;
-  t->force_lane = 0;
-  status = tc_predict_zheng07_batch_device(
-      t, (const double*)t->theta.ptr, n_theta, n_draws, n_gauss, flags,
-      (double*)t->out_ngal.ptr, (double*)t->out_xi.ptr);
-  t->force_lane = -1;
+  status = predict_device(t, make_call(t, /*pinned=*/true), (const double*)t->theta.ptr,
+                          n_theta, n_draws, n_gauss, flags, (double*)t->out_ngal.ptr,
+                          (double*)t->out_xi.ptr);
   if (status != TC_OK) return status;
   return copy_out(&t->h_out, ngal, ngal_count, t->out_ngal.ptr, xi, xi_count,
                   t->out_xi.ptr, t->stream);
@@ -904,6 +890,37 @@ int upload_chi2_data(tc_table* t, const double* data, const double* precision) {
   return TC_OK;
 }
 
+
+// A likelihood of 0 < n_draws <= max_slab(t) draws on device pointers as `call` describes it
+// (the arguments are checked): tc_chi2_zheng07_batch_device and its asynchronous twin.
+int chi2_on_device(tc_table* t, Call call, const double* theta_device, int n_theta, int64_t n_draws,
+                int n_gauss, unsigned flags, const double* data, const double* precision,
+                double* ngal_device, double* chi2_device) {
+  TC_HIP(hipSetDevice(t->device));
+  int status = TC_OK;
+  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  status = upload_chi2_data(t, data, precision);
+  if (status != TC_OK) return status;
+  // xi stays in a workspace of the lane the call runs on; the lane's `finished` event is
+  // re-recorded behind the chi2 kernel, so the next call on this lane (whose finalisation
+  // waits for that event through the chain of lanes) cannot overwrite it early
+  tc_table::Lane& lane = t->lanes[call.lane];
+  status = lane.xi.reserve((size_t)n_draws * t->n_r * 8, lane.stream);
+  if (status != TC_OK) return status;
+  call.chi2_data = (const double*)t->chi2_data.ptr;
+  call.chi2_out = chi2_device;
+  bool written = false;
+  status = predict_device(t, call, theta_device, n_theta, n_draws, n_gauss, flags, ngal_device,
+                          (double*)lane.xi.ptr, &written);
+  if (status != TC_OK) return status;
+  if (written) return TC_OK;            // (the finalisation kernel wrote chi2 itself)
+  status = launch_chi2((const double*)lane.xi.ptr, n_draws, t->n_r, call.chi2_data,
+                       call.chi2_data + t->n_r, chi2_device, lane.stream);
+  if (status != TC_OK) return status;
+  if (!call.pinned && call.chain) TC_HIP(hipEventRecord(lane.finished, lane.stream));
+  return TC_OK;
+}
+
 }  // namespace
 
 int tc_chi2_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
@@ -918,37 +935,8 @@ int tc_chi2_zheng07_batch_device(tc_table* t, const double* theta_device, int n_
   TC_CHECK(data && precision && ngal_device && chi2_device, "NULL pointer");
   TC_CHECK(n_draws <= max_slab(t), "at most %lld draws per call",
            (long long)max_slab(t));
-  TC_HIP(hipSetDevice(t->device));
-  if (t->resident.running) {
-    const int stopped = resident_stop(t);
-    if (stopped != TC_OK) return stopped;
-  }
-  status = upload_chi2_data(t, data, precision);
-  if (status != TC_OK) return status;
-  // xi stays in a workspace of the lane the call runs on; the lane's `finished` event is
-  // re-recorded behind the chi2 kernel, so the next call on this lane (whose finalisation
-  // waits for that event through the chain of lanes) cannot overwrite it early
-  const int lane_index =
-      t->force_lane >= 0   ? t->force_lane
-      : t->async_lane >= 0 ? t->async_lane
-      : t->tuning.pipeline ? (int)(t->device_calls % t->n_lanes)
-                           : 0;
-  tc_table::Lane& lane = t->lanes[lane_index];
-  status = lane.xi.reserve((size_t)n_draws * t->n_r * 8, lane.stream);
-  if (status != TC_OK) return status;
-  const double* d_data = (const double*)t->chi2_data.ptr;
-  t->fuse_chi2_data = d_data;
-  t->fuse_chi2_out = chi2_device;
-  status = tc_predict_zheng07_batch_device(t, theta_device, n_theta, n_draws, n_gauss, flags,
-                                           ngal_device, (double*)lane.xi.ptr);
-  t->fuse_chi2_out = nullptr;
-  if (status != TC_OK) return status;
-  if (t->chi2_fused) return TC_OK;      // (the finalisation kernel wrote chi2 itself)
-  status = launch_chi2((const double*)lane.xi.ptr, n_draws, t->n_r, d_data, d_data + t->n_r,
-                       chi2_device, lane.stream);
-  if (status != TC_OK) return status;
-  if (t->force_lane < 0 && t->chain) TC_HIP(hipEventRecord(lane.finished, lane.stream));
-  return TC_OK;
+  return chi2_on_device(t, make_call(t, /*pinned=*/false), theta_device, n_theta, n_draws, n_gauss,
+                     flags, data, precision, ngal_device, chi2_device);
 }
 
 int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
@@ -991,16 +979,14 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   }
   double* d_chi2 = d_ngal + n_draws;
   // (one slab: the finalisation kernel may write the likelihood itself)
-  const bool fuse = n_draws <= max_slab(t);
-  t->force_lane = 0;
-  t->fuse_chi2_data = d_data;
-  t->fuse_chi2_out = fuse ? d_chi2 : nullptr;
-  status = tc_predict_zheng07_batch_device(t, theta_device, n_theta, n_draws, n_gauss, flags,
-                                           d_ngal, (double*)t->out_xi.ptr);
-  t->fuse_chi2_out = nullptr;
-  t->force_lane = -1;
+  Call call = make_call(t, /*pinned=*/true);
+  call.chi2_data = d_data;
+  call.chi2_out = n_draws <= max_slab(t) ? d_chi2 : nullptr;
+  bool written = false;
+  status = predict_device(t, call, theta_device, n_theta, n_draws, n_gauss, flags, d_ngal,
+                          (double*)t->out_xi.ptr, &written);
   if (status != TC_OK) return status;
-  if (!(fuse && t->chi2_fused))
+  if (!written)
     status = launch_chi2((const double*)t->out_xi.ptr, n_draws, n_r, d_data, d_precision,
                          d_chi2, t->stream);
   if (status != TC_OK) return status;
@@ -1027,7 +1013,7 @@ int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
   int status = TC_OK;
   if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
   const bool pinned = request == GradLane::kPinned;
-  t->cur = pinned || !t->tuning.pipeline ? 0 : (int)(t->device_calls++ % t->n_lanes);
+  t->cur = next_lane(pinned, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls);
   hipStream_t stream = t->lanes[t->cur].stream;
   status = for_each_slab(n_draws, max_slab(t),
                          [&](int64_t begin, int64_t n) { return run(begin, n, stream); });
@@ -1374,15 +1360,16 @@ int next_ticket(tc_table* t, tc_table::Ticket** out) {
 // (upload, three kernels, download, the ticket's event) is queued on that lane's stream, so
 // lanes overlap each other's copies and kernels and nothing orders one ticket against
 // another.
-// `staging`: the buffers are the library's own page-locked staging areas (hipHostMalloc: the
-// device sees them at the same addresses) -- the chunks of a synchronous call, predict_chunked.
+// `chunk` (or NULL): the call is a chunk of a synchronous call (predict_chunked) and this is what
+// every chunk carries; the buffers are then the library's own page-locked staging areas
+// (hipHostMalloc: the device sees them at the same addresses).
 // wait_for / kernels_done (the chunks of a synchronous call with large results): the call's
 // kernels start behind `wait_for`, and `kernels_done` is recorded between its kernels and its
 // download -- so that the chunks' kernels run one after the other, each with the chip to itself,
 // while the previous chunk's results travel.
 int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws, int n_gauss,
                   unsigned flags, const double* data, const double* precision, double* ngal,
-                  double* second, bool chi2, int64_t* ticket_out, bool staging,
+                  double* second, bool chi2, int64_t* ticket_out, const Call* chunk,
                   hipEvent_t wait_for, hipEvent_t kernels_done) {
   int status = check_predict_args(t, theta, n_theta, n_draws, n_gauss, flags);
   if (status != TC_OK) return status;
@@ -1398,6 +1385,7 @@ int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws
   const size_t second_count = chi2 ? (size_t)n_draws : (size_t)n_draws * n_comp * t->n_r;
   const size_t theta_bytes = (size_t)n_draws * n_theta * sizeof(double);
   void *theta_seen = nullptr, *ngal_seen = nullptr, *second_seen = nullptr;
+  const bool staging = chunk != nullptr;
   if (staging) {
     theta_seen = (void*)theta;
     ngal_seen = ngal;
@@ -1414,8 +1402,12 @@ int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws
     if (stopped != TC_OK) return stopped;
   }
   tc_table::Ticket* ticket = nullptr;
-  const int lane_index = t->tuning.pipeline ? (int)(t->device_calls++ % t->n_lanes) : 0;
-  tc_table::Lane& lane = t->lanes[lane_index];
+  // (the finalisations of asynchronous calls are never chained: each has its ticket)
+  Call call = chunk != nullptr ? *chunk : probe_call(t);
+  call.lane = next_lane(false, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls);
+  call.async = true;
+  call.chain = false;
+  tc_table::Lane& lane = t->lanes[call.lane];
   if (n_draws > 0) {
     // Which arrays the kernels address in the caller's page-locked memory themselves and
     // which travel by copy command: see Tuning::async_direct_in / async_direct_out.
@@ -1445,15 +1437,10 @@ int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws
                             lane.stream));
     }
     if (wait_for != nullptr) TC_HIP(hipStreamWaitEvent(lane.stream, wait_for, 0));
-    const bool saved_chain = t->chain;
-    t->async_lane = lane_index;
-    t->chain = false;
-    status = chi2 ? tc_chi2_zheng07_batch_device(t, d_theta, n_theta, n_draws, n_gauss, flags,
-                                                 data, precision, d_ngal, d_second)
-                  : tc_predict_zheng07_batch_device(t, d_theta, n_theta, n_draws, n_gauss,
-                                                    flags, d_ngal, d_second);
-    t->async_lane = -1;
-    t->chain = saved_chain;
+    status = chi2 ? chi2_on_device(t, call, d_theta, n_theta, n_draws, n_gauss, flags, data,
+                                precision, d_ngal, d_second)
+                  : predict_device(t, call, d_theta, n_theta, n_draws, n_gauss, flags, d_ngal,
+                                   d_second);
     if (status != TC_OK) return status;
     if (kernels_done != nullptr) TC_HIP(hipEventRecord(kernels_done, lane.stream));
     Range range("download");
@@ -1483,7 +1470,7 @@ int tc_predict_zheng07_batch_async(tc_table* t, const double* theta, int n_theta
                                    int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
                                    double* xi, int64_t* ticket) {
   return predict_async(t, theta, n_theta, n_draws, n_gauss, flags, nullptr, nullptr, ngal, xi,
-                       false, ticket, false);
+                       false, ticket, nullptr);
 }
 
 int tc_chi2_zheng07_batch_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
@@ -1491,7 +1478,7 @@ int tc_chi2_zheng07_batch_async(tc_table* t, const double* theta, int n_theta, i
                                 const double* precision, double* ngal, double* chi2,
                                 int64_t* ticket) {
   return predict_async(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal, chi2,
-                       true, ticket, false);
+                       true, ticket, nullptr);
 }
 
 int tc_table_wait(tc_table* t, int64_t ticket) {
@@ -1553,8 +1540,8 @@ int tc_mean_occupation_zheng07_batch(tc_table* t, const double* theta, int n_the
     TC_HIP(hipMemcpyAsync(t->theta.ptr, theta + begin * n_theta,
                           (size_t)n * n_theta * 8, hipMemcpyHostToDevice, t->stream));
     t->cur = 0;
-    status = run_occupation(t, (const double*)t->theta.ptr, n_theta, n, ldb, n_gauss,
-                            flags, (double*)t->occupation.ptr);
+    status = run_occupation(t, probe_call(t), (const double*)t->theta.ptr, n_theta, n, ldb,
+                            n_gauss, flags, (double*)t->occupation.ptr);
     if (status != TC_OK) return status;
     TC_HIP(hipMemcpyAsync(occupation + begin * t->n_bins, t->occupation.ptr,
                           occ_bytes, hipMemcpyDeviceToHost, t->stream));
@@ -1601,7 +1588,7 @@ int tc_predict_occupation_batch(tc_table* t, const double* occupation,
     if (status != TC_OK) return status;
     t->cur = 0;
     t->lanes[0].ngal_parts = 1;
-    status = run_contraction(t, n, ldb, flags, (double*)t->out_ngal.ptr,
+    status = run_contraction(t, probe_call(t), n, ldb, flags, (double*)t->out_ngal.ptr,
                              (double*)t->out_xi.ptr);
     if (status != TC_OK) return status;
     status = copy_out(&t->h_out, ngal + begin * (separate ? 2 : 1), ngal_count,
@@ -1712,7 +1699,8 @@ int autotune(tc_table* t, unsigned flags) {
       t->tuning.fused_draws = shapes[k];
       choice.us[i][1 + k] = 0.0f;
       // (the shape asked for is the one that would run?)
-      if (tc::choose_fused_form(fused_query(t, n, 10, flags)).draws != shapes[k]) continue;
+      if (tc::choose_fused_form(fused_query(t, probe_call(t), n, 10, flags)).draws != shapes[k])
+        continue;
       status = time_form(n, &choice.us[i][1 + k]);
       if (status != TC_OK) return status;
       // (a one-launch form must win by 2 %: ties go to the three kernels)
