@@ -284,6 +284,37 @@ int tc_chi2_grad_assembias_batch_device(tc_table* table, const double* theta_dev
                                         double* ngal_device, double* chi2_device,
                                         double* dngal_device, double* dchi2_device,
                                         double* fisher_device);
+/* The gradients of the Leauthaud et al. (2011) family (what TC_FLAG_LEAUTHAUD11 predicts): theta
+ * is (n_draws, 14) as for the forward calls, n_theta must be 14, and the derivatives are those
+ * with respect to the first eleven columns -- logm0, logm1, beta, delta, gamma, scatter, alphasat,
+ * bsat, betasat, bcut, betacut; threshold, h and h_s are inputs --, 11 wherever 5 stands above:
+ * dngal (n_draws, 11), dxi (n_draws, 11, n_r), dchi2 (n_draws, 11), fisher (n_draws, 11, 11).
+ * The inverse stellar-to-halo mass relation is solved per quadrature node by Newton's method and
+ * differentiated at the root by the implicit function theorem; the occupation is smooth, so the
+ * derivative is exact everywhere.  flags: 0 or TC_FLAG_MODULATE_WITH_CENOCC (the family is
+ * implied; TC_FLAG_LEAUTHAUD11, TC_FLAG_ASSEMBIAS and every other flag is TC_ERR_UNSUPPORTED).
+ * Otherwise as the plain calls: one launch per batch, a draw's results depend on the draw alone,
+ * float32 tables and tables beyond the LDS budget (12 for 6 quantities, 7 rows per central and
+ * 12 per satellite bin) are refused.  The likelihood calls take a trailing `fisher`, which may
+ * be NULL: not asked for. */
+int tc_predict_grad_leauthaud11_batch(tc_table* table, const double* theta, int n_theta,
+                                      int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                      double* ngal, double* xi, double* dngal, double* dxi);
+int tc_predict_grad_leauthaud11_batch_device(tc_table* table, const double* theta_device,
+                                             int n_theta, int64_t n_draws, int n_gauss_prim,
+                                             unsigned flags, double* ngal_device,
+                                             double* xi_device, double* dngal_device,
+                                             double* dxi_device);
+int tc_chi2_grad_leauthaud11_batch(tc_table* table, const double* theta, int n_theta,
+                                   int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                   const double* data, const double* precision, double* ngal,
+                                   double* chi2, double* dngal, double* dchi2, double* fisher);
+int tc_chi2_grad_leauthaud11_batch_device(tc_table* table, const double* theta_device,
+                                          int n_theta, int64_t n_draws, int n_gauss_prim,
+                                          unsigned flags, const double* data,
+                                          const double* precision, double* ngal_device,
+                                          double* chi2_device, double* dngal_device,
+                                          double* dchi2_device, double* fisher_device);
 
 /* A handful of independent draws in ONE launch (the proposals of an ensemble sampler's step,
  * or the reference's un-batched predict(), README.md:72-75, for n_walkers = 1): every

@@ -31,11 +31,20 @@ int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* den
 
 /* The LDS bytes per workgroup that the launch layer asks for and refuses by
  * (tabcorr_amd/csrc/grad.h): kernel 0 grad_auto_kernel, 1 grad_cross_kernel, 2
- * grad_interp_auto_kernel, 3 grad_interp_cross_kernel; n_params 5 (plain Zheng07) or 7 (decorated
- * with assembly bias); chi2: the likelihood is finished in the launch; n_dim: the interpolator's
+ * grad_interp_auto_kernel, 3 grad_interp_cross_kernel; n_params 5 (plain Zheng07), 7 (decorated
+ * with assembly bias) or 11 (Leauthaud11: kernels 0 and 1 only); chi2: the likelihood is finished in the launch; n_dim: the interpolator's
  * axes (ignored by kernels 0 and 1, as n_bins and n_central are by 1 and 3). */
 int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n_r, int n_dim,
                       int chi2, int64_t* bytes);
+
+/* The node arithmetic of the Leauthaud11 gradient kernels (tabcorr_amd/csrc/grad_leauthaud11.h)
+ * on the host, for one draw theta (14 columns) and n halo masses: log_mstar (n) the root of the
+ * stellar-to-halo mass relation, n_cen (n) and dn_cen (n, 11) the centrals' occupation and its
+ * derivatives with respect to the first eleven theta columns, n_sat (n) and dn_sat (n, 11) the
+ * satellites' (modulate != 0: times <N_cen>, by the product rule). */
+int tc_debug_leauthaud11_node_grad(const double* theta, int modulate, int64_t n,
+                                   const double* mass, double* log_mstar, double* n_cen,
+                                   double* dn_cen, double* n_sat, double* dn_sat);
 
 /* The moment expansion of a central bin's node sum (tabcorr_amd/csrc/series.h) on the host,
  * next to the node loop it replaces: for one bin [log_min, log_max] with

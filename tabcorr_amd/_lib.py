@@ -60,6 +60,9 @@ SIGNATURES = {
                           c_double_p],
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_grad_lds': [ctypes.c_int] * 7 + [c_int64_p],
+    'tc_debug_leauthaud11_node_grad': [c_double_p, ctypes.c_int, ctypes.c_int64, c_double_p,
+                                       c_double_p, c_double_p, c_double_p, c_double_p,
+                                       c_double_p],
     'tc_pair_indices': [ctypes.c_int, c_int32_p, c_int32_p, c_int32_p],
     'tc_spline_interpolation_matrix': [ctypes.c_int, c_double_p, c_double_p],
     'tc_spline_weights': [ctypes.c_int, c_double_p, c_double_p, ctypes.c_double, c_double_p,
@@ -156,6 +159,22 @@ SIGNATURES = {
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
         c_double_p, c_double_p, c_double_p, c_double_p],
     'tc_chi2_grad_assembias_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    'tc_predict_grad_leauthaud11_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p],
+    'tc_predict_grad_leauthaud11_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p],
+    'tc_chi2_grad_leauthaud11_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_chi2_grad_leauthaud11_batch_device': [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],

@@ -1,6 +1,7 @@
 // Analytic gradients of (ngal, xi, chi2) with respect to the five Zheng07 parameters -- or, for
 // the model decorated with Heaviside assembly bias at the median split, those and the two
-// strengths (`n_params` = 5 or 7 below, a template parameter of the kernels) --: the
+// strengths, or the eleven parameters of the Leauthaud11 family (`n_params` = 5, 7 or 11 below, a
+// template parameter of the kernels) --: the
 // argument block of the gradient kernels (grad_kernels.hip.h), their LDS budget and the dense
 // matrix-operand layout of a mode-auto table.  Plain C++ for the host-only units that fill these
 // in (spline.h, which it includes, is compiled for the device too).
@@ -24,13 +25,24 @@ constexpr int kGradParams = 5;        // logMmin, sigma_logM, logM0, logM1, alph
 // N_cen' = N + s_b c(A_cen) min(N, 1 - N) per node and N_sat' = (1 + s_b c(A_sat)) N with c the
 // clip to [-1, 1] and s_b = +1 for a bin whose secondary percentile lies above 0.5, else -1
 constexpr int kGradParamsAssembias = 7;
+// The Leauthaud11 family (grad_leauthaud11.h): logm0, logm1, beta, delta, gamma, scatter,
+// alphasat, bsat, betasat, bcut, betacut -- the first eleven of the fourteen theta columns of the
+// forward kernels; threshold, h and h_s behind them are inputs and are not differentiated.
+constexpr int kGradParamsLeauthaud11 = 11;
+constexpr int kGradThetaLeauthaud11 = 14;
+// theta columns of a draw: the differentiated parameters, and for Leauthaud11 the three inputs
+constexpr int grad_theta_columns(int n_params) {
+  return n_params == kGradParamsLeauthaud11 ? kGradThetaLeauthaud11 : n_params;
+}
 constexpr int kGradDraws = 16;        // draws per workgroup: the N of one v_mfma_f64_16x16x4_f64
 constexpr int kGradWaves = 4;
 constexpr int kGradThreads = 64 * kGradWaves;
 constexpr int kGradCrossSlab = 64;    // mode cross: bins whose w and dw one LDS slab holds
 
 struct GradArgs {
-  const double* theta;       // (n_draws, 5) -- 7 wherever 5 stands below, decorated
+  // (n_draws, 5) -- 7 wherever 5 stands below, decorated; Leauthaud11: (n_draws, 14), and 11
+  // wherever 5 stands below
+  const double* theta;
   int64_t n_draws;
   int n_bins;
   int n_central;
@@ -66,14 +78,36 @@ struct GradArgs {
 // zeros stands for everything else: the derivatives a central bin does not have and the padding
 // of the matrix up to whole tiles.  Decorated (n_params = 7): a central bin keeps a fourth row,
 // dw/dA_cen, a satellite bin a seventh, dw/dA_sat.
-constexpr int grad_central_rows(int n_params) { return n_params == kGradParams ? 3 : 4; }
-constexpr int grad_satellite_rows(int n_params) { return n_params == kGradParams ? 6 : 7; }
+// Leauthaud11 (n_params = 11): a central bin keeps w and its six non-zero derivatives (the five
+// relation parameters and scatter), a satellite bin w and all eleven.
+//
+// The family trait: the rows a central and a satellite bin keep, and the row (within its bin's)
+// of quantity p = 0 (w), 1 + k (dw/dtheta_k); -1: the bin does not keep it, it is the row of zeros.
+constexpr int grad_central_rows(int n_params) {
+  return n_params == kGradParams ? 3 : n_params == kGradParamsAssembias ? 4 : 7;
+}
+constexpr int grad_satellite_rows(int n_params) {
+  return n_params == kGradParams ? 6 : n_params == kGradParamsAssembias ? 7 : 12;
+}
+constexpr int grad_central_row(int n_params, int p) {
+  if (n_params == kGradParamsLeauthaud11) return p < 7 ? p : -1;
+  if (p < 3) return p;
+  return n_params == kGradParamsAssembias && p == n_params - 1 ? 3 : -1;      // A_cen
+}
+constexpr int grad_satellite_row(int n_params, int p) {
+  if (n_params != kGradParamsAssembias) return p;
+  if (p == n_params - 1) return -1;                                            // A_cen
+  return p == n_params ? n_params - 1 : p;                                     // A_sat
+}
+// Whether a bin's rows are simply its first quantities, in order (plain, Leauthaud11), so that they
+// are written as one run; the decorated rows skip a quantity.
+constexpr bool grad_rows_in_order(int n_params) { return n_params != kGradParamsAssembias; }
 constexpr int grad_auto_rows(int n_bins, int n_central, int n_params = kGradParams) {
   return grad_central_rows(n_params) * n_central +
          grad_satellite_rows(n_params) * (n_bins - n_central) + 1;
 }
 // ... then the totals (6, kGradDraws) and, for the likelihood, (6, n_r, kGradDraws) residuals
-// and derivatives -- 8 for 6 where decorated, here and below
+// and derivatives -- 8 for 6 where decorated, 12 for the Leauthaud11 family, here and below
 constexpr size_t grad_auto_lds_bytes(int n_bins, int n_central, int n_r, bool chi2,
                                      int n_params = kGradParams) {
   return ((size_t)grad_auto_rows(n_bins, n_central, n_params) + (n_params + 1) +

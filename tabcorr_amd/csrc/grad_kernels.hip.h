@@ -2,7 +2,8 @@
 // derivatives with respect to the five parameters, one launch per batch (grad.h: the argument
 // block, the LDS budget and the operand layout; launch.hip: run_grad).  NP, a template parameter
 // of every kernel and piece, is the number of differentiated parameters: 5, or 7 for the model
-// decorated with assembly bias (the two strengths last); "6" below reads NP + 1 there.
+// decorated with assembly bias (the two strengths last), or 11 for the Leauthaud11 family
+// (grad_leauthaud11.h: its node arithmetic, which the host runs too); "6" below reads NP + 1 there.
 //
 // A workgroup of four waves carries kGradDraws = 16 draws from theta to the results:
 //   1  the node loops of every bin (tabcorr.py:537-578) for <N> and d<N>/dtheta_k, which share
@@ -25,14 +26,11 @@
 
 #include "fastmath.h"
 #include "grad_device.hip.h"
+#include "grad_leauthaud11.h"
 
 namespace tc {
 
 namespace grad {
-
-constexpr double kLn10 = 2.302585092994045684;
-constexpr double kLog2E = 1.4426950408889634074;
-constexpr double kTwoOverSqrtPi = 1.1283791670955125739;
 
 struct Draw {
   double log_m_min, inv_sigma, m0, m0_ln10, inv_m1, alpha;
@@ -43,30 +41,25 @@ struct Draw {
 
 constexpr bool decorated(int np) { return np == kGradParamsAssembias; }
 
+// The per-draw constants of a family's node loops.
+template <int NP>
+struct DrawOf {
+  typedef Draw type;
+};
+template <>
+struct DrawOf<kGradParamsLeauthaud11> {
+  typedef Leauthaud11Draw type;
+};
+
 // <N_cen> and its derivatives with respect to logMmin and sigma_logM at one node:
-// N = (1 + erf x) / 2, dN/dlogMmin = -exp(-x^2) / (sigma sqrt(pi)), dN/dsigma = x dN/dlogMmin.
-// erf_gauss_fast counts the Gaussian as zero from |x| = 6 on; the derivative of a draw whose
-// every node lies out there is made of exactly these tails, so they are evaluated: exp(-x^2) =
-// 2^z with the rounding error of the product z = -x^2 log2 e carried along.
-// x_abs, gauss_out: |x| and 2/sqrt(pi) exp(-x^2), for the decorated centrals.
+// N = (1 + erf x) / 2, dN/dlogMmin = -exp(-x^2) / (sigma sqrt(pi)), dN/dsigma = x dN/dlogMmin
+// (grad_leauthaud11.h: central_node_at, with the Gaussian's tails).
 __device__ __forceinline__ void central_node(const double* mt, const fm::Consts& k, const Draw& d,
                                              double log_m, double* n, double* dn0, double* dn1,
                                              double* x_abs = nullptr,
                                              double* gauss_out = nullptr) {
-  const double x = (log_m - d.log_m_min) * d.inv_sigma;
-  double gauss;
-  const double e = fm::erf_gauss_fast(mt, k, x, &gauss);
-  const double x2 = x * x;
-  const double zh = -x2 * kLog2E;
-  const double zl = fma(-x2, kLog2E, -zh) - fma(x, x, -x2) * kLog2E;
-  const double t = fm::exp2_fast(mt, k, zh, zh > -1000.0);
-  const double tail = kTwoOverSqrtPi * fma(t, zl * fm::kLn2, t);
-  gauss = fabs(x) < 6.0 ? gauss : tail;
-  *n = fma(0.5, e, 0.5);
-  *dn0 = -0.5 * gauss * d.inv_sigma;
-  *dn1 = *dn0 * x;
-  if (x_abs != nullptr) *x_abs = fabs(x);
-  if (gauss_out != nullptr) *gauss_out = gauss;
+  central_node_at(mt, k, (log_m - d.log_m_min) * d.inv_sigma, d.inv_sigma, n, dn0, dn1, x_abs,
+                  gauss_out);
 }
 
 // w = n_h <N> of bin i (library order: the centrals first) and its NP derivatives:
@@ -159,6 +152,43 @@ __device__ __forceinline__ void bin_values(const GradArgs& a, const fm::Consts& 
   for (int p = 0; p < NP + 1; ++p) out[p] = n_h * acc[p];
 }
 
+// The same for the Leauthaud11 family: out[0] = w, out[1 + k] = dw / dtheta_k, k = 0 .. 10; a
+// central bin's last five are zero.  One Newton solve per central node, and with
+// modulate_with_cenocc one per satellite node.
+template <int NP>
+__device__ __forceinline__ void bin_values(const GradArgs& a, const fm::Consts& k,
+                                           const Leauthaud11Draw& d, int i, double out[NP + 1]) {
+  static_assert(NP == kGradParamsLeauthaud11, "the Leauthaud11 family has eleven parameters");
+  const double* mt = a.math_table;
+  const double* weight = a.weight + (size_t)i * a.n_gauss;
+  const double* log_m = a.log_m + (size_t)i * a.n_gauss;
+  double acc[NP + 1];
+#pragma unroll
+  for (int p = 0; p < NP + 1; ++p) acc[p] = 0.0;
+  if (i < a.n_central) {
+    for (int node = 0; node < a.n_gauss; ++node) {
+      double v[7];
+      leauthaud11_central_node(mt, k, d, log_m[node], v);
+      const double wn = weight[node];
+#pragma unroll
+      for (int p = 0; p < 7; ++p) acc[p] = fma(wn, v[p], acc[p]);
+    }
+  } else {
+    const double* m = a.m + (size_t)i * a.n_gauss;
+    for (int node = 0; node < a.n_gauss; ++node) {
+      double c[7], v[NP + 1];
+      if (a.modulate) leauthaud11_central_node(mt, k, d, log_m[node], c);
+      leauthaud11_satellite_node(mt, k, d, log_m[node], m[node], a.modulate != 0, c, v);
+      const double wn = weight[node];
+#pragma unroll
+      for (int p = 0; p < NP + 1; ++p) acc[p] = fma(wn, v[p], acc[p]);
+    }
+  }
+  const double n_h = a.n_h[i];
+#pragma unroll
+  for (int p = 0; p < NP + 1; ++p) out[p] = n_h * acc[p];
+}
+
 // The clip of a strength to [-1, 1] as the forward kernels apply it (kernels.hip.h:
 // clip_strength; NaN stays NaN) and its derivative, at the boundary the one facing inside.
 __device__ __forceinline__ void clip_strength_grad(double a, double* c, double* dc) {
@@ -167,7 +197,9 @@ __device__ __forceinline__ void clip_strength_grad(double a, double* c, double* 
 }
 
 template <int NP>
-__device__ __forceinline__ Draw load_draw(const GradArgs& a, const fm::Consts& k, int64_t draw) {
+__device__ __forceinline__ typename DrawOf<NP>::type load_draw(const GradArgs& a,
+                                                               const fm::Consts& k,
+                                                               int64_t draw) {
   const double* theta = a.theta + clamp_draw(draw, a.n_draws) * NP;
   Draw d;
   d.log_m_min = theta[0];
@@ -184,18 +216,27 @@ __device__ __forceinline__ Draw load_draw(const GradArgs& a, const fm::Consts& k
   return d;
 }
 
-// LDS row of (bin i, quantity p) in grad_auto_kernel (grad.h: grad_auto_rows).  Decorated: a
-// central bin's fourth row is p = 6 (A_cen), a satellite bin's seventh p = 7 (A_sat).
+template <>
+__device__ __forceinline__ Leauthaud11Draw load_draw<kGradParamsLeauthaud11>(
+    const GradArgs& a, const fm::Consts& k, int64_t draw) {
+  return prepare_leauthaud11(a.math_table, k,
+                             a.theta + clamp_draw(draw, a.n_draws) * kGradThetaLeauthaud11);
+}
+
+// LDS row of (bin i, quantity p) in grad_auto_kernel, by the family's trait (grad.h:
+// grad_central_row, grad_satellite_row, grad_auto_rows).  Decorated: a central bin's fourth row is
+// p = 6 (A_cen), a satellite bin's seventh p = 7 (A_sat).
 template <int NP>
 __device__ __forceinline__ int auto_row(int i, int p, int n_bins, int n_central, int zero_row) {
   if (i >= n_bins) return zero_row;
-  if (!decorated(NP)) {
-    if (i < n_central) return p < 3 ? 3 * i + p : zero_row;
-    return 3 * n_central + 6 * (i - n_central) + p;
+  if (i < n_central) {
+    const int row = grad_central_row(NP, p);
+    return row < 0 ? zero_row : grad_central_rows(NP) * i + row;
   }
-  if (i < n_central) return p < 3 ? 4 * i + p : (p == NP - 1 ? 4 * i + 3 : zero_row);
-  if (p == NP - 1) return zero_row;
-  return 4 * n_central + NP * (i - n_central) + (p == NP ? NP - 1 : p);
+  const int row = grad_satellite_row(NP, p);
+  return row < 0 ? zero_row
+                 : grad_central_rows(NP) * n_central + grad_satellite_rows(NP) * (i - n_central) +
+                       row;
 }
 
 // chi2 = e^T P e and dchi2 / dtheta_k = 2 e^T P_sym dxi_k with P_sym = (P + P^T) / 2, from the
@@ -277,7 +318,8 @@ __device__ __forceinline__ void finish_fisher(const GradArgs& a, const double* s
 // Phase 1: thread = (bin i % 16, draw) writes w and dw of its bins, and the row of zeros.
 template <int NP>
 __device__ __forceinline__ void auto_node_loops(const GradArgs& a, const fm::Consts& k,
-                                                const Draw& d, double* w, int zero_row) {
+                                                const typename DrawOf<NP>::type& d, double* w,
+                                                int zero_row) {
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   const int n_bins = a.n_bins, n_central = a.n_central;
@@ -285,11 +327,11 @@ __device__ __forceinline__ void auto_node_loops(const GradArgs& a, const fm::Con
   for (int i = t / kGradDraws; i < n_bins; i += kGradThreads / kGradDraws) {
     double out[NP + 1];
     bin_values<NP>(a, k, d, i, out);
-    if (!decorated(NP)) {
+    if (grad_rows_in_order(NP)) {
       const int base = auto_row<NP>(i, 0, n_bins, n_central, zero_row);
-      const int count = i < n_central ? 3 : 6;
+      const int count = i < n_central ? grad_central_rows(NP) : grad_satellite_rows(NP);
 #pragma unroll
-      for (int p = 0; p < 6; ++p)
+      for (int p = 0; p < NP + 1; ++p)
         if (p < count) w[(base + p) * kGradDraws + col] = out[p];
     } else {
       // (the rows a bin does not have are the row of zeros: not written)
@@ -359,7 +401,8 @@ __device__ __forceinline__ double auto_dxi(const double* acc, int p, double xi,
 // w and dw of the bins slab0 .. slab0 + count - 1 into the slab (6, kGradCrossSlab, 16).
 template <int NP>
 __device__ __forceinline__ void cross_node_loops(const GradArgs& a, const fm::Consts& k,
-                                                 const Draw& d, int slab0, int count, double* w) {
+                                                 const typename DrawOf<NP>::type& d, int slab0,
+                                                 int count, double* w) {
   const int t = threadIdx.x;
   const int col = t % kGradDraws;
   for (int li = t / kGradDraws; li < count; li += kGradThreads / kGradDraws) {
@@ -389,7 +432,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
 
   // phase 1: thread = (bin i % 16, draw)
   {
-    const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+    const typename grad::DrawOf<NP>::type d = grad::load_draw<NP>(a, k, draw0 + col);
     grad::auto_node_loops<NP>(a, k, d, w, zero_row);
   }
   __syncthreads();
@@ -460,7 +503,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   double* y = w + NQ * kGradCrossSlab * kGradDraws;                    // (6, n_r, 16)
   double* total = y + (size_t)NQ * n_r * kGradDraws;                   // (6, 16)
   const fm::Consts k = fm::make_consts();
-  const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+  const typename grad::DrawOf<NP>::type d = grad::load_draw<NP>(a, k, draw0 + col);
   const int n_items = NQ * n_r * kGradDraws;
   for (int item = t; item < n_items; item += kGradThreads) y[item] = 0.0;
   double my_total = 0.0;

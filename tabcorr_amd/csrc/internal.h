@@ -716,7 +716,8 @@ int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_
 // not serve (TC_ERR_UNSUPPORTED with a message), the handle's copy of the matrix, the launch.
 // xi / dxi NULL: chi2 / dchi2 from chi2_data (data, then the precision matrix, on the device) and,
 // where `fisher` is given, the Fisher matrix (n_draws, 5, 5) of the likelihood.  n_params:
-// tc::kGradParams, or tc::kGradParamsAssembias for the decorated model (7 wherever 5 stands).
+// tc::kGradParams, tc::kGradParamsAssembias for the decorated model (7 wherever 5 stands), or
+// tc::kGradParamsLeauthaud11 for that family (11, of the 14 theta columns).
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                     int n_gauss, unsigned flags, bool chi2, int n_params = tc::kGradParams);
 int build_grad_table(tc_table* t);
@@ -851,6 +852,8 @@ int launch_grad_interp_instance(int mode, int device, dim3 grid, int lds, hipStr
                                 hipEvent_t k0, hipEvent_t k1, const tc::GradInterpArgs& ga);
 int launch_grad_assembias_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                                    hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
+int launch_grad_leauthaud11_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
+                                     hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
 int launch_grad_interp_assembias_instance(int mode, int device, dim3 grid, int lds,
                                           hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
                                           const tc::GradInterpArgs& ga);

@@ -1127,25 +1127,33 @@ int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n
                     int n_gauss, unsigned flags, bool chi2, int n_params) {
   TC_CHECK(t != nullptr, "table handle is NULL");
   const bool decorated = n_params == tc::kGradParamsAssembias;
+  const bool leauthaud = n_params == tc::kGradParamsLeauthaud11;
   const unsigned unserved = flags & ~(unsigned)TC_FLAG_MODULATE_WITH_CENOCC;
   if (unserved & TC_FLAG_SEPARATE_GAL_TYPE)
     return fail(TC_ERR_UNSUPPORTED, "gradients are implemented for the total prediction only "
                                     "(not separate_gal_type)");
   if (unserved & TC_FLAG_ASSEMBIAS)
     return fail(TC_ERR_UNSUPPORTED,
-                decorated ? "the assembly-bias gradient entry points are decorated as they are: "
-                            "flags may hold TC_FLAG_MODULATE_WITH_CENOCC only"
-                          : "gradients are not implemented for assembly bias by this entry "
-                            "point (see the *_grad_assembias_* ones)");
+                leauthaud   ? "the Leauthaud11 family has no assembly bias: flags may hold "
+                              "TC_FLAG_MODULATE_WITH_CENOCC only"
+                : decorated ? "the assembly-bias gradient entry points are decorated as they are: "
+                              "flags may hold TC_FLAG_MODULATE_WITH_CENOCC only"
+                            : "gradients are not implemented for assembly bias by this entry "
+                              "point (see the *_grad_assembias_* ones)");
   if (unserved & TC_FLAG_LEAUTHAUD11)
-    return fail(TC_ERR_UNSUPPORTED, "gradients are implemented for the Zheng07 family only");
+    return fail(TC_ERR_UNSUPPORTED,
+                leauthaud ? "the Leauthaud11 gradient entry points are of that family as they "
+                            "are: flags may hold TC_FLAG_MODULATE_WITH_CENOCC only"
+                          : "gradients are implemented for the Zheng07 family only (see the "
+                            "*_grad_leauthaud11_* entry points)");
   if (unserved != 0) return fail(TC_ERR_UNSUPPORTED, "gradients: unknown flags 0x%x", unserved);
   if (t->compute_dtype != TC_DTYPE_F64)
     return fail(TC_ERR_UNSUPPORTED, "gradients need a float64 compute dtype");
   TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
   TC_CHECK(n_draws == 0 || theta != nullptr, "theta is NULL");
   TC_CHECK(n_gauss >= 1 && n_gauss <= 4096, "n_gauss_prim must be in [1, 4096]");
-  TC_CHECK(n_theta == n_params, "theta must have %d columns, got %d", n_params, n_theta);
+  TC_CHECK(n_theta == tc::grad_theta_columns(n_params), "theta must have %d columns, got %d",
+           tc::grad_theta_columns(n_params), n_theta);
   return check_grad_fit(t, "gradients", grad_lds(t, chi2, n_params));
 }
 
@@ -1247,8 +1255,10 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
   ga.percentile = decorated ? (const double*)t->d_percentile : nullptr;
   const int lds = (int)grad_lds(t, xi == nullptr, n_params);
   return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-    return (decorated ? launch_grad_assembias_instance : launch_grad_instance)(
-        t->mode, t->device, grid, lds, stream, k0, k1, ga);
+    const auto instance = n_params == tc::kGradParamsLeauthaud11
+                              ? launch_grad_leauthaud11_instance
+                              : (decorated ? launch_grad_assembias_instance : launch_grad_instance);
+    return instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
   });
 }
 

@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "grad_leauthaud11.h"
 #include "internal.h"
 #include "series.h"
 
@@ -536,8 +537,11 @@ int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* den
 int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n_r, int n_dim,
                       int chi2, int64_t* bytes) {
   TC_CHECK(kernel >= 0 && kernel <= 3 && bytes, "invalid arguments");
-  TC_CHECK(n_params == tc::kGradParams || n_params == tc::kGradParamsAssembias,
-           "n_params must be %d or %d", tc::kGradParams, tc::kGradParamsAssembias);
+  const bool leauthaud = n_params == tc::kGradParamsLeauthaud11;
+  TC_CHECK(n_params == tc::kGradParams || n_params == tc::kGradParamsAssembias || leauthaud,
+           "n_params must be %d, %d or %d", tc::kGradParams, tc::kGradParamsAssembias,
+           tc::kGradParamsLeauthaud11);
+  TC_CHECK(!leauthaud || kernel <= 1, "the Leauthaud11 family has no interpolator kernels");
   TC_CHECK(n_bins >= n_central && n_central >= 0 && n_r >= 0 && n_dim >= 0, "invalid sizes");
   const size_t sizes[4] = {
       tc::grad_auto_lds_bytes(n_bins, n_central, n_r, chi2 != 0, n_params),
@@ -545,6 +549,36 @@ int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n
       tc::grad_interp_auto_lds_bytes(n_bins, n_central, n_r, n_dim, chi2 != 0, n_params),
       tc::grad_interp_cross_lds_bytes(n_r, n_dim, chi2 != 0, n_params)};
   *bytes = (int64_t)sizes[kernel];
+  return TC_OK;
+}
+
+int tc_debug_leauthaud11_node_grad(const double* theta, int modulate, int64_t n,
+                                   const double* mass, double* log_mstar, double* n_cen,
+                                   double* dn_cen, double* n_sat, double* dn_sat) {
+  TC_CHECK(theta && n >= 0 && mass && log_mstar && n_cen && dn_cen && n_sat && dn_sat,
+           "NULL argument");
+  static std::vector<double> table;
+  if (table.empty()) {
+    table.resize(tc::fm::kTableDoubles);
+    tc::fm::build_tables(table.data());
+  }
+  const tc::fm::Consts k = tc::fm::make_consts();
+  const int np = tc::kGradParamsLeauthaud11;
+  const tc::grad::Leauthaud11Draw d = tc::grad::prepare_leauthaud11(table.data(), k, theta);
+  for (int64_t i = 0; i < n; ++i) {
+    // log10 M as launch.hip: get_quadrature has it
+    const double log_m = std::log10(mass[i]);
+    double cen[7], sat[12];
+    log_mstar[i] = tc::grad::leauthaud11_central_node(table.data(), k, d, log_m, cen);
+    tc::grad::leauthaud11_satellite_node(table.data(), k, d, log_m, mass[i], modulate != 0, cen,
+                                         sat);
+    n_cen[i] = cen[0];
+    n_sat[i] = sat[0];
+    for (int p = 0; p < np; ++p) {
+      dn_cen[i * np + p] = p < 6 ? cen[1 + p] : 0.0;
+      dn_sat[i * np + p] = sat[1 + p];
+    }
+  }
   return TC_OK;
 }
 

@@ -1022,14 +1022,16 @@ int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
   return TC_OK;
 }
 
-// (n_params: tc::kGradParams, or tc::kGradParamsAssembias for the decorated model)
+// (n_params: tc::kGradParams, tc::kGradParamsAssembias for the decorated model, or
+// tc::kGradParamsLeauthaud11, whose draws have tc::grad_theta_columns(n_params) = 14 columns)
 int grad_device(tc_table* t, GradLane request, const double* theta_device, int64_t n_draws,
                 int n_gauss, unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
                 const double* chi2_data, double* chi2, double* dchi2, double* fisher,
                 int n_params = tc::kGradParams) {
   const int64_t n_r = t->n_r, np = n_params;
   return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
-    return run_grad(t, theta_device + begin * np, n, n_gauss, flags, ngal + begin,
+    return run_grad(t, theta_device + begin * tc::grad_theta_columns(n_params), n, n_gauss, flags,
+                    ngal + begin,
                     xi ? xi + begin * n_r : nullptr, dngal + begin * np,
                     dxi ? dxi + begin * np * n_r : nullptr, chi2_data,
                     chi2 ? chi2 + begin : nullptr, dchi2 ? dchi2 + begin * np : nullptr,
@@ -1047,13 +1049,14 @@ int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, un
   const bool chi2 = chi2_data != nullptr;
   const size_t n = (size_t)n_draws, n_r = (size_t)t->n_r, np = (size_t)n_params;
   const size_t value_count = chi2 ? n : n * n_r;
-  int status = t->theta.reserve(n * np * 8, t->stream);
+  const size_t theta_bytes = n * (size_t)tc::grad_theta_columns(n_params) * 8;
+  int status = t->theta.reserve(theta_bytes, t->stream);
   if (status == TC_OK) status = t->out_ngal.reserve(n * (1 + np) * 8, t->stream);
   const size_t fisher_count = fisher ? n * np * np : 0;
   if (status == TC_OK)
     status = t->out_xi.reserve((value_count * (1 + np) + fisher_count) * 8, t->stream);
   if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(t->theta.ptr, theta, n * np * 8, hipMemcpyHostToDevice, t->stream));
+  TC_HIP(hipMemcpyAsync(t->theta.ptr, theta, theta_bytes, hipMemcpyHostToDevice, t->stream));
   double* d_ngal = (double*)t->out_ngal.ptr;
   double* d_dngal = d_ngal + n;
   double* d_value = (double*)t->out_xi.ptr;
@@ -1222,6 +1225,52 @@ int tc_chi2_grad_assembias_batch(tc_table* t, const double* theta, int n_theta, 
                                  double* dngal, double* dchi2, double* fisher) {
   return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
                               chi2, dngal, dchi2, false, fisher, tc::kGradParamsAssembias);
+}
+
+// ---- gradients of the Leauthaud11 family: fourteen theta columns, eleven differentiated
+// (grad.h: kGradParamsLeauthaud11); `fisher` may be NULL ----
+
+int tc_predict_grad_leauthaud11_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                             int64_t n_draws, int n_gauss, unsigned flags,
+                                             double* ngal_device, double* xi_device,
+                                             double* dngal_device, double* dxi_device) {
+  const int np = tc::kGradParamsLeauthaud11;
+  const int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, false, np);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
+  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
+                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr, np);
+}
+
+int tc_predict_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta,
+                                      int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
+                                      double* xi, double* dngal, double* dxi) {
+  const int np = tc::kGradParamsLeauthaud11;
+  const int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, false, np);
+  if (status != TC_OK) return status;
+  if (n_draws == 0) return TC_OK;
+  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
+  return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi, nullptr, np);
+}
+
+int tc_chi2_grad_leauthaud11_batch_device(tc_table* t, const double* theta_device, int n_theta,
+                                          int64_t n_draws, int n_gauss, unsigned flags,
+                                          const double* data, const double* precision,
+                                          double* ngal_device, double* chi2_device,
+                                          double* dngal_device, double* dchi2_device,
+                                          double* fisher_device) {
+  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
+                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
+                                false, fisher_device, tc::kGradParamsLeauthaud11);
+}
+
+int tc_chi2_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                                   int n_gauss, unsigned flags, const double* data,
+                                   const double* precision, double* ngal, double* chi2,
+                                   double* dngal, double* dchi2, double* fisher) {
+  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
+                              chi2, dngal, dchi2, false, fisher, tc::kGradParamsLeauthaud11);
 }
 
 // ---- occupation VJP (launch.hip: run_vjp) -------------------------------------------------

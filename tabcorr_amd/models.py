@@ -117,6 +117,12 @@ LEAUTHAUD11_KEYS = ('smhm_m0_0', 'smhm_m0_a', 'smhm_m1_0', 'smhm_m1_a',
                     'smhm_delta_a', 'smhm_gamma_0', 'smhm_gamma_a',
                     'scatter_model_param1', 'alphasat', 'bsat', 'betasat',
                     'bcut', 'betacut')
+# the differentiated columns of the family's draws (`family='leauthaud11'` of
+# the gradient calls): the first eleven of the fourteen device columns of
+# `Leauthaud11Model.device_theta`; threshold, h and h_s behind them are inputs
+LEAUTHAUD11_GRAD_KEYS = ('logm0', 'logm1', 'beta', 'delta', 'gamma',
+                         'scatter', 'alphasat', 'bsat', 'betasat', 'bcut',
+                         'betacut')
 
 
 def behroozi10_log_halo_mass(log_stellar_mass, log_m0, log_m1, beta, delta,
@@ -216,6 +222,23 @@ class Leauthaud11Model:
                                 p['betacut'], self.threshold,
                                 self.littleh_smhm, self.littleh_sats],
                         dtype=np.float64)
+
+    def device_jacobian(self):
+        """The derivative of the first eleven columns of `device_theta`
+        (`LEAUTHAUD11_GRAD_KEYS`) with respect to the sixteen parameters of
+        ``param_dict`` in `LEAUTHAUD11_KEYS` order, ``(11, 16)``: with
+        a = 1 / (1 + z), ``dX / dsmhm_X_0 = 1`` and ``dX / dsmhm_X_a = a - 1``
+        for the five relation parameters, the identity for the other six.  A
+        gradient in device columns times this matrix is the gradient in the
+        model's own parameters."""
+        a = 1.0 / (1.0 + self.redshift)
+        jacobian = np.zeros((len(LEAUTHAUD11_GRAD_KEYS), len(LEAUTHAUD11_KEYS)))
+        for k in range(5):
+            jacobian[k, 2 * k] = 1.0
+            jacobian[k, 2 * k + 1] = a - 1.0
+        for k in range(5, 11):
+            jacobian[k, k + 5] = 1.0
+        return jacobian
 
     def mean_occupation_centrals(self, prim_haloprop=None, **kwargs):
         return leauthaud11_centrals(prim_haloprop, self.device_theta())

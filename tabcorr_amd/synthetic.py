@@ -122,6 +122,25 @@ def zheng07_draws(n_draws, seed=1):
     return rng.uniform(ZHENG07_LOW, ZHENG07_HIGH, size=(n_draws, 5))
 
 
+# logm0, logm1, beta, delta, gamma, scatter, alphasat, bsat, betasat, bcut, betacut, threshold, h
+# of the stellar-to-halo mass relation, h of the satellite terms: halotools' ``leauthaud11``
+# defaults and a box around them (the Hubble parameters stay as they are)
+LEAUTHAUD11_CENTRE = np.array([10.72, 12.35, 0.43, 0.56, 1.54, 0.2, 1.0, 10.62, 0.859, 1.47,
+                               -0.13, 10.5, 0.7, 0.72])
+LEAUTHAUD11_WIDTH = np.array([0.3, 0.3, 0.08, 0.1, 0.4, 0.08, 0.2, 3.0, 0.1, 0.5, 0.1, 0.5, 0.0,
+                              0.0])
+
+
+def leauthaud11_draws(n_draws, seed=1):
+    """Return ``(n_draws, 14)`` uniform Leauthaud11 draws (the device columns of
+    `tabcorr_amd.Leauthaud11Model.device_theta`) of the box around halotools' defaults, the
+    first one at them."""
+    rng = np.random.default_rng(seed)
+    theta = LEAUTHAUD11_CENTRE + LEAUTHAUD11_WIDTH * rng.uniform(-1, 1, size=(n_draws, 14))
+    theta[0] = LEAUTHAUD11_CENTRE
+    return theta
+
+
 def interpolator_grid(shape, keys=None, low=None, high=None):
     """Return the regular grid of extra parameters of a synthetic interpolator.
 

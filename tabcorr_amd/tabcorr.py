@@ -26,7 +26,8 @@ import numpy as np
 from . import _lib
 from . import pinned
 from .galtable import GalTypeTable
-from .models import ZHENG07_ASSEMBIAS_KEYS, ZHENG07_KEYS, device_spec
+from .models import (LEAUTHAUD11_GRAD_KEYS, LEAUTHAUD11_KEYS,
+                     ZHENG07_ASSEMBIAS_KEYS, ZHENG07_KEYS, device_spec)
 
 ATTR_KEYS = ['tpcf', 'mode', 'simname', 'redshift', 'Num_ptcl_requirement',
              'prim_haloprop_key', 'sec_haloprop_key']
@@ -722,7 +723,8 @@ class TabCorr:
     # -- analytic gradients -----------------------------------------------------------
 
     def predict_batch_grad(self, theta, n_gauss_prim=10,
-                           modulate_with_cenocc=False, assembias=False):
+                           modulate_with_cenocc=False, assembias=False,
+                           family='zheng07'):
         """`predict_batch` together with the exact derivatives of its results
         with respect to the five Zheng07 parameters (`ZHENG07_KEYS` order), in
         one kernel launch: what a best-fit search, a Fisher forecast or an
@@ -741,6 +743,15 @@ class TabCorr:
         the derivative of the function computed: a strength beyond
         ``[-1, 1]`` is clipped, its column is exactly zero.
 
+        ``family='leauthaud11'``: ``theta`` has the 14 columns
+        ``predict_batch(..., family='leauthaud11')`` takes, and the
+        derivatives are those with respect to the first eleven
+        (`tabcorr_amd.models.LEAUTHAUD11_GRAD_KEYS`; threshold, h and h_s are
+        inputs): 11 stands wherever 5 does below.  The inverse stellar-to-halo
+        mass relation is differentiated at its root; the occupation is
+        smooth, so the derivative is exact everywhere.  Not together with
+        ``assembias``.
+
         Returns
         -------
         ngal : ``(n_draws, )``
@@ -751,14 +762,17 @@ class TabCorr:
         Raises ``NotImplementedError`` for what the kernel does not serve
         (float32 tables, very large mode-auto tables).
         """
-        theta = _grad_theta(theta, assembias)
+        theta = _grad_theta(theta, assembias, family)
         device = self.to_device()
-        n_draws, n_cols = theta.shape
+        n_draws = len(theta)
+        n_cols = len(_grad_keys(assembias, family))
         ngal = np.empty(n_draws)
         xi = np.empty((n_draws, device.n_r))
         dngal = np.empty((n_draws, n_cols))
         dxi = np.empty((n_draws, n_cols, device.n_r))
-        entry = (device.lib.tc_predict_grad_assembias_batch if assembias
+        entry = (device.lib.tc_predict_grad_leauthaud11_batch
+                 if family == 'leauthaud11'
+                 else device.lib.tc_predict_grad_assembias_batch if assembias
                  else device.lib.tc_predict_grad_zheng07_batch)
         with device.lock:
             _lib.check(entry(
@@ -771,21 +785,23 @@ class TabCorr:
                 dxi.reshape((n_draws, n_cols) + shape))
 
     def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
-                        modulate_with_cenocc=False, assembias=False):
+                        modulate_with_cenocc=False, assembias=False,
+                        family='zheng07'):
         """`chi2_batch` with its gradient: ``dchi2[:, k] = 2 (xi - data)^T P_sym
         dxi / dtheta_k`` with ``P_sym = (precision + precision^T) / 2``,
         finished on the device in the launch that computes ``xi``.
-        ``assembias=True``: 7 columns, as in `predict_batch_grad`.
+        ``assembias=True``: 7 columns, ``family='leauthaud11'``: 11 (of 14
+        theta columns), as in `predict_batch_grad`.
 
         Returns
         -------
         ngal, chi2 : ``(n_draws, )``
         dngal, dchi2 : ``(n_draws, 5)``
         """
-        if assembias:
-            return self._chi2_grad_assembias(
+        if assembias or family != 'zheng07':
+            return self._chi2_grad_wide(
                 theta, data, precision, n_gauss_prim, modulate_with_cenocc,
-                False)[:4]
+                False, assembias, family)[:4]
         theta = _grad_theta(theta)
         # (the rows of the table's own matrix: a wrong argument is refused
         # before any device is touched, as a wrong theta is)
@@ -804,22 +820,27 @@ class TabCorr:
                 _lib.as_double_p(dngal), _lib.as_double_p(dchi2)))
         return ngal, chi2, dngal, dchi2
 
-    def _chi2_grad_assembias(self, theta, data, precision, n_gauss_prim,
-                             modulate_with_cenocc, want_fisher):
-        """The likelihood gradient of the decorated model, with or without
-        its Fisher matrix: one entry point serves both."""
-        theta = _grad_theta(theta, True)
+    def _chi2_grad_wide(self, theta, data, precision, n_gauss_prim,
+                        modulate_with_cenocc, want_fisher, assembias, family):
+        """The likelihood gradient of the decorated model or of the
+        Leauthaud11 family, with or without its Fisher matrix: one entry point
+        serves both."""
+        theta = _grad_theta(theta, assembias, family)
         data, precision = _chi2_operands(data, precision,
                                          len(self.tpcf_matrix))
         device = self.to_device()
-        n_draws, n_cols = theta.shape
+        n_draws = len(theta)
+        n_cols = len(_grad_keys(assembias, family))
+        entry = (device.lib.tc_chi2_grad_leauthaud11_batch
+                 if family == 'leauthaud11'
+                 else device.lib.tc_chi2_grad_assembias_batch)
         ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
         dngal = np.empty((n_draws, n_cols))
         dchi2 = np.empty((n_draws, n_cols))
         fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
         with device.lock:
-            _lib.check(device.lib.tc_chi2_grad_assembias_batch(
-                device.handle, _lib.as_double_p(theta), n_cols, n_draws,
+            _lib.check(entry(
+                device.handle, _lib.as_double_p(theta), theta.shape[1], n_draws,
                 n_gauss_prim, _flags(False, modulate_with_cenocc),
                 _lib.as_double_p(data), _lib.as_double_p(precision),
                 _lib.as_double_p(ngal), _lib.as_double_p(chi2),
@@ -833,7 +854,11 @@ class TabCorr:
         `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model);
         with ``assembias=True`` a decorated one (`tabcorr_amd.Zheng07Model`
         with a ``sec_haloprop_key``), the dicts then keyed by
-        `ZHENG07_ASSEMBIAS_KEYS`.
+        `ZHENG07_ASSEMBIAS_KEYS`.  A `tabcorr_amd.Leauthaud11Model` is served
+        too: the dicts are then keyed by the sixteen `LEAUTHAUD11_KEYS` of its
+        ``param_dict``, the eleven device columns carried to them by
+        `Leauthaud11Model.device_jacobian` (``d/dsmhm_X_0 = d/dX``,
+        ``d/dsmhm_X_a = (a - 1) d/dX`` with ``a = 1 / (1 + z)``).
 
         Returns
         -------
@@ -844,7 +869,18 @@ class TabCorr:
         """
         if check_consistency:
             self._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'predict_grad')
+        spec = _grad_spec(model, assembias, 'predict_grad', leauthaud11=True)
+        if spec.family == 'leauthaud11':
+            ngal, xi, dngal, dxi = self.predict_batch_grad(
+                spec.theta[np.newaxis], n_gauss_prim=n_gauss_prim,
+                modulate_with_cenocc=spec.modulate_with_cenocc,
+                family='leauthaud11')
+            columns = _leauthaud11_columns(model)
+            return (float(ngal[0]), xi[0],
+                    {key: float(factor * dngal[0, k])
+                     for key, (k, factor) in columns.items()},
+                    {key: factor * dxi[0, k]
+                     for key, (k, factor) in columns.items()})
         keys = _grad_keys(assembias)
         ngal, xi, dngal, dxi = self.predict_batch_grad(
             np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
@@ -858,7 +894,8 @@ class TabCorr:
     # -- Fisher matrix of the likelihood ---------------------------------------------------
 
     def chi2_fisher_batch(self, theta, data, precision, n_gauss_prim=10,
-                          modulate_with_cenocc=False, assembias=False):
+                          modulate_with_cenocc=False, assembias=False,
+                          family='zheng07'):
         """`chi2_grad_batch` with the Fisher matrix of the likelihood, from
         the same launch: with ``dxi_k`` the Jacobian column of parameter ``k``
         (`ZHENG07_KEYS` order),
@@ -880,7 +917,8 @@ class TabCorr:
         on its batch, and not on ``data``.  Where the value divides by zero
         (``ngal = 0``, ``sigma_logM = 0``) the entries are NaN or inf, as the
         gradients are.  ``assembias=True``: 7 columns, as in
-        `predict_batch_grad`, and a ``(7, 7)`` matrix.
+        `predict_batch_grad`, and a ``(7, 7)`` matrix;
+        ``family='leauthaud11'``: 11 columns and an ``(11, 11)`` matrix.
 
         Returns
         -------
@@ -888,10 +926,10 @@ class TabCorr:
         dngal, dchi2 : ``(n_draws, 5)`` -- those of `chi2_grad_batch`, bit for bit
         fisher : ``(n_draws, 5, 5)``
         """
-        if assembias:
-            return self._chi2_grad_assembias(
+        if assembias or family != 'zheng07':
+            return self._chi2_grad_wide(
                 theta, data, precision, n_gauss_prim, modulate_with_cenocc,
-                True)
+                True, assembias, family)
         theta = _grad_theta(theta)
         data, precision = _chi2_operands(data, precision,
                                          len(self.tpcf_matrix))
@@ -911,7 +949,8 @@ class TabCorr:
         return ngal, chi2, dngal, dchi2, fisher
 
     def fisher_batch(self, theta, precision, n_gauss_prim=10,
-                     modulate_with_cenocc=False, assembias=False):
+                     modulate_with_cenocc=False, assembias=False,
+                     family='zheng07'):
         """The forecast form of `chi2_fisher_batch`, which needs no data: the
         same launch with a zero data vector, without ``chi2`` and ``dchi2``.
         The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal`` part of
@@ -926,7 +965,8 @@ class TabCorr:
         ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
             theta, np.zeros(len(self.tpcf_matrix)), precision,
             n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias)
+            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
+            family=family)
         return ngal, dngal, fisher
 
     def fisher(self, model, precision, n_gauss_prim=10,
@@ -936,7 +976,10 @@ class TabCorr:
         as `predict_grad` takes.  The Gauss-Newton Hessian of chi2 is
         ``2 fisher``; the ``ngal`` part of a likelihood is the caller's, from
         ``dngal`` by an outer product.  ``assembias=True``: a decorated
-        model, `ZHENG07_ASSEMBIAS_KEYS` and a ``(7, 7)`` matrix.
+        model, `ZHENG07_ASSEMBIAS_KEYS` and a ``(7, 7)`` matrix.  A
+        `tabcorr_amd.Leauthaud11Model`: `LEAUTHAUD11_KEYS` and the
+        ``(16, 16)`` matrix ``J^T F J`` with ``F`` the ``(11, 11)`` matrix of
+        the device columns and ``J`` `Leauthaud11Model.device_jacobian`.
 
         Returns
         -------
@@ -947,7 +990,17 @@ class TabCorr:
         """
         if check_consistency:
             self._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'fisher')
+        spec = _grad_spec(model, assembias, 'fisher', leauthaud11=True)
+        if spec.family == 'leauthaud11':
+            ngal, dngal, fisher = self.fisher_batch(
+                spec.theta[np.newaxis], precision, n_gauss_prim=n_gauss_prim,
+                modulate_with_cenocc=spec.modulate_with_cenocc,
+                family='leauthaud11')
+            jacobian = model.device_jacobian()
+            return (float(ngal[0]),
+                    {key: float(factor * dngal[0, k]) for key, (k, factor)
+                     in _leauthaud11_columns(model).items()},
+                    jacobian.T @ fisher[0] @ jacobian)
         keys = _grad_keys(assembias)
         ngal, dngal, fisher = self.fisher_batch(
             np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
@@ -982,8 +1035,9 @@ class TabCorr:
         launch.  Contracted with the caller's own ``d<N>/dtheta`` (``n_bins``
         numbers per parameter, e.g. from differenced `mean_occupation_batch`
         calls) it is the gradient of any scalar of ``(ngal, xi)`` for EVERY
-        occupation model -- decorated, Leauthaud11 or custom -- whatever the
-        number of parameters.
+        occupation model, whatever the number of parameters.  (Zheng07, its
+        assembly-bias decoration and Leauthaud11 have analytic gradients of
+        their own: `predict_batch_grad`.)
 
         Parameters
         ----------
@@ -1135,26 +1189,53 @@ def _flags(separate_gal_type=False, modulate_with_cenocc=False,
             (_lib.FLAG_LEAUTHAUD11 if family == 'leauthaud11' else 0))
 
 
-def _grad_keys(assembias=False):
+def _grad_keys(assembias=False, family='zheng07'):
     """The differentiated model parameters, in column order."""
+    if family == 'leauthaud11':
+        return LEAUTHAUD11_GRAD_KEYS
     return ZHENG07_ASSEMBIAS_KEYS if assembias else ZHENG07_KEYS
 
 
-def _grad_theta(theta, assembias=False):
+def _grad_theta(theta, assembias=False, family='zheng07'):
     """The ``(n_draws, 5)`` parameter array of the gradient calls --
-    ``(n_draws, 7)`` for the model decorated with assembly bias."""
+    ``(n_draws, 7)`` for the model decorated with assembly bias,
+    ``(n_draws, 14)`` for the Leauthaud11 family (eleven differentiated
+    columns and the three inputs)."""
+    if family not in ('zheng07', 'leauthaud11'):
+        raise ValueError("family must be 'zheng07' or 'leauthaud11'.")
+    if family == 'leauthaud11' and assembias:
+        raise ValueError("family='leauthaud11' has no assembly bias: not "
+                         "together with assembias=True.")
     theta = _lib.contiguous(np.atleast_2d(theta))
-    n_cols = len(_grad_keys(assembias))
+    n_cols = 14 if family == 'leauthaud11' else len(_grad_keys(assembias))
     if theta.ndim != 2 or theta.shape[1] != n_cols:
         raise ValueError('theta must have shape (n_draws, {}), got {}.'.format(
             n_cols, theta.shape))
     return theta
 
 
-def _grad_spec(model, assembias, what):
+def _leauthaud11_columns(model):
+    """`LEAUTHAUD11_KEYS` -> (device column, factor): each of the sixteen
+    parameters moves one of the eleven device columns -- ``smhm_X_0`` and
+    ``smhm_X_a`` the relation's X, the other six their own --, by its entry
+    of `Leauthaud11Model.device_jacobian` (zero for ``smhm_X_a`` at
+    redshift 0)."""
+    jacobian = model.device_jacobian()
+    columns = {}
+    for j, key in enumerate(LEAUTHAUD11_KEYS):
+        k = j // 2 if j < 10 else j - 5
+        columns[key] = (k, float(jacobian[k, j]))
+    return columns
+
+
+def _grad_spec(model, assembias, what, leauthaud11=False):
     """The device spec of the model of an un-batched gradient call: plain
-    Zheng07 -- with ``assembias`` Zheng07 decorated with assembly bias."""
+    Zheng07 -- with ``assembias`` Zheng07 decorated with assembly bias;
+    ``leauthaud11``: the caller serves a `Leauthaud11Model` too."""
     spec = device_spec(model)
+    if (leauthaud11 and not assembias and spec is not None and
+            spec.family == 'leauthaud11'):
+        return spec
     if not assembias:
         if spec is None or spec.family != 'zheng07' or spec.assembias:
             raise NotImplementedError(

@@ -36,8 +36,17 @@ differences over seven parameters.  Device-resident and pipelined, as the first 
 the host-array methods.  The expectation is about 8/6 of the plain gradient -- eight quantities
 for six in the dot products and the LDS rows, the matrix stream unchanged.
 
+The Leauthaud11 leg (--only leauthaud11; not part of the default run) times the gradients of
+that family, predict_batch_grad(family='leauthaud11') and chi2_fisher_batch(...), on BASELINE
+configs[1] and on the bolplanck w_p table of tests/golden next to what they replace -- 22 calls
+of predict_batch(family='leauthaud11'), the central differences over eleven parameters -- and
+next to the Zheng07 gradient on the same table.  Device-resident and pipelined, as the first leg,
+with and without modulate_with_cenocc (one Newton solve more per satellite node).  The
+expectation is about twice the Zheng07 gradient's matrix work, twelve dot products per row for
+six, and node loops that the Newton solves dominate.
+
 Prints one JSON line and, with --notes, appends the figures to that file.  --only vjp, --only
-fisher, --only assembias: that leg alone.
+fisher, --only assembias, --only leauthaud11: that leg alone.
 """
 
 import argparse
@@ -176,6 +185,95 @@ def measure_assembias(name, n_prim, n_r, n_draws, seconds):
     result['host_differences_us'] = 7 * (result['host_forward_us'] +
                                          result['host_forward_again_us'])
     return result
+
+
+def measure_leauthaud11(name, halotab, modulate, n_draws, seconds):
+    from tabcorr_amd import _lib, synthetic
+    device = halotab.to_device()
+    lib, handle = device.lib, device.handle
+    n_r = device.n_r
+    memory = Device(lib, _lib)
+    theta = np.ascontiguousarray(synthetic.leauthaud11_draws(n_draws, seed=1))
+    plain = synthetic.zheng07_draws(n_draws, seed=1)
+    d_theta, d_plain = memory.upload(theta), memory.upload(plain)
+    d_ngal, d_xi = memory.malloc(n_draws), memory.malloc(n_draws * n_r)
+    d_dngal, d_dxi = memory.malloc(n_draws * 11), memory.malloc(n_draws * 11 * n_r)
+    d_chi2, d_dchi2 = memory.malloc(n_draws), memory.malloc(n_draws * 11)
+    d_fisher = memory.malloc(n_draws * 121)
+    rng = np.random.default_rng(3)
+    data = np.ascontiguousarray(rng.uniform(0.5, 1.5, n_r))
+    precision = np.ascontiguousarray(np.eye(n_r) + 0.01 * rng.normal(size=(n_r, n_r)))
+    operands = (_lib.as_double_p(data), _lib.as_double_p(precision))
+    flags = _lib.FLAG_MODULATE_WITH_CENOCC if modulate else 0
+
+    def forward():
+        _lib.check(lib.tc_predict_zheng07_batch_device(
+            handle, d_theta, 14, n_draws, 10, flags | _lib.FLAG_LEAUTHAUD11, d_ngal, d_xi))
+
+    def gradient():
+        _lib.check(lib.tc_predict_grad_leauthaud11_batch_device(
+            handle, d_theta, 14, n_draws, 10, flags, d_ngal, d_xi, d_dngal, d_dxi))
+
+    def chi2_fisher():
+        _lib.check(lib.tc_chi2_grad_leauthaud11_batch_device(
+            handle, d_theta, 14, n_draws, 10, flags, *operands, d_ngal, d_chi2, d_dngal, d_dchi2,
+            d_fisher))
+
+    def zheng07_gradient():
+        _lib.check(lib.tc_predict_grad_zheng07_batch_device(handle, d_plain, 5, n_draws, 10,
+                                                            flags, d_ngal, d_xi, d_dngal, d_dxi))
+
+    def synchronize():
+        _lib.check(lib.tc_table_synchronize(handle))
+
+    result = {'table': name, 'n_bins': len(halotab.gal_type), 'n_r': n_r, 'n_draws': n_draws,
+              'modulate': bool(modulate)}
+    try:
+        # forward first and last: the two figures bracket the drift of the run
+        for key, call in (('forward_us', forward), ('grad_us', gradient),
+                          ('chi2_fisher_us', chi2_fisher), ('zheng07_grad_us', zheng07_gradient),
+                          ('forward_again_us', forward)):
+            result[key] = sustained(call, synchronize, seconds) * 1e6
+        # the gradient kernel alone, from the launches' own events
+        milliseconds, mean, count = ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+        _lib.check(lib.tc_table_timer_begin(handle, 1))
+        gradient()
+        synchronize()
+        _lib.check(lib.tc_table_timer_end(handle, ctypes.byref(milliseconds)))
+        _lib.check(lib.tc_table_kernel_time(handle, ctypes.byref(count), ctypes.byref(mean)))
+        result['grad_kernel_us'] = count.value * mean.value * 1e3
+        workgroups, waves, lds = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        splits = ctypes.c_int()
+        _lib.check(lib.tc_table_last_launch(handle, ctypes.byref(workgroups), ctypes.byref(waves),
+                                            ctypes.byref(splits), ctypes.byref(lds)))
+        result['grad_lds_bytes'] = lds.value
+    finally:
+        synchronize()
+        memory.free_all()
+    forward_us = 0.5 * (result['forward_us'] + result['forward_again_us'])
+    result['differences_us'] = 22 * forward_us
+    result['differences_over_grad'] = result['differences_us'] / result['grad_us']
+    result['differences_over_chi2_fisher'] = result['differences_us'] / result['chi2_fisher_us']
+    result['grad_over_zheng07_grad'] = result['grad_us'] / result['zheng07_grad_us']
+    return result
+
+
+def write_leauthaud11_notes(notes, results, n_draws):
+    notes.write('\n## tools/grad_bench.py --only leauthaud11, %d draws per call\n\n' % n_draws)
+    notes.write('Device-resident, pipelined, us per call.\n\n')
+    notes.write('| table | bins | modulate | forward(leauthaud11) us | gradient us (kernel alone) | '
+                'chi2 + Fisher us | 22 forward calls us | Zheng07 gradient us | '
+                '22 forward / gradient | 22 forward / chi2 + Fisher | gradient / Zheng07 gradient '
+                '| LDS bytes |\n')
+    notes.write('|---|---|---|---|---|---|---|---|---|---|---|---|\n')
+    for r in results:
+        notes.write('| %s | %d | %s | %.1f, %.1f after | %.1f (%.1f) | %.1f | %.1f | %.1f | %.2f | '
+                    '%.2f | %.2f | %d |\n' % (
+                        r['table'], r['n_bins'], 'yes' if r['modulate'] else 'no',
+                        r['forward_us'], r['forward_again_us'], r['grad_us'], r['grad_kernel_us'],
+                        r['chi2_fisher_us'], r['differences_us'], r['zheng07_grad_us'],
+                        r['differences_over_grad'], r['differences_over_chi2_fisher'],
+                        r['grad_over_zheng07_grad'], r['grad_lds_bytes']))
 
 
 def write_assembias_notes(notes, results, n_draws):
@@ -417,9 +515,26 @@ def main():
     parser.add_argument('--draws', type=int, default=10000)
     parser.add_argument('--seconds', type=float, default=1.0)
     parser.add_argument('--notes', default=None, help='append the figures to this file')
-    parser.add_argument('--only', choices=['vjp', 'fisher', 'assembias'], default=None,
+    parser.add_argument('--only', choices=['vjp', 'fisher', 'assembias', 'leauthaud11'],
+                        default=None,
                         help='one leg alone')
     args = parser.parse_args()
+    if args.only == 'leauthaud11':
+        from tabcorr_amd import TabCorr, synthetic
+        table = synthetic.synthetic_table(50, 1, (19, ), 'auto', seed=0)
+        tables = [('BASELINE configs[1]',
+                   TabCorr.from_arrays(table['gal_type'], table['tpcf_matrix'],
+                                       table['tpcf_shape'], table['attrs'])),
+                  ('bolplanck w_p table',
+                   TabCorr.read(os.path.join(REPO, 'tests', 'golden', 'bolplanck_wp.hdf5')))]
+        results = [measure_leauthaud11(name, halotab, modulate, args.draws, args.seconds)
+                   for name, halotab in tables for modulate in (False, True)]
+        print(json.dumps({'leauthaud11_metric': 'us per call, device-resident, pipelined',
+                          'leauthaud11': results}))
+        if args.notes:
+            with open(args.notes, 'a') as notes:
+                write_leauthaud11_notes(notes, results, args.draws)
+        return
     if args.only == 'assembias':
         results = [measure_assembias('two percentiles, 100 bins', 25, 19, args.draws,
                                      args.seconds),
