@@ -700,8 +700,16 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *                 the PCIe aperture (no PCIe reads while the kernel polls); 0: in page-locked
  *                 host memory, as on systems without a large BAR.
  *   "deterministic"  which of a call's possible kernel forms runs, and hence the LAST BITS of its
- *                 results (every form agrees with the reference to ~1e-14; the reference itself,
- *                 tabcorr/tabcorr.py:580-683, is deterministic).
+ *                 results (the reference itself, tabcorr/tabcorr.py:580-683, is deterministic).
+ *                 Every form's mean occupations agree PER BIN with the reference's formula in
+ *                 extended precision to 1.2e-15 absolute (centrals) and 7.7e-15 relative
+ *                 (satellites) -- largest over the strata of tests/test_gpu_occupation_forms.py on
+ *                 an MI355X: occ_zheng07_kernel 1.2e-15 / 7.6e-15, the one-launch forms 8 x 64
+ *                 8.9e-16 / 6.3e-15, 16 x 64 4.5e-16 / 5.4e-15, 8 x 32 4.1e-16 / 5.0e-15, 8 x 40
+ *                 4.5e-16 / 5.9e-15, mode cross 8.3e-16 / 7.6e-15 (register form 4.7e-16 /
+ *                 6.5e-15), un-batched 3.5e-16 / 3.3e-15 -- for |sigma_logM| >= 0.03 and
+ *                 satellite bins whose condition number with respect to M0 is at most 24: the
+ *                 rounding of 10^logM0 (6e-16) reaches a bin multiplied by that number.
  *                 0 (default): the fastest form for the call -- a function of the table, the
  *                 flags, the entry point (un-batched, host arrays, device pointers,
  *                 asynchronous) and the batch size.  Never of timing or of the number of calls

@@ -22,6 +22,13 @@ extern "C" {
  * as the assembly-bias gradient kernels form it from the Gaussian of kind 5 (half_erfc_from_gauss;
  * from |x| = 6 on, where kind 5 is zero, from the libm Gaussian). */
 int tc_debug_fastmath(int kind, int64_t n, const double* x, double* y);
+/* The same functions as the DEVICE compiles them (needs a GPU): a small kernel stages the table
+ * in LDS as the occupation kernel does and applies kinds 0 - 7 to x; kind 8 is the reciprocal of
+ * the satellites' expansion (series.h: sat::reciprocal -- the hardware estimate and two Newton
+ * steps on the device, 1.0 / x on the host), kind 9 exp2 with keep == false (exactly 0).  The
+ * device text differs from the host's in log2 (frexp_mant / frexp_exp / ubfe against frexp and
+ * shifts), ldexp and the contraction of a * b + c. */
+int tc_debug_fastmath_device(int kind, int64_t n, const double* x, double* y);
 
 /* The dense matrix-operand layout the gradient kernel of mode auto reads
  * (tabcorr_amd/csrc/grad.h), built from packed (n_r, n_bins (n_bins + 1) / 2) lower triangles

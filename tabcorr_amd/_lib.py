@@ -58,6 +58,8 @@ SIGNATURES = {
     'tc_gauss_legendre': [ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_fastmath': [ctypes.c_int, ctypes.c_int64, c_double_p,
                           c_double_p],
+    'tc_debug_fastmath_device': [ctypes.c_int, ctypes.c_int64, c_double_p,
+                                 c_double_p],
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_grad_lds': [ctypes.c_int] * 7 + [c_int64_p],
     'tc_debug_leauthaud11_node_grad': [c_double_p, ctypes.c_int, ctypes.c_int64, c_double_p,

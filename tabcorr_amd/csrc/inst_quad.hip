@@ -207,3 +207,80 @@ int launch_occ_from_array_kernel(const double* occupation_device, int64_t n_draw
 
 }  // namespace host
 }  // namespace tc
+
+// ---- TEST INFRASTRUCTURE (include/tabcorr_amd_testing.h: tc_debug_fastmath_device) ------------
+//
+// The table-driven functions of fastmath.h and series::sat::reciprocal as the DEVICE compiles
+// them (frexp_mant / frexp_exp / ubfe in log2, the hardware reciprocal with two Newton steps,
+// the device's ldexp and FMA contraction), with the table staged in LDS as occ_zheng07_kernel
+// stages it.  Never called by the product.
+namespace tc {
+
+__global__ __launch_bounds__(256) void debug_fastmath_kernel(int kind, int64_t n,
+                                                             const double* math_table,
+                                                             const double* x, double* y) {
+  __shared__ __attribute__((aligned(16))) double table[fm::kTableDoubles];
+  const fm::Consts kc = fm::make_consts();
+  {
+    typedef double __attribute__((ext_vector_type(2))) double2v;
+    const double2v* src = (const double2v*)math_table;
+    double2v* dst = (double2v*)table;
+    for (int i = threadIdx.x; i < fm::kTableDoubles / 2; i += blockDim.x) dst[i] = src[i];
+  }
+  __syncthreads();
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const double v = x[i];
+    double out = 0.0, gauss = 0.0;
+    switch (kind) {
+      case 0: out = fm::erf_fast(table, kc, v); break;
+      case 1: out = fm::log2_fast(table, kc, v); break;
+      case 2: out = fm::exp2_fast(table, kc, v); break;
+      case 3: out = fm::exp10_fast(table, kc, v); break;
+      case 4: out = fm::erf_gauss_fast(table, kc, v, &gauss); break;
+      case 5:
+        (void)fm::erf_gauss_fast(table, kc, v, &gauss);
+        out = gauss;
+        break;
+      case 6: out = fm::log_fast(table, kc, v); break;
+      case 7:
+        (void)fm::erf_gauss_fast(table, kc, v, &gauss);
+        if (fabs(v) >= 6.0) gauss = 1.1283791670955125739 * exp(-v * v);
+        out = fm::half_erfc_from_gauss(fabs(v), gauss);
+        break;
+      case 8: out = series::sat::reciprocal(v); break;
+      default: out = fm::exp2_fast(table, kc, v, false); break;      // 9: keep == false
+    }
+    y[i] = out;
+  }
+}
+
+}  // namespace tc
+
+extern "C" int tc_debug_fastmath_device(int kind, int64_t n, const double* x, double* y) {
+  using tc::host::fail;
+  TC_CHECK(kind >= 0 && kind <= 9 && n >= 0 && (n == 0 || (x && y)), "invalid arguments");
+  if (n == 0) return TC_OK;
+  std::vector<double> table(tc::fm::kTableDoubles);
+  tc::fm::build_tables(table.data());
+  const size_t bytes = (size_t)n * sizeof(double), table_bytes = table.size() * sizeof(double);
+  void *d_table = nullptr, *d_x = nullptr, *d_y = nullptr;
+  auto run = [&]() -> int {
+    TC_HIP(hipMalloc(&d_table, table_bytes));
+    TC_HIP(hipMalloc(&d_x, bytes));
+    TC_HIP(hipMalloc(&d_y, bytes));
+    TC_HIP(hipMemcpy(d_table, table.data(), table_bytes, hipMemcpyHostToDevice));
+    TC_HIP(hipMemcpy(d_x, x, bytes, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(tc::debug_fastmath_kernel, dim3(blocks), dim3(256), 0, nullptr, kind, n,
+                       (const double*)d_table, (const double*)d_x, (double*)d_y);
+    TC_HIP(hipGetLastError());
+    TC_HIP(hipDeviceSynchronize());
+    TC_HIP(hipMemcpy(y, d_y, bytes, hipMemcpyDeviceToHost));
+    return TC_OK;
+  };
+  const int status = run();
+  for (void* p : {d_table, d_x, d_y})
+    if (p != nullptr) (void)hipFree(p);
+  return status;
+}
