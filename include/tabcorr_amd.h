@@ -20,7 +20,10 @@
  *     table handles it was created from (their caches, lanes, timers and fused-likelihood
  *     state): a call on the interpolator must not run concurrently with a call on any of
  *     its tables either (the Python classes take the tables' locks with the
- *     interpolator's).
+ *     interpolator's).  A joint handle (tc_joint) works through its tables in the same way --
+ *     its launches run on the lanes of its FIRST table and read every table's matrix --: a call
+ *     on the joint must not run concurrently with a call on any of its tables, and no call on
+ *     it may follow the destruction of one of them.
  *   - there is no CPU fallback: every compute entry point fails with TC_ERR_HIP when
  *     no gfx950 device is usable.
  */
@@ -66,6 +69,7 @@ extern "C" {
 typedef struct tc_table tc_table;
 typedef struct tc_interp tc_interp;
 typedef struct tc_comm tc_comm;
+typedef struct tc_joint tc_joint;
 
 /* ---- runtime ---------------------------------------------------------------------- */
 
@@ -523,6 +527,65 @@ int tc_interp_chi2_grad_assembias_batch_device(tc_interp* interp, const double* 
                                                double* ngal_device, double* chi2_device,
                                                double* dngal_device, double* dchi2_device,
                                                double* fisher_device);
+
+/* Joint likelihood of several tables (extension): the data vector of the reference's documented
+ * likelihood step is the concatenation of two tables' predictions, (w_p, DeltaSigma)
+ * (docs/guides/overview.rst:86-92), and its covariance couples them.  A joint handle over 1 .. 16
+ * tables that share one halo table evaluates a batch of draws against ALL of them in one launch:
+ * the occupations and their derivatives once per draw, then every table's contraction (mode auto
+ * and mode cross may be mixed) into its rows r_offset[t] .. r_offset[t] + n_r[t] of the N =
+ * sum_t n_r[t] concatenated ones, in list order.
+ *
+ * tc_joint_create: every table on the same device, with a float64 compute dtype and the bins
+ * (all gal_type columns) of the first one, no handle twice; anything else is TC_ERR_INVALID with
+ * a message naming the table.  The joint owns no table: it works through them (Conventions);
+ * tc_joint_destroy does not touch them.  tc_joint_info: r_offset holds n_tables entries; any pointer may be
+ * NULL. */
+int tc_joint_create(tc_table* const* tables, int n_tables, tc_joint** joint);
+int tc_joint_destroy(tc_joint* joint);
+int tc_joint_synchronize(tc_joint* joint);
+int tc_joint_info(const tc_joint* joint, int* n_tables, int* n_r_total, int* r_offset);
+/* The concatenated prediction with its exact derivatives (tc_predict_grad_zheng07_batch): ngal
+ * (n_draws), xi (n_draws, N), dngal (n_draws, 5), dxi (n_draws, 5, N) -- the tables share their
+ * bins, so there is one ngal per draw.  flags selects the family: 0 or
+ * TC_FLAG_MODULATE_WITH_CENOCC plain Zheng07 (n_theta 5); with TC_FLAG_ASSEMBIAS the model
+ * decorated with assembly bias (tc_predict_grad_assembias_batch: n_theta 7, and 7 wherever 5
+ * stands).  TC_ERR_UNSUPPORTED with a message: TC_FLAG_LEAUTHAUD11, TC_FLAG_SEPARATE_GAL_TYPE,
+ * any other flag, and a joint beyond the LDS of a workgroup: the rows of w and dw of every bin (3
+ * per central and 6 per satellite bin; 4 and 7 decorated) plus 6 (8) rows of totals plus, for the
+ * likelihood, 6 N (8 N) rows of 128 bytes within 160 KiB.  Every joint keeps the rows in LDS, so
+ * a joint of mode-cross tables with more bins than that admits is refused although each table
+ * alone is served.
+ * One launch per batch; a draw's results depend on the draw alone (batch-invariant by
+ * construction), and a row's arithmetic does not depend on the wave that runs it.  A joint of ONE
+ * table returns the bits of that table's own tc_predict_grad_* / tc_chi2_grad_* /
+ * tc_chi2_fisher_* call.  Where ngal = 0 the results are what IEEE arithmetic gives.
+ * Host arrays run slab-wise on lane 0 of the first table; the `_device` forms enqueue on its next
+ * lane and return (tc_joint_synchronize waits). */
+int tc_joint_predict_grad_batch(tc_joint* joint, const double* theta, int n_theta,
+                                int64_t n_draws, int n_gauss_prim, unsigned flags, double* ngal,
+                                double* xi, double* dngal, double* dxi);
+int tc_joint_predict_grad_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
+                                       int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                       double* ngal_device, double* xi_device,
+                                       double* dngal_device, double* dxi_device);
+/* chi2, its gradient and the Fisher matrix of the joint data vector, finished in the same launch
+ * against the full precision matrix: data (N) and precision (N, N) in the concatenated order,
+ * host arrays in both forms (uploaded when they change).  chi2 (n_draws), dchi2 (n_draws, 5),
+ * fisher (n_draws, 5, 5) -- which may be NULL: not asked for -- are defined as by
+ * tc_chi2_fisher_zheng07_batch with N for n_r: P_sym = (precision + precision^T) / 2, the sums
+ * over s ascending inside r ascending, every pair k <= l computed once (bit-symmetric); fisher
+ * does not depend on `data`, and the other outputs do not depend on whether it is asked for. */
+int tc_joint_chi2_grad_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
+                             int n_gauss_prim, unsigned flags, const double* data,
+                             const double* precision, double* ngal, double* chi2, double* dngal,
+                             double* dchi2, double* fisher);
+int tc_joint_chi2_grad_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
+                                    int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                    const double* data, const double* precision,
+                                    double* ngal_device, double* chi2_device,
+                                    double* dngal_device, double* dchi2_device,
+                                    double* fisher_device);
 
 /* Asynchronous host-to-host forms (page-locked theta, x, outputs; see
  * tc_predict_zheng07_batch_async): upload, kernels and download of a call on one of the

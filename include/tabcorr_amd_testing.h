@@ -97,6 +97,11 @@ int tc_debug_quad_schedule(int n_bins, int n_central, int by_type, int n_tiles, 
  * predict_fused_kernel walk (hostmath.h: triangle_parts): first block row, block column and
  * number of units of each of the n_parts parts. */
 int tc_debug_triangle_parts(int n_rb, int n_parts, int32_t* rb0, int32_t* cb0, int32_t* count);
+/* The LDS bytes per workgroup of grad_joint_kernel (tabcorr_amd/csrc/joint.h: joint_lds_bytes)
+ * for a joint of tables with n_bins bins, the first n_central centrals, and n_r_total result rows
+ * in all -- no device needed; chi2: the likelihood is finished in the launch; n_params 5 or 7. */
+int tc_debug_joint_lds_bytes(int n_bins, int n_central, int n_r_total, int chi2, int n_params,
+                             int64_t* bytes);
 /* Groups of bins that share their Gauss-Legendre nodes (tabcorr_amd/csrc/hostmath.h:
  * find_node_groups; identical log_prim_haloprop_min / max and galaxy type), for n_bins bins in
  * library order of which the first n_central are centrals: group i = member[begin[i] ..

@@ -285,6 +285,28 @@ SIGNATURES = {
         ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p],
+    # joint of tables: the family by flags, the trailing fisher may be None
+    'tc_joint_create': [c_void_pp, ctypes.c_int, c_void_pp],
+    'tc_joint_destroy': [ctypes.c_void_p],
+    'tc_joint_synchronize': [ctypes.c_void_p],
+    'tc_joint_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p],
+    'tc_joint_predict_grad_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p],
+    'tc_joint_predict_grad_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p],
+    'tc_joint_chi2_grad_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p, c_double_p, c_double_p, c_double_p],
+    'tc_joint_chi2_grad_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
+    'tc_debug_joint_lds_bytes': [ctypes.c_int] * 5 + [c_int64_p],
     'tc_table_set_option': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int],
     'tc_table_timer_begin': [ctypes.c_void_p, ctypes.c_int],
     'tc_table_timer_end': [ctypes.c_void_p, c_float_p],

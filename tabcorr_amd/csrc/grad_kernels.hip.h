@@ -313,7 +313,8 @@ __device__ __forceinline__ void finish_fisher(const GradArgs& a, const double* s
   }
 }
 
-// ---- the pieces of grad_auto_kernel (grad_interp_auto_kernel runs them per class and table) -----
+// ---- the pieces of grad_auto_kernel (grad_interp_auto_kernel runs them per class and table,
+// joint_kernels.hip.h: grad_joint_kernel once per draw and then per table of a joint) ----------
 
 // Phase 1: thread = (bin i % 16, draw) writes w and dw of its bins, and the row of zeros.
 template <int NP>
@@ -396,6 +397,76 @@ __device__ __forceinline__ double auto_dxi(const double* acc, int p, double xi,
   return 2.0 * acc[p] * inv_ngal2 - 2.0 * xi * total[p * kGradDraws + col] * inv_ngal;
 }
 
+// Phase 1 of a workgroup whose rows stay in LDS (grad_auto_kernel, grad_joint_kernel): the node
+// loops of every bin into w, then the totals over the bins in bin order -- total (6, 16) = ngal and
+// its derivatives, stored for the draws of the batch --; both behind a barrier.
+template <int NP>
+__device__ __forceinline__ void auto_occupations(const GradArgs& a, const fm::Consts& k, double* w,
+                                                 double* total, int64_t draw0, int zero_row) {
+  const int t = threadIdx.x;
+  const int col = t % kGradDraws;
+  {
+    const typename DrawOf<NP>::type d = load_draw<NP>(a, k, draw0 + col);
+    auto_node_loops<NP>(a, k, d, w, zero_row);
+  }
+  __syncthreads();
+  if (t < (NP + 1) * kGradDraws) {
+    const int p = t / kGradDraws;
+    const double sum = auto_total<NP>(w, p, col, a.n_bins, a.n_central, zero_row);
+    total[t] = sum;
+    const int64_t draw = draw0 + col;
+    if (draw < a.n_draws) {
+      if (p == 0)
+        a.ngal[draw] = sum;
+      else
+        a.dngal[draw * NP + (p - 1)] = sum;
+    }
+  }
+  __syncthreads();
+}
+
+// Where quantity p (0: the value, 1 + k: its derivative) of row r of the a.n_r result rows of a
+// draw goes: the prediction's arrays, or -- the likelihood -- the stash that finish_chi2 and
+// finish_fisher read, the value as its residual against the data.
+template <int NP>
+__device__ __forceinline__ void store_result(const GradArgs& a, double* stash, int64_t draw,
+                                             int col, int r, int p, double value) {
+  const int n_r = a.n_r;
+  if (a.xi != nullptr) {
+    if (draw >= a.n_draws) return;
+    if (p == 0)
+      a.xi[draw * n_r + r] = value;
+    else
+      a.dxi[(draw * NP + (p - 1)) * n_r + r] = value;
+  } else {
+    stash[((size_t)p * n_r + r) * kGradDraws + col] = p == 0 ? value - a.chi2_data[r] : value;
+  }
+}
+
+// Phase 3 of one r bin of mode auto, one wave: xi and dxi from the products `acc` (auto_products)
+// and the totals, written to result row r by the wave's first row group.
+template <int NP>
+__device__ __forceinline__ void auto_store_row(const GradArgs& a, const double* acc,
+                                               const double* total, double* stash, int64_t draw,
+                                               int r, double inv_ngal, double inv_ngal2) {
+  const int lane = threadIdx.x % 64;
+  const int group = lane / kGradDraws, col = lane % kGradDraws;
+  const double xi = auto_xi(acc, inv_ngal2);
+  if (group == 0) store_result<NP>(a, stash, draw, col, r, 0, xi);
+#pragma unroll
+  for (int p = 1; p < NP + 1; ++p) {
+    const double dxi = auto_dxi(acc, p, xi, total, col, inv_ngal, inv_ngal2);
+    if (group == 0) store_result<NP>(a, stash, draw, col, r, p, dxi);
+  }
+}
+
+// Phase 3, mode cross: xi = y_0 / ngal and dxi_k = (y_k - xi dngal_k) / ngal from the products
+// y_p = T_r . (quantity p of the bins).
+__device__ __forceinline__ double cross_xi(double y0, double inv_ngal) { return y0 * inv_ngal; }
+__device__ __forceinline__ double cross_dxi(double y, double xi, double dngal, double inv_ngal) {
+  return (y - xi * dngal) * inv_ngal;
+}
+
 // ---- the pieces of grad_cross_kernel ------------------------------------------------------------
 
 // w and dw of the bins slab0 .. slab0 + count - 1 into the slab (6, kGradCrossSlab, 16).
@@ -430,56 +501,18 @@ __global__ __launch_bounds__(kGradThreads) void grad_auto_kernel(const GradArgs 
   double* stash = total + NQ * kGradDraws;                     // (6, n_r, 16), likelihood only
   const fm::Consts k = fm::make_consts();
 
-  // phase 1: thread = (bin i % 16, draw)
-  {
-    const typename grad::DrawOf<NP>::type d = grad::load_draw<NP>(a, k, draw0 + col);
-    grad::auto_node_loops<NP>(a, k, d, w, zero_row);
-  }
-  __syncthreads();
-  // totals over the bins in bin order: ngal and its derivatives
-  if (t < NQ * kGradDraws) {
-    const int p = t / kGradDraws;
-    const double sum = grad::auto_total<NP>(w, p, col, n_bins, n_central, zero_row);
-    total[t] = sum;
-    const int64_t draw = draw0 + col;
-    if (draw < a.n_draws) {
-      if (p == 0)
-        a.ngal[draw] = sum;
-      else
-        a.dngal[draw * NP + (p - 1)] = sum;
-    }
-  }
-  __syncthreads();
+  // phase 1: thread = (bin i % 16, draw); the totals are ngal and its derivatives
+  grad::auto_occupations<NP>(a, k, w, total, draw0, zero_row);
 
   // phase 2: wave v takes the r bins v, v + 4, ...
-  const int lane = t % 64, wave = t / 64;
-  const int group = lane / kGradDraws;
+  const int wave = t / 64;
   const double ngal = total[col];
   const double inv_ngal = 1.0 / ngal;
   const double inv_ngal2 = 1.0 / (ngal * ngal);
   for (int r = wave; r < n_r; r += kGradWaves) {
     double acc[NQ];
     grad::auto_products<NP>(a, w, r, zero_row, acc);
-    const double xi = grad::auto_xi(acc, inv_ngal2);
-    const int64_t draw = draw0 + col;
-    if (group == 0) {
-      if (a.xi != nullptr) {
-        if (draw < a.n_draws) a.xi[draw * n_r + r] = xi;
-      } else {
-        stash[(size_t)r * kGradDraws + col] = xi - a.chi2_data[r];
-      }
-    }
-#pragma unroll
-    for (int p = 1; p < NQ; ++p) {
-      const double dxi = grad::auto_dxi(acc, p, xi, total, col, inv_ngal, inv_ngal2);
-      if (group == 0) {
-        if (a.xi != nullptr) {
-          if (draw < a.n_draws) a.dxi[(draw * NP + (p - 1)) * n_r + r] = dxi;
-        } else {
-          stash[((size_t)p * n_r + r) * kGradDraws + col] = dxi;
-        }
-      }
-    }
+    grad::auto_store_row<NP>(a, acc, total, stash, draw0 + col, r, inv_ngal, inv_ngal2);
   }
   if (a.xi == nullptr) {
     __syncthreads();
@@ -542,8 +575,8 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
     const int r = item / (NQ * kGradDraws), p = item / kGradDraws % NQ;
     if (p == 0) continue;
     const size_t slot = ((size_t)p * n_r + r) * kGradDraws + col;
-    const double xi = y[(size_t)r * kGradDraws + col] * inv_ngal;
-    const double dxi = (y[slot] - xi * total[p * kGradDraws + col]) * inv_ngal;
+    const double xi = grad::cross_xi(y[(size_t)r * kGradDraws + col], inv_ngal);
+    const double dxi = grad::cross_dxi(y[slot], xi, total[p * kGradDraws + col], inv_ngal);
     if (a.xi == nullptr)
       y[slot] = dxi;
     else if (draw < a.n_draws)
@@ -552,7 +585,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_cross_kernel(const GradArgs
   __syncthreads();
   for (int item = t; item < n_r * kGradDraws; item += kGradThreads) {
     const int r = item / kGradDraws;
-    const double xi = y[item] * inv_ngal;       // (item % 16 == col: 256 is a multiple of 16)
+    const double xi = grad::cross_xi(y[item], inv_ngal);   // (item % 16 == col: 256 = 16 x 16)
     if (a.xi == nullptr)
       y[item] = xi - a.chi2_data[r];
     else if (draw < a.n_draws)

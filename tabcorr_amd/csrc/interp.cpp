@@ -85,12 +85,6 @@ struct tc_interp {
 
 namespace {
 
-bool same_bins(const tc_table* a, const tc_table* b) {
-  return a->n_h == b->n_h && a->log_min == b->log_min && a->log_max == b->log_max &&
-         a->percentile == b->percentile && a->dist_index == b->dist_index &&
-         a->legacy == b->legacy;
-}
-
 // Data vector and precision matrix of a likelihood: uploaded when they differ from the last upload.
 int upload_chi2_data(tc_interp* it, const double* data, const double* precision) {
   const int n_r = it->tables[0]->n_r;

@@ -1097,14 +1097,18 @@ int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* t
 
 // ---- gradients, one launch per batch (grad_kernels.hip.h) -------------------------------------
 
-// What neither derivative family serves: a workgroup beyond the LDS of a CU, a dense operand
-// beyond 2 GiB.  `what`: the leading words of the message.
-static int check_grad_fit(const tc_table* t, const char* what, size_t lds) {
+bool same_bins(const tc_table* a, const tc_table* b) {
+  return a->n_h == b->n_h && a->log_min == b->log_min && a->log_max == b->log_max &&
+         a->percentile == b->percentile && a->dist_index == b->dist_index &&
+         a->legacy == b->legacy;
+}
+
+int check_grad_fit(const tc_table* t, const char* what, size_t lds, int n_r) {
   if (lds > (size_t)kMaxLdsBytes)
     return fail(TC_ERR_UNSUPPORTED,
                 "%s: a table of %d bins and %d correlation function bins needs %zu bytes "
                 "of LDS per workgroup, beyond the %d there are",
-                what, t->n_bins, t->n_r, lds, kMaxLdsBytes);
+                what, t->n_bins, n_r < 0 ? t->n_r : n_r, lds, kMaxLdsBytes);
   if (t->mode == TC_MODE_AUTO &&
       tc::grad_operand_doubles(t->n_bins, t->n_r) * sizeof(double) > ((size_t)1 << 31))
     return fail(TC_ERR_UNSUPPORTED, "%s: the dense matrix of %d bins exceeds 2 GiB", what,
@@ -1124,7 +1128,7 @@ static size_t vjp_lds(const tc_table* t) {
 }
 
 int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
-                    int n_gauss, unsigned flags, bool chi2, int n_params) {
+                    int n_gauss, unsigned flags, bool chi2, int n_params, bool fit) {
   TC_CHECK(t != nullptr, "table handle is NULL");
   const bool decorated = n_params == tc::kGradParamsAssembias;
   const bool leauthaud = n_params == tc::kGradParamsLeauthaud11;
@@ -1154,7 +1158,7 @@ int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n
   TC_CHECK(n_gauss >= 1 && n_gauss <= 4096, "n_gauss_prim must be in [1, 4096]");
   TC_CHECK(n_theta == tc::grad_theta_columns(n_params), "theta must have %d columns, got %d",
            tc::grad_theta_columns(n_params), n_theta);
-  return check_grad_fit(t, "gradients", grad_lds(t, chi2, n_params));
+  return fit ? check_grad_fit(t, "gradients", grad_lds(t, chi2, n_params)) : TC_OK;
 }
 
 int build_grad_table(tc_table* t) {
@@ -1260,6 +1264,23 @@ int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gau
                               : (decorated ? launch_grad_assembias_instance : launch_grad_instance);
     return instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
   });
+}
+
+int run_grad_joint(tc_table* t0, tc::JointArgs ja, int n_params, hipStream_t stream) {
+  Range range("joint gradients (one launch)");
+  Quadrature* q = nullptr;
+  const int status = get_quadrature(t0, ja.grad.n_gauss, &q);
+  if (status != TC_OK) return status;
+  ja.grad.log_m = (const double*)q->log_m;
+  ja.grad.m = (const double*)q->m;
+  ja.grad.weight = (const double*)q->weight;
+  const int lds = (int)tc::joint_lds_bytes(ja.grad.n_bins, ja.grad.n_central, ja.grad.n_r,
+                                           ja.grad.xi == nullptr, n_params);
+  return launch_grad_batch(t0, ja.grad.n_draws, lds,
+                           [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+                             return launch_grad_joint_instance(n_params, t0->device, grid, lds,
+                                                               stream, k0, k1, ja);
+                           });
 }
 
 // ---- occupation VJP, one launch per batch (vjp_kernels.hip.h) ---------------------------------

@@ -1004,24 +1004,6 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
 
 namespace {
 
-// A derivative call on device pointers: run(begin, n, stream) for every slab of the batch, one
-// launch each, on lane 0 (pinned) or on the next lane of the rotation (as
-// tc_predict_zheng07_batch_device).
-extern "C++" template <typename Run>
-int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
-  TC_HIP(hipSetDevice(t->device));
-  int status = TC_OK;
-  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  const bool pinned = request == GradLane::kPinned;
-  t->cur = next_lane(pinned, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls);
-  hipStream_t stream = t->lanes[t->cur].stream;
-  status = for_each_slab(n_draws, max_slab(t),
-                         [&](int64_t begin, int64_t n) { return run(begin, n, stream); });
-  if (status != TC_OK) return status;
-  t->prev = pinned ? -1 : t->cur;
-  return TC_OK;
-}
-
 // (n_params: tc::kGradParams, tc::kGradParamsAssembias for the decorated model, or
 // tc::kGradParamsLeauthaud11, whose draws have tc::grad_theta_columns(n_params) = 14 columns)
 int grad_device(tc_table* t, GradLane request, const double* theta_device, int64_t n_draws,
@@ -1039,43 +1021,22 @@ int grad_device(tc_table* t, GradLane request, const double* theta_device, int64
   });
 }
 
-// Host arrays: the draws go up and the four result arrays come down on lane 0; `wide` = doubles
-// per draw of the two large results (xi and dxi, or chi2 and dchi2).  `fisher` (with chi2_data
-// only, or NULL): one array more comes down, from behind the other two.
+// Host arrays (internal.h: grad_host_arrays): `value` / `dvalue` are xi and dxi, or (chi2_data
+// given) chi2 and dchi2; `fisher` (with chi2_data only, or NULL): one array more comes down.
 int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, unsigned flags,
               const double* chi2_data, double* ngal, double* value, double* dngal,
               double* dvalue, double* fisher = nullptr, int n_params = tc::kGradParams) {
-  TC_HIP(hipSetDevice(t->device));
   const bool chi2 = chi2_data != nullptr;
-  const size_t n = (size_t)n_draws, n_r = (size_t)t->n_r, np = (size_t)n_params;
-  const size_t value_count = chi2 ? n : n * n_r;
-  const size_t theta_bytes = n * (size_t)tc::grad_theta_columns(n_params) * 8;
-  int status = t->theta.reserve(theta_bytes, t->stream);
-  if (status == TC_OK) status = t->out_ngal.reserve(n * (1 + np) * 8, t->stream);
-  const size_t fisher_count = fisher ? n * np * np : 0;
-  if (status == TC_OK)
-    status = t->out_xi.reserve((value_count * (1 + np) + fisher_count) * 8, t->stream);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(t->theta.ptr, theta, theta_bytes, hipMemcpyHostToDevice, t->stream));
-  double* d_ngal = (double*)t->out_ngal.ptr;
-  double* d_dngal = d_ngal + n;
-  double* d_value = (double*)t->out_xi.ptr;
-  double* d_dvalue = d_value + value_count;
-  double* d_fisher = fisher ? d_dvalue + value_count * np : nullptr;
-  status = grad_device(t, GradLane::kPinned, (const double*)t->theta.ptr, n_draws, n_gauss, flags,
-                       d_ngal, chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                       chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr, d_fisher,
-                       n_params);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * np * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * np * 8, hipMemcpyDeviceToHost,
-                        t->stream));
-  if (fisher)
-    TC_HIP(hipMemcpyAsync(fisher, d_fisher, fisher_count * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipStreamSynchronize(t->stream));
-  return TC_OK;
+  return grad_host_arrays(
+      t, theta, tc::grad_theta_columns(n_params), n_draws, n_params,
+      chi2 ? (size_t)1 : (size_t)t->n_r, ngal, value, dngal, dvalue, fisher,
+      [&](const double* d_theta, double* d_ngal, double* d_dngal, double* d_value,
+          double* d_dvalue, double* d_fisher) {
+        return grad_device(t, GradLane::kPinned, d_theta, n_draws, n_gauss, flags, d_ngal,
+                           chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
+                           chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr,
+                           d_fisher, n_params);
+      });
 }
 
 }  // namespace

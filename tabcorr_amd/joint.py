@@ -1,0 +1,293 @@
+"""``JointLikelihood``: tables that share one halo table, fitted together.
+
+The reference's documented likelihood step evaluates two tables per model
+(``docs/guides/overview.rst:86-92``: ``halotab_wp.predict(model)``, then
+``halotab_ds.predict(model)``); the data vector of such an analysis is the
+concatenation (w_p, DeltaSigma), and its covariance couples the probes.  A
+`JointLikelihood` evaluates a batch of draws against all of its tables in ONE
+kernel launch (``tc_joint_*``, ``include/tabcorr_amd.h``): the occupations and
+their derivatives once per draw, every table's contraction, and chi2, its
+gradient and the Fisher matrix against the full ``(N, N)`` precision matrix,
+``N`` the sum of the tables' correlation function bins.
+"""
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .tabcorr import _flags, _grad_keys, _grad_spec, _grad_theta
+
+MAX_TABLES = 16
+# the gal_type columns the device reads (tabcorr.py: _DeviceTable)
+BIN_COLUMNS = ('n_h', 'log_prim_haloprop_min', 'log_prim_haloprop_max',
+               'sec_haloprop_percentile', 'prim_haloprop_dist_index')
+
+
+def _same_bins(a, b):
+    """Whether two gal_type tables describe the same bins."""
+    if len(a) != len(b) or not np.array_equal(a.is_centrals(),
+                                              b.is_centrals()):
+        return False
+    for name in BIN_COLUMNS:
+        if (name in a.colnames) != (name in b.colnames):
+            return False
+        if name in a.colnames and not np.array_equal(a[name], b[name]):
+            return False
+    return True
+
+
+def _zheng07_only(family):
+    if family not in ('zheng07', 'leauthaud11'):
+        raise ValueError("family must be 'zheng07' or 'leauthaud11'.")
+    if family != 'zheng07':
+        raise NotImplementedError(
+            'A joint serves the Zheng07 family only (plain or decorated with '
+            'assembly bias).')
+
+
+class _Locks:
+    """Every table's lock, taken in one fixed order whatever the order of the
+    tables in the joint (`TabCorr.predict_joint` takes them the same way)."""
+
+    def __init__(self, devices):
+        self.locks = [d.lock for d in sorted(devices, key=id)]
+
+    def __enter__(self):
+        for lock in self.locks:
+            lock.acquire()
+
+    def __exit__(self, *exc):
+        for lock in reversed(self.locks):
+            lock.release()
+
+
+class _DeviceJoint:
+    """Owner of a ``tc_joint`` handle; keeps its tables' handles alive.  A
+    joint works through its tables (``include/tabcorr_amd.h``): every call
+    sits behind `lock`, all of their locks."""
+
+    def __init__(self, devices):
+        self.lib = devices[0].lib
+        self.devices = devices
+        handles = (ctypes.c_void_p * len(devices))(
+            *[d.handle.value for d in devices])
+        handle = ctypes.c_void_p()
+        _lib.check(self.lib.tc_joint_create(handles, len(devices),
+                                            ctypes.byref(handle)))
+        self.handle = handle
+        self.lock = _Locks(devices)
+
+    def __del__(self):
+        handle = getattr(self, 'handle', None)
+        if handle is not None and handle.value is not None:
+            try:
+                self.lib.tc_joint_destroy(handle)
+            except Exception:  # interpreter shutdown
+                pass
+            self.handle = None
+
+
+class JointLikelihood:
+    """``JointLikelihood([halotab_wp, halotab_ds])``: 1 to 16 `TabCorr`
+    tables with identical ``gal_type`` tables (mode ``'auto'`` and mode
+    ``'cross'`` may be mixed).  The tables' results are concatenated in list
+    order: table ``k`` owns ``joint.slices[k]`` of the ``joint.n_r_total``
+    entries of ``data`` and of the rows and columns of ``precision``.
+
+    Plain Zheng07 and, with ``assembias=True``, the model decorated with
+    assembly bias (7 columns wherever 5 stand); total correlation functions,
+    float64 tables.
+    """
+
+    def __init__(self, tabcorr_list):
+        self.tabcorr_list = list(tabcorr_list)
+        n_tables = len(self.tabcorr_list)
+        if n_tables < 1 or n_tables > MAX_TABLES:
+            raise ValueError('A joint takes 1 to {} tables, got {}.'.format(
+                MAX_TABLES, n_tables))
+        first = self.tabcorr_list[0]
+        for k, halotab in enumerate(self.tabcorr_list):
+            if any(halotab is other for other in self.tabcorr_list[:k]):
+                raise ValueError(
+                    'Table {} appears twice in the joint.'.format(k))
+            if halotab.compute_dtype != 'float64':
+                raise ValueError('Table {} does not have a float64 compute '
+                                 'dtype.'.format(k))
+            if not _same_bins(halotab.gal_type, first.gal_type):
+                raise ValueError('Table {} does not have the gal_type table '
+                                 'of table 0.'.format(k))
+        sizes = [len(halotab.tpcf_matrix) for halotab in self.tabcorr_list]
+        offsets = np.concatenate([[0], np.cumsum(sizes)])
+        self.slices = [slice(int(offsets[k]), int(offsets[k + 1]))
+                       for k in range(n_tables)]
+        self.n_r_total = int(offsets[-1])
+        self._device = None
+
+    def to_device(self):
+        """Upload the tables and create the joint handle (done lazily by the
+        first call)."""
+        devices = [halotab.to_device() for halotab in self.tabcorr_list]
+        if self._device is None or any(
+                a is not b for a, b in zip(self._device.devices, devices)):
+            self._device = _DeviceJoint(devices)
+        return self._device
+
+    # -- arguments ------------------------------------------------------------
+
+    def _operands(self, data, precision):
+        """``data`` -- a flat ``(N, )`` vector or a list of per-table arrays
+        -- and ``precision`` ``(N, N)``, contiguous, or a ValueError."""
+        n = self.n_r_total
+        if isinstance(data, (list, tuple)) and len(data) == len(self.slices) \
+                and not np.isscalar(data[0]):
+            parts = [np.ravel(np.asarray(part, dtype=np.float64))
+                     for part in data]
+            for k, part in enumerate(parts):
+                size = self.slices[k].stop - self.slices[k].start
+                if part.size != size:
+                    raise ValueError('data of table {} must have {} entries, '
+                                     'got {}.'.format(k, size, part.size))
+            data = np.concatenate(parts)
+        data = _lib.contiguous(data)
+        precision = _lib.contiguous(precision)
+        if data.shape != (n, ) or precision.shape != (n, n):
+            raise ValueError('data must have {0} entries and precision shape '
+                             '({0}, {0}).'.format(n))
+        return data, precision
+
+    def _split(self, array, leading):
+        """The per-table parts of an array whose last axis is the joint one,
+        each reshaped to ``leading + tpcf_shape``."""
+        return [np.ascontiguousarray(array[..., part]).reshape(
+            leading + tuple(halotab.tpcf_shape))
+            for part, halotab in zip(self.slices, self.tabcorr_list)]
+
+    # -- batched calls --------------------------------------------------------
+
+    def predict_batch_grad(self, theta, n_gauss_prim=10,
+                           modulate_with_cenocc=False, assembias=False,
+                           family='zheng07'):
+        """`TabCorr.predict_batch_grad` of every table in one launch.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )`` -- the tables share their bins: one per draw
+        xis : list, per table ``(n_draws, ) + tpcf_shape``
+        dngal : ``(n_draws, 5)``
+        dxis : list, per table ``(n_draws, 5) + tpcf_shape``
+
+        Raises ``NotImplementedError`` for ``family='leauthaud11'`` and for a
+        joint whose rows do not fit the kernel's LDS.
+        """
+        _zheng07_only(family)
+        theta = _grad_theta(theta, assembias)
+        n_draws, n_cols, n = len(theta), theta.shape[1], self.n_r_total
+        ngal, xi = np.empty(n_draws), np.empty((n_draws, n))
+        dngal = np.empty((n_draws, n_cols))
+        dxi = np.empty((n_draws, n_cols, n))
+        device = self.to_device()
+        with device.lock:
+            _lib.check(device.lib.tc_joint_predict_grad_batch(
+                device.handle, _lib.as_double_p(theta), n_cols, n_draws,
+                n_gauss_prim, _flags(False, modulate_with_cenocc, assembias),
+                _lib.as_double_p(ngal), _lib.as_double_p(xi),
+                _lib.as_double_p(dngal), _lib.as_double_p(dxi)))
+        return (ngal, self._split(xi, (n_draws, )), dngal,
+                self._split(dxi, (n_draws, n_cols)))
+
+    def _chi2(self, theta, data, precision, n_gauss_prim,
+              modulate_with_cenocc, assembias, want_fisher, family):
+        _zheng07_only(family)
+        theta = _grad_theta(theta, assembias)
+        data, precision = self._operands(data, precision)
+        n_draws, n_cols = len(theta), theta.shape[1]
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dngal = np.empty((n_draws, n_cols))
+        dchi2 = np.empty((n_draws, n_cols))
+        fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
+        device = self.to_device()
+        with device.lock:
+            _lib.check(device.lib.tc_joint_chi2_grad_batch(
+                device.handle, _lib.as_double_p(theta), n_cols, n_draws,
+                n_gauss_prim, _flags(False, modulate_with_cenocc, assembias),
+                _lib.as_double_p(data), _lib.as_double_p(precision),
+                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
+                _lib.as_double_p(dngal), _lib.as_double_p(dchi2),
+                _lib.as_double_p(fisher) if want_fisher else None))
+        return ngal, chi2, dngal, dchi2, fisher
+
+    def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
+                        modulate_with_cenocc=False, assembias=False,
+                        family='zheng07'):
+        """chi2 of the concatenated data vector and its gradient
+        (`TabCorr.chi2_grad_batch` with ``N`` for ``n_r``): ``ngal, chi2``
+        ``(n_draws, )``, ``dngal, dchi2`` ``(n_draws, 5)``."""
+        return self._chi2(theta, data, precision, n_gauss_prim,
+                          modulate_with_cenocc, assembias, False, family)[:4]
+
+    def chi2_fisher_batch(self, theta, data, precision, n_gauss_prim=10,
+                          modulate_with_cenocc=False, assembias=False,
+                          family='zheng07'):
+        """`chi2_grad_batch` with the Fisher matrix ``fisher[:, k, l] =
+        dxi_k^T P_sym dxi_l`` of the joint data vector, ``(n_draws, 5, 5)``,
+        from the same launch (`TabCorr.chi2_fisher_batch`): the off-diagonal
+        blocks of ``precision`` couple the tables."""
+        return self._chi2(theta, data, precision, n_gauss_prim,
+                          modulate_with_cenocc, assembias, True, family)
+
+    def fisher_batch(self, theta, precision, n_gauss_prim=10,
+                     modulate_with_cenocc=False, assembias=False,
+                     family='zheng07'):
+        """The forecast form, which needs no data: ``ngal, dngal, fisher``."""
+        ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
+            theta, np.zeros(self.n_r_total), precision,
+            n_gauss_prim=n_gauss_prim,
+            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
+            family=family)
+        return ngal, dngal, fisher
+
+    # -- un-batched forms -----------------------------------------------------
+
+    def _model_theta(self, model, check_consistency, assembias, what):
+        if check_consistency:
+            for halotab in self.tabcorr_list:
+                halotab._check_consistency_cached(model)
+        spec = _grad_spec(model, assembias, what)
+        keys = _grad_keys(assembias)
+        theta = np.asarray(spec.theta,
+                           dtype=np.float64)[np.newaxis, :len(keys)]
+        return spec, keys, theta
+
+    def predict_grad(self, model, n_gauss_prim=10, check_consistency=True,
+                     assembias=False):
+        """Un-batched `predict_batch_grad` for a model object, as
+        `TabCorr.predict_grad`: ``ngal`` (float), ``xis`` (list of arrays of
+        each table's ``tpcf_shape``), ``dngal`` (dict by parameter name) and
+        ``dxis`` (dict by parameter name of lists)."""
+        spec, keys, theta = self._model_theta(model, check_consistency,
+                                              assembias, 'predict_grad')
+        ngal, xis, dngal, dxis = self.predict_batch_grad(
+            theta, n_gauss_prim=n_gauss_prim,
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
+        return (float(ngal[0]), [xi[0] for xi in xis],
+                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
+                {key: [dxi[0, k] for dxi in dxis]
+                 for k, key in enumerate(keys)})
+
+    def chi2_fisher(self, model, data, precision, n_gauss_prim=10,
+                    check_consistency=True, assembias=False):
+        """Un-batched `chi2_fisher_batch` for a model object: ``ngal``,
+        ``chi2`` (floats), ``dngal``, ``dchi2`` (dicts by parameter name) and
+        ``fisher`` ``(5, 5)`` in the order of the keys."""
+        spec, keys, theta = self._model_theta(model, check_consistency,
+                                              assembias, 'chi2_fisher')
+        ngal, chi2, dngal, dchi2, fisher = self.chi2_fisher_batch(
+            theta, data, precision, n_gauss_prim=n_gauss_prim,
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
+        return (float(ngal[0]), float(chi2[0]),
+                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
+                {key: float(dchi2[0, k]) for k, key in enumerate(keys)},
+                fisher[0])
