@@ -44,6 +44,15 @@ int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* den
 int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n_r, int n_dim,
                       int chi2, int64_t* bytes);
 
+/* The slab arithmetic of the derivative entry points (tabcorr_amd/csrc/grad_call.h:
+ * GradRequest::slab): the element offsets that the slab beginning at draw `begin` adds to the
+ * arrays of a call of the family n_params (5, 7 or 11) with n_extra interpolator axes and n_r
+ * result rows per draw, in the prediction form or (likelihood != 0) the likelihood form with its
+ * Fisher matrix -- offsets[7]: theta, x, ngal, dngal, xi or chi2, dxi or dchi2, fisher; -1 where
+ * the call has no such array. */
+int tc_debug_grad_slab(int n_params, int n_extra, int n_r, int likelihood, int64_t begin,
+                       int64_t* offsets);
+
 /* The node arithmetic of the Leauthaud11 gradient kernels (tabcorr_amd/csrc/grad_leauthaud11.h)
  * on the host, for one draw theta (14 columns) and n halo masses: log_mstar (n) the root of the
  * stellar-to-halo mass relation, n_cen (n) and dn_cen (n, 11) the centrals' occupation and its

@@ -62,6 +62,7 @@ SIGNATURES = {
                                  c_double_p],
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_grad_lds': [ctypes.c_int] * 7 + [c_int64_p],
+    'tc_debug_grad_slab': [ctypes.c_int] * 4 + [ctypes.c_int64, c_int64_p],
     'tc_debug_leauthaud11_node_grad': [c_double_p, ctypes.c_int, ctypes.c_int64, c_double_p,
                                        c_double_p, c_double_p, c_double_p, c_double_p,
                                        c_double_p],
@@ -123,63 +124,6 @@ SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
         ctypes.c_void_p],
-    'tc_predict_grad_zheng07_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p],
-    'tc_predict_grad_zheng07_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p],
-    'tc_chi2_grad_zheng07_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p],
-    'tc_chi2_grad_zheng07_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-    'tc_chi2_fisher_zheng07_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_chi2_fisher_zheng07_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-    # (decorated with assembly bias: 7 columns; the trailing fisher may be None)
-    'tc_predict_grad_assembias_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p],
-    'tc_predict_grad_assembias_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p],
-    'tc_chi2_grad_assembias_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_chi2_grad_assembias_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-    'tc_predict_grad_leauthaud11_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p],
-    'tc_predict_grad_leauthaud11_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p],
-    'tc_chi2_grad_leauthaud11_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_chi2_grad_leauthaud11_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'tc_predict_zheng07_many': [
         ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int,
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p],
@@ -208,20 +152,6 @@ SIGNATURES = {
     'tc_predict_occupation_batch': [
         ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_uint,
         c_double_p, c_double_p],
-    'tc_predict_occupation_vjp_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_uint,
-        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_predict_occupation_vjp_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p],
-    'tc_chi2_occupation_grad_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int64, ctypes.c_uint,
-        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_chi2_occupation_grad_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint,
-        c_double_p, c_double_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p],
     'tc_interp_create': [c_void_pp, ctypes.c_int, ctypes.c_int, c_double_p,
                          c_void_pp],
     'tc_interp_destroy': [ctypes.c_void_p],
@@ -243,69 +173,11 @@ SIGNATURES = {
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
         ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
         ctypes.c_void_p, ctypes.c_void_p],
-    'tc_interp_predict_grad_zheng07_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        c_double_p, c_double_p],
-    'tc_interp_predict_grad_zheng07_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-    'tc_interp_chi2_grad_zheng07_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_interp_chi2_grad_zheng07_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-    'tc_interp_chi2_fisher_zheng07_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_interp_chi2_fisher_zheng07_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p],
-    'tc_interp_predict_grad_assembias_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        c_double_p, c_double_p],
-    'tc_interp_predict_grad_assembias_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
-    'tc_interp_chi2_grad_assembias_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_interp_chi2_grad_assembias_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p],
-    # joint of tables: the family by flags, the trailing fisher may be None
+    # joint of tables
     'tc_joint_create': [c_void_pp, ctypes.c_int, c_void_pp],
     'tc_joint_destroy': [ctypes.c_void_p],
     'tc_joint_synchronize': [ctypes.c_void_p],
     'tc_joint_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p],
-    'tc_joint_predict_grad_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p],
-    'tc_joint_predict_grad_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p],
-    'tc_joint_chi2_grad_batch': [
-        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
-        c_double_p, c_double_p, c_double_p, c_double_p],
-    'tc_joint_chi2_grad_batch_device': [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
-        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
     'tc_debug_joint_lds_bytes': [ctypes.c_int] * 5 + [c_int64_p],
     'tc_table_set_option': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int],
     'tc_table_timer_begin': [ctypes.c_void_p, ctypes.c_int],
@@ -357,6 +229,49 @@ SIGNATURES = {
     'tc_comm_barrier': [ctypes.c_void_p],
     'tc_comm_synchronize': [ctypes.c_void_p],
 }
+
+# The gradient entries: (handle kind, family, form) -> the host-array symbol; the device-pointer
+# twin is `name + '_device'`.  Forms: 'predict' (ngal, xi, dngal, dxi), 'chi2' (ngal, chi2, dngal,
+# dchi2) and 'fisher' (the same with the Fisher matrix).  Plain Zheng07 has an entry of its own
+# for the Fisher matrix; the other families and the joint (whose family is in the flags) take a
+# trailing `fisher` that may be None.
+GRAD_ENTRIES = {}
+for _kind, _prefix, _families in (('table', 'tc_', ('zheng07', 'assembias', 'leauthaud11')),
+                                  ('interp', 'tc_interp_', ('zheng07', 'assembias')),
+                                  ('joint', 'tc_joint_', (None, ))):
+    for _family in _families:
+        _stem = '' if _family is None else '_' + _family
+        for _form, _entry in (('predict', 'predict_grad'), ('chi2', 'chi2_grad'),
+                              ('fisher', 'chi2_fisher' if _family == 'zheng07' else 'chi2_grad')):
+            for _key in ('zheng07', 'assembias') if _family is None else (_family, ):
+                GRAD_ENTRIES[_kind, _key, _form] = '%s%s%s_batch' % (_prefix, _entry, _stem)
+GRAD_OPTIONAL_FISHER = {GRAD_ENTRIES[_key] for _key in GRAD_ENTRIES if _key[2] == 'chi2' and
+                        GRAD_ENTRIES[_key] == GRAD_ENTRIES[_key[:2] + ('fisher', )]}
+
+
+def _derivative_signatures():
+    """The argument lists of the derivative entries, composed: the handle, the draws (and an
+    interpolator's x), the counts and flags, the likelihood's operands (host pointers in both
+    twins), four outputs and, where the entry has one, the Fisher matrix.  The occupation VJP:
+    the handle, the occupations, n_draws and flags, the cotangents or the operands, three
+    outputs.  A `_device` twin takes device pointers for every array."""
+    out = {}
+    for device in (False, True):
+        array = ctypes.c_void_p if device else c_double_p
+        suffix = '_device' if device else ''
+        for (kind, _, form), name in GRAD_ENTRIES.items():
+            head = [ctypes.c_void_p, array, ctypes.c_int] + [array] * (kind == 'interp')
+            head += [ctypes.c_int64, ctypes.c_int, ctypes.c_uint]
+            operands = [c_double_p, c_double_p] * (form != 'predict')
+            fisher = [array] * (form == 'fisher' or name in GRAD_OPTIONAL_FISHER)
+            out[name + suffix] = head + operands + [array] * 4 + fisher
+        head = [ctypes.c_void_p, array, ctypes.c_int64, ctypes.c_uint]
+        out['tc_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 3
+        out['tc_chi2_occupation_grad_batch' + suffix] = head + [c_double_p] * 2 + [array] * 3
+    return out
+
+
+SIGNATURES.update(_derivative_signatures())
 
 _lib = None
 

@@ -1,0 +1,243 @@
+// A derivative call on its way from a C entry point to its launches (host only): the request that
+// every gradient entry of a table, an interpolator and a joint fills, and -- for the translation
+// units that know the handles (internal.h includes this header behind them) -- the one staging
+// path of the host-array entries and the one entry sequence.  The first part is plain C++ without
+// the HIP runtime: tools/sanitize/host_driver.cpp and tc_debug_grad_slab evaluate it as it stands.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "grad.h"
+
+namespace tc {
+namespace host {
+
+// The lane a derivative call asks for: lane 0, pinned (the host-array entry points stage their
+// copies on it), or the next lane of the handle's rotation (the device-pointer entry points).
+enum class GradLane { kPinned, kNext };
+
+// One gradient call, or one slab of it, on device pointers.  `value` / `dvalue` are xi (n_draws,
+// n_r) and dxi (n_draws, n_cols, n_r) of the prediction form, chi2 (n_draws) and dchi2 (n_draws,
+// n_cols) of the likelihood form: likelihood() says which, and outputs() is the one place that
+// tells the kernels.
+struct GradRequest {
+  int n_params;              // the family: tc::kGradParams, tc::kGradParamsAssembias (7 columns
+                             // wherever 5 stand) or tc::kGradParamsLeauthaud11 (11, of 14 of theta)
+  int n_extra;               // an interpolator's n_dim: columns behind the family's; else 0
+  int n_gauss;
+  unsigned flags;
+  int64_t n_draws;
+  int n_r;                   // rows of a draw's result: a table's n_r, a joint's n_r_total
+  const double* theta;       // (n_draws, theta_columns())
+  const double* x;           // (n_draws, n_extra), or NULL
+  const double* chi2_data;   // on the device: data (n_r), then the precision matrix (n_r, n_r);
+                             // NULL: the prediction form
+  double* ngal;              // (n_draws)
+  double* dngal;             // (n_draws, n_cols())
+  double* value;
+  double* dvalue;
+  double* fisher;            // (n_draws, n_cols(), n_cols()), likelihood form only; NULL: not asked for
+
+  bool likelihood() const { return chi2_data != nullptr; }
+  int n_cols() const { return n_params + n_extra; }
+  int theta_columns() const { return tc::grad_theta_columns(n_params); }
+  // doubles per draw of `value`, and per draw and column of `dvalue`
+  int64_t wide() const { return likelihood() ? 1 : n_r; }
+
+  // The draws [begin, begin + n) of the call: every offset a 64-bit product.
+  GradRequest slab(int64_t begin, int64_t n) const {
+    const int64_t cols = n_cols();
+    GradRequest out = *this;
+    out.n_draws = n;
+    out.theta = theta + begin * theta_columns();
+    out.x = x ? x + begin * n_extra : nullptr;
+    out.ngal = ngal + begin;
+    out.dngal = dngal + begin * cols;
+    out.value = value + begin * wide();
+    out.dvalue = dvalue + begin * cols * wide();
+    out.fisher = fisher ? fisher + begin * cols * cols : nullptr;
+    return out;
+  }
+
+  // The result arrays and the likelihood's operands of the argument block.
+  void outputs(tc::GradArgs* ga) const {
+    ga->ngal = ngal;
+    ga->dngal = dngal;
+    ga->xi = likelihood() ? nullptr : value;
+    ga->dxi = likelihood() ? nullptr : dvalue;
+    ga->chi2_data = chi2_data;
+    ga->chi2 = likelihood() ? value : nullptr;
+    ga->dchi2 = likelihood() ? dvalue : nullptr;
+    ga->fisher = fisher;
+  }
+};
+
+// The element offsets that slab `begin` adds to the seven arrays of a request of this shape --
+// theta, x, ngal, dngal, value, dvalue, fisher; -1: the request has no such array -- read off
+// slab() itself (tc_debug_grad_slab; tools/sanitize/host_driver.cpp).
+inline void grad_slab_offsets(int n_params, int n_extra, int n_r, bool likelihood, int64_t begin,
+                              int64_t offsets[7]) {
+  static double anchor[1];
+  GradRequest whole{};
+  whole.n_params = n_params;
+  whole.n_extra = n_extra;
+  whole.n_r = n_r;
+  whole.n_draws = begin + 1;
+  whole.theta = anchor;
+  whole.x = n_extra > 0 ? anchor : nullptr;
+  whole.chi2_data = likelihood ? anchor : nullptr;
+  whole.ngal = whole.dngal = whole.value = whole.dvalue = anchor;
+  whole.fisher = likelihood ? anchor : nullptr;
+  const GradRequest slab = whole.slab(begin, 1);
+  offsets[0] = slab.theta - whole.theta;
+  offsets[1] = whole.x ? slab.x - whole.x : -1;
+  offsets[2] = slab.ngal - whole.ngal;
+  offsets[3] = slab.dngal - whole.dngal;
+  offsets[4] = slab.value - whole.value;
+  offsets[5] = slab.dvalue - whole.dvalue;
+  offsets[6] = whole.fisher ? slab.fisher - whole.fisher : -1;
+}
+
+}  // namespace host
+}  // namespace tc
+
+#ifdef TC_INTERNAL_HANDLES   // (internal.h: the handles and the HIP runtime are known)
+
+namespace tc {
+namespace host {
+
+// Where the arrays of an entry point live: device pointers (the *_device symbols, which take
+// the next lane and return once the work is queued) or host arrays (staged through the handle's
+// buffers on lane 0, complete when the call returns).
+enum class GradRoute { kDevice, kHost };
+
+// The likelihood's operands as an entry point receives them, on the host.
+struct Chi2Host {
+  const double* data;
+  const double* precision;
+};
+
+// What check_grad_args refuses (TC_ERR_UNSUPPORTED with a message) or finds wrong about a request
+// of `t`'s: flags, dtype, the shape of theta (`n_theta` columns as the caller states them), the
+// workgroup's LDS for the prediction or the `likelihood` form.  fit = false: everything but the
+// table's own fit (check_grad_fit), which a joint of tables decides for all of them together.
+int check_grad_args(const tc_table* t, const GradRequest& request, int n_theta, bool likelihood,
+                    bool fit);
+// One launch of the family's kernel for a request of at most max_slab(t) draws on `stream`.
+int run_grad(tc_table* t, const GradRequest& request, hipStream_t stream);
+// The joint gradient kernel (joint_kernels.hip.h) for such a request on `stream`, timed and
+// reported through the first table: `ja` complete but for what the request holds and
+// grad.log_m / m / weight (the first table's quadrature of ja.grad.n_gauss nodes).
+int run_grad_joint(tc_table* t0, tc::JointArgs ja, const GradRequest& request, hipStream_t stream);
+
+// A derivative call on device pointers: run(begin, n, stream) for every slab of the batch, one
+// launch each, on lane 0 (pinned) or on the next lane of the rotation (as
+// tc_predict_zheng07_batch_device).
+template <typename Run>
+int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
+  TC_HIP(hipSetDevice(t->device));
+  int status = TC_OK;
+  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  const bool pinned = request == GradLane::kPinned;
+  t->cur = next_lane(pinned, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls);
+  hipStream_t stream = t->lanes[t->cur].stream;
+  status = for_each_slab(n_draws, max_slab(t),
+                         [&](int64_t begin, int64_t n) { return run(begin, n, stream); });
+  if (status != TC_OK) return status;
+  t->prev = pinned ? -1 : t->cur;
+  return TC_OK;
+}
+
+// The buffers of a handle that a host-array call is staged through, and the stream of its copies.
+struct GradStaging {
+  DeviceBuffer* theta;
+  DeviceBuffer* x;           // NULL: the handle's calls have no extra parameters
+  DeviceBuffer* out_ngal;    // ngal, then dngal
+  DeviceBuffer* out_xi;      // value, then dvalue, then the Fisher matrix
+  hipStream_t stream;
+};
+
+// A request on host arrays: the draws go up, device(staged request) enqueues the launches on the
+// staging buffers, and the results come down -- ngal, dngal, value, dvalue and, where asked for,
+// the Fisher matrix.
+template <typename Device>
+int grad_host_arrays(const GradStaging& stage, const GradRequest& request, Device device) {
+  const size_t n = (size_t)request.n_draws, cols = (size_t)request.n_cols();
+  const size_t value_count = n * (size_t)request.wide();
+  const size_t theta_bytes = n * (size_t)request.theta_columns() * 8;
+  const size_t x_bytes = n * (size_t)request.n_extra * 8;
+  const size_t fisher_count = request.fisher ? n * cols * cols : 0;
+  int status = stage.theta->reserve(theta_bytes, stage.stream);
+  if (status == TC_OK && stage.x) status = stage.x->reserve(x_bytes, stage.stream);
+  if (status == TC_OK) status = stage.out_ngal->reserve(n * (1 + cols) * 8, stage.stream);
+  if (status == TC_OK)
+    status = stage.out_xi->reserve((value_count * (1 + cols) + fisher_count) * 8, stage.stream);
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(stage.theta->ptr, request.theta, theta_bytes, hipMemcpyHostToDevice,
+                        stage.stream));
+  if (stage.x)
+    TC_HIP(hipMemcpyAsync(stage.x->ptr, request.x, x_bytes, hipMemcpyHostToDevice, stage.stream));
+  GradRequest staged = request;
+  staged.theta = (const double*)stage.theta->ptr;
+  staged.x = stage.x ? (const double*)stage.x->ptr : nullptr;
+  staged.ngal = (double*)stage.out_ngal->ptr;
+  staged.dngal = staged.ngal + n;
+  staged.value = (double*)stage.out_xi->ptr;
+  staged.dvalue = staged.value + value_count;
+  staged.fisher = request.fisher ? staged.dvalue + value_count * cols : nullptr;
+  status = device(staged);
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(request.ngal, staged.ngal, n * 8, hipMemcpyDeviceToHost, stage.stream));
+  TC_HIP(hipMemcpyAsync(request.dngal, staged.dngal, n * cols * 8, hipMemcpyDeviceToHost,
+                        stage.stream));
+  TC_HIP(hipMemcpyAsync(request.value, staged.value, value_count * 8, hipMemcpyDeviceToHost,
+                        stage.stream));
+  TC_HIP(hipMemcpyAsync(request.dvalue, staged.dvalue, value_count * cols * 8,
+                        hipMemcpyDeviceToHost, stage.stream));
+  if (request.fisher)
+    TC_HIP(hipMemcpyAsync(request.fisher, staged.fisher, fisher_count * 8, hipMemcpyDeviceToHost,
+                          stage.stream));
+  TC_HIP(hipStreamSynchronize(stage.stream));
+  return TC_OK;
+}
+
+// Every gradient entry point of the C ABI: the request as the caller stated it (chi2_data not
+// yet known) and, for the likelihood form, its operands on the host; fisher_required: the entry
+// has a Fisher matrix among its outputs, which then must not be NULL.  A handle kind supplies
+//   check(request, n_theta, likelihood)   what it refuses, the NULL handle first
+//   null_message(likelihood)              the words of its NULL-pointer refusal
+//   device_id(), operands(), drain()      its device; its operand cache and the wait for everything
+//                                         that may still read the cache's old values
+//   staging()                             the buffers and the stream of its host-array calls
+//   device(lane, request)                 the launches of a request on device pointers
+template <typename Adapter>
+int grad_entry(Adapter adapter, GradRoute where, GradRequest request, int n_theta,
+               const Chi2Host* operands, bool fisher_required) {
+  const bool likelihood = operands != nullptr;
+  int status = adapter.check(request, n_theta, likelihood);
+  if (status != TC_OK) return status;
+  if (request.n_draws == 0) return TC_OK;
+  const bool complete =
+      request.ngal && request.value && request.dngal && request.dvalue &&
+      (request.n_extra == 0 || request.x) &&
+      (!likelihood ||
+       (operands->data && operands->precision && (!fisher_required || request.fisher)));
+  TC_CHECK(complete, "%s", adapter.null_message(likelihood));
+  TC_HIP(hipSetDevice(adapter.device_id()));
+  if (likelihood) {
+    status = adapter.operands().upload(request.n_r, operands->data, operands->precision,
+                                       adapter.staging().stream, [&] { return adapter.drain(); });
+    if (status != TC_OK) return status;
+    request.chi2_data = adapter.operands().device();
+  }
+  if (where == GradRoute::kDevice) return adapter.device(GradLane::kNext, request);
+  return grad_host_arrays(adapter.staging(), request, [&](const GradRequest& staged) {
+    return adapter.device(GradLane::kPinned, staged);
+  });
+}
+
+}  // namespace host
+}  // namespace tc
+
+#endif  // TC_INTERNAL_HANDLES

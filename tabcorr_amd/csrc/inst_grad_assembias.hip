@@ -7,17 +7,21 @@
 namespace tc {
 namespace host {
 
-int launch_grad_assembias_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
-                                   hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga) {
+template <>
+int launch_grad_family<tc::kGradParamsAssembias, tc::GradArgs>(int mode, int device, dim3 grid,
+                                                               int lds, hipStream_t stream,
+                                                               hipEvent_t k0, hipEvent_t k1,
+                                                               const tc::GradArgs& ga) {
   return launch_grad_kernel(mode == TC_MODE_AUTO
                                 ? tc::grad_auto_kernel<tc::kGradParamsAssembias>
                                 : tc::grad_cross_kernel<tc::kGradParamsAssembias>,
                             device, grid, lds, stream, k0, k1, ga);
 }
 
-int launch_grad_interp_assembias_instance(int mode, int device, dim3 grid, int lds,
-                                          hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
-                                          const tc::GradInterpArgs& ga) {
+template <>
+int launch_grad_family<tc::kGradParamsAssembias, tc::GradInterpArgs>(
+    int mode, int device, dim3 grid, int lds, hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
+    const tc::GradInterpArgs& ga) {
   return launch_grad_kernel(mode == TC_MODE_AUTO
                                 ? tc::grad_interp_auto_kernel<tc::kGradParamsAssembias>
                                 : tc::grad_interp_cross_kernel<tc::kGradParamsAssembias>,

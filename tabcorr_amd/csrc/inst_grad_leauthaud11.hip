@@ -8,8 +8,11 @@
 namespace tc {
 namespace host {
 
-int launch_grad_leauthaud11_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
-                                     hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga) {
+template <>
+int launch_grad_family<tc::kGradParamsLeauthaud11, tc::GradArgs>(int mode, int device, dim3 grid,
+                                                                 int lds, hipStream_t stream,
+                                                                 hipEvent_t k0, hipEvent_t k1,
+                                                                 const tc::GradArgs& ga) {
   return launch_grad_kernel(mode == TC_MODE_AUTO
                                 ? tc::grad_auto_kernel<tc::kGradParamsLeauthaud11>
                                 : tc::grad_cross_kernel<tc::kGradParamsLeauthaud11>,

@@ -88,6 +88,31 @@ struct DeviceBuffer {
   }
 };
 
+// The data vector and the precision matrix of a likelihood on the device.  They do not change
+// between calls: they go up when they differ from the host copy of the last upload, after
+// drain() has waited for the kernels of earlier calls, which may still be reading the old values.
+struct Chi2Operands {
+  DeviceBuffer buffer;          // data (n), then the precision matrix (n, n)
+  std::vector<double> host;     // host copy of what `buffer` holds
+  const double* device() const { return (const double*)buffer.ptr; }
+  template <typename Drain>
+  int upload(int n, const double* data, const double* precision, hipStream_t stream,
+             Drain drain) {
+    const size_t rows = (size_t)n, count = (rows + 1) * rows;
+    int status = buffer.reserve(count * 8, stream);
+    if (status != TC_OK) return status;
+    if (host.size() == count && memcmp(host.data(), data, rows * 8) == 0 &&
+        memcmp(host.data() + rows, precision, rows * rows * 8) == 0)
+      return TC_OK;
+    if ((status = drain()) != TC_OK) return status;
+    host.assign(data, data + rows);
+    host.insert(host.end(), precision, precision + rows * rows);
+    TC_HIP(hipMemcpyAsync(buffer.ptr, host.data(), count * 8, hipMemcpyHostToDevice, stream));
+    TC_HIP(hipStreamSynchronize(stream));
+    return TC_OK;
+  }
+};
+
 // Page-locked host staging for small transfers: hipMemcpyAsync from / to pageable
 // memory goes through an internal bounce buffer and costs tens of microseconds per
 // call, which dominates the latency of un-batched predict() calls.
@@ -529,8 +554,7 @@ struct tc_table {
   int64_t next_ticket = 0;
   uint64_t device_calls = 0;         // calls that took a lane of the rotation (next_lane)
   tc::host::DeviceBuffer theta, out_ngal, out_xi, occupation, trace, wave_trace;
-  tc::host::DeviceBuffer chi2_data;          // data vector + precision matrix of chi2 calls
-  std::vector<double> chi2_host;             // host copy of what chi2_data holds
+  tc::host::Chi2Operands chi2;               // data vector + precision matrix of chi2 calls
   size_t wave_trace_count = 0;
   tc::host::PinnedBuffer h_in, h_out;
   tc::host::SingleWorkspace single_ws;       // un-batched path
@@ -713,17 +737,6 @@ bool batch_invariant_form(tc_table* t, int n_gauss, unsigned flags);
 int series_mask(const tc_table* t);
 int check_predict_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
                        int n_gauss, unsigned flags);
-// Gradients (grad_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels do
-// not serve (TC_ERR_UNSUPPORTED with a message), the handle's copy of the matrix, the launch.
-// xi / dxi NULL: chi2 / dchi2 from chi2_data (data, then the precision matrix, on the device) and,
-// where `fisher` is given, the Fisher matrix (n_draws, 5, 5) of the likelihood.  n_params:
-// tc::kGradParams, tc::kGradParamsAssembias for the decorated model (7 wherever 5 stands), or
-// tc::kGradParamsLeauthaud11 for that family (11, of the 14 theta columns).
-// fit = false: everything but the table's own fit (check_grad_fit), which a joint of tables
-// decides for all of them together.
-int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
-                    int n_gauss, unsigned flags, bool chi2, int n_params = tc::kGradParams,
-                    bool fit = true);
 // What no derivative kernel serves: a workgroup of `lds` bytes beyond the LDS of a CU, a dense
 // operand beyond 2 GiB.  `what`: the leading words of the message; n_r: the result rows the
 // workgroup keeps (the table's own by default, the N of a joint).
@@ -732,9 +745,6 @@ int build_grad_table(tc_table* t);
 // Whether two tables have the same bins (gal_type columns in library order): they share their
 // occupations -- the classes of an interpolator, the tables of a joint.
 bool same_bins(const tc_table* a, const tc_table* b);
-// The lane a derivative call asks for: lane 0, pinned (the host-array entry points stage their
-// copies on it), or the next lane of the handle's rotation (the device-pointer entry points).
-enum class GradLane { kPinned, kNext };
 // The table-shape fields of the argument block: n_bins, n_central, n_gauss, n_r, modulate,
 // math_table, row_tiles and k_steps.
 void fill_grad_shape(const tc_table* t, int n_gauss, unsigned flags, tc::GradArgs* ga);
@@ -742,14 +752,6 @@ void fill_grad_shape(const tc_table* t, int n_gauss, unsigned flags, tc::GradArg
 // workgroup, the table's timing events, `launch`, then what the handle reports of its last launch.
 int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
                       const std::function<int(dim3, hipEvent_t, hipEvent_t)>& launch);
-int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
-             unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-             const double* chi2_data, double* chi2, double* dchi2, double* fisher,
-             hipStream_t stream, int n_params = tc::kGradParams);
-// The joint gradient kernel (joint_kernels.hip.h) for one slab of draws on `stream`, timed and
-// reported through the first table: `ja` complete but for grad.log_m / m / weight (the first
-// table's quadrature of ja.grad.n_gauss nodes).
-int run_grad_joint(tc_table* t0, tc::JointArgs ja, int n_params, hipStream_t stream);
 // Occupation VJP (vjp_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels
 // do not serve (TC_ERR_UNSUPPORTED with a message), then the launch against the gradient table.
 // g_xi NULL: the likelihood form -- chi2 and dchi2 / docc from chi2_data (on the device).
@@ -820,60 +822,6 @@ int resident_stop(tc_table* t);
 bool resident_eligible(const tc_table* t, int n_gauss);
 // Is a single-draw resident kernel of ANOTHER handle running on this handle's device?
 bool other_resident_running(const tc_table* t);
-// A derivative call on device pointers: run(begin, n, stream) for every slab of the batch, one
-// launch each, on lane 0 (pinned) or on the next lane of the rotation (as
-// tc_predict_zheng07_batch_device).
-template <typename Run>
-int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
-  TC_HIP(hipSetDevice(t->device));
-  int status = TC_OK;
-  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  const bool pinned = request == GradLane::kPinned;
-  t->cur = next_lane(pinned, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls);
-  hipStream_t stream = t->lanes[t->cur].stream;
-  status = for_each_slab(n_draws, max_slab(t),
-                         [&](int64_t begin, int64_t n) { return run(begin, n, stream); });
-  if (status != TC_OK) return status;
-  t->prev = pinned ? -1 : t->cur;
-  return TC_OK;
-}
-// A derivative call on host arrays through the staging buffers of `t`, on lane 0: the draws
-// (`theta_columns` each) go up, device(theta, ngal, dngal, value, dvalue, fisher) enqueues the
-// launches on device pointers, and the results come down -- ngal (n), dngal (n, np), value and
-// dvalue with `wide` doubles per draw and column (n_r for xi and dxi, 1 for chi2 and dchi2) and,
-// where `fisher` is given, (n, np, np) from behind the other two.
-template <typename Device>
-int grad_host_arrays(tc_table* t, const double* theta, int theta_columns, int64_t n_draws,
-                     int n_params, size_t wide, double* ngal, double* value, double* dngal,
-                     double* dvalue, double* fisher, Device device) {
-  TC_HIP(hipSetDevice(t->device));
-  const size_t n = (size_t)n_draws, np = (size_t)n_params;
-  const size_t value_count = n * wide;
-  const size_t theta_bytes = n * (size_t)theta_columns * 8;
-  int status = t->theta.reserve(theta_bytes, t->stream);
-  if (status == TC_OK) status = t->out_ngal.reserve(n * (1 + np) * 8, t->stream);
-  const size_t fisher_count = fisher ? n * np * np : 0;
-  if (status == TC_OK)
-    status = t->out_xi.reserve((value_count * (1 + np) + fisher_count) * 8, t->stream);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(t->theta.ptr, theta, theta_bytes, hipMemcpyHostToDevice, t->stream));
-  double* d_ngal = (double*)t->out_ngal.ptr;
-  double* d_dngal = d_ngal + n;
-  double* d_value = (double*)t->out_xi.ptr;
-  double* d_dvalue = d_value + value_count;
-  double* d_fisher = fisher ? d_dvalue + value_count * np : nullptr;
-  status = device((const double*)t->theta.ptr, d_ngal, d_dngal, d_value, d_dvalue, d_fisher);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * np * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * np * 8, hipMemcpyDeviceToHost,
-                        t->stream));
-  if (fisher)
-    TC_HIP(hipMemcpyAsync(fisher, d_fisher, fisher_count * 8, hipMemcpyDeviceToHost, t->stream));
-  TC_HIP(hipStreamSynchronize(t->stream));
-  return TC_OK;
-}
 // 2 .. kEnsembleMaxWalkers draws through the resident ensemble kernel, host to host.
 bool ensemble_eligible(const tc_table* t, int64_t n_walkers, int n_gauss, unsigned flags);
 int ensemble_predict(tc_table* t, const double* theta, int n_theta, int n_walkers, int n_gauss,
@@ -915,17 +863,17 @@ int launch_fused_instance(const FusedInstance& instance, int device, int n_u, di
 int launch_cross_instance(bool assembias, bool modulate, bool defer, int device, int rows,
                           dim3 grid, dim3 block, int lds, hipStream_t stream, hipEvent_t k0,
                           hipEvent_t k1, const tc::CrossFusedArgs& ca);
-int launch_grad_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
-                         hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
-int launch_grad_interp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
-                                hipEvent_t k0, hipEvent_t k1, const tc::GradInterpArgs& ga);
-int launch_grad_assembias_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
-                                   hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
-int launch_grad_leauthaud11_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
-                                     hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
-int launch_grad_interp_assembias_instance(int mode, int device, dim3 grid, int lds,
-                                          hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
-                                          const tc::GradInterpArgs& ga);
+// The derivative kernels of the family `n_params` (inst_grad.hip, inst_grad_assembias.hip,
+// inst_grad_leauthaud11.hip), of a table and of an interpolator; a family without kernels is an
+// error.  launch_grad_family<NP>: the family's own launcher, defined in its translation unit.
+template <int NP, typename Args>
+int launch_grad_family(int mode, int device, dim3 grid, int lds, hipStream_t stream, hipEvent_t k0,
+                       hipEvent_t k1, const Args& ga);
+int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
+                         hipStream_t stream, hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga);
+int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
+                         hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
+                         const tc::GradInterpArgs& ga);
 int launch_grad_joint_instance(int n_params, int device, dim3 grid, int lds, hipStream_t stream,
                                hipEvent_t k0, hipEvent_t k1, const tc::JointArgs& ja);
 int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
@@ -943,3 +891,7 @@ int copy_out(PinnedBuffer* stage, double* ngal, size_t ngal_count, const void* d
 
 }  // namespace host
 }  // namespace tc
+
+// (behind the handles: the request of a derivative call, its staging path and its entry sequence)
+#define TC_INTERNAL_HANDLES 1
+#include "grad_call.h"

@@ -72,8 +72,7 @@ struct tc_interp {
   uint64_t device_calls = 0;
   hipStream_t stream = nullptr;               // = lanes[0].stream
   DeviceBuffer theta, x, out_ngal, out_xi;  // host-buffer calls
-  DeviceBuffer chi2_data;                   // fused likelihood: data + precision
-  std::vector<double> chi2_host;            // host copy of what chi2_data holds
+  Chi2Operands chi2;                        // likelihood: data + precision
   PinnedBuffer h_in, h_out;
   SingleWorkspace single_ws;                // un-batched calls
   std::map<std::pair<int, int>, std::unique_ptr<DeviceChunking>> chunkings;
@@ -85,25 +84,11 @@ struct tc_interp {
 
 namespace {
 
-// Data vector and precision matrix of a likelihood: uploaded when they differ from the last upload.
-int upload_chi2_data(tc_interp* it, const double* data, const double* precision) {
-  const int n_r = it->tables[0]->n_r;
-  const size_t data_count = (size_t)(n_r + 1) * n_r;
-  int status = it->chi2_data.reserve(data_count * 8, it->stream);
-  if (status != TC_OK) return status;
-  if (it->chi2_host.size() != data_count ||
-      memcmp(it->chi2_host.data(), data, (size_t)n_r * 8) != 0 ||
-      memcmp(it->chi2_host.data() + n_r, precision, (size_t)n_r * n_r * 8) != 0) {
-    // (earlier kernels of any lane may still read the old ones)
-    status = tc_interp_synchronize(it);
-    if (status != TC_OK) return status;
-    it->chi2_host.assign(data, data + n_r);
-    it->chi2_host.insert(it->chi2_host.end(), precision, precision + (size_t)n_r * n_r);
-    TC_HIP(hipMemcpyAsync(it->chi2_data.ptr, it->chi2_host.data(), data_count * 8,
-                          hipMemcpyHostToDevice, it->stream));
-    TC_HIP(hipStreamSynchronize(it->stream));
-  }
-  return TC_OK;
+// Data vector and precision matrix of a likelihood on the device (internal.h: Chi2Operands):
+// before new values go up, everything queued on the interpolator is waited for.
+int upload_operands(tc_interp* it, const double* data, const double* precision) {
+  return it->chi2.upload(it->tables[0]->n_r, data, precision, it->stream,
+                         [it] { return tc_interp_synchronize(it); });
 }
 
 // One slab of an interpolated prediction as `call` describes it (internal.h: its lane is one of
@@ -407,11 +392,11 @@ int interp_chi2_device(tc_interp* it, Call call, const double* theta_device, int
   tc_table* t0 = it->tables[0];
   const int n_r = t0->n_r;
   tc_interp::Lane& L = it->lanes[call.lane];
-  int status = upload_chi2_data(it, data, precision);
+  int status = upload_operands(it, data, precision);
   if (status != TC_OK) return status;
   status = L.chi2_xi.reserve((size_t)n_draws * n_r * 8, L.stream);
   if (status != TC_OK) return status;
-  call.chi2_data = (const double*)it->chi2_data.ptr;
+  call.chi2_data = it->chi2.device();
   call.chi2_out = n_draws <= max_slab(t0) ? chi2_device : nullptr;   // (one slab)
   bool written = false;
   status = interp_predict_device(it, call, theta_device, n_theta, x_device, n_draws, n_gauss,
@@ -599,7 +584,7 @@ int tc_interp_destroy(tc_interp* it) {
       b->release();
     if (lane.finished) (void)hipEventDestroy(lane.finished);
   }
-  for (DeviceBuffer* b : {&it->theta, &it->x, &it->out_ngal, &it->out_xi, &it->chi2_data})
+  for (DeviceBuffer* b : {&it->theta, &it->x, &it->out_ngal, &it->out_xi, &it->chi2.buffer})
     b->release();
   it->cross_fused.release();
   it->cross_fused_wide.release();
@@ -1060,25 +1045,6 @@ size_t interp_grad_lds(const tc_interp* it, bool chi2, int n_params) {
              : tc::grad_interp_cross_lds_bytes(t0->n_r, it->n_dim, chi2, n_params);
 }
 
-// What the table entry points refuse (check_grad_args on the first table: flags, float32, the
-// shape of theta) and a grid that does not fit the LDS of a workgroup.
-int check_interp_grad_args(const tc_interp* it, const void* theta, int n_theta, int64_t n_draws,
-                           int n_gauss, unsigned flags, bool chi2,
-                           int n_params = tc::kGradParams) {
-  TC_CHECK(it != nullptr, "interp handle is NULL");
-  const tc_table* t0 = it->tables[0];
-  const int status =
-      check_grad_args(t0, theta, n_theta, n_draws, n_gauss, flags, chi2, n_params);
-  if (status != TC_OK) return status;
-  const size_t lds = interp_grad_lds(it, chi2, n_params);
-  if (lds > (size_t)kMaxLdsBytes)
-    return fail(TC_ERR_UNSUPPORTED,
-                "gradients: a grid of %d dimensions over tables of %d bins and %d correlation "
-                "function bins needs %zu bytes of LDS per workgroup, beyond the %d there are",
-                it->n_dim, t0->n_bins, t0->n_r, lds, kMaxLdsBytes);
-  return TC_OK;
-}
-
 int build_grad_walk(tc_interp* it) {
   if (it->grad_walk.built) return TC_OK;
   const int n_classes = (int)it->class_table.size();
@@ -1112,187 +1078,135 @@ int build_grad_walk(tc_interp* it) {
   return TC_OK;
 }
 
-// One launch per slab of draws on the call's lane.  xi / dxi NULL: chi2 / dchi2 from chi2_data
-// and, where `fisher` is given, the Fisher matrix (n_draws, 5 + n_dim, 5 + n_dim).  n_params:
-// tc::kGradParams, or tc::kGradParamsAssembias for the decorated model (7 wherever 5 stands).
-int interp_grad_device(tc_interp* it, GradLane request, const double* theta_device,
-                       const double* x_device, int64_t n_draws, int n_gauss, unsigned flags,
-                       double* ngal, double* xi, double* dngal, double* dxi,
-                       const double* chi2_data, double* chi2, double* dchi2, double* fisher,
-                       int n_params = tc::kGradParams) {
-  TC_HIP(hipSetDevice(it->device));
-  tc_table* t0 = it->tables[0];
-  int status = TC_OK;
-  for (tc_table* t : it->tables)
-    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  const tc_interp::SinglePointers* pointers = nullptr;
-  status = class_pointers(it, n_gauss, &pointers);
-  if (status == TC_OK) status = build_grad_walk(it);
-  if (status != TC_OK) return status;
-  it->cur = next_lane(request == GradLane::kPinned, t0->tuning.pipeline != 0, it->n_lanes,
-                      &it->device_calls);
-  tc_interp::Lane& L = it->lanes[it->cur];
-  const bool with_chi2 = xi == nullptr;
-  const bool decorated = n_params == tc::kGradParamsAssembias;
-  const int n_r = t0->n_r, n_dim = it->n_dim, n_cols = n_params + n_dim;
-  tc::GradInterpArgs ga{};
-  fill_grad_shape(t0, n_gauss, flags, &ga.table);
-  ga.table.chi2_data = chi2_data;
-  ga.n_dim = n_dim;
-  ga.n_classes = (int)it->class_table.size();
-  for (int d = 0; d < n_dim; ++d) {
-    ga.n_axis[d] = (int)it->xp[d].size();
-    ga.axis_offset[d] = it->axis_offset[d];
-    ga.a_offset[d] = it->a_offset[d];
+// An interpolator as grad_entry sees it.
+struct InterpGrad {
+  tc_interp* it;
+  // What the table entry points refuse (check_grad_args on the first table: flags, float32, the
+  // shape of theta) and a grid that does not fit the LDS of a workgroup.
+  int check(const GradRequest& request, int n_theta, bool likelihood) const {
+    TC_CHECK(it != nullptr, "interp handle is NULL");
+    const tc_table* t0 = it->tables[0];
+    const int status = check_grad_args(t0, request, n_theta, likelihood, /*fit=*/true);
+    if (status != TC_OK) return status;
+    const size_t lds = interp_grad_lds(it, likelihood, request.n_params);
+    if (lds > (size_t)kMaxLdsBytes)
+      return fail(TC_ERR_UNSUPPORTED,
+                  "gradients: a grid of %d dimensions over tables of %d bins and %d correlation "
+                  "function bins needs %zu bytes of LDS per workgroup, beyond the %d there are",
+                  it->n_dim, t0->n_bins, t0->n_r, lds, kMaxLdsBytes);
+    return TC_OK;
   }
-  ga.xp = (const double*)it->d_xp;
-  ga.a = (const double*)it->d_a;
-  ga.class_begin = (const int32_t*)it->grad_walk.class_begin;
-  ga.walk_node = (const int32_t*)it->grad_walk.node;
-  ga.matrices = (const double* const*)it->grad_walk.matrices;
-  ga.class_log_m = (const double* const*)pointers->log_m;
-  ga.class_m = (const double* const*)pointers->m;
-  ga.class_weight = (const double* const*)pointers->weight;
-  ga.class_n_h = (const double* const*)pointers->n_h;
-  ga.class_percentile = decorated ? (const double* const*)pointers->percentile : nullptr;
-  const int lds = (int)interp_grad_lds(it, with_chi2, n_params);
-  return for_each_slab(n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
-    Range range("interpolator gradients (one launch)");
-    ga.table.theta = theta_device + begin * n_params;
-    ga.x = x_device + begin * n_dim;
-    ga.table.n_draws = n;
-    ga.table.ngal = ngal + begin;
-    ga.table.dngal = dngal + begin * n_cols;
-    ga.table.xi = xi ? xi + begin * n_r : nullptr;
-    ga.table.dxi = dxi ? dxi + begin * n_cols * n_r : nullptr;
-    ga.table.chi2 = chi2 ? chi2 + begin : nullptr;
-    ga.table.dchi2 = dchi2 ? dchi2 + begin * n_cols : nullptr;
-    ga.table.fisher = fisher ? fisher + begin * n_cols * n_cols : nullptr;
-    // (timed through the first table's timer)
-    return launch_grad_batch(t0, n, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-      return (decorated ? launch_grad_interp_assembias_instance : launch_grad_interp_instance)(
-          t0->mode, it->device, grid, lds, L.stream, k0, k1, ga);
+  const char* null_message(bool) const { return "NULL pointer"; }
+  int device_id() const { return it->device; }
+  Chi2Operands& operands() const { return it->chi2; }
+  // (earlier kernels of any lane may still read the old operands)
+  int drain() const { return tc_interp_synchronize(it); }
+  GradStaging staging() const {
+    return {&it->theta, &it->x, &it->out_ngal, &it->out_xi, it->stream};
+  }
+  // One launch per slab of draws on a lane of the interpolator's own (it->cur; no table's `prev`
+  // is written: nothing chains to these launches); the resident kernels of all its tables stop.
+  int device(GradLane lane, const GradRequest& request) const {
+    TC_HIP(hipSetDevice(it->device));
+    tc_table* t0 = it->tables[0];
+    int status = TC_OK;
+    for (tc_table* t : it->tables)
+      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+    const tc_interp::SinglePointers* pointers = nullptr;
+    status = class_pointers(it, request.n_gauss, &pointers);
+    if (status == TC_OK) status = build_grad_walk(it);
+    if (status != TC_OK) return status;
+    it->cur = next_lane(lane == GradLane::kPinned, t0->tuning.pipeline != 0, it->n_lanes,
+                        &it->device_calls);
+    tc_interp::Lane& L = it->lanes[it->cur];
+    const int n_params = request.n_params, n_dim = it->n_dim;
+    tc::GradInterpArgs ga{};
+    fill_grad_shape(t0, request.n_gauss, request.flags, &ga.table);
+    ga.n_dim = n_dim;
+    ga.n_classes = (int)it->class_table.size();
+    for (int d = 0; d < n_dim; ++d) {
+      ga.n_axis[d] = (int)it->xp[d].size();
+      ga.axis_offset[d] = it->axis_offset[d];
+      ga.a_offset[d] = it->a_offset[d];
+    }
+    ga.xp = (const double*)it->d_xp;
+    ga.a = (const double*)it->d_a;
+    ga.class_begin = (const int32_t*)it->grad_walk.class_begin;
+    ga.walk_node = (const int32_t*)it->grad_walk.node;
+    ga.matrices = (const double* const*)it->grad_walk.matrices;
+    ga.class_log_m = (const double* const*)pointers->log_m;
+    ga.class_m = (const double* const*)pointers->m;
+    ga.class_weight = (const double* const*)pointers->weight;
+    ga.class_n_h = (const double* const*)pointers->n_h;
+    ga.class_percentile = n_params == tc::kGradParamsAssembias
+                              ? (const double* const*)pointers->percentile
+                              : nullptr;
+    const int lds = (int)interp_grad_lds(it, request.likelihood(), n_params);
+    return for_each_slab(request.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
+      Range range("interpolator gradients (one launch)");
+      const GradRequest slab = request.slab(begin, n);
+      ga.table.theta = slab.theta;
+      ga.x = slab.x;
+      ga.table.n_draws = n;
+      slab.outputs(&ga.table);
+      // (timed through the first table's timer)
+      return launch_grad_batch(t0, n, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+        return launch_grad_instance(n_params, t0->mode, it->device, grid, lds, L.stream, k0, k1,
+                                    ga);
+      });
     });
-  });
-}
+  }
+};
 
-// Host arrays: the draws go up and the four result arrays come down on lane 0; `value` / `dvalue`
-// are xi and dxi, or (chi2_data given) chi2 and dchi2.  `fisher` (with chi2_data only, or NULL):
-// one array more comes down, from behind the other two.
-int interp_grad_host(tc_interp* it, const double* theta, const double* x, int64_t n_draws,
-                     int n_gauss, unsigned flags, const double* chi2_data, double* ngal,
-                     double* value, double* dngal, double* dvalue, double* fisher = nullptr,
-                     int n_params = tc::kGradParams) {
-  TC_HIP(hipSetDevice(it->device));
-  const bool chi2 = chi2_data != nullptr;
-  const size_t n = (size_t)n_draws, n_r = (size_t)it->tables[0]->n_r;
-  const size_t np = (size_t)n_params, n_cols = np + it->n_dim;
-  const size_t value_count = chi2 ? n : n * n_r;
-  int status = it->theta.reserve(n * np * 8, it->stream);
-  if (status == TC_OK) status = it->x.reserve(n * it->n_dim * 8, it->stream);
-  if (status == TC_OK) status = it->out_ngal.reserve(n * (1 + n_cols) * 8, it->stream);
-  const size_t fisher_count = fisher ? n * n_cols * n_cols : 0;
-  if (status == TC_OK)
-    status = it->out_xi.reserve((value_count * (1 + n_cols) + fisher_count) * 8, it->stream);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, n * np * 8, hipMemcpyHostToDevice, it->stream));
-  TC_HIP(hipMemcpyAsync(it->x.ptr, x, n * it->n_dim * 8, hipMemcpyHostToDevice, it->stream));
-  double* d_ngal = (double*)it->out_ngal.ptr;
-  double* d_dngal = d_ngal + n;
-  double* d_value = (double*)it->out_xi.ptr;
-  double* d_dvalue = d_value + value_count;
-  double* d_fisher = fisher ? d_dvalue + value_count * n_cols : nullptr;
-  status = interp_grad_device(it, GradLane::kPinned, (const double*)it->theta.ptr,
-                              (const double*)it->x.ptr, n_draws, n_gauss, flags, d_ngal,
-                              chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                              chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr,
-                              d_fisher, n_params);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(ngal, d_ngal, n * 8, hipMemcpyDeviceToHost, it->stream));
-  TC_HIP(hipMemcpyAsync(dngal, d_dngal, n * n_cols * 8, hipMemcpyDeviceToHost, it->stream));
-  TC_HIP(hipMemcpyAsync(value, d_value, value_count * 8, hipMemcpyDeviceToHost, it->stream));
-  TC_HIP(hipMemcpyAsync(dvalue, d_dvalue, value_count * n_cols * 8, hipMemcpyDeviceToHost,
-                        it->stream));
-  if (fisher)
-    TC_HIP(hipMemcpyAsync(fisher, d_fisher, fisher_count * 8, hipMemcpyDeviceToHost, it->stream));
-  TC_HIP(hipStreamSynchronize(it->stream));
-  return TC_OK;
+// The request of an interpolator entry point of the family `n_params`, in the order of the C
+// arguments: the n_dim extra parameters are columns behind the family's.
+GradRequest interp_request(const tc_interp* it, int n_params, const double* theta, const double* x,
+                           int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
+                           double* value, double* dngal, double* dvalue, double* fisher) {
+  GradRequest request{};
+  request.n_params = n_params;
+  request.n_extra = it ? it->n_dim : 0;
+  request.n_gauss = n_gauss;
+  request.flags = flags;
+  request.n_draws = n_draws;
+  request.n_r = it ? it->tables[0]->n_r : 0;
+  request.theta = theta;
+  request.x = x;
+  request.ngal = ngal;
+  request.dngal = dngal;
+  request.value = value;
+  request.dvalue = dvalue;
+  request.fisher = fisher;
+  return request;
 }
 
 }  // namespace
+
+// ---- the plain model (`fisher` among the outputs of the tc_interp_chi2_fisher_* entries only,
+// where it must not be NULL) and the model decorated with assembly bias (seven columns of theta,
+// the strengths last, then the n_dim extra parameters; `fisher` may be NULL) ----
 
 int tc_interp_predict_grad_zheng07_batch_device(tc_interp* it, const double* theta_device,
                                                 int n_theta, const double* x_device,
                                                 int64_t n_draws, int n_gauss, unsigned flags,
                                                 double* ngal_device, double* xi_device,
                                                 double* dngal_device, double* dxi_device) {
-  const int status =
-      check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, false);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x_device && ngal_device && xi_device && dngal_device && dxi_device, "NULL pointer");
-  return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
-                            flags, ngal_device, xi_device, dngal_device, dxi_device, nullptr,
-                            nullptr, nullptr, nullptr);
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParams, theta_device, x_device, n_draws, n_gauss,
+                                   flags, ngal_device, xi_device, dngal_device, dxi_device,
+                                   nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_interp_predict_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
                                          const double* x, int64_t n_draws, int n_gauss,
                                          unsigned flags, double* ngal, double* xi, double* dngal,
                                          double* dxi) {
-  const int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, false);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x && ngal && xi && dngal && dxi, "NULL pointer");
-  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi);
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParams, theta, x, n_draws, n_gauss, flags, ngal,
+                                   xi, dngal, dxi, nullptr),
+                    n_theta, nullptr, false);
 }
-
-namespace {
-
-// The likelihood entries on device pointers and on host arrays; `want_fisher`: the entry has a
-// Fisher matrix among its outputs (the tc_interp_chi2_fisher_* entries), which then must not be
-// NULL.
-int interp_chi2_grad_device_entry(tc_interp* it, const double* theta_device, int n_theta,
-                                  const double* x_device, int64_t n_draws, int n_gauss,
-                                  unsigned flags, const double* data, const double* precision,
-                                  double* ngal_device, double* chi2_device, double* dngal_device,
-                                  double* dchi2_device, bool want_fisher, double* fisher_device,
-                                  int n_params = tc::kGradParams) {
-  int status =
-      check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, true, n_params);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x_device && data && precision && ngal_device && chi2_device && dngal_device &&
-               dchi2_device && (!want_fisher || fisher_device),
-           "NULL pointer");
-  TC_HIP(hipSetDevice(it->device));
-  status = upload_chi2_data(it, data, precision);
-  if (status != TC_OK) return status;
-  return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
-                            flags, ngal_device, nullptr, dngal_device, nullptr,
-                            (const double*)it->chi2_data.ptr, chi2_device, dchi2_device,
-                            fisher_device, n_params);
-}
-
-int interp_chi2_grad_host_entry(tc_interp* it, const double* theta, int n_theta, const double* x,
-                                int64_t n_draws, int n_gauss, unsigned flags, const double* data,
-                                const double* precision, double* ngal, double* chi2,
-                                double* dngal, double* dchi2, bool want_fisher, double* fisher,
-                                int n_params = tc::kGradParams) {
-  int status = check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, true, n_params);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x && data && precision && ngal && chi2 && dngal && dchi2 && (!want_fisher || fisher),
-           "NULL pointer");
-  TC_HIP(hipSetDevice(it->device));
-  status = upload_chi2_data(it, data, precision);
-  if (status != TC_OK) return status;
-  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags,
-                          (const double*)it->chi2_data.ptr, ngal, chi2, dngal, dchi2, fisher,
-                          n_params);
-}
-
-}  // namespace
 
 int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* it, const double* theta_device,
                                              int n_theta, const double* x_device,
@@ -1300,9 +1214,12 @@ int tc_interp_chi2_grad_zheng07_batch_device(tc_interp* it, const double* theta_
                                              const double* data, const double* precision,
                                              double* ngal_device, double* chi2_device,
                                              double* dngal_device, double* dchi2_device) {
-  return interp_chi2_grad_device_entry(it, theta_device, n_theta, x_device, n_draws, n_gauss,
-                                       flags, data, precision, ngal_device, chi2_device,
-                                       dngal_device, dchi2_device, false, nullptr);
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParams, theta_device, x_device, n_draws, n_gauss,
+                                   flags, ngal_device, chi2_device, dngal_device, dchi2_device,
+                                   nullptr),
+                    n_theta, &operands, false);
 }
 
 int tc_interp_chi2_grad_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -1310,8 +1227,11 @@ int tc_interp_chi2_grad_zheng07_batch(tc_interp* it, const double* theta, int n_
                                       unsigned flags, const double* data,
                                       const double* precision, double* ngal, double* chi2,
                                       double* dngal, double* dchi2) {
-  return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
-                                     precision, ngal, chi2, dngal, dchi2, false, nullptr);
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParams, theta, x, n_draws, n_gauss, flags, ngal,
+                                   chi2, dngal, dchi2, nullptr),
+                    n_theta, &operands, false);
 }
 
 int tc_interp_chi2_fisher_zheng07_batch_device(tc_interp* it, const double* theta_device,
@@ -1321,9 +1241,12 @@ int tc_interp_chi2_fisher_zheng07_batch_device(tc_interp* it, const double* thet
                                                double* ngal_device, double* chi2_device,
                                                double* dngal_device, double* dchi2_device,
                                                double* fisher_device) {
-  return interp_chi2_grad_device_entry(it, theta_device, n_theta, x_device, n_draws, n_gauss,
-                                       flags, data, precision, ngal_device, chi2_device,
-                                       dngal_device, dchi2_device, true, fisher_device);
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParams, theta_device, x_device, n_draws, n_gauss,
+                                   flags, ngal_device, chi2_device, dngal_device, dchi2_device,
+                                   fisher_device),
+                    n_theta, &operands, true);
 }
 
 int tc_interp_chi2_fisher_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -1331,41 +1254,33 @@ int tc_interp_chi2_fisher_zheng07_batch(tc_interp* it, const double* theta, int 
                                         unsigned flags, const double* data,
                                         const double* precision, double* ngal, double* chi2,
                                         double* dngal, double* dchi2, double* fisher) {
-  return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
-                                     precision, ngal, chi2, dngal, dchi2, true, fisher);
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParams, theta, x, n_draws, n_gauss, flags, ngal,
+                                   chi2, dngal, dchi2, fisher),
+                    n_theta, &operands, true);
 }
-
-// ---- gradients of the model decorated with assembly bias: seven columns of theta, the
-// strengths last, then the n_dim extra parameters; `fisher` may be NULL ----
 
 int tc_interp_predict_grad_assembias_batch_device(tc_interp* it, const double* theta_device,
                                                   int n_theta, const double* x_device,
                                                   int64_t n_draws, int n_gauss, unsigned flags,
                                                   double* ngal_device, double* xi_device,
                                                   double* dngal_device, double* dxi_device) {
-  const int np = tc::kGradParamsAssembias;
-  const int status =
-      check_interp_grad_args(it, theta_device, n_theta, n_draws, n_gauss, flags, false, np);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x_device && ngal_device && xi_device && dngal_device && dxi_device, "NULL pointer");
-  return interp_grad_device(it, GradLane::kNext, theta_device, x_device, n_draws, n_gauss,
-                            flags, ngal_device, xi_device, dngal_device, dxi_device, nullptr,
-                            nullptr, nullptr, nullptr, np);
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParamsAssembias, theta_device, x_device, n_draws,
+                                   n_gauss, flags, ngal_device, xi_device, dngal_device,
+                                   dxi_device, nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_interp_predict_grad_assembias_batch(tc_interp* it, const double* theta, int n_theta,
                                            const double* x, int64_t n_draws, int n_gauss,
                                            unsigned flags, double* ngal, double* xi,
                                            double* dngal, double* dxi) {
-  const int np = tc::kGradParamsAssembias;
-  const int status =
-      check_interp_grad_args(it, theta, n_theta, n_draws, n_gauss, flags, false, np);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(x && ngal && xi && dngal && dxi, "NULL pointer");
-  return interp_grad_host(it, theta, x, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi,
-                          nullptr, np);
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParamsAssembias, theta, x, n_draws, n_gauss, flags,
+                                   ngal, xi, dngal, dxi, nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_interp_chi2_grad_assembias_batch_device(tc_interp* it, const double* theta_device,
@@ -1375,10 +1290,12 @@ int tc_interp_chi2_grad_assembias_batch_device(tc_interp* it, const double* thet
                                                double* ngal_device, double* chi2_device,
                                                double* dngal_device, double* dchi2_device,
                                                double* fisher_device) {
-  return interp_chi2_grad_device_entry(it, theta_device, n_theta, x_device, n_draws, n_gauss,
-                                       flags, data, precision, ngal_device, chi2_device,
-                                       dngal_device, dchi2_device, false, fisher_device,
-                                       tc::kGradParamsAssembias);
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParamsAssembias, theta_device, x_device, n_draws,
+                                   n_gauss, flags, ngal_device, chi2_device, dngal_device,
+                                   dchi2_device, fisher_device),
+                    n_theta, &operands, false);
 }
 
 int tc_interp_chi2_grad_assembias_batch(tc_interp* it, const double* theta, int n_theta,
@@ -1386,9 +1303,11 @@ int tc_interp_chi2_grad_assembias_batch(tc_interp* it, const double* theta, int 
                                         unsigned flags, const double* data,
                                         const double* precision, double* ngal, double* chi2,
                                         double* dngal, double* dchi2, double* fisher) {
-  return interp_chi2_grad_host_entry(it, theta, n_theta, x, n_draws, n_gauss, flags, data,
-                                     precision, ngal, chi2, dngal, dchi2, false, fisher,
-                                     tc::kGradParamsAssembias);
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParamsAssembias, theta, x, n_draws, n_gauss, flags,
+                                   ngal, chi2, dngal, dchi2, fisher),
+                    n_theta, &operands, false);
 }
 
 int tc_interp_wait(tc_interp* it, int64_t ticket) {

@@ -13,115 +13,92 @@ struct tc_joint {
   std::vector<tc_table*> tables;
   std::vector<int> r_offset;
   int n_r_total = 0;
-  DeviceBuffer chi2_data;             // data (N), then the precision matrix (N, N)
-  std::vector<double> chi2_host;      // host copy of what chi2_data holds
+  Chi2Operands chi2;                  // data (N), then the precision matrix (N, N)
 };
 
 namespace {
-
-// Data vector and precision matrix of the joint likelihood: uploaded when they differ from the
-// last upload.
-int upload_chi2_data(tc_joint* joint, const double* data, const double* precision) {
-  tc_table* t0 = joint->tables[0];
-  const size_t n = (size_t)joint->n_r_total;
-  const size_t data_count = (n + 1) * n;
-  int status = joint->chi2_data.reserve(data_count * 8, t0->stream);
-  if (status != TC_OK) return status;
-  if (joint->chi2_host.size() != data_count ||
-      memcmp(joint->chi2_host.data(), data, n * 8) != 0 ||
-      memcmp(joint->chi2_host.data() + n, precision, n * n * 8) != 0) {
-    // (earlier kernels of any lane may still read the old ones)
-    status = tc_table_synchronize(t0);
-    if (status != TC_OK) return status;
-    joint->chi2_host.assign(data, data + n);
-    joint->chi2_host.insert(joint->chi2_host.end(), precision, precision + n * n);
-    TC_HIP(hipMemcpyAsync(joint->chi2_data.ptr, joint->chi2_host.data(), data_count * 8,
-                          hipMemcpyHostToDevice, t0->stream));
-    TC_HIP(hipStreamSynchronize(t0->stream));
-  }
-  return TC_OK;
-}
 
 // The family a call's flags select: plain Zheng07, or (TC_FLAG_ASSEMBIAS) the decorated model.
 int joint_params(unsigned flags) {
   return (flags & TC_FLAG_ASSEMBIAS) ? tc::kGradParamsAssembias : tc::kGradParams;
 }
 
-// What the table entry points refuse (check_grad_args on the first table; the tables are float64
-// and share their bins by construction) and a joint beyond the LDS of a workgroup.
-int check_joint_args(const tc_joint* joint, const void* theta, int n_theta, int64_t n_draws,
-                     int n_gauss, unsigned flags, bool chi2) {
-  TC_CHECK(joint != nullptr, "joint handle is NULL");
-  const int n_params = joint_params(flags);
-  const tc_table* t0 = joint->tables[0];
-  int status = check_grad_args(t0, theta, n_theta, n_draws, n_gauss,
-                               flags & ~(unsigned)TC_FLAG_ASSEMBIAS, chi2, n_params, false);
-  const size_t lds = tc::joint_lds_bytes(t0->n_bins, t0->plan.n_central, joint->n_r_total, chi2,
-                                         n_params);
-  for (size_t k = 0; status == TC_OK && k < joint->tables.size(); ++k)
-    status = check_grad_fit(joint->tables[k], "joint gradients", lds, joint->n_r_total);
-  return status;
-}
-
-// One launch per slab of draws on lane 0 (pinned) or the next lane of the first table.  xi / dxi
-// NULL: chi2 / dchi2 from chi2_data and, where `fisher` is given, the Fisher matrix.
-int joint_device(tc_joint* joint, GradLane request, const double* theta_device, int64_t n_draws,
-                 int n_gauss, unsigned flags, double* ngal, double* xi, double* dngal,
-                 double* dxi, const double* chi2_data, double* chi2, double* dchi2,
-                 double* fisher) {
-  TC_HIP(hipSetDevice(joint->device));
-  tc_table* t0 = joint->tables[0];
-  const int n_params = joint_params(flags);
-  const int64_t np = n_params, n_total = joint->n_r_total;
-  tc::JointArgs ja{};
-  fill_grad_shape(t0, n_gauss, flags, &ja.grad);
-  ja.grad.n_r = joint->n_r_total;
-  ja.grad.n_h = (const double*)t0->d_n_h;
-  ja.grad.percentile =
-      n_params == tc::kGradParamsAssembias ? (const double*)t0->d_percentile : nullptr;
-  ja.grad.chi2_data = chi2_data;
-  ja.n_tables = (int)joint->tables.size();
-  for (int k = 0; k < ja.n_tables; ++k) {
-    tc_table* t = joint->tables[k];
-    int status = TC_OK;
-    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-    if ((status = build_grad_table(t)) != TC_OK) return status;
-    ja.mode[k] = t->mode;
-    ja.n_r[k] = t->n_r;
-    ja.r_offset[k] = joint->r_offset[k];
-    ja.matrix[k] = (const double*)t->grad.d_matrix;
+// A joint as grad_entry sees it: it works through its first table.
+struct JointGrad {
+  tc_joint* joint;
+  // What the table entry points refuse (check_grad_args on the first table, with the family's
+  // flag taken out of the flags and without the table's own fit; the tables are float64 and
+  // share their bins by construction) and a joint beyond the LDS of a workgroup.
+  int check(const GradRequest& request, int n_theta, bool likelihood) const {
+    TC_CHECK(joint != nullptr, "joint handle is NULL");
+    const tc_table* t0 = joint->tables[0];
+    GradRequest unflagged = request;
+    unflagged.flags &= ~(unsigned)TC_FLAG_ASSEMBIAS;
+    int status = check_grad_args(t0, unflagged, n_theta, likelihood, /*fit=*/false);
+    const size_t lds = tc::joint_lds_bytes(t0->n_bins, t0->plan.n_central, joint->n_r_total,
+                                           likelihood, request.n_params);
+    for (size_t k = 0; status == TC_OK && k < joint->tables.size(); ++k)
+      status = check_grad_fit(joint->tables[k], "joint gradients", lds, joint->n_r_total);
+    return status;
   }
-  return grad_slabs(t0, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
-    ja.grad.theta = theta_device + begin * np;
-    ja.grad.n_draws = n;
-    ja.grad.ngal = ngal + begin;
-    ja.grad.dngal = dngal + begin * np;
-    ja.grad.xi = xi ? xi + begin * n_total : nullptr;
-    ja.grad.dxi = dxi ? dxi + begin * np * n_total : nullptr;
-    ja.grad.chi2 = chi2 ? chi2 + begin : nullptr;
-    ja.grad.dchi2 = dchi2 ? dchi2 + begin * np : nullptr;
-    ja.grad.fisher = fisher ? fisher + begin * np * np : nullptr;
-    return run_grad_joint(t0, ja, n_params, stream);
-  });
-}
+  const char* null_message(bool likelihood) const {
+    return likelihood ? "NULL pointer" : "output pointer is NULL";
+  }
+  int device_id() const { return joint->device; }
+  Chi2Operands& operands() const { return joint->chi2; }
+  // (earlier kernels of any lane of the first table may still read the old operands)
+  int drain() const { return tc_table_synchronize(joint->tables[0]); }
+  GradStaging staging() const {
+    tc_table* t0 = joint->tables[0];
+    return {&t0->theta, nullptr, &t0->out_ngal, &t0->out_xi, t0->stream};
+  }
+  // One launch per slab of draws on lane 0 (pinned) or the next lane of the first table; the
+  // resident kernels of all the tables stop.
+  int device(GradLane lane, const GradRequest& request) const {
+    TC_HIP(hipSetDevice(joint->device));
+    tc_table* t0 = joint->tables[0];
+    tc::JointArgs ja{};
+    fill_grad_shape(t0, request.n_gauss, request.flags, &ja.grad);
+    ja.grad.n_r = joint->n_r_total;
+    ja.grad.n_h = (const double*)t0->d_n_h;
+    ja.grad.percentile = request.n_params == tc::kGradParamsAssembias
+                             ? (const double*)t0->d_percentile
+                             : nullptr;
+    ja.n_tables = (int)joint->tables.size();
+    for (int k = 0; k < ja.n_tables; ++k) {
+      tc_table* t = joint->tables[k];
+      int status = TC_OK;
+      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+      if ((status = build_grad_table(t)) != TC_OK) return status;
+      ja.mode[k] = t->mode;
+      ja.n_r[k] = t->n_r;
+      ja.r_offset[k] = joint->r_offset[k];
+      ja.matrix[k] = (const double*)t->grad.d_matrix;
+    }
+    return grad_slabs(t0, lane, request.n_draws,
+                      [&](int64_t begin, int64_t n, hipStream_t stream) {
+                        return run_grad_joint(t0, ja, request.slab(begin, n), stream);
+                      });
+  }
+};
 
-// Host arrays through the first table's staging buffers: `value` / `dvalue` are xi and dxi, or
-// (chi2_data given) chi2 and dchi2.
-int joint_host(tc_joint* joint, const double* theta, int64_t n_draws, int n_gauss, unsigned flags,
-               const double* chi2_data, double* ngal, double* value, double* dngal,
-               double* dvalue, double* fisher) {
-  const bool chi2 = chi2_data != nullptr;
-  const int n_params = joint_params(flags);
-  return grad_host_arrays(
-      joint->tables[0], theta, n_params, n_draws, n_params,
-      chi2 ? (size_t)1 : (size_t)joint->n_r_total, ngal, value, dngal, dvalue, fisher,
-      [&](const double* d_theta, double* d_ngal, double* d_dngal, double* d_value,
-          double* d_dvalue, double* d_fisher) {
-        return joint_device(joint, GradLane::kPinned, d_theta, n_draws, n_gauss, flags, d_ngal,
-                            chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                            chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr,
-                            d_fisher);
-      });
+// The request of a joint entry point, in the order of the C arguments: the family by the flags.
+GradRequest joint_request(const tc_joint* joint, const double* theta, int64_t n_draws, int n_gauss,
+                          unsigned flags, double* ngal, double* value, double* dngal,
+                          double* dvalue, double* fisher) {
+  GradRequest request{};
+  request.n_params = joint_params(flags);
+  request.n_gauss = n_gauss;
+  request.flags = flags;
+  request.n_draws = n_draws;
+  request.n_r = joint ? joint->n_r_total : 0;
+  request.theta = theta;
+  request.ngal = ngal;
+  request.dngal = dngal;
+  request.value = value;
+  request.dvalue = dvalue;
+  request.fisher = fisher;
+  return request;
 }
 
 }  // namespace
@@ -162,7 +139,7 @@ int tc_joint_destroy(tc_joint* joint) {
   // (hipFree waits for the kernels that may still read the likelihood's operands; the tables
   // are not touched: they may be gone already)
   (void)hipSetDevice(joint->device);
-  joint->chi2_data.release();
+  joint->chi2.buffer.release();
   delete joint;
   return TC_OK;
 }
@@ -184,24 +161,19 @@ int tc_joint_predict_grad_batch_device(tc_joint* joint, const double* theta_devi
                                        int64_t n_draws, int n_gauss, unsigned flags,
                                        double* ngal_device, double* xi_device,
                                        double* dngal_device, double* dxi_device) {
-  const int status =
-      check_joint_args(joint, theta_device, n_theta, n_draws, n_gauss, flags, false);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
-  return joint_device(joint, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                      xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr);
+  return grad_entry(JointGrad{joint}, GradRoute::kDevice,
+                    joint_request(joint, theta_device, n_draws, n_gauss, flags, ngal_device,
+                                  xi_device, dngal_device, dxi_device, nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_joint_predict_grad_batch(tc_joint* joint, const double* theta, int n_theta,
                                 int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
                                 double* xi, double* dngal, double* dxi) {
-  const int status = check_joint_args(joint, theta, n_theta, n_draws, n_gauss, flags, false);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
-  return joint_host(joint, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi,
-                    nullptr);
+  return grad_entry(JointGrad{joint}, GradRoute::kHost,
+                    joint_request(joint, theta, n_draws, n_gauss, flags, ngal, xi, dngal, dxi,
+                                  nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_joint_chi2_grad_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
@@ -210,32 +182,22 @@ int tc_joint_chi2_grad_batch_device(tc_joint* joint, const double* theta_device,
                                     double* ngal_device, double* chi2_device,
                                     double* dngal_device, double* dchi2_device,
                                     double* fisher_device) {
-  int status = check_joint_args(joint, theta_device, n_theta, n_draws, n_gauss, flags, true);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(data && precision && ngal_device && chi2_device && dngal_device && dchi2_device,
-           "NULL pointer");
-  TC_HIP(hipSetDevice(joint->device));
-  status = upload_chi2_data(joint, data, precision);
-  if (status != TC_OK) return status;
-  return joint_device(joint, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                      nullptr, dngal_device, nullptr, (const double*)joint->chi2_data.ptr,
-                      chi2_device, dchi2_device, fisher_device);
+  const Chi2Host operands{data, precision};
+  return grad_entry(JointGrad{joint}, GradRoute::kDevice,
+                    joint_request(joint, theta_device, n_draws, n_gauss, flags, ngal_device,
+                                  chi2_device, dngal_device, dchi2_device, fisher_device),
+                    n_theta, &operands, false);
 }
 
 int tc_joint_chi2_grad_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
                              int n_gauss, unsigned flags, const double* data,
                              const double* precision, double* ngal, double* chi2, double* dngal,
                              double* dchi2, double* fisher) {
-  int status = check_joint_args(joint, theta, n_theta, n_draws, n_gauss, flags, true);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(data && precision && ngal && chi2 && dngal && dchi2, "NULL pointer");
-  TC_HIP(hipSetDevice(joint->device));
-  status = upload_chi2_data(joint, data, precision);
-  if (status != TC_OK) return status;
-  return joint_host(joint, theta, n_draws, n_gauss, flags, (const double*)joint->chi2_data.ptr,
-                    ngal, chi2, dngal, dchi2, fisher);
+  const Chi2Host operands{data, precision};
+  return grad_entry(JointGrad{joint}, GradRoute::kHost,
+                    joint_request(joint, theta, n_draws, n_gauss, flags, ngal, chi2, dngal, dchi2,
+                                  fisher),
+                    n_theta, &operands, false);
 }
 
 int tc_debug_joint_lds_bytes(int n_bins, int n_central, int n_r_total, int chi2, int n_params,

@@ -1127,9 +1127,11 @@ static size_t vjp_lds(const tc_table* t) {
                                  : tc::vjp_cross_lds_bytes(t->n_r);
 }
 
-int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n_draws,
-                    int n_gauss, unsigned flags, bool chi2, int n_params, bool fit) {
+int check_grad_args(const tc_table* t, const GradRequest& request, int n_theta, bool likelihood,
+                    bool fit) {
   TC_CHECK(t != nullptr, "table handle is NULL");
+  const int n_params = request.n_params, n_gauss = request.n_gauss;
+  const unsigned flags = request.flags;
   const bool decorated = n_params == tc::kGradParamsAssembias;
   const bool leauthaud = n_params == tc::kGradParamsLeauthaud11;
   const unsigned unserved = flags & ~(unsigned)TC_FLAG_MODULATE_WITH_CENOCC;
@@ -1153,12 +1155,12 @@ int check_grad_args(const tc_table* t, const void* theta, int n_theta, int64_t n
   if (unserved != 0) return fail(TC_ERR_UNSUPPORTED, "gradients: unknown flags 0x%x", unserved);
   if (t->compute_dtype != TC_DTYPE_F64)
     return fail(TC_ERR_UNSUPPORTED, "gradients need a float64 compute dtype");
-  TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
-  TC_CHECK(n_draws == 0 || theta != nullptr, "theta is NULL");
+  TC_CHECK(request.n_draws >= 0, "n_draws must be non-negative");
+  TC_CHECK(request.n_draws == 0 || request.theta != nullptr, "theta is NULL");
   TC_CHECK(n_gauss >= 1 && n_gauss <= 4096, "n_gauss_prim must be in [1, 4096]");
-  TC_CHECK(n_theta == tc::grad_theta_columns(n_params), "theta must have %d columns, got %d",
-           tc::grad_theta_columns(n_params), n_theta);
-  return fit ? check_grad_fit(t, "gradients", grad_lds(t, chi2, n_params)) : TC_OK;
+  TC_CHECK(n_theta == request.theta_columns(), "theta must have %d columns, got %d",
+           request.theta_columns(), n_theta);
+  return fit ? check_grad_fit(t, "gradients", grad_lds(t, likelihood, n_params)) : TC_OK;
 }
 
 int build_grad_table(tc_table* t) {
@@ -1229,45 +1231,71 @@ int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
   return TC_OK;
 }
 
-int run_grad(tc_table* t, const double* theta_device, int64_t n_draws, int n_gauss,
-             unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-             const double* chi2_data, double* chi2, double* dchi2, double* fisher,
-             hipStream_t stream, int n_params) {
+// (a family without kernels is an error, never another family's kernel)
+static int no_grad_family(int n_params) {
+  return fail(TC_ERR_INVALID, "no derivative kernel differentiates %d parameters", n_params);
+}
+
+int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
+                         hipStream_t stream, hipEvent_t k0, hipEvent_t k1, const tc::GradArgs& ga) {
+  switch (n_params) {
+    case tc::kGradParams:
+      return launch_grad_family<tc::kGradParams>(mode, device, grid, lds, stream, k0, k1, ga);
+    case tc::kGradParamsAssembias:
+      return launch_grad_family<tc::kGradParamsAssembias>(mode, device, grid, lds, stream, k0, k1,
+                                                          ga);
+    case tc::kGradParamsLeauthaud11:
+      return launch_grad_family<tc::kGradParamsLeauthaud11>(mode, device, grid, lds, stream, k0,
+                                                            k1, ga);
+  }
+  return no_grad_family(n_params);
+}
+
+int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
+                         hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
+                         const tc::GradInterpArgs& ga) {
+  switch (n_params) {
+    case tc::kGradParams:
+      return launch_grad_family<tc::kGradParams>(mode, device, grid, lds, stream, k0, k1, ga);
+    case tc::kGradParamsAssembias:
+      return launch_grad_family<tc::kGradParamsAssembias>(mode, device, grid, lds, stream, k0, k1,
+                                                          ga);
+  }
+  return no_grad_family(n_params);
+}
+
+int run_grad(tc_table* t, const GradRequest& request, hipStream_t stream) {
   Range range("gradients (one launch)");
-  const bool decorated = n_params == tc::kGradParamsAssembias;
+  const int n_params = request.n_params;
   Quadrature* q = nullptr;
-  int status = get_quadrature(t, n_gauss, &q);
+  int status = get_quadrature(t, request.n_gauss, &q);
   if (status == TC_OK) status = build_grad_table(t);
   if (status != TC_OK) return status;
   tc::GradArgs ga{};
-  fill_grad_shape(t, n_gauss, flags, &ga);
-  ga.theta = theta_device;
-  ga.n_draws = n_draws;
+  fill_grad_shape(t, request.n_gauss, request.flags, &ga);
+  ga.theta = request.theta;
+  ga.n_draws = request.n_draws;
+  request.outputs(&ga);
   ga.log_m = (const double*)q->log_m;
   ga.m = (const double*)q->m;
   ga.weight = (const double*)q->weight;
   ga.n_h = (const double*)t->d_n_h;
   ga.matrix = (const double*)t->grad.d_matrix;
-  ga.ngal = ngal;
-  ga.dngal = dngal;
-  ga.xi = xi;
-  ga.dxi = dxi;
-  ga.chi2_data = chi2_data;
-  ga.chi2 = chi2;
-  ga.dchi2 = dchi2;
-  ga.fisher = fisher;
-  ga.percentile = decorated ? (const double*)t->d_percentile : nullptr;
-  const int lds = (int)grad_lds(t, xi == nullptr, n_params);
-  return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-    const auto instance = n_params == tc::kGradParamsLeauthaud11
-                              ? launch_grad_leauthaud11_instance
-                              : (decorated ? launch_grad_assembias_instance : launch_grad_instance);
-    return instance(t->mode, t->device, grid, lds, stream, k0, k1, ga);
+  ga.percentile =
+      n_params == tc::kGradParamsAssembias ? (const double*)t->d_percentile : nullptr;
+  const int lds = (int)grad_lds(t, request.likelihood(), n_params);
+  return launch_grad_batch(t, request.n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+    return launch_grad_instance(n_params, t->mode, t->device, grid, lds, stream, k0, k1, ga);
   });
 }
 
-int run_grad_joint(tc_table* t0, tc::JointArgs ja, int n_params, hipStream_t stream) {
+int run_grad_joint(tc_table* t0, tc::JointArgs ja, const GradRequest& request,
+                   hipStream_t stream) {
   Range range("joint gradients (one launch)");
+  const int n_params = request.n_params;
+  ja.grad.theta = request.theta;
+  ja.grad.n_draws = request.n_draws;
+  request.outputs(&ja.grad);
   Quadrature* q = nullptr;
   const int status = get_quadrature(t0, ja.grad.n_gauss, &q);
   if (status != TC_OK) return status;
@@ -1275,7 +1303,7 @@ int run_grad_joint(tc_table* t0, tc::JointArgs ja, int n_params, hipStream_t str
   ja.grad.m = (const double*)q->m;
   ja.grad.weight = (const double*)q->weight;
   const int lds = (int)tc::joint_lds_bytes(ja.grad.n_bins, ja.grad.n_central, ja.grad.n_r,
-                                           ja.grad.xi == nullptr, n_params);
+                                           request.likelihood(), n_params);
   return launch_grad_batch(t0, ja.grad.n_draws, lds,
                            [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
                              return launch_grad_joint_instance(n_params, t0->device, grid, lds,

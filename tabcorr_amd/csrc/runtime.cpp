@@ -552,6 +552,18 @@ int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n
   return TC_OK;
 }
 
+int tc_debug_grad_slab(int n_params, int n_extra, int n_r, int likelihood, int64_t begin,
+                       int64_t* offsets) {
+  TC_CHECK(offsets != nullptr, "offsets is NULL");
+  TC_CHECK(n_params == tc::kGradParams || n_params == tc::kGradParamsAssembias ||
+               n_params == tc::kGradParamsLeauthaud11,
+           "n_params must be %d, %d or %d", tc::kGradParams, tc::kGradParamsAssembias,
+           tc::kGradParamsLeauthaud11);
+  TC_CHECK(n_extra >= 0 && n_r >= 1 && begin >= 0, "invalid sizes");
+  grad_slab_offsets(n_params, n_extra, n_r, likelihood != 0, begin, offsets);
+  return TC_OK;
+}
+
 int tc_debug_leauthaud11_node_grad(const double* theta, int modulate, int64_t n,
                                    const double* mass, double* log_mstar, double* n_cen,
                                    double* dn_cen, double* n_sat, double* dn_sat) {

@@ -261,7 +261,7 @@ int tc_table_destroy(tc_table* t) {
   t->cross_fused_wide.release();
   t->grad.release();
   for (DeviceBuffer* b : {&t->theta, &t->out_ngal, &t->out_xi, &t->occupation,
-                          &t->trace, &t->wave_trace, &t->chi2_data})
+                          &t->trace, &t->wave_trace, &t->chi2.buffer})
     b->release();
   for (tc_table::Lane& lane : t->lanes) {
     lane.nbuf.release();
@@ -868,28 +868,18 @@ int tc_predict_zheng07_batch(tc_table* t, const double* theta, int n_theta,
 
 namespace {
 
-// The data vector and the precision matrix of a likelihood do not change between calls:
-// they are uploaded when they differ from the host copy of the last upload.
-int upload_chi2_data(tc_table* t, const double* data, const double* precision) {
-  const int n_r = t->n_r;
-  int status = t->chi2_data.reserve((size_t)(n_r + 1) * n_r * 8, t->stream);
-  if (status != TC_OK) return status;
-  const size_t data_count = (size_t)(n_r + 1) * n_r;
-  if (t->chi2_host.size() != data_count ||
-      memcmp(t->chi2_host.data(), data, (size_t)n_r * 8) != 0 ||
-      memcmp(t->chi2_host.data() + n_r, precision, (size_t)n_r * n_r * 8) != 0) {
-    // (kernels of earlier calls may still be reading the old values)
-    for (tc_table::Lane& lane : t->lanes)
-      if (lane.stream) TC_HIP(hipStreamSynchronize(lane.stream));
-    t->chi2_host.assign(data, data + n_r);
-    t->chi2_host.insert(t->chi2_host.end(), precision, precision + (size_t)n_r * n_r);
-    TC_HIP(hipMemcpyAsync(t->chi2_data.ptr, t->chi2_host.data(), data_count * 8,
-                          hipMemcpyHostToDevice, t->stream));
-    TC_HIP(hipStreamSynchronize(t->stream));
-  }
+// What the operand cache of a table waits for before new values go up: every lane's stream.
+int drain_lanes(tc_table* t) {
+  for (tc_table::Lane& lane : t->lanes)
+    if (lane.stream) TC_HIP(hipStreamSynchronize(lane.stream));
   return TC_OK;
 }
 
+// The data vector and the precision matrix of a likelihood on the device (internal.h:
+// Chi2Operands).
+int upload_operands(tc_table* t, const double* data, const double* precision) {
+  return t->chi2.upload(t->n_r, data, precision, t->stream, [t] { return drain_lanes(t); });
+}
 
 // A likelihood of 0 < n_draws <= max_slab(t) draws on device pointers as `call` describes it
 // (the arguments are checked): tc_chi2_zheng07_batch_device and its asynchronous twin.
@@ -899,7 +889,7 @@ int chi2_on_device(tc_table* t, Call call, const double* theta_device, int n_the
   TC_HIP(hipSetDevice(t->device));
   int status = TC_OK;
   if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  status = upload_chi2_data(t, data, precision);
+  status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
   // xi stays in a workspace of the lane the call runs on; the lane's `finished` event is
   // re-recorded behind the chi2 kernel, so the next call on this lane (whose finalisation
@@ -907,7 +897,7 @@ int chi2_on_device(tc_table* t, Call call, const double* theta_device, int n_the
   tc_table::Lane& lane = t->lanes[call.lane];
   status = lane.xi.reserve((size_t)n_draws * t->n_r * 8, lane.stream);
   if (status != TC_OK) return status;
-  call.chi2_data = (const double*)t->chi2_data.ptr;
+  call.chi2_data = t->chi2.device();
   call.chi2_out = chi2_device;
   bool written = false;
   status = predict_device(t, call, theta_device, n_theta, n_draws, n_gauss, flags, ngal_device,
@@ -954,10 +944,10 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   const size_t xi_count = (size_t)n_draws * n_r;
   const size_t theta_bytes = (size_t)n_draws * n_theta * sizeof(double);
   status = t->out_xi.reserve(xi_count * 8, t->stream);
-  if (status == TC_OK) status = upload_chi2_data(t, data, precision);
+  if (status == TC_OK) status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
-  double* d_data = (double*)t->chi2_data.ptr;
-  double* d_precision = d_data + n_r;
+  const double* d_data = t->chi2.device();
+  const double* d_precision = d_data + n_r;
   // small calls: draws read from and results written to page-locked host memory directly
   const bool direct = theta_bytes + (size_t)n_draws * 16 <= zero_copy_limit() &&
                       t->h_in.reserve(theta_bytes) == TC_OK &&
@@ -1000,43 +990,51 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
                   d_chi2, t->stream);
 }
 
-// ---- gradients (launch.hip: run_grad) -----------------------------------------------------
+// ---- gradients (grad_call.h: grad_entry; launch.hip: run_grad) ----------------------------
 
 namespace {
 
-// (n_params: tc::kGradParams, tc::kGradParamsAssembias for the decorated model, or
-// tc::kGradParamsLeauthaud11, whose draws have tc::grad_theta_columns(n_params) = 14 columns)
-int grad_device(tc_table* t, GradLane request, const double* theta_device, int64_t n_draws,
-                int n_gauss, unsigned flags, double* ngal, double* xi, double* dngal, double* dxi,
-                const double* chi2_data, double* chi2, double* dchi2, double* fisher,
-                int n_params = tc::kGradParams) {
-  const int64_t n_r = t->n_r, np = n_params;
-  return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
-    return run_grad(t, theta_device + begin * tc::grad_theta_columns(n_params), n, n_gauss, flags,
-                    ngal + begin,
-                    xi ? xi + begin * n_r : nullptr, dngal + begin * np,
-                    dxi ? dxi + begin * np * n_r : nullptr, chi2_data,
-                    chi2 ? chi2 + begin : nullptr, dchi2 ? dchi2 + begin * np : nullptr,
-                    fisher ? fisher + begin * np * np : nullptr, stream, n_params);
-  });
-}
+// A table as grad_entry sees it.
+struct TableGrad {
+  tc_table* t;
+  int check(const GradRequest& request, int n_theta, bool likelihood) const {
+    return check_grad_args(t, request, n_theta, likelihood, /*fit=*/true);
+  }
+  const char* null_message(bool likelihood) const {
+    return likelihood ? "NULL pointer" : "output pointer is NULL";
+  }
+  int device_id() const { return t->device; }
+  Chi2Operands& operands() const { return t->chi2; }
+  int drain() const { return drain_lanes(t); }      // each lane's stream
+  GradStaging staging() const {
+    return {&t->theta, nullptr, &t->out_ngal, &t->out_xi, t->stream};
+  }
+  // (grad_slabs: the table's resident kernel stops, the lane is the table's next, t->prev says
+  // who may chain to it)
+  int device(GradLane lane, const GradRequest& request) const {
+    return grad_slabs(t, lane, request.n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
+      return run_grad(t, request.slab(begin, n), stream);
+    });
+  }
+};
 
-// Host arrays (internal.h: grad_host_arrays): `value` / `dvalue` are xi and dxi, or (chi2_data
-// given) chi2 and dchi2; `fisher` (with chi2_data only, or NULL): one array more comes down.
-int grad_host(tc_table* t, const double* theta, int64_t n_draws, int n_gauss, unsigned flags,
-              const double* chi2_data, double* ngal, double* value, double* dngal,
-              double* dvalue, double* fisher = nullptr, int n_params = tc::kGradParams) {
-  const bool chi2 = chi2_data != nullptr;
-  return grad_host_arrays(
-      t, theta, tc::grad_theta_columns(n_params), n_draws, n_params,
-      chi2 ? (size_t)1 : (size_t)t->n_r, ngal, value, dngal, dvalue, fisher,
-      [&](const double* d_theta, double* d_ngal, double* d_dngal, double* d_value,
-          double* d_dvalue, double* d_fisher) {
-        return grad_device(t, GradLane::kPinned, d_theta, n_draws, n_gauss, flags, d_ngal,
-                           chi2 ? nullptr : d_value, d_dngal, chi2 ? nullptr : d_dvalue,
-                           chi2_data, chi2 ? d_value : nullptr, chi2 ? d_dvalue : nullptr,
-                           d_fisher, n_params);
-      });
+// The request of a table entry point of the family `n_params`, in the order of the C arguments.
+GradRequest table_request(const tc_table* t, int n_params, const double* theta, int64_t n_draws,
+                          int n_gauss, unsigned flags, double* ngal, double* value,
+                          double* dngal, double* dvalue, double* fisher) {
+  GradRequest request{};
+  request.n_params = n_params;
+  request.n_gauss = n_gauss;
+  request.flags = flags;
+  request.n_draws = n_draws;
+  request.n_r = t ? t->n_r : 0;
+  request.theta = theta;
+  request.ngal = ngal;
+  request.dngal = dngal;
+  request.value = value;
+  request.dvalue = dvalue;
+  request.fisher = fisher;
+  return request;
 }
 
 }  // namespace
@@ -1045,82 +1043,42 @@ int tc_predict_grad_zheng07_batch_device(tc_table* t, const double* theta_device
                                          int64_t n_draws, int n_gauss, unsigned flags,
                                          double* ngal_device, double* xi_device,
                                          double* dngal_device, double* dxi_device) {
-  const int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, false);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
-  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr);
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParams, theta_device, n_draws, n_gauss, flags,
+                                  ngal_device, xi_device, dngal_device, dxi_device, nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_predict_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta,
                                   int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
                                   double* xi, double* dngal, double* dxi) {
-  const int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, false);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
-  return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi);
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParams, theta, n_draws, n_gauss, flags, ngal, xi,
+                                  dngal, dxi, nullptr),
+                    n_theta, nullptr, false);
 }
-
-namespace {
-
-// The likelihood entries on device pointers and on host arrays; `want_fisher`: the entry has a
-// Fisher matrix among its outputs (the tc_chi2_fisher_* entries), which then must not be NULL.
-int chi2_grad_device_entry(tc_table* t, const double* theta_device, int n_theta, int64_t n_draws,
-                           int n_gauss, unsigned flags, const double* data,
-                           const double* precision, double* ngal_device, double* chi2_device,
-                           double* dngal_device, double* dchi2_device, bool want_fisher,
-                           double* fisher_device, int n_params = tc::kGradParams) {
-  int status =
-      check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, true, n_params);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(data && precision && ngal_device && chi2_device && dngal_device && dchi2_device &&
-               (!want_fisher || fisher_device),
-           "NULL pointer");
-  TC_HIP(hipSetDevice(t->device));
-  status = upload_chi2_data(t, data, precision);
-  if (status != TC_OK) return status;
-  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                     nullptr, dngal_device, nullptr, (const double*)t->chi2_data.ptr, chi2_device,
-                     dchi2_device, fisher_device, n_params);
-}
-
-int chi2_grad_host_entry(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
-                         int n_gauss, unsigned flags, const double* data, const double* precision,
-                         double* ngal, double* chi2, double* dngal, double* dchi2,
-                         bool want_fisher, double* fisher, int n_params = tc::kGradParams) {
-  int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, true, n_params);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(data && precision && ngal && chi2 && dngal && dchi2 && (!want_fisher || fisher),
-           "NULL pointer");
-  TC_HIP(hipSetDevice(t->device));
-  status = upload_chi2_data(t, data, precision);
-  if (status != TC_OK) return status;
-  return grad_host(t, theta, n_draws, n_gauss, flags, (const double*)t->chi2_data.ptr, ngal,
-                   chi2, dngal, dchi2, fisher, n_params);
-}
-
-}  // namespace
 
 int tc_chi2_grad_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
                                       int64_t n_draws, int n_gauss, unsigned flags,
                                       const double* data, const double* precision,
                                       double* ngal_device, double* chi2_device,
                                       double* dngal_device, double* dchi2_device) {
-  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
-                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
-                                false, nullptr);
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParams, theta_device, n_draws, n_gauss, flags,
+                                  ngal_device, chi2_device, dngal_device, dchi2_device, nullptr),
+                    n_theta, &operands, false);
 }
 
 int tc_chi2_grad_zheng07_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
                                int n_gauss, unsigned flags, const double* data,
                                const double* precision, double* ngal, double* chi2,
                                double* dngal, double* dchi2) {
-  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
-                              chi2, dngal, dchi2, false, nullptr);
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParams, theta, n_draws, n_gauss, flags, ngal, chi2,
+                                  dngal, dchi2, nullptr),
+                    n_theta, &operands, false);
 }
 
 int tc_chi2_fisher_zheng07_batch_device(tc_table* t, const double* theta_device, int n_theta,
@@ -1129,109 +1087,113 @@ int tc_chi2_fisher_zheng07_batch_device(tc_table* t, const double* theta_device,
                                         double* ngal_device, double* chi2_device,
                                         double* dngal_device, double* dchi2_device,
                                         double* fisher_device) {
-  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
-                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
-                                true, fisher_device);
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParams, theta_device, n_draws, n_gauss, flags,
+                                  ngal_device, chi2_device, dngal_device, dchi2_device,
+                                  fisher_device),
+                    n_theta, &operands, true);
 }
 
 int tc_chi2_fisher_zheng07_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
                                  int n_gauss, unsigned flags, const double* data,
                                  const double* precision, double* ngal, double* chi2,
                                  double* dngal, double* dchi2, double* fisher) {
-  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
-                              chi2, dngal, dchi2, true, fisher);
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParams, theta, n_draws, n_gauss, flags, ngal, chi2,
+                                  dngal, dchi2, fisher),
+                    n_theta, &operands, true);
 }
 
-// ---- gradients of the model decorated with assembly bias: seven columns, the strengths last;
-// `fisher` may be NULL ----
+// ---- gradients of the model decorated with assembly bias (seven columns, the strengths last)
+// and of the Leauthaud11 family (fourteen theta columns, eleven differentiated: grad.h:
+// kGradParamsLeauthaud11); `fisher` may be NULL ----
 
 int tc_predict_grad_assembias_batch_device(tc_table* t, const double* theta_device, int n_theta,
-                                           int64_t n_draws, int n_gauss, unsigned flags,
-                                           double* ngal_device, double* xi_device,
-                                           double* dngal_device, double* dxi_device) {
-  const int np = tc::kGradParamsAssembias;
-  const int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, false, np);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
-  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr, np);
+                                        int64_t n_draws, int n_gauss, unsigned flags,
+                                        double* ngal_device, double* xi_device,
+                                        double* dngal_device, double* dxi_device) {
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParamsAssembias, theta_device, n_draws, n_gauss, flags, ngal_device,
+                                  xi_device, dngal_device, dxi_device, nullptr),
+                    n_theta, nullptr, false);
 }
 
-int tc_predict_grad_assembias_batch(tc_table* t, const double* theta, int n_theta,
-                                    int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
-                                    double* xi, double* dngal, double* dxi) {
-  const int np = tc::kGradParamsAssembias;
-  const int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, false, np);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
-  return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi, nullptr, np);
+int tc_predict_grad_assembias_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                                 int n_gauss, unsigned flags, double* ngal, double* xi,
+                                 double* dngal, double* dxi) {
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParamsAssembias, theta, n_draws, n_gauss, flags, ngal, xi, dngal,
+                                  dxi, nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_chi2_grad_assembias_batch_device(tc_table* t, const double* theta_device, int n_theta,
-                                        int64_t n_draws, int n_gauss, unsigned flags,
-                                        const double* data, const double* precision,
-                                        double* ngal_device, double* chi2_device,
-                                        double* dngal_device, double* dchi2_device,
-                                        double* fisher_device) {
-  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
-                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
-                                false, fisher_device, tc::kGradParamsAssembias);
+                                     int64_t n_draws, int n_gauss, unsigned flags,
+                                     const double* data, const double* precision,
+                                     double* ngal_device, double* chi2_device,
+                                     double* dngal_device, double* dchi2_device,
+                                     double* fisher_device) {
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParamsAssembias, theta_device, n_draws, n_gauss, flags, ngal_device,
+                                  chi2_device, dngal_device, dchi2_device, fisher_device),
+                    n_theta, &operands, false);
 }
 
 int tc_chi2_grad_assembias_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
-                                 int n_gauss, unsigned flags, const double* data,
-                                 const double* precision, double* ngal, double* chi2,
-                                 double* dngal, double* dchi2, double* fisher) {
-  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
-                              chi2, dngal, dchi2, false, fisher, tc::kGradParamsAssembias);
+                              int n_gauss, unsigned flags, const double* data,
+                              const double* precision, double* ngal, double* chi2, double* dngal,
+                              double* dchi2, double* fisher) {
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParamsAssembias, theta, n_draws, n_gauss, flags, ngal, chi2, dngal,
+                                  dchi2, fisher),
+                    n_theta, &operands, false);
 }
-
-// ---- gradients of the Leauthaud11 family: fourteen theta columns, eleven differentiated
-// (grad.h: kGradParamsLeauthaud11); `fisher` may be NULL ----
 
 int tc_predict_grad_leauthaud11_batch_device(tc_table* t, const double* theta_device, int n_theta,
-                                             int64_t n_draws, int n_gauss, unsigned flags,
-                                             double* ngal_device, double* xi_device,
-                                             double* dngal_device, double* dxi_device) {
-  const int np = tc::kGradParamsLeauthaud11;
-  const int status = check_grad_args(t, theta_device, n_theta, n_draws, n_gauss, flags, false, np);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal_device && xi_device && dngal_device && dxi_device, "output pointer is NULL");
-  return grad_device(t, GradLane::kNext, theta_device, n_draws, n_gauss, flags, ngal_device,
-                     xi_device, dngal_device, dxi_device, nullptr, nullptr, nullptr, nullptr, np);
+                                        int64_t n_draws, int n_gauss, unsigned flags,
+                                        double* ngal_device, double* xi_device,
+                                        double* dngal_device, double* dxi_device) {
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParamsLeauthaud11, theta_device, n_draws, n_gauss, flags, ngal_device,
+                                  xi_device, dngal_device, dxi_device, nullptr),
+                    n_theta, nullptr, false);
 }
 
-int tc_predict_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta,
-                                      int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
-                                      double* xi, double* dngal, double* dxi) {
-  const int np = tc::kGradParamsLeauthaud11;
-  const int status = check_grad_args(t, theta, n_theta, n_draws, n_gauss, flags, false, np);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(ngal && xi && dngal && dxi, "output pointer is NULL");
-  return grad_host(t, theta, n_draws, n_gauss, flags, nullptr, ngal, xi, dngal, dxi, nullptr, np);
+int tc_predict_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
+                                 int n_gauss, unsigned flags, double* ngal, double* xi,
+                                 double* dngal, double* dxi) {
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParamsLeauthaud11, theta, n_draws, n_gauss, flags, ngal, xi, dngal,
+                                  dxi, nullptr),
+                    n_theta, nullptr, false);
 }
 
 int tc_chi2_grad_leauthaud11_batch_device(tc_table* t, const double* theta_device, int n_theta,
-                                          int64_t n_draws, int n_gauss, unsigned flags,
-                                          const double* data, const double* precision,
-                                          double* ngal_device, double* chi2_device,
-                                          double* dngal_device, double* dchi2_device,
-                                          double* fisher_device) {
-  return chi2_grad_device_entry(t, theta_device, n_theta, n_draws, n_gauss, flags, data,
-                                precision, ngal_device, chi2_device, dngal_device, dchi2_device,
-                                false, fisher_device, tc::kGradParamsLeauthaud11);
+                                     int64_t n_draws, int n_gauss, unsigned flags,
+                                     const double* data, const double* precision,
+                                     double* ngal_device, double* chi2_device,
+                                     double* dngal_device, double* dchi2_device,
+                                     double* fisher_device) {
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kDevice,
+                    table_request(t, tc::kGradParamsLeauthaud11, theta_device, n_draws, n_gauss, flags, ngal_device,
+                                  chi2_device, dngal_device, dchi2_device, fisher_device),
+                    n_theta, &operands, false);
 }
 
 int tc_chi2_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
-                                   int n_gauss, unsigned flags, const double* data,
-                                   const double* precision, double* ngal, double* chi2,
-                                   double* dngal, double* dchi2, double* fisher) {
-  return chi2_grad_host_entry(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal,
-                              chi2, dngal, dchi2, false, fisher, tc::kGradParamsLeauthaud11);
+                              int n_gauss, unsigned flags, const double* data,
+                              const double* precision, double* ngal, double* chi2, double* dngal,
+                              double* dchi2, double* fisher) {
+  const Chi2Host operands{data, precision};
+  return grad_entry(TableGrad{t}, GradRoute::kHost,
+                    table_request(t, tc::kGradParamsLeauthaud11, theta, n_draws, n_gauss, flags, ngal, chi2, dngal,
+                                  dchi2, fisher),
+                    n_theta, &operands, false);
 }
 
 // ---- occupation VJP (launch.hip: run_vjp) -------------------------------------------------
@@ -1333,10 +1295,10 @@ int tc_chi2_occupation_grad_batch_device(tc_table* t, const double* occupation_d
                dchi2_docc_device,
            "NULL pointer");
   TC_HIP(hipSetDevice(t->device));
-  status = upload_chi2_data(t, data, precision);
+  status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
   return vjp_device(t, GradLane::kNext, occupation_device, n_draws, nullptr, nullptr,
-                    (const double*)t->chi2_data.ptr, ngal_device, nullptr, chi2_device,
+                    t->chi2.device(), ngal_device, nullptr, chi2_device,
                     dchi2_docc_device);
 }
 
@@ -1348,9 +1310,9 @@ int tc_chi2_occupation_grad_batch(tc_table* t, const double* occupation, int64_t
   if (n_draws == 0) return TC_OK;
   TC_CHECK(occupation && data && precision && ngal && chi2 && dchi2_docc, "NULL pointer");
   TC_HIP(hipSetDevice(t->device));
-  status = upload_chi2_data(t, data, precision);
+  status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
-  return vjp_host(t, occupation, n_draws, nullptr, nullptr, (const double*)t->chi2_data.ptr,
+  return vjp_host(t, occupation, n_draws, nullptr, nullptr, t->chi2.device(),
                   ngal, chi2, dchi2_docc);
 }
 

@@ -19,11 +19,11 @@ import threading
 
 import numpy as np
 
+from . import _grad
 from . import _lib
 from . import pinned
 from .galtable import GalTypeTable
 from .models import device_spec
-from .models import ZHENG07_KEYS
 from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _chi2_operands, _flags,
                       _grad_keys, _grad_spec, _grad_theta, _unbatch)
 
@@ -488,26 +488,19 @@ class Interpolator:
         (float32 tables, grids whose rows do not fit the LDS of a workgroup).
         """
         theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
-        device = self.to_device()
-        n_draws, n_r = len(theta), device.tables[0].n_r
-        n_cols = theta.shape[1] + len(self.keys)
-        ngal = np.empty(n_draws)
-        xi = np.empty((n_draws, n_r))
-        dngal = np.empty((n_draws, n_cols))
-        dxi = np.empty((n_draws, n_cols, n_r))
-        entry = (device.lib.tc_interp_predict_grad_assembias_batch
-                 if assembias
-                 else device.lib.tc_interp_predict_grad_zheng07_batch)
-        with device.lock:
-            _lib.check(entry(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                _lib.as_double_p(x), n_draws, n_gauss_prim,
-                _flags(False, modulate_with_cenocc), _lib.as_double_p(ngal),
-                _lib.as_double_p(xi), _lib.as_double_p(dngal),
-                _lib.as_double_p(dxi)))
-        shape = tuple(self.tabcorr_list[0].tpcf_shape)
-        return (ngal, xi.reshape((n_draws, ) + shape), dngal,
-                dxi.reshape((n_draws, n_cols) + shape))
+        return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
+                               assembias)
+
+    def _grad_call(self, theta, x, n_gauss_prim, modulate_with_cenocc,
+                   assembias, operands=None, want_fisher=False):
+        """The derivative entry for checked ``(theta, x)``: the family's
+        columns, then ``self.keys``."""
+        return _grad.call(
+            self.to_device(), 'interp', _grad.family_of(assembias),
+            [theta, theta.shape[1], x, len(theta), n_gauss_prim,
+             _flags(False, modulate_with_cenocc)],
+            theta.shape[1] + len(self.keys), self.tabcorr_list[0].tpcf_shape,
+            operands, want_fisher)
 
     def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
                         extrapolate=False, modulate_with_cenocc=False,
@@ -523,53 +516,11 @@ class Interpolator:
         ngal, chi2 : ``(n_draws, )``
         dngal, dchi2 : ``(n_draws, 5 + D)``
         """
-        if assembias:
-            return self._chi2_grad_assembias(
-                theta, x, data, precision, n_gauss_prim, extrapolate,
-                modulate_with_cenocc, False)[:4]
-        theta, x = self._grad_inputs(theta, x, extrapolate)
-        data, precision = _chi2_operands(
+        theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
+        operands = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(theta)
-        n_cols = len(ZHENG07_KEYS) + len(self.keys)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal = np.empty((n_draws, n_cols))
-        dchi2 = np.empty((n_draws, n_cols))
-        with device.lock:
-            _lib.check(device.lib.tc_interp_chi2_grad_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                _lib.as_double_p(x), n_draws, n_gauss_prim,
-                _flags(False, modulate_with_cenocc), _lib.as_double_p(data),
-                _lib.as_double_p(precision), _lib.as_double_p(ngal),
-                _lib.as_double_p(chi2), _lib.as_double_p(dngal),
-                _lib.as_double_p(dchi2)))
-        return ngal, chi2, dngal, dchi2
-
-    def _chi2_grad_assembias(self, theta, x, data, precision, n_gauss_prim,
-                             extrapolate, modulate_with_cenocc, want_fisher):
-        """The likelihood gradient of the decorated model, with or without
-        its Fisher matrix: one entry point serves both."""
-        theta, x = self._grad_inputs(theta, x, extrapolate, True)
-        data, precision = _chi2_operands(
-            data, precision, len(self.tabcorr_list[0].tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(theta)
-        n_cols = theta.shape[1] + len(self.keys)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal = np.empty((n_draws, n_cols))
-        dchi2 = np.empty((n_draws, n_cols))
-        fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
-        with device.lock:
-            _lib.check(device.lib.tc_interp_chi2_grad_assembias_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                _lib.as_double_p(x), n_draws, n_gauss_prim,
-                _flags(False, modulate_with_cenocc), _lib.as_double_p(data),
-                _lib.as_double_p(precision), _lib.as_double_p(ngal),
-                _lib.as_double_p(chi2), _lib.as_double_p(dngal),
-                _lib.as_double_p(dchi2),
-                _lib.as_double_p(fisher) if want_fisher else None))
-        return ngal, chi2, dngal, dchi2, fisher
+        return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
+                               assembias, operands)
 
     def predict_grad(self, model, n_gauss_prim=10, extrapolate=False,
                      check_consistency=True, assembias=False):
@@ -599,9 +550,8 @@ class Interpolator:
             modulate_with_cenocc=spec.modulate_with_cenocc,
             assembias=assembias)
         keys = model_keys + tuple(self.keys)
-        return (float(ngal[0]), xi[0],
-                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
-                {key: dxi[0, k] for k, key in enumerate(keys)})
+        return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], keys),
+                _grad.keyed(dxi[0], keys))
 
     # -- Fisher matrix of the likelihood ------------------------------------------------
 
@@ -630,29 +580,11 @@ class Interpolator:
             for bit
         fisher : ``(n_draws, 5 + D, 5 + D)``
         """
-        if assembias:
-            return self._chi2_grad_assembias(
-                theta, x, data, precision, n_gauss_prim, extrapolate,
-                modulate_with_cenocc, True)
-        theta, x = self._grad_inputs(theta, x, extrapolate)
-        data, precision = _chi2_operands(
+        theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
+        operands = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(theta)
-        n_cols = len(ZHENG07_KEYS) + len(self.keys)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal = np.empty((n_draws, n_cols))
-        dchi2 = np.empty((n_draws, n_cols))
-        fisher = np.empty((n_draws, n_cols, n_cols))
-        with device.lock:
-            _lib.check(device.lib.tc_interp_chi2_fisher_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                _lib.as_double_p(x), n_draws, n_gauss_prim,
-                _flags(False, modulate_with_cenocc), _lib.as_double_p(data),
-                _lib.as_double_p(precision), _lib.as_double_p(ngal),
-                _lib.as_double_p(chi2), _lib.as_double_p(dngal),
-                _lib.as_double_p(dchi2), _lib.as_double_p(fisher)))
-        return ngal, chi2, dngal, dchi2, fisher
+        return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
+                               assembias, operands, True)
 
     def fisher_batch(self, theta, x, precision, n_gauss_prim=10,
                      extrapolate=False, modulate_with_cenocc=False,
@@ -704,9 +636,7 @@ class Interpolator:
             modulate_with_cenocc=spec.modulate_with_cenocc,
             assembias=assembias)
         keys = model_keys + tuple(self.keys)
-        return (float(ngal[0]),
-                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
-                fisher[0])
+        return float(ngal[0]), _grad.keyed(dngal[0], keys), fisher[0]
 
     # -- generic models: host callbacks + device contraction per table -----------------
 

@@ -15,6 +15,7 @@ import ctypes
 
 import numpy as np
 
+from . import _grad
 from . import _lib
 from .tabcorr import _flags, _grad_keys, _grad_spec, _grad_theta
 
@@ -182,40 +183,29 @@ class JointLikelihood:
         """
         _zheng07_only(family)
         theta = _grad_theta(theta, assembias)
-        n_draws, n_cols, n = len(theta), theta.shape[1], self.n_r_total
-        ngal, xi = np.empty(n_draws), np.empty((n_draws, n))
-        dngal = np.empty((n_draws, n_cols))
-        dxi = np.empty((n_draws, n_cols, n))
-        device = self.to_device()
-        with device.lock:
-            _lib.check(device.lib.tc_joint_predict_grad_batch(
-                device.handle, _lib.as_double_p(theta), n_cols, n_draws,
-                n_gauss_prim, _flags(False, modulate_with_cenocc, assembias),
-                _lib.as_double_p(ngal), _lib.as_double_p(xi),
-                _lib.as_double_p(dngal), _lib.as_double_p(dxi)))
+        n_draws, n_cols = theta.shape
+        ngal, xi, dngal, dxi = self._grad_call(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias)
         return (ngal, self._split(xi, (n_draws, )), dngal,
                 self._split(dxi, (n_draws, n_cols)))
+
+    def _grad_call(self, theta, n_gauss_prim, modulate_with_cenocc, assembias,
+                   operands=None, want_fisher=False):
+        """The derivative entry for checked draws: the results on the joint
+        axis of ``n_r_total`` entries; the family is in the flags."""
+        return _grad.call(
+            self.to_device(), 'joint', _grad.family_of(assembias),
+            [theta, theta.shape[1], len(theta), n_gauss_prim,
+             _flags(False, modulate_with_cenocc, assembias)],
+            theta.shape[1], (self.n_r_total, ), operands, want_fisher)
 
     def _chi2(self, theta, data, precision, n_gauss_prim,
               modulate_with_cenocc, assembias, want_fisher, family):
         _zheng07_only(family)
         theta = _grad_theta(theta, assembias)
-        data, precision = self._operands(data, precision)
-        n_draws, n_cols = len(theta), theta.shape[1]
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal = np.empty((n_draws, n_cols))
-        dchi2 = np.empty((n_draws, n_cols))
-        fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
-        device = self.to_device()
-        with device.lock:
-            _lib.check(device.lib.tc_joint_chi2_grad_batch(
-                device.handle, _lib.as_double_p(theta), n_cols, n_draws,
-                n_gauss_prim, _flags(False, modulate_with_cenocc, assembias),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                _lib.as_double_p(dngal), _lib.as_double_p(dchi2),
-                _lib.as_double_p(fisher) if want_fisher else None))
-        return ngal, chi2, dngal, dchi2, fisher
+        operands = self._operands(data, precision)
+        return self._grad_call(theta, n_gauss_prim, modulate_with_cenocc,
+                               assembias, operands, want_fisher)
 
     def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
                         modulate_with_cenocc=False, assembias=False,
@@ -224,7 +214,7 @@ class JointLikelihood:
         (`TabCorr.chi2_grad_batch` with ``N`` for ``n_r``): ``ngal, chi2``
         ``(n_draws, )``, ``dngal, dchi2`` ``(n_draws, 5)``."""
         return self._chi2(theta, data, precision, n_gauss_prim,
-                          modulate_with_cenocc, assembias, False, family)[:4]
+                          modulate_with_cenocc, assembias, False, family)
 
     def chi2_fisher_batch(self, theta, data, precision, n_gauss_prim=10,
                           modulate_with_cenocc=False, assembias=False,
@@ -272,7 +262,7 @@ class JointLikelihood:
             modulate_with_cenocc=spec.modulate_with_cenocc,
             assembias=assembias)
         return (float(ngal[0]), [xi[0] for xi in xis],
-                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
+                _grad.keyed(dngal[0], keys),
                 {key: [dxi[0, k] for dxi in dxis]
                  for k, key in enumerate(keys)})
 
@@ -287,7 +277,5 @@ class JointLikelihood:
             theta, data, precision, n_gauss_prim=n_gauss_prim,
             modulate_with_cenocc=spec.modulate_with_cenocc,
             assembias=assembias)
-        return (float(ngal[0]), float(chi2[0]),
-                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
-                {key: float(dchi2[0, k]) for k, key in enumerate(keys)},
-                fisher[0])
+        return (float(ngal[0]), float(chi2[0]), _grad.keyed(dngal[0], keys),
+                _grad.keyed(dchi2[0], keys), fisher[0])

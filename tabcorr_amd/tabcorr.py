@@ -23,6 +23,7 @@ import threading
 
 import numpy as np
 
+from . import _grad
 from . import _lib
 from . import pinned
 from .galtable import GalTypeTable
@@ -763,26 +764,11 @@ class TabCorr:
         (float32 tables, very large mode-auto tables).
         """
         theta = _grad_theta(theta, assembias, family)
-        device = self.to_device()
-        n_draws = len(theta)
-        n_cols = len(_grad_keys(assembias, family))
-        ngal = np.empty(n_draws)
-        xi = np.empty((n_draws, device.n_r))
-        dngal = np.empty((n_draws, n_cols))
-        dxi = np.empty((n_draws, n_cols, device.n_r))
-        entry = (device.lib.tc_predict_grad_leauthaud11_batch
-                 if family == 'leauthaud11'
-                 else device.lib.tc_predict_grad_assembias_batch if assembias
-                 else device.lib.tc_predict_grad_zheng07_batch)
-        with device.lock:
-            _lib.check(entry(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
-                _lib.as_double_p(ngal), _lib.as_double_p(xi),
-                _lib.as_double_p(dngal), _lib.as_double_p(dxi)))
-        shape = tuple(self.tpcf_shape)
-        return (ngal, xi.reshape((n_draws, ) + shape), dngal,
-                dxi.reshape((n_draws, n_cols) + shape))
+        return _grad.call(
+            self.to_device(), 'table', _grad.family_of(assembias, family),
+            [theta, theta.shape[1], len(theta), n_gauss_prim,
+             _flags(False, modulate_with_cenocc)],
+            len(_grad_keys(assembias, family)), self.tpcf_shape)
 
     def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
                         modulate_with_cenocc=False, assembias=False,
@@ -798,55 +784,25 @@ class TabCorr:
         ngal, chi2 : ``(n_draws, )``
         dngal, dchi2 : ``(n_draws, 5)``
         """
-        if assembias or family != 'zheng07':
-            return self._chi2_grad_wide(
-                theta, data, precision, n_gauss_prim, modulate_with_cenocc,
-                False, assembias, family)[:4]
-        theta = _grad_theta(theta)
-        # (the rows of the table's own matrix: a wrong argument is refused
-        # before any device is touched, as a wrong theta is)
-        data, precision = _chi2_operands(data, precision,
-                                         len(self.tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(theta)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal, dchi2 = np.empty((n_draws, 5)), np.empty((n_draws, 5))
-        with device.lock:
-            _lib.check(device.lib.tc_chi2_grad_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                _lib.as_double_p(dngal), _lib.as_double_p(dchi2)))
-        return ngal, chi2, dngal, dchi2
+        return self._likelihood_grad(theta, data, precision, n_gauss_prim,
+                                     modulate_with_cenocc, assembias, family,
+                                     False)
 
-    def _chi2_grad_wide(self, theta, data, precision, n_gauss_prim,
-                        modulate_with_cenocc, want_fisher, assembias, family):
-        """The likelihood gradient of the decorated model or of the
-        Leauthaud11 family, with or without its Fisher matrix: one entry point
-        serves both."""
+    def _likelihood_grad(self, theta, data, precision, n_gauss_prim,
+                         modulate_with_cenocc, assembias, family,
+                         want_fisher):
+        """The arguments of `chi2_grad_batch` and `chi2_fisher_batch`,
+        checked before any device is touched (the rows of the table's own
+        matrix), and their call."""
         theta = _grad_theta(theta, assembias, family)
         data, precision = _chi2_operands(data, precision,
                                          len(self.tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(theta)
-        n_cols = len(_grad_keys(assembias, family))
-        entry = (device.lib.tc_chi2_grad_leauthaud11_batch
-                 if family == 'leauthaud11'
-                 else device.lib.tc_chi2_grad_assembias_batch)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal = np.empty((n_draws, n_cols))
-        dchi2 = np.empty((n_draws, n_cols))
-        fisher = np.empty((n_draws, n_cols, n_cols)) if want_fisher else None
-        with device.lock:
-            _lib.check(entry(
-                device.handle, _lib.as_double_p(theta), theta.shape[1], n_draws,
-                n_gauss_prim, _flags(False, modulate_with_cenocc),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                _lib.as_double_p(dngal), _lib.as_double_p(dchi2),
-                _lib.as_double_p(fisher) if want_fisher else None))
-        return ngal, chi2, dngal, dchi2, fisher
+        return _grad.call(
+            self.to_device(), 'table', _grad.family_of(assembias, family),
+            [theta, theta.shape[1], len(theta), n_gauss_prim,
+             _flags(False, modulate_with_cenocc)],
+            len(_grad_keys(assembias, family)), self.tpcf_shape,
+            (data, precision), want_fisher)
 
     def predict_grad(self, model, n_gauss_prim=10, check_consistency=True,
                      assembias=False):
@@ -877,19 +833,16 @@ class TabCorr:
                 family='leauthaud11')
             columns = _leauthaud11_columns(model)
             return (float(ngal[0]), xi[0],
-                    {key: float(factor * dngal[0, k])
-                     for key, (k, factor) in columns.items()},
-                    {key: factor * dxi[0, k]
-                     for key, (k, factor) in columns.items()})
+                    _grad.keyed(dngal[0], columns=columns),
+                    _grad.keyed(dxi[0], columns=columns))
         keys = _grad_keys(assembias)
         ngal, xi, dngal, dxi = self.predict_batch_grad(
             np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
             n_gauss_prim=n_gauss_prim,
             modulate_with_cenocc=spec.modulate_with_cenocc,
             assembias=assembias)
-        return (float(ngal[0]), xi[0],
-                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
-                {key: dxi[0, k] for k, key in enumerate(keys)})
+        return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], keys),
+                _grad.keyed(dxi[0], keys))
 
     # -- Fisher matrix of the likelihood ---------------------------------------------------
 
@@ -926,27 +879,9 @@ class TabCorr:
         dngal, dchi2 : ``(n_draws, 5)`` -- those of `chi2_grad_batch`, bit for bit
         fisher : ``(n_draws, 5, 5)``
         """
-        if assembias or family != 'zheng07':
-            return self._chi2_grad_wide(
-                theta, data, precision, n_gauss_prim, modulate_with_cenocc,
-                True, assembias, family)
-        theta = _grad_theta(theta)
-        data, precision = _chi2_operands(data, precision,
-                                         len(self.tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(theta)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dngal, dchi2 = np.empty((n_draws, 5)), np.empty((n_draws, 5))
-        fisher = np.empty((n_draws, 5, 5))
-        with device.lock:
-            _lib.check(device.lib.tc_chi2_fisher_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                n_draws, n_gauss_prim, _flags(False, modulate_with_cenocc),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                _lib.as_double_p(dngal), _lib.as_double_p(dchi2),
-                _lib.as_double_p(fisher)))
-        return ngal, chi2, dngal, dchi2, fisher
+        return self._likelihood_grad(theta, data, precision, n_gauss_prim,
+                                     modulate_with_cenocc, assembias, family,
+                                     True)
 
     def fisher_batch(self, theta, precision, n_gauss_prim=10,
                      modulate_with_cenocc=False, assembias=False,
@@ -998,8 +933,8 @@ class TabCorr:
                 family='leauthaud11')
             jacobian = model.device_jacobian()
             return (float(ngal[0]),
-                    {key: float(factor * dngal[0, k]) for key, (k, factor)
-                     in _leauthaud11_columns(model).items()},
+                    _grad.keyed(dngal[0],
+                                columns=_leauthaud11_columns(model)),
                     jacobian.T @ fisher[0] @ jacobian)
         keys = _grad_keys(assembias)
         ngal, dngal, fisher = self.fisher_batch(
@@ -1007,9 +942,7 @@ class TabCorr:
             precision, n_gauss_prim=n_gauss_prim,
             modulate_with_cenocc=spec.modulate_with_cenocc,
             assembias=assembias)
-        return (float(ngal[0]),
-                {key: float(dngal[0, k]) for k, key in enumerate(keys)},
-                fisher[0])
+        return float(ngal[0]), _grad.keyed(dngal[0], keys), fisher[0]
 
     # -- reverse mode at the occupation seam ---------------------------------------------
 

@@ -3,8 +3,8 @@
 // HIP.  Walks the same entry points the C ABI uses (bin permutation and segmentation,
 // chunking, the quadratic-form layout / schedule / table fill / emulation, spline
 // matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort and label-block
-// plan, the choice of the one-launch form) over a sweep of shapes and checks the results against direct
-// evaluations.  Exit status 0 = all
+// plan, the choice of the one-launch form, the slabs of a derivative call) over a sweep of shapes
+// and checks the results against direct evaluations.  Exit status 0 = all
 // checks passed and no sanitizer report (-fno-sanitize-recover aborts on the first).
 //
 //   make -C tools/sanitize && tools/sanitize/host_driver
@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../tabcorr_amd/csrc/fastmath.h"
+#include "../../tabcorr_amd/csrc/grad_call.h"
 #include "../../tabcorr_amd/csrc/hostmath.h"
 #include "../../tabcorr_amd/csrc/kernel_args.h"
 
@@ -451,7 +452,31 @@ static void check_fused_form() {
   EXPECT(one_launch > 300, "only %d queries took a one-launch form", one_launch);
 }
 
+// The slab arithmetic of the derivative entry points (grad_call.h: GradRequest::slab) against the
+// closed forms, up to products far beyond 2^31 elements: every one of them in 64 bits.
+static void check_grad_slabs() {
+  const int64_t begins[] = {0, 1, 1 << 18, (1 << 18) + 17, ((int64_t)1 << 31) - 1,
+                            (int64_t)1 << 31, ((int64_t)1 << 31) + 5, ((int64_t)1 << 33) + 3};
+  for (int n_params : {tc::kGradParams, tc::kGradParamsAssembias, tc::kGradParamsLeauthaud11})
+    for (int n_extra : {0, 1, 3})
+      for (int n_r : {1, 2, 19, 38, 1000})
+        for (int likelihood = 0; likelihood < 2; ++likelihood)
+          for (int64_t begin : begins) {
+            int64_t at[7];
+            tc::host::grad_slab_offsets(n_params, n_extra, n_r, likelihood != 0, begin, at);
+            const int64_t cols = n_params + n_extra, wide = likelihood ? 1 : n_r;
+            EXPECT(at[0] == begin * tc::grad_theta_columns(n_params) &&
+                       at[1] == (n_extra ? begin * n_extra : -1) && at[2] == begin &&
+                       at[3] == begin * cols && at[4] == begin * wide &&
+                       at[5] == begin * cols * wide &&
+                       at[6] == (likelihood ? begin * cols * cols : -1),
+                   "slab offsets of %d + %d columns, %d rows, likelihood %d at draw %lld", n_params,
+                   n_extra, n_r, likelihood, (long long)begin);
+          }
+}
+
 int main() {
+  check_grad_slabs();
   check_quadrature();
   check_splines();
   check_plans();
