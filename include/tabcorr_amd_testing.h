@@ -53,6 +53,17 @@ int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n
 int tc_debug_grad_slab(int n_params, int n_extra, int n_r, int likelihood, int64_t begin,
                        int64_t* offsets);
 
+/* The chunks of a synchronous host-array prediction or likelihood (tabcorr_amd/csrc/hostmath.h:
+ * plan_sync_chunks) -- no device needed -- of n_draws draws with out_bytes_per_draw bytes of
+ * results per draw, second_cols of them doubles of the second array.  options: the values of
+ * "sync_chunks", "sync_stagger", "pipeline" (three ints); n_lanes: the handle's lanes; call: bit 0
+ * option "ordered", 1 a likelihood, 2 a float32 table, 3 an interpolator, 4 mode cross.
+ * n_chunks = 0: the serial path; else chunk k holds the draws [begins[k], begins[k + 1]) (begins:
+ * capacity 65), every chunk at least one; staggered: the chunks' kernels run one after the other. */
+int tc_debug_sync_chunks(int64_t n_draws, int64_t out_bytes_per_draw, int64_t second_cols,
+                         const int* options, int n_lanes, unsigned call, int* n_chunks,
+                         int64_t* begins, int* staggered);
+
 /* The node arithmetic of the Leauthaud11 gradient kernels (tabcorr_amd/csrc/grad_leauthaud11.h)
  * on the host, for one draw theta (14 columns) and n halo masses: log_mstar (n) the root of the
  * stellar-to-halo mass relation, n_cen (n) and dn_cen (n, 11) the centrals' occupation and its

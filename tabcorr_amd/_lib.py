@@ -63,6 +63,8 @@ SIGNATURES = {
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_grad_lds': [ctypes.c_int] * 7 + [c_int64_p],
     'tc_debug_grad_slab': [ctypes.c_int] * 4 + [ctypes.c_int64, c_int64_p],
+    'tc_debug_sync_chunks': [ctypes.c_int64] * 3 + [c_int_p, ctypes.c_int, ctypes.c_uint,
+                                                    c_int_p, c_int64_p, c_int_p],
     'tc_debug_leauthaud11_node_grad': [c_double_p, ctypes.c_int, ctypes.c_int64, c_double_p,
                                        c_double_p, c_double_p, c_double_p, c_double_p,
                                        c_double_p],
@@ -247,6 +249,14 @@ for _kind, _prefix, _families in (('table', 'tc_', ('zheng07', 'assembias', 'lea
                 GRAD_ENTRIES[_kind, _key, _form] = '%s%s%s_batch' % (_prefix, _entry, _stem)
 GRAD_OPTIONAL_FISHER = {GRAD_ENTRIES[_key] for _key in GRAD_ENTRIES if _key[2] == 'chi2' and
                         GRAD_ENTRIES[_key] == GRAD_ENTRIES[_key[:2] + ('fisher', )]}
+
+
+# The forward entries: (handle kind, form, route) -> symbol.
+FORWARD_ENTRIES = {
+    (_kind, _form, _route): 'tc_%s%s_zheng07_batch%s' % (_prefix, _form, _suffix)
+    for _kind, _prefix in (('table', ''), ('interp', 'interp_'))
+    for _form in ('predict', 'chi2')
+    for _route, _suffix in (('host', ''), ('device', '_device'), ('async', '_async'))}
 
 
 def _derivative_signatures():

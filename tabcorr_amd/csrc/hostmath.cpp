@@ -814,6 +814,59 @@ int fused_lds_bytes(int dens_rows, int waves, int draws) {
           fused_scratch_doubles(waves)) * 8;
 }
 
+// The chunks of a synchronous host-array call (predict_call.h: forward_chunked runs them; what was
+// measured for each rule: profiles/r05_notes.md section 4, profiles/r06_notes.md section 10).
+SyncChunkPlan plan_sync_chunks(const SyncChunkQuery& q) {
+  SyncChunkPlan plan;
+  const int64_t n_draws = q.n_draws, out_bytes = n_draws * q.out_bytes_per_draw;
+  if (q.sync_chunks < 0 || !q.pipeline || q.n_lanes < 2 || q.chain || n_draws < 1) return plan;
+  int64_t n_chunks = 0;
+  if (q.sync_chunks >= 1) {
+    n_chunks = std::min<int64_t>(std::min(q.sync_chunks, 64), (n_draws + 63) / 64);
+  } else if (n_draws < 2048) {
+    return plan;
+  } else if (q.interpolator && q.cross) {
+    // (one piece through the asynchronous path; two and more chunks of an interpolator's one-launch
+    // form take 217-470 us per 10^4 draws from one batch of calls to the next, one a steady 245)
+    n_chunks = 1;
+  } else {
+    // auto: about a megabyte of results per chunk, 2 .. 8 chunks of at least 1024 draws (all
+    // chunks' kernels share the chip and finish together: more buy nothing for small results)
+    n_chunks = std::min<int64_t>(std::min<int64_t>(8, n_draws / 1024),
+                                 std::max<int64_t>(2, out_bytes >> 20));
+  }
+  const int64_t chunk = ((n_draws + n_chunks - 1) / n_chunks + 63) / 64 * 64;
+  n_chunks = (n_draws + chunk - 1) / chunk;
+  int64_t begins[65];
+  for (int k = 0; k <= n_chunks; ++k) begins[k] = std::min<int64_t>(n_draws, k * chunk);
+  // Large results (16 MB and more, 2 KB per draw and more, float32 tables -- only there do the
+  // transfers weigh against the kernels): the chunks' kernels run ONE AFTER THE OTHER (events
+  // between the lanes), chunk k - 1 travelling and being copied while chunk k computes, and the
+  // chunks SHRINK towards the end, so that little is left exposed behind the last kernel.
+  plan.staggered = !q.interpolator && q.sync_stagger != 0 && out_bytes >= ((int64_t)16 << 20) &&
+                   q.second_cols * 8 >= 2048 && n_chunks >= 4 && !q.likelihood && q.float32;
+  if (plan.staggered) {
+    if (q.sync_chunks == 0) n_chunks = std::min<int64_t>(n_chunks, 6);
+    double share[64];
+    const double ratio = std::pow(0.01 * q.sync_stagger, 1.0 / (n_chunks - 1));
+    double total = 0.0, done = 0.0;
+    for (int k = 0; k < n_chunks; ++k) total += share[k] = std::pow(ratio, k);
+    for (int k = 0; k < n_chunks; ++k) {
+      done += share[k];
+      const int64_t end =
+          k + 1 == n_chunks
+              ? n_draws
+              : std::min<int64_t>(n_draws, ((int64_t)(n_draws * done / total) + 63) / 64 * 64);
+      begins[k + 1] = std::max(end, begins[k]);
+    }
+  }
+  // (rounding up to 64 can make two boundaries coincide: a chunk without draws would launch
+  // nothing and leave the event its successor waits for unrecorded)
+  for (int k = 1; k <= n_chunks; ++k)
+    if (begins[k] > plan.begins[plan.n_chunks]) plan.begins[++plan.n_chunks] = begins[k];
+  return plan;
+}
+
 // One launch per slab of draws (predict_fused_kernel): float64 quadratic form with one r tile,
 // densities of a workgroup's draws within the LDS.  In order of precedence: what the kernel
 // does not serve; the latency form; option "deterministic" = 2; a measured choice; the rule for

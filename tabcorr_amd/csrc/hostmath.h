@@ -334,6 +334,25 @@ struct FusedForm {
 };
 FusedForm choose_fused_form(const FusedQuery& query);
 
+// What the chunk plan of a synchronous host-array call reads (internal.h: plan_forward_chunks).
+struct SyncChunkQuery {
+  int64_t n_draws = 0;
+  int64_t out_bytes_per_draw = 0;   // result bytes of a draw: 8 (ngal_cols + second_cols)
+  int64_t second_cols = 0;          // doubles of a draw's second array
+  int sync_chunks = 0, sync_stagger = 0, pipeline = 1;   // options (internal.h: Tuning)
+  int n_lanes = 2;
+  bool chain = false;               // option "ordered"
+  bool likelihood = false, float32 = false, interpolator = false, cross = false;
+};
+// The chunks [begins[k], begins[k + 1]) of the call, each of at least one draw, every inner
+// boundary a multiple of 64; n_chunks == 0: the serial path.  staggered: see plan_sync_chunks.
+struct SyncChunkPlan {
+  int n_chunks = 0;
+  int64_t begins[65] = {0};
+  bool staggered = false;
+};
+SyncChunkPlan plan_sync_chunks(const SyncChunkQuery& query);
+
 // The re-laid-out matrix of a layout: (n_rtiles, n_units, (n_u + 1) / 2, 64 lanes, 2)
 // doubles with the pair prefactor folded in; `matrix` is the reference's (n_r, n_pairs)
 // tpcf_matrix in float64 or float32, `perm` the library's bin order.

@@ -349,7 +349,7 @@ struct Tuning {
   // kernel directly 57 / the likelihood 47.5; ALL results stored directly 66 (1.5 MB of
   // 64-byte writes over PCIe from the shader cores lose to the copy engine); downloads on a
   // stream of their own 91-105 (cross-stream events), more lanes 72-80 (four hardware queues).
-  // synchronous host calls as overlapping chunks of draws (table.cpp: predict_chunked):
+  // synchronous host calls as overlapping chunks of draws (hostmath.h: plan_sync_chunks):
   // sync_chunks 0 auto (from 2048 draws on), -1 never, N >= 1 that many; sync_form: draws per
   // workgroup of the one-launch form the chunks take where it serves the table (so that the
   // result does not depend on the number of chunks; 0: whatever a pipelined call of the chunk's
@@ -453,6 +453,10 @@ struct Tuning {
 }  // namespace host
 }  // namespace tc
 
+// (behind the runtime and the staging buffers: a forward call's request, ticket ring and chunks)
+#define TC_INTERNAL_HANDLES 1
+#include "predict_call.h"
+
 using tc::AutoChoice;      // (hostmath.h)
 
 struct tc_table {
@@ -499,7 +503,7 @@ struct tc_table {
   tc::host::CrossFused cross_fused, cross_fused_wide;
   tc::host::GradTable grad;      // gradient entry points
   std::vector<hipEvent_t> chunk_events;    // between the chunks of a synchronous host call with
-                                           // large results (table.cpp: predict_chunked)
+                                           // large results (a staggered plan_sync_chunks)
   bool quad = false;
   tc::QuadTiling quad_tiling;
   tc::host::QuadTable quad_by_type, quad_total;
@@ -543,15 +547,7 @@ struct tc_table {
   // costs 0.3 us per step on prior draws and 3 us on posterior-like ones, whose short
   // occupation kernels then wait for a neighbour's finalisation: tools/archive/r03_clustered.py).
   bool chain = false;
-  // Tickets of the asynchronous host calls (tc_*_async): a ring of events; a ticket whose
-  // slot was reused is older than every lane's current work.
-  struct Ticket {
-    hipEvent_t done = nullptr;
-    int64_t id = -1;
-  };
-  static constexpr int kMaxTickets = 64;
-  Ticket tickets[kMaxTickets];
-  int64_t next_ticket = 0;
+  tc::host::Tickets tickets;         // of the asynchronous host calls (tc_*_async)
   uint64_t device_calls = 0;         // calls that took a lane of the rotation (next_lane)
   tc::host::DeviceBuffer theta, out_ngal, out_xi, occupation, trace, wave_trace;
   tc::host::Chi2Operands chi2;               // data vector + precision matrix of chi2 calls
@@ -659,7 +655,7 @@ struct Call {
   int cross_target = 0;
   bool sync_spread = false;
   // options "fused_draws" and "fused_min_draws" as this call sees them (the chunks of a
-  // synchronous call take one form whatever their size: table.cpp, predict_chunked)
+  // synchronous call take one form whatever their size: table.cpp, TableForward::hints)
   int fused_draws = 0, fused_min_draws = 0;
 };
 // The one rule for a call's lane: lane 0 for a pinned call and with option "pipeline" off, else
@@ -687,6 +683,26 @@ inline Call make_call(tc_table* t, bool pinned) {
 // ... and what a device-pointer call WOULD carry, taking no lane (questions about forms)
 inline Call probe_call(const tc_table* t, bool pinned = false) {
   return make_call(t, 0, pinned, t->n_lanes);
+}
+
+// The request of a forward entry point of a handle whose first (or only) table is `t0`, in the
+// order of the C arguments (n_extra, x: an interpolator's axes).
+inline PredictRequest forward_request(const tc_table* t0, const double* theta, int n_theta,
+                                      int n_extra, const double* x, int64_t n_draws, int n_gauss,
+                                      unsigned flags, double* ngal, double* second,
+                                      bool likelihood) {
+  return PredictRequest{n_theta, n_extra, n_gauss, flags, n_draws, t0 ? t0->n_r : 0,
+                        t0 ? t0->plan.n_components : 0, theta, x, ngal, second, likelihood};
+}
+// The chunks of a synchronous host-array request on such a handle with `n_lanes` lanes (its
+// options are t0's; chain: option "ordered", which an interpolator does not read).
+inline tc::SyncChunkPlan plan_forward_chunks(const tc_table* t0, int n_lanes, bool chain,
+                                             bool interpolator, const PredictRequest& request) {
+  return tc::plan_sync_chunks(
+      {request.n_draws, (int64_t)request.out_cols() * 8, (int64_t)request.second_cols(),
+       t0->tuning.sync_chunks, t0->tuning.sync_stagger, t0->tuning.pipeline, n_lanes, chain,
+       request.likelihood, t0->compute_dtype == TC_DTYPE_F32, interpolator,
+       t0->mode == TC_MODE_CROSS});
 }
 
 // ---- launch layer (launch.hip) --------------------------------------------------------
@@ -893,5 +909,4 @@ int copy_out(PinnedBuffer* stage, double* ngal, size_t ngal_count, const void* d
 }  // namespace tc
 
 // (behind the handles: the request of a derivative call, its staging path and its entry sequence)
-#define TC_INTERNAL_HANDLES 1
 #include "grad_call.h"

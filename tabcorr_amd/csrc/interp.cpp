@@ -77,9 +77,7 @@ struct tc_interp {
   SingleWorkspace single_ws;                // un-batched calls
   std::map<std::pair<int, int>, std::unique_ptr<DeviceChunking>> chunkings;
   CrossFused cross_fused, cross_fused_wide; // mode cross: one launch per batch (launch.hip)
-  // asynchronous host calls (tc_interp_*_async): tickets as for a table handle
-  tc_table::Ticket tickets[tc_table::kMaxTickets];
-  int64_t next_ticket = 0;
+  Tickets tickets;                          // of the asynchronous host calls (tc_interp_*_async)
 };
 
 namespace {
@@ -591,8 +589,7 @@ int tc_interp_destroy(tc_interp* it) {
   it->h_in.release();
   it->h_out.release();
   it->single_ws.buffer.release();
-  for (tc_table::Ticket& ticket : it->tickets)
-    if (ticket.done) (void)hipEventDestroy(ticket.done);
+  it->tickets.release();
   for (tc_interp::Lane& lane : it->lanes)
     if (lane.stream) (void)hipStreamDestroy(lane.stream);
   delete it;
@@ -756,58 +753,31 @@ int interp_predict_one(tc_interp* it, const double* theta, int n_theta, const do
 
 }  // namespace
 
-namespace {
-int interp_async(tc_interp* it, const double* theta, int n_theta, const double* x,
-                 int64_t n_draws, int n_gauss, unsigned flags, const double* data,
-                 const double* precision, double* ngal, double* second, bool chi2,
-                 int64_t* ticket_out, int cross_target = -1);
+// ---- forward calls (predict_call.h: PredictRequest, forward_chunked, forward_zero_copy) -------
 
-// A synchronous host-array call as overlapping chunks of draws (table.cpp: predict_chunked has
-// the reasoning): chunk k's draws and extra parameters are staged and queued on lane k % lanes
-// while chunk k - 1 computes, its results are copied to the caller's arrays (on four host
-// threads) while later chunks compute and travel.  The interpolator's kernels cut a draw's
+namespace {
+int interp_async(tc_interp* it, const PredictRequest& request, const double* data,
+                 const double* precision, int64_t* ticket_out, const Call* chunk);
+
+// An interpolator as forward_chunked and forward_zero_copy see it.  Its kernels cut a draw's
 // sums where the batch size puts them: chunks agree with one piece to rounding.
-int interp_chunked(tc_interp* it, const double* theta, int n_theta, const double* x,
-                   int64_t n_draws, int n_gauss, unsigned flags, double* ngal, double* xi,
-                   int n_chunks) {
-  tc_table* t0 = it->tables[0];
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  const size_t ngal_cols = separate ? 2 : 1;
-  const size_t xi_cols = (size_t)(separate ? t0->plan.n_components : 1) * t0->n_r;
-  const size_t in_cols = (size_t)n_theta + it->n_dim;
-  int status = it->h_in.reserve((size_t)n_draws * in_cols * 8);
-  if (status == TC_OK) status = it->h_out.reserve((size_t)n_draws * (ngal_cols + xi_cols) * 8);
-  if (status != TC_OK) return status;
-  const int64_t chunk = ((n_draws + n_chunks - 1) / n_chunks + 63) / 64 * 64;
-  n_chunks = (int)((n_draws + chunk - 1) / chunk);
-  TC_CHECK(n_chunks <= 64, "internal: too many chunks");
-  int64_t tickets[64];
-  double* h_in = (double*)it->h_in.ptr;
-  double* h_out = (double*)it->h_out.ptr;
-  for (int k = 0; k < n_chunks && status == TC_OK; ++k) {
-    const int64_t begin = k * chunk, n = std::min(chunk, n_draws - begin);
-    double* in = h_in + begin * in_cols;          // [theta | x] of the chunk
-    memcpy(in, theta + begin * n_theta, (size_t)n * n_theta * 8);
-    memcpy(in + n * n_theta, x + begin * it->n_dim, (size_t)n * it->n_dim * 8);
-    double* out = h_out + begin * (ngal_cols + xi_cols);
-    status = interp_async(it, in, n_theta, in + n * n_theta, n, n_gauss, flags, nullptr, nullptr,
-                          out, out + n * ngal_cols, false, &tickets[k], 512 / n_chunks);
-    if (status != TC_OK) n_chunks = k;
+struct InterpForward {
+  static constexpr bool kThreadedCopyOut = false;
+  tc_interp* it;
+  tc_interp* handle() const { return it; }
+  Call hints(const PredictRequest&, const tc::SyncChunkPlan&) const { return Call(); }
+  std::vector<hipEvent_t>* chunk_events() const { return nullptr; }   // (never staggered)
+  int enqueue(const PredictRequest& part, const Call& hints, hipEvent_t, hipEvent_t,
+              int64_t* ticket) const {
+    return interp_async(it, part, nullptr, nullptr, ticket, &hints);
   }
-  for (int k = 0; k < n_chunks; ++k) {
-    const int64_t begin = k * chunk, n = std::min(chunk, n_draws - begin);
-    const int waited = tc_interp_wait(it, tickets[k]);
-    if (waited != TC_OK) {
-      (void)tc_interp_synchronize(it);
-      return waited;
-    }
-    if (status != TC_OK) continue;
-    const double* out = h_out + begin * (ngal_cols + xi_cols);
-    memcpy(ngal + begin * ngal_cols, out, (size_t)n * ngal_cols * 8);
-    parallel_copy(xi + begin * xi_cols, out + n * ngal_cols, (size_t)n * xi_cols * 8);
+  int synchronize() const { return tc_interp_synchronize(it); }
+  int run(const PredictRequest& staged) const {
+    return interp_predict_device(it, interp_call(it, /*pinned=*/true), staged.theta, staged.n_theta,
+                                 staged.x, staged.n_draws, staged.n_gauss, staged.flags,
+                                 staged.ngal, staged.second);
   }
-  return status;
-}
+};
 }  // namespace
 
 int tc_interp_predict_zheng07_batch(tc_interp* it, const double* theta, int n_theta,
@@ -833,70 +803,29 @@ int tc_interp_predict_zheng07_batch(tc_interp* it, const double* theta, int n_th
   if (!invariant && single_draw_eligible(it->tables[0], n_draws, n_gauss, flags) &&
       (int64_t)it->n_tables * single_draw_blocks(it->tables[0]) <= 8192)
     return interp_predict_one(it, theta, n_theta, x, n_gauss, flags, ngal, xi);
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  const int n_comp = separate ? it->tables[0]->plan.n_components : 1;
-  const size_t ngal_count = (size_t)n_draws * (separate ? 2 : 1);
-  const size_t xi_count = (size_t)n_draws * n_comp * it->tables[0]->n_r;
-  const size_t theta_count = (size_t)n_draws * n_theta, x_count = (size_t)n_draws * it->n_dim;
+  const PredictRequest request = forward_request(it->tables[0], theta, n_theta, it->n_dim, x,
+                                                 n_draws, n_gauss, flags, ngal, xi, false);
   // small and medium calls: the kernels address page-locked host buffers directly
-  // (table.cpp: tc_predict_zheng07_batch)
-  if ((theta_count + x_count + ngal_count + xi_count) * 8 <= zero_copy_limit() &&
-      it->h_in.reserve((theta_count + x_count) * 8) == TC_OK &&
-      it->h_out.reserve((ngal_count + xi_count) * 8) == TC_OK) {
-    double* in = (double*)it->h_in.ptr;
-    double* out = (double*)it->h_out.ptr;
-    memcpy(in, theta, theta_count * 8);
-    memcpy(in + theta_count, x, x_count * 8);
-    status = interp_predict_device(it, interp_call(it, /*pinned=*/true), in, n_theta,
-                                   in + theta_count, n_draws, n_gauss, flags, out,
-                                   out + ngal_count);
-    if (status != TC_OK) return status;
-    TC_HIP(hipStreamSynchronize(it->stream));
-    memcpy(ngal, out, ngal_count * 8);
-    memcpy(xi, out + ngal_count, xi_count * 8);
-    return TC_OK;
-  }
-  {
-    // (option "sync_chunks" of the first table: 0 = 2 .. 8 chunks of about a megabyte of results
-    // from 2048 draws on, N >= 1 that many, -1 the serial path below)
-    const tc_table* t0 = it->tables[0];
-    int n_chunks = 0;
-    if (t0->tuning.sync_chunks >= 0 && t0->tuning.pipeline && it->n_lanes >= 2) {
-      if (t0->tuning.sync_chunks >= 1)
-        n_chunks = (int)std::min<int64_t>(t0->tuning.sync_chunks, (n_draws + 63) / 64);
-      else if (n_draws >= 2048 && t0->mode == TC_MODE_CROSS)
-        // (one piece through the asynchronous path: staging, kernels that store the results
-        // themselves, the copy on four threads.  Two and more chunks of an interpolator's
-        // one-launch form take 217-470 us per 10^4 draws of the AbacusSummit fixture from one
-        // batch of calls to the next -- the runtime's mapping of the lanes' streams to hardware
-        // queues is the suspect --, one chunk a steady 245; a single table's chunks are steady:
-        // 168 -> 143, tools/r05_sync_chunks.py)
-        n_chunks = 1;
-      else if (n_draws >= 2048)
-        n_chunks = (int)std::min<int64_t>(
-            std::min<int64_t>(8, n_draws / 1024),
-            std::max<int64_t>(2, (int64_t)((ngal_count + xi_count) * 8 >> 20)));
-    }
-    if (n_chunks > 0)
-      return interp_chunked(it, theta, n_theta, x, n_draws, n_gauss, flags, ngal, xi, n_chunks);
-  }
-  status = it->theta.reserve((size_t)n_draws * n_theta * 8, it->stream);
-  if (status == TC_OK) status = it->x.reserve((size_t)n_draws * it->n_dim * 8, it->stream);
-  if (status == TC_OK) status = it->out_ngal.reserve(ngal_count * 8, it->stream);
-  if (status == TC_OK) status = it->out_xi.reserve(xi_count * 8, it->stream);
+  const InterpForward forward{it};
+  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
+  // (option "sync_chunks" of the first table; -1: the serial path below)
+  const tc::SyncChunkPlan plan =
+      plan_forward_chunks(it->tables[0], it->n_lanes, false, true, request);
+  if (plan.n_chunks > 0) return forward_chunked(forward, request, plan);
+  status = it->theta.reserve(request.theta_bytes(), it->stream);
+  if (status == TC_OK) status = it->x.reserve(request.x_bytes(), it->stream);
+  if (status == TC_OK) status = it->out_ngal.reserve(request.ngal_count() * 8, it->stream);
+  if (status == TC_OK) status = it->out_xi.reserve(request.second_count() * 8, it->stream);
   if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, (size_t)n_draws * n_theta * 8,
-                        hipMemcpyHostToDevice, it->stream));
-  TC_HIP(hipMemcpyAsync(it->x.ptr, x, (size_t)n_draws * it->n_dim * 8,
-                        hipMemcpyHostToDevice, it->stream));
-  status = interp_predict_device(it, interp_call(it, /*pinned=*/true),
-                                 (const double*)it->theta.ptr, n_theta, (const double*)it->x.ptr,
-                                 n_draws, n_gauss, flags, (double*)it->out_ngal.ptr,
-                                 (double*)it->out_xi.ptr);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(ngal, it->out_ngal.ptr, ngal_count * 8, hipMemcpyDeviceToHost,
+  TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, request.theta_bytes(), hipMemcpyHostToDevice,
                         it->stream));
-  TC_HIP(hipMemcpyAsync(xi, it->out_xi.ptr, xi_count * 8, hipMemcpyDeviceToHost,
+  TC_HIP(hipMemcpyAsync(it->x.ptr, x, request.x_bytes(), hipMemcpyHostToDevice, it->stream));
+  status = forward.run(request.on((const double*)it->theta.ptr, (const double*)it->x.ptr,
+                                  (double*)it->out_ngal.ptr, (double*)it->out_xi.ptr));
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(ngal, it->out_ngal.ptr, request.ngal_count() * 8, hipMemcpyDeviceToHost,
+                        it->stream));
+  TC_HIP(hipMemcpyAsync(xi, it->out_xi.ptr, request.second_count() * 8, hipMemcpyDeviceToHost,
                         it->stream));
   TC_HIP(hipStreamSynchronize(it->stream));
   return TC_OK;
@@ -929,89 +858,80 @@ int tc_interp_chi2_zheng07_batch(tc_interp* it, const double* theta, int n_theta
   if (n_draws == 0) return TC_OK;
   TC_CHECK(x && data && precision && ngal && chi2, "NULL pointer");
   TC_HIP(hipSetDevice(it->device));
-  const size_t theta_bytes = (size_t)n_draws * n_theta * 8;
-  const size_t x_bytes = (size_t)n_draws * it->n_dim * 8;
-  status = it->theta.reserve(theta_bytes, it->stream);
-  if (status == TC_OK) status = it->x.reserve(x_bytes, it->stream);
-  if (status == TC_OK) status = it->out_ngal.reserve((size_t)n_draws * 2 * 8, it->stream);
+  const PredictRequest request = forward_request(it->tables[0], theta, n_theta, it->n_dim, x,
+                                                 n_draws, n_gauss, flags, ngal, chi2, true);
+  status = it->theta.reserve(request.theta_bytes(), it->stream);
+  if (status == TC_OK) status = it->x.reserve(request.x_bytes(), it->stream);
+  if (status == TC_OK) status = it->out_ngal.reserve(request.out_bytes(), it->stream);
   if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, theta_bytes, hipMemcpyHostToDevice, it->stream));
-  TC_HIP(hipMemcpyAsync(it->x.ptr, x, x_bytes, hipMemcpyHostToDevice, it->stream));
+  TC_HIP(hipMemcpyAsync(it->theta.ptr, theta, request.theta_bytes(), hipMemcpyHostToDevice,
+                        it->stream));
+  TC_HIP(hipMemcpyAsync(it->x.ptr, x, request.x_bytes(), hipMemcpyHostToDevice, it->stream));
   double* d_ngal = (double*)it->out_ngal.ptr;
-  double* d_chi2 = d_ngal + n_draws;
+  double* d_chi2 = d_ngal + request.ngal_count();
   TC_CHECK(!(flags & TC_FLAG_SEPARATE_GAL_TYPE),
            "chi2 is defined for the total correlation function only");
   status = interp_chi2_device(it, interp_call(it, /*pinned=*/true), (const double*)it->theta.ptr,
                               n_theta, (const double*)it->x.ptr, n_draws, n_gauss, flags, data,
                               precision, d_ngal, d_chi2);
   if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(ngal, d_ngal, (size_t)n_draws * 8, hipMemcpyDeviceToHost, it->stream));
-  TC_HIP(hipMemcpyAsync(chi2, d_chi2, (size_t)n_draws * 8, hipMemcpyDeviceToHost, it->stream));
+  TC_HIP(hipMemcpyAsync(ngal, d_ngal, request.ngal_count() * 8, hipMemcpyDeviceToHost,
+                        it->stream));
+  TC_HIP(hipMemcpyAsync(chi2, d_chi2, request.second_count() * 8, hipMemcpyDeviceToHost,
+                        it->stream));
   TC_HIP(hipStreamSynchronize(it->stream));
   return TC_OK;
 }
 
 namespace {
 
-int interp_async(tc_interp* it, const double* theta, int n_theta, const double* x,
-                 int64_t n_draws, int n_gauss, unsigned flags, const double* data,
-                 const double* precision, double* ngal, double* second, bool chi2,
-                 int64_t* ticket_out, int cross_target) {
-  TC_CHECK(it != nullptr, "interp handle is NULL");
-  tc_table* t0 = it->tables[0];
-  int status = check_predict_args(t0, theta, n_theta, n_draws, n_gauss, flags);
+int interp_async(tc_interp* it, const PredictRequest& r, const double* data,
+                 const double* precision, int64_t* ticket_out, const Call* chunk) {
+  int status = check_predict_args(it->tables[0], r.theta, r.n_theta, r.n_draws, r.n_gauss, r.flags);
   if (status != TC_OK) return status;
+  const int64_t n_draws = r.n_draws;
+  const bool chi2 = r.likelihood;
   TC_CHECK(ticket_out != nullptr, "ticket is NULL");
-  TC_CHECK(n_draws == 0 || (x && ngal && second), "NULL pointer");
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  TC_CHECK(!(chi2 && separate), "chi2 is defined for the total correlation function only");
+  TC_CHECK(n_draws == 0 || (r.x && r.ngal && r.second), "NULL pointer");
+  TC_CHECK(!(chi2 && r.separate()), "chi2 is defined for the total correlation function only");
   TC_CHECK(!chi2 || (data && precision), "NULL pointer");
-  const int n_comp = separate ? t0->plan.n_components : 1;
-  const size_t ngal_count = (size_t)n_draws * (separate ? 2 : 1);
-  const size_t second_count = chi2 ? (size_t)n_draws : (size_t)n_draws * n_comp * t0->n_r;
-  const size_t theta_count = (size_t)n_draws * n_theta, x_count = (size_t)n_draws * it->n_dim;
-  // (cross_target >= 0: a chunk of a synchronous call -- Call::cross_target -- in the library's
-  // own page-locked staging areas)
-  TC_CHECK(n_draws == 0 || cross_target >= 0 ||
-               (is_pinned(theta, theta_count * 8) && is_pinned(x, x_count * 8) &&
-                is_pinned(ngal, ngal_count * 8) && is_pinned(second, second_count * 8)),
+  const size_t ngal_count = r.ngal_count(), second_count = r.second_count();
+  // (chunk: a chunk of a synchronous call -- what it carries of a Call is its cross_target -- in
+  // the library's own page-locked staging areas)
+  TC_CHECK(n_draws == 0 || chunk != nullptr ||
+               (is_pinned(r.theta, r.theta_bytes()) && is_pinned(r.x, r.x_bytes()) &&
+                is_pinned(r.ngal, ngal_count * 8) && is_pinned(r.second, second_count * 8)),
            "asynchronous calls need page-locked buffers (tc_host_alloc / tc_host_register)");
   TC_HIP(hipSetDevice(it->device));
   // everything of a call -- upload, kernels, download, the ticket's event -- on the next lane's
   // stream: the lanes overlap each other's transfers and kernels
   Call call = interp_call(it, /*pinned=*/false);
-  call.cross_target = std::max(0, cross_target);
+  call.cross_target = chunk != nullptr ? chunk->cross_target : 0;
   tc_interp::Lane& L = it->lanes[call.lane];
   hipStream_t last = L.stream;
   if (n_draws > 0) {
-    status = L.stage_out.reserve((ngal_count + second_count) * 8, L.stream);
-    if (status == TC_OK) status = L.stage_in.reserve((theta_count + x_count) * 8, L.stream);
+    status = L.stage_out.reserve(r.out_bytes(), L.stream);
+    if (status == TC_OK) status = L.stage_in.reserve(r.in_bytes(), L.stream);
     if (status != TC_OK) return status;
     double* d_theta = (double*)L.stage_in.ptr;
-    double* d_x = d_theta + theta_count;
+    double* d_x = d_theta + n_draws * r.n_theta;
     double* d_ngal = (double*)L.stage_out.ptr;
     double* d_second = d_ngal + ngal_count;
     {
       Range range("upload");
-      TC_HIP(hipMemcpyAsync(d_theta, theta, theta_count * 8, hipMemcpyHostToDevice, L.stream));
-      TC_HIP(hipMemcpyAsync(d_x, x, x_count * 8, hipMemcpyHostToDevice, L.stream));
+      TC_HIP(hipMemcpyAsync(d_theta, r.theta, r.theta_bytes(), hipMemcpyHostToDevice, L.stream));
+      TC_HIP(hipMemcpyAsync(d_x, r.x, r.x_bytes(), hipMemcpyHostToDevice, L.stream));
     }
-    status = chi2 ? interp_chi2_device(it, call, d_theta, n_theta, d_x, n_draws, n_gauss, flags,
-                                       data, precision, d_ngal, d_second)
-                  : interp_predict_device(it, call, d_theta, n_theta, d_x, n_draws, n_gauss,
-                                          flags, d_ngal, d_second);
+    status = chi2 ? interp_chi2_device(it, call, d_theta, r.n_theta, d_x, n_draws, r.n_gauss,
+                                       r.flags, data, precision, d_ngal, d_second)
+                  : interp_predict_device(it, call, d_theta, r.n_theta, d_x, n_draws, r.n_gauss,
+                                          r.flags, d_ngal, d_second);
     if (status != TC_OK) return status;
     Range range("download");
-    TC_HIP(hipMemcpyAsync(ngal, d_ngal, ngal_count * 8, hipMemcpyDeviceToHost, L.stream));
-    TC_HIP(hipMemcpyAsync(second, d_second, second_count * 8, hipMemcpyDeviceToHost, L.stream));
+    TC_HIP(hipMemcpyAsync(r.ngal, d_ngal, ngal_count * 8, hipMemcpyDeviceToHost, L.stream));
+    TC_HIP(hipMemcpyAsync(r.second, d_second, second_count * 8, hipMemcpyDeviceToHost, L.stream));
   }
-  tc_table::Ticket& slot = it->tickets[it->next_ticket % tc_table::kMaxTickets];
-  if (slot.done == nullptr)
-    TC_HIP(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-  slot.id = it->next_ticket++;
-  TC_HIP(hipEventRecord(slot.done, last));
-  *ticket_out = slot.id;
-  return TC_OK;
+  return it->tickets.issue(last, ticket_out);
 }
 
 }  // namespace
@@ -1020,8 +940,10 @@ int tc_interp_predict_zheng07_batch_async(tc_interp* it, const double* theta, in
                                           const double* x, int64_t n_draws, int n_gauss,
                                           unsigned flags, double* ngal, double* xi,
                                           int64_t* ticket) {
-  return interp_async(it, theta, n_theta, x, n_draws, n_gauss, flags, nullptr, nullptr, ngal, xi,
-                      false, ticket);
+  TC_CHECK(it != nullptr, "interp handle is NULL");
+  return interp_async(it, forward_request(it->tables[0], theta, n_theta, it->n_dim, x, n_draws,
+                                          n_gauss, flags, ngal, xi, false),
+                      nullptr, nullptr, ticket, nullptr);
 }
 
 int tc_interp_chi2_zheng07_batch_async(tc_interp* it, const double* theta, int n_theta,
@@ -1029,8 +951,10 @@ int tc_interp_chi2_zheng07_batch_async(tc_interp* it, const double* theta, int n
                                        unsigned flags, const double* data,
                                        const double* precision, double* ngal, double* chi2,
                                        int64_t* ticket) {
-  return interp_async(it, theta, n_theta, x, n_draws, n_gauss, flags, data, precision, ngal,
-                      chi2, true, ticket);
+  TC_CHECK(it != nullptr, "interp handle is NULL");
+  return interp_async(it, forward_request(it->tables[0], theta, n_theta, it->n_dim, x, n_draws,
+                                          n_gauss, flags, ngal, chi2, true),
+                      data, precision, ticket, nullptr);
 }
 
 // ---- gradients (grad_interp_kernels.hip.h) ------------------------------------------------
@@ -1312,35 +1236,13 @@ int tc_interp_chi2_grad_assembias_batch(tc_interp* it, const double* theta, int 
 
 int tc_interp_wait(tc_interp* it, int64_t ticket) {
   TC_CHECK(it != nullptr, "interp handle is NULL");
-  TC_CHECK(ticket >= 0 && ticket < it->next_ticket, "unknown ticket %lld", (long long)ticket);
-  const tc_table::Ticket& slot = it->tickets[ticket % tc_table::kMaxTickets];
-  if (slot.id == ticket) {
-    TC_HIP(hipEventSynchronize(slot.done));
-    return TC_OK;
-  }
-  // the slot was reused: the ticket is older than everything queued now
-  return tc_interp_synchronize(it);
+  return it->tickets.wait(ticket, [it] { return tc_interp_synchronize(it); });
 }
 
 int tc_interp_query(tc_interp* it, int64_t ticket, int* done) {
   TC_CHECK(it != nullptr && done != nullptr, "NULL argument");
-  TC_CHECK(ticket >= 0 && ticket < it->next_ticket, "unknown ticket %lld", (long long)ticket);
-  const tc_table::Ticket& slot = it->tickets[ticket % tc_table::kMaxTickets];
-  *done = 0;
-  // (a reused slot: the ticket is done once both lanes have passed their later work)
-  hipError_t state = hipSuccess;
-  if (slot.id == ticket) {
-    state = hipEventQuery(slot.done);
-  } else {
-    for (tc_interp::Lane& lane : it->lanes) {
-      const hipError_t lane_state = hipStreamQuery(lane.stream);
-      if (lane_state != hipSuccess) state = lane_state;
-    }
-  }
-  if (state == hipSuccess) *done = 1;
-  else if (state != hipErrorNotReady)
-    return fail(TC_ERR_HIP, "query failed: %s", hipGetErrorString(state));
-  return TC_OK;
+  static const char* const what[2] = {"query", "query"};
+  return it->tickets.query(ticket, done, it->lanes, what);
 }
 
 }  // extern "C"

@@ -564,6 +564,22 @@ int tc_debug_grad_slab(int n_params, int n_extra, int n_r, int likelihood, int64
   return TC_OK;
 }
 
+int tc_debug_sync_chunks(int64_t n_draws, int64_t out_bytes_per_draw, int64_t second_cols,
+                         const int* options, int n_lanes, unsigned call, int* n_chunks,
+                         int64_t* begins, int* staggered) {
+  TC_CHECK(options && n_chunks && begins && staggered, "NULL argument");
+  TC_CHECK(n_draws >= 0 && out_bytes_per_draw >= 16 && second_cols >= 1 && n_lanes >= 1 &&
+               options[0] >= -1 && options[0] <= 64 && options[1] >= 0 && options[1] <= 100,
+           "invalid sizes, or sync_chunks not in [-1, 64], or sync_stagger not in [0, 100]");
+  const tc::SyncChunkPlan plan = tc::plan_sync_chunks(
+      {n_draws, out_bytes_per_draw, second_cols, options[0], options[1], options[2], n_lanes,
+       (call & 1u) != 0, (call & 2u) != 0, (call & 4u) != 0, (call & 8u) != 0, (call & 16u) != 0});
+  *n_chunks = plan.n_chunks;
+  *staggered = plan.staggered ? 1 : 0;
+  for (int k = 0; k <= plan.n_chunks; ++k) begins[k] = plan.begins[k];
+  return TC_OK;
+}
+
 int tc_debug_leauthaud11_node_grad(const double* theta, int modulate, int64_t n,
                                    const double* mass, double* log_mstar, double* n_cen,
                                    double* dn_cen, double* n_sat, double* dn_sat) {

@@ -274,8 +274,7 @@ int tc_table_destroy(tc_table* t) {
     lane.cross_counters.release();
     if (lane.finished) (void)hipEventDestroy(lane.finished);
   }
-  for (tc_table::Ticket& ticket : t->tickets)
-    if (ticket.done) (void)hipEventDestroy(ticket.done);
+  t->tickets.release();
   t->h_in.release();
   t->h_out.release();
   t->single_ws.buffer.release();
@@ -664,143 +663,65 @@ int tc_predict_zheng07_joint(tc_table* const* tables, int n_tables, const double
   return first_error;
 }
 
+// ---- forward calls (predict_call.h: PredictRequest, forward_chunked, forward_zero_copy) -------
+
 namespace {
-int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws, int n_gauss,
-                  unsigned flags, const double* data, const double* precision, double* ngal,
-                  double* second, bool chi2, int64_t* ticket_out, const Call* chunk,
+int predict_async(tc_table* t, const PredictRequest& request, const double* data,
+                  const double* precision, int64_t* ticket_out, const Call* chunk,
                   hipEvent_t wait_for = nullptr, hipEvent_t kernels_done = nullptr);
 
-// How many chunks a synchronous host call of n_draws with out_bytes of results is cut into
-// (0: not chunked -- the serial path).
-int sync_chunks(const tc_table* t, int64_t n_draws, size_t out_bytes) {
-  if (t->tuning.sync_chunks < 0 || !t->tuning.pipeline || t->n_lanes < 2 || t->chain) return 0;
-  if (t->tuning.sync_chunks >= 1)
-    return (int)std::min<int64_t>(t->tuning.sync_chunks, (n_draws + 63) / 64);
-  // auto: about a megabyte of results per chunk, 2 .. 8 chunks of at least 1024 draws.  (All
-  // chunks' kernels share the chip and finish together, so more chunks buy nothing for small
-  // results -- 10^4 draws x 19 r values: 2 chunks 128 us, 3: 130, 4: 134, serial 150 -- while
-  // the 61 MB of a (19, 40) table's 10^4 draws travel and are copied under the kernels.)
-  if (n_draws < 2048) return 0;
-  const int64_t by_bytes = std::max<int64_t>(2, (int64_t)(out_bytes >> 20));
-  return (int)std::min<int64_t>(std::min<int64_t>(8, n_draws / 1024), by_bytes);
-}
-
-// A synchronous host-to-host call as overlapping chunks of draws: the draws
-// of chunk k are staged and queued on lane k % lanes while chunk k - 1 computes; the results of
-// chunk k are copied to the caller's arrays (on four host threads: parallel_copy) while later
-// chunks compute and travel.  Before: upload -> all kernels alone on one lane -> whole download
-// -> synchronise, strictly in series.  Every chunk takes the form the library picks for a
-// PIPELINED call -- for tables the one-launch form serves, workgroups of 32 draws (option
-// "sync_form"), whose results do not depend on where a draw sits in which batch: there the
-// call returns the same bits for any number of chunks (tests/test_gpu_async.py); elsewhere the
-// chunks differ from one piece by rounding (the schedule of the three-kernel path cuts a
-// draw's sums where the batch size puts them).
-int predict_chunked(tc_table* t, const double* theta, int n_theta, int64_t n_draws, int n_gauss,
-                    unsigned flags, const double* data, const double* precision, double* ngal,
-                    double* second, bool chi2, int n_chunks) {
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  const int n_comp = separate ? t->plan.n_components : 1;
-  const size_t ngal_cols = separate ? 2 : 1;
-  const size_t second_cols = chi2 ? 1 : (size_t)n_comp * t->n_r;
-  const size_t theta_bytes = (size_t)n_draws * n_theta * sizeof(double);
-  const size_t out_bytes = (size_t)n_draws * (ngal_cols + second_cols) * sizeof(double);
-  int status = t->h_in.reserve(theta_bytes);
-  if (status == TC_OK) status = t->h_out.reserve(out_bytes);
-  if (status != TC_OK) return status;
-  const int64_t chunk = ((n_draws + n_chunks - 1) / n_chunks + 63) / 64 * 64;
-  n_chunks = (int)((n_draws + chunk - 1) / chunk);
-  int64_t tickets[64], begins[65];
-  TC_CHECK(n_chunks <= 64, "internal: too many chunks");
-  for (int k = 0; k <= n_chunks; ++k) begins[k] = std::min<int64_t>(n_draws, k * chunk);
-  // Large results (tens of megabytes: a (19, 40) table's 10^4 draws are 61 MB): equal chunks on
-  // four lanes finish in two groups of four, and the second group's downloads -- 145 us each,
-  // queued behind one another -- have no kernels left to hide under (0.6 of 3.2 ms).  Instead
-  // the chunks' kernels run ONE AFTER THE OTHER (events between the lanes), each with the chip
-  // to itself, chunk k - 1 travelling and being copied while chunk k computes, and the chunks
-  // SHRINK towards the end, so that what is left exposed behind the last kernel is a few
-  // hundred draws' worth of transfer and copy.
-  // (results of 2 KB per draw and more only: with a few values per draw the transfers are small
-  // beside the kernels, and a chunk's launch alone on the chip runs below the rate of four
-  // overlapping ones -- 4 x 10^5 draws of 19 values 2.48 against 2.19 ms, tools/r06_big_sync.py)
-  const bool staggered = t->tuning.sync_stagger != 0 && out_bytes >= ((size_t)16 << 20) &&
-                         second_cols * sizeof(double) >= 2048 && n_chunks >= 4 && !chi2 &&
-                         t->n_lanes >= 2 &&
-                         // (float32 tables: there the transfers are half of what the kernels
-                         // take; the same table in float64 computes twice as long and loses
-                         // more to small launches than the transfers cost: 2.0e6 -> 1.8e6)
-                         t->compute_dtype == TC_DTYPE_F32;
-  if (staggered) {
-    // (tools/r06_stagger.py, 10^4 draws of a (19, 40) float32 table into arrays the caller
-    // keeps, 1e6 calls/s: 6 chunks shrinking to 2 / 5 / 10 / 20 % of the first 3.44 / 3.58 / 3.62 /
-    // 3.49; 7 chunks 3.52 / 3.58 / 3.49 / 3.45; 8 chunks 3.34 / 3.38 / 3.51 / 3.39; equal chunks
-    // on four lanes 3.14)
-    if (t->tuning.sync_chunks == 0) n_chunks = std::min(n_chunks, 6);
-    double share[64];
-    const double ratio = std::pow(0.01 * t->tuning.sync_stagger, 1.0 / (n_chunks - 1));
-    double total = 0.0, done = 0.0;
-    for (int k = 0; k < n_chunks; ++k) total += share[k] = std::pow(ratio, k);
-    begins[0] = 0;
-    for (int k = 0; k < n_chunks; ++k) {
-      done += share[k];
-      const int64_t end = k + 1 == n_chunks
-                              ? n_draws
-                              : std::min<int64_t>(n_draws, ((int64_t)(n_draws * done / total) + 63) / 64 * 64);
-      begins[k + 1] = std::max(end, begins[k]);
+// A table as forward_chunked and forward_zero_copy see it: the handle (its staging areas h_in and
+// h_out, its tickets, its pinned lane's stream), the Call every chunk carries, the events between
+// the chunks of a staggered plan (NULL: never staggered), the asynchronous path, the wait for
+// everything queued, and the launches on the pinned lane.
+struct TableForward {
+  static constexpr bool kThreadedCopyOut = true;
+  tc_table* t;
+  tc_table* handle() const { return t; }
+  // Every chunk takes the one-launch form with sync_form draws per workgroup wherever it serves
+  // the table at all: a draw's result there does not depend on the number of chunks
+  // (tests/test_gpu_async.py); elsewhere chunks differ from one piece by rounding.
+  Call hints(const PredictRequest& request, const tc::SyncChunkPlan& plan) const {
+    Call hints = probe_call(t);
+    hints.async = true;                      // (as the chunks will run)
+    hints.chain = false;
+    // (the latency form for every chunk when the whole call fits one round of 40-draw workgroups:
+    // the chunks' launches then fill the chip together)
+    hints.sync_spread = request.n_draws >= t->tuning.fused_spread_min &&
+                        (request.n_draws + 39) / 40 + plan.n_chunks <= (int64_t)t->n_cus;
+    hints.sync_spread = hints.sync_spread &&
+        tc::choose_fused_form(fused_query(t, hints, request.n_draws, request.n_gauss,
+                                          request.flags)).draws == 40;
+    if (hints.sync_spread) {
+      hints.fused_draws = 40;
+    } else if (t->tuning.sync_form != 0 && hints.fused_draws == 0 && t->tuning.fused == 1 &&
+               t->tuning.deterministic < 2) {
+      hints.fused_draws = t->tuning.sync_form;
+      if (hints.fused_min_draws == 0) hints.fused_min_draws = 1;
     }
-    while ((int)t->chunk_events.size() < n_chunks) {
-      hipEvent_t event;
-      TC_HIP(hipEventCreateWithFlags(&event, hipEventDisableTiming));
-      t->chunk_events.push_back(event);
-    }
+    return hints;
   }
-  double* h_theta = (double*)t->h_in.ptr;
-  double* h_out = (double*)t->h_out.ptr;
-  // (one form for every chunk size: the one-launch form with sync_form draws per workgroup
-  // wherever it serves the table at all, not only from the batch size on where it pays)
-  // (mode cross: the workgroups of ALL chunks together should fill the chip once -- see
-  // Call::cross_target)
-  Call hints = probe_call(t);
-  hints.async = true;                      // (as the chunks will run)
-  hints.chain = false;
-  hints.cross_target = 512 / n_chunks;
-  // (the latency form for every chunk when the whole call fits one round of 40-draw workgroups:
-  // the chunks' launches then fill the chip together)
-  hints.sync_spread = n_draws >= t->tuning.fused_spread_min &&
-                      (n_draws + 39) / 40 + n_chunks <= (int64_t)t->n_cus;
-  hints.sync_spread = hints.sync_spread &&
-      tc::choose_fused_form(fused_query(t, hints, n_draws, n_gauss, flags)).draws == 40;
-  if (hints.sync_spread) {
-    hints.fused_draws = 40;
-  } else if (t->tuning.sync_form != 0 && hints.fused_draws == 0 && t->tuning.fused == 1 &&
-             t->tuning.deterministic < 2) {
-    hints.fused_draws = t->tuning.sync_form;
-    if (hints.fused_min_draws == 0) hints.fused_min_draws = 1;
+  std::vector<hipEvent_t>* chunk_events() const { return &t->chunk_events; }
+  int enqueue(const PredictRequest& part, const Call& hints, hipEvent_t wait_for,
+              hipEvent_t kernels_done, int64_t* ticket) const {
+    return predict_async(t, part, nullptr, nullptr, ticket, &hints, wait_for, kernels_done);
   }
-  for (int k = 0; k < n_chunks && status == TC_OK; ++k) {
-    const int64_t begin = begins[k], n = begins[k + 1] - begin;
-    memcpy(h_theta + begin * n_theta, theta + begin * n_theta, (size_t)n * n_theta * 8);
-    // (the chunk's results side by side in the staging area: [ngal | xi] -- one copy command)
-    double* out = h_out + begin * (ngal_cols + second_cols);
-    status = predict_async(t, h_theta + begin * n_theta, n_theta, n, n_gauss, flags, data,
-                           precision, out, out + n * ngal_cols, chi2, &tickets[k], &hints,
-                           staggered && k > 0 ? t->chunk_events[k - 1] : nullptr,
-                           staggered ? t->chunk_events[k] : nullptr);
-    if (status != TC_OK) n_chunks = k;       // (wait for what was queued, then report)
+  int synchronize() const { return tc_table_synchronize(t); }
+  // (a likelihood: operands on the device, xi to t->out_xi; one slab's finalisation may write it)
+  int run(const PredictRequest& s) const {
+    Call call = make_call(t, /*pinned=*/true);
+    call.chi2_data = s.likelihood ? t->chi2.device() : nullptr;
+    call.chi2_out = s.likelihood && s.n_draws <= max_slab(t) ? s.second : nullptr;
+    bool written = !s.likelihood;
+    double* xi = s.likelihood ? (double*)t->out_xi.ptr : s.second;
+    int status = predict_device(t, call, s.theta, s.n_theta, s.n_draws, s.n_gauss, s.flags, s.ngal,
+                                xi, s.likelihood ? &written : nullptr);
+    if (status == TC_OK && !written)
+      status = launch_chi2(xi, s.n_draws, t->n_r, call.chi2_data, call.chi2_data + t->n_r,
+                           s.second, t->stream);
+    return status;
   }
-  for (int k = 0; k < n_chunks; ++k) {
-    const int64_t begin = begins[k], n = begins[k + 1] - begin;
-    const int waited = tc_table_wait(t, tickets[k]);
-    if (waited != TC_OK) {
-      (void)tc_table_synchronize(t);
-      return waited;
-    }
-    if (status != TC_OK) continue;
-    const double* out = h_out + begin * (ngal_cols + second_cols);
-    memcpy(ngal + begin * ngal_cols, out, (size_t)n * ngal_cols * 8);
-    parallel_copy(second + begin * second_cols, out + n * ngal_cols, (size_t)n * second_cols * 8);
-  }
-  return status;
-}
+};
 }  // namespace
 
 int tc_predict_zheng07_batch(tc_table* t, const double* theta, int n_theta,
@@ -811,17 +732,8 @@ int tc_predict_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   if (n_draws == 0) return TC_OK;
   TC_CHECK(ngal && xi, "output pointer is NULL");
   TC_HIP(hipSetDevice(t->device));
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  const int n_comp = separate ? t->plan.n_components : 1;
-  const size_t ngal_count = (size_t)n_draws * (separate ? 2 : 1);
-  const size_t xi_count = (size_t)n_draws * n_comp * t->n_r;
-  const size_t theta_bytes = (size_t)n_draws * n_theta * sizeof(double);
-  const size_t out_bytes = (ngal_count + xi_count) * sizeof(double);
-  // Small and medium calls (the un-batched predict() of an MCMC step, an ensemble of a few
-  // thousand walkers): no copy commands at all.  The kernels read the draws from and write
-  // the results to page-locked host memory, which the device addresses directly; two API
-  // calls and two copy-engine round trips less (1 draw 45 -> 40 us, 1000 draws 72 -> 54 us;
-  // beyond ~1 MB the copy engines win).
+  const PredictRequest request =
+      forward_request(t, theta, n_theta, 0, nullptr, n_draws, n_gauss, flags, ngal, xi, false);
   // (option "deterministic" = 2: neither of the un-batched kernels -- their sums are cut
   // differently from the batched forms')
   const bool invariant = batch_invariant_form(t, n_gauss, flags);
@@ -837,33 +749,22 @@ int tc_predict_zheng07_batch(tc_table* t, const double* theta, int n_theta,
     // combination replaced by a few hundred additions here (kernels.hip.h: single_draw_kernel)
     return tc_predict_zheng07_many(t, theta, n_theta, (int)n_draws, n_gauss, flags, ngal, xi);
   }
-  if (theta_bytes + out_bytes <= zero_copy_limit() && t->h_in.reserve(theta_bytes) == TC_OK &&
-      t->h_out.reserve(out_bytes) == TC_OK) {
-    memcpy(t->h_in.ptr, theta, theta_bytes);
-    double* h = (double*)t->h_out.ptr;
-    status = predict_device(t, make_call(t, /*pinned=*/true), (const double*)t->h_in.ptr,
-                            n_theta, n_draws, n_gauss, flags, h, h + ngal_count);
-    if (status != TC_OK) return status;
-    TC_HIP(hipStreamSynchronize(t->stream));
-    memcpy(ngal, h, ngal_count * 8);
-    parallel_copy(xi, h + ngal_count, xi_count * 8);
-    return TC_OK;
-  }
-  if (const int n_chunks = sync_chunks(t, n_draws, out_bytes))
-    return predict_chunked(t, theta, n_theta, n_draws, n_gauss, flags, nullptr, nullptr, ngal, xi,
-                           false, n_chunks);
-  status = t->theta.reserve(theta_bytes, t->stream);
-  if (status == TC_OK) status = t->out_ngal.reserve(ngal_count * 8, t->stream);
-  if (status == TC_OK) status = t->out_xi.reserve(xi_count * 8, t->stream);
+  // small and medium calls (an MCMC step, a few thousand walkers): straight on page-locked staging
+  const TableForward forward{t};
+  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
+  const tc::SyncChunkPlan plan = plan_forward_chunks(t, t->n_lanes, t->chain, false, request);
+  if (plan.n_chunks > 0) return forward_chunked(forward, request, plan);
+  status = t->theta.reserve(request.theta_bytes(), t->stream);
+  if (status == TC_OK) status = t->out_ngal.reserve(request.ngal_count() * 8, t->stream);
+  if (status == TC_OK) status = t->out_xi.reserve(request.second_count() * 8, t->stream);
   if (status != TC_OK) return status;
-  status = copy_in(&t->h_in, t->theta.ptr, theta, theta_bytes, t->stream);
+  status = copy_in(&t->h_in, t->theta.ptr, theta, request.theta_bytes(), t->stream);
   if (status != TC_OK) return status;
-  status = predict_device(t, make_call(t, /*pinned=*/true), (const double*)t->theta.ptr,
-                          n_theta, n_draws, n_gauss, flags, (double*)t->out_ngal.ptr,
-                          (double*)t->out_xi.ptr);
+  status = forward.run(request.on((const double*)t->theta.ptr, nullptr, (double*)t->out_ngal.ptr,
+                                  (double*)t->out_xi.ptr));
   if (status != TC_OK) return status;
-  return copy_out(&t->h_out, ngal, ngal_count, t->out_ngal.ptr, xi, xi_count,
-                  t->out_xi.ptr, t->stream);
+  return copy_out(&t->h_out, ngal, request.ngal_count(), t->out_ngal.ptr, xi,
+                  request.second_count(), t->out_xi.ptr, t->stream);
 }
 
 namespace {
@@ -940,53 +841,24 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
   if (n_draws == 0) return TC_OK;
   TC_CHECK(data && precision && ngal && chi2, "NULL pointer");
   TC_HIP(hipSetDevice(t->device));
-  const int n_r = t->n_r;
-  const size_t xi_count = (size_t)n_draws * n_r;
-  const size_t theta_bytes = (size_t)n_draws * n_theta * sizeof(double);
-  status = t->out_xi.reserve(xi_count * 8, t->stream);
+  const PredictRequest request =
+      forward_request(t, theta, n_theta, 0, nullptr, n_draws, n_gauss, flags, ngal, chi2, true);
+  status = t->out_xi.reserve((size_t)n_draws * t->n_r * 8, t->stream);   // (run()'s workspace)
   if (status == TC_OK) status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
-  const double* d_data = t->chi2.device();
-  const double* d_precision = d_data + n_r;
   // small calls: draws read from and results written to page-locked host memory directly
-  const bool direct = theta_bytes + (size_t)n_draws * 16 <= zero_copy_limit() &&
-                      t->h_in.reserve(theta_bytes) == TC_OK &&
-                      t->h_out.reserve((size_t)n_draws * 16) == TC_OK;
-  const double* theta_device = nullptr;
-  double* d_ngal = nullptr;
-  if (direct) {
-    memcpy(t->h_in.ptr, theta, theta_bytes);
-    theta_device = (const double*)t->h_in.ptr;
-    d_ngal = (double*)t->h_out.ptr;
-  } else {
-    status = t->theta.reserve(theta_bytes, t->stream);
-    if (status == TC_OK) status = t->out_ngal.reserve((size_t)n_draws * 2 * 8, t->stream);
-    if (status != TC_OK) return status;
-    status = copy_in(&t->h_in, t->theta.ptr, theta, theta_bytes, t->stream);
-    if (status != TC_OK) return status;
-    theta_device = (const double*)t->theta.ptr;
-    d_ngal = (double*)t->out_ngal.ptr;
-  }
-  double* d_chi2 = d_ngal + n_draws;
-  // (one slab: the finalisation kernel may write the likelihood itself)
-  Call call = make_call(t, /*pinned=*/true);
-  call.chi2_data = d_data;
-  call.chi2_out = n_draws <= max_slab(t) ? d_chi2 : nullptr;
-  bool written = false;
-  status = predict_device(t, call, theta_device, n_theta, n_draws, n_gauss, flags, d_ngal,
-                          (double*)t->out_xi.ptr, &written);
+  const TableForward forward{t};
+  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
+  status = t->theta.reserve(request.theta_bytes(), t->stream);
+  if (status == TC_OK) status = t->out_ngal.reserve(request.out_bytes(), t->stream);
   if (status != TC_OK) return status;
-  if (!written)
-    status = launch_chi2((const double*)t->out_xi.ptr, n_draws, n_r, d_data, d_precision,
-                         d_chi2, t->stream);
+  status = copy_in(&t->h_in, t->theta.ptr, theta, request.theta_bytes(), t->stream);
   if (status != TC_OK) return status;
-  if (direct) {
-    TC_HIP(hipStreamSynchronize(t->stream));
-    memcpy(ngal, d_ngal, (size_t)n_draws * 8);
-    memcpy(chi2, d_chi2, (size_t)n_draws * 8);
-    return TC_OK;
-  }
-  return copy_out(&t->h_out, ngal, (size_t)n_draws, d_ngal, chi2, (size_t)n_draws,
+  double* d_ngal = (double*)t->out_ngal.ptr;
+  double* d_chi2 = d_ngal + request.ngal_count();
+  status = forward.run(request.on((const double*)t->theta.ptr, nullptr, d_ngal, d_chi2));
+  if (status != TC_OK) return status;
+  return copy_out(&t->h_out, ngal, request.ngal_count(), d_ngal, chi2, request.second_count(),
                   d_chi2, t->stream);
 }
 
@@ -1318,62 +1190,40 @@ int tc_chi2_occupation_grad_batch(tc_table* t, const double* occupation, int64_t
 
 namespace {
 
-// Next ticket of the handle: its event (created on first use of the slot) and its number.
-int next_ticket(tc_table* t, tc_table::Ticket** out) {
-  tc_table::Ticket& slot = t->tickets[t->next_ticket % tc_table::kMaxTickets];
-  if (slot.done == nullptr)
-    TC_HIP(hipEventCreateWithFlags(&slot.done, hipEventDisableTiming));
-  slot.id = t->next_ticket++;
-  *out = &slot;
-  return TC_OK;
-}
-
 // Asynchronous host-to-host prediction or likelihood on the handle's next lane: everything
-// (upload, three kernels, download, the ticket's event) is queued on that lane's stream, so
-// lanes overlap each other's copies and kernels and nothing orders one ticket against
-// another.
-// `chunk` (or NULL): the call is a chunk of a synchronous call (predict_chunked) and this is what
-// every chunk carries; the buffers are then the library's own page-locked staging areas
-// (hipHostMalloc: the device sees them at the same addresses).
-// wait_for / kernels_done (the chunks of a synchronous call with large results): the call's
-// kernels start behind `wait_for`, and `kernels_done` is recorded between its kernels and its
-// download -- so that the chunks' kernels run one after the other, each with the chip to itself,
-// while the previous chunk's results travel.
-int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws, int n_gauss,
-                  unsigned flags, const double* data, const double* precision, double* ngal,
-                  double* second, bool chi2, int64_t* ticket_out, const Call* chunk,
+// (upload, three kernels, download, the ticket's event) is queued on that lane's stream, so lanes
+// overlap each other's copies and kernels and nothing orders one ticket against another.
+// `chunk` (or NULL): the call is a chunk of a synchronous call (forward_chunked) and this is what
+// every chunk carries; the buffers are then the library's own page-locked staging areas.
+// wait_for / kernels_done (the chunks of a staggered plan): the call's kernels start behind
+// `wait_for`, and `kernels_done` is recorded between its kernels and its download -- the chunks'
+// kernels run one after the other, each with the chip to itself, while the previous results travel.
+int predict_async(tc_table* t, const PredictRequest& r, const double* data,
+                  const double* precision, int64_t* ticket_out, const Call* chunk,
                   hipEvent_t wait_for, hipEvent_t kernels_done) {
-  int status = check_predict_args(t, theta, n_theta, n_draws, n_gauss, flags);
+  int status = check_predict_args(t, r.theta, r.n_theta, r.n_draws, r.n_gauss, r.flags);
   if (status != TC_OK) return status;
+  const int64_t n_draws = r.n_draws;
+  const bool chi2 = r.likelihood;
   TC_CHECK(ticket_out != nullptr, "ticket is NULL");
-  TC_CHECK(n_draws == 0 || (ngal && second), "output pointer is NULL");
-  const bool separate = (flags & TC_FLAG_SEPARATE_GAL_TYPE) != 0;
-  TC_CHECK(!(chi2 && separate), "chi2 is defined for the total correlation function only");
+  TC_CHECK(n_draws == 0 || (r.ngal && r.second), "output pointer is NULL");
+  TC_CHECK(!(chi2 && r.separate()), "chi2 is defined for the total correlation function only");
   TC_CHECK(!chi2 || (data && precision), "NULL pointer");
   TC_CHECK(!chi2 || n_draws <= max_slab(t), "at most %lld draws per call",
            (long long)max_slab(t));
-  const int n_comp = separate ? t->plan.n_components : 1;
-  const size_t ngal_count = (size_t)n_draws * (separate ? 2 : 1);
-  const size_t second_count = chi2 ? (size_t)n_draws : (size_t)n_draws * n_comp * t->n_r;
-  const size_t theta_bytes = (size_t)n_draws * n_theta * sizeof(double);
-  void *theta_seen = nullptr, *ngal_seen = nullptr, *second_seen = nullptr;
+  const size_t ngal_count = r.ngal_count(), second_count = r.second_count();
+  const size_t theta_bytes = r.theta_bytes();
+  void *theta_seen = (void*)r.theta, *ngal_seen = r.ngal, *second_seen = r.second;
   const bool staging = chunk != nullptr;
-  if (staging) {
-    theta_seen = (void*)theta;
-    ngal_seen = ngal;
-    second_seen = second;
-  } else {
-    TC_CHECK(n_draws == 0 || (is_pinned(theta, theta_bytes, &theta_seen) &&
-                              is_pinned(ngal, ngal_count * 8, &ngal_seen) &&
-                              is_pinned(second, second_count * 8, &second_seen)),
-             "asynchronous calls need page-locked buffers (tc_host_alloc / tc_host_register)");
-  }
+  TC_CHECK(staging || n_draws == 0 || (is_pinned(r.theta, theta_bytes, &theta_seen) &&
+                                       is_pinned(r.ngal, ngal_count * 8, &ngal_seen) &&
+                                       is_pinned(r.second, second_count * 8, &second_seen)),
+           "asynchronous calls need page-locked buffers (tc_host_alloc / tc_host_register)");
   TC_HIP(hipSetDevice(t->device));
   if (t->resident.running) {
     const int stopped = resident_stop(t);
     if (stopped != TC_OK) return stopped;
   }
-  tc_table::Ticket* ticket = nullptr;
   // (the finalisations of asynchronous calls are never chained: each has its ticket)
   Call call = chunk != nullptr ? *chunk : probe_call(t);
   call.lane = next_lane(false, t->tuning.pipeline != 0, t->n_lanes, &t->device_calls);
@@ -1383,9 +1233,8 @@ int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws
   if (n_draws > 0) {
     // Which arrays the kernels address in the caller's page-locked memory themselves and
     // which travel by copy command: see Tuning::async_direct_in / async_direct_out.
-    // (the chunks of a synchronous call: the kernels store up to 1 MB per array themselves --
-    // one call's 10^4 draws of 19 r values in two chunks 128 us against 151 with copy commands;
-    // larger chunks, e.g. of a (19, 40) table, go through the copy engines)
+    // (the chunks of a synchronous call: the kernels store up to 1 MB per array themselves -- 10^4
+    // draws of 19 r values in two chunks 128 us against 151; larger chunks by the copy engines)
     const int mode = staging ? t->tuning.sync_direct_out : t->tuning.async_direct_out;
     const size_t direct_bytes = staging ? kSyncDirectOutBytes : kDirectOutBytes;
     auto direct = [mode, direct_bytes](void* seen, size_t count) {
@@ -1405,35 +1254,31 @@ int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws
                                      : (double*)lane.out.ptr + ngal_count;
     if (!direct_in) {
       Range range("upload");
-      TC_HIP(hipMemcpyAsync(lane.in_theta.ptr, theta, theta_bytes, hipMemcpyHostToDevice,
+      TC_HIP(hipMemcpyAsync(lane.in_theta.ptr, r.theta, theta_bytes, hipMemcpyHostToDevice,
                             lane.stream));
     }
     if (wait_for != nullptr) TC_HIP(hipStreamWaitEvent(lane.stream, wait_for, 0));
-    status = chi2 ? chi2_on_device(t, call, d_theta, n_theta, n_draws, n_gauss, flags, data,
-                                precision, d_ngal, d_second)
-                  : predict_device(t, call, d_theta, n_theta, n_draws, n_gauss, flags, d_ngal,
-                                   d_second);
+    status = chi2 ? chi2_on_device(t, call, d_theta, r.n_theta, n_draws, r.n_gauss, r.flags, data,
+                                   precision, d_ngal, d_second)
+                  : predict_device(t, call, d_theta, r.n_theta, n_draws, r.n_gauss, r.flags,
+                                   d_ngal, d_second);
     if (status != TC_OK) return status;
     if (kernels_done != nullptr) TC_HIP(hipEventRecord(kernels_done, lane.stream));
     Range range("download");
-    if (!direct_ngal && !direct_second && second == ngal + ngal_count) {
+    if (!direct_ngal && !direct_second && r.second == r.ngal + ngal_count) {
       // (adjacent in the caller's memory as in the staging buffer: one command)
-      TC_HIP(hipMemcpyAsync(ngal, d_ngal, (ngal_count + second_count) * 8,
+      TC_HIP(hipMemcpyAsync(r.ngal, d_ngal, (ngal_count + second_count) * 8,
                             hipMemcpyDeviceToHost, lane.stream));
     } else {
       if (!direct_ngal)
-        TC_HIP(hipMemcpyAsync(ngal, d_ngal, ngal_count * 8, hipMemcpyDeviceToHost,
+        TC_HIP(hipMemcpyAsync(r.ngal, d_ngal, ngal_count * 8, hipMemcpyDeviceToHost,
                               lane.stream));
       if (!direct_second)
-        TC_HIP(hipMemcpyAsync(second, d_second, second_count * 8, hipMemcpyDeviceToHost,
+        TC_HIP(hipMemcpyAsync(r.second, d_second, second_count * 8, hipMemcpyDeviceToHost,
                               lane.stream));
     }
   }
-  status = next_ticket(t, &ticket);
-  if (status != TC_OK) return status;
-  TC_HIP(hipEventRecord(ticket->done, lane.stream));
-  *ticket_out = ticket->id;
-  return TC_OK;
+  return t->tickets.issue(lane.stream, ticket_out);
 }
 
 }  // namespace
@@ -1441,52 +1286,29 @@ int predict_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws
 int tc_predict_zheng07_batch_async(tc_table* t, const double* theta, int n_theta,
                                    int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
                                    double* xi, int64_t* ticket) {
-  return predict_async(t, theta, n_theta, n_draws, n_gauss, flags, nullptr, nullptr, ngal, xi,
-                       false, ticket, nullptr);
+  return predict_async(t, forward_request(t, theta, n_theta, 0, nullptr, n_draws, n_gauss, flags,
+                                          ngal, xi, false),
+                       nullptr, nullptr, ticket, nullptr);
 }
 
 int tc_chi2_zheng07_batch_async(tc_table* t, const double* theta, int n_theta, int64_t n_draws,
                                 int n_gauss, unsigned flags, const double* data,
                                 const double* precision, double* ngal, double* chi2,
                                 int64_t* ticket) {
-  return predict_async(t, theta, n_theta, n_draws, n_gauss, flags, data, precision, ngal, chi2,
-                       true, ticket, nullptr);
+  return predict_async(t, forward_request(t, theta, n_theta, 0, nullptr, n_draws, n_gauss, flags,
+                                          ngal, chi2, true),
+                       data, precision, ticket, nullptr);
 }
 
 int tc_table_wait(tc_table* t, int64_t ticket) {
   TC_CHECK(t != nullptr, "table handle is NULL");
-  TC_CHECK(ticket >= 0 && ticket < t->next_ticket, "unknown ticket %lld", (long long)ticket);
-  const tc_table::Ticket& slot = t->tickets[ticket % tc_table::kMaxTickets];
-  if (slot.id == ticket) {
-    TC_HIP(hipEventSynchronize(slot.done));
-    return TC_OK;
-  }
-  // the slot was reused: the ticket is older than the work now queued on every lane
-  return tc_table_synchronize(t);
+  return t->tickets.wait(ticket, [t] { return tc_table_synchronize(t); });
 }
 
 int tc_table_query(tc_table* t, int64_t ticket, int* done) {
   TC_CHECK(t != nullptr && done != nullptr, "NULL argument");
-  TC_CHECK(ticket >= 0 && ticket < t->next_ticket, "unknown ticket %lld", (long long)ticket);
-  const tc_table::Ticket& slot = t->tickets[ticket % tc_table::kMaxTickets];
-  *done = 0;
-  if (slot.id == ticket) {
-    const hipError_t state = hipEventQuery(slot.done);
-    if (state == hipSuccess) *done = 1;
-    else if (state != hipErrorNotReady)
-      return fail(TC_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(state));
-    return TC_OK;
-  }
-  // a reused slot: done once every lane has passed its own later tickets
-  *done = 1;
-  for (tc_table::Lane& lane : t->lanes) {
-    if (lane.stream == nullptr) continue;
-    const hipError_t state = hipStreamQuery(lane.stream);
-    if (state == hipErrorNotReady) *done = 0;
-    else if (state != hipSuccess)
-      return fail(TC_ERR_HIP, "hipStreamQuery failed: %s", hipGetErrorString(state));
-  }
-  return TC_OK;
+  static const char* const what[2] = {"hipEventQuery", "hipStreamQuery"};
+  return t->tickets.query(ticket, done, t->lanes, what);
 }
 
 int tc_mean_occupation_zheng07_batch(tc_table* t, const double* theta, int n_theta,
@@ -1850,7 +1672,7 @@ int tc_table_set_option(tc_table* t, const char* name, int value) {
   } else if (key == "sync_stagger") {
     // synchronous host calls with 16 MB of results and more run their chunks' kernels one after
     // the other, the chunks shrinking geometrically to this many per cent of the first
-    // (default 10; 0: equal chunks on all lanes as for small results; predict_chunked)
+    // (default 10; 0: equal chunks on all lanes as for small results; plan_sync_chunks)
     TC_CHECK(value >= 0 && value <= 100, "sync_stagger must be in [0, 100]");
     t->tuning.sync_stagger = value;
   } else if (key == "sync_form") {

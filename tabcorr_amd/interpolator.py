@@ -19,9 +19,9 @@ import threading
 
 import numpy as np
 
+from . import _forward
 from . import _grad
 from . import _lib
-from . import pinned
 from .galtable import GalTypeTable
 from .models import device_spec
 from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _chi2_operands, _flags,
@@ -312,6 +312,16 @@ class Interpolator:
                 n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
                 modulate_with_cenocc=modulate_with_cenocc,
                 assembias=assembias, family=family, out=out).wait()
+        device, inputs, shapes = self._forward_inputs(
+            theta, x, extrapolate, n_gauss_prim,
+            _flags(separate_gal_type, modulate_with_cenocc, assembias, family))
+        ngal, xi = _forward.call(device, 'interp', 'predict', inputs, shapes)
+        return self.tabcorr_list[0]._package(ngal, xi, separate_gal_type)
+
+    def _forward_inputs(self, theta, x, extrapolate, n_gauss_prim, flags,
+                        likelihood=False):
+        """The device, a forward entry's arguments from the handle to the
+        operands, the results' shapes; ``x`` is checked before any device."""
         theta = _lib.contiguous(np.atleast_2d(theta))
         x = _lib.contiguous(np.atleast_2d(x))
         if x.shape != (len(theta), len(self.keys)):
@@ -319,28 +329,10 @@ class Interpolator:
                 len(self.keys)))
         self._check_range(x, extrapolate)
         device = self.to_device()
-        table = device.tables[0]
-        flags = _flags(separate_gal_type, modulate_with_cenocc, assembias,
-                       family)
         n_draws = len(theta)
-        n_comp = table.n_components if separate_gal_type else 1
-        ngal = np.empty((n_draws, 2 if separate_gal_type else 1))
-        xi = np.empty((n_draws, n_comp, table.n_r))
-        with device.lock:
-            _lib.check(device.lib.tc_interp_predict_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                _lib.as_double_p(x), n_draws, n_gauss_prim, flags,
-                _lib.as_double_p(ngal), _lib.as_double_p(xi)))
-        return self.tabcorr_list[0]._package(ngal, xi, separate_gal_type)
-
-    def _async_inputs(self, theta, x, extrapolate):
-        theta = _lib.contiguous(np.atleast_2d(theta))
-        x = _lib.contiguous(np.atleast_2d(x))
-        if x.shape != (len(theta), len(self.keys)):
-            raise ValueError('x must have shape (n_draws, {}).'.format(
-                len(self.keys)))
-        self._check_range(x, extrapolate)
-        return theta, x
+        return (device,
+                (theta, theta.shape[1], x, n_draws, n_gauss_prim, flags),
+                _forward.shapes(device.tables[0], n_draws, flags, likelihood))
 
     def predict_batch_async(self, theta, x, separate_gal_type=False,
                             n_gauss_prim=10, extrapolate=False,
@@ -349,61 +341,25 @@ class Interpolator:
         """`predict_batch` without waiting for the device (see
         `TabCorr.predict_batch_async`): returns a
         `tabcorr_amd.pinned.PendingPrediction`."""
-        theta, x = self._async_inputs(theta, x, extrapolate)
-        device = self.to_device()
-        table = device.tables[0]
-        flags = _flags(separate_gal_type, modulate_with_cenocc, assembias,
-                       family)
-        n_draws = len(theta)
-        n_comp = table.n_components if separate_gal_type else 1
-        shapes = [(n_draws, 2 if separate_gal_type else 1),
-                  (n_draws, n_comp, table.n_r)]
-        (ngal, xi), pooled_out = pinned.stage_outputs(shapes, out)
-        (theta_p, x_p), pooled_in = pinned.stage_inputs([theta, x])
-        ticket = ctypes.c_int64(-1)
-        with device.lock:
-            _lib.check(device.lib.tc_interp_predict_zheng07_batch_async(
-                device.handle, _lib.as_double_p(theta_p), theta.shape[1],
-                _lib.as_double_p(x_p), n_draws, n_gauss_prim, flags,
-                _lib.as_double_p(ngal), _lib.as_double_p(xi),
-                ctypes.byref(ticket)))
+        device, inputs, shapes = self._forward_inputs(
+            theta, x, extrapolate, n_gauss_prim,
+            _flags(separate_gal_type, modulate_with_cenocc, assembias, family))
         first = self.tabcorr_list[0]
-        return pinned.PendingPrediction(
-            device, device.lib.tc_interp_wait, device.lib.tc_interp_query,
-            ticket.value,
-            [theta_p, x_p], [ngal, xi], pooled_in, pooled_out,
-            lambda n, v: first._package(n, v, separate_gal_type))
+        return _forward.call_async(
+            device, 'interp', 'predict', inputs, shapes,
+            lambda n, v: first._package(n, v, separate_gal_type), out=out)
 
     def chi2_batch_async(self, theta, x, data, precision, n_gauss_prim=10,
                          extrapolate=False, modulate_with_cenocc=False,
                          assembias=False, family='zheng07', out=None):
         """`chi2_batch` without waiting for the device."""
-        theta, x = self._async_inputs(theta, x, extrapolate)
-        device = self.to_device()
-        n_r = device.tables[0].n_r
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
-        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(n_r))
-        n_draws = len(theta)
-        (ngal, chi2), pooled_out = pinned.stage_outputs(
-            [(n_draws, ), (n_draws, )], out)
-        (theta_p, x_p), pooled_in = pinned.stage_inputs([theta, x])
-        ticket = ctypes.c_int64(-1)
-        with device.lock:
-            _lib.check(device.lib.tc_interp_chi2_zheng07_batch_async(
-                device.handle, _lib.as_double_p(theta_p), theta.shape[1],
-                _lib.as_double_p(x_p), n_draws, n_gauss_prim,
-                _flags(False, modulate_with_cenocc, assembias, family),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                ctypes.byref(ticket)))
-        return pinned.PendingPrediction(
-            device, device.lib.tc_interp_wait, device.lib.tc_interp_query,
-            ticket.value,
-            [theta_p, x_p], [ngal, chi2], pooled_in, pooled_out,
-            lambda n, c: (n, c))
+        device, inputs, shapes = self._forward_inputs(
+            theta, x, extrapolate, n_gauss_prim,
+            _flags(False, modulate_with_cenocc, assembias, family), True)
+        return _forward.call_async(
+            device, 'interp', 'chi2', inputs, shapes, lambda n, c: (n, c),
+            operands=_chi2_operands(data, precision, device.tables[0].n_r),
+            out=out)
 
     def chi2_batch(self, theta, x, data, precision, n_gauss_prim=10,
                    extrapolate=False, modulate_with_cenocc=False,
@@ -417,29 +373,12 @@ class Interpolator:
         -------
         ngal, chi2 : numpy.ndarray ``(n_draws, )``
         """
-        theta = _lib.contiguous(np.atleast_2d(theta))
-        x = _lib.contiguous(np.atleast_2d(x))
-        if x.shape != (len(theta), len(self.keys)):
-            raise ValueError('x must have shape (n_draws, {}).'.format(
-                len(self.keys)))
-        self._check_range(x, extrapolate)
-        device = self.to_device()
-        n_r = device.tables[0].n_r
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
-        if data.shape != (n_r, ) or precision.shape != (n_r, n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(n_r))
-        ngal = np.empty(len(theta))
-        chi2 = np.empty(len(theta))
-        with device.lock:
-            _lib.check(device.lib.tc_interp_chi2_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                _lib.as_double_p(x), len(theta), n_gauss_prim,
-                _flags(False, modulate_with_cenocc, assembias, family),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2)))
-        return ngal, chi2
+        device, inputs, shapes = self._forward_inputs(
+            theta, x, extrapolate, n_gauss_prim,
+            _flags(False, modulate_with_cenocc, assembias, family), True)
+        return _forward.call(
+            device, 'interp', 'chi2', inputs, shapes,
+            _chi2_operands(data, precision, device.tables[0].n_r))
 
     # -- analytic gradients ----------------------------------------------------------
 

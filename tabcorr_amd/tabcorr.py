@@ -23,6 +23,7 @@ import threading
 
 import numpy as np
 
+from . import _forward
 from . import _grad
 from . import _lib
 from . import pinned
@@ -629,24 +630,21 @@ class TabCorr:
                 n_gauss_prim=n_gauss_prim,
                 modulate_with_cenocc=modulate_with_cenocc,
                 assembias=assembias, family=family, out=out).wait()
+        device, inputs, shapes = self._forward_inputs(
+            theta, n_gauss_prim, _flags(separate_gal_type, modulate_with_cenocc,
+                                        assembias, family))
+        ngal, xi = _forward.call(device, 'table', 'predict', inputs, shapes,
+                                 (), out)
+        return self._package(ngal, xi, separate_gal_type)
+
+    def _forward_inputs(self, theta, n_gauss_prim, flags, likelihood=False):
+        """The device, what follows its handle in a forward entry's arguments
+        up to the operands, and the shapes of the two results."""
         device = self.to_device()
         theta = _lib.contiguous(np.atleast_2d(theta))
-        flags = _flags(separate_gal_type, modulate_with_cenocc, assembias,
-                       family)
         n_draws = len(theta)
-        n_comp = device.n_components if separate_gal_type else 1
-        shapes = [(n_draws, 2 if separate_gal_type else 1),
-                  (n_draws, n_comp, device.n_r)]
-        if out is not None:
-            ngal, xi = pinned.caller_outputs(shapes, out)
-        else:
-            ngal, xi = np.empty(shapes[0]), np.empty(shapes[1])
-        with device.lock:
-            _lib.check(device.lib.tc_predict_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                n_draws, n_gauss_prim, flags, _lib.as_double_p(ngal),
-                _lib.as_double_p(xi)))
-        return self._package(ngal, xi, separate_gal_type)
+        return (device, (theta, theta.shape[1], n_draws, n_gauss_prim, flags),
+                _forward.shapes(device, n_draws, flags, likelihood))
 
     def predict_batch_async(self, theta, separate_gal_type=False,
                             n_gauss_prim=10, modulate_with_cenocc=False,
@@ -664,26 +662,12 @@ class TabCorr:
         one at ``wait()``.  Do not modify a pinned ``theta`` or read ``out``
         before ``wait()`` returned.
         """
-        device = self.to_device()
-        theta = _lib.contiguous(np.atleast_2d(theta))
-        flags = _flags(separate_gal_type, modulate_with_cenocc, assembias,
-                       family)
-        n_draws = len(theta)
-        n_comp = device.n_components if separate_gal_type else 1
-        shapes = [(n_draws, 2 if separate_gal_type else 1),
-                  (n_draws, n_comp, device.n_r)]
-        (ngal, xi), pooled_out = pinned.stage_outputs(shapes, out)
-        (theta_pinned, ), pooled_in = pinned.stage_inputs([theta])
-        ticket = ctypes.c_int64(-1)
-        with device.lock:
-            _lib.check(device.lib.tc_predict_zheng07_batch_async(
-                device.handle, _lib.as_double_p(theta_pinned), theta.shape[1],
-                n_draws, n_gauss_prim, flags, _lib.as_double_p(ngal),
-                _lib.as_double_p(xi), ctypes.byref(ticket)))
-        return pinned.PendingPrediction(
-            device, device.lib.tc_table_wait, device.lib.tc_table_query,
-            ticket.value, [theta_pinned], [ngal, xi], pooled_in, pooled_out,
-            lambda n, x: self._package(n, x, separate_gal_type))
+        device, inputs, shapes = self._forward_inputs(
+            theta, n_gauss_prim, _flags(separate_gal_type, modulate_with_cenocc,
+                                        assembias, family))
+        return _forward.call_async(
+            device, 'table', 'predict', inputs, shapes,
+            lambda n, x: self._package(n, x, separate_gal_type), out=out)
 
     def chi2_batch(self, theta, data, precision, n_gauss_prim=10,
                    modulate_with_cenocc=False, assembias=False,
@@ -702,24 +686,11 @@ class TabCorr:
         -------
         ngal, chi2 : numpy.ndarray ``(n_draws, )``
         """
-        device = self.to_device()
-        theta = _lib.contiguous(np.atleast_2d(theta))
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
-        if data.shape != (device.n_r, ) or precision.shape != (device.n_r,
-                                                               device.n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(device.n_r))
-        ngal = np.empty(len(theta))
-        chi2 = np.empty(len(theta))
-        with device.lock:
-            _lib.check(device.lib.tc_chi2_zheng07_batch(
-                device.handle, _lib.as_double_p(theta), theta.shape[1],
-                len(theta), n_gauss_prim,
-                _flags(False, modulate_with_cenocc, assembias, family),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2)))
-        return ngal, chi2
+        device, inputs, shapes = self._forward_inputs(
+            theta, n_gauss_prim,
+            _flags(False, modulate_with_cenocc, assembias, family), True)
+        return _forward.call(device, 'table', 'chi2', inputs, shapes,
+                             _chi2_operands(data, precision, device.n_r))
 
     # -- analytic gradients -----------------------------------------------------------
 
@@ -1055,31 +1026,12 @@ class TabCorr:
         """`chi2_batch` without waiting (see `predict_batch_async`): 8 bytes
         per parameter go to the device and 16 bytes per draw come back.
         ``out=(ngal, chi2)``: page-locked arrays of ``n_draws`` elements."""
-        device = self.to_device()
-        theta = _lib.contiguous(np.atleast_2d(theta))
-        data = _lib.contiguous(np.ravel(data))
-        precision = _lib.contiguous(precision)
-        if data.shape != (device.n_r, ) or precision.shape != (device.n_r,
-                                                               device.n_r):
-            raise ValueError('data must have {0} entries and precision shape '
-                             '({0}, {0}).'.format(device.n_r))
-        n_draws = len(theta)
-        (ngal, chi2), pooled_out = pinned.stage_outputs(
-            [(n_draws, ), (n_draws, )], out)
-        (theta_pinned, ), pooled_in = pinned.stage_inputs([theta])
-        ticket = ctypes.c_int64(-1)
-        with device.lock:
-            _lib.check(device.lib.tc_chi2_zheng07_batch_async(
-                device.handle, _lib.as_double_p(theta_pinned), theta.shape[1],
-                n_draws, n_gauss_prim,
-                _flags(False, modulate_with_cenocc, assembias, family),
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                ctypes.byref(ticket)))
-        return pinned.PendingPrediction(
-            device, device.lib.tc_table_wait, device.lib.tc_table_query,
-            ticket.value, [theta_pinned], [ngal, chi2], pooled_in, pooled_out,
-            lambda n, c: (n, c))
+        device, inputs, shapes = self._forward_inputs(
+            theta, n_gauss_prim,
+            _flags(False, modulate_with_cenocc, assembias, family), True)
+        return _forward.call_async(
+            device, 'table', 'chi2', inputs, shapes, lambda n, c: (n, c),
+            operands=_chi2_operands(data, precision, device.n_r), out=out)
 
     def _predict_occupation(self, occupation, separate_gal_type):
         device = self.to_device()

@@ -873,7 +873,7 @@ def test_resident_ensemble_kernel_gives_up_cleanly():
                                   'float32 rp-pi table', 'mode cross'])
 def test_synchronous_calls_in_chunks(case):
     """a synchronous host-array call is cut into chunks of draws whose
-    staging, kernels, transfers and copies overlap (table.cpp: predict_chunked).  Against the
+    staging, kernels, transfers and copies overlap (predict_call.h: forward_chunked).  Against the
     oracle on draws of every chunk and around the chunk boundaries; the same bits for any
     number of chunks where the one-launch form serves the table (its workgroups of 32 draws do
     not care where a draw sits), rounding elsewhere; ragged sizes; the serial path agrees."""
@@ -940,7 +940,7 @@ def test_synchronous_calls_in_chunks(case):
 
 @pytest.mark.parametrize('mode', ['auto', 'cross'])
 def test_synchronous_interpolator_calls_in_chunks(mode):
-    """Interpolator.predict_batch on host arrays in chunks (interp.cpp: interp_chunked): the
+    """Interpolator.predict_batch on host arrays in chunks (predict_call.h: forward_chunked): the
     oracle on draws of every chunk, any number of chunks against one piece to rounding, ragged
     sizes, separated by galaxy type."""
     from tabcorr_amd import Interpolator, synthetic, _lib

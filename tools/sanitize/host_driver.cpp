@@ -3,7 +3,8 @@
 // HIP.  Walks the same entry points the C ABI uses (bin permutation and segmentation,
 // chunking, the quadratic-form layout / schedule / table fill / emulation, spline
 // matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort and label-block
-// plan, the choice of the one-launch form, the slabs of a derivative call) over a sweep of shapes
+// plan, the choice of the one-launch form, the slabs of a derivative call, the chunk plan and the
+// chunks of a forward call) over a sweep of shapes
 // and checks the results against direct evaluations.  Exit status 0 = all
 // checks passed and no sanitizer report (-fno-sanitize-recover aborts on the first).
 //
@@ -20,6 +21,7 @@
 #include "../../tabcorr_amd/csrc/grad_call.h"
 #include "../../tabcorr_amd/csrc/hostmath.h"
 #include "../../tabcorr_amd/csrc/kernel_args.h"
+#include "../../tabcorr_amd/csrc/predict_call.h"
 
 static int g_failures = 0;
 #define EXPECT(condition, ...)                 \
@@ -475,7 +477,92 @@ static void check_grad_slabs() {
           }
 }
 
+// hostmath.h: plan_sync_chunks over the sweep of tests/test_predict_call_cpu.py: boundaries from 0
+// to n_draws, strictly increasing, inner ones multiples of 64, at most 64 chunks, never staggered
+// for an interpolator or a likelihood; and the chunk arithmetic of the forward entry points
+// (predict_call.h: PredictRequest::chunk) against the closed forms beyond 2^31 elements.
+static void check_forward_calls() {
+  int planned = 0, staggered = 0;
+  for (int64_t n_draws : {0, 1, 63, 64, 65, 100, 2047, 2048, 4096, 5013, 9037, 10000, 400000})
+    for (int sync_chunks : {-1, 0, 1, 2, 3, 7, 8, 64})
+      for (int sync_stagger : {0, 1, 10, 50, 100})
+        for (int doubles : {8, 20, 257, 761})
+          for (int bits = 0; bits < 32; ++bits) {
+            tc::SyncChunkQuery q;
+            q.n_draws = n_draws;
+            q.out_bytes_per_draw = 8 * doubles;
+            q.likelihood = bits & 1;
+            q.second_cols = q.likelihood ? 1 : doubles - 1;
+            q.sync_chunks = sync_chunks;
+            q.sync_stagger = sync_stagger;
+            q.n_lanes = bits & 2 ? 4 : 1;
+            q.float32 = bits & 4;
+            q.interpolator = bits & 8;
+            q.cross = bits & 16;
+            const tc::SyncChunkPlan plan = tc::plan_sync_chunks(q);
+            EXPECT(plan.n_chunks >= 0 && plan.n_chunks <= 64, "%d chunks", plan.n_chunks);
+            if (plan.n_chunks == 0) {
+              EXPECT(!plan.staggered, "a staggered serial call");
+              continue;
+            }
+            ++planned;
+            staggered += plan.staggered;
+            EXPECT(q.n_lanes >= 2 && sync_chunks >= 0, "chunks on the serial path");
+            EXPECT(!plan.staggered || (!q.interpolator && !q.likelihood && q.float32),
+                   "a staggered plan where none belongs");
+            EXPECT(plan.begins[0] == 0 && plan.begins[plan.n_chunks] == n_draws,
+                   "%lld draws: chunks from %lld to %lld", (long long)n_draws,
+                   (long long)plan.begins[0], (long long)plan.begins[plan.n_chunks]);
+            for (int k = 1; k <= plan.n_chunks; ++k) {
+              EXPECT(plan.begins[k] > plan.begins[k - 1], "%lld draws: chunk %d is empty",
+                     (long long)n_draws, k - 1);
+              EXPECT(k == plan.n_chunks || plan.begins[k] % 64 == 0, "boundary %lld",
+                     (long long)plan.begins[k]);
+            }
+          }
+  EXPECT(planned > 5000 && staggered > 50, "%d plans, %d staggered", planned, staggered);
+
+  // (chunk() on arrays that exist, so that every chunk lies inside them; the byte counts, which
+  // are plain integers, up to 2^33 draws: every product in 64 bits)
+  const int64_t n_whole = 4096;
+  for (int n_extra : {0, 2})
+    for (int form = 0; form < 3; ++form)          // total, separated by galaxy type, likelihood
+      for (int n_r : {1, 19, 256}) {
+        const int n_theta = 5, n_comp = 3;
+        const int64_t ngal_cols = form == 1 ? 2 : 1;
+        const int64_t second_cols = form == 2 ? 1 : (int64_t)(form == 1 ? n_comp : 1) * n_r;
+        std::vector<double> theta(n_whole * n_theta), x(n_whole * n_extra + 1),
+            ngal(n_whole * ngal_cols), second(n_whole * second_cols);
+        const tc::host::PredictRequest whole{
+            n_theta, n_extra, 10, form == 1 ? (unsigned)TC_FLAG_SEPARATE_GAL_TYPE : 0u, n_whole, n_r,
+            n_comp, theta.data(), n_extra ? x.data() : nullptr, ngal.data(), second.data(),
+            form == 2};
+        EXPECT((int64_t)whole.in_bytes() == n_whole * (n_theta + n_extra) * 8 &&
+                   (int64_t)whole.out_bytes() == n_whole * (ngal_cols + second_cols) * 8,
+               "bytes of form %d", form);
+        for (int64_t begin : {(int64_t)0, (int64_t)1, (int64_t)64, (int64_t)1409, n_whole - 81}) {
+          const tc::host::PredictRequest part = whole.chunk(begin, 81);
+          EXPECT(part.n_draws == 81 && part.theta - whole.theta == begin * n_theta &&
+                     (n_extra ? part.x - whole.x == begin * n_extra : part.x == nullptr) &&
+                     part.ngal - whole.ngal == begin * ngal_cols &&
+                     part.second - whole.second == begin * second_cols &&
+                     (int64_t)part.ngal_count() == 81 * ngal_cols &&
+                     (int64_t)part.second_count() == 81 * second_cols,
+                 "chunk of form %d, %d extra columns, %d rows at draw %lld", form, n_extra, n_r,
+                 (long long)begin);
+        }
+        tc::host::PredictRequest huge = whole;
+        huge.n_draws = ((int64_t)1 << 33) + 3;
+        EXPECT(huge.theta_bytes() == (size_t)huge.n_draws * n_theta * 8 &&
+                   huge.x_bytes() == (size_t)huge.n_draws * n_extra * 8 &&
+                   huge.second_count() == (size_t)huge.n_draws * second_cols &&
+                   huge.out_bytes() == (size_t)huge.n_draws * (ngal_cols + second_cols) * 8,
+               "64-bit sizes of form %d", form);
+      }
+}
+
 int main() {
+  check_forward_calls();
   check_grad_slabs();
   check_quadrature();
   check_splines();
