@@ -70,6 +70,7 @@ typedef struct tc_table tc_table;
 typedef struct tc_interp tc_interp;
 typedef struct tc_comm tc_comm;
 typedef struct tc_joint tc_joint;
+typedef struct tc_joint_interp tc_joint_interp;
 
 /* ---- runtime ---------------------------------------------------------------------- */
 
@@ -586,6 +587,68 @@ int tc_joint_chi2_grad_batch_device(tc_joint* joint, const double* theta_device,
                                     double* ngal_device, double* chi2_device,
                                     double* dngal_device, double* dchi2_device,
                                     double* fisher_device);
+
+/* Joint likelihood of several interpolators (extension): the reference's AbacusSummit database
+ * and its own suite read TWO interpolators, `wp` and `ds`, built over the same grid of simulations,
+ * for one model; the covariance of the data vector (w_p, DeltaSigma) couples them, and the fit's
+ * parameters are the model's AND the grid's extra parameters x.  A joint handle over 1 .. 16
+ * interpolators evaluates a batch of draws (theta, x) against ALL of them in one launch: the
+ * occupations of every class of halo tables once, every member's contraction at every grid node
+ * (a member is mode auto or mode cross throughout; members may differ) into its rows r_offset[m]
+ * .. r_offset[m] + n_r[m] of the N = sum_m n_r[m] concatenated ones, in list order.
+ *
+ * tc_joint_interp_create: every member on the same device and of float64 tables, no handle twice,
+ * the same axes (bit-identical abscissae) and grid nodes as member 0 -- the members' LIST orders
+ * may differ: tables are matched by grid node --, and at every node the bins (all gal_type
+ * columns) of member 0's table there; anything else is TC_ERR_INVALID with a message naming the
+ * member.  The walk over the grid is member 0's.  The joint owns no member and no table: it
+ * works through them (Conventions: a call excludes calls on any member and any of their tables);
+ * tc_joint_interp_destroy does not touch them.  tc_joint_interp_info: r_offset holds n_members
+ * entries; any pointer may be NULL. */
+int tc_joint_interp_create(tc_interp* const* members, int n_members, tc_joint_interp** joint);
+int tc_joint_interp_destroy(tc_joint_interp* joint);
+int tc_joint_interp_synchronize(tc_joint_interp* joint);
+int tc_joint_interp_info(const tc_joint_interp* joint, int* n_members, int* n_dim, int* n_r_total,
+                         int* r_offset);
+/* The concatenated prediction with its exact derivatives (tc_interp_predict_grad_zheng07_batch
+ * with N for n_r): ngal (n_draws), xi (n_draws, N), dngal (n_draws, 5 + n_dim), dxi (n_draws,
+ * 5 + n_dim, N), the model's columns first.  flags selects the family as for tc_joint_*: with
+ * TC_FLAG_ASSEMBIAS n_theta is 7, and 7 stands wherever 5 does.
+ * One of two forms, chosen from the members' modes alone: a member of mode auto -- every bin's
+ * rows stay in LDS (the budget of the interpolator's mode-auto kernel with N rows, plus
+ * (6 + n_dim) rows per result row of the mode-cross members); all members mode cross -- the bins
+ * in slabs, any number of them (the budget of the interpolator's mode-cross kernel with N rows).
+ * A joint beyond the 160 KiB of a workgroup is TC_ERR_UNSUPPORTED with a message; the members
+ * stay usable.  A draw's results depend on the draw alone; the order of every sum is member 0's
+ * walk.  The rows of a mode-auto member, and of every member of an all-cross joint, are the bits
+ * of that member's own tc_interp_predict_grad_* call where its list agrees node for node with
+ * member 0's; ngal and dngal are member 0's bits; a joint of ONE member returns that member's
+ * bits in every form.
+ * Host arrays run slab-wise on lane 0 of member 0; the `_device` forms enqueue on its next lane
+ * and return (tc_joint_interp_synchronize waits). */
+int tc_joint_interp_predict_grad_batch(tc_joint_interp* joint, const double* theta, int n_theta,
+                                       const double* x, int64_t n_draws, int n_gauss_prim,
+                                       unsigned flags, double* ngal, double* xi, double* dngal,
+                                       double* dxi);
+int tc_joint_interp_predict_grad_batch_device(tc_joint_interp* joint, const double* theta_device,
+                                              int n_theta, const double* x_device,
+                                              int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                              double* ngal_device, double* xi_device,
+                                              double* dngal_device, double* dxi_device);
+/* chi2, its gradient and the Fisher matrix over (theta, x) of the joint data vector against the
+ * full (N, N) precision matrix, in the same launch (tc_joint_chi2_grad_batch with 5 + n_dim
+ * columns): fisher (n_draws, 5 + n_dim, 5 + n_dim) may be NULL: not asked for. */
+int tc_joint_interp_chi2_grad_batch(tc_joint_interp* joint, const double* theta, int n_theta,
+                                    const double* x, int64_t n_draws, int n_gauss_prim,
+                                    unsigned flags, const double* data, const double* precision,
+                                    double* ngal, double* chi2, double* dngal, double* dchi2,
+                                    double* fisher);
+int tc_joint_interp_chi2_grad_batch_device(tc_joint_interp* joint, const double* theta_device,
+                                           int n_theta, const double* x_device, int64_t n_draws,
+                                           int n_gauss_prim, unsigned flags, const double* data,
+                                           const double* precision, double* ngal_device,
+                                           double* chi2_device, double* dngal_device,
+                                           double* dchi2_device, double* fisher_device);
 
 /* Asynchronous host-to-host forms (page-locked theta, x, outputs; see
  * tc_predict_zheng07_batch_async): upload, kernels and download of a call on one of the

@@ -122,6 +122,14 @@ int tc_debug_triangle_parts(int n_rb, int n_parts, int32_t* rb0, int32_t* cb0, i
  * in all -- no device needed; chi2: the likelihood is finished in the launch; n_params 5 or 7. */
 int tc_debug_joint_lds_bytes(int n_bins, int n_central, int n_r_total, int chi2, int n_params,
                              int64_t* bytes);
+/* The LDS bytes per workgroup of grad_joint_interp_kernel (tabcorr_amd/csrc/joint_interp.h:
+ * joint_interp_lds_bytes) -- no device needed.  form 1: the rows form (a member is mode auto) of a
+ * joint over tables of n_bins bins, the first n_central centrals, with n_r_total result rows in
+ * all, n_r_cross of them those of mode-cross members; form 0: the slab form (every member mode
+ * cross; n_bins and n_central are not read, n_r_cross must be n_r_total).  n_dim: the grid's
+ * dimensions; n_params 5 or 7. */
+int tc_debug_joint_interp_lds_bytes(int form, int n_bins, int n_central, int n_r_total,
+                                    int n_r_cross, int n_dim, int n_params, int64_t* bytes);
 /* Groups of bins that share their Gauss-Legendre nodes (tabcorr_amd/csrc/hostmath.h:
  * find_node_groups; identical log_prim_haloprop_min / max and galaxy type), for n_bins bins in
  * library order of which the first n_central are centrals: group i = member[begin[i] ..

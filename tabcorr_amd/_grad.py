@@ -1,4 +1,5 @@
-"""The derivative calls of `TabCorr`, `Interpolator` and `JointLikelihood`: one
+"""The derivative calls of `TabCorr`, `Interpolator`, `JointLikelihood` and
+`JointInterpolator`: one
 helper allocates the outputs, calls the entry under the handle's lock, checks
 the status and returns the results reshaped.  Which entry serves a (handle
 kind, family, form) is `_lib.GRAD_ENTRIES`' to say."""
@@ -19,8 +20,8 @@ def family_of(assembias=False, family='zheng07'):
 def call(device, kind, family, inputs, n_cols, shape, operands=None,
          want_fisher=False):
     """The derivative entry of a handle `kind` (``'table'``, ``'interp'``,
-    ``'joint'``) and model `family` on `device` (the handle's wrapper, whose
-    lock the call holds).
+    ``'joint'``, ``'joint_interp'``) and model `family` on `device` (the
+    handle's wrapper, whose lock the call holds).
 
     `inputs` is what follows the handle up to the operands, the draws first:
     arrays are passed as pointers, everything else as it is.  `n_cols`

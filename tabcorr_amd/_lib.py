@@ -181,6 +181,12 @@ SIGNATURES = {
     'tc_joint_synchronize': [ctypes.c_void_p],
     'tc_joint_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p],
     'tc_debug_joint_lds_bytes': [ctypes.c_int] * 5 + [c_int64_p],
+    # joint of interpolators
+    'tc_joint_interp_create': [c_void_pp, ctypes.c_int, c_void_pp],
+    'tc_joint_interp_destroy': [ctypes.c_void_p],
+    'tc_joint_interp_synchronize': [ctypes.c_void_p],
+    'tc_joint_interp_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p],
+    'tc_debug_joint_interp_lds_bytes': [ctypes.c_int] * 7 + [c_int64_p],
     'tc_table_set_option': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int],
     'tc_table_timer_begin': [ctypes.c_void_p, ctypes.c_int],
     'tc_table_timer_end': [ctypes.c_void_p, c_float_p],
@@ -235,12 +241,13 @@ SIGNATURES = {
 # The gradient entries: (handle kind, family, form) -> the host-array symbol; the device-pointer
 # twin is `name + '_device'`.  Forms: 'predict' (ngal, xi, dngal, dxi), 'chi2' (ngal, chi2, dngal,
 # dchi2) and 'fisher' (the same with the Fisher matrix).  Plain Zheng07 has an entry of its own
-# for the Fisher matrix; the other families and the joint (whose family is in the flags) take a
-# trailing `fisher` that may be None.
+# for the Fisher matrix; the other families and the joints (whose family is in the flags) take a
+# trailing `fisher` that may be None.  A joint of interpolators takes x as an interpolator does.
 GRAD_ENTRIES = {}
 for _kind, _prefix, _families in (('table', 'tc_', ('zheng07', 'assembias', 'leauthaud11')),
                                   ('interp', 'tc_interp_', ('zheng07', 'assembias')),
-                                  ('joint', 'tc_joint_', (None, ))):
+                                  ('joint', 'tc_joint_', (None, )),
+                                  ('joint_interp', 'tc_joint_interp_', (None, ))):
     for _family in _families:
         _stem = '' if _family is None else '_' + _family
         for _form, _entry in (('predict', 'predict_grad'), ('chi2', 'chi2_grad'),
@@ -270,7 +277,7 @@ def _derivative_signatures():
         array = ctypes.c_void_p if device else c_double_p
         suffix = '_device' if device else ''
         for (kind, _, form), name in GRAD_ENTRIES.items():
-            head = [ctypes.c_void_p, array, ctypes.c_int] + [array] * (kind == 'interp')
+            head = [ctypes.c_void_p, array, ctypes.c_int] + [array] * (kind in ('interp', 'joint_interp'))
             head += [ctypes.c_int64, ctypes.c_int, ctypes.c_uint]
             operands = [c_double_p, c_double_p] * (form != 'predict')
             fisher = [array] * (form == 'fisher' or name in GRAD_OPTIONAL_FISHER)

@@ -237,6 +237,26 @@ int grad_entry(Adapter adapter, GradRoute where, GradRequest request, int n_thet
   });
 }
 
+// ---- what a joint of interpolators takes from its members (interp.cpp; joint_interp.cpp) -------
+// A member as the joint reads it: the tables in list order, their grid nodes (K, n_dim), the
+// axes, and the list index of the table at every position of the member's walk (class by class,
+// inside a class in list order).
+struct InterpParts {
+  int device;
+  int n_dim;
+  const std::vector<tc_table*>* tables;
+  const std::vector<std::vector<double>>* xp;
+  const std::vector<int32_t>* table_node;
+  std::vector<int32_t> walk;
+};
+InterpParts interp_parts(const tc_interp* it);
+// The argument block of an interpolator's derivative kernels but for the draws and the outputs:
+// the resident kernels of its tables stop, the walk and the classes' pointers are built.
+int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpArgs* ga);
+GradStaging interp_grad_staging(tc_interp* it);
+// The stream of the lane a derivative call takes: lane 0 (pinned) or the next of the rotation.
+hipStream_t interp_grad_stream(tc_interp* it, GradLane lane);
+
 }  // namespace host
 }  // namespace tc
 

@@ -26,6 +26,7 @@
 #include "fastmath.h"
 #include "grad.h"
 #include "joint.h"
+#include "joint_interp.h"
 #include "vjp.h"
 #include "hostmath.h"
 #include "kernel_args.h"
@@ -857,7 +858,7 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
                 const double* precision, double* chi2, hipStream_t stream);
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
-// inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_vjp.hip) ----
+// inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_joint_interp.hip, inst_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -892,6 +893,10 @@ int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
                          const tc::GradInterpArgs& ga);
 int launch_grad_joint_instance(int n_params, int device, dim3 grid, int lds, hipStream_t stream,
                                hipEvent_t k0, hipEvent_t k1, const tc::JointArgs& ja);
+// grad_joint_interp_kernel<n_params, form> (joint_interp.h: kJointInterpRows / kJointInterpSlabs)
+int launch_grad_joint_interp_instance(int n_params, int form, int device, dim3 grid, int lds,
+                                      hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
+                                      const tc::JointInterpArgs& ja);
 int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                         hipEvent_t k0, hipEvent_t k1, const tc::VjpArgs& va);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);

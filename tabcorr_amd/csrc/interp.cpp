@@ -1033,38 +1033,11 @@ struct InterpGrad {
   int device(GradLane lane, const GradRequest& request) const {
     TC_HIP(hipSetDevice(it->device));
     tc_table* t0 = it->tables[0];
-    int status = TC_OK;
-    for (tc_table* t : it->tables)
-      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-    const tc_interp::SinglePointers* pointers = nullptr;
-    status = class_pointers(it, request.n_gauss, &pointers);
-    if (status == TC_OK) status = build_grad_walk(it);
-    if (status != TC_OK) return status;
-    it->cur = next_lane(lane == GradLane::kPinned, t0->tuning.pipeline != 0, it->n_lanes,
-                        &it->device_calls);
-    tc_interp::Lane& L = it->lanes[it->cur];
-    const int n_params = request.n_params, n_dim = it->n_dim;
     tc::GradInterpArgs ga{};
-    fill_grad_shape(t0, request.n_gauss, request.flags, &ga.table);
-    ga.n_dim = n_dim;
-    ga.n_classes = (int)it->class_table.size();
-    for (int d = 0; d < n_dim; ++d) {
-      ga.n_axis[d] = (int)it->xp[d].size();
-      ga.axis_offset[d] = it->axis_offset[d];
-      ga.a_offset[d] = it->a_offset[d];
-    }
-    ga.xp = (const double*)it->d_xp;
-    ga.a = (const double*)it->d_a;
-    ga.class_begin = (const int32_t*)it->grad_walk.class_begin;
-    ga.walk_node = (const int32_t*)it->grad_walk.node;
-    ga.matrices = (const double* const*)it->grad_walk.matrices;
-    ga.class_log_m = (const double* const*)pointers->log_m;
-    ga.class_m = (const double* const*)pointers->m;
-    ga.class_weight = (const double* const*)pointers->weight;
-    ga.class_n_h = (const double* const*)pointers->n_h;
-    ga.class_percentile = n_params == tc::kGradParamsAssembias
-                              ? (const double* const*)pointers->percentile
-                              : nullptr;
+    const int status = interp_grad_args(it, request, &ga);
+    if (status != TC_OK) return status;
+    hipStream_t stream = interp_grad_stream(it, lane);
+    const int n_params = request.n_params;
     const int lds = (int)interp_grad_lds(it, request.likelihood(), n_params);
     return for_each_slab(request.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
       Range range("interpolator gradients (one launch)");
@@ -1075,8 +1048,7 @@ struct InterpGrad {
       slab.outputs(&ga.table);
       // (timed through the first table's timer)
       return launch_grad_batch(t0, n, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-        return launch_grad_instance(n_params, t0->mode, it->device, grid, lds, L.stream, k0, k1,
-                                    ga);
+        return launch_grad_instance(n_params, t0->mode, it->device, grid, lds, stream, k0, k1, ga);
       });
     });
   }
@@ -1105,6 +1077,70 @@ GradRequest interp_request(const tc_interp* it, int n_params, const double* thet
 }
 
 }  // namespace
+
+}  // extern "C"
+
+// ---- what a joint of interpolators takes from its members (grad_call.h) ---------------------
+namespace tc {
+namespace host {
+
+InterpParts interp_parts(const tc_interp* it) {
+  InterpParts parts{it->device, it->n_dim, &it->tables, &it->xp, &it->table_node, {}};
+  // (the order of build_grad_walk)
+  for (size_t v = 0; v < it->class_table.size(); ++v)
+    for (int k = 0; k < it->n_tables; ++k)
+      if (it->table_class[k] == (int32_t)v) parts.walk.push_back(k);
+  return parts;
+}
+
+int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpArgs* out) {
+  tc_table* t0 = it->tables[0];
+  int status = TC_OK;
+  for (tc_table* t : it->tables)
+    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  const tc_interp::SinglePointers* pointers = nullptr;
+  status = class_pointers(it, request.n_gauss, &pointers);
+  if (status == TC_OK) status = build_grad_walk(it);
+  if (status != TC_OK) return status;
+  const int n_dim = it->n_dim;
+  tc::GradInterpArgs& ga = *out;
+  fill_grad_shape(t0, request.n_gauss, request.flags, &ga.table);
+  ga.n_dim = n_dim;
+  ga.n_classes = (int)it->class_table.size();
+  for (int d = 0; d < n_dim; ++d) {
+    ga.n_axis[d] = (int)it->xp[d].size();
+    ga.axis_offset[d] = it->axis_offset[d];
+    ga.a_offset[d] = it->a_offset[d];
+  }
+  ga.xp = (const double*)it->d_xp;
+  ga.a = (const double*)it->d_a;
+  ga.class_begin = (const int32_t*)it->grad_walk.class_begin;
+  ga.walk_node = (const int32_t*)it->grad_walk.node;
+  ga.matrices = (const double* const*)it->grad_walk.matrices;
+  ga.class_log_m = (const double* const*)pointers->log_m;
+  ga.class_m = (const double* const*)pointers->m;
+  ga.class_weight = (const double* const*)pointers->weight;
+  ga.class_n_h = (const double* const*)pointers->n_h;
+  ga.class_percentile = request.n_params == tc::kGradParamsAssembias
+                            ? (const double* const*)pointers->percentile
+                            : nullptr;
+  return TC_OK;
+}
+
+GradStaging interp_grad_staging(tc_interp* it) {
+  return {&it->theta, &it->x, &it->out_ngal, &it->out_xi, it->stream};
+}
+
+hipStream_t interp_grad_stream(tc_interp* it, GradLane lane) {
+  it->cur = next_lane(lane == GradLane::kPinned, it->tables[0]->tuning.pipeline != 0, it->n_lanes,
+                      &it->device_calls);
+  return it->lanes[it->cur].stream;
+}
+
+}  // namespace host
+}  // namespace tc
+
+extern "C" {
 
 // ---- the plain model (`fisher` among the outputs of the tc_interp_chi2_fisher_* entries only,
 // where it must not be NULL) and the model decorated with assembly bias (seven columns of theta,

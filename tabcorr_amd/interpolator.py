@@ -61,7 +61,11 @@ class _HandleLocks:
 
     def __init__(self, tables):
         unique = {id(t.lock): t.lock for t in tables}
-        self._locks = [threading.RLock()] + [unique[k] for k in sorted(unique)]
+        # (a joint of interpolators takes the two parts of several handles in
+        # this order: joint._MemberLocks)
+        self.own = threading.RLock()
+        self.of_tables = [unique[k] for k in sorted(unique)]
+        self._locks = [self.own] + self.of_tables
 
     def __enter__(self):
         for lock in self._locks:

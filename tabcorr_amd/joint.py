@@ -279,3 +279,276 @@ class JointLikelihood:
             assembias=assembias)
         return (float(ngal[0]), float(chi2[0]), _grad.keyed(dngal[0], keys),
                 _grad.keyed(dchi2[0], keys), fisher[0])
+
+
+# ---- joint of interpolators ---------------------------------------------------
+
+MAX_MEMBERS = 16
+
+
+class _MemberLocks:
+    """The locks of every member of a joint of interpolators in one fixed
+    order: the interpolator handles' own locks first, then every table's, each
+    group by identity as `interpolator._HandleLocks` orders a handle's."""
+
+    def __init__(self, devices):
+        own = {id(d.lock.own): d.lock.own for d in devices}
+        tables = {id(lock): lock for d in devices for lock in d.lock.of_tables}
+        self.locks = ([own[k] for k in sorted(own)] +
+                      [tables[k] for k in sorted(tables)])
+
+    __enter__ = _Locks.__enter__
+    __exit__ = _Locks.__exit__
+
+
+class _DeviceJointInterp:
+    """Owner of a ``tc_joint_interp`` handle; keeps its members' handles
+    alive.  The joint works through its members and their tables: every call
+    sits behind `lock`, all of their locks."""
+
+    def __init__(self, devices):
+        self.lib = devices[0].lib
+        self.devices = devices
+        handles = (ctypes.c_void_p * len(devices))(
+            *[d.handle.value for d in devices])
+        handle = ctypes.c_void_p()
+        _lib.check(self.lib.tc_joint_interp_create(
+            handles, len(devices), ctypes.byref(handle)))
+        self.handle = handle
+        self.lock = _MemberLocks(devices)
+
+    def __del__(self):
+        handle = getattr(self, 'handle', None)
+        if handle is not None and handle.value is not None:
+            try:
+                self.lib.tc_joint_interp_destroy(handle)
+            except Exception:  # interpreter shutdown
+                pass
+            self.handle = None
+
+
+def _grid_nodes(interpolator):
+    """The grid node (one index per axis) of every table of the list."""
+    return [tuple(int(np.searchsorted(xp, value))
+                  for xp, value in zip(interpolator.xp, point))
+            for point in interpolator.points]
+
+
+class JointInterpolator:
+    """``JointInterpolator([interp_wp, interp_ds])``: 1 to 16 `Interpolator`
+    members built over the same grid -- the same ``keys`` in the same order,
+    bit-identical abscissae per axis -- whose tables share their ``gal_type``
+    table grid node by grid node (the reference's AbacusSummit database reads
+    a ``wp`` and a ``ds`` interpolator for one model).  A member is mode
+    ``'auto'`` or mode ``'cross'`` throughout; the members may differ, and so
+    may the orders of their lists: tables are matched by grid node, and the
+    walk over the grid is member 0's.
+
+    The members' results are concatenated in list order: member ``m`` owns
+    ``joint.slices[m]`` of the ``joint.n_r_total`` entries of ``data`` and of
+    the rows and columns of ``precision``.  Derivatives have ``5 + D`` columns
+    -- `ZHENG07_KEYS`, then ``joint.keys`` -- and ``7 + D`` with
+    ``assembias=True``.  One kernel launch per call (``tc_joint_interp_*``,
+    ``include/tabcorr_amd.h``): the occupations of every class of halo tables
+    once for all members, and chi2, its gradient and the Fisher matrix over
+    ``(theta, x)`` against the full ``(N, N)`` precision matrix.
+    """
+
+    def __init__(self, interpolators):
+        from .interpolator import Interpolator
+        self.interpolators = list(interpolators)
+        n_members = len(self.interpolators)
+        if n_members < 1 or n_members > MAX_MEMBERS:
+            raise ValueError('A joint takes 1 to {} interpolators, got '
+                             '{}.'.format(MAX_MEMBERS, n_members))
+        for m, member in enumerate(self.interpolators):
+            if not isinstance(member, Interpolator):
+                raise ValueError(
+                    'Member {} is not an Interpolator.'.format(m))
+            if any(member is other for other in self.interpolators[:m]):
+                raise ValueError(
+                    'Member {} appears twice in the joint.'.format(m))
+        first = self.interpolators[0]
+        nodes = {node: k for k, node in enumerate(_grid_nodes(first))}
+        for m, member in enumerate(self.interpolators):
+            if list(member.keys) != list(first.keys):
+                raise ValueError('Member {} does not have the keys of member '
+                                 '0, in their order.'.format(m))
+            if any(a.tobytes() != b.tobytes()
+                   for a, b in zip(member.xp, first.xp)):
+                raise ValueError('Member {} does not have the abscissae of '
+                                 'member 0.'.format(m))
+            mine = _grid_nodes(member)
+            if sorted(mine) != sorted(nodes):
+                raise ValueError('Member {} does not have the grid points of '
+                                 'member 0.'.format(m))
+            modes = {halotab.attrs['mode'] for halotab in member.tabcorr_list}
+            if len(modes) != 1:
+                raise ValueError('Member {} mixes the modes of its '
+                                 'tables.'.format(m))
+            for k, halotab in enumerate(member.tabcorr_list):
+                if halotab.compute_dtype != 'float64':
+                    raise ValueError('Member {}: table {} does not have a '
+                                     'float64 compute dtype.'.format(m, k))
+                partner = first.tabcorr_list[nodes[mine[k]]]
+                if not _same_bins(halotab.gal_type, partner.gal_type):
+                    raise ValueError(
+                        'Member {}: table {} does not have the gal_type table '
+                        "of member 0's table at its grid node.".format(m, k))
+        self.keys = list(first.keys)
+        sizes = [len(member.tabcorr_list[0].tpcf_matrix)
+                 for member in self.interpolators]
+        offsets = np.concatenate([[0], np.cumsum(sizes)])
+        self.slices = [slice(int(offsets[m]), int(offsets[m + 1]))
+                       for m in range(n_members)]
+        self.n_r_total = int(offsets[-1])
+        self._device = None
+
+    def to_device(self):
+        """Upload the members and create the joint handle (done lazily by the
+        first call)."""
+        devices = [member.to_device() for member in self.interpolators]
+        if self._device is None or any(
+                a is not b for a, b in zip(self._device.devices, devices)):
+            self._device = _DeviceJointInterp(devices)
+        return self._device
+
+    # -- arguments ------------------------------------------------------------
+
+    _operands = JointLikelihood._operands
+
+    def _split(self, array, leading):
+        return [np.ascontiguousarray(array[..., part]).reshape(
+            leading + tuple(member.tabcorr_list[0].tpcf_shape))
+            for part, member in zip(self.slices, self.interpolators)]
+
+    def _inputs(self, theta, x, extrapolate, assembias, family):
+        """``theta (n, 5)`` -- ``(n, 7)`` decorated -- and ``x (n, D)``,
+        checked before any device is touched (`Interpolator._grad_inputs`)."""
+        _zheng07_only(family)
+        return self.interpolators[0]._grad_inputs(theta, x, extrapolate,
+                                                  assembias)
+
+    def _grad_call(self, theta, x, n_gauss_prim, modulate_with_cenocc,
+                   assembias, operands=None, want_fisher=False):
+        """The derivative entry for checked ``(theta, x)``: the results on the
+        joint axis of ``n_r_total`` entries; the family is in the flags."""
+        return _grad.call(
+            self.to_device(), 'joint_interp', _grad.family_of(assembias),
+            [theta, theta.shape[1], x, len(theta), n_gauss_prim,
+             _flags(False, modulate_with_cenocc, assembias)],
+            theta.shape[1] + len(self.keys), (self.n_r_total, ), operands,
+            want_fisher)
+
+    # -- batched calls --------------------------------------------------------
+
+    def predict_batch_grad(self, theta, x, n_gauss_prim=10, extrapolate=False,
+                           modulate_with_cenocc=False, assembias=False,
+                           family='zheng07'):
+        """`Interpolator.predict_batch_grad` of every member in one launch.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )`` -- the members share their halo tables
+        xis : list, per member ``(n_draws, ) + tpcf_shape``
+        dngal : ``(n_draws, 5 + D)``
+        dxis : list, per member ``(n_draws, 5 + D) + tpcf_shape``
+
+        Raises ``ValueError`` for ``x`` outside the grid unless
+        ``extrapolate``, ``NotImplementedError`` for
+        ``family='leauthaud11'`` and for a joint whose rows do not fit the
+        kernel's LDS.
+        """
+        theta, x = self._inputs(theta, x, extrapolate, assembias, family)
+        n_draws = len(theta)
+        ngal, xi, dngal, dxi = self._grad_call(
+            theta, x, n_gauss_prim, modulate_with_cenocc, assembias)
+        return (ngal, self._split(xi, (n_draws, )), dngal,
+                self._split(dxi, (n_draws, dngal.shape[1])))
+
+    def _chi2(self, theta, x, data, precision, n_gauss_prim, extrapolate,
+              modulate_with_cenocc, assembias, want_fisher, family):
+        theta, x = self._inputs(theta, x, extrapolate, assembias, family)
+        operands = self._operands(data, precision)
+        return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
+                               assembias, operands, want_fisher)
+
+    def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
+                        extrapolate=False, modulate_with_cenocc=False,
+                        assembias=False, family='zheng07'):
+        """chi2 of the concatenated data vector and its gradient with respect
+        to ``(theta, x)`` (`Interpolator.chi2_grad_batch` with ``N`` for
+        ``n_r``): ``ngal, chi2`` ``(n_draws, )``, ``dngal, dchi2``
+        ``(n_draws, 5 + D)``.  ``data`` is flat ``(N, )`` or a list of
+        per-member arrays, ``precision`` ``(N, N)``."""
+        return self._chi2(theta, x, data, precision, n_gauss_prim, extrapolate,
+                          modulate_with_cenocc, assembias, False, family)
+
+    def chi2_fisher_batch(self, theta, x, data, precision, n_gauss_prim=10,
+                          extrapolate=False, modulate_with_cenocc=False,
+                          assembias=False, family='zheng07'):
+        """`chi2_grad_batch` with the Fisher matrix ``fisher[:, k, l] =
+        dxi_k^T P_sym dxi_l`` of the joint data vector over ``(theta, x)``,
+        ``(n_draws, 5 + D, 5 + D)``, from the same launch: the off-diagonal
+        blocks of ``precision`` couple the members."""
+        return self._chi2(theta, x, data, precision, n_gauss_prim, extrapolate,
+                          modulate_with_cenocc, assembias, True, family)
+
+    def fisher_batch(self, theta, x, precision, n_gauss_prim=10,
+                     extrapolate=False, modulate_with_cenocc=False,
+                     assembias=False, family='zheng07'):
+        """The forecast form, which needs no data: ``ngal, dngal, fisher``."""
+        ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
+            theta, x, np.zeros(self.n_r_total), precision,
+            n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
+            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
+            family=family)
+        return ngal, dngal, fisher
+
+    # -- un-batched forms -----------------------------------------------------
+
+    def _model_inputs(self, model, check_consistency, assembias, what):
+        x = self.interpolators[0]._x_model(model)
+        if check_consistency:
+            for member in self.interpolators:
+                for halotab in member.tabcorr_list:
+                    halotab._check_consistency_cached(model)
+        spec = _grad_spec(model, assembias, what)
+        model_keys = tuple(_grad_keys(assembias))
+        theta = np.asarray(spec.theta,
+                           dtype=np.float64)[np.newaxis, :len(model_keys)]
+        return spec, model_keys + tuple(self.keys), theta, x[np.newaxis]
+
+    def predict_grad(self, model, n_gauss_prim=10, extrapolate=False,
+                     check_consistency=True, assembias=False):
+        """Un-batched `predict_batch_grad` for a model object whose
+        ``param_dict`` holds the extra parameters, as
+        `Interpolator.predict_grad`: ``ngal`` (float), ``xis`` (list of arrays
+        of each member's ``tpcf_shape``), ``dngal`` (dict by the model keys,
+        then ``self.keys``) and ``dxis`` (dict by the same keys of lists)."""
+        spec, keys, theta, x = self._model_inputs(
+            model, check_consistency, assembias, 'predict_grad')
+        ngal, xis, dngal, dxis = self.predict_batch_grad(
+            theta, x, n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
+        return (float(ngal[0]), [xi[0] for xi in xis],
+                _grad.keyed(dngal[0], keys),
+                {key: [dxi[0, k] for dxi in dxis]
+                 for k, key in enumerate(keys)})
+
+    def chi2_fisher(self, model, data, precision, n_gauss_prim=10,
+                    extrapolate=False, check_consistency=True,
+                    assembias=False):
+        """Un-batched `chi2_fisher_batch` for a model object: ``ngal``,
+        ``chi2`` (floats), ``dngal``, ``dchi2`` (dicts by the model keys, then
+        ``self.keys``) and ``fisher`` ``(5 + D, 5 + D)`` in that order."""
+        spec, keys, theta, x = self._model_inputs(
+            model, check_consistency, assembias, 'chi2_fisher')
+        ngal, chi2, dngal, dchi2, fisher = self.chi2_fisher_batch(
+            theta, x, data, precision, n_gauss_prim=n_gauss_prim,
+            extrapolate=extrapolate,
+            modulate_with_cenocc=spec.modulate_with_cenocc,
+            assembias=assembias)
+        return (float(ngal[0]), float(chi2[0]), _grad.keyed(dngal[0], keys),
+                _grad.keyed(dchi2[0], keys), fisher[0])

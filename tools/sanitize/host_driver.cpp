@@ -4,7 +4,8 @@
 // chunking, the quadratic-form layout / schedule / table fill / emulation, spline
 // matrices, quadrature nodes, the fast-math tables, the pair counter's cell sort and label-block
 // plan, the choice of the one-launch form, the slabs of a derivative call, the chunk plan and the
-// chunks of a forward call) over a sweep of shapes
+// chunks of a forward call, the LDS budgets and the node matching of a joint of interpolators)
+// over a sweep of shapes
 // and checks the results against direct evaluations.  Exit status 0 = all
 // checks passed and no sanitizer report (-fno-sanitize-recover aborts on the first).
 //
@@ -20,6 +21,7 @@
 #include "../../tabcorr_amd/csrc/fastmath.h"
 #include "../../tabcorr_amd/csrc/grad_call.h"
 #include "../../tabcorr_amd/csrc/hostmath.h"
+#include "../../tabcorr_amd/csrc/joint_interp.h"
 #include "../../tabcorr_amd/csrc/kernel_args.h"
 #include "../../tabcorr_amd/csrc/predict_call.h"
 
@@ -561,7 +563,71 @@ static void check_forward_calls() {
       }
 }
 
+// joint_interp.h: the LDS budgets of both forms against the interpolator kernels' own with N rows,
+// and joint_interp_permutation on shuffled grids of one to three axes: every walk position finds
+// the member's table at its node, and a member with a node twice (another one missing) is refused.
+static void check_joint_interp() {
+  for (int n_params : {tc::kGradParams, tc::kGradParamsAssembias})
+    for (int n_dim : {1, 2, tc::kGradMaxDim})
+      for (int n_bins : {1, 18, 100, 1104})
+        for (int n_r_total : {1, 8, 26, 38}) {
+          const int n_central = n_bins / 2;
+          const size_t row = (size_t)tc::kGradDraws * sizeof(double);
+          EXPECT(tc::joint_interp_lds_bytes(tc::kJointInterpSlabs, n_bins, n_central, n_r_total,
+                                            n_r_total, n_dim, n_params) ==
+                     tc::grad_interp_cross_lds_bytes(n_r_total, n_dim, false, n_params),
+                 "slab budget of %d rows", n_r_total);
+          for (int n_r_cross : {0, 1, n_r_total - 1}) {
+            if (n_r_cross < 0 || n_r_cross >= n_r_total) continue;
+            EXPECT(tc::joint_interp_lds_bytes(tc::kJointInterpRows, n_bins, n_central, n_r_total,
+                                              n_r_cross, n_dim, n_params) ==
+                       tc::grad_interp_auto_lds_bytes(n_bins, n_central, n_r_total, n_dim, false,
+                                                      n_params) +
+                           (size_t)(n_params + 1 + n_dim) * n_r_cross * row,
+                   "rows budget of %d bins, %d rows, %d cross", n_bins, n_r_total, n_r_cross);
+          }
+        }
+  const int modes[3] = {TC_MODE_CROSS, TC_MODE_AUTO, TC_MODE_CROSS};
+  EXPECT(tc::joint_interp_form(modes, 3) == tc::kJointInterpRows &&
+             tc::joint_interp_form(modes, 1) == tc::kJointInterpSlabs &&
+             tc::joint_interp_form(modes + 2, 1) == tc::kJointInterpSlabs,
+         "form by the members' modes");
+  std::mt19937_64 rng(8);
+  const int axis[3] = {4, 5, 3};
+  for (int n_dim = 1; n_dim <= 3; ++n_dim) {
+    int n_tables = 1;
+    for (int d = 0; d < n_dim; ++d) n_tables *= axis[d];
+    std::vector<int32_t> node0((size_t)n_tables * n_dim);
+    for (int k = 0; k < n_tables; ++k) {
+      int rest = k;
+      for (int d = 0; d < n_dim; ++d) {
+        node0[(size_t)k * n_dim + d] = rest % axis[d];
+        rest /= axis[d];
+      }
+    }
+    std::vector<int32_t> walk0(n_tables), order(n_tables), found(n_tables);
+    std::iota(walk0.begin(), walk0.end(), 0);
+    std::iota(order.begin(), order.end(), 0);
+    std::shuffle(walk0.begin(), walk0.end(), rng);
+    std::shuffle(order.begin(), order.end(), rng);
+    std::vector<int32_t> node((size_t)n_tables * n_dim);
+    for (int k = 0; k < n_tables; ++k)
+      for (int d = 0; d < n_dim; ++d)
+        node[(size_t)k * n_dim + d] = node0[(size_t)order[k] * n_dim + d];
+    EXPECT(tc::joint_interp_permutation(n_tables, n_dim, walk0.data(), node0.data(), node.data(),
+                                        found.data()),
+           "a shuffled member of %d axes is refused", n_dim);
+    for (int s = 0; s < n_tables; ++s)
+      EXPECT(order[found[s]] == walk0[s], "walk position %d finds table %d", s, found[s]);
+    for (int d = 0; d < n_dim; ++d) node[d] = node[n_dim + d];
+    EXPECT(!tc::joint_interp_permutation(n_tables, n_dim, walk0.data(), node0.data(), node.data(),
+                                         found.data()),
+           "a member with a node twice is accepted");
+  }
+}
+
 int main() {
+  check_joint_interp();
   check_forward_calls();
   check_grad_slabs();
   check_quadrature();
