@@ -587,6 +587,37 @@ int tc_joint_chi2_grad_batch_device(tc_joint* joint, const double* theta_device,
                                     double* ngal_device, double* chi2_device,
                                     double* dngal_device, double* dchi2_device,
                                     double* fisher_device);
+/* The forward form, what an ensemble sampler asks per step: the concatenated prediction -- ngal
+ * (n_draws), xi (n_draws, N) -- or chi2 (n_draws) of the joint data vector against the full
+ * precision matrix, chi2 = (xi - data)^T precision (xi - data) with xi never stored, in ONE launch
+ * per batch without any derivative: the occupations once per draw, every mode-auto table's packed
+ * triangle (its own forward unit layout) on the matrix cores, every mode-cross table by one fma
+ * chain per row over the bins in library order.  The arguments are those of
+ * tc_joint_chi2_grad_batch without the derivative outputs; n_theta 5, or 7 with
+ * TC_FLAG_ASSEMBIAS; flags may also hold TC_FLAG_MODULATE_WITH_CENOCC.  data and precision are
+ * host arrays in both forms (uploaded when they change).
+ * TC_ERR_UNSUPPORTED with a message, the joint and its tables staying usable:
+ * TC_FLAG_SEPARATE_GAL_TYPE, TC_FLAG_LEAUTHAUD11, any other flag; a mode-auto table of more than
+ * 20 correlation function bins (one r tile) or without the unit layout of the one-launch form
+ * (more than 248 bins); a workgroup beyond 160 KiB of LDS: 8 x (max(64 x bins in whole fours,
+ * 65 N) + max(2306, N (N + 1)) + 1024 + 256 N) bytes.
+ * A draw's results depend on the draw alone: not on the batch, its place in it, or the entry
+ * point; ngal does not depend on the tables.  Where ngal = 0 the results are what IEEE arithmetic
+ * gives.  Host arrays take the forward path of the tables (page-locked staging for small calls,
+ * overlapping chunks beyond) on the first table's staging areas and lanes; the `_device` forms
+ * enqueue on its next lane and return (tc_joint_synchronize waits). */
+int tc_joint_predict_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
+                           int n_gauss_prim, unsigned flags, double* ngal, double* xi);
+int tc_joint_predict_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
+                                  int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                  double* ngal_device, double* xi_device);
+int tc_joint_chi2_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
+                        int n_gauss_prim, unsigned flags, const double* data,
+                        const double* precision, double* ngal, double* chi2);
+int tc_joint_chi2_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
+                               int64_t n_draws, int n_gauss_prim, unsigned flags,
+                               const double* data, const double* precision, double* ngal_device,
+                               double* chi2_device);
 
 /* Joint likelihood of several interpolators (extension): the reference's AbacusSummit database
  * and its own suite read TWO interpolators, `wp` and `ds`, built over the same grid of simulations,

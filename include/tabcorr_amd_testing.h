@@ -122,6 +122,17 @@ int tc_debug_triangle_parts(int n_rb, int n_parts, int32_t* rb0, int32_t* cb0, i
  * in all -- no device needed; chi2: the likelihood is finished in the launch; n_params 5 or 7. */
 int tc_debug_joint_lds_bytes(int n_bins, int n_central, int n_r_total, int chi2, int n_params,
                              int64_t* bytes);
+/* The LDS bytes per workgroup of joint_forward_kernel (tabcorr_amd/csrc/joint.h:
+ * joint_forward_lds_bytes) for tables of n_bins bins, n_r_total result rows in all and `waves`
+ * waves per workgroup (the kernel's: 8) -- no device needed. */
+int tc_debug_joint_forward_lds_bytes(int n_bins, int n_r_total, int waves, int64_t* bytes);
+/* What the forward entries of a joint refuse on the host, from plain numbers -- no device, no
+ * handle: n_tables tables of n_bins bins with mode[k] (0 auto, 1 cross), n_r[k] correlation
+ * function bins and compute_dtype[k] (TC_DTYPE_*).  TC_OK and the workgroup's LDS in *lds_bytes
+ * (may be NULL), or TC_ERR_UNSUPPORTED with the entry's message: a member that is not float64, a
+ * mode-auto member of more than 20 r bins, a workgroup beyond 160 KiB (*lds_bytes is set). */
+int tc_debug_joint_forward_fit(int n_bins, int n_tables, const int* mode, const int* n_r,
+                               const int* compute_dtype, int64_t* lds_bytes);
 /* The LDS bytes per workgroup of grad_joint_interp_kernel (tabcorr_amd/csrc/joint_interp.h:
  * joint_interp_lds_bytes) -- no device needed.  form 1: the rows form (a member is mode auto) of a
  * joint over tables of n_bins bins, the first n_central centrals, with n_r_total result rows in

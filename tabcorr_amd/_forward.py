@@ -40,7 +40,7 @@ def _run(device, kind, form, route, inputs, operands, outputs, *ticket):
 
 def call(device, kind, form, inputs, shapes, operands=(), out=None):
     """The synchronous host-array entry of a handle `kind` (``'table'``,
-    ``'interp'``) and `form` (``'predict'``, ``'chi2'``) on `device`, the
+    ``'interp'``, ``'joint'``: a joint of tables, called as a table) and `form` (``'predict'``, ``'chi2'``) on `device`, the
     handle's wrapper.  `out`: the caller's arrays for the results, else new
     ones (allocated in the order of the C arguments, as `_grad.call`)."""
     outputs = (empty(shapes[0]), empty(shapes[1])) if out is None else \

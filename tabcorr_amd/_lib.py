@@ -181,6 +181,24 @@ SIGNATURES = {
     'tc_joint_synchronize': [ctypes.c_void_p],
     'tc_joint_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p],
     'tc_debug_joint_lds_bytes': [ctypes.c_int] * 5 + [c_int64_p],
+    # ... its forward entries: a table's without the `_zheng07` (the family is in the flags)
+    'tc_joint_predict_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p],
+    'tc_joint_predict_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p],
+    'tc_joint_chi2_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, c_double_p,
+        c_double_p],
+    'tc_joint_chi2_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+        ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
+        ctypes.c_void_p],
+    'tc_debug_joint_forward_lds_bytes': [ctypes.c_int] * 3 + [c_int64_p],
+    'tc_debug_joint_forward_fit': [ctypes.c_int, ctypes.c_int, c_int_p, c_int_p, c_int_p,
+                                   c_int64_p],
     # joint of interpolators
     'tc_joint_interp_create': [c_void_pp, ctypes.c_int, c_void_pp],
     'tc_joint_interp_destroy': [ctypes.c_void_p],
@@ -264,6 +282,11 @@ FORWARD_ENTRIES = {
     for _kind, _prefix in (('table', ''), ('interp', 'interp_'))
     for _form in ('predict', 'chi2')
     for _route, _suffix in (('host', ''), ('device', '_device'), ('async', '_async'))}
+# (a joint of tables: the family is in the flags, and there are no asynchronous entries)
+FORWARD_ENTRIES.update({
+    ('joint', _form, _route): 'tc_joint_%s_batch%s' % (_form, _suffix)
+    for _form in ('predict', 'chi2')
+    for _route, _suffix in (('host', ''), ('device', '_device'))})
 
 
 def _derivative_signatures():

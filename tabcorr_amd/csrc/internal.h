@@ -858,7 +858,8 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
                 const double* precision, double* chi2, hipStream_t stream);
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
-// inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_joint_interp.hip, inst_vjp.hip) ----
+// inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_joint_forward.hip,
+// inst_joint_interp.hip, inst_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -893,6 +894,10 @@ int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
                          const tc::GradInterpArgs& ga);
 int launch_grad_joint_instance(int n_params, int device, dim3 grid, int lds, hipStream_t stream,
                                hipEvent_t k0, hipEvent_t k1, const tc::JointArgs& ja);
+// joint_forward_kernel<n_gauss (10, else any), assembias, modulate> (inst_joint_forward.hip)
+int launch_joint_forward_instance(int n_gauss, bool assembias, bool modulate, int device,
+                                  dim3 grid, int lds, hipStream_t stream, hipEvent_t k0,
+                                  hipEvent_t k1, const tc::JointForwardArgs& ja);
 // grad_joint_interp_kernel<n_params, form> (joint_interp.h: kJointInterpRows / kJointInterpSlabs)
 int launch_grad_joint_interp_instance(int n_params, int form, int device, dim3 grid, int lds,
                                       hipStream_t stream, hipEvent_t k0, hipEvent_t k1,

@@ -4,6 +4,9 @@
 // against the full (N, N) precision matrix.  The handle works THROUGH its tables, as an
 // interpolator does: the quadrature, the lanes, the staging buffers and the kernel timer are the
 // first table's, the matrices every table's own (launch.hip: build_grad_table).
+// The forward entries -- the concatenated prediction or chi2 alone -- take ONE launch of
+// joint_forward_kernel (joint_forward_kernels.hip.h) on the mode-auto tables' own forward unit
+// layouts, and the forward call path of the tables (predict_call.h) through the first table.
 #include "internal.h"
 
 using namespace tc::host;
@@ -99,6 +102,258 @@ GradRequest joint_request(const tc_joint* joint, const double* theta, int64_t n_
   request.dvalue = dvalue;
   request.fisher = fisher;
   return request;
+}
+
+// ---- forward calls (joint_forward_kernels.hip.h; predict_call.h) --------------------------------
+
+// What joint_forward_kernel does not serve, from plain numbers (tc_debug_joint_forward_fit asks
+// with them too): a member that is not float64, a mode-auto member beyond one r tile, a workgroup
+// beyond the LDS of a CU.  *lds_bytes: the workgroup's LDS, where the members are served.
+int joint_forward_fit(int n_bins, int n_tables, const int* mode, const int* n_r, const int* dtype,
+                      int64_t* lds_bytes) {
+  int total = 0;
+  for (int k = 0; k < n_tables; ++k) {
+    if (dtype[k] != TC_DTYPE_F64)
+      return fail(TC_ERR_UNSUPPORTED,
+                  "joint forward calls need a float64 compute dtype: table %d has none", k);
+    if (mode[k] == TC_MODE_AUTO && n_r[k] > 4 * tc::kQuadMaxU)
+      return fail(TC_ERR_UNSUPPORTED,
+                  "joint forward calls: table %d (mode auto) has %d correlation function bins, "
+                  "more than the one r tile of %d that the one-launch form serves",
+                  k, n_r[k], 4 * tc::kQuadMaxU);
+    total += n_r[k];
+  }
+  const size_t lds = tc::joint_forward_lds_bytes(n_bins, total, tc::kJointForwardWaves);
+  if (lds_bytes != nullptr) *lds_bytes = (int64_t)lds;
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "joint forward calls: tables of %d bins and %d correlation function bins in all "
+                "need %zu bytes of LDS per workgroup, beyond the %d there are",
+                n_bins, total, lds, kMaxLdsBytes);
+  return TC_OK;
+}
+
+// The arguments of a forward entry point, the NULL handle first; then what the kernel refuses.
+int check_joint_forward(const tc_joint* joint, const PredictRequest& request) {
+  TC_CHECK(joint != nullptr, "joint handle is NULL");
+  const unsigned flags = request.flags;
+  if (flags & TC_FLAG_SEPARATE_GAL_TYPE)
+    return fail(TC_ERR_UNSUPPORTED, "joint forward calls are implemented for the total "
+                                    "prediction only (not separate_gal_type)");
+  if (flags & TC_FLAG_LEAUTHAUD11)
+    return fail(TC_ERR_UNSUPPORTED, "joint forward calls are implemented for the Zheng07 family "
+                                    "only");
+  const unsigned unserved =
+      flags & ~(unsigned)(TC_FLAG_MODULATE_WITH_CENOCC | TC_FLAG_ASSEMBIAS);
+  if (unserved != 0)
+    return fail(TC_ERR_UNSUPPORTED, "joint forward calls: unknown flags 0x%x", unserved);
+  const tc_table* t0 = joint->tables[0];
+  int status = check_predict_args(t0, request.theta, request.n_theta, request.n_draws,
+                                  request.n_gauss, flags);
+  if (status != TC_OK) return status;
+  const int n_tables = (int)joint->tables.size();
+  int mode[tc::kJointMaxTables], n_r[tc::kJointMaxTables], dtype[tc::kJointMaxTables];
+  for (int k = 0; k < n_tables; ++k) {
+    mode[k] = joint->tables[k]->mode;
+    n_r[k] = joint->tables[k]->n_r;
+    dtype[k] = joint->tables[k]->compute_dtype;
+  }
+  status = joint_forward_fit(t0->n_bins, n_tables, mode, n_r, dtype, nullptr);
+  if (status != TC_OK) return status;
+  for (int k = 0; k < n_tables; ++k) {
+    const tc_table* t = joint->tables[k];
+    if (t->mode != TC_MODE_AUTO) continue;
+    const tc::QuadLayout& layout = t->quad_total.layout;
+    if (!(t->quad && t->quad_total.d_table != nullptr && t->quad_tiling.n_rtiles == 1 &&
+          layout.comps.size() == 1 && layout.comps[0].triangular))
+      return fail(TC_ERR_UNSUPPORTED,
+                  "joint forward calls: table %d (mode auto, %d bins) does not have the unit "
+                  "layout of the one-launch form", k, t->n_bins);
+  }
+  return TC_OK;
+}
+
+// The argument block but for the draws and the outputs: the resident kernels of the tables stop,
+// the mode-cross matrices are built (launch.hip: build_grad_table), the passes are numbered.
+int joint_forward_args(tc_joint* joint, int n_theta, int n_gauss, unsigned flags,
+                       tc::JointForwardArgs* out) {
+  tc_table* t0 = joint->tables[0];
+  tc::JointForwardArgs ja{};
+  ja.n_theta = n_theta;
+  ja.n_bins = t0->n_bins;
+  ja.n_central = t0->plan.n_central;
+  ja.n_gauss = n_gauss;
+  ja.dens_rows = (t0->n_bins + 3) / 4 * 4;
+  ja.n_r = joint->n_r_total;
+  Quadrature* q = nullptr;
+  int status = get_quadrature(t0, n_gauss, &q);
+  if (status != TC_OK) return status;
+  ja.log_m = (const double*)q->log_m;
+  ja.m = (const double*)q->m;
+  ja.weight = (const double*)q->weight;
+  ja.n_h = (const double*)t0->d_n_h;
+  ja.percentile = (const double*)t0->d_percentile;
+  ja.split = 0.5;
+  ja.math_table = (const double*)t0->d_math_table;
+  ja.n_tables = (int)joint->tables.size();
+  const int parts = tc::joint_forward_parts(tc::kJointForwardWaves);
+  bool first_auto = true;
+  for (int k = 0; k < ja.n_tables; ++k) {
+    tc_table* t = joint->tables[k];
+    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+    ja.mode[k] = t->mode;
+    ja.n_rows[k] = t->n_r;
+    ja.r_offset[k] = joint->r_offset[k];
+    ja.job_begin[k + 1] = ja.job_begin[k];
+    if (t->mode == TC_MODE_AUTO) {
+      const tc::QuadComp& comp = t->quad_total.layout.comps[0];
+      const int n_u = t->quad_tiling.n_u;
+      ja.matrix[k] = t->quad_total.d_table;
+      ja.n_u[k] = n_u;
+      ja.table_bytes[k] =
+          (uint32_t)((size_t)t->quad_total.layout.n_units * (size_t)((n_u + 1) / 2) * 1024);
+      ja.job_begin[k + 1] += (n_u + 1) / 2 * 2 * parts;
+      if (first_auto) {
+        tc::triangle_parts(comp.n_rb, parts, ja.part_rb0, ja.part_cb0, ja.part_count);
+        ja.n_cb = comp.n_cb;
+        ja.i_row0 = comp.i_bin0;
+        ja.j_row0 = comp.j_bin0;
+        ja.unit_base = (int)comp.unit_base;
+        first_auto = false;
+      }
+    } else {
+      if ((status = build_grad_table(t)) != TC_OK) return status;
+      ja.matrix[k] = t->grad.d_matrix;
+    }
+  }
+  *out = ja;
+  return TC_OK;
+}
+
+// One launch per slab of the draws of `r` (device pointers) on `stream`, timed and reported
+// through the first table.
+int joint_forward_launches(tc_joint* joint, const tc::JointForwardArgs& shape,
+                           const PredictRequest& r, hipStream_t stream) {
+  Range range("joint forward (one launch)");
+  tc_table* t0 = joint->tables[0];
+  const int lds = (int)tc::joint_forward_lds_bytes(shape.n_bins, shape.n_r,
+                                                   tc::kJointForwardWaves);
+  return for_each_slab(r.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
+    const PredictRequest slab = r.chunk(begin, n);
+    tc::JointForwardArgs ja = shape;
+    ja.theta = slab.theta;
+    ja.n_draws = n;
+    ja.ngal = slab.ngal;
+    ja.xi = r.likelihood ? nullptr : slab.second;
+    ja.chi2_data = r.likelihood ? joint->chi2.device() : nullptr;
+    ja.chi2 = r.likelihood ? slab.second : nullptr;
+    const dim3 grid((unsigned)((n + tc::kJointForwardDraws - 1) / tc::kJointForwardDraws));
+    hipEvent_t k0 = nullptr, k1 = nullptr;
+    int status = next_kernel_events(t0, &k0, &k1);
+    if (status != TC_OK) return status;
+    status = launch_joint_forward_instance(
+        shape.n_gauss, (r.flags & TC_FLAG_ASSEMBIAS) != 0,
+        (r.flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0, t0->device, grid, lds, stream, k0, k1, ja);
+    if (status != TC_OK) return status;
+    t0->last_workgroups = (int)grid.x;
+    t0->last_waves = tc::kJointForwardWaves;
+    t0->last_splits = 0;
+    t0->last_lds = lds;
+    return TC_OK;
+  });
+}
+
+// A joint as forward_chunked and forward_zero_copy see it (table.cpp: TableForward): it works
+// through its first table -- the staging areas, the tickets, the lanes and the chunk events are
+// that table's.
+struct JointForward {
+  static constexpr bool kThreadedCopyOut = true;
+  tc_joint* joint;
+  const tc::JointForwardArgs* shape;
+  tc_table* handle() const { return joint->tables[0]; }
+  // (one form: a draw's result does not depend on the chunks)
+  Call hints(const PredictRequest&, const tc::SyncChunkPlan&) const {
+    return probe_call(handle());
+  }
+  std::vector<hipEvent_t>* chunk_events() const { return &handle()->chunk_events; }
+  // A chunk on the first table's next lane: draws up, the launch, results down, the ticket.
+  int enqueue(const PredictRequest& part, const Call&, hipEvent_t wait_for,
+              hipEvent_t kernels_done, int64_t* ticket) const {
+    tc_table* t0 = handle();
+    tc_table::Lane& lane = t0->lanes[next_lane(false, t0->tuning.pipeline != 0, t0->n_lanes,
+                                               &t0->device_calls)];
+    int status = lane.in_theta.reserve(part.theta_bytes(), lane.stream);
+    if (status == TC_OK) status = lane.out.reserve(part.out_bytes(), lane.stream);
+    if (status != TC_OK) return status;
+    TC_HIP(hipMemcpyAsync(lane.in_theta.ptr, part.theta, part.theta_bytes(),
+                          hipMemcpyHostToDevice, lane.stream));
+    if (wait_for != nullptr) TC_HIP(hipStreamWaitEvent(lane.stream, wait_for, 0));
+    double* out = (double*)lane.out.ptr;
+    status = joint_forward_launches(
+        joint, *shape,
+        part.on((const double*)lane.in_theta.ptr, nullptr, out, out + part.ngal_count()),
+        lane.stream);
+    if (status != TC_OK) return status;
+    if (kernels_done != nullptr) TC_HIP(hipEventRecord(kernels_done, lane.stream));
+    // (the staged results lie side by side, [ngal | second]: one copy command)
+    TC_HIP(hipMemcpyAsync(part.ngal, out, part.out_bytes(), hipMemcpyDeviceToHost, lane.stream));
+    return t0->tickets.issue(lane.stream, ticket);
+  }
+  int synchronize() const { return tc_table_synchronize(handle()); }
+  // (the pinned lane of the first table)
+  int run(const PredictRequest& s) const {
+    return joint_forward_launches(joint, *shape, s, handle()->stream);
+  }
+};
+
+// The request of a joint forward entry point, in the order of the C arguments.
+PredictRequest joint_forward_request(const tc_joint* joint, const double* theta, int n_theta,
+                                     int64_t n_draws, int n_gauss, unsigned flags, double* ngal,
+                                     double* second, bool likelihood) {
+  return PredictRequest{n_theta, 0,     n_gauss, flags,  n_draws,   joint ? joint->n_r_total : 0,
+                        1,       theta, nullptr, ngal,   second,    likelihood};
+}
+
+// Every forward entry point of a joint: the checks, the likelihood's operands, then the launches
+// on device pointers (the first table's next lane) or the forward path of host arrays.
+int joint_forward_entry(tc_joint* joint, bool host, const PredictRequest& request,
+                        const Chi2Host* operands) {
+  int status = check_joint_forward(joint, request);
+  if (status != TC_OK) return status;
+  if (request.n_draws == 0) return TC_OK;
+  TC_CHECK(request.ngal && request.second, "output pointer is NULL");
+  TC_CHECK(operands == nullptr || (operands->data && operands->precision), "NULL pointer");
+  tc_table* t0 = joint->tables[0];
+  TC_HIP(hipSetDevice(joint->device));
+  if (operands != nullptr) {
+    status = joint->chi2.upload(joint->n_r_total, operands->data, operands->precision, t0->stream,
+                                [&] { return tc_table_synchronize(t0); });
+    if (status != TC_OK) return status;
+  }
+  tc::JointForwardArgs shape;
+  status = joint_forward_args(joint, request.n_theta, request.n_gauss, request.flags, &shape);
+  if (status != TC_OK) return status;
+  if (!host) {
+    t0->cur = next_lane(false, t0->tuning.pipeline != 0, t0->n_lanes, &t0->device_calls);
+    status = joint_forward_launches(joint, shape, request, t0->lanes[t0->cur].stream);
+    if (status == TC_OK) t0->prev = t0->cur;
+    return status;
+  }
+  const JointForward forward{joint, &shape};
+  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
+  const tc::SyncChunkPlan plan = plan_forward_chunks(t0, t0->n_lanes, false, false, request);
+  if (plan.n_chunks > 0) return forward_chunked(forward, request, plan);
+  status = t0->theta.reserve(request.theta_bytes(), t0->stream);
+  if (status == TC_OK) status = t0->out_ngal.reserve(request.out_bytes(), t0->stream);
+  if (status != TC_OK) return status;
+  status = copy_in(&t0->h_in, t0->theta.ptr, request.theta, request.theta_bytes(), t0->stream);
+  if (status != TC_OK) return status;
+  double* d_ngal = (double*)t0->out_ngal.ptr;
+  double* d_second = d_ngal + request.ngal_count();
+  status = forward.run(request.on((const double*)t0->theta.ptr, nullptr, d_ngal, d_second));
+  if (status != TC_OK) return status;
+  return copy_out(&t0->h_out, request.ngal, request.ngal_count(), d_ngal, request.second,
+                  request.second_count(), d_second, t0->stream);
 }
 
 }  // namespace
@@ -198,6 +453,63 @@ int tc_joint_chi2_grad_batch(tc_joint* joint, const double* theta, int n_theta, 
                     joint_request(joint, theta, n_draws, n_gauss, flags, ngal, chi2, dngal, dchi2,
                                   fisher),
                     n_theta, &operands, false);
+}
+
+int tc_joint_predict_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
+                                  int64_t n_draws, int n_gauss, unsigned flags,
+                                  double* ngal_device, double* xi_device) {
+  return joint_forward_entry(joint, false,
+                             joint_forward_request(joint, theta_device, n_theta, n_draws, n_gauss,
+                                                   flags, ngal_device, xi_device, false),
+                             nullptr);
+}
+
+int tc_joint_predict_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
+                           int n_gauss, unsigned flags, double* ngal, double* xi) {
+  return joint_forward_entry(joint, true,
+                             joint_forward_request(joint, theta, n_theta, n_draws, n_gauss, flags,
+                                                   ngal, xi, false),
+                             nullptr);
+}
+
+int tc_joint_chi2_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
+                               int64_t n_draws, int n_gauss, unsigned flags, const double* data,
+                               const double* precision, double* ngal_device,
+                               double* chi2_device) {
+  const Chi2Host operands{data, precision};
+  return joint_forward_entry(joint, false,
+                             joint_forward_request(joint, theta_device, n_theta, n_draws, n_gauss,
+                                                   flags, ngal_device, chi2_device, true),
+                             &operands);
+}
+
+int tc_joint_chi2_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
+                        int n_gauss, unsigned flags, const double* data, const double* precision,
+                        double* ngal, double* chi2) {
+  const Chi2Host operands{data, precision};
+  return joint_forward_entry(joint, true,
+                             joint_forward_request(joint, theta, n_theta, n_draws, n_gauss, flags,
+                                                   ngal, chi2, true),
+                             &operands);
+}
+
+int tc_debug_joint_forward_lds_bytes(int n_bins, int n_r_total, int waves, int64_t* bytes) {
+  TC_CHECK(bytes != nullptr, "bytes is NULL");
+  TC_CHECK(n_bins >= 1 && n_r_total >= 1 && waves >= 2 && waves % 2 == 0 &&
+               waves <= 2 * tc::kFusedMaxParts,
+           "invalid shape");
+  *bytes = (int64_t)tc::joint_forward_lds_bytes(n_bins, n_r_total, waves);
+  return TC_OK;
+}
+
+int tc_debug_joint_forward_fit(int n_bins, int n_tables, const int* mode, const int* n_r,
+                               const int* compute_dtype, int64_t* lds_bytes) {
+  TC_CHECK(mode != nullptr && n_r != nullptr && compute_dtype != nullptr, "NULL pointer");
+  TC_CHECK(n_bins >= 1 && n_tables >= 1 && n_tables <= tc::kJointMaxTables, "invalid shape");
+  for (int k = 0; k < n_tables; ++k)
+    TC_CHECK((mode[k] == TC_MODE_AUTO || mode[k] == TC_MODE_CROSS) && n_r[k] >= 1,
+             "invalid table %d", k);
+  return joint_forward_fit(n_bins, n_tables, mode, n_r, compute_dtype, lds_bytes);
 }
 
 int tc_debug_joint_lds_bytes(int n_bins, int n_central, int n_r_total, int chi2, int n_params,

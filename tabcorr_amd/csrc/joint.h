@@ -40,4 +40,73 @@ constexpr size_t joint_lds_bytes(int n_bins, int n_central, int n_r_total, bool 
   return grad_auto_lds_bytes(n_bins, n_central, n_r_total, chi2, n_params);
 }
 
+// ---- the forward form (joint_forward_kernels.hip.h: joint_forward_kernel) -----------------------
+// One launch per batch, kJointForwardDraws draws per workgroup of kJointForwardWaves waves: the
+// occupations once, every mode-auto table's packed triangle (the table's own forward unit layout)
+// on the matrix cores, every mode-cross table by one fma chain per row, then the concatenated
+// prediction or chi2 against the (N, N) precision matrix.
+constexpr int kJointForwardWaves = 8;
+constexpr int kJointForwardDraws = kLanes;      // two tiles of kQuadTile draws
+// Parts a mode-auto table's triangle is cut into per tile of 32 draws: with the two tiles and the
+// pairs of r sub-tiles, (n_u + 1) / 2 * 2 * parts passes per table are dealt to the waves.
+constexpr int joint_forward_parts(int waves) { return waves / 2; }
+
+struct JointForwardArgs {
+  const double* theta;       // (n_draws, n_theta)
+  int n_theta;
+  int n_bins;
+  int n_central;
+  int n_gauss;
+  int dens_rows;             // rows of the LDS density array: whole blocks of four
+  int n_r;                   // N, the concatenated rows
+  int64_t n_draws;
+  const double* log_m;       // quadrature constants as in FusedArgs
+  const double* m;
+  const double* weight;
+  const double* n_h;
+  const double* percentile;
+  double split;
+  const double* math_table;
+  double* ngal;              // (n_draws)
+  double* xi;                // (n_draws, N); NULL: the likelihood form
+  const double* chi2_data;   // data (N), then the precision matrix (N, N)
+  double* chi2;              // (n_draws)
+  int n_tables;
+  int mode[kJointMaxTables];
+  int n_rows[kJointMaxTables];            // a table's n_r
+  int r_offset[kJointMaxTables];
+  // mode auto: the table's unit layout of the whole triangle (QuadTable::d_table), n_u sub-tiles
+  // of four r values, table_bytes long; mode cross: (n_bins in library order, n_r) doubles
+  const void* matrix[kJointMaxTables];
+  uint32_t table_bytes[kJointMaxTables];
+  int n_u[kJointMaxTables];
+  int job_begin[kJointMaxTables + 1];     // first pass of every table (mode cross: none)
+  // the parts of the triangle (hostmath.h: triangle_parts; the tables share their bins, so also
+  // the triangle) and the component's place in the densities and in the unit numbering
+  int part_rb0[kFusedMaxParts];
+  int part_cb0[kFusedMaxParts];
+  int part_count[kFusedMaxParts];
+  int n_cb;
+  int i_row0, j_row0;
+  int unit_base;
+};
+
+constexpr size_t joint_forward_max(size_t a, size_t b) { return a > b ? a : b; }
+
+// LDS of joint_forward_kernel in bytes, for tables of n_bins bins, N = n_r_total rows and `waves`
+// waves per workgroup, in the order of the regions:
+//   B  the densities (rows in whole blocks of four, 64), later the results tile (N, 65);
+//   A  the math table, later the likelihood's data and precision matrix, N (N + 1);
+//   the waves' sums of the number density and of chi2, (2, waves, 64);
+//   the passes' sums, (parts, N, 64): a mode-cross row takes part 0 only.
+constexpr size_t joint_forward_lds_bytes(int n_bins, int n_r_total, int waves) {
+  const size_t n = (size_t)n_r_total;
+  const size_t dens_rows = ((size_t)n_bins + 3) / 4 * 4;
+  // (region B in whole 16-byte words: the math table behind it is read by such)
+  return 8 * (joint_forward_max(dens_rows * kLanes, (n * (kLanes + 1) + 1) / 2 * 2) +
+              joint_forward_max((size_t)kMathTableDoubles, n * (n + 1)) +
+              2 * (size_t)waves * kLanes +
+              (size_t)joint_forward_parts(waves) * n * kLanes);
+}
+
 }  // namespace tc

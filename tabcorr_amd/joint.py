@@ -8,13 +8,16 @@ concatenation (w_p, DeltaSigma), and its covariance couples the probes.  A
 kernel launch (``tc_joint_*``, ``include/tabcorr_amd.h``): the occupations and
 their derivatives once per draw, every table's contraction, and chi2, its
 gradient and the Fisher matrix against the full ``(N, N)`` precision matrix,
-``N`` the sum of the tables' correlation function bins.
+``N`` the sum of the tables' correlation function bins.  The forward calls
+`predict_batch` and `chi2_batch` -- what an ensemble sampler asks per step --
+take a launch of their own kind, without any derivative.
 """
 
 import ctypes
 
 import numpy as np
 
+from . import _forward
 from . import _grad
 from . import _lib
 from .tabcorr import _flags, _grad_keys, _grad_spec, _grad_theta
@@ -165,6 +168,56 @@ class JointLikelihood:
             for part, halotab in zip(self.slices, self.tabcorr_list)]
 
     # -- batched calls --------------------------------------------------------
+
+    def _forward_call(self, form, theta, n_gauss_prim, modulate_with_cenocc,
+                      assembias, family, operands=()):
+        """The forward entry (``_lib.FORWARD_ENTRIES['joint', form, 'host']``)
+        for draws and operands that are checked here, before any device is
+        touched: the results on the joint axis of ``n_r_total`` entries."""
+        _zheng07_only(family)
+        theta = _grad_theta(theta, assembias)
+        if operands:
+            operands = self._operands(*operands)
+        n_draws = len(theta)
+        shapes = ((n_draws, ), (n_draws, ) if operands else
+                  (n_draws, self.n_r_total))
+        return _forward.call(
+            self.to_device(), 'joint', form,
+            (theta, theta.shape[1], n_draws, n_gauss_prim,
+             _flags(False, modulate_with_cenocc, assembias)), shapes, operands)
+
+    def predict_batch(self, theta, n_gauss_prim=10, modulate_with_cenocc=False,
+                      assembias=False, family='zheng07'):
+        """`TabCorr.predict_batch` of every table in one launch, without any
+        derivative: the occupations once per draw, then every table's
+        contraction.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )`` -- the tables share their bins: one per draw
+        xis : list, per table ``(n_draws, ) + tpcf_shape``
+
+        ``theta`` is ``(n_draws, 5)``, ``(n_draws, 7)`` with
+        ``assembias=True``.  Raises ``NotImplementedError`` for
+        ``family='leauthaud11'`` and for a joint the one-launch kernel does
+        not serve: a mode ``'auto'`` table of more than 20 correlation
+        function bins, or rows beyond the kernel's LDS."""
+        ngal, xi = self._forward_call('predict', theta, n_gauss_prim,
+                                      modulate_with_cenocc, assembias, family)
+        return ngal, self._split(xi, (len(ngal), ))
+
+    def chi2_batch(self, theta, data, precision, n_gauss_prim=10,
+                   modulate_with_cenocc=False, assembias=False,
+                   family='zheng07'):
+        """``chi2 = (xi - data)^T precision (xi - data)`` of the concatenated
+        data vector for every draw, finished in the launch of `predict_batch`
+        (``xi`` is never stored): ``ngal, chi2``, each ``(n_draws, )`` -- what
+        an ensemble sampler asks per step.  ``data`` and ``precision`` as
+        `chi2_grad_batch` takes them; the signature is the one
+        `parallel.chi2_batch_sharded` calls a predictor with."""
+        return self._forward_call('chi2', theta, n_gauss_prim,
+                                  modulate_with_cenocc, assembias, family,
+                                  (data, precision))
 
     def predict_batch_grad(self, theta, n_gauss_prim=10,
                            modulate_with_cenocc=False, assembias=False,

@@ -6,6 +6,11 @@ Prints one JSON line (profiles/joint_notes.md).
     python tools/joint_bench.py joint            # this tree: the joint calls and the tables' calls
     python tools/joint_bench.py tables DIR       # the tables' calls with the package of the
                                                  # checkout DIR (the commit before the joint)
+    python tools/joint_bench.py forward [DIR]    # the forward form (profiles/joint_forward_notes.md):
+                                                 # tc_joint_chi2_batch_device against (A) the joint's
+                                                 # chi2_grad entry with fisher = NULL and (B) the two
+                                                 # tables' own tc_chi2_zheng07_batch_device calls; a
+                                                 # checkout DIR without the forward entries gives A and B
 """
 import ctypes
 import json
@@ -16,7 +21,7 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 which = sys.argv[1]
-assert which in ('joint', 'tables')
+assert which in ('joint', 'tables', 'forward')
 sys.path.insert(0, os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else REPO)
 sys.path.insert(1, os.path.join(REPO, 'tests'))
 import tabcorr_amd  # noqa: E402
@@ -69,6 +74,55 @@ def timed(handle, call, synchronize):
 
 result = {'which': which, 'n_draws': N}
 devices = [h.to_device() for h in halotabs]
+if which == 'forward':
+    from tabcorr_amd import JointLikelihood
+    joint = JointLikelihood(halotabs).to_device()
+    data, precision = operands(38)
+    sync = lambda: _lib.check(lib.tc_joint_synchronize(joint.handle))
+
+    def call_grad():
+        _lib.check(lib.tc_joint_chi2_grad_batch_device(
+            joint.handle, d_theta, 5, N, 10, 0, _lib.as_double_p(data),
+            _lib.as_double_p(precision), d_ngal, d_chi2, d_dngal, d_dchi2, None))
+
+    result['A_joint_chi2_grad'] = timed(devices[0].handle, call_grad, sync)
+    for name, device in zip(('wp', 'ds'), devices):
+        kept = operands(device.n_r)
+
+        def call(device=device, kept=kept):
+            _lib.check(lib.tc_chi2_zheng07_batch_device(
+                device.handle, d_theta, 5, N, 10, 0, _lib.as_double_p(kept[0]),
+                _lib.as_double_p(kept[1]), d_ngal, d_chi2))
+
+        result['table_chi2_' + name] = timed(
+            device.handle, call,
+            lambda device=device: _lib.check(lib.tc_table_synchronize(device.handle)))
+    result['B_tables_chi2_us'] = sum(result['table_chi2_' + name]['us_per_call']
+                                     for name in ('wp', 'ds'))
+    if hasattr(lib, 'tc_joint_chi2_batch_device'):
+        d_xi = malloc(N * 38)
+        # the pair, and each table alone in a joint: what the matrix and the chains cost
+        for label, members in (('joint', halotabs), ('joint_wp', halotabs[:1]),
+                               ('joint_ds', halotabs[1:])):
+            member = JointLikelihood(members)
+            handle = member.to_device().handle
+            kept = operands(member.n_r_total)
+
+            def call_chi2(handle=handle, kept=kept):
+                _lib.check(lib.tc_joint_chi2_batch_device(
+                    handle, d_theta, 5, N, 10, 0, _lib.as_double_p(kept[0]),
+                    _lib.as_double_p(kept[1]), d_ngal, d_chi2))
+
+            def call_predict(handle=handle):
+                _lib.check(lib.tc_joint_predict_batch_device(handle, d_theta, 5, N, 10, 0, d_ngal,
+                                                             d_xi))
+
+            wait = lambda handle=handle: _lib.check(lib.tc_joint_synchronize(handle))
+            timer = members[0].to_device().handle
+            result[label + '_chi2'] = timed(timer, call_chi2, wait)
+            result[label + '_predict'] = timed(timer, call_predict, wait)
+    print(json.dumps(result))
+    sys.exit(0)
 for name, device in zip(('wp', 'ds'), devices):
     data, precision = operands(device.n_r)
     kept = (data, precision)
