@@ -618,6 +618,51 @@ int tc_joint_chi2_batch_device(tc_joint* joint, const double* theta_device, int 
                                int64_t n_draws, int n_gauss_prim, unsigned flags,
                                const double* data, const double* precision, double* ngal_device,
                                double* chi2_device);
+/* The occupation seam of a joint, for ANY occupation model (tc_predict_occupation_vjp_batch and
+ * tc_chi2_occupation_grad_batch with N for n_r, in ONE launch per batch for all the tables):
+ * occupation (n_draws, n_bins) in gal_type row order; the concatenated prediction ngal (n_draws),
+ * xi (n_draws, N); and for cotangents g_ngal (n_draws; NULL = 0) and g_xi (n_draws, N) the
+ * vector-Jacobian product g_occupation (n_draws, n_bins), gal_type row order:
+ *   g_occ,i = n_h,i [ g_ngal + (2 / ngal^2) sum_auto g_r U_ri + (1 / ngal) sum_cross g_r T_ri
+ *                     - (2 / ngal) sum_auto g_r xi_r - (1 / ngal) sum_cross g_r xi_r ]
+ * with U_r = S_r w of a mode-auto table's row and T_r the matrix row of a mode-cross one.  g_xi and
+ * g_occupation both NULL: the forward-only form, (ngal, xi) alone; exactly one of them NULL is
+ * TC_ERR_INVALID.  flags must be 0 (TC_ERR_INVALID otherwise).
+ * tc_joint_chi2_occupation_grad_batch: chi2 = (xi - data)^T precision (xi - data) of the joint
+ * data vector and dchi2_docc = the product above with g = 2 P_sym (xi - data), g_ngal = 0, formed
+ * in the launch from its own xi -- the off-diagonal blocks of `precision` couple the tables.
+ * dchi2_docc may be NULL: not asked for, (ngal, chi2) alone with one product per mode-auto table;
+ * the other outputs do not depend on whether it is asked for.  data (N) and precision (N, N) are
+ * host arrays in both forms (uploaded when they change).
+ * Contracted with the caller's own d<N>/dtheta the results are the gradient for every occupation
+ * model, Leauthaud11 among them (examples/example_joint_custom_model_grad.py).
+ * One launch per batch; a draw's results depend on the draw alone, not on the batch, its place in
+ * it or the entry point, and a row's arithmetic does not depend on the wave that runs it.  A joint
+ * of ONE table returns the bits of that table's own tc_predict_occupation_vjp_batch /
+ * tc_chi2_occupation_grad_batch call.  Where ngal = 0 the results are what IEEE arithmetic gives.
+ * TC_ERR_UNSUPPORTED with a message naming the bytes, the joint and its tables staying usable: a
+ * workgroup beyond 160 KiB of LDS, 128 x (2 bins + 1 + max(4 N_auto, N) + 2 N + 3) bytes with
+ * N_auto the rows of the mode-auto tables (every bin stays in LDS, also for mode-cross tables).
+ * Host arrays run slab-wise on lane 0 of the first table; the `_device` forms enqueue on its next
+ * lane and return (tc_joint_synchronize waits). */
+int tc_joint_predict_occupation_vjp_batch(tc_joint* joint, const double* occupation,
+                                          int64_t n_draws, unsigned flags, const double* g_ngal,
+                                          const double* g_xi, double* ngal, double* xi,
+                                          double* g_occupation);
+int tc_joint_predict_occupation_vjp_batch_device(tc_joint* joint, const double* occupation_device,
+                                                 int64_t n_draws, unsigned flags,
+                                                 const double* g_ngal_device,
+                                                 const double* g_xi_device, double* ngal_device,
+                                                 double* xi_device, double* g_occupation_device);
+int tc_joint_chi2_occupation_grad_batch(tc_joint* joint, const double* occupation,
+                                        int64_t n_draws, unsigned flags, const double* data,
+                                        const double* precision, double* ngal, double* chi2,
+                                        double* dchi2_docc);
+int tc_joint_chi2_occupation_grad_batch_device(tc_joint* joint, const double* occupation_device,
+                                               int64_t n_draws, unsigned flags,
+                                               const double* data, const double* precision,
+                                               double* ngal_device, double* chi2_device,
+                                               double* dchi2_docc_device);
 
 /* Joint likelihood of several interpolators (extension): the reference's AbacusSummit database
  * and its own suite read TWO interpolators, `wp` and `ds`, built over the same grid of simulations,

@@ -126,6 +126,10 @@ int tc_debug_joint_lds_bytes(int n_bins, int n_central, int n_r_total, int chi2,
  * joint_forward_lds_bytes) for tables of n_bins bins, n_r_total result rows in all and `waves`
  * waves per workgroup (the kernel's: 8) -- no device needed. */
 int tc_debug_joint_forward_lds_bytes(int n_bins, int n_r_total, int waves, int64_t* bytes);
+/* The LDS bytes per workgroup of vjp_joint_kernel (tabcorr_amd/csrc/joint.h: joint_vjp_lds_bytes)
+ * for tables of n_bins bins, n_r_total result rows in all and n_r_auto of them those of mode-auto
+ * tables -- no device needed. */
+int tc_debug_joint_vjp_lds_bytes(int n_bins, int n_r_total, int n_r_auto, int64_t* bytes);
 /* What the forward entries of a joint refuse on the host, from plain numbers -- no device, no
  * handle: n_tables tables of n_bins bins with mode[k] (0 auto, 1 cross), n_r[k] correlation
  * function bins and compute_dtype[k] (TC_DTYPE_*).  TC_OK and the workgroup's LDS in *lds_bytes

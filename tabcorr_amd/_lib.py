@@ -197,6 +197,7 @@ SIGNATURES = {
         ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p, ctypes.c_void_p,
         ctypes.c_void_p],
     'tc_debug_joint_forward_lds_bytes': [ctypes.c_int] * 3 + [c_int64_p],
+    'tc_debug_joint_vjp_lds_bytes': [ctypes.c_int] * 3 + [c_int64_p],
     'tc_debug_joint_forward_fit': [ctypes.c_int, ctypes.c_int, c_int_p, c_int_p, c_int_p,
                                    c_int64_p],
     # joint of interpolators
@@ -308,6 +309,10 @@ def _derivative_signatures():
         head = [ctypes.c_void_p, array, ctypes.c_int64, ctypes.c_uint]
         out['tc_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 3
         out['tc_chi2_occupation_grad_batch' + suffix] = head + [c_double_p] * 2 + [array] * 3
+        # (a joint of tables: the same arguments with N for n_r)
+        out['tc_joint_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 3
+        out['tc_joint_chi2_occupation_grad_batch' + suffix] = (head + [c_double_p] * 2 +
+                                                              [array] * 3)
     return out
 
 

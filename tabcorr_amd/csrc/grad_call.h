@@ -73,6 +73,40 @@ struct GradRequest {
   }
 };
 
+// One call at the occupation seam (vjp.h), or one slab of it, of a table or of a joint.  Which
+// arrays are there says the form: g_occupation NULL is the forward-only form (a joint's), and
+// chi2_data the likelihood form, whose value is chi2 (n_draws) where the prediction's is xi
+// (n_draws, n_r) with the cotangents g_xi and, or NULL = 0, g_ngal.
+struct VjpRequest {
+  int64_t n_draws;
+  int n_bins;
+  int n_r;                   // rows of a draw's result: a table's n_r, a joint's n_r_total
+  const double* occupation;  // (n_draws, n_bins)
+  const double* g_ngal;      // (n_draws), or NULL
+  const double* g_xi;        // (n_draws, n_r), or NULL
+  const double* chi2_data;   // on the device: data (n_r), then the precision matrix (n_r, n_r)
+  double* ngal;              // (n_draws)
+  double* xi;                // (n_draws, n_r), or NULL
+  double* chi2;              // (n_draws), or NULL
+  double* g_occupation;      // (n_draws, n_bins), or NULL
+
+  bool likelihood() const { return chi2_data != nullptr; }
+
+  // The draws [begin, begin + n) of the call: every offset a 64-bit product.
+  VjpRequest slab(int64_t begin, int64_t n) const {
+    VjpRequest out = *this;
+    out.n_draws = n;
+    out.occupation = occupation + begin * n_bins;
+    out.g_ngal = g_ngal ? g_ngal + begin : nullptr;
+    out.g_xi = g_xi ? g_xi + begin * n_r : nullptr;
+    out.ngal = ngal + begin;
+    out.xi = xi ? xi + begin * n_r : nullptr;
+    out.chi2 = chi2 ? chi2 + begin : nullptr;
+    out.g_occupation = g_occupation ? g_occupation + begin * n_bins : nullptr;
+    return out;
+  }
+};
+
 // The element offsets that slab `begin` adds to the seven arrays of a request of this shape --
 // theta, x, ngal, dngal, value, dvalue, fisher; -1: the request has no such array -- read off
 // slab() itself (tc_debug_grad_slab; tools/sanitize/host_driver.cpp).
@@ -131,6 +165,14 @@ int run_grad(tc_table* t, const GradRequest& request, hipStream_t stream);
 // grad.log_m / m / weight (the first table's quadrature of ja.grad.n_gauss nodes).
 int run_grad_joint(tc_table* t0, tc::JointArgs ja, const GradRequest& request, hipStream_t stream);
 
+// One launch of the table's occupation-seam kernel (vjp_kernels.hip.h) for a request of at most
+// max_slab(t) draws on `stream`, against the gradient table.
+int run_vjp(tc_table* t, const VjpRequest& request, hipStream_t stream);
+// The occupation-seam kernel of a joint (joint_vjp_kernels.hip.h) for such a request on `stream`,
+// timed and reported through the first table: `ja` complete but for what the request holds.
+int run_vjp_joint(tc_table* t0, tc::JointVjpArgs ja, const VjpRequest& request,
+                  hipStream_t stream);
+
 // A derivative call on device pointers: run(begin, n, stream) for every slab of the batch, one
 // launch each, on lane 0 (pinned) or on the next lane of the rotation (as
 // tc_predict_zheng07_batch_device).
@@ -147,6 +189,66 @@ int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
   if (status != TC_OK) return status;
   t->prev = pinned ? -1 : t->cur;
   return TC_OK;
+}
+
+// A call at the occupation seam on device pointers, on a lane of `t` (a joint: its first table):
+// run(slab, stream) for every slab of the batch, one launch each.
+template <typename Run>
+int vjp_device(tc_table* t, GradLane lane, const VjpRequest& request, Run run) {
+  return grad_slabs(t, lane, request.n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
+    return run(request.slab(begin, n), stream);
+  });
+}
+
+// ... and on host arrays (chi2_data on the device), slab by slab on lane 0 of `t`: the
+// occupations and the cotangents go up in one workspace, the results come down from another.
+template <typename Run>
+int vjp_host(tc_table* t, const VjpRequest& request, Run run) {
+  TC_HIP(hipSetDevice(t->device));
+  int stopped = TC_OK;
+  if (t->resident.running && (stopped = resident_stop(t)) != TC_OK) return stopped;
+  const bool chi2 = request.likelihood();
+  const bool cotangents = !chi2 && request.g_xi != nullptr;
+  const bool backward = request.g_occupation != nullptr;
+  const size_t n_r = (size_t)request.n_r, n_bins = (size_t)request.n_bins;
+  return for_each_slab(request.n_draws, max_slab(t), [&](int64_t begin, int64_t n_slab) {
+    const VjpRequest host = request.slab(begin, n_slab);
+    const size_t n = (size_t)n_slab;
+    const size_t value_count = chi2 ? n : n * n_r;
+    int status = t->occupation.reserve(n * (n_bins + n_r + 1) * 8, t->stream);
+    if (status == TC_OK) status = t->out_ngal.reserve(n * 8, t->stream);
+    if (status == TC_OK) status = t->out_xi.reserve((n * n_bins + value_count) * 8, t->stream);
+    if (status != TC_OK) return status;
+    double* d_occupation = (double*)t->occupation.ptr;
+    double* d_g_xi = d_occupation + n * n_bins;
+    double* d_g_ngal = d_g_xi + n * n_r;
+    double* d_g_occupation = (double*)t->out_xi.ptr;
+    double* d_value = d_g_occupation + n * n_bins;
+    TC_HIP(hipMemcpyAsync(d_occupation, host.occupation, n * n_bins * 8, hipMemcpyHostToDevice,
+                          t->stream));
+    if (cotangents)
+      TC_HIP(hipMemcpyAsync(d_g_xi, host.g_xi, n * n_r * 8, hipMemcpyHostToDevice, t->stream));
+    if (cotangents && host.g_ngal != nullptr)
+      TC_HIP(hipMemcpyAsync(d_g_ngal, host.g_ngal, n * 8, hipMemcpyHostToDevice, t->stream));
+    VjpRequest staged = host;
+    staged.occupation = d_occupation;
+    staged.g_ngal = cotangents && host.g_ngal != nullptr ? d_g_ngal : nullptr;
+    staged.g_xi = cotangents ? d_g_xi : nullptr;
+    staged.ngal = (double*)t->out_ngal.ptr;
+    staged.xi = chi2 ? nullptr : d_value;
+    staged.chi2 = chi2 ? d_value : nullptr;
+    staged.g_occupation = backward ? d_g_occupation : nullptr;
+    status = vjp_device(t, GradLane::kPinned, staged, run);
+    if (status != TC_OK) return status;
+    TC_HIP(hipMemcpyAsync(host.ngal, staged.ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
+    TC_HIP(hipMemcpyAsync(chi2 ? host.chi2 : host.xi, d_value, value_count * 8,
+                          hipMemcpyDeviceToHost, t->stream));
+    if (backward)
+      TC_HIP(hipMemcpyAsync(host.g_occupation, d_g_occupation, n * n_bins * 8,
+                            hipMemcpyDeviceToHost, t->stream));
+    TC_HIP(hipStreamSynchronize(t->stream));
+    return (int)TC_OK;
+  });
 }
 
 // The buffers of a handle that a host-array call is staged through, and the stream of its copies.

@@ -771,11 +771,9 @@ int launch_grad_batch(tc_table* t, int64_t n_draws, int lds,
                       const std::function<int(dim3, hipEvent_t, hipEvent_t)>& launch);
 // Occupation VJP (vjp_kernels.hip.h), one launch per slab of draws on `stream`: what the kernels
 // do not serve (TC_ERR_UNSUPPORTED with a message), then the launch against the gradient table.
-// g_xi NULL: the likelihood form -- chi2 and dchi2 / docc from chi2_data (on the device).
+// request.chi2_data (on the device): the likelihood form -- chi2 and dchi2 / docc.
 int check_vjp_args(const tc_table* t, int64_t n_draws, unsigned flags);
-int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const double* g_ngal,
-            const double* g_xi, const double* chi2_data, double* ngal, double* xi, double* chi2,
-            double* g_occupation, hipStream_t stream);
+// (grad_call.h: run_vjp, run_vjp_joint)
 // Mode cross, one launch per batch (predict_cross_fused_kernel): the coefficient rows of one
 // table / K tables with common mass bins (cf->rows == 0 afterwards: not available), whether a
 // call takes that form, and the launch (`interp`: the spline part of the arguments, or NULL).
@@ -859,7 +857,7 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
 // inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_joint_forward.hip,
-// inst_joint_interp.hip, inst_vjp.hip) ----
+// inst_joint_interp.hip, inst_vjp.hip, inst_joint_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -904,6 +902,8 @@ int launch_grad_joint_interp_instance(int n_params, int form, int device, dim3 g
                                       const tc::JointInterpArgs& ja);
 int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                         hipEvent_t k0, hipEvent_t k1, const tc::VjpArgs& va);
+int launch_vjp_joint_instance(int device, dim3 grid, int lds, hipStream_t stream, hipEvent_t k0,
+                              hipEvent_t k1, const tc::JointVjpArgs& ja);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_resident_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_ensemble_kernel(int device, int grid, int lds_bytes, hipStream_t stream,

@@ -7,6 +7,9 @@
 // The forward entries -- the concatenated prediction or chi2 alone -- take ONE launch of
 // joint_forward_kernel (joint_forward_kernels.hip.h) on the mode-auto tables' own forward unit
 // layouts, and the forward call path of the tables (predict_call.h) through the first table.
+// The entries at the occupation seam -- any occupation model -- take ONE launch of vjp_joint_kernel
+// (joint_vjp_kernels.hip.h) on the tables' gradient matrices, and the staging path of the tables'
+// own VJP entries (grad_call.h: vjp_host, vjp_device) through the first table.
 #include "internal.h"
 
 using namespace tc::host;
@@ -356,9 +359,143 @@ int joint_forward_entry(tc_joint* joint, bool host, const PredictRequest& reques
                   request.second_count(), d_second, t0->stream);
 }
 
+// ---- the occupation seam (joint_vjp_kernels.hip.h) ----------------------------------------------
+
+int joint_rows_auto(const tc_joint* joint) {
+  int rows = 0;
+  for (const tc_table* t : joint->tables)
+    if (t->mode == TC_MODE_AUTO) rows += t->n_r;
+  return rows;
+}
+
+// What the entries at the occupation seam refuse, the NULL handle first: flags, a negative number
+// of draws, a workgroup beyond the LDS of a CU (check_grad_fit, for all the tables together).
+int check_joint_vjp(const tc_joint* joint, int64_t n_draws, unsigned flags) {
+  TC_CHECK(joint != nullptr, "joint handle is NULL");
+  TC_CHECK(flags == 0, "joint occupation VJP: flags must be 0, got 0x%x", flags);
+  TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
+  const size_t lds = tc::joint_vjp_lds_bytes(joint->tables[0]->n_bins, joint->n_r_total,
+                                             joint_rows_auto(joint));
+  int status = TC_OK;
+  for (size_t k = 0; status == TC_OK && k < joint->tables.size(); ++k)
+    status = check_grad_fit(joint->tables[k], "joint occupation VJP", lds, joint->n_r_total);
+  return status;
+}
+
+// Every entry at the occupation seam: `request` as the caller stated it (chi2_data not yet
+// known) on device pointers (the first table's next lane) or host arrays (slab-wise on its lane
+// 0), and, for the likelihood form, its operands on the host.
+int joint_vjp_entry(tc_joint* joint, bool host, unsigned flags, VjpRequest request,
+                    const Chi2Host* operands) {
+  int status = check_joint_vjp(joint, request.n_draws, flags);
+  if (status != TC_OK) return status;
+  if (request.n_draws == 0) return TC_OK;
+  if (operands != nullptr) {
+    TC_CHECK(request.occupation && operands->data && operands->precision && request.ngal &&
+                 request.chi2,
+             "NULL pointer");
+  } else {
+    TC_CHECK(request.occupation && request.ngal && request.xi, "NULL pointer");
+    TC_CHECK((request.g_xi == nullptr) == (request.g_occupation == nullptr),
+             "g_xi and g_occupation go together: both NULL is the forward-only form");
+  }
+  tc_table* t0 = joint->tables[0];
+  TC_HIP(hipSetDevice(joint->device));
+  if (operands != nullptr) {
+    status = joint->chi2.upload(joint->n_r_total, operands->data, operands->precision, t0->stream,
+                                [&] { return tc_table_synchronize(t0); });
+    if (status != TC_OK) return status;
+    request.chi2_data = joint->chi2.device();
+  }
+  tc::JointVjpArgs ja{};
+  ja.vjp.n_bins = t0->n_bins;
+  ja.vjp.n_r = joint->n_r_total;
+  ja.vjp.perm = (const int32_t*)t0->d_perm;
+  ja.vjp.n_h = (const double*)t0->d_n_h;
+  ja.vjp.row_tiles = tc::grad_row_tiles(t0->n_bins);
+  ja.vjp.k_steps = tc::grad_k_steps(t0->n_bins);
+  ja.n_tables = (int)joint->tables.size();
+  for (int k = 0; k < ja.n_tables; ++k) {
+    tc_table* t = joint->tables[k];
+    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+    if ((status = build_grad_table(t)) != TC_OK) return status;
+    ja.mode[k] = t->mode;
+    ja.n_r[k] = t->n_r;
+    ja.r_offset[k] = joint->r_offset[k];
+    ja.matrix[k] = (const double*)t->grad.d_matrix;
+    if (t->mode == TC_MODE_AUTO) ja.n_r_auto += t->n_r;
+    else ja.n_cross += 1;
+  }
+  const auto run = [&](const VjpRequest& slab, hipStream_t stream) {
+    return run_vjp_joint(t0, ja, slab, stream);
+  };
+  return host ? vjp_host(t0, request, run) : vjp_device(t0, GradLane::kNext, request, run);
+}
+
+// The request of such an entry, in the order of the C arguments.
+VjpRequest joint_vjp_request(const tc_joint* joint, const double* occupation, int64_t n_draws,
+                             const double* g_ngal, const double* g_xi, double* ngal, double* xi,
+                             double* chi2, double* g_occupation) {
+  return VjpRequest{n_draws, joint ? joint->tables[0]->n_bins : 0, joint ? joint->n_r_total : 0,
+                    occupation, g_ngal, g_xi, nullptr, ngal, xi, chi2, g_occupation};
+}
+
 }  // namespace
 
 extern "C" {
+
+int tc_joint_predict_occupation_vjp_batch(tc_joint* joint, const double* occupation,
+                                          int64_t n_draws, unsigned flags, const double* g_ngal,
+                                          const double* g_xi, double* ngal, double* xi,
+                                          double* g_occupation) {
+  return joint_vjp_entry(joint, true, flags,
+                         joint_vjp_request(joint, occupation, n_draws, g_ngal, g_xi, ngal, xi,
+                                           nullptr, g_occupation),
+                         nullptr);
+}
+
+int tc_joint_predict_occupation_vjp_batch_device(tc_joint* joint, const double* occupation_device,
+                                                 int64_t n_draws, unsigned flags,
+                                                 const double* g_ngal_device,
+                                                 const double* g_xi_device, double* ngal_device,
+                                                 double* xi_device, double* g_occupation_device) {
+  return joint_vjp_entry(joint, false, flags,
+                         joint_vjp_request(joint, occupation_device, n_draws, g_ngal_device,
+                                           g_xi_device, ngal_device, xi_device, nullptr,
+                                           g_occupation_device),
+                         nullptr);
+}
+
+int tc_joint_chi2_occupation_grad_batch(tc_joint* joint, const double* occupation,
+                                        int64_t n_draws, unsigned flags, const double* data,
+                                        const double* precision, double* ngal, double* chi2,
+                                        double* dchi2_docc) {
+  const Chi2Host operands{data, precision};
+  return joint_vjp_entry(joint, true, flags,
+                         joint_vjp_request(joint, occupation, n_draws, nullptr, nullptr, ngal,
+                                           nullptr, chi2, dchi2_docc),
+                         &operands);
+}
+
+int tc_joint_chi2_occupation_grad_batch_device(tc_joint* joint, const double* occupation_device,
+                                               int64_t n_draws, unsigned flags,
+                                               const double* data, const double* precision,
+                                               double* ngal_device, double* chi2_device,
+                                               double* dchi2_docc_device) {
+  const Chi2Host operands{data, precision};
+  return joint_vjp_entry(joint, false, flags,
+                         joint_vjp_request(joint, occupation_device, n_draws, nullptr, nullptr,
+                                           ngal_device, nullptr, chi2_device, dchi2_docc_device),
+                         &operands);
+}
+
+int tc_debug_joint_vjp_lds_bytes(int n_bins, int n_r_total, int n_r_auto, int64_t* bytes) {
+  TC_CHECK(bytes != nullptr, "bytes is NULL");
+  TC_CHECK(n_bins >= 1 && n_r_total >= 1 && n_r_auto >= 0 && n_r_auto <= n_r_total,
+           "invalid shape");
+  *bytes = (int64_t)tc::joint_vjp_lds_bytes(n_bins, n_r_total, n_r_auto);
+  return TC_OK;
+}
 
 int tc_joint_create(tc_table* const* tables, int n_tables, tc_joint** joint) {
   TC_CHECK(joint != nullptr, "joint output pointer is NULL");

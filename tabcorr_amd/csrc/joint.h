@@ -10,6 +10,7 @@
 
 #include "../../include/tabcorr_amd.h"
 #include "grad.h"
+#include "vjp.h"
 
 namespace tc {
 
@@ -38,6 +39,41 @@ struct JointArgs {
 constexpr size_t joint_lds_bytes(int n_bins, int n_central, int n_r_total, bool chi2,
                                  int n_params = kGradParams) {
   return grad_auto_lds_bytes(n_bins, n_central, n_r_total, chi2, n_params);
+}
+
+// ---- the occupation seam (joint_vjp_kernels.hip.h: vjp_joint_kernel) ----------------------------
+// predict(occupation) of every table, its vector-Jacobian product with respect to the occupation
+// array, and chi2 of the concatenated data vector with or without its gradient -- for ANY
+// occupation model.  The formulas are those of vjp.h, summed over the tables:
+//   g_n,i = n_h,i [ g_ngal + (2 / ngal^2) sum_auto g_r U_ri + (1 / ngal) sum_cross g_r T_ri
+//                   - (2 / ngal) sum_auto g_r xi_r - (1 / ngal) sum_cross g_r xi_r ]
+struct JointVjpArgs {
+  // What the tables share, as for one table, with n_r := N wherever n_r stands: g_xi and xi
+  // (n_draws, N), chi2_data = data (N), then the precision matrix (N, N).  vjp.matrix is not
+  // read: every table has its own below.  vjp.g_occupation NULL: the forward-only form, which
+  // writes (ngal, xi) or (ngal, chi2); otherwise vjp.g_xi NULL is the likelihood form.
+  VjpArgs vjp;
+  int n_tables;
+  int mode[kJointMaxTables];              // TC_MODE_AUTO / TC_MODE_CROSS
+  int n_r[kJointMaxTables];
+  int r_offset[kJointMaxTables];
+  int n_r_auto;                           // rows of the mode-auto tables in all
+  int n_cross;                            // mode-cross tables
+  // VjpArgs::matrix of every table
+  const double* matrix[kJointMaxTables];
+};
+
+// LDS of vjp_joint_kernel in rows of kGradDraws doubles: w of every bin, one row of zeros and the
+// auto tables' sum_r g_r U_ri of every bin; one partial q_r per wave and auto row, later (P e) of
+// all N rows; the cotangent and xi of all N rows; ngal and the two sums of g_r xi_r.  EVERY joint
+// keeps the bins in LDS, as grad_joint_kernel does.
+constexpr int joint_vjp_rows(int n_bins, int n_r_total, int n_r_auto) {
+  return 2 * n_bins + 1 +
+         (kGradWaves * n_r_auto > n_r_total ? kGradWaves * n_r_auto : n_r_total) +
+         2 * n_r_total + 3;
+}
+constexpr size_t joint_vjp_lds_bytes(int n_bins, int n_r_total, int n_r_auto) {
+  return (size_t)joint_vjp_rows(n_bins, n_r_total, n_r_auto) * kGradDraws * sizeof(double);
 }
 
 // ---- the forward form (joint_forward_kernels.hip.h: joint_forward_kernel) -----------------------

@@ -1325,15 +1325,25 @@ int check_vjp_args(const tc_table* t, int64_t n_draws, unsigned flags) {
   return check_grad_fit(t, "occupation VJP", vjp_lds(t));
 }
 
-int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const double* g_ngal,
-            const double* g_xi, const double* chi2_data, double* ngal, double* xi, double* chi2,
-            double* g_occupation, hipStream_t stream) {
+// (the arrays of a slab into the argument block)
+static void fill_vjp_arrays(const VjpRequest& r, tc::VjpArgs* va) {
+  va->occupation = r.occupation;
+  va->n_draws = r.n_draws;
+  va->g_ngal = r.g_ngal;
+  va->g_xi = r.g_xi;
+  va->chi2_data = r.chi2_data;
+  va->ngal = r.ngal;
+  va->xi = r.xi;
+  va->chi2 = r.chi2;
+  va->g_occupation = r.g_occupation;
+}
+
+int run_vjp(tc_table* t, const VjpRequest& request, hipStream_t stream) {
   Range range("occupation VJP (one launch)");
   int status = build_grad_table(t);
   if (status != TC_OK) return status;
   tc::VjpArgs va{};
-  va.occupation = occupation_device;
-  va.n_draws = n_draws;
+  fill_vjp_arrays(request, &va);
   va.n_bins = t->n_bins;
   va.n_r = t->n_r;
   va.perm = (const int32_t*)t->d_perm;
@@ -1341,17 +1351,24 @@ int run_vjp(tc_table* t, const double* occupation_device, int64_t n_draws, const
   va.matrix = (const double*)t->grad.d_matrix;
   va.row_tiles = tc::grad_row_tiles(t->n_bins);
   va.k_steps = tc::grad_k_steps(t->n_bins);
-  va.g_ngal = g_ngal;
-  va.g_xi = g_xi;
-  va.chi2_data = chi2_data;
-  va.ngal = ngal;
-  va.xi = xi;
-  va.chi2 = chi2;
-  va.g_occupation = g_occupation;
   const int lds = (int)vjp_lds(t);
-  return launch_grad_batch(t, n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-    return launch_vjp_instance(t->mode, t->device, grid, lds, stream, k0, k1, va);
-  });
+  return launch_grad_batch(t, request.n_draws, lds,
+                           [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+                             return launch_vjp_instance(t->mode, t->device, grid, lds, stream, k0,
+                                                        k1, va);
+                           });
+}
+
+int run_vjp_joint(tc_table* t0, tc::JointVjpArgs ja, const VjpRequest& request,
+                  hipStream_t stream) {
+  Range range("joint occupation VJP (one launch)");
+  fill_vjp_arrays(request, &ja.vjp);
+  const int lds = (int)tc::joint_vjp_lds_bytes(ja.vjp.n_bins, ja.vjp.n_r, ja.n_r_auto);
+  return launch_grad_batch(t0, request.n_draws, lds,
+                           [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+                             return launch_vjp_joint_instance(t0->device, grid, lds, stream, k0,
+                                                              k1, ja);
+                           });
 }
 
 // ---- mode cross, one launch per batch -----------------------------------------------------

@@ -1072,63 +1072,22 @@ int tc_chi2_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta
 
 namespace {
 
-int vjp_device(tc_table* t, GradLane request, const double* occupation, int64_t n_draws,
-               const double* g_ngal, const double* g_xi, const double* chi2_data, double* ngal,
-               double* xi, double* chi2, double* g_occupation) {
-  const int64_t n_r = t->n_r, n_bins = t->n_bins;
-  return grad_slabs(t, request, n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
-    return run_vjp(t, occupation + begin * n_bins, n, g_ngal ? g_ngal + begin : nullptr,
-                   g_xi ? g_xi + begin * n_r : nullptr, chi2_data, ngal + begin,
-                   xi ? xi + begin * n_r : nullptr, chi2 ? chi2 + begin : nullptr,
-                   g_occupation + begin * n_bins, stream);
-  });
+// The request of a table's entry point at the occupation seam, in the order of the C arguments.
+VjpRequest vjp_request(const tc_table* t, const double* occupation, int64_t n_draws,
+                       const double* g_ngal, const double* g_xi, const double* chi2_data,
+                       double* ngal, double* xi, double* chi2, double* g_occupation) {
+  return VjpRequest{n_draws, t->n_bins, t->n_r, occupation, g_ngal, g_xi,
+                    chi2_data, ngal,      xi,     chi2,       g_occupation};
 }
 
-// Host arrays, slab by slab on lane 0: the occupations and the cotangents go up in one workspace,
-// the results come down from another.  `value`: xi (n_draws, n_r), or chi2 (n_draws) with
-// chi2_data.
-int vjp_host(tc_table* t, const double* occupation, int64_t n_draws, const double* g_ngal,
-             const double* g_xi, const double* chi2_data, double* ngal, double* value,
-             double* g_occupation) {
-  TC_HIP(hipSetDevice(t->device));
-  int status = TC_OK;
-  if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  const bool chi2 = chi2_data != nullptr;
-  const size_t n_r = (size_t)t->n_r, n_bins = (size_t)t->n_bins;
-  return for_each_slab(n_draws, max_slab(t), [&](int64_t begin, int64_t n_slab) {
-    const size_t n = (size_t)n_slab;
-    const size_t value_count = chi2 ? n : n * n_r;
-    int status = t->occupation.reserve(n * (n_bins + n_r + 1) * 8, t->stream);
-    if (status == TC_OK) status = t->out_ngal.reserve(n * 8, t->stream);
-    if (status == TC_OK) status = t->out_xi.reserve((n * n_bins + value_count) * 8, t->stream);
-    if (status != TC_OK) return status;
-    double* d_occupation = (double*)t->occupation.ptr;
-    double* d_g_xi = d_occupation + n * n_bins;
-    double* d_g_ngal = d_g_xi + n * n_r;
-    double* d_ngal = (double*)t->out_ngal.ptr;
-    double* d_g_occupation = (double*)t->out_xi.ptr;
-    double* d_value = d_g_occupation + n * n_bins;
-    TC_HIP(hipMemcpyAsync(d_occupation, occupation + (size_t)begin * n_bins, n * n_bins * 8,
-                          hipMemcpyHostToDevice, t->stream));
-    if (!chi2)
-      TC_HIP(hipMemcpyAsync(d_g_xi, g_xi + (size_t)begin * n_r, n * n_r * 8,
-                            hipMemcpyHostToDevice, t->stream));
-    if (!chi2 && g_ngal != nullptr)
-      TC_HIP(hipMemcpyAsync(d_g_ngal, g_ngal + begin, n * 8, hipMemcpyHostToDevice, t->stream));
-    status = vjp_device(t, GradLane::kPinned, d_occupation, n_slab,
-                        !chi2 && g_ngal != nullptr ? d_g_ngal : nullptr, chi2 ? nullptr : d_g_xi,
-                        chi2_data, d_ngal, chi2 ? nullptr : d_value, chi2 ? d_value : nullptr,
-                        d_g_occupation);
-    if (status != TC_OK) return status;
-    TC_HIP(hipMemcpyAsync(ngal + begin, d_ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
-    TC_HIP(hipMemcpyAsync(value + (size_t)begin * (chi2 ? 1 : n_r), d_value, value_count * 8,
-                          hipMemcpyDeviceToHost, t->stream));
-    TC_HIP(hipMemcpyAsync(g_occupation + (size_t)begin * n_bins, d_g_occupation, n * n_bins * 8,
-                          hipMemcpyDeviceToHost, t->stream));
-    TC_HIP(hipStreamSynchronize(t->stream));
-    return (int)TC_OK;
-  });
-}
+// (the launcher of the staging path: one launch of the table's kernel per slab)
+struct VjpLauncher {
+  tc_table* t;
+  int operator()(const VjpRequest& slab, hipStream_t stream) const {
+    return run_vjp(t, slab, stream);
+  }
+};
+VjpLauncher vjp_launcher(tc_table* t) { return VjpLauncher{t}; }
 
 }  // namespace
 
@@ -1142,8 +1101,10 @@ int tc_predict_occupation_vjp_batch_device(tc_table* t, const double* occupation
   if (n_draws == 0) return TC_OK;
   TC_CHECK(occupation_device && g_xi_device && ngal_device && xi_device && g_occupation_device,
            "NULL pointer");
-  return vjp_device(t, GradLane::kNext, occupation_device, n_draws, g_ngal_device, g_xi_device,
-                    nullptr, ngal_device, xi_device, nullptr, g_occupation_device);
+  return vjp_device(t, GradLane::kNext,
+                    vjp_request(t, occupation_device, n_draws, g_ngal_device, g_xi_device, nullptr,
+                                ngal_device, xi_device, nullptr, g_occupation_device),
+                    vjp_launcher(t));
 }
 
 int tc_predict_occupation_vjp_batch(tc_table* t, const double* occupation, int64_t n_draws,
@@ -1153,7 +1114,10 @@ int tc_predict_occupation_vjp_batch(tc_table* t, const double* occupation, int64
   if (status != TC_OK) return status;
   if (n_draws == 0) return TC_OK;
   TC_CHECK(occupation && g_xi && ngal && xi && g_occupation, "NULL pointer");
-  return vjp_host(t, occupation, n_draws, g_ngal, g_xi, nullptr, ngal, xi, g_occupation);
+  return vjp_host(t,
+                  vjp_request(t, occupation, n_draws, g_ngal, g_xi, nullptr, ngal, xi, nullptr,
+                              g_occupation),
+                  vjp_launcher(t));
 }
 
 int tc_chi2_occupation_grad_batch_device(tc_table* t, const double* occupation_device,
@@ -1169,9 +1133,10 @@ int tc_chi2_occupation_grad_batch_device(tc_table* t, const double* occupation_d
   TC_HIP(hipSetDevice(t->device));
   status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
-  return vjp_device(t, GradLane::kNext, occupation_device, n_draws, nullptr, nullptr,
-                    t->chi2.device(), ngal_device, nullptr, chi2_device,
-                    dchi2_docc_device);
+  return vjp_device(t, GradLane::kNext,
+                    vjp_request(t, occupation_device, n_draws, nullptr, nullptr, t->chi2.device(),
+                                ngal_device, nullptr, chi2_device, dchi2_docc_device),
+                    vjp_launcher(t));
 }
 
 int tc_chi2_occupation_grad_batch(tc_table* t, const double* occupation, int64_t n_draws,
@@ -1184,8 +1149,10 @@ int tc_chi2_occupation_grad_batch(tc_table* t, const double* occupation, int64_t
   TC_HIP(hipSetDevice(t->device));
   status = upload_operands(t, data, precision);
   if (status != TC_OK) return status;
-  return vjp_host(t, occupation, n_draws, nullptr, nullptr, t->chi2.device(),
-                  ngal, chi2, dchi2_docc);
+  return vjp_host(t,
+                  vjp_request(t, occupation, n_draws, nullptr, nullptr, t->chi2.device(), ngal,
+                              nullptr, chi2, dchi2_docc),
+                  vjp_launcher(t));
 }
 
 namespace {

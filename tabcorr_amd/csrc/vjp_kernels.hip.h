@@ -1,5 +1,6 @@
 // Vector-Jacobian product of predict(occupation) with respect to the occupation array, one launch
-// per batch (vjp.h: the formulas, the argument block and the LDS budget; launch.hip: run_vjp).
+// per batch (vjp.h: the formulas, the argument block and the LDS budget; launch.hip: run_vjp;
+// vjp_device.hip.h: the pieces these kernels share with the joint's, joint_vjp_kernels.hip.h).
 //
 // A workgroup of four waves carries kGradDraws = 16 draws, one per LDS column:
 //   1  w = n . n_h of every bin from the caller's array (reference row order, through perm) into
@@ -24,99 +25,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "grad_device.hip.h"
-#include "vjp.h"
+#include "vjp_device.hip.h"
 
 namespace tc {
-
-namespace vjp {
-
-// One pass of mode auto over the row tiles of this wave.  with_q: qpart[(r 4 + wave), col] +=
-// the tiles' share of w . U_r (qpart starts at zero); with_g: gsum[i, col] = sum_r g_r U_ri for
-// the rows i of the tiles.  lane = (row group l / 16, draw l % 16); D[row = l / 16 + 4 v][draw]
-// in register v.
-__device__ __forceinline__ void auto_pass(const VjpArgs& a, const double* w, const double* gbar,
-                                          double* gsum, double* qpart, int zero_row, bool with_q,
-                                          bool with_g) {
-  const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
-  const int group = lane / kGradDraws, col = lane % kGradDraws;
-  const int n_bins = a.n_bins, n_r = a.n_r;
-  const int tiles = a.row_tiles, steps = a.k_steps;
-  using grad::f64x4;
-  for (int tile = wave; tile < tiles; tile += kGradWaves) {
-    double w_row[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int i = 16 * tile + group + 4 * v;
-      w_row[v] = w[(i < n_bins ? i : zero_row) * kGradDraws + col];
-    }
-    f64x4 g = {0.0, 0.0, 0.0, 0.0};
-    for (int r = 0; r < n_r; ++r) {
-      const double* a_lane = a.matrix + ((size_t)r * tiles + tile) * steps * 64 + lane;
-      const f64x4 u = grad::dense_tile_product(a_lane, steps, w, group, col, [=](int j) {
-        return j < n_bins ? j : zero_row;
-      });
-      if (with_q) {
-        double q = 0.0;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) q = fma(w_row[v], u[v], q);
-        q = grad::sum_row_groups(q);
-        if (group == 0) qpart[(r * kGradWaves + wave) * kGradDraws + col] += q;
-      }
-      if (with_g) {
-        const double g_r = gbar[r * kGradDraws + col];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) g[v] = fma(g_r, u[v], g[v]);
-      }
-    }
-    if (with_g) {
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int i = 16 * tile + group + 4 * v;
-        if (i < n_bins) gsum[i * kGradDraws + col] = g[v];
-      }
-    }
-  }
-}
-
-// Likelihood form, items (r, draw): gbar_r = sum_s (P_rs + P_sr) e_s = (2 P_sym e)_r and pe_r =
-// (P e)_r with e = xi - data, in s order.
-__device__ __forceinline__ void chi2_cotangent(const VjpArgs& a, const double* xis, double* gbar,
-                                               double* pe) {
-  const int n_r = a.n_r;
-  const double* data = a.chi2_data;
-  const double* precision = a.chi2_data + n_r;
-  for (int item = threadIdx.x; item < n_r * kGradDraws; item += kGradThreads) {
-    const int r = item / kGradDraws, col = item % kGradDraws;
-    double both = 0.0, row = 0.0;
-    for (int s = 0; s < n_r; ++s) {
-      const double e = xis[s * kGradDraws + col] - data[s];
-      const double p_rs = precision[(size_t)r * n_r + s];
-      both = fma(p_rs + precision[(size_t)s * n_r + r], e, both);
-      row = fma(p_rs, e, row);
-    }
-    gbar[item] = both;
-    pe[item] = row;
-  }
-}
-
-// Threads 0 .. 15 = draw: c = sum_r g_r xi_r into `dot` and, likelihood form, chi2 = e . (P e).
-__device__ __forceinline__ void finish_draws(const VjpArgs& a, const double* xis,
-                                             const double* gbar, const double* pe, double* dot,
-                                             int64_t draw0) {
-  const int t = threadIdx.x;
-  if (t >= kGradDraws) return;
-  const int n_r = a.n_r;
-  double c = 0.0, chi2 = 0.0;
-  for (int r = 0; r < n_r; ++r) c = fma(gbar[r * kGradDraws + t], xis[r * kGradDraws + t], c);
-  dot[t] = c;
-  if (a.g_xi != nullptr) return;
-  for (int r = 0; r < n_r; ++r)
-    chi2 = fma(xis[r * kGradDraws + t] - a.chi2_data[r], pe[r * kGradDraws + t], chi2);
-  if (draw0 + t < a.n_draws) a.chi2[draw0 + t] = chi2;
-}
-
-}  // namespace vjp
 
 // ---- mode auto ----------------------------------------------------------------------------------
 __global__ __launch_bounds__(kGradThreads) void vjp_auto_kernel(const VjpArgs a) {
@@ -155,7 +66,8 @@ __global__ __launch_bounds__(kGradThreads) void vjp_auto_kernel(const VjpArgs a)
   }
 
   // phase 2: the product (the likelihood form: for q_r alone)
-  vjp::auto_pass(a, w, gbar, gsum, qpart, zero_row, true, !likelihood);
+  const vjp::OneTable table{a, true};
+  vjp::auto_pass(a, table, w, gbar, gsum, qpart, zero_row, true, !likelihood);
   __syncthreads();
   const double ngal = total[col];
   const double inv_ngal = 1.0 / ngal;
@@ -175,9 +87,9 @@ __global__ __launch_bounds__(kGradThreads) void vjp_auto_kernel(const VjpArgs a)
     vjp::chi2_cotangent(a, xis, gbar, qpart);
     __syncthreads();
     // the product once more, now with its cotangent
-    vjp::auto_pass(a, w, gbar, gsum, qpart, zero_row, false, true);
+    vjp::auto_pass(a, table, w, gbar, gsum, qpart, zero_row, false, true);
   }
-  vjp::finish_draws(a, xis, gbar, qpart, total + kGradDraws, draw0);
+  vjp::finish_draws(a, table, xis, gbar, qpart, total + kGradDraws, nullptr, draw0);
   __syncthreads();
 
   // phase 3
@@ -187,7 +99,7 @@ __global__ __launch_bounds__(kGradThreads) void vjp_auto_kernel(const VjpArgs a)
   for (int item = t; item < n_bins * kGradDraws; item += kGradThreads) {
     const int i = item / kGradDraws;
     a.g_occupation[draw * n_bins + a.perm[i]] =
-        a.n_h[i] * (g_ngal + 2.0 * inv_ngal2 * gsum[item] - 2.0 * inv_ngal * c);
+        vjp::chain_rule(a.n_h[i], g_ngal, inv_ngal, inv_ngal2, gsum[item], c, 0.0, 0.0);
   }
 }
 
@@ -248,7 +160,8 @@ __global__ __launch_bounds__(kGradThreads) void vjp_cross_kernel(const VjpArgs a
     vjp::chi2_cotangent(a, xis, gbar, y);
     __syncthreads();
   }
-  vjp::finish_draws(a, xis, gbar, y, total + kGradDraws, draw0);
+  const vjp::OneTable table{a, false};
+  vjp::finish_draws(a, table, xis, gbar, y, nullptr, total + kGradDraws, draw0);
   __syncthreads();
 
   // pass 2
@@ -261,7 +174,7 @@ __global__ __launch_bounds__(kGradThreads) void vjp_cross_kernel(const VjpArgs a
     double sum = 0.0;
     for (int r = 0; r < n_r; ++r) sum = fma(gbar[r * kGradDraws + col], row[r], sum);
     a.g_occupation[draw * n_bins + a.perm[i]] =
-        a.n_h[i] * (g_ngal + sum * inv_ngal - c * inv_ngal);
+        vjp::chain_rule(a.n_h[i], g_ngal, inv_ngal, 0.0, 0.0, 0.0, sum, c);
   }
 }
 

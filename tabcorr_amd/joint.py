@@ -10,7 +10,10 @@ their derivatives once per draw, every table's contraction, and chi2, its
 gradient and the Fisher matrix against the full ``(N, N)`` precision matrix,
 ``N`` the sum of the tables' correlation function bins.  The forward calls
 `predict_batch` and `chi2_batch` -- what an ensemble sampler asks per step --
-take a launch of their own kind, without any derivative.
+take a launch of their own kind, without any derivative.  For every other
+occupation model there is the occupation seam: `predict_occupation`,
+`predict_vjp`, `chi2_occupation` and `chi2_grad_occupation` take the occupation
+array itself, again one launch for all tables.
 """
 
 import ctypes
@@ -99,9 +102,19 @@ class JointLikelihood:
     order: table ``k`` owns ``joint.slices[k]`` of the ``joint.n_r_total``
     entries of ``data`` and of the rows and columns of ``precision``.
 
-    Plain Zheng07 and, with ``assembias=True``, the model decorated with
-    assembly bias (7 columns wherever 5 stand); total correlation functions,
-    float64 tables.
+    Total correlation functions, float64 tables.  Which calls serve which
+    model:
+
+    - the calls that take ``theta`` -- `predict_batch`, `chi2_batch`,
+      `predict_batch_grad`, `chi2_grad_batch`, `chi2_fisher_batch`,
+      `fisher_batch` and the un-batched `predict_grad`, `chi2_fisher` --
+      serve plain Zheng07 and, with ``assembias=True``, the model decorated
+      with assembly bias (7 columns wherever 5 stand);
+      ``family='leauthaud11'`` raises ``NotImplementedError``;
+    - the calls that take the occupation array -- `predict_occupation`,
+      `predict_vjp`, `chi2_occupation`, `chi2_grad_occupation` -- serve ANY
+      occupation model, Leauthaud11 and custom ones among them: the caller
+      contracts their results with the model's own ``d<N>/dtheta``.
     """
 
     def __init__(self, tabcorr_list):
@@ -289,6 +302,128 @@ class JointLikelihood:
             modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
             family=family)
         return ngal, dngal, fisher
+
+    # -- the occupation seam: any occupation model -----------------------------
+
+    def _cotangents(self, g_xis, n_draws, batched):
+        """``g_xis`` -- a list with one array per table of shape ``(n_draws, )
+        + tpcf_shape``, or one ``(n_draws, N)`` array (without the leading
+        axis when un-batched) -- on the joint axis, contiguous ``(n_draws,
+        N)``, or a ValueError."""
+        leading = (n_draws, ) if batched else ()
+        if isinstance(g_xis, (list, tuple)):
+            if len(g_xis) != len(self.tabcorr_list):
+                raise ValueError('g_xis must hold one array per table ({}), '
+                                 'got {}.'.format(len(self.tabcorr_list),
+                                                  len(g_xis)))
+            parts = []
+            for k, (part, halotab) in enumerate(zip(g_xis,
+                                                    self.tabcorr_list)):
+                part = np.asarray(part, dtype=np.float64)
+                shape = leading + tuple(halotab.tpcf_shape)
+                if part.shape != shape:
+                    raise ValueError('g_xis of table {} must have shape {}, '
+                                     'got {}.'.format(k, shape, part.shape))
+                parts.append(part.reshape(n_draws, -1))
+            return _lib.contiguous(np.concatenate(parts, axis=1))
+        g_xi = np.asarray(g_xis, dtype=np.float64)
+        if g_xi.shape != leading + (self.n_r_total, ):
+            raise ValueError('g_xis must be a list of per-table arrays or '
+                             'have shape {}, got {}.'.format(
+                                 leading + (self.n_r_total, ), g_xi.shape))
+        return _lib.contiguous(g_xi.reshape(n_draws, self.n_r_total))
+
+    def _predict_occupation(self, occupation, g_xis, g_ngal):
+        """`predict_occupation` (``g_xis`` None) and `predict_vjp`: the
+        arguments are checked before any device is touched."""
+        occupation, batched = self.tabcorr_list[0]._vjp_occupation(occupation)
+        n_draws = len(occupation)
+        g_xi = None
+        if g_xis is not None:
+            g_xi = self._cotangents(g_xis, n_draws, batched)
+            if g_ngal is not None:
+                g_ngal = np.asarray(g_ngal, dtype=np.float64)
+                if g_ngal.shape != ((n_draws, ) if batched else ()):
+                    raise ValueError(
+                        'g_ngal must have shape {}, got {}.'.format(
+                            (n_draws, ) if batched else (), g_ngal.shape))
+                g_ngal = _lib.contiguous(g_ngal.reshape(n_draws))
+        device = self.to_device()
+        ngal = np.empty(n_draws)
+        xi = np.empty((n_draws, self.n_r_total))
+        g_occupation = None if g_xi is None else np.empty_like(occupation)
+        with device.lock:
+            _lib.check(device.lib.tc_joint_predict_occupation_vjp_batch(
+                device.handle, _lib.as_double_p(occupation), n_draws, 0,
+                None if g_ngal is None else _lib.as_double_p(g_ngal),
+                None if g_xi is None else _lib.as_double_p(g_xi),
+                _lib.as_double_p(ngal), _lib.as_double_p(xi),
+                None if g_xi is None else _lib.as_double_p(g_occupation)))
+        xis = self._split(xi, (n_draws, ))
+        if not batched:
+            ngal, xis = ngal[0], [part[0] for part in xis]
+            g_occupation = None if g_xi is None else g_occupation[0]
+        return ngal, xis, g_occupation
+
+    def predict_occupation(self, occupation):
+        """``predict(occupation)`` of every table in one launch, for ANY
+        occupation model: ``ngal`` ``(n_draws, )`` and ``xis``, per table
+        ``(n_draws, ) + tpcf_shape``.  ``occupation`` is ``(n_draws, n_bins)``
+        in the row order of ``gal_type``, or ``(n_bins, )`` (un-batched: a
+        float and arrays of ``tpcf_shape``).  Raises ``NotImplementedError``
+        for a joint whose rows do not fit the kernel's LDS."""
+        return self._predict_occupation(occupation, None, None)[:2]
+
+    def predict_vjp(self, occupation, g_xis, g_ngal=None):
+        """`predict_occupation` with its vector-Jacobian product with respect
+        to the occupation array (`TabCorr.predict_vjp` for all the tables at
+        once): ``g_occupation[d, i] = g_ngal[d] dngal[d] / dn[d, i] + sum_r
+        g_xi[d, r] dxi[d, r] / dn[d, i]`` with ``r`` over the joint axis, in
+        one kernel launch.  ``g_xis`` is a list with one array per table of
+        shape ``(n_draws, ) + tpcf_shape``, or one ``(n_draws, N)`` array;
+        ``g_ngal`` ``(n_draws, )`` or None = 0.  Returns ``ngal, xis,
+        g_occupation``, the last ``(n_draws, n_bins)`` in the row order of
+        ``gal_type``."""
+        if g_xis is None:
+            raise ValueError('g_xis is None: predict_occupation is the '
+                             'forward-only call.')
+        return self._predict_occupation(occupation, g_xis, g_ngal)
+
+    def _chi2_occupation(self, occupation, data, precision, gradient):
+        occupation, batched = self.tabcorr_list[0]._vjp_occupation(occupation)
+        data, precision = self._operands(data, precision)
+        device = self.to_device()
+        n_draws = len(occupation)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        dchi2 = np.empty_like(occupation) if gradient else None
+        with device.lock:
+            _lib.check(device.lib.tc_joint_chi2_occupation_grad_batch(
+                device.handle, _lib.as_double_p(occupation), n_draws, 0,
+                _lib.as_double_p(data), _lib.as_double_p(precision),
+                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
+                _lib.as_double_p(dchi2) if gradient else None))
+        if not batched:
+            return ngal[0], chi2[0], dchi2[0] if gradient else None
+        return ngal, chi2, dchi2
+
+    def chi2_occupation(self, occupation, data, precision):
+        """``chi2 = (xi - data)^T precision (xi - data)`` of the concatenated
+        `predict_occupation`, finished in the launch: ``ngal, chi2``
+        ``(n_draws, )`` (scalars for a 1-D occupation).  ``data`` and
+        ``precision`` as `chi2_grad_batch` takes them."""
+        return self._chi2_occupation(occupation, data, precision, False)[:2]
+
+    def chi2_grad_occupation(self, occupation, data, precision):
+        """`chi2_occupation` with its gradient with respect to the occupation
+        array -- `predict_vjp` with ``g = 2 P_sym (xi - data)`` over the joint
+        axis and ``g_ngal = 0``, formed on the device in the same launch, so
+        that the off-diagonal blocks of ``precision`` couple the tables:
+        ``ngal, chi2, dchi2_docc``, the last ``(n_draws, n_bins)`` in the row
+        order of ``gal_type``.  Contracted with the caller's own
+        ``d<N>/dtheta`` it is the gradient of the joint likelihood for EVERY
+        occupation model (``examples/example_joint_custom_model_grad.py``:
+        Leauthaud11)."""
+        return self._chi2_occupation(occupation, data, precision, True)
 
     # -- un-batched forms -----------------------------------------------------
 
