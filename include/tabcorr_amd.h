@@ -850,6 +850,16 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *                 no expansion serves (sigma_logM below about a tenth of a bin width, parameters
  *                 to fix up) join the deferred pairs: the node loops of BOTH galaxy types leave
  *                 the loop of bins (configs[1] 37.8 -> 37.2 us).  0: the node loops in place.
+ *   "fused_skip"  1 (default): the one-launch form with eight waves x 64 draws and "fused_defer" 2
+ *                 places a workgroup's draws in its density array in the order of M0 and
+ *                 issues no matrix instruction for a block of four bins whose densities are
+ *                 exactly zero for all 16 draws of a group (a Zheng07 satellite bin is, for
+ *                 every draw with M0 at or above it) -- only where that keeps the bits: every
+ *                 matrix entry finite, every pair-weight sum of the workgroup below 1e280.
+ *                 The parts (0, 1) and (2, 3) of the matrix units then share a SIMD, since the
+ *                 zero blocks lie in the later parts.  BASELINE configs[1] 35.9 -> 34.4 us per
+ *                 10^4 draws.  3: the parts paired as ever; 2: the draws where they are as
+ *                 well; 0: every product.  Same bits all four (profiles/skip_notes.md).
  *   "cross_wide_min_draws"  default 4096.  Mode cross (tpcf_matrix with one column per halo
  *                 bin), tables or interpolators of up to 16 result rows whose node groups have
  *                 at most two members: undecorated batches of this many draws take the one-launch

@@ -388,6 +388,10 @@ struct Tuning {
   int cross_defer = 1;          // mode cross, one launch: deferred (group, draw) pairs (kernel_args.h)
   int fused_defer = 2;          // predict_fused_kernel: 1 the satellites' expansion + deferred
                                 // pairs, 2 the centrals' likewise (where their expansion is on)
+  int fused_skip = 1;           // predict_fused_kernel, 8 x 64 with fused_defer 2 (fused_skip.h): 1 the
+                                // draws of a workgroup in the order of M0, no products of all-zero
+                                // density blocks, the parts (0, 1) / (2, 3) on a SIMD; 3 the parts
+                                // paired as ever; 2 the draws where they are as well; 0 none of it
   int fused_sat_cap = 6;        // ... in place up to 12 + 4 x this many terms (0 .. 5), or
                                 // 6 = series::sat::kShortest: the shortest that serves the bin
   int cross_wide_min_draws = 4096;   // launch.hip: choose_cross_fused (0: never the wide form)

@@ -352,7 +352,9 @@ struct FusedArgs {
   int separate;              // 1: ngal (n_draws, 2), xi (n_draws, 3, n_r): cc, cs, ss
   int n_r;
   int priority;              // wave priorities: phase 2 | phase 1 << 2 | phase 3 << 4; bits 8 - 10:
-                             // developer knobs; bit 11: every entry of the matrix is finite
+                             // developer knobs; bit 11: every entry of the matrix is finite;
+                             // bit 13: no products of all-zero density blocks, bit 14: a
+                             // workgroup's draws in the order of M0 (fused_skip.h)
   int64_t n_draws;
   const double* log_m;       // quadrature constants as in OccArgs
   const double* m;

@@ -16,6 +16,7 @@
 #include "epilogue.h"
 #include "fastmath.h"
 #include "fused_walk.h"
+#include "fused_skip.h"
 #include "hostmath.h"
 #include "kernel_args.h"
 #include "series.h"
@@ -2168,6 +2169,79 @@ __device__ __forceinline__ void fused_quad_pass(__amdgpu_buffer_rsrc_t rs_t, uns
       });
 }
 
+// The same pass with the products of all-zero density blocks left out (fused_skip.h): mask_b /
+// mask_e hold, two bits per block (the tile's even and odd draws: b.x / e.x and b.y / e.y), the
+// blocks of the component's columns / rows whose 64 densities are zero for the group.  The
+// loads and the walk are fused_quad_pass's; a unit costs one extract of its two bits and a
+// branch per group around the group's products.
+template <int UU, int DL>
+__device__ __forceinline__ void fused_quad_pass_skip(__amdgpu_buffer_rsrc_t rs_t, unsigned off_a,
+                                                     unsigned unit_bytes, const double* dens_b,
+                                                     const double* dens_e, const FusedPart& part,
+                                                     uint64_t mask_b, uint64_t mask_e,
+                                                     double (&F)[2][2]) {
+  f64x2 t[2], b[2];
+  f64x4 D[UU][2];
+  f64x2 e[4];
+  unsigned row_bits = 0;
+  fused_walk(
+      part,
+      [&](auto stage, unsigned unit, int column, bool) {
+        constexpr int kStage = decltype(stage)::value;
+        t[kStage] = buffer_load16<0>(rs_t, off_a, unit * unit_bytes);
+        b[kStage] = *(const f64x2*)(dens_b + 4 * column * DL);
+      },
+      [&](int rb) {
+        row_bits = skip_bits(mask_e, rb);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) e[v] = *(const f64x2*)(dens_e + (4 * rb + v) * DL);
+      },
+      [&](auto stage, bool first, int, int cb) {
+        constexpr int kStage = decltype(stage)::value;
+        auto products = [&](auto group, bool start) {
+          constexpr int G = decltype(group)::value;
+          const double bv = G ? b[kStage].y : b[kStage].x;
+#pragma unroll
+          for (int u = 0; u < UU; ++u) {
+            const double av = u ? t[kStage].y : t[kStage].x;
+            if (start) {
+              const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
+              D[u][G] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, zero, 0, 0, 0);
+            } else {
+              D[u][G] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, D[u][G], 0, 0, 0);
+            }
+          }
+        };
+        skip_consume(
+            first, row_bits, row_bits | skip_bits(mask_b, cb),
+            products,
+            [&](auto group) {
+              constexpr int G = decltype(group)::value;
+              const f64x4 zero = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+              for (int u = 0; u < UU; ++u) D[u][G] = zero;
+            });
+      },
+      [&]() {
+        t[0] = t[1];
+        b[0] = b[1];
+      },
+      [&](int) {
+        if (!(row_bits & 1u)) {
+#pragma unroll
+          for (int u = 0; u < UU; ++u)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) F[u][0] = fma(D[u][0][v], e[v].x, F[u][0]);
+        }
+        if (!(row_bits & 2u)) {
+#pragma unroll
+          for (int u = 0; u < UU; ++u)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) F[u][1] = fma(D[u][1][v], e[v].y, F[u][1]);
+        }
+      });
+}
+
 // Inclusive prefix sum of `value` over the 64 lanes: inside the rows of 16 lanes by shifts, then
 // across them by the two row broadcasts (data-parallel primitives: no LDS round trips).
 __device__ __forceinline__ int wave_prefix_sum(int value) {
@@ -2412,6 +2486,12 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
   const int64_t b0 = col + draw;
   const int64_t b = b0 < a.n_draws ? b0 : a.n_draws - 1;
   double norm;
+  // SKIP (fused_skip.h): the column of the lane's draw in the density array -- its rank by M0
+  // among the workgroup's draws, so that the draws whose lowest satellite bins are exactly zero
+  // share their groups of 16 -- and, in phase 2, no products of all-zero blocks.  a.priority,
+  // bit 13: skip, bit 14: order, bit 15: which parts share a SIMD.
+  constexpr bool SKIP = SATDEFER == 2 && DL == 64 && W == 8;
+  int at = draw;
   {
     // (every wave sets up its lanes' draws itself: cheaper than a hand-over through LDS)
     const double* th = a.theta + b * a.n_theta;
@@ -2423,6 +2503,18 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
                               : draw_params<ASSEMBIAS>(table, kc, th);
     series_setup<MODULATE>(dp, (GROUPED ? a.group.series : a.series) != nullptr && DL != 32,
                            (GROUPED ? a.group.sat_series : a.sat_series) != nullptr && DL != 32);
+    if constexpr (SKIP) {
+      if ((a.priority >> 14) & 1) {
+        // (every wave ranks its lanes' draws itself, as it sets them up itself: a draw that
+        // takes no satellites at all has M0 = 1e300 here and ranks last)
+        const uint32_t key = skip_unique_key(skip_key(dp.m0), lane);
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < 64; ++j)
+          rank += (uint32_t)__builtin_amdgcn_readlane((int)key, j) < key ? 1 : 0;
+        at = skip_column(rank);
+      }
+    }
     sc_f64 log_m = (sc_f64)a.log_m;
     sc_f64 mass = (sc_f64)a.m;
     sc_f64 weight = (sc_f64)a.weight;
@@ -2491,7 +2583,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
                             SATDEFER ? &deferred : nullptr);
       if (SATDEFER && deferred && live) mine |= 1u << ((g - wave) / W);
       const double value = acc * n_h[g];
-      if (half == 0 && live) dens_at(g, draw) = value;
+      if (half == 0 && live) dens_at(g, at) = value;
       if (central) sum_cen += value; else sum_sat += value;
     }
     wave_stamp(0);
@@ -2534,6 +2626,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
         const double sat_scale = __shfl(dp.sat_scale, from, 64);
         const double alpha = __shfl(dp.alpha, from, 64);
         const int bad = __shfl(dp.bad, from, 64);
+        const int at_from = SKIP ? __shfl(at, from, 64) : from;
         double acc = 0.0;
         const bool cen_pair = SATDEFER == 2 && g < a.n_central;
         if (SATDEFER == 2 && __builtin_amdgcn_ballot_w64(active && cen_pair) != 0) {
@@ -2590,7 +2683,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
         }
         if (!cen_pair) acc = sat;
         }
-        if (active) dens_at(g, from) = acc * a.n_h[g];
+        if (active) dens_at(g, at_from) = acc * a.n_h[g];
         wave_stamp(4);
       }
       // (the draw's deferred bins, in bin order)
@@ -2598,7 +2691,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
         if (left != 0) {
           const int j = __builtin_ctz(left);
           left &= left - 1;
-          const double value = dens_at(wave + W * j, draw);
+          const double value = dens_at(wave + W * j, at);
           if (SATDEFER == 2 && wave + W * j < a.n_central) sum_cen += value;
           else sum_sat += value;
         }
@@ -2625,6 +2718,13 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
       } else {
         a.ngal[b0] = total;
       }
+    }
+    if constexpr (SKIP) {
+      // (from here on a lane holds the pair-weight sum of the draw in ITS column)
+      const long long bits = __builtin_bit_cast(long long, norm);
+      const int lo = __builtin_amdgcn_ds_permute(at * 4, (int)bits);
+      const int hi = __builtin_amdgcn_ds_permute(at * 4, (int)(bits >> 32));
+      norm = __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
     }
   }
 
@@ -2677,7 +2777,12 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     // tile's waves take the parts half a turn on, so that the pair does not reach its row ends
     // and waits in the same cycle)
     const int sub = wave / PARTS;
-    const int part = (wave % PARTS + sub * (PARTS / 2)) % PARTS;
+    // (SKIP, a.priority bit 15: the zero blocks lie in the later parts, the second most of them, so
+    // a SIMD holds the parts (0, 1) or (2, 3) instead: its two waves' work adds up more evenly)
+    const int quarter = wave % PARTS;
+    const int part = SKIP && ((a.priority >> 15) & 1)
+                         ? ((((quarter & 1) << 1) | (quarter >> 1)) ^ sub)
+                         : (quarter + sub * (PARTS / 2)) % PARTS;
     slot = sub * PARTS + part;
     const unsigned off_a = lane * 16;
     // (the component's columns are density rows j_row0 ..., its rows i_row0 ...)
@@ -2689,10 +2794,56 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     const FusedPart walk = {a.part_rb0[part],        a.part_cb0[part],
                             a.part_count[part],      a.part_triangular[part],
                             a.part_n_cb[part],       (unsigned)a.part_unit_base[part]};
+    // SKIP: the masks of this wave's tile over the blocks of its component's columns and rows
+    // (fused_skip.h; every wave reads its own: 16 bytes per lane and two ballots per block, no
+    // barrier), where leaving products out keeps the bits: every matrix entry finite (bit 11),
+    // every draw's pair-weight sum below 1e280.  Only the blocks the part touches count: a wave
+    // with no zero block among them -- the first part, the centrals' rows -- walks as ever.
+    uint64_t mask_b = 0, mask_e = 0;
+    if constexpr (SKIP) {
+      if (((a.priority >> 11) & 1) && ((a.priority >> 13) & 1) &&
+          a.dens_rows <= 4 * kSkipMaxBlocks &&
+          __builtin_amdgcn_ballot_w64(!(norm < 1e280)) == 0) {
+        int rb_last = walk.rb0;
+        for (int left = walk.count - (walk_row_length(walk, walk.rb0) - walk.cb0); left > 0;
+             left -= walk_row_length(walk, rb_last))
+          ++rb_last;
+        auto masks = [&](const double* first, int row0, int block0, int block1) {
+          uint64_t mask = 0;
+          const int n_blocks = (a.dens_rows - row0) >> 2;
+          for (int block = block0; block <= block1 && block < n_blocks; ++block) {
+            const f64x2 value = *(const f64x2*)(first + 4 * block * DL);
+            const unsigned bits =
+                (__builtin_amdgcn_ballot_w64(!skip_is_zero(value.x)) == 0 ? 1u : 0u) |
+                (__builtin_amdgcn_ballot_w64(!skip_is_zero(value.y)) == 0 ? 2u : 0u);
+            mask |= (uint64_t)bits << (2 * block);
+          }
+          return mask;
+        };
+        if (walk.count > 0) {
+          mask_b = masks(dens_b, a.part_j_row0[part], 0,
+                         walk.triangular ? rb_last : walk.n_cb - 1);
+          mask_e = a.part_i_row0[part] == a.part_j_row0[part] && walk.triangular
+                       ? mask_b & (~(uint64_t)0 << (2 * walk.rb0))
+                       : masks(dens_e + kq * DL, a.part_i_row0[part], walk.rb0, rb_last);
+        }
+      }
+    }
 #pragma unroll
     for (int p = 0; p < UP; ++p) {
       F[p][0][0] = F[p][0][1] = F[p][1][0] = F[p][1][1] = 0.0;
       if (skip & 2) continue;
+      if constexpr (SKIP) {
+        if ((mask_b | mask_e) != 0) {
+          if (2 * p + 1 < U)
+            fused_quad_pass_skip<2, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk,
+                                        mask_b, mask_e, F[p]);
+          else
+            fused_quad_pass_skip<1, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk,
+                                        mask_b, mask_e, F[p]);
+          continue;
+        }
+      }
       if (2 * p + 1 < U)
         fused_quad_pass<2, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk, F[p]);
       else
@@ -2758,6 +2909,8 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
   stamp(9);
   set_priority((a.priority >> 4) & 3);
   double(*tile)[kLanes + 1] = (double(*)[kLanes + 1])table;
+  // (SKIP: the results of column `lane` belong to the draw that was placed there)
+  const int to = SKIP ? __builtin_amdgcn_ds_permute(at * 4, lane) : lane;
   if (a.separate) {
     // cen-cen = the first quarter of the tile's waves, cen-sat = the two middle quarters,
     // sat-sat = the last quarter, one component after the other through the results tile.  The reference forms every term / sum first
@@ -2775,7 +2928,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
         const double* first = dens + ((PARTS * sub + p_begin) * (4 * U) + rr) * kQuadTile + d;
         double sum = first[0];
         for (int p = 1; p < p_count; ++p) sum += first[p * (4 * U) * kQuadTile];
-        tile[rr][lane] = poisoned ? __builtin_nan("") : sum / norm;
+        tile[rr][to] = poisoned ? __builtin_nan("") : sum / norm;
       }
       __syncthreads();
       for (int idx = threadIdx.x; idx < a.n_r * DL; idx += blockDim.x) {
@@ -2807,7 +2960,7 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
       double sum = first[0];
 #pragma unroll
       for (int part = 1; part < PARTS; ++part) sum += first[part * (4 * U) * kQuadTile];
-      tile[rr][lane] = sum / norm;
+      tile[rr][to] = sum / norm;
     }
   }
   __syncthreads();

@@ -1011,7 +1011,12 @@ int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* t
                 ((t->tuning.prio_fused_out & 3) << 4) |
                 ((env_int_early("TC_FUSED_SKIP", 0) & 3) << 8) |  // (developer builds only)
                 // (the latency form may add its row shares four sums at a time: FusedArgs)
-                (q_table.finite ? 1 << 11 : 0);
+                (q_table.finite ? 1 << 11 : 0) |
+                // (fused_skip.h: no products of all-zero blocks | the draws in the order of M0 | the
+                // parts (0, 1) and (2, 3) on a SIMD)
+                (t->tuning.fused_skip != 0 ? 1 << 13 : 0) |
+                (t->tuning.fused_skip == 1 || t->tuning.fused_skip == 3 ? 1 << 14 : 0) |
+                (t->tuning.fused_skip == 1 ? 1 << 15 : 0);
   fa.n_draws = n_draws;
   fa.n_groups = t->node_groups.n_groups;
   fa.n_central_groups = t->node_groups.n_central_groups;

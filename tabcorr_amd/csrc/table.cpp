@@ -1583,6 +1583,10 @@ int tc_table_set_option(tc_table* t, const char* name, int value) {
     // developer A/B: 0 = predict_fused_kernel runs the satellites' node loops in place
     TC_CHECK(value >= 0 && value <= 2, "fused_defer must be 0, 1 or 2");
     t->tuning.fused_defer = value;
+  } else if (key == "fused_skip") {
+    // A/B and tests: 0 = predict_fused_kernel's matrix phase issues every product (same bits)
+    TC_CHECK(value >= 0 && value <= 3, "fused_skip must be 0 .. 3");
+    t->tuning.fused_skip = value;
   } else if (key == "fused_sat_cap") {
     TC_CHECK(value >= 0 && value <= 6, "fused_sat_cap must be in [0, 6]");
     t->tuning.fused_sat_cap = value;
