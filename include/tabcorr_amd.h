@@ -725,6 +725,59 @@ int tc_joint_interp_chi2_grad_batch_device(tc_joint_interp* joint, const double*
                                            const double* precision, double* ngal_device,
                                            double* chi2_device, double* dngal_device,
                                            double* dchi2_device, double* fisher_device);
+/* The forward form of a joint of interpolators, what an ensemble sampler over (theta, x) asks per
+ * step (tc_joint_predict_batch / tc_joint_chi2_batch with the grid's x): ngal (n_draws) and the
+ * concatenated prediction xi (n_draws, N), or chi2 (n_draws) = (xi - data)^T precision (xi - data)
+ * of the joint data vector against the full (N, N) precision matrix with xi never stored, in ONE
+ * launch per batch without any derivative, 64 draws per workgroup.  With c_k(x) the
+ * tensor-product spline weight of grid node k (x clamped to the outermost segment) and v(k) the
+ * class of halo tables at node k: ngal = sum_k c_k ngal_v(k), and per member m and row r
+ * xi[r_offset[m] + r] = sum_k c_k xi_r^(m,k), xi_r^(m,k) = d^T S_r d / ngal_v^2 over the packed
+ * triangle of the member's table at node k (mode auto) or T_r . d / ngal_v (mode cross) -- the
+ * semantics of tc_interp_predict_zheng07_batch per member.  The occupations of a class are
+ * evaluated once for all members; a mode-auto member's table runs in its own forward unit layout
+ * on the matrix cores, a mode-cross member's by one fma chain per (node, row, draw) over the bins
+ * in library order.  The arguments are those of tc_joint_interp_chi2_grad_batch without the
+ * derivative outputs; n_theta 5, or 7 with TC_FLAG_ASSEMBIAS; flags may also hold
+ * TC_FLAG_MODULATE_WITH_CENOCC.  data and precision are host arrays in both forms (uploaded when
+ * they change).
+ * One of two forms, chosen from the members' modes alone.  Rows form (a member is mode auto):
+ * every bin's densities of the class in flight stay in LDS; a workgroup needs the bytes of
+ * tc_joint_predict_batch for N rows plus 512 x (sum of the axes' nodes + 2).  Slab form (every
+ * member mode cross): the bins in slabs of 64, any number of them; 8 x (max(4096, 65 N) +
+ * max(2306, N (N + 1)) + 1024 + 128 N + 64 x (sum of the axes' nodes + 2)) bytes.
+ * TC_ERR_UNSUPPORTED with a message naming the bytes or the limit, the joint and its members
+ * staying usable: TC_FLAG_SEPARATE_GAL_TYPE, TC_FLAG_LEAUTHAUD11, any other flag; a mode-auto
+ * member of more than 20 correlation function bins (one r tile) or more than 248 bins (no unit
+ * layout of the one-launch form); a workgroup beyond 160 KiB of LDS.
+ * Guarantees: ONE form per joint.  A draw's results depend on the draw alone: not on the batch
+ * size, the draw's place in the batch, or the host or device entry.  The ngal of
+ * tc_joint_interp_chi2_batch is bit for bit that of tc_joint_interp_predict_batch, and it does
+ * not depend on which members are in the joint (only on member 0's walk over the grid).
+ * Permuting the members returns the same bits block for block (the members' lists agreeing), and
+ * so does permuting the LIST of a member other than member 0: tables are matched by grid node,
+ * the walk is member 0's.  No bit claim is made against tc_interp_predict_zheng07_batch, whose
+ * kernels cut a draw's sums where the batch size puts them.
+ * Host arrays take the forward path of the tables (page-locked staging for small calls,
+ * overlapping chunks beyond) on member 0's staging areas and lanes; the `_device` forms enqueue on
+ * its next lane and return (tc_joint_interp_synchronize waits).  There are no asynchronous
+ * entries. */
+int tc_joint_interp_predict_batch(tc_joint_interp* joint, const double* theta, int n_theta,
+                                  const double* x, int64_t n_draws, int n_gauss_prim,
+                                  unsigned flags, double* ngal, double* xi);
+int tc_joint_interp_predict_batch_device(tc_joint_interp* joint, const double* theta_device,
+                                         int n_theta, const double* x_device, int64_t n_draws,
+                                         int n_gauss_prim, unsigned flags, double* ngal_device,
+                                         double* xi_device);
+int tc_joint_interp_chi2_batch(tc_joint_interp* joint, const double* theta, int n_theta,
+                               const double* x, int64_t n_draws, int n_gauss_prim, unsigned flags,
+                               const double* data, const double* precision, double* ngal,
+                               double* chi2);
+int tc_joint_interp_chi2_batch_device(tc_joint_interp* joint, const double* theta_device,
+                                      int n_theta, const double* x_device, int64_t n_draws,
+                                      int n_gauss_prim, unsigned flags, const double* data,
+                                      const double* precision, double* ngal_device,
+                                      double* chi2_device);
 
 /* Asynchronous host-to-host forms (page-locked theta, x, outputs; see
  * tc_predict_zheng07_batch_async): upload, kernels and download of a call on one of the

@@ -145,6 +145,21 @@ int tc_debug_joint_forward_fit(int n_bins, int n_tables, const int* mode, const 
  * dimensions; n_params 5 or 7. */
 int tc_debug_joint_interp_lds_bytes(int form, int n_bins, int n_central, int n_r_total,
                                     int n_r_cross, int n_dim, int n_params, int64_t* bytes);
+/* The LDS bytes per workgroup of joint_interp_forward_kernel (tabcorr_amd/csrc/joint_interp.h:
+ * joint_interp_forward_lds_bytes) -- no device needed.  form 1: the rows form of a joint over
+ * tables of n_bins bins; form 0: the slab form (n_bins is not read); n_r_total result rows in all,
+ * n_weight_rows the sum of the grid axes' nodes, `waves` waves per workgroup (the kernel's: 8). */
+int tc_debug_joint_interp_forward_lds_bytes(int form, int n_bins, int n_r_total,
+                                            int n_weight_rows, int waves, int64_t* bytes);
+/* What the forward entries of a joint of interpolators refuse on the host, from plain numbers --
+ * no device, no handle: n_members members over tables of n_bins bins with mode[m] (0 auto, 1
+ * cross) and n_r[m] correlation function bins, on a grid of n_dim axes of n_axis[d] nodes.  TC_OK,
+ * the joint's form in *form and the workgroup's LDS in *lds_bytes (either may be NULL), or
+ * TC_ERR_UNSUPPORTED with the entry's message: a mode-auto member of more than 20 r bins or more
+ * than 248 bins, a workgroup beyond 160 KiB (*form and *lds_bytes are set). */
+int tc_debug_joint_interp_forward_fit(int n_bins, int n_members, const int* mode, const int* n_r,
+                                      int n_dim, const int* n_axis, int* form,
+                                      int64_t* lds_bytes);
 /* Groups of bins that share their Gauss-Legendre nodes (tabcorr_amd/csrc/hostmath.h:
  * find_node_groups; identical log_prim_haloprop_min / max and galaxy type), for n_bins bins in
  * library order of which the first n_central are centrals: group i = member[begin[i] ..

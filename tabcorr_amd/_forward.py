@@ -3,7 +3,7 @@ likelihoods, synchronous and asynchronous: allocate or stage the outputs, call
 the entry `_lib.FORWARD_ENTRIES` names under the handle's lock, check the
 status, return the results.  `inputs` is what follows the handle up to the
 operands: ``(theta, n_theta, ...)`` of a table, ``(theta, n_theta, x, ...)``
-of an interpolator; `shapes` those of the two results; `operands` ``(data,
+of an interpolator or a joint of interpolators; `shapes` those of the two results; `operands` ``(data,
 precision)`` of a likelihood.  A microsecond is 2 % of a small call: the
 arguments are spelt out, not looped over."""
 
@@ -26,7 +26,7 @@ def shapes(table, n_draws, flags, likelihood):
 
 
 def _run(device, kind, form, route, inputs, operands, outputs, *ticket):
-    if kind == 'interp':
+    if kind in ('interp', 'joint_interp'):
         inputs = (p(inputs[0]), inputs[1], p(inputs[2])) + inputs[3:]
     else:
         inputs = (p(inputs[0]), ) + inputs[1:]
@@ -40,7 +40,9 @@ def _run(device, kind, form, route, inputs, operands, outputs, *ticket):
 
 def call(device, kind, form, inputs, shapes, operands=(), out=None):
     """The synchronous host-array entry of a handle `kind` (``'table'``,
-    ``'interp'``, ``'joint'``: a joint of tables, called as a table) and `form` (``'predict'``, ``'chi2'``) on `device`, the
+    ``'interp'``, ``'joint'``: a joint of tables, called as a table,
+    ``'joint_interp'``: a joint of interpolators, called as an interpolator)
+    and `form` (``'predict'``, ``'chi2'``) on `device`, the
     handle's wrapper.  `out`: the caller's arrays for the results, else new
     ones (allocated in the order of the C arguments, as `_grad.call`)."""
     outputs = (empty(shapes[0]), empty(shapes[1])) if out is None else \

@@ -206,6 +206,25 @@ SIGNATURES = {
     'tc_joint_interp_synchronize': [ctypes.c_void_p],
     'tc_joint_interp_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p],
     'tc_debug_joint_interp_lds_bytes': [ctypes.c_int] * 7 + [c_int64_p],
+    # ... its forward entries: an interpolator's without the `_zheng07`
+    'tc_joint_interp_predict_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p],
+    'tc_joint_interp_predict_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
+        ctypes.c_void_p],
+    'tc_joint_interp_chi2_batch': [
+        ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        c_double_p, c_double_p],
+    'tc_joint_interp_chi2_batch_device': [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+        ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p,
+        ctypes.c_void_p, ctypes.c_void_p],
+    'tc_debug_joint_interp_forward_lds_bytes': [ctypes.c_int] * 5 + [c_int64_p],
+    'tc_debug_joint_interp_forward_fit': [ctypes.c_int, ctypes.c_int, c_int_p, c_int_p,
+                                          ctypes.c_int, c_int_p, c_int_p, c_int64_p],
     'tc_table_set_option': [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int],
     'tc_table_timer_begin': [ctypes.c_void_p, ctypes.c_int],
     'tc_table_timer_end': [ctypes.c_void_p, c_float_p],
@@ -283,9 +302,11 @@ FORWARD_ENTRIES = {
     for _kind, _prefix in (('table', ''), ('interp', 'interp_'))
     for _form in ('predict', 'chi2')
     for _route, _suffix in (('host', ''), ('device', '_device'), ('async', '_async'))}
-# (a joint of tables: the family is in the flags, and there are no asynchronous entries)
+# (the joints, of tables and of interpolators: the family is in the flags, and there are no
+# asynchronous entries)
 FORWARD_ENTRIES.update({
-    ('joint', _form, _route): 'tc_joint_%s_batch%s' % (_form, _suffix)
+    (_kind, _form, _route): 'tc_%s_%s_batch%s' % (_kind, _form, _suffix)
+    for _kind in ('joint', 'joint_interp')
     for _form in ('predict', 'chi2')
     for _route, _suffix in (('host', ''), ('device', '_device'))})
 

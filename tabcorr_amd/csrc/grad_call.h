@@ -354,10 +354,35 @@ struct InterpParts {
 InterpParts interp_parts(const tc_interp* it);
 // The argument block of an interpolator's derivative kernels but for the draws and the outputs:
 // the resident kernels of its tables stop, the walk and the classes' pointers are built.
-int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpArgs* ga);
+// with_matrices = false: the walk and the classes alone -- ga->matrices stays as it is (NULL
+// before the first derivative call) and no table's gradient matrix is built: what the forward
+// calls of a joint ask for, which read every member's own forward layouts.
+int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpArgs* ga,
+                     bool with_matrices = true);
 GradStaging interp_grad_staging(tc_interp* it);
 // The stream of the lane a derivative call takes: lane 0 (pinned) or the next of the rotation.
 hipStream_t interp_grad_stream(tc_interp* it, GradLane lane);
+// What the forward calls of a joint take from member 0 (predict_call.h: forward_chunked,
+// forward_zero_copy): its page-locked staging areas, its tickets, the device buffers of its
+// host-array calls and the stream of lane 0; n_lanes: the lanes its calls rotate over.
+struct InterpForwardParts {
+  PinnedBuffer* h_in;
+  PinnedBuffer* h_out;
+  Tickets* tickets;
+  DeviceBuffer* theta;
+  DeviceBuffer* x;
+  DeviceBuffer* out;
+  hipStream_t stream;
+  int n_lanes;
+};
+InterpForwardParts interp_forward_parts(tc_interp* it);
+// The next lane of the rotation: its stream and the staging buffers of a chunk's draws and results.
+struct InterpForwardLane {
+  hipStream_t stream;
+  DeviceBuffer* stage_in;
+  DeviceBuffer* stage_out;
+};
+InterpForwardLane interp_forward_lane(tc_interp* it);
 
 }  // namespace host
 }  // namespace tc

@@ -861,7 +861,7 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
 // inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_joint_forward.hip,
-// inst_joint_interp.hip, inst_vjp.hip, inst_joint_vjp.hip) ----
+// inst_joint_interp.hip, inst_joint_interp_forward.hip, inst_vjp.hip, inst_joint_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -904,6 +904,12 @@ int launch_joint_forward_instance(int n_gauss, bool assembias, bool modulate, in
 int launch_grad_joint_interp_instance(int n_params, int form, int device, dim3 grid, int lds,
                                       hipStream_t stream, hipEvent_t k0, hipEvent_t k1,
                                       const tc::JointInterpArgs& ja);
+// joint_interp_forward_kernel<n_gauss (10, else any), assembias, modulate, form>
+// (inst_joint_interp_forward.hip)
+int launch_joint_interp_forward_instance(int n_gauss, bool assembias, bool modulate, int form,
+                                         int device, dim3 grid, int lds, hipStream_t stream,
+                                         hipEvent_t k0, hipEvent_t k1,
+                                         const tc::JointInterpForwardArgs& ja);
 int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
                         hipEvent_t k0, hipEvent_t k1, const tc::VjpArgs& va);
 int launch_vjp_joint_instance(int device, dim3 grid, int lds, hipStream_t stream, hipEvent_t k0,

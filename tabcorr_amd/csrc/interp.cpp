@@ -969,36 +969,45 @@ size_t interp_grad_lds(const tc_interp* it, bool chi2, int n_params) {
              : tc::grad_interp_cross_lds_bytes(t0->n_r, it->n_dim, chi2, n_params);
 }
 
-int build_grad_walk(tc_interp* it) {
-  if (it->grad_walk.built) return TC_OK;
+// The walk (class_begin, node) and, with_matrices, the tables' gradient matrices in its order: a
+// joint's forward calls take the walk alone and build no gradient matrix (grad_call.h).
+int build_grad_walk(tc_interp* it, bool with_matrices) {
+  if (it->grad_walk.built && (!with_matrices || it->grad_walk.matrices != nullptr)) return TC_OK;
   const int n_classes = (int)it->class_table.size();
   std::vector<int32_t> class_begin(1, 0), node;
   std::vector<void*> matrices;
   for (int v = 0; v < n_classes; ++v) {
     for (int k = 0; k < it->n_tables; ++k) {
       if (it->table_class[k] != v) continue;
-      const int status = build_grad_table(it->tables[k]);
-      if (status != TC_OK) return status;
-      matrices.push_back(it->tables[k]->grad.d_matrix);
+      if (with_matrices) {
+        const int status = build_grad_table(it->tables[k]);
+        if (status != TC_OK) return status;
+        matrices.push_back(it->tables[k]->grad.d_matrix);
+      }
       node.insert(node.end(), it->table_node.begin() + (size_t)k * it->n_dim,
                   it->table_node.begin() + (size_t)(k + 1) * it->n_dim);
     }
-    class_begin.push_back((int32_t)matrices.size());
+    class_begin.push_back((int32_t)(node.size() / it->n_dim));
   }
   // (into locals: a failure half-way leaves nothing behind)
   void* uploaded[3] = {nullptr, nullptr, nullptr};
-  int status = upload(class_begin, &uploaded[0]);
-  if (status == TC_OK) status = upload(node, &uploaded[1]);
-  if (status == TC_OK) status = upload(matrices, &uploaded[2]);
+  int status = TC_OK;
+  if (!it->grad_walk.built) {
+    status = upload(class_begin, &uploaded[0]);
+    if (status == TC_OK) status = upload(node, &uploaded[1]);
+  }
+  if (status == TC_OK && with_matrices) status = upload(matrices, &uploaded[2]);
   if (status != TC_OK) {
     for (void* p : uploaded)
       if (p) (void)hipFree(p);
     return status;
   }
-  it->grad_walk.class_begin = uploaded[0];
-  it->grad_walk.node = uploaded[1];
-  it->grad_walk.matrices = uploaded[2];
-  it->grad_walk.built = true;
+  if (!it->grad_walk.built) {
+    it->grad_walk.class_begin = uploaded[0];
+    it->grad_walk.node = uploaded[1];
+    it->grad_walk.built = true;
+  }
+  if (with_matrices) it->grad_walk.matrices = uploaded[2];
   return TC_OK;
 }
 
@@ -1093,14 +1102,15 @@ InterpParts interp_parts(const tc_interp* it) {
   return parts;
 }
 
-int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpArgs* out) {
+int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpArgs* out,
+                     bool with_matrices) {
   tc_table* t0 = it->tables[0];
   int status = TC_OK;
   for (tc_table* t : it->tables)
     if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
   const tc_interp::SinglePointers* pointers = nullptr;
   status = class_pointers(it, request.n_gauss, &pointers);
-  if (status == TC_OK) status = build_grad_walk(it);
+  if (status == TC_OK) status = build_grad_walk(it, with_matrices);
   if (status != TC_OK) return status;
   const int n_dim = it->n_dim;
   tc::GradInterpArgs& ga = *out;
@@ -1135,6 +1145,17 @@ hipStream_t interp_grad_stream(tc_interp* it, GradLane lane) {
   it->cur = next_lane(lane == GradLane::kPinned, it->tables[0]->tuning.pipeline != 0, it->n_lanes,
                       &it->device_calls);
   return it->lanes[it->cur].stream;
+}
+
+InterpForwardParts interp_forward_parts(tc_interp* it) {
+  return {&it->h_in, &it->h_out, &it->tickets, &it->theta, &it->x, &it->out_ngal, it->stream,
+          it->n_lanes};
+}
+
+InterpForwardLane interp_forward_lane(tc_interp* it) {
+  (void)interp_grad_stream(it, GradLane::kNext);
+  tc_interp::Lane& lane = it->lanes[it->cur];
+  return {lane.stream, &lane.stage_in, &lane.stage_out};
 }
 
 }  // namespace host

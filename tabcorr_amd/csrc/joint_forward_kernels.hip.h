@@ -29,6 +29,40 @@
 
 namespace tc {
 
+// The end of step 3, behind the barrier that follows the results tile (N, 65) -- shared with
+// joint_interp_forward_kernel: tile_write_xi of the workgroup's valid draws, or (chi2 != NULL)
+// chi2 = delta^T P delta for the lane's draw (as predict_fused_kernel) against `operands` in
+// LDS, data (N) then the precision matrix (N, N): wave w sums the rows i = w, w + 8, ... into
+// red[w], wave 0 adds the waves' sums in wave order.
+__device__ __forceinline__ void joint_forward_results(
+    const double (*tile)[kLanes + 1], const double* operands,
+    double (*red)[kLanes], int n_total, int64_t col, int64_t n_draws, double* xi, double* chi2) {
+  constexpr int W = kJointForwardWaves, DL = kJointForwardDraws;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t n_valid = n_draws - col < DL ? n_draws - col : DL;
+  if (chi2 != nullptr) {
+    const double* data = operands;
+    const double* matrix = operands + n_total;
+    double part = 0.0;
+    for (int i = wave; i < n_total; i += W) {
+      double inner = 0.0;
+      for (int j = 0; j < n_total; ++j)
+        inner = fma(matrix[i * n_total + j], tile[j][lane] - data[j], inner);
+      part = fma(tile[i][lane] - data[i], inner, part);
+    }
+    red[wave][lane] = part;
+    __syncthreads();
+    if (wave == 0 && lane < n_valid) {
+      double total = 0.0;
+      for (int w = 0; w < W; ++w) total += red[w][lane];
+      chi2[col + lane] = total;
+    }
+    return;
+  }
+  tile_write_xi(&tile[0][0], n_total, DL, n_valid, xi + col * (int64_t)n_total, n_total, 0);
+}
+
 template <int NGAUSS, bool ASSEMBIAS, bool MODULATE>
 __global__ __launch_bounds__(64 * kJointForwardWaves) void joint_forward_kernel(
     const JointForwardArgs a) {
@@ -168,28 +202,7 @@ __global__ __launch_bounds__(64 * kJointForwardWaves) void joint_forward_kernel(
     }
   }
   __syncthreads();
-  const int64_t n_valid = a.n_draws - col < DL ? a.n_draws - col : DL;
-  if (a.chi2 != nullptr) {
-    // chi2 = delta^T P delta for the lane's draw (as predict_fused_kernel)
-    const double* data = table;
-    const double* matrix = table + n_total;
-    double part = 0.0;
-    for (int i = wave; i < n_total; i += W) {
-      double inner = 0.0;
-      for (int j = 0; j < n_total; ++j)
-        inner = fma(matrix[i * n_total + j], tile[j][lane] - data[j], inner);
-      part = fma(tile[i][lane] - data[i], inner, part);
-    }
-    red[0][wave][lane] = part;
-    __syncthreads();
-    if (wave == 0 && lane < n_valid) {
-      double total = 0.0;
-      for (int w = 0; w < W; ++w) total += red[0][w][lane];
-      a.chi2[col + lane] = total;
-    }
-    return;
-  }
-  tile_write_xi(&tile[0][0], n_total, DL, n_valid, a.xi + col * (int64_t)n_total, n_total, 0);
+  joint_forward_results(tile, table, red[0], n_total, col, a.n_draws, a.xi, a.chi2);
 }
 
 }  // namespace tc

@@ -6,6 +6,9 @@
 // the grid, the walk, the classes' quadrature, the lanes, the staging buffers and the kernel timer
 // are member 0's (as InterpGrad takes them, interp.cpp), the matrices every member's own tables'
 // (launch.hip: build_grad_table), matched to member 0's walk by grid node.
+// The forward entries -- the concatenated prediction or chi2 alone -- take ONE launch of
+// joint_interp_forward_kernel (joint_interp_forward_kernels.hip.h) on the mode-auto members' own
+// forward unit layouts, and the forward call path of the tables (predict_call.h) through member 0.
 #include "internal.h"
 
 using namespace tc::host;
@@ -23,6 +26,8 @@ struct tc_joint_interp {
   // per member: the list index of its table at every position of member 0's walk
   std::vector<std::vector<int32_t>> order;
   std::vector<void*> d_matrices;          // per member (K) device pointers, at the first call
+  // ... of the forward kernel: a mode-auto member's unit layouts, at the first forward call
+  std::vector<void*> d_forward_matrices;
   Chi2Operands chi2;                      // data (N), then the precision matrix (N, N)
 };
 
@@ -146,6 +151,304 @@ GradRequest joint_interp_request(const tc_joint_interp* joint, const double* the
   return request;
 }
 
+// ---- forward calls (joint_interp_forward_kernels.hip.h; predict_call.h) -------------------------
+
+// What joint_interp_forward_kernel does not serve, from plain numbers
+// (tc_debug_joint_interp_forward_fit asks with them too): a mode-auto member beyond the
+// one-launch unit layout -- one r tile, 248 bins --, a workgroup beyond the LDS of a CU.  *form: the
+// joint's; *lds_bytes: the workgroup's LDS, where the members are served.
+int joint_interp_forward_fit(int n_bins, int n_members, const int* mode, const int* n_r, int n_dim,
+                             const int* n_axis, int* form, int64_t* lds_bytes) {
+  int total = 0, weight_rows = 0;
+  for (int m = 0; m < n_members; ++m) {
+    if (mode[m] == TC_MODE_AUTO && n_r[m] > 4 * tc::kQuadMaxU)
+      return fail(TC_ERR_UNSUPPORTED,
+                  "joint interpolator forward calls: member %d (mode auto) has %d correlation "
+                  "function bins, more than the one r tile of %d that the one-launch form serves",
+                  m, n_r[m], 4 * tc::kQuadMaxU);
+    if (mode[m] == TC_MODE_AUTO && n_bins > tc::kJointInterpForwardAutoBins)
+      return fail(TC_ERR_UNSUPPORTED,
+                  "joint interpolator forward calls: member %d (mode auto) has %d bins, more "
+                  "than the %d whose unit layout the one-launch form serves",
+                  m, n_bins, tc::kJointInterpForwardAutoBins);
+    total += n_r[m];
+  }
+  for (int d = 0; d < n_dim; ++d) weight_rows += n_axis[d];
+  const int chosen = tc::joint_interp_form(mode, n_members);
+  const size_t lds = tc::joint_interp_forward_lds_bytes(chosen, n_bins, total, weight_rows,
+                                                        tc::kJointForwardWaves);
+  if (form != nullptr) *form = chosen;
+  if (lds_bytes != nullptr) *lds_bytes = (int64_t)lds;
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "joint interpolator forward calls: members of %d bins and %d correlation "
+                "function bins in all over a grid of %d nodes along its axes need %zu bytes of "
+                "LDS per workgroup, beyond the %d there are",
+                n_bins, total, weight_rows, lds, kMaxLdsBytes);
+  return TC_OK;
+}
+
+// The arguments of a forward entry point, the NULL handle first; then what the kernel refuses.
+int check_joint_interp_forward(const tc_joint_interp* joint, const PredictRequest& request) {
+  TC_CHECK(joint != nullptr, "joint handle is NULL");
+  const unsigned flags = request.flags;
+  if (flags & TC_FLAG_SEPARATE_GAL_TYPE)
+    return fail(TC_ERR_UNSUPPORTED, "joint interpolator forward calls are implemented for the "
+                                    "total prediction only (not separate_gal_type)");
+  if (flags & TC_FLAG_LEAUTHAUD11)
+    return fail(TC_ERR_UNSUPPORTED, "joint interpolator forward calls are implemented for the "
+                                    "Zheng07 family only");
+  const unsigned unserved =
+      flags & ~(unsigned)(TC_FLAG_MODULATE_WITH_CENOCC | TC_FLAG_ASSEMBIAS);
+  if (unserved != 0)
+    return fail(TC_ERR_UNSUPPORTED, "joint interpolator forward calls: unknown flags 0x%x",
+                unserved);
+  const tc_table* t0 = table_of(joint, 0);
+  int status = check_predict_args(t0, request.theta, request.n_theta, request.n_draws,
+                                  request.n_gauss, flags);
+  if (status != TC_OK) return status;
+  const InterpParts first = interp_parts(joint->members[0]);
+  int n_axis[tc::kGradMaxDim];
+  for (int d = 0; d < joint->n_dim; ++d) n_axis[d] = (int)(*first.xp)[d].size();
+  status = joint_interp_forward_fit(t0->n_bins, (int)joint->members.size(), joint->mode.data(),
+                                    joint->n_r.data(), joint->n_dim, n_axis, nullptr, nullptr);
+  if (status != TC_OK) return status;
+  for (size_t m = 0; m < joint->members.size(); ++m) {
+    if (joint->mode[m] != TC_MODE_AUTO) continue;
+    for (const tc_table* t : joint->tables[m]) {
+      const tc::QuadLayout& layout = t->quad_total.layout;
+      if (!(t->quad && t->quad_total.d_table != nullptr && t->quad_tiling.n_rtiles == 1 &&
+            layout.comps.size() == 1 && layout.comps[0].triangular))
+        return fail(TC_ERR_UNSUPPORTED,
+                    "joint interpolator forward calls: a table of member %d (mode auto, %d bins) "
+                    "does not have the unit layout of the one-launch form", (int)m, t->n_bins);
+    }
+  }
+  return TC_OK;
+}
+
+// The argument block but for the draws and the outputs: the resident kernels of every table
+// stop, member 0's walk and classes are built (interp_grad_args, without the gradient matrices:
+// only a mode-cross member's (bins, r) matrices are built here), every member's matrices are
+// matched to the walk, the passes are numbered.
+int joint_interp_forward_args(tc_joint_interp* joint, int n_theta, int n_gauss, unsigned flags,
+                              tc::JointInterpForwardArgs* out) {
+  tc_table* t0 = table_of(joint, 0);
+  GradRequest walk{};
+  walk.n_params = joint_params(flags);
+  walk.n_gauss = n_gauss;
+  walk.flags = flags;
+  tc::GradInterpArgs ia{};
+  // (the walk and the classes alone: no table's gradient matrix is built for a forward call)
+  int status = interp_grad_args(joint->members[0], walk, &ia, /*with_matrices=*/false);
+  if (status != TC_OK) return status;
+  tc::JointInterpForwardArgs ja{};
+  ja.n_theta = n_theta;
+  ja.n_dim = joint->n_dim;
+  ja.n_bins = t0->n_bins;
+  ja.n_central = t0->plan.n_central;
+  ja.n_gauss = n_gauss;
+  ja.dens_rows = (t0->n_bins + 3) / 4 * 4;
+  ja.n_r = joint->n_r_total;
+  ja.split = 0.5;
+  ja.math_table = (const double*)t0->d_math_table;
+  for (int d = 0; d < joint->n_dim; ++d) {
+    ja.n_axis[d] = ia.n_axis[d];
+    ja.axis_offset[d] = ia.axis_offset[d];
+    ja.a_offset[d] = ia.a_offset[d];
+    ja.weight_row[d] = ja.n_weight_rows;
+    ja.n_weight_rows += ia.n_axis[d];
+  }
+  ja.xp = ia.xp;
+  ja.a = ia.a;
+  ja.n_classes = ia.n_classes;
+  ja.class_begin = ia.class_begin;
+  ja.walk_node = ia.walk_node;
+  ja.class_log_m = ia.class_log_m;
+  ja.class_m = ia.class_m;
+  ja.class_weight = ia.class_weight;
+  ja.class_n_h = ia.class_n_h;
+  ja.class_percentile = ia.class_percentile;
+  ja.n_members = (int)joint->members.size();
+  const int parts = tc::joint_forward_parts(tc::kJointForwardWaves);
+  bool first_auto = true;
+  for (int m = 0; m < ja.n_members; ++m) {
+    const std::vector<tc_table*>& tables = joint->tables[m];
+    const bool is_auto = joint->mode[m] == TC_MODE_AUTO;
+    for (tc_table* t : tables) {
+      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+      if (!is_auto && (status = build_grad_table(t)) != TC_OK) return status;
+    }
+    if (joint->d_forward_matrices[m] == nullptr) {
+      std::vector<void*> matrices;
+      for (int32_t k : joint->order[m])
+        matrices.push_back(is_auto ? tables[k]->quad_total.d_table : tables[k]->grad.d_matrix);
+      if ((status = upload(matrices, &joint->d_forward_matrices[m])) != TC_OK) return status;
+    }
+    ja.mode[m] = joint->mode[m];
+    ja.n_rows[m] = joint->n_r[m];
+    ja.r_offset[m] = joint->r_offset[m];
+    ja.matrices[m] = (const void* const*)joint->d_forward_matrices[m];
+    ja.job_begin[m + 1] = ja.job_begin[m];
+    if (!is_auto) continue;
+    const tc_table* t = tables[0];
+    const tc::QuadComp& comp = t->quad_total.layout.comps[0];
+    const int n_u = t->quad_tiling.n_u;
+    ja.n_u[m] = n_u;
+    ja.table_bytes[m] =
+        (uint32_t)((size_t)t->quad_total.layout.n_units * (size_t)((n_u + 1) / 2) * 1024);
+    ja.job_begin[m + 1] += (n_u + 1) / 2 * 2 * parts;
+    if (first_auto) {
+      tc::triangle_parts(comp.n_rb, parts, ja.part_rb0, ja.part_cb0, ja.part_count);
+      ja.n_cb = comp.n_cb;
+      ja.i_row0 = comp.i_bin0;
+      ja.j_row0 = comp.j_bin0;
+      ja.unit_base = (int)comp.unit_base;
+      first_auto = false;
+    }
+  }
+  *out = ja;
+  return TC_OK;
+}
+
+// One launch per slab of the draws of `r` (device pointers) on `stream`, timed and reported
+// through member 0's first table.
+int joint_interp_forward_launches(tc_joint_interp* joint, const tc::JointInterpForwardArgs& shape,
+                                  const PredictRequest& r, hipStream_t stream) {
+  Range range("joint interpolator forward (one launch)");
+  tc_table* t0 = table_of(joint, 0);
+  const int lds = (int)tc::joint_interp_forward_lds_bytes(
+      joint->form, shape.n_bins, shape.n_r, shape.n_weight_rows, tc::kJointForwardWaves);
+  return for_each_slab(r.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
+    const PredictRequest slab = r.chunk(begin, n);
+    tc::JointInterpForwardArgs ja = shape;
+    ja.theta = slab.theta;
+    ja.x = slab.x;
+    ja.n_draws = n;
+    ja.ngal = slab.ngal;
+    ja.xi = r.likelihood ? nullptr : slab.second;
+    ja.chi2_data = r.likelihood ? joint->chi2.device() : nullptr;
+    ja.chi2 = r.likelihood ? slab.second : nullptr;
+    const dim3 grid((unsigned)((n + tc::kJointForwardDraws - 1) / tc::kJointForwardDraws));
+    hipEvent_t k0 = nullptr, k1 = nullptr;
+    int status = next_kernel_events(t0, &k0, &k1);
+    if (status != TC_OK) return status;
+    status = launch_joint_interp_forward_instance(
+        shape.n_gauss, (r.flags & TC_FLAG_ASSEMBIAS) != 0,
+        (r.flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0, joint->form, joint->device, grid, lds,
+        stream, k0, k1, ja);
+    if (status != TC_OK) return status;
+    t0->last_workgroups = (int)grid.x;
+    t0->last_waves = tc::kJointForwardWaves;
+    t0->last_splits = 0;
+    t0->last_lds = lds;
+    return TC_OK;
+  });
+}
+
+// A joint of interpolators as forward_chunked and forward_zero_copy see it (joint.cpp:
+// JointForward): it works through member 0 -- the staging areas, the tickets and the lanes are
+// that interpolator's.
+struct JointInterpForward {
+  static constexpr bool kThreadedCopyOut = true;
+  // member 0's staging areas under the names the forward path reads
+  struct Staging {
+    PinnedBuffer& h_in;
+    PinnedBuffer& h_out;
+    Tickets& tickets;
+    hipStream_t stream;
+  };
+  tc_joint_interp* joint;
+  const tc::JointInterpForwardArgs* shape;
+  Staging areas;
+  const Staging* handle() const { return &areas; }
+  // (one form: a draw's result does not depend on the chunks)
+  Call hints(const PredictRequest&, const tc::SyncChunkPlan&) const { return Call(); }
+  std::vector<hipEvent_t>* chunk_events() const { return nullptr; }   // (never staggered)
+  // A chunk on member 0's next lane: draws up, the launch, results down, the ticket.
+  int enqueue(const PredictRequest& part, const Call&, hipEvent_t, hipEvent_t,
+              int64_t* ticket) const {
+    const InterpForwardLane lane = interp_forward_lane(joint->members[0]);
+    int status = lane.stage_in->reserve(part.in_bytes(), lane.stream);
+    if (status == TC_OK) status = lane.stage_out->reserve(part.out_bytes(), lane.stream);
+    if (status != TC_OK) return status;
+    // (the staged draws lie side by side, [theta | x], and so do the results, [ngal | second]:
+    // one copy command each way)
+    double* in = (double*)lane.stage_in->ptr;
+    double* result = (double*)lane.stage_out->ptr;
+    TC_HIP(hipMemcpyAsync(in, part.theta, part.in_bytes(), hipMemcpyHostToDevice, lane.stream));
+    status = joint_interp_forward_launches(
+        joint, *shape,
+        part.on(in, in + part.n_draws * part.n_theta, result, result + part.ngal_count()),
+        lane.stream);
+    if (status != TC_OK) return status;
+    TC_HIP(hipMemcpyAsync(part.ngal, result, part.out_bytes(), hipMemcpyDeviceToHost,
+                          lane.stream));
+    return areas.tickets.issue(lane.stream, ticket);
+  }
+  int synchronize() const { return tc_interp_synchronize(joint->members[0]); }
+  // (lane 0 of member 0)
+  int run(const PredictRequest& s) const {
+    return joint_interp_forward_launches(joint, *shape, s, areas.stream);
+  }
+};
+
+// The request of a forward entry point, in the order of the C arguments.
+PredictRequest joint_interp_forward_request(const tc_joint_interp* joint, const double* theta,
+                                            int n_theta, const double* x, int64_t n_draws,
+                                            int n_gauss, unsigned flags, double* ngal,
+                                            double* second, bool likelihood) {
+  return PredictRequest{n_theta, joint ? joint->n_dim : 0, n_gauss, flags, n_draws,
+                        joint ? joint->n_r_total : 0, 1, theta, x, ngal, second, likelihood};
+}
+
+// Every forward entry point: the checks, the likelihood's operands, then the launches on device
+// pointers (member 0's next lane) or the forward path of host arrays.
+int joint_interp_forward_entry(tc_joint_interp* joint, bool host, const PredictRequest& request,
+                               const Chi2Host* operands) {
+  int status = check_joint_interp_forward(joint, request);
+  if (status != TC_OK) return status;
+  if (request.n_draws == 0) return TC_OK;
+  TC_CHECK(request.x && request.ngal && request.second, "NULL pointer");
+  TC_CHECK(operands == nullptr || (operands->data && operands->precision), "NULL pointer");
+  tc_interp* first = joint->members[0];
+  const InterpForwardParts parts = interp_forward_parts(first);
+  TC_HIP(hipSetDevice(joint->device));
+  if (operands != nullptr) {
+    status = joint->chi2.upload(joint->n_r_total, operands->data, operands->precision,
+                                parts.stream, [&] { return tc_interp_synchronize(first); });
+    if (status != TC_OK) return status;
+  }
+  tc::JointInterpForwardArgs shape;
+  status = joint_interp_forward_args(joint, request.n_theta, request.n_gauss, request.flags,
+                                     &shape);
+  if (status != TC_OK) return status;
+  if (!host)
+    return joint_interp_forward_launches(joint, shape, request,
+                                         interp_grad_stream(first, GradLane::kNext));
+  const JointInterpForward forward{joint, &shape,
+                                   {*parts.h_in, *parts.h_out, *parts.tickets, parts.stream}};
+  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
+  const tc::SyncChunkPlan plan =
+      plan_forward_chunks(table_of(joint, 0), parts.n_lanes, false, false, request);
+  if (plan.n_chunks > 0) return forward_chunked(forward, request, plan);
+  status = parts.theta->reserve(request.theta_bytes(), parts.stream);
+  if (status == TC_OK) status = parts.x->reserve(request.x_bytes(), parts.stream);
+  if (status == TC_OK) status = parts.out->reserve(request.out_bytes(), parts.stream);
+  if (status != TC_OK) return status;
+  TC_HIP(hipMemcpyAsync(parts.theta->ptr, request.theta, request.theta_bytes(),
+                        hipMemcpyHostToDevice, parts.stream));
+  TC_HIP(hipMemcpyAsync(parts.x->ptr, request.x, request.x_bytes(), hipMemcpyHostToDevice,
+                        parts.stream));
+  double* d_ngal = (double*)parts.out->ptr;
+  double* d_second = d_ngal + request.ngal_count();
+  status = forward.run(request.on((const double*)parts.theta->ptr, (const double*)parts.x->ptr,
+                                  d_ngal, d_second));
+  if (status != TC_OK) return status;
+  return copy_out(parts.h_out, request.ngal, request.ngal_count(), d_ngal, request.second,
+                  request.second_count(), d_second, parts.stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -169,6 +472,7 @@ int tc_joint_interp_create(tc_interp* const* members, int n_members, tc_joint_in
   out->n_tables = n_tables;
   out->members.assign(members, members + n_members);
   out->d_matrices.assign(n_members, nullptr);
+  out->d_forward_matrices.assign(n_members, nullptr);
   for (int m = 0; m < n_members; ++m) {
     const InterpParts parts = interp_parts(members[m]);
     TC_CHECK(parts.device == first.device, "member %d is on device %d, member 0 on device %d", m,
@@ -216,6 +520,8 @@ int tc_joint_interp_destroy(tc_joint_interp* joint) {
   (void)hipSetDevice(joint->device);
   joint->chi2.buffer.release();
   for (void* p : joint->d_matrices)
+    if (p) (void)hipFree(p);
+  for (void* p : joint->d_forward_matrices)
     if (p) (void)hipFree(p);
   delete joint;
   return TC_OK;
@@ -282,6 +588,80 @@ int tc_joint_interp_chi2_grad_batch(tc_joint_interp* joint, const double* theta,
                     joint_interp_request(joint, theta, x, n_draws, n_gauss, flags, ngal, chi2,
                                          dngal, dchi2, fisher),
                     n_theta, &operands, false);
+}
+
+int tc_joint_interp_predict_batch_device(tc_joint_interp* joint, const double* theta_device,
+                                         int n_theta, const double* x_device, int64_t n_draws,
+                                         int n_gauss, unsigned flags, double* ngal_device,
+                                         double* xi_device) {
+  return joint_interp_forward_entry(
+      joint, false,
+      joint_interp_forward_request(joint, theta_device, n_theta, x_device, n_draws, n_gauss, flags,
+                                   ngal_device, xi_device, false),
+      nullptr);
+}
+
+int tc_joint_interp_predict_batch(tc_joint_interp* joint, const double* theta, int n_theta,
+                                  const double* x, int64_t n_draws, int n_gauss, unsigned flags,
+                                  double* ngal, double* xi) {
+  return joint_interp_forward_entry(
+      joint, true,
+      joint_interp_forward_request(joint, theta, n_theta, x, n_draws, n_gauss, flags, ngal, xi,
+                                   false),
+      nullptr);
+}
+
+int tc_joint_interp_chi2_batch_device(tc_joint_interp* joint, const double* theta_device,
+                                      int n_theta, const double* x_device, int64_t n_draws,
+                                      int n_gauss, unsigned flags, const double* data,
+                                      const double* precision, double* ngal_device,
+                                      double* chi2_device) {
+  const Chi2Host operands{data, precision};
+  return joint_interp_forward_entry(
+      joint, false,
+      joint_interp_forward_request(joint, theta_device, n_theta, x_device, n_draws, n_gauss, flags,
+                                   ngal_device, chi2_device, true),
+      &operands);
+}
+
+int tc_joint_interp_chi2_batch(tc_joint_interp* joint, const double* theta, int n_theta,
+                               const double* x, int64_t n_draws, int n_gauss, unsigned flags,
+                               const double* data, const double* precision, double* ngal,
+                               double* chi2) {
+  const Chi2Host operands{data, precision};
+  return joint_interp_forward_entry(
+      joint, true,
+      joint_interp_forward_request(joint, theta, n_theta, x, n_draws, n_gauss, flags, ngal, chi2,
+                                   true),
+      &operands);
+}
+
+int tc_debug_joint_interp_forward_lds_bytes(int form, int n_bins, int n_r_total,
+                                            int n_weight_rows, int waves, int64_t* bytes) {
+  TC_CHECK(bytes != nullptr, "bytes is NULL");
+  TC_CHECK(form == tc::kJointInterpRows || form == tc::kJointInterpSlabs,
+           "form must be %d (rows) or %d (slabs)", tc::kJointInterpRows, tc::kJointInterpSlabs);
+  TC_CHECK(n_bins >= 1 && n_r_total >= 1 && n_weight_rows >= 4 && waves >= 2 && waves % 2 == 0 &&
+               waves <= 2 * tc::kFusedMaxParts,
+           "invalid shape");
+  *bytes = (int64_t)tc::joint_interp_forward_lds_bytes(form, n_bins, n_r_total, n_weight_rows,
+                                                       waves);
+  return TC_OK;
+}
+
+int tc_debug_joint_interp_forward_fit(int n_bins, int n_members, const int* mode, const int* n_r,
+                                      int n_dim, const int* n_axis, int* form,
+                                      int64_t* lds_bytes) {
+  TC_CHECK(mode != nullptr && n_r != nullptr && n_axis != nullptr, "NULL pointer");
+  TC_CHECK(n_bins >= 1 && n_members >= 1 && n_members <= tc::kJointInterpMaxMembers &&
+               n_dim >= 1 && n_dim <= tc::kGradMaxDim,
+           "invalid shape");
+  for (int m = 0; m < n_members; ++m)
+    TC_CHECK((mode[m] == TC_MODE_AUTO || mode[m] == TC_MODE_CROSS) && n_r[m] >= 1,
+             "invalid member %d", m);
+  for (int d = 0; d < n_dim; ++d)
+    TC_CHECK(n_axis[d] >= 4 && n_axis[d] <= tc::kGradMaxAxis, "invalid axis %d", d);
+  return joint_interp_forward_fit(n_bins, n_members, mode, n_r, n_dim, n_axis, form, lds_bytes);
 }
 
 int tc_debug_joint_interp_lds_bytes(int form, int n_bins, int n_central, int n_r_total,

@@ -14,6 +14,7 @@
 
 #include "../../include/tabcorr_amd.h"
 #include "grad.h"
+#include "joint.h"
 
 namespace tc {
 
@@ -67,6 +68,104 @@ constexpr size_t joint_interp_lds_bytes(int form, int n_bins, int n_central, int
              ? joint_interp_rows_lds_bytes(n_bins, n_central, n_r_total, n_r_cross, n_dim,
                                            n_params)
              : joint_interp_slabs_lds_bytes(n_r_total, n_dim, n_params);
+}
+
+// ---- the forward form (joint_interp_forward_kernels.hip.h: joint_interp_forward_kernel) ----------
+// (ngal, xi) or (ngal, chi2) of a batch of draws (theta, x) without any derivative, one launch
+// per batch in the geometry of joint_forward_kernel (joint.h): kJointForwardDraws draws per
+// workgroup of kJointForwardWaves waves.  The classes in member 0's walk order, the occupations
+// of a class once for all members; a mode-auto member's table at a grid node in its own forward
+// unit layout on the matrix cores, a mode-cross member's by one fma chain per (row, draw).
+constexpr int kJointInterpForwardSlab = 64;   // slab form: bins whose densities one LDS slab holds
+// most bins of a mode-auto member: beyond them a table has no one-launch unit layout (table.cpp)
+constexpr int kJointInterpForwardAutoBins = 248;
+static_assert(kJointInterpForwardSlab % kJointForwardWaves == 0,
+              "a wave sums the same bins of a class in both forms: ngal has one set of bits");
+
+struct JointInterpForwardArgs {
+  const double* theta;       // (n_draws, n_theta)
+  const double* x;           // (n_draws, n_dim)
+  int n_theta;
+  int n_dim;
+  int n_bins;
+  int n_central;
+  int n_gauss;
+  int dens_rows;             // rows form: rows of the LDS density array, whole blocks of four
+  int n_r;                   // N, the concatenated rows
+  int64_t n_draws;
+  double split;
+  const double* math_table;
+  // the grid, as in GradInterpArgs; weight_row[d]: the first of axis d's n_axis[d] rows among the
+  // n_weight_rows = sum_d n_axis[d] rows of spline weights in LDS
+  int n_axis[kGradMaxDim];
+  int axis_offset[kGradMaxDim];
+  int a_offset[kGradMaxDim];
+  int weight_row[kGradMaxDim];
+  int n_weight_rows;
+  const double* xp;
+  const double* a;
+  // member 0's walk and the classes' quadrature constants and n_h, as in GradInterpArgs
+  int n_classes;
+  const int32_t* class_begin;
+  const int32_t* walk_node;
+  const double* const* class_log_m;
+  const double* const* class_m;
+  const double* const* class_weight;
+  const double* const* class_n_h;
+  const double* const* class_percentile;
+  double* ngal;              // (n_draws)
+  double* xi;                // (n_draws, N); NULL: the likelihood form
+  const double* chi2_data;   // data (N), then the precision matrix (N, N)
+  double* chi2;              // (n_draws)
+  int n_members;
+  int mode[kJointInterpMaxMembers];
+  int n_rows[kJointInterpMaxMembers];
+  int r_offset[kJointInterpMaxMembers];
+  // (K) per member, at every position of member 0's walk: mode auto the table's unit layout of
+  // the whole triangle (QuadTable::d_table, table_bytes long, n_u sub-tiles of four r values),
+  // mode cross (n_bins in library order, n_r) doubles
+  const void* const* matrices[kJointInterpMaxMembers];
+  uint32_t table_bytes[kJointInterpMaxMembers];
+  int n_u[kJointInterpMaxMembers];
+  int job_begin[kJointInterpMaxMembers + 1];   // first pass of every member (mode cross: none)
+  // the parts of the triangle and the component's place, as in JointForwardArgs
+  int part_rb0[kFusedMaxParts];
+  int part_cb0[kFusedMaxParts];
+  int part_count[kFusedMaxParts];
+  int n_cb;
+  int i_row0, j_row0;
+  int unit_base;
+};
+
+// LDS of the rows form in bytes: the regions of joint_forward_kernel (joint.h:
+// joint_forward_lds_bytes) -- the passes' per-part slabs of `sums` ARE the accumulators of the
+// walk, sums[part][row][draw] += scale x F, reduced once at the end --, then the spline weights of
+// the 64 draws (n_weight_rows, 64) and the class's 1 / ngal and 1 / ngal^2 (2, 64).
+constexpr size_t joint_interp_forward_rows_lds_bytes(int n_bins, int n_r_total, int n_weight_rows,
+                                                     int waves) {
+  return joint_forward_lds_bytes(n_bins, n_r_total, waves) +
+         8 * ((size_t)n_weight_rows + 2) * kLanes;
+}
+// ... of the slab form, in the order of the regions:
+//   B  one slab of densities (kJointInterpForwardSlab, 64), later the results tile (N, 65);
+//   A  the math table, later the likelihood's data and precision matrix, N (N + 1);
+//   the waves' sums of the number density and of chi2, (2, waves, 64);
+//   the products of the class in flight and the accumulators, (2, N, 64);
+//   the spline weights (n_weight_rows, 64) and the class's 1 / ngal and 1 / ngal^2 (2, 64).
+constexpr size_t joint_interp_forward_slabs_lds_bytes(int n_r_total, int n_weight_rows,
+                                                      int waves) {
+  const size_t n = (size_t)n_r_total;
+  return 8 * (joint_forward_max((size_t)kJointInterpForwardSlab * kLanes,
+                                (n * (kLanes + 1) + 1) / 2 * 2) +
+              joint_forward_max((size_t)kMathTableDoubles, n * (n + 1)) +
+              2 * (size_t)waves * kLanes + 2 * n * kLanes +
+              ((size_t)n_weight_rows + 2) * kLanes);
+}
+constexpr size_t joint_interp_forward_lds_bytes(int form, int n_bins, int n_r_total,
+                                                int n_weight_rows, int waves) {
+  return form == kJointInterpRows
+             ? joint_interp_forward_rows_lds_bytes(n_bins, n_r_total, n_weight_rows, waves)
+             : joint_interp_forward_slabs_lds_bytes(n_r_total, n_weight_rows, waves);
 }
 
 // ---- the members' tables, matched by grid node ---------------------------------------------------

@@ -539,7 +539,12 @@ class JointInterpolator:
     ``assembias=True``.  One kernel launch per call (``tc_joint_interp_*``,
     ``include/tabcorr_amd.h``): the occupations of every class of halo tables
     once for all members, and chi2, its gradient and the Fisher matrix over
-    ``(theta, x)`` against the full ``(N, N)`` precision matrix.
+    ``(theta, x)`` against the full ``(N, N)`` precision matrix.  The forward
+    calls `predict_batch` and `chi2_batch` -- what an ensemble sampler over
+    ``(theta, x)`` asks per step -- take a launch of their own kind, without
+    any derivative: a draw's results there depend on the draw alone, and
+    permuting the members or the list of a member other than member 0 returns
+    the same bits.
     """
 
     def __init__(self, interpolators):
@@ -629,6 +634,60 @@ class JointInterpolator:
             want_fisher)
 
     # -- batched calls --------------------------------------------------------
+
+    def _forward_call(self, form, theta, x, n_gauss_prim, extrapolate,
+                      modulate_with_cenocc, assembias, family, operands=()):
+        """The forward entry (``_lib.FORWARD_ENTRIES['joint_interp', form,
+        'host']``) for ``(theta, x)`` and operands that are checked here,
+        before any device is touched: the results on the joint axis of
+        ``n_r_total`` entries."""
+        theta, x = self._inputs(theta, x, extrapolate, assembias, family)
+        if operands:
+            operands = self._operands(*operands)
+        n_draws = len(theta)
+        shapes = ((n_draws, ), (n_draws, ) if operands else
+                  (n_draws, self.n_r_total))
+        return _forward.call(
+            self.to_device(), 'joint_interp', form,
+            (theta, theta.shape[1], x, n_draws, n_gauss_prim,
+             _flags(False, modulate_with_cenocc, assembias)), shapes, operands)
+
+    def predict_batch(self, theta, x, n_gauss_prim=10, extrapolate=False,
+                      modulate_with_cenocc=False, assembias=False,
+                      family='zheng07'):
+        """`Interpolator.predict_batch` of every member in one launch, without
+        any derivative: the occupations of every class of halo tables once for
+        all members, then every member's contraction at every grid node.
+
+        Returns
+        -------
+        ngal : ``(n_draws, )`` -- the members share their halo tables
+        xis : list, per member ``(n_draws, ) + tpcf_shape``
+
+        ``theta`` is ``(n_draws, 5)``, ``(n_draws, 7)`` with
+        ``assembias=True``; ``x`` is ``(n_draws, D)``.  Raises ``ValueError``
+        for ``x`` outside the grid unless ``extrapolate``,
+        ``NotImplementedError`` for ``family='leauthaud11'`` and for a joint
+        the one-launch kernel does not serve: a mode ``'auto'`` member of more
+        than 20 correlation function bins or more than 248 bins, or rows
+        beyond the kernel's LDS."""
+        ngal, xi = self._forward_call('predict', theta, x, n_gauss_prim,
+                                      extrapolate, modulate_with_cenocc,
+                                      assembias, family)
+        return ngal, self._split(xi, (len(ngal), ))
+
+    def chi2_batch(self, theta, x, data, precision, n_gauss_prim=10,
+                   extrapolate=False, modulate_with_cenocc=False,
+                   assembias=False, family='zheng07'):
+        """``chi2 = (xi - data)^T precision (xi - data)`` of the concatenated
+        data vector for every draw ``(theta, x)``, finished in the launch of
+        `predict_batch` (``xi`` is never stored): ``ngal, chi2``, each
+        ``(n_draws, )`` -- what an ensemble sampler over the model's and the
+        grid's parameters asks per step.  ``data`` and ``precision`` as
+        `chi2_grad_batch` takes them."""
+        return self._forward_call('chi2', theta, x, n_gauss_prim, extrapolate,
+                                  modulate_with_cenocc, assembias, family,
+                                  (data, precision))
 
     def predict_batch_grad(self, theta, x, n_gauss_prim=10, extrapolate=False,
                            modulate_with_cenocc=False, assembias=False,

@@ -13,6 +13,14 @@ repeats each.  Prints one JSON line (profiles/joint_notes.md).
     python tools/joint_interp_bench.py joint         # this tree: the joint's and the members' calls
     python tools/joint_interp_bench.py members DIR   # the members' calls with the package of the
                                                      # checkout DIR (the commit before the joint)
+    python tools/joint_interp_bench.py forward [DIR] # the forward form (profiles/
+                                                     # joint_interp_forward_notes.md):
+                                                     # tc_joint_interp_chi2_batch_device against A,
+                                                     # the joint's chi2_grad call without the Fisher
+                                                     # matrix, and B, the sum of the members' own
+                                                     # tc_interp_chi2_zheng07_batch_device calls;
+                                                     # with the package of a checkout DIR that has
+                                                     # no forward form yet: A and B alone
 """
 import ctypes
 import json
@@ -23,7 +31,7 @@ import numpy as np
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 which = sys.argv[1]
-assert which in ('joint', 'members')
+assert which in ('joint', 'members', 'forward')
 sys.path.insert(0, os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else REPO)
 import tabcorr_amd  # noqa: E402
 from tabcorr_amd import Interpolator, TabCorr, _lib, synthetic  # noqa: E402
@@ -95,14 +103,63 @@ def timed(handle, call, synchronize):
     return out
 
 
+def measure_forward(members, d_theta, d_x, d_ngal, d_chi2, d_dngal, d_dchi2):
+    """B: every member's own forward likelihood; A: the joint's chi2 and gradient, no Fisher
+    matrix; and the joint's forward likelihood where the package has it."""
+    from tabcorr_amd import JointInterpolator
+    result = {}
+    for m, interp in enumerate(members):
+        device = interp.to_device()
+        kept = operands(device.tables[0].n_r)
+
+        def call(device=device, kept=kept):
+            _lib.check(lib.tc_interp_chi2_zheng07_batch_device(
+                device.handle, d_theta, 5, d_x, N, 10, 0, _lib.as_double_p(kept[0]),
+                _lib.as_double_p(kept[1]), d_ngal, d_chi2))
+
+        def sync(device=device):
+            _lib.check(lib.tc_interp_synchronize(device.handle))
+
+        result['B_member_%d_chi2' % m] = timed(device.tables[0].handle, call, sync)
+    joint = JointInterpolator(members)
+    device = joint.to_device()
+    data, precision = operands(joint.n_r_total)
+    handle = members[0].to_device().tables[0].handle
+
+    def sync():
+        _lib.check(lib.tc_joint_interp_synchronize(device.handle))
+
+    def call_grad():
+        _lib.check(lib.tc_joint_interp_chi2_grad_batch_device(
+            device.handle, d_theta, 5, d_x, N, 10, 0, _lib.as_double_p(data),
+            _lib.as_double_p(precision), d_ngal, d_chi2, d_dngal, d_dchi2, None))
+
+    result['A_joint_chi2_grad'] = timed(handle, call_grad, sync)
+    entry = _lib.FORWARD_ENTRIES.get(('joint_interp', 'chi2', 'device'))
+    if entry is not None:
+        forward = getattr(lib, entry)
+
+        def call_forward():
+            _lib.check(forward(device.handle, d_theta, 5, d_x, N, 10, 0, _lib.as_double_p(data),
+                               _lib.as_double_p(precision), d_ngal, d_chi2))
+
+        result['joint_chi2_forward'] = timed(handle, call_forward, sync)
+    return result
+
+
 def measure(members, theta):
     n_dim = len(members[0].keys)
     x = np.ascontiguousarray(np.stack([rng.uniform(xp[0], xp[-1], N) for xp in members[0].xp],
                                       axis=-1))
     n_cols = 5 + n_dim
     d_theta, d_x = upload(theta), upload(x)
-    d_ngal, d_chi2, d_dngal, d_dchi2, d_fisher = (malloc(N), malloc(N), malloc(n_cols * N),
-                                                  malloc(n_cols * N), malloc(n_cols * n_cols * N))
+    d_ngal, d_chi2, d_dngal, d_dchi2 = malloc(N), malloc(N), malloc(n_cols * N), malloc(n_cols * N)
+    if which == 'forward':
+        result = measure_forward(members, d_theta, d_x, d_ngal, d_chi2, d_dngal, d_dchi2)
+        for ptr in (d_theta, d_x, d_ngal, d_chi2, d_dngal, d_dchi2):
+            lib.tc_device_free(ptr)
+        return result
+    d_fisher = malloc(n_cols * n_cols * N)
     result = {}
     for m, interp in enumerate(members):
         device = interp.to_device()
