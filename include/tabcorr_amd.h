@@ -529,6 +529,61 @@ int tc_interp_chi2_grad_assembias_batch_device(tc_interp* interp, const double* 
                                                double* dngal_device, double* dchi2_device,
                                                double* fisher_device);
 
+/* The occupation seam of an interpolator (extension): the interface for ANY occupation model.
+ * The tables of an interpolator fall into n_classes classes of identical halo tables
+ * (interpolator.py:63-70), numbered by first appearance in the list.  tc_interp_info: table_class
+ * holds n_tables entries (the class of every table), class_table n_classes (the first table of
+ * every class); any pointer may be NULL.
+ * occupation: (n_draws, n_classes, n_bins) mean occupations, class v's row in the gal_type row
+ * order of that class's tables; x: (n_draws, n_dim), out of range clamped to the outermost
+ * polynomial as above.  With c_t(x) the spline weight of table t: ngal = sum_t c_t ngal_t and
+ * xi_r = sum_t c_t xi_t,r (ngal (n_draws), xi (n_draws, n_r)).
+ * tc_interp_predict_occupation_vjp_batch: with the cotangents g_ngal (n_draws; NULL = 0) and g_xi
+ * (n_draws, n_r) also g_occupation (n_draws, n_classes, n_bins) = g_ngal dngal/dn + sum_r g_r
+ * dxi_r/dn and g_x (n_draws, n_dim) likewise with respect to x.  g_xi, g_occupation and g_x all
+ * NULL: the forward-only form -- (ngal, xi) alone, the same bits, no adjoint work; some but not
+ * all of them NULL is TC_ERR_INVALID.
+ * tc_interp_chi2_occupation_grad_batch: chi2 (n_draws) of the interpolated prediction against
+ * data (n_r) and precision (n_r, n_r) -- host arrays in both forms, uploaded when they change --
+ * with dchi2_docc (n_draws, n_classes, n_bins), dchi2_dx (n_draws, n_dim) and dngal_dx (n_draws,
+ * n_dim); the three all NULL: the forward-only form, some but not all TC_ERR_INVALID.  The
+ * cotangent 2 P_sym (xi - data) is formed in the launch, which walks the tables twice.
+ * One launch per batch; a draw's results depend on the draw alone, not on the batch, its place in
+ * it or the entry point.  TC_ERR_UNSUPPORTED with a message, the interpolator and its tables
+ * staying usable: a float32 compute dtype, TC_FLAG_SEPARATE_GAL_TYPE, any other flag, and a
+ * workgroup beyond 160 KiB of LDS ("LDS" in the message) -- rows of 128 bytes: 64 n_dim of
+ * spline weights, (2 + n_dim) n_r + 4 of cotangents, results and per-draw sums, and in mode auto
+ * 3 n_bins + 1 + 5 n_r (the class in flight: w, the table's and the class's sum_r g_r U_ri, the
+ * per-wave partial q_r), in mode cross 64 + (1 + n_dim) n_r (one slab of w for any number of
+ * bins, the class's weighted products).
+ * Host arrays run slab-wise on lane 0 of the interpolator; the `_device` forms enqueue on its
+ * next lane and return (tc_interp_synchronize waits). */
+int tc_interp_info(const tc_interp* interp, int* n_tables, int* n_classes, int* table_class,
+                   int* class_table);
+int tc_interp_predict_occupation_vjp_batch(tc_interp* interp, const double* occupation,
+                                           const double* x, int64_t n_draws, unsigned flags,
+                                           const double* g_ngal, const double* g_xi, double* ngal,
+                                           double* xi, double* g_occupation, double* g_x);
+int tc_interp_predict_occupation_vjp_batch_device(tc_interp* interp,
+                                                  const double* occupation_device,
+                                                  const double* x_device, int64_t n_draws,
+                                                  unsigned flags, const double* g_ngal_device,
+                                                  const double* g_xi_device, double* ngal_device,
+                                                  double* xi_device, double* g_occupation_device,
+                                                  double* g_x_device);
+int tc_interp_chi2_occupation_grad_batch(tc_interp* interp, const double* occupation,
+                                         const double* x, int64_t n_draws, unsigned flags,
+                                         const double* data, const double* precision, double* ngal,
+                                         double* chi2, double* dchi2_docc, double* dchi2_dx,
+                                         double* dngal_dx);
+int tc_interp_chi2_occupation_grad_batch_device(tc_interp* interp,
+                                                const double* occupation_device,
+                                                const double* x_device, int64_t n_draws,
+                                                unsigned flags, const double* data,
+                                                const double* precision, double* ngal_device,
+                                                double* chi2_device, double* dchi2_docc_device,
+                                                double* dchi2_dx_device, double* dngal_dx_device);
+
 /* Joint likelihood of several tables (extension): the data vector of the reference's documented
  * likelihood step is the concatenation of two tables' predictions, (w_p, DeltaSigma)
  * (docs/guides/overview.rst:86-92), and its covariance couples them.  A joint handle over 1 .. 16

@@ -130,6 +130,11 @@ int tc_debug_joint_forward_lds_bytes(int n_bins, int n_r_total, int waves, int64
  * for tables of n_bins bins, n_r_total result rows in all and n_r_auto of them those of mode-auto
  * tables -- no device needed. */
 int tc_debug_joint_vjp_lds_bytes(int n_bins, int n_r_total, int n_r_auto, int64_t* bytes);
+/* The LDS bytes per workgroup of vjp_interp_auto_kernel (mode 0) / vjp_interp_cross_kernel (mode
+ * 1; n_bins is not read) (tabcorr_amd/csrc/vjp.h: interp_vjp_auto_lds_bytes,
+ * interp_vjp_cross_lds_bytes) for an interpolator of n_dim dimensions over tables of n_bins bins
+ * and n_r correlation function bins -- no device needed. */
+int tc_debug_interp_vjp_lds_bytes(int mode, int n_bins, int n_r, int n_dim, int64_t* bytes);
 /* What the forward entries of a joint refuse on the host, from plain numbers -- no device, no
  * handle: n_tables tables of n_bins bins with mode[k] (0 auto, 1 cross), n_r[k] correlation
  * function bins and compute_dtype[k] (TC_DTYPE_*).  TC_OK and the workgroup's LDS in *lds_bytes

@@ -160,6 +160,8 @@ SIGNATURES = {
     'tc_interp_synchronize': [ctypes.c_void_p],
     'tc_interp_axis': [ctypes.c_void_p, ctypes.c_int, c_int_p, c_double_p,
                        ctypes.c_int],
+    'tc_interp_info': [ctypes.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p],
+    'tc_debug_interp_vjp_lds_bytes': [ctypes.c_int] * 4 + [c_int64_p],
     'tc_interp_predict_zheng07_batch': [
         ctypes.c_void_p, c_double_p, ctypes.c_int, c_double_p,
         ctypes.c_int64, ctypes.c_int, ctypes.c_uint, c_double_p, c_double_p],
@@ -334,6 +336,11 @@ def _derivative_signatures():
         out['tc_joint_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 3
         out['tc_joint_chi2_occupation_grad_batch' + suffix] = (head + [c_double_p] * 2 +
                                                               [array] * 3)
+        # (an interpolator: x behind the occupations, and the outputs with respect to x last)
+        head = [ctypes.c_void_p, array, array, ctypes.c_int64, ctypes.c_uint]
+        out['tc_interp_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 4
+        out['tc_interp_chi2_occupation_grad_batch' + suffix] = (head + [c_double_p] * 2 +
+                                                               [array] * 5)
     return out
 
 

@@ -23,7 +23,8 @@ SOURCES = ['inst_fused.hip', 'inst_fused32.hip', 'inst_fused16.hip', 'inst_fused
            'inst_cross.hip', 'inst_quad.hip', 'inst_single.hip', 'inst_grad.hip',
            'inst_grad_assembias.hip', 'inst_grad_leauthaud11.hip', 'inst_joint.hip',
            'inst_joint_forward.hip', 'inst_joint_interp.hip', 'inst_joint_interp_forward.hip',
-           'inst_vjp.hip', 'inst_joint_vjp.hip', 'launch.hip', 'paircount.hip',
+           'inst_vjp.hip', 'inst_joint_vjp.hip', 'inst_interp_vjp.hip', 'launch.hip',
+           'paircount.hip',
            'table.cpp', 'interp.cpp', 'joint.cpp', 'joint_interp.cpp', 'comm.cpp', 'runtime.cpp',
            'hostmath.cpp']
 # per-unit flags (inst_single.hip: see its header)

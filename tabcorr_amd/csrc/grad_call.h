@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "grad.h"
+#include "vjp.h"
 
 namespace tc {
 namespace host {
@@ -73,37 +74,63 @@ struct GradRequest {
   }
 };
 
-// One call at the occupation seam (vjp.h), or one slab of it, of a table or of a joint.  Which
-// arrays are there says the form: g_occupation NULL is the forward-only form (a joint's), and
-// chi2_data the likelihood form, whose value is chi2 (n_draws) where the prediction's is xi
-// (n_draws, n_r) with the cotangents g_xi and, or NULL = 0, g_ngal.
+// One call at the occupation seam (vjp.h), or one slab of it, of a table, of a joint or of an
+// interpolator.  Which arrays are there says the form: g_occupation NULL is the forward-only form
+// (a joint's, an interpolator's), and chi2_data the likelihood form, whose value is chi2 (n_draws)
+// where the prediction's is xi (n_draws, n_r) with the cotangents g_xi and, or NULL = 0, g_ngal.
+// An interpolator's draws carry n_classes rows of occupations and n_extra grid parameters x, and
+// its adjoint forms return g_x (the likelihood form: dchi2 / dx, and dngal_dx beside it).
 struct VjpRequest {
   int64_t n_draws;
   int n_bins;
   int n_r;                   // rows of a draw's result: a table's n_r, a joint's n_r_total
-  const double* occupation;  // (n_draws, n_bins)
+  const double* occupation;  // (n_draws, n_classes, n_bins)
   const double* g_ngal;      // (n_draws), or NULL
   const double* g_xi;        // (n_draws, n_r), or NULL
   const double* chi2_data;   // on the device: data (n_r), then the precision matrix (n_r, n_r)
   double* ngal;              // (n_draws)
   double* xi;                // (n_draws, n_r), or NULL
   double* chi2;              // (n_draws), or NULL
-  double* g_occupation;      // (n_draws, n_bins), or NULL
+  double* g_occupation;      // (n_draws, n_classes, n_bins), or NULL
+  // an interpolator's (a table and a joint: 1, 0 and NULLs)
+  int n_classes;
+  int n_extra;               // an interpolator's n_dim
+  const double* x;           // (n_draws, n_extra), or NULL
+  double* g_x;               // (n_draws, n_extra), or NULL
+  double* dngal_dx;          // (n_draws, n_extra), or NULL
 
   bool likelihood() const { return chi2_data != nullptr; }
+  // doubles of a draw's occupations
+  int64_t wide() const { return (int64_t)n_classes * n_bins; }
 
   // The draws [begin, begin + n) of the call: every offset a 64-bit product.
   VjpRequest slab(int64_t begin, int64_t n) const {
     VjpRequest out = *this;
     out.n_draws = n;
-    out.occupation = occupation + begin * n_bins;
+    out.occupation = occupation + begin * wide();
     out.g_ngal = g_ngal ? g_ngal + begin : nullptr;
     out.g_xi = g_xi ? g_xi + begin * n_r : nullptr;
     out.ngal = ngal + begin;
     out.xi = xi ? xi + begin * n_r : nullptr;
     out.chi2 = chi2 ? chi2 + begin : nullptr;
-    out.g_occupation = g_occupation ? g_occupation + begin * n_bins : nullptr;
+    out.g_occupation = g_occupation ? g_occupation + begin * wide() : nullptr;
+    out.x = x ? x + begin * n_extra : nullptr;
+    out.g_x = g_x ? g_x + begin * n_extra : nullptr;
+    out.dngal_dx = dngal_dx ? dngal_dx + begin * n_extra : nullptr;
     return out;
+  }
+
+  // The arrays of the argument block (x and the two x-outputs stand beside it: InterpVjpArgs).
+  void arrays(tc::VjpArgs* va) const {
+    va->occupation = occupation;
+    va->n_draws = n_draws;
+    va->g_ngal = g_ngal;
+    va->g_xi = g_xi;
+    va->chi2_data = chi2_data;
+    va->ngal = ngal;
+    va->xi = xi;
+    va->chi2 = chi2;
+    va->g_occupation = g_occupation;
   }
 };
 
@@ -200,54 +227,90 @@ int vjp_device(tc_table* t, GradLane lane, const VjpRequest& request, Run run) {
   });
 }
 
-// ... and on host arrays (chi2_data on the device), slab by slab on lane 0 of `t`: the
-// occupations and the cotangents go up in one workspace, the results come down from another.
+// The buffers a host-array call at the occupation seam is staged through, the stream of its
+// copies and the draws of one slab: a table's own (a joint: its first table's), an interpolator's.
+struct VjpStaging {
+  DeviceBuffer* in;          // occupations, cotangents, x
+  DeviceBuffer* out_ngal;
+  DeviceBuffer* out;         // g_occupation, the value, g_x, dngal_dx
+  hipStream_t stream;
+  int64_t max_slab;
+};
+
+// A call at the occupation seam on host arrays (chi2_data on the device), slab by slab: the
+// occupations, the cotangents and x go up in one workspace, device(staged slab) enqueues the
+// launches on the stream of the staging, and the results come down from another.
+template <typename Device>
+int vjp_host_arrays(const VjpStaging& stage, const VjpRequest& request, Device device) {
+  const bool chi2 = request.likelihood();
+  const bool cotangents = !chi2 && request.g_xi != nullptr;
+  const bool backward = request.g_occupation != nullptr;
+  const size_t n_r = (size_t)request.n_r, wide = (size_t)request.wide();
+  const size_t n_extra = (size_t)request.n_extra;
+  return for_each_slab(request.n_draws, stage.max_slab, [&](int64_t begin, int64_t n_slab) {
+    const VjpRequest host = request.slab(begin, n_slab);
+    const size_t n = (size_t)n_slab;
+    const size_t value_count = chi2 ? n : n * n_r;
+    int status = stage.in->reserve(n * (wide + n_r + 1 + n_extra) * 8, stage.stream);
+    if (status == TC_OK) status = stage.out_ngal->reserve(n * 8, stage.stream);
+    if (status == TC_OK)
+      status = stage.out->reserve((n * wide + value_count + 2 * n * n_extra) * 8, stage.stream);
+    if (status != TC_OK) return status;
+    double* d_occupation = (double*)stage.in->ptr;
+    double* d_g_xi = d_occupation + n * wide;
+    double* d_g_ngal = d_g_xi + n * n_r;
+    double* d_x = d_g_ngal + n;
+    double* d_g_occupation = (double*)stage.out->ptr;
+    double* d_value = d_g_occupation + n * wide;
+    double* d_g_x = d_value + value_count;
+    double* d_dngal_dx = d_g_x + n * n_extra;
+    TC_HIP(hipMemcpyAsync(d_occupation, host.occupation, n * wide * 8, hipMemcpyHostToDevice,
+                          stage.stream));
+    if (cotangents)
+      TC_HIP(hipMemcpyAsync(d_g_xi, host.g_xi, n * n_r * 8, hipMemcpyHostToDevice, stage.stream));
+    if (cotangents && host.g_ngal != nullptr)
+      TC_HIP(hipMemcpyAsync(d_g_ngal, host.g_ngal, n * 8, hipMemcpyHostToDevice, stage.stream));
+    if (host.x != nullptr)
+      TC_HIP(hipMemcpyAsync(d_x, host.x, n * n_extra * 8, hipMemcpyHostToDevice, stage.stream));
+    VjpRequest staged = host;
+    staged.occupation = d_occupation;
+    staged.g_ngal = cotangents && host.g_ngal != nullptr ? d_g_ngal : nullptr;
+    staged.g_xi = cotangents ? d_g_xi : nullptr;
+    staged.x = host.x != nullptr ? d_x : nullptr;
+    staged.ngal = (double*)stage.out_ngal->ptr;
+    staged.xi = chi2 ? nullptr : d_value;
+    staged.chi2 = chi2 ? d_value : nullptr;
+    staged.g_occupation = backward ? d_g_occupation : nullptr;
+    staged.g_x = host.g_x != nullptr ? d_g_x : nullptr;
+    staged.dngal_dx = host.dngal_dx != nullptr ? d_dngal_dx : nullptr;
+    status = device(staged);
+    if (status != TC_OK) return status;
+    TC_HIP(hipMemcpyAsync(host.ngal, staged.ngal, n * 8, hipMemcpyDeviceToHost, stage.stream));
+    TC_HIP(hipMemcpyAsync(chi2 ? host.chi2 : host.xi, d_value, value_count * 8,
+                          hipMemcpyDeviceToHost, stage.stream));
+    if (backward)
+      TC_HIP(hipMemcpyAsync(host.g_occupation, d_g_occupation, n * wide * 8,
+                            hipMemcpyDeviceToHost, stage.stream));
+    if (host.g_x != nullptr)
+      TC_HIP(hipMemcpyAsync(host.g_x, d_g_x, n * n_extra * 8, hipMemcpyDeviceToHost,
+                            stage.stream));
+    if (host.dngal_dx != nullptr)
+      TC_HIP(hipMemcpyAsync(host.dngal_dx, d_dngal_dx, n * n_extra * 8, hipMemcpyDeviceToHost,
+                            stage.stream));
+    TC_HIP(hipStreamSynchronize(stage.stream));
+    return (int)TC_OK;
+  });
+}
+
+// ... of a table (a joint: its first table), on its lane 0.
 template <typename Run>
 int vjp_host(tc_table* t, const VjpRequest& request, Run run) {
   TC_HIP(hipSetDevice(t->device));
   int stopped = TC_OK;
   if (t->resident.running && (stopped = resident_stop(t)) != TC_OK) return stopped;
-  const bool chi2 = request.likelihood();
-  const bool cotangents = !chi2 && request.g_xi != nullptr;
-  const bool backward = request.g_occupation != nullptr;
-  const size_t n_r = (size_t)request.n_r, n_bins = (size_t)request.n_bins;
-  return for_each_slab(request.n_draws, max_slab(t), [&](int64_t begin, int64_t n_slab) {
-    const VjpRequest host = request.slab(begin, n_slab);
-    const size_t n = (size_t)n_slab;
-    const size_t value_count = chi2 ? n : n * n_r;
-    int status = t->occupation.reserve(n * (n_bins + n_r + 1) * 8, t->stream);
-    if (status == TC_OK) status = t->out_ngal.reserve(n * 8, t->stream);
-    if (status == TC_OK) status = t->out_xi.reserve((n * n_bins + value_count) * 8, t->stream);
-    if (status != TC_OK) return status;
-    double* d_occupation = (double*)t->occupation.ptr;
-    double* d_g_xi = d_occupation + n * n_bins;
-    double* d_g_ngal = d_g_xi + n * n_r;
-    double* d_g_occupation = (double*)t->out_xi.ptr;
-    double* d_value = d_g_occupation + n * n_bins;
-    TC_HIP(hipMemcpyAsync(d_occupation, host.occupation, n * n_bins * 8, hipMemcpyHostToDevice,
-                          t->stream));
-    if (cotangents)
-      TC_HIP(hipMemcpyAsync(d_g_xi, host.g_xi, n * n_r * 8, hipMemcpyHostToDevice, t->stream));
-    if (cotangents && host.g_ngal != nullptr)
-      TC_HIP(hipMemcpyAsync(d_g_ngal, host.g_ngal, n * 8, hipMemcpyHostToDevice, t->stream));
-    VjpRequest staged = host;
-    staged.occupation = d_occupation;
-    staged.g_ngal = cotangents && host.g_ngal != nullptr ? d_g_ngal : nullptr;
-    staged.g_xi = cotangents ? d_g_xi : nullptr;
-    staged.ngal = (double*)t->out_ngal.ptr;
-    staged.xi = chi2 ? nullptr : d_value;
-    staged.chi2 = chi2 ? d_value : nullptr;
-    staged.g_occupation = backward ? d_g_occupation : nullptr;
-    status = vjp_device(t, GradLane::kPinned, staged, run);
-    if (status != TC_OK) return status;
-    TC_HIP(hipMemcpyAsync(host.ngal, staged.ngal, n * 8, hipMemcpyDeviceToHost, t->stream));
-    TC_HIP(hipMemcpyAsync(chi2 ? host.chi2 : host.xi, d_value, value_count * 8,
-                          hipMemcpyDeviceToHost, t->stream));
-    if (backward)
-      TC_HIP(hipMemcpyAsync(host.g_occupation, d_g_occupation, n * n_bins * 8,
-                            hipMemcpyDeviceToHost, t->stream));
-    TC_HIP(hipStreamSynchronize(t->stream));
-    return (int)TC_OK;
+  const VjpStaging stage{&t->occupation, &t->out_ngal, &t->out_xi, t->stream, max_slab(t)};
+  return vjp_host_arrays(stage, request, [&](const VjpRequest& staged) {
+    return vjp_device(t, GradLane::kPinned, staged, run);
   });
 }
 

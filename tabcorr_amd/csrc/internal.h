@@ -861,7 +861,8 @@ int launch_chi2(const double* xi, int64_t n_draws, int n_r, const double* data,
 
 // ---- kernel instances (inst_quad.hip, inst_fused.hip, inst_cross.hip, inst_single.hip,
 // inst_grad.hip, inst_grad_assembias.hip, inst_joint.hip, inst_joint_forward.hip,
-// inst_joint_interp.hip, inst_joint_interp_forward.hip, inst_vjp.hip, inst_joint_vjp.hip) ----
+// inst_joint_interp.hip, inst_joint_interp_forward.hip, inst_vjp.hip, inst_joint_vjp.hip,
+// inst_interp_vjp.hip) ----
 // The device code lives in these translation units; launch.hip fills the argument blocks and
 // says which instance it wants.
 int launch_occupation(const tc::OccArgs& oa, unsigned flags, int n_gauss, bool grouped,
@@ -914,6 +915,9 @@ int launch_vjp_instance(int mode, int device, dim3 grid, int lds, hipStream_t st
                         hipEvent_t k0, hipEvent_t k1, const tc::VjpArgs& va);
 int launch_vjp_joint_instance(int device, dim3 grid, int lds, hipStream_t stream, hipEvent_t k0,
                               hipEvent_t k1, const tc::JointVjpArgs& ja);
+// vjp_interp_auto_kernel / vjp_interp_cross_kernel (inst_interp_vjp.hip)
+int launch_vjp_interp_instance(int mode, int device, dim3 grid, int lds, hipStream_t stream,
+                               hipEvent_t k0, hipEvent_t k1, const tc::InterpVjpArgs& ia);
 int launch_single_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_resident_kernel(int blocks, hipStream_t stream, const tc::SingleArgs& sa);
 int launch_ensemble_kernel(int device, int grid, int lds_bytes, hipStream_t stream,

@@ -41,6 +41,7 @@ struct tc_interp {
     void* class_begin = nullptr;              // (classes + 1)
     void* node = nullptr;                     // (K, D)
     void* matrices = nullptr;                 // (K) device pointers
+    void* class_n_h = nullptr;                // (classes) device pointers: n_h of every class
   };
   GradWalk grad_walk;
   // Lanes (stream + workspaces), as for a table handle: consecutive device-pointer and
@@ -569,7 +570,8 @@ int tc_interp_destroy(tc_interp* it) {
     for (void* p : {kv.second.log_m, kv.second.m, kv.second.weight, kv.second.n_h,
                     kv.second.percentile})
       if (p) (void)hipFree(p);
-  for (void* p : {it->grad_walk.class_begin, it->grad_walk.node, it->grad_walk.matrices})
+  for (void* p : {it->grad_walk.class_begin, it->grad_walk.node, it->grad_walk.matrices,
+                  it->grad_walk.class_n_h})
     if (p) (void)hipFree(p);
   for (tc_interp::Lane& lane : it->lanes) {
     for (void* p : {lane.d_nbufs, lane.d_nbufs32, lane.d_ngal_parts})
@@ -975,8 +977,9 @@ int build_grad_walk(tc_interp* it, bool with_matrices) {
   if (it->grad_walk.built && (!with_matrices || it->grad_walk.matrices != nullptr)) return TC_OK;
   const int n_classes = (int)it->class_table.size();
   std::vector<int32_t> class_begin(1, 0), node;
-  std::vector<void*> matrices;
+  std::vector<void*> matrices, class_n_h;
   for (int v = 0; v < n_classes; ++v) {
+    class_n_h.push_back(it->tables[it->class_table[v]]->d_n_h);
     for (int k = 0; k < it->n_tables; ++k) {
       if (it->table_class[k] != v) continue;
       if (with_matrices) {
@@ -990,11 +993,12 @@ int build_grad_walk(tc_interp* it, bool with_matrices) {
     class_begin.push_back((int32_t)(node.size() / it->n_dim));
   }
   // (into locals: a failure half-way leaves nothing behind)
-  void* uploaded[3] = {nullptr, nullptr, nullptr};
+  void* uploaded[4] = {nullptr, nullptr, nullptr, nullptr};
   int status = TC_OK;
   if (!it->grad_walk.built) {
     status = upload(class_begin, &uploaded[0]);
     if (status == TC_OK) status = upload(node, &uploaded[1]);
+    if (status == TC_OK) status = upload(class_n_h, &uploaded[3]);
   }
   if (status == TC_OK && with_matrices) status = upload(matrices, &uploaded[2]);
   if (status != TC_OK) {
@@ -1005,10 +1009,27 @@ int build_grad_walk(tc_interp* it, bool with_matrices) {
   if (!it->grad_walk.built) {
     it->grad_walk.class_begin = uploaded[0];
     it->grad_walk.node = uploaded[1];
+    it->grad_walk.class_n_h = uploaded[3];
     it->grad_walk.built = true;
   }
   if (with_matrices) it->grad_walk.matrices = uploaded[2];
   return TC_OK;
+}
+
+// The grid and the walk of the argument block (build_grad_walk has run).
+void fill_interp_grid(const tc_interp* it, tc::GradInterpArgs* ga) {
+  ga->n_dim = it->n_dim;
+  ga->n_classes = (int)it->class_table.size();
+  for (int d = 0; d < it->n_dim; ++d) {
+    ga->n_axis[d] = (int)it->xp[d].size();
+    ga->axis_offset[d] = it->axis_offset[d];
+    ga->a_offset[d] = it->a_offset[d];
+  }
+  ga->xp = (const double*)it->d_xp;
+  ga->a = (const double*)it->d_a;
+  ga->class_begin = (const int32_t*)it->grad_walk.class_begin;
+  ga->walk_node = (const int32_t*)it->grad_walk.node;
+  ga->matrices = (const double* const*)it->grad_walk.matrices;
 }
 
 // An interpolator as grad_entry sees it.
@@ -1112,21 +1133,9 @@ int interp_grad_args(tc_interp* it, const GradRequest& request, tc::GradInterpAr
   status = class_pointers(it, request.n_gauss, &pointers);
   if (status == TC_OK) status = build_grad_walk(it, with_matrices);
   if (status != TC_OK) return status;
-  const int n_dim = it->n_dim;
   tc::GradInterpArgs& ga = *out;
   fill_grad_shape(t0, request.n_gauss, request.flags, &ga.table);
-  ga.n_dim = n_dim;
-  ga.n_classes = (int)it->class_table.size();
-  for (int d = 0; d < n_dim; ++d) {
-    ga.n_axis[d] = (int)it->xp[d].size();
-    ga.axis_offset[d] = it->axis_offset[d];
-    ga.a_offset[d] = it->a_offset[d];
-  }
-  ga.xp = (const double*)it->d_xp;
-  ga.a = (const double*)it->d_a;
-  ga.class_begin = (const int32_t*)it->grad_walk.class_begin;
-  ga.walk_node = (const int32_t*)it->grad_walk.node;
-  ga.matrices = (const double* const*)it->grad_walk.matrices;
+  fill_interp_grid(it, &ga);
   ga.class_log_m = (const double* const*)pointers->log_m;
   ga.class_m = (const double* const*)pointers->m;
   ga.class_weight = (const double* const*)pointers->weight;
@@ -1289,6 +1298,205 @@ int tc_interp_chi2_grad_assembias_batch(tc_interp* it, const double* theta, int 
                     interp_request(it, tc::kGradParamsAssembias, theta, x, n_draws, n_gauss, flags,
                                    ngal, chi2, dngal, dchi2, fisher),
                     n_theta, &operands, false);
+}
+
+// ---- the occupation seam (interp_vjp_kernels.hip.h) ---------------------------------------------
+
+namespace {
+
+size_t interp_vjp_lds(const tc_interp* it) {
+  const tc_table* t0 = it->tables[0];
+  return t0->mode == TC_MODE_AUTO
+             ? tc::interp_vjp_auto_lds_bytes(t0->n_bins, t0->n_r, it->n_dim)
+             : tc::interp_vjp_cross_lds_bytes(t0->n_r, it->n_dim);
+}
+
+// What the entries at the occupation seam refuse, the NULL handle first: flags, float32, a negative
+// number of draws, a workgroup beyond the LDS of a CU.
+int check_interp_vjp(const tc_interp* it, int64_t n_draws, unsigned flags) {
+  TC_CHECK(it != nullptr, "interp handle is NULL");
+  const tc_table* t0 = it->tables[0];
+  if (flags & TC_FLAG_SEPARATE_GAL_TYPE)
+    return fail(TC_ERR_UNSUPPORTED, "the interpolator occupation VJP is implemented for the total "
+                                    "prediction only (not separate_gal_type)");
+  if (flags != 0)
+    return fail(TC_ERR_UNSUPPORTED, "interpolator occupation VJP: flags must be 0, got 0x%x",
+                flags);
+  if (t0->compute_dtype != TC_DTYPE_F64)
+    return fail(TC_ERR_UNSUPPORTED,
+                "the interpolator occupation VJP needs a float64 compute dtype");
+  TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
+  const size_t lds = interp_vjp_lds(it);
+  if (lds > (size_t)kMaxLdsBytes)
+    return fail(TC_ERR_UNSUPPORTED,
+                "interpolator occupation VJP: a grid of %d dimensions over tables of %d bins and "
+                "%d correlation function bins needs %zu bytes of LDS per workgroup, beyond the %d "
+                "there are",
+                it->n_dim, t0->n_bins, t0->n_r, lds, kMaxLdsBytes);
+  return check_grad_fit(t0, "interpolator occupation VJP", lds);
+}
+
+// Every entry at the occupation seam: `request` as the caller stated it (chi2_data not yet
+// known) on device pointers (the interpolator's next lane) or host arrays (slab-wise on its lane
+// 0), and, for the likelihood form, its operands on the host.
+int interp_vjp_entry(tc_interp* it, bool host, unsigned flags, VjpRequest request,
+                     const Chi2Host* operands) {
+  int status = check_interp_vjp(it, request.n_draws, flags);
+  if (status != TC_OK) return status;
+  if (request.n_draws == 0) return TC_OK;
+  if (operands != nullptr) {
+    TC_CHECK(request.occupation && request.x && operands->data && operands->precision &&
+                 request.ngal && request.chi2,
+             "NULL pointer");
+    const int given = (request.g_occupation != nullptr) + (request.g_x != nullptr) +
+                      (request.dngal_dx != nullptr);
+    TC_CHECK(given == 0 || given == 3,
+             "dchi2_docc, dchi2_dx and dngal_dx go together: all NULL is the forward-only form");
+  } else {
+    TC_CHECK(request.occupation && request.x && request.ngal && request.xi, "NULL pointer");
+    const int given = (request.g_xi != nullptr) + (request.g_occupation != nullptr) +
+                      (request.g_x != nullptr);
+    TC_CHECK(given == 0 || given == 3,
+             "g_xi, g_occupation and g_x go together: all NULL is the forward-only form");
+  }
+  tc_table* t0 = it->tables[0];
+  TC_HIP(hipSetDevice(it->device));
+  for (tc_table* t : it->tables)
+    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+  status = build_grad_walk(it, /*with_matrices=*/true);
+  if (status != TC_OK) return status;
+  if (operands != nullptr) {
+    status = upload_operands(it, operands->data, operands->precision);
+    if (status != TC_OK) return status;
+    request.chi2_data = it->chi2.device();
+  }
+  tc::InterpVjpArgs ia{};
+  fill_interp_grid(it, &ia.interp);
+  ia.interp.class_n_h = (const double* const*)it->grad_walk.class_n_h;
+  ia.vjp.n_bins = t0->n_bins;
+  ia.vjp.n_r = t0->n_r;
+  ia.vjp.perm = (const int32_t*)t0->d_perm;
+  ia.vjp.row_tiles = tc::grad_row_tiles(t0->n_bins);
+  ia.vjp.k_steps = tc::grad_k_steps(t0->n_bins);
+  const int lds = (int)interp_vjp_lds(it);
+  // (one launch per slab of at most max_slab(t0) draws, timed through the first table's timer)
+  const auto run = [&](const VjpRequest& slab, hipStream_t stream) {
+    Range range("interpolator occupation VJP (one launch)");
+    slab.arrays(&ia.vjp);
+    ia.interp.table.n_draws = slab.n_draws;
+    ia.interp.x = slab.x;
+    ia.g_x = slab.g_x;
+    ia.dngal_dx = slab.dngal_dx;
+    return launch_grad_batch(t0, slab.n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+      return launch_vjp_interp_instance(t0->mode, it->device, grid, lds, stream, k0, k1, ia);
+    });
+  };
+  if (host) {
+    const VjpStaging stage{&it->theta, &it->out_ngal, &it->out_xi, it->stream, max_slab(t0)};
+    return vjp_host_arrays(stage, request, [&](const VjpRequest& staged) {
+      return run(staged, interp_grad_stream(it, GradLane::kPinned));
+    });
+  }
+  hipStream_t stream = interp_grad_stream(it, GradLane::kNext);
+  return for_each_slab(request.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
+    return run(request.slab(begin, n), stream);
+  });
+}
+
+// The request of such an entry, in the order of the C arguments.
+VjpRequest interp_vjp_request(const tc_interp* it, const double* occupation, const double* x,
+                              int64_t n_draws, const double* g_ngal, const double* g_xi,
+                              double* ngal, double* xi, double* chi2, double* g_occupation,
+                              double* g_x, double* dngal_dx) {
+  return VjpRequest{n_draws,
+                    it ? it->tables[0]->n_bins : 0,
+                    it ? it->tables[0]->n_r : 0,
+                    occupation,
+                    g_ngal,
+                    g_xi,
+                    nullptr,
+                    ngal,
+                    xi,
+                    chi2,
+                    g_occupation,
+                    it ? (int)it->class_table.size() : 1,
+                    it ? it->n_dim : 0,
+                    x,
+                    g_x,
+                    dngal_dx};
+}
+
+}  // namespace
+
+int tc_interp_info(const tc_interp* it, int* n_tables, int* n_classes, int* table_class,
+                   int* class_table) {
+  TC_CHECK(it != nullptr, "interp handle is NULL");
+  if (n_tables != nullptr) *n_tables = it->n_tables;
+  if (n_classes != nullptr) *n_classes = (int)it->class_table.size();
+  if (table_class != nullptr)
+    for (int k = 0; k < it->n_tables; ++k) table_class[k] = it->table_class[k];
+  if (class_table != nullptr)
+    for (size_t v = 0; v < it->class_table.size(); ++v) class_table[v] = it->class_table[v];
+  return TC_OK;
+}
+
+int tc_interp_predict_occupation_vjp_batch(tc_interp* it, const double* occupation,
+                                           const double* x, int64_t n_draws, unsigned flags,
+                                           const double* g_ngal, const double* g_xi, double* ngal,
+                                           double* xi, double* g_occupation, double* g_x) {
+  return interp_vjp_entry(it, true, flags,
+                          interp_vjp_request(it, occupation, x, n_draws, g_ngal, g_xi, ngal, xi,
+                                             nullptr, g_occupation, g_x, nullptr),
+                          nullptr);
+}
+
+int tc_interp_predict_occupation_vjp_batch_device(tc_interp* it, const double* occupation_device,
+                                                  const double* x_device, int64_t n_draws,
+                                                  unsigned flags, const double* g_ngal_device,
+                                                  const double* g_xi_device, double* ngal_device,
+                                                  double* xi_device, double* g_occupation_device,
+                                                  double* g_x_device) {
+  return interp_vjp_entry(it, false, flags,
+                          interp_vjp_request(it, occupation_device, x_device, n_draws,
+                                             g_ngal_device, g_xi_device, ngal_device, xi_device,
+                                             nullptr, g_occupation_device, g_x_device, nullptr),
+                          nullptr);
+}
+
+int tc_interp_chi2_occupation_grad_batch(tc_interp* it, const double* occupation, const double* x,
+                                         int64_t n_draws, unsigned flags, const double* data,
+                                         const double* precision, double* ngal, double* chi2,
+                                         double* dchi2_docc, double* dchi2_dx, double* dngal_dx) {
+  const Chi2Host operands{data, precision};
+  return interp_vjp_entry(it, true, flags,
+                          interp_vjp_request(it, occupation, x, n_draws, nullptr, nullptr, ngal,
+                                             nullptr, chi2, dchi2_docc, dchi2_dx, dngal_dx),
+                          &operands);
+}
+
+int tc_interp_chi2_occupation_grad_batch_device(tc_interp* it, const double* occupation_device,
+                                                const double* x_device, int64_t n_draws,
+                                                unsigned flags, const double* data,
+                                                const double* precision, double* ngal_device,
+                                                double* chi2_device, double* dchi2_docc_device,
+                                                double* dchi2_dx_device,
+                                                double* dngal_dx_device) {
+  const Chi2Host operands{data, precision};
+  return interp_vjp_entry(it, false, flags,
+                          interp_vjp_request(it, occupation_device, x_device, n_draws, nullptr,
+                                             nullptr, ngal_device, nullptr, chi2_device,
+                                             dchi2_docc_device, dchi2_dx_device, dngal_dx_device),
+                          &operands);
+}
+
+int tc_debug_interp_vjp_lds_bytes(int mode, int n_bins, int n_r, int n_dim, int64_t* bytes) {
+  TC_CHECK(bytes != nullptr, "bytes is NULL");
+  TC_CHECK((mode == TC_MODE_AUTO || mode == TC_MODE_CROSS) && n_bins >= 1 && n_r >= 1 &&
+               n_dim >= 1 && n_dim <= tc::kMaxInterpDim,
+           "invalid shape");
+  *bytes = (int64_t)(mode == TC_MODE_AUTO ? tc::interp_vjp_auto_lds_bytes(n_bins, n_r, n_dim)
+                                          : tc::interp_vjp_cross_lds_bytes(n_r, n_dim));
+  return TC_OK;
 }
 
 int tc_interp_wait(tc_interp* it, int64_t ticket) {

@@ -437,7 +437,8 @@ VjpRequest joint_vjp_request(const tc_joint* joint, const double* occupation, in
                              const double* g_ngal, const double* g_xi, double* ngal, double* xi,
                              double* chi2, double* g_occupation) {
   return VjpRequest{n_draws, joint ? joint->tables[0]->n_bins : 0, joint ? joint->n_r_total : 0,
-                    occupation, g_ngal, g_xi, nullptr, ngal, xi, chi2, g_occupation};
+                    occupation, g_ngal, g_xi, nullptr, ngal, xi, chi2, g_occupation,
+                    1, 0, nullptr, nullptr, nullptr};
 }
 
 }  // namespace

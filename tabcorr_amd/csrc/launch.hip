@@ -1330,25 +1330,12 @@ int check_vjp_args(const tc_table* t, int64_t n_draws, unsigned flags) {
   return check_grad_fit(t, "occupation VJP", vjp_lds(t));
 }
 
-// (the arrays of a slab into the argument block)
-static void fill_vjp_arrays(const VjpRequest& r, tc::VjpArgs* va) {
-  va->occupation = r.occupation;
-  va->n_draws = r.n_draws;
-  va->g_ngal = r.g_ngal;
-  va->g_xi = r.g_xi;
-  va->chi2_data = r.chi2_data;
-  va->ngal = r.ngal;
-  va->xi = r.xi;
-  va->chi2 = r.chi2;
-  va->g_occupation = r.g_occupation;
-}
-
 int run_vjp(tc_table* t, const VjpRequest& request, hipStream_t stream) {
   Range range("occupation VJP (one launch)");
   int status = build_grad_table(t);
   if (status != TC_OK) return status;
   tc::VjpArgs va{};
-  fill_vjp_arrays(request, &va);
+  request.arrays(&va);
   va.n_bins = t->n_bins;
   va.n_r = t->n_r;
   va.perm = (const int32_t*)t->d_perm;
@@ -1367,7 +1354,7 @@ int run_vjp(tc_table* t, const VjpRequest& request, hipStream_t stream) {
 int run_vjp_joint(tc_table* t0, tc::JointVjpArgs ja, const VjpRequest& request,
                   hipStream_t stream) {
   Range range("joint occupation VJP (one launch)");
-  fill_vjp_arrays(request, &ja.vjp);
+  request.arrays(&ja.vjp);
   const int lds = (int)tc::joint_vjp_lds_bytes(ja.vjp.n_bins, ja.vjp.n_r, ja.n_r_auto);
   return launch_grad_batch(t0, request.n_draws, lds,
                            [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {

@@ -1076,8 +1076,9 @@ namespace {
 VjpRequest vjp_request(const tc_table* t, const double* occupation, int64_t n_draws,
                        const double* g_ngal, const double* g_xi, const double* chi2_data,
                        double* ngal, double* xi, double* chi2, double* g_occupation) {
-  return VjpRequest{n_draws, t->n_bins, t->n_r, occupation, g_ngal, g_xi,
-                    chi2_data, ngal,      xi,     chi2,       g_occupation};
+  return VjpRequest{n_draws,   t->n_bins, t->n_r, occupation, g_ngal,       g_xi,
+                    chi2_data, ngal,      xi,     chi2,       g_occupation, 1,
+                    0,         nullptr,   nullptr, nullptr};
 }
 
 // (the launcher of the staging path: one launch of the table's kernel per slab)

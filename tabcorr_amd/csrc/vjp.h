@@ -57,4 +57,48 @@ constexpr size_t vjp_cross_lds_bytes(int n_r) {
   return ((size_t)kGradCrossSlab + 3 * (size_t)n_r + 2) * kGradDraws * sizeof(double);
 }
 
+// ---- the occupation seam of an interpolator (interp_vjp_kernels.hip.h) ---------------------------
+// Tables t on a grid with the tensor-product spline weights c_t(x), classes v of tables with one
+// halo table; a draw's occupation is (n_classes, n_bins), class v's row in the gal_type order of
+// that class's tables.  With w = n_v . n_h,v and ngal_t = sum w (the class's):
+//   ngal = sum_t c_t ngal_t, xi_r = sum_t c_t xi_t,r
+//   g_n[v,i] = n_h,v,i sum_{t in v} c_t [ the bracket of the table formulas above ]
+//   g_x[d] = sum_t (dc_t/dx_d) [ g_ngal ngal_t + sum_r g_r xi_t,r ]
+// Likelihood form: g = 2 P_sym (xi - data) of the INTERPOLATED xi, g_ngal = 0; it also returns
+// dngal_dx[d] = sum_t (dc_t/dx_d) ngal_t.
+struct InterpVjpArgs {
+  // the grid, the walk (class_begin, walk_node, matrices) and class_n_h as for the gradient
+  // kernels; of `table` only n_draws is read (grad::interp_weights)
+  GradInterpArgs interp;
+  // occupation and g_occupation (n_draws, n_classes, n_bins); n_h and matrix are set per class
+  // and per table by the kernel.  g_occupation NULL: the forward-only form
+  VjpArgs vjp;
+  double* g_x;               // (n_draws, n_dim): the likelihood form's dchi2 / dx
+  double* dngal_dx;          // (n_draws, n_dim), likelihood form only
+};
+
+// LDS rows of kGradDraws doubles that both kernels keep: the weights and derivative weights of
+// every axis; per r bin the cotangent, the interpolated xi (the likelihood form: then the
+// residual) and the n_dim accumulators of dxi_r / dx_d; four rows of per-draw sums.
+constexpr int interp_vjp_common_rows(int n_r, int n_dim) {
+  return 2 * n_dim * kGradMaxAxis + (2 + n_dim) * n_r + 4;
+}
+// vjp_interp_auto_kernel: w of every bin of the class in flight and one row of zeros, per bin
+// the table's sum_r g_r U_ri and the class accumulator of g_n, one partial q_r per wave and the
+// class's share of xi.
+constexpr int interp_vjp_auto_rows(int n_bins, int n_r, int n_dim) {
+  return 3 * n_bins + 1 + (kGradWaves + 1) * n_r + interp_vjp_common_rows(n_r, n_dim);
+}
+constexpr size_t interp_vjp_auto_lds_bytes(int n_bins, int n_r, int n_dim) {
+  return (size_t)interp_vjp_auto_rows(n_bins, n_r, n_dim) * kGradDraws * sizeof(double);
+}
+// vjp_interp_cross_kernel: one slab of w, and the class's weighted products (1 + n_dim, n_r);
+// any number of bins.
+constexpr int interp_vjp_cross_rows(int n_r, int n_dim) {
+  return kGradCrossSlab + (1 + n_dim) * n_r + interp_vjp_common_rows(n_r, n_dim);
+}
+constexpr size_t interp_vjp_cross_lds_bytes(int n_r, int n_dim) {
+  return (size_t)interp_vjp_cross_rows(n_r, n_dim) * kGradDraws * sizeof(double);
+}
+
 }  // namespace tc

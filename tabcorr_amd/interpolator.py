@@ -581,6 +581,234 @@ class Interpolator:
         keys = model_keys + tuple(self.keys)
         return float(ngal[0]), _grad.keyed(dngal[0], keys), fisher[0]
 
+    # -- the occupation seam: any occupation model, one launch ---------------------------
+
+    def _classes(self):
+        """``table_class`` and ``class_tables``: the classes of identical
+        halo tables (``tabcorr/interpolator.py:63-70``), numbered by first
+        appearance in ``tabcorr_list``."""
+        if getattr(self, '_class_cache', None) is None:
+            raws, table_class, class_tables = [], [], []
+            for k, halotab in enumerate(self.tabcorr_list):
+                raw = halotab.gal_type.as_array()
+                for v, other in enumerate(raws):
+                    if other.dtype == raw.dtype and np.array_equal(other, raw):
+                        table_class.append(v)
+                        break
+                else:
+                    table_class.append(len(raws))
+                    class_tables.append(k)
+                    raws.append(raw)
+            self._class_cache = (np.array(table_class, dtype=np.int64),
+                                 np.array(class_tables, dtype=np.int64))
+        return self._class_cache
+
+    @property
+    def table_class(self):
+        """``(K, )``: the class of every table of ``tabcorr_list`` -- tables
+        with identical halo tables share their occupations."""
+        return self._classes()[0]
+
+    @property
+    def class_tables(self):
+        """``(C, )``: the first table of every class, in class order (first
+        appearance in ``tabcorr_list``)."""
+        return self._classes()[1]
+
+    def mean_occupation(self, model, n_gauss_prim=10, check_consistency=True,
+                        **occ_kwargs):
+        """The mean occupations of ``model`` for the occupation seam:
+        ``(C, n_bins)``, the Gauss-Legendre average of the model's callbacks
+        (``tabcorr/tabcorr.py:537-578``) for the first table of every class,
+        on the host (row ``v`` in the ``gal_type`` row order of that class's
+        tables).  ANY occupation model, with or without ``**occ_kwargs``."""
+        if check_consistency:
+            for halotab in self.tabcorr_list:
+                halotab._check_consistency_cached(model)
+        return np.stack([
+            self.tabcorr_list[k]._host_mean_occupation(
+                model, n_gauss_prim, **occ_kwargs)
+            for k in self.class_tables])
+
+    def class_weights(self, x):
+        """``(n_draws, C)``: the sum of the tables' spline weights ``c_t(x)``
+        over every class, on the host (``tc_spline_weights``: the text the
+        kernels run; an ``x`` outside the grid takes the outermost
+        polynomial).  It is the factor that the seam's calls leave to a
+        likelihood with an ``ngal`` term: ``dngal/docc[:, v] =
+        class_weights[:, v, None] * n_h_v`` with ``n_h_v`` the
+        ``gal_type['n_h']`` of class ``v``."""
+        x = _lib.contiguous(np.atleast_2d(x))
+        if x.ndim != 2 or x.shape[1] != len(self.keys):
+            raise ValueError('x must have shape (n_draws, {}).'.format(
+                len(self.keys)))
+        lib = _lib.load()
+        a = self._spline_matrices()
+        coef = np.ones((len(x), len(self.tabcorr_list)))
+        for d, xp in enumerate(self.xp):
+            xp = _lib.contiguous(xp)
+            node = np.searchsorted(xp, self.points[:, d])
+            weight, dweight = np.empty(len(xp)), np.empty(len(xp))
+            for i in range(len(x)):
+                _lib.check(lib.tc_spline_weights(
+                    len(xp), _lib.as_double_p(xp), _lib.as_double_p(a[d]),
+                    float(x[i, d]), _lib.as_double_p(weight),
+                    _lib.as_double_p(dweight), None))
+                coef[i] *= weight[node]
+        out = np.zeros((len(x), len(self.class_tables)))
+        for k, v in enumerate(self.table_class):
+            out[:, v] += coef[:, k]
+        return out
+
+    def _seam_inputs(self, occupation, x, extrapolate):
+        """The contiguous ``(n, C, n_bins)`` occupations and ``(n, D)`` grid
+        parameters of the seam's calls; wrong shapes and an ``x`` outside the
+        grid are refused before any device is touched."""
+        n_classes = len(self.class_tables)
+        n_bins = len(self.tabcorr_list[0].gal_type)
+        occupation = np.asarray(occupation, dtype=np.float64)
+        if occupation.ndim == 2 and n_classes == 1:
+            occupation = occupation[:, np.newaxis, :]
+        if occupation.ndim != 3 or occupation.shape[1:] != (n_classes, n_bins):
+            raise ValueError(
+                'The mean occupation array must have shape (n_draws, {}, {})'
+                ', got {}.'.format(n_classes, n_bins, occupation.shape))
+        x = _lib.contiguous(np.atleast_2d(x))
+        if x.shape != (len(occupation), len(self.keys)):
+            raise ValueError('x must have shape (n_draws, {}).'.format(
+                len(self.keys)))
+        self._check_range(x, extrapolate)
+        return _lib.contiguous(occupation), x
+
+    def _seam_device(self):
+        device = self.to_device()
+        if not getattr(self, '_classes_checked', False):
+            n_tables, n_classes = ctypes.c_int(0), ctypes.c_int(0)
+            table_class = np.zeros(len(self.tabcorr_list), dtype=np.int32)
+            with device.lock:
+                _lib.check(device.lib.tc_interp_info(
+                    device.handle, ctypes.byref(n_tables),
+                    ctypes.byref(n_classes),
+                    table_class.ctypes.data_as(_lib.c_int_p), None))
+            if not np.array_equal(table_class, self.table_class):
+                raise RuntimeError(
+                    'the library groups the tables into other classes ({}) '
+                    'than the host ({})'.format(table_class, self.table_class))
+            self._classes_checked = True
+        return device
+
+    def _predict_occupation(self, occupation, x, g_xi, g_ngal, extrapolate):
+        occupation, x = self._seam_inputs(occupation, x, extrapolate)
+        n_draws = len(occupation)
+        shape = tuple(self.tabcorr_list[0].tpcf_shape)
+        n_r = len(self.tabcorr_list[0].tpcf_matrix)
+        backward = g_xi is not None
+        if backward:
+            g_xi = np.asarray(g_xi, dtype=np.float64)
+            if g_xi.shape != (n_draws, ) + shape:
+                raise ValueError('g_xi must have shape {}, got {}.'.format(
+                    (n_draws, ) + shape, g_xi.shape))
+            g_xi = _lib.contiguous(g_xi.reshape(n_draws, n_r))
+            if g_ngal is not None:
+                g_ngal = np.asarray(g_ngal, dtype=np.float64)
+                if g_ngal.shape != (n_draws, ):
+                    raise ValueError(
+                        'g_ngal must have shape {}, got {}.'.format(
+                            (n_draws, ), g_ngal.shape))
+                g_ngal = _lib.contiguous(g_ngal)
+        device = self._seam_device()
+        ngal = np.empty(n_draws)
+        xi = np.empty((n_draws, n_r))
+        g_occupation = np.empty_like(occupation) if backward else None
+        g_x = np.empty_like(x) if backward else None
+        pointer = _lib.as_double_p
+        with device.lock:
+            _lib.check(device.lib.tc_interp_predict_occupation_vjp_batch(
+                device.handle, pointer(occupation), pointer(x), n_draws, 0,
+                pointer(g_ngal) if backward and g_ngal is not None else None,
+                pointer(g_xi) if backward else None, pointer(ngal),
+                pointer(xi), pointer(g_occupation) if backward else None,
+                pointer(g_x) if backward else None))
+        return ngal, xi.reshape((n_draws, ) + shape), g_occupation, g_x
+
+    def predict_occupation(self, occupation, x, extrapolate=False):
+        """The interpolated ``predict(occupation)`` for ANY occupation model,
+        in one launch: ``occupation`` ``(n_draws, C, n_bins)`` as
+        `mean_occupation` returns it per draw (``(n_draws, n_bins)`` where
+        ``C = 1``), ``x`` ``(n_draws, D)`` in the order of ``self.keys``.
+
+        Returns ``ngal (n_draws, )`` and ``xi (n_draws, ) + tpcf_shape``.
+        Raises ``NotImplementedError`` for what the kernel does not serve
+        (float32 tables, grids whose rows do not fit the LDS of a workgroup).
+        """
+        return self._predict_occupation(occupation, x, None, None,
+                                        extrapolate)[:2]
+
+    def predict_vjp(self, occupation, x, g_xi, g_ngal=None,
+                    extrapolate=False):
+        """`predict_occupation` with its vector-Jacobian product with respect
+        to the occupation array AND the grid parameters, in the same launch:
+        for cotangents ``g_ngal (n_draws, )`` (None = 0) and ``g_xi
+        (n_draws, ) + tpcf_shape``, ``g_occupation[d, v, i] = g_ngal[d]
+        dngal[d] / dn[d, v, i] + sum_r g_xi[d, r] dxi[d, r] / dn[d, v, i]`` and
+        ``g_x[d, e]`` likewise with respect to ``x[d, e]``.  Contracted with
+        the caller's own ``d<N>/dtheta`` it is the gradient of any scalar of
+        ``(ngal, xi)`` for EVERY occupation model.
+
+        Returns ``ngal, xi, g_occupation (n_draws, C, n_bins), g_x
+        (n_draws, D)``.
+        """
+        if g_xi is None:
+            raise ValueError('g_xi is None: predict_occupation is the '
+                             'forward-only call.')
+        return self._predict_occupation(occupation, x, g_xi, g_ngal,
+                                        extrapolate)
+
+    def _chi2_occupation(self, occupation, x, data, precision, extrapolate,
+                         gradient):
+        occupation, x = self._seam_inputs(occupation, x, extrapolate)
+        data, precision = _chi2_operands(
+            data, precision, len(self.tabcorr_list[0].tpcf_matrix))
+        device = self._seam_device()
+        n_draws = len(occupation)
+        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
+        outputs = [np.empty_like(occupation), np.empty_like(x),
+                   np.empty_like(x)] if gradient else [None] * 3
+        pointer = _lib.as_double_p
+        with device.lock:
+            _lib.check(device.lib.tc_interp_chi2_occupation_grad_batch(
+                device.handle, pointer(occupation), pointer(x), n_draws, 0,
+                pointer(data), pointer(precision), pointer(ngal),
+                pointer(chi2),
+                *[pointer(a) if gradient else None for a in outputs]))
+        return (ngal, chi2) + tuple(outputs)
+
+    def chi2_occupation(self, occupation, x, data, precision,
+                        extrapolate=False):
+        """``chi2 = (xi - data)^T precision (xi - data)`` of
+        `predict_occupation`, finished in the launch: ``ngal, chi2``
+        ``(n_draws, )``."""
+        return self._chi2_occupation(occupation, x, data, precision,
+                                     extrapolate, False)[:2]
+
+    def chi2_grad_occupation(self, occupation, x, data, precision,
+                             extrapolate=False):
+        """`chi2_occupation` with its gradient with respect to the occupation
+        array and the grid parameters -- `predict_vjp` with ``g_xi = 2 P_sym
+        (xi - data)``, ``P_sym = (precision + precision^T) / 2``, and
+        ``g_ngal = 0``, formed on the device from the interpolated ``xi`` in
+        the same launch.  For a likelihood with an ``ngal`` term ``dngal_dx``
+        comes with it, and ``dngal/docc`` needs no launch (`class_weights`).
+        Contracted with the caller's own ``d<N>/dtheta`` the results are the
+        gradient over ``(theta, x)`` for EVERY occupation model
+        (``examples/example_interp_custom_model_grad.py``: Leauthaud11).
+
+        Returns ``ngal, chi2 (n_draws, )``, ``dchi2_docc (n_draws, C,
+        n_bins)``, ``dchi2_dx`` and ``dngal_dx (n_draws, D)``.
+        """
+        return self._chi2_occupation(occupation, x, data, precision,
+                                     extrapolate, True)
+
     # -- generic models: host callbacks + device contraction per table -----------------
 
     def _spline_matrices(self):
