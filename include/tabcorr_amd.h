@@ -529,6 +529,38 @@ int tc_interp_chi2_grad_assembias_batch_device(tc_interp* interp, const double* 
                                                double* dngal_device, double* dchi2_device,
                                                double* fisher_device);
 
+/* The interpolator's gradients for the Leauthaud et al. (2011) family (as
+ * tc_predict_grad_leauthaud11_batch: theta (n_draws, 14), n_theta must be 14, flags 0 or
+ * TC_FLAG_MODULATE_WITH_CENOCC -- the family is implied, every other flag is
+ * TC_ERR_UNSUPPORTED): 11 + D columns, the eleven differentiated model parameters first -- dngal
+ * (n_draws, 11 + D), dxi (n_draws, 11 + D, n_r), dchi2 (n_draws, 11 + D), fisher (n_draws, 11 + D,
+ * 11 + D), which may be NULL.  The LDS budget: 12 for 6 quantities, 7 rows per central and 12 per
+ * satellite bin in mode auto; in mode cross one slab of 32 bins (12 x 33 rows with the totals)
+ * where the other families keep 64.  Grids of up to four dimensions (12 + D quantities per draw,
+ * of 16): beyond them TC_ERR_UNSUPPORTED. */
+int tc_interp_predict_grad_leauthaud11_batch(tc_interp* interp, const double* theta, int n_theta,
+                                             const double* x, int64_t n_draws, int n_gauss_prim,
+                                             unsigned flags, double* ngal, double* xi,
+                                             double* dngal, double* dxi);
+int tc_interp_predict_grad_leauthaud11_batch_device(tc_interp* interp, const double* theta_device,
+                                                    int n_theta, const double* x_device,
+                                                    int64_t n_draws, int n_gauss_prim,
+                                                    unsigned flags, double* ngal_device,
+                                                    double* xi_device, double* dngal_device,
+                                                    double* dxi_device);
+int tc_interp_chi2_grad_leauthaud11_batch(tc_interp* interp, const double* theta, int n_theta,
+                                          const double* x, int64_t n_draws, int n_gauss_prim,
+                                          unsigned flags, const double* data,
+                                          const double* precision, double* ngal, double* chi2,
+                                          double* dngal, double* dchi2, double* fisher);
+int tc_interp_chi2_grad_leauthaud11_batch_device(tc_interp* interp, const double* theta_device,
+                                                 int n_theta, const double* x_device,
+                                                 int64_t n_draws, int n_gauss_prim, unsigned flags,
+                                                 const double* data, const double* precision,
+                                                 double* ngal_device, double* chi2_device,
+                                                 double* dngal_device, double* dchi2_device,
+                                                 double* fisher_device);
+
 /* The occupation seam of an interpolator (extension): the interface for ANY occupation model.
  * The tables of an interpolator fall into n_classes classes of identical halo tables
  * (interpolator.py:63-70), numbered by first appearance in the list.  tc_interp_info: table_class

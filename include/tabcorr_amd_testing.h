@@ -39,10 +39,20 @@ int tc_debug_grad_operand(int n_bins, int n_r, const double* packed, double* den
 /* The LDS bytes per workgroup that the launch layer asks for and refuses by
  * (tabcorr_amd/csrc/grad.h): kernel 0 grad_auto_kernel, 1 grad_cross_kernel, 2
  * grad_interp_auto_kernel, 3 grad_interp_cross_kernel; n_params 5 (plain Zheng07), 7 (decorated
- * with assembly bias) or 11 (Leauthaud11: kernels 0 and 1 only); chi2: the likelihood is finished in the launch; n_dim: the interpolator's
+ * with assembly bias) or 11 (Leauthaud11: kernels 0 and 1 only, the interpolator's budget of every
+ * family is tc_debug_interp_grad_lds_bytes'); chi2: the likelihood is finished in the launch; n_dim: the interpolator's
  * axes (ignored by kernels 0 and 1, as n_bins and n_central are by 1 and 3). */
 int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n_r, int n_dim,
                       int chi2, int64_t* bytes);
+
+/* The LDS bytes per workgroup of the interpolator's gradient kernels (tabcorr_amd/csrc/grad.h:
+ * grad_interp_auto_lds_bytes, grad_interp_cross_lds_bytes) for every family: mode TC_MODE_AUTO or
+ * TC_MODE_CROSS, n_params 5, 7 or 11; for 5 and 7 what tc_debug_grad_lds(2 | 3, ...) returns.  In
+ * mode cross the slab holds 64 bins for 5 and 7 parameters and 32 for 11 (n_bins and n_central
+ * are ignored there).  TC_ERR_UNSUPPORTED for more axes than the family serves: n_params + 1 +
+ * n_dim quantities per draw must not exceed 16, which leaves 11 parameters four axes. */
+int tc_debug_interp_grad_lds_bytes(int mode, int n_params, int n_bins, int n_central, int n_r,
+                                   int n_dim, int chi2, int64_t* bytes);
 
 /* The slab arithmetic of the derivative entry points (tabcorr_amd/csrc/grad_call.h:
  * GradRequest::slab): the element offsets that the slab beginning at draw `begin` adds to the

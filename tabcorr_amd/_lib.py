@@ -62,6 +62,7 @@ SIGNATURES = {
                                  c_double_p],
     'tc_debug_grad_operand': [ctypes.c_int, ctypes.c_int, c_double_p, c_double_p],
     'tc_debug_grad_lds': [ctypes.c_int] * 7 + [c_int64_p],
+    'tc_debug_interp_grad_lds_bytes': [ctypes.c_int] * 7 + [c_int64_p],
     'tc_debug_grad_slab': [ctypes.c_int] * 4 + [ctypes.c_int64, c_int64_p],
     'tc_debug_sync_chunks': [ctypes.c_int64] * 3 + [c_int_p, ctypes.c_int, ctypes.c_uint,
                                                     c_int_p, c_int64_p, c_int_p],
@@ -285,7 +286,7 @@ SIGNATURES = {
 # trailing `fisher` that may be None.  A joint of interpolators takes x as an interpolator does.
 GRAD_ENTRIES = {}
 for _kind, _prefix, _families in (('table', 'tc_', ('zheng07', 'assembias', 'leauthaud11')),
-                                  ('interp', 'tc_interp_', ('zheng07', 'assembias')),
+                                  ('interp', 'tc_interp_', ('zheng07', 'assembias', 'leauthaud11')),
                                   ('joint', 'tc_joint_', (None, )),
                                   ('joint_interp', 'tc_joint_interp_', (None, ))):
     for _family in _families:

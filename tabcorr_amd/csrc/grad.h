@@ -38,6 +38,13 @@ constexpr int kGradDraws = 16;        // draws per workgroup: the N of one v_mfm
 constexpr int kGradWaves = 4;
 constexpr int kGradThreads = 64 * kGradWaves;
 constexpr int kGradCrossSlab = 64;    // mode cross: bins whose w and dw one LDS slab holds
+// ... of the INTERPOLATOR's cross kernel, a trait of the family: its LDS also keeps the products
+// of the class in flight and the accumulators, (2 (n_params + 1 + n_dim), n_r) rows, and with the
+// twelve quantities of the Leauthaud11 family a slab of 64 bins (98 KB) would leave no room for the
+// 14 r bins of a grid of three dimensions.  Half the slab does (126 KB).
+constexpr int grad_interp_cross_slab(int n_params) {
+  return n_params == kGradParamsLeauthaud11 ? 32 : kGradCrossSlab;
+}
 
 struct GradArgs {
   // (n_draws, 5) -- 7 wherever 5 stands below, decorated; Leauthaud11: (n_draws, 14), and 11
@@ -163,8 +170,8 @@ constexpr int kGradMaxAxis = kMaxInterpAxis;
 struct GradInterpArgs {
   // theta, the sizes, the flags, math_table, row_tiles / k_steps and the result arrays as for one
   // table: dngal (n_draws, 5 + n_dim), dxi (n_draws, 5 + n_dim, n_r), dchi2 (n_draws, 5 + n_dim),
-  // the five Zheng07 parameters first.  log_m, m, weight, n_h and matrix are set per class and
-  // per table by the kernel.
+  // the five Zheng07 parameters first (7 decorated, 11 of the Leauthaud11 family for 5).  log_m,
+  // m, weight, n_h and matrix are set per class and per table by the kernel.
   GradArgs table;
   const double* x;                    // (n_draws, n_dim)
   int n_dim;
@@ -183,12 +190,23 @@ struct GradInterpArgs {
   const double* const* class_m;
   const double* const* class_weight;
   const double* const* class_n_h;
-  const double* const* class_percentile;   // decorated only
+  const double* const* class_percentile;   // decorated only; else NULL
 };
+
+// The axes an interpolator may have for the family: both kernels finish ngal, chi2 and their
+// derivatives with one thread per (quantity, draw), kGradThreads / kGradDraws = 16 quantities at
+// the most, of which the family takes n_params + 1 -- every grid tc_interp_create admits for 5 and
+// 7 parameters, four axes for the eleven of the Leauthaud11 family.
+constexpr int grad_interp_max_dim(int n_params) {
+  return kGradThreads / kGradDraws - (n_params + 1) < kGradMaxDim
+             ? kGradThreads / kGradDraws - (n_params + 1)
+             : kGradMaxDim;
+}
 
 // LDS rows of kGradDraws doubles that both interpolator kernels keep: the weights and derivative
 // weights of every axis, and the (6 + n_dim) accumulators of xi per r bin ((8 + n_dim) where
-// decorated).  The likelihood is finished in the accumulators themselves (`chi2` costs nothing).
+// decorated, (12 + n_dim) for the Leauthaud11 family).  The likelihood is finished in the
+// accumulators themselves (`chi2` costs nothing).
 constexpr size_t grad_interp_common_rows(int n_r, int n_dim, int n_params = kGradParams) {
   return 2 * (size_t)n_dim * kGradMaxAxis + (size_t)(n_params + 1 + n_dim) * n_r;
 }
@@ -199,11 +217,11 @@ constexpr size_t grad_interp_auto_lds_bytes(int n_bins, int n_central, int n_r, 
           grad_interp_common_rows(n_r, n_dim, n_params)) *
          kGradDraws * sizeof(double);
 }
-// grad_interp_cross_kernel: one slab, the totals and the weighted products (6 + n_dim, n_r) of
-// the class in flight.
+// grad_interp_cross_kernel: one slab (of the family's length: grad_interp_cross_slab), the totals
+// and the weighted products (6 + n_dim, n_r) of the class in flight.
 constexpr size_t grad_interp_cross_lds_bytes(int n_r, int n_dim, bool /* chi2 */,
                                              int n_params = kGradParams) {
-  return ((size_t)(n_params + 1) * ((size_t)kGradCrossSlab + 1) +
+  return ((size_t)(n_params + 1) * ((size_t)grad_interp_cross_slab(n_params) + 1) +
           (size_t)(n_params + 1 + n_dim) * n_r + grad_interp_common_rows(n_r, n_dim, n_params)) *
          kGradDraws * sizeof(double);
 }

@@ -55,12 +55,14 @@ __device__ __forceinline__ f64x4 dense_tile_product(const double* a_lane, int st
   return u;
 }
 
-// sum + T_r[slab] . (quantity p of the slab) for one draw, in bin order.
+// sum + T_r[slab] . (quantity p of the slab) for one draw, in bin order.  SLAB: the bins the
+// slab (quantities, SLAB, 16) at w is laid out for.
+template <int SLAB = kGradCrossSlab>
 __device__ __forceinline__ double cross_slab_product(const double* matrix, int n_r, int r,
                                                      int slab0, int count, const double* w, int p,
                                                      int col, double sum) {
   const double* column = matrix + (size_t)slab0 * n_r + r;
-  const double* rows = w + (size_t)p * kGradCrossSlab * kGradDraws + col;
+  const double* rows = w + (size_t)p * SLAB * kGradDraws + col;
   for (int li = 0; li < count; ++li)
     sum = fma(column[(size_t)li * n_r], rows[li * kGradDraws], sum);
   return sum;

@@ -18,7 +18,8 @@
 //      the Fisher matrix over the same 5 + n_dim quantities.
 // The order of every sum -- tables, rows, slabs -- is fixed by the interpolator: a draw's results
 // do not depend on the batch or on the draw's neighbours.
-// NP as in grad_kernels.hip.h: 5, or 7 for the decorated model, where "6" reads 8 and "5" 7.
+// NP as in grad_kernels.hip.h: 5, or 7 for the decorated model, where "6" reads 8 and "5" 7, or
+// 11 for the Leauthaud11 family (theta then has 14 columns), where they read 12 and 11.
 #pragma once
 
 #include "grad_kernels.hip.h"
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_auto_kernel(const Gr
     grad::set_class(a, ia, v);
     __syncthreads();
     {
-      const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+      const typename grad::DrawOf<NP>::type d = grad::load_draw<NP>(a, k, draw0 + col);
       grad::auto_node_loops<NP>(a, k, d, w, zero_row);
     }
     __syncthreads();
@@ -176,9 +177,11 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_auto_kernel(const Gr
 // Inside a class xi_t = T_t . w / ngal shares w and ngal, so the class is linear in the slab
 // products: Y_q = sum_t coef_{t,q} T_t . (w or dw_q) accumulates over slabs and tables, the chain
 // rule of grad_cross_kernel is applied once per class and the class added to the accumulators.
+// The slab holds grad_interp_cross_slab(NP) bins (grad.h).
 template <int NP>
 __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const GradInterpArgs ia) {
   constexpr int NQ = NP + 1;
+  constexpr int kSlab = grad_interp_cross_slab(NP);
   extern __shared__ double grad_lds[];
   GradArgs a = ia.table;
   const int t = threadIdx.x;
@@ -188,12 +191,12 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
   const int n_q = NQ + n_dim;
   const int n_items = n_q * n_r * kGradDraws;
   double* w = grad_lds;                                               // (6, slab, 16)
-  double* total = w + NQ * kGradCrossSlab * kGradDraws;                // (6, 16), one class
+  double* total = w + NQ * kSlab * kGradDraws;                         // (6, 16), one class
   double* weights = total + NQ * kGradDraws;                           // (2, n_dim, 32, 16)
   double* y = weights + (size_t)2 * n_dim * kGradMaxAxis * kGradDraws;      // (n_q, n_r, 16), one class
   double* sums = y + n_items;                                         // (n_q, n_r, 16)
   const fm::Consts k = fm::make_consts();
-  const grad::Draw d = grad::load_draw<NP>(a, k, draw0 + col);
+  const typename grad::DrawOf<NP>::type d = grad::load_draw<NP>(a, k, draw0 + col);
   grad::interp_weights(ia, draw0, weights);
   for (int item = t; item < n_items; item += kGradThreads) sums[item] = 0.0;
   double my_ngal = 0.0;                                               // thread = (q, draw)
@@ -203,14 +206,14 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
     __syncthreads();
     for (int item = t; item < n_items; item += kGradThreads) y[item] = 0.0;
     double my_total = 0.0;
-    for (int slab0 = 0; slab0 < n_bins; slab0 += kGradCrossSlab) {
-      const int count = min(kGradCrossSlab, n_bins - slab0);
+    for (int slab0 = 0; slab0 < n_bins; slab0 += kSlab) {
+      const int count = min(kSlab, n_bins - slab0);
       __syncthreads();
-      grad::cross_node_loops<NP>(a, k, d, slab0, count, w);
+      grad::cross_node_loops<NP, kSlab>(a, k, d, slab0, count, w);
       __syncthreads();
       if (t < NQ * kGradDraws) {
         const int p = t / kGradDraws;
-        for (int li = 0; li < count; ++li) my_total += w[(p * kGradCrossSlab + li) * kGradDraws + col];
+        for (int li = 0; li < count; ++li) my_total += w[(p * kSlab + li) * kGradDraws + col];
       }
       for (int s = s_begin; s < s_end; ++s) {
         const int32_t* node = ia.walk_node + (size_t)s * n_dim;
@@ -220,7 +223,7 @@ __global__ __launch_bounds__(kGradThreads) void grad_interp_cross_kernel(const G
         for (int item = t; item < NQ * n_r * kGradDraws; item += kGradThreads) {
           const int r = item / (NQ * kGradDraws), p = item / kGradDraws % NQ;
           const double product =
-              grad::cross_slab_product(matrix, n_r, r, slab0, count, w, p, col, 0.0);
+              grad::cross_slab_product<kSlab>(matrix, n_r, r, slab0, count, w, p, col, 0.0);
           const size_t stride = (size_t)n_r * kGradDraws;
           double* slot = y + (size_t)r * kGradDraws + col;
           slot[p * stride] = fma(grad::interp_coef(ia, weights, node, 0, col), product,

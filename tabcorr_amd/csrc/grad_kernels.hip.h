@@ -469,8 +469,8 @@ __device__ __forceinline__ double cross_dxi(double y, double xi, double dngal, d
 
 // ---- the pieces of grad_cross_kernel ------------------------------------------------------------
 
-// w and dw of the bins slab0 .. slab0 + count - 1 into the slab (6, kGradCrossSlab, 16).
-template <int NP>
+// w and dw of the bins slab0 .. slab0 + count - 1 into the slab (6, SLAB, 16).
+template <int NP, int SLAB = kGradCrossSlab>
 __device__ __forceinline__ void cross_node_loops(const GradArgs& a, const fm::Consts& k,
                                                  const typename DrawOf<NP>::type& d, int slab0,
                                                  int count, double* w) {
@@ -480,7 +480,7 @@ __device__ __forceinline__ void cross_node_loops(const GradArgs& a, const fm::Co
     double out[NP + 1];
     bin_values<NP>(a, k, d, slab0 + li, out);
 #pragma unroll
-    for (int p = 0; p < NP + 1; ++p) w[(p * kGradCrossSlab + li) * kGradDraws + col] = out[p];
+    for (int p = 0; p < NP + 1; ++p) w[(p * SLAB + li) * kGradDraws + col] = out[p];
   }
 }
 

@@ -1042,6 +1042,12 @@ struct InterpGrad {
     const tc_table* t0 = it->tables[0];
     const int status = check_grad_args(t0, request, n_theta, likelihood, /*fit=*/true);
     if (status != TC_OK) return status;
+    if (it->n_dim > tc::grad_interp_max_dim(request.n_params))
+      return fail(TC_ERR_UNSUPPORTED,
+                  "gradients of %d parameters: a grid of %d dimensions, beyond the %d that the "
+                  "kernels' %d quantities per draw leave room for",
+                  request.n_params, it->n_dim, tc::grad_interp_max_dim(request.n_params),
+                  tc::kGradThreads / tc::kGradDraws);
     const size_t lds = interp_grad_lds(it, likelihood, request.n_params);
     if (lds > (size_t)kMaxLdsBytes)
       return fail(TC_ERR_UNSUPPORTED,
@@ -1297,6 +1303,58 @@ int tc_interp_chi2_grad_assembias_batch(tc_interp* it, const double* theta, int 
   return grad_entry(InterpGrad{it}, GradRoute::kHost,
                     interp_request(it, tc::kGradParamsAssembias, theta, x, n_draws, n_gauss, flags,
                                    ngal, chi2, dngal, dchi2, fisher),
+                    n_theta, &operands, false);
+}
+
+// ---- the Leauthaud11 family (fourteen columns of theta, eleven differentiated, then the n_dim
+// extra parameters; `fisher` may be NULL) ----
+
+int tc_interp_predict_grad_leauthaud11_batch_device(tc_interp* it, const double* theta_device,
+                                                    int n_theta, const double* x_device,
+                                                    int64_t n_draws, int n_gauss, unsigned flags,
+                                                    double* ngal_device, double* xi_device,
+                                                    double* dngal_device, double* dxi_device) {
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParamsLeauthaud11, theta_device, x_device, n_draws,
+                                   n_gauss, flags, ngal_device, xi_device, dngal_device,
+                                   dxi_device, nullptr),
+                    n_theta, nullptr, false);
+}
+
+int tc_interp_predict_grad_leauthaud11_batch(tc_interp* it, const double* theta, int n_theta,
+                                             const double* x, int64_t n_draws, int n_gauss,
+                                             unsigned flags, double* ngal, double* xi,
+                                             double* dngal, double* dxi) {
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParamsLeauthaud11, theta, x, n_draws, n_gauss,
+                                   flags, ngal, xi, dngal, dxi, nullptr),
+                    n_theta, nullptr, false);
+}
+
+int tc_interp_chi2_grad_leauthaud11_batch_device(tc_interp* it, const double* theta_device,
+                                                 int n_theta, const double* x_device,
+                                                 int64_t n_draws, int n_gauss, unsigned flags,
+                                                 const double* data, const double* precision,
+                                                 double* ngal_device, double* chi2_device,
+                                                 double* dngal_device, double* dchi2_device,
+                                                 double* fisher_device) {
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kDevice,
+                    interp_request(it, tc::kGradParamsLeauthaud11, theta_device, x_device, n_draws,
+                                   n_gauss, flags, ngal_device, chi2_device, dngal_device,
+                                   dchi2_device, fisher_device),
+                    n_theta, &operands, false);
+}
+
+int tc_interp_chi2_grad_leauthaud11_batch(tc_interp* it, const double* theta, int n_theta,
+                                          const double* x, int64_t n_draws, int n_gauss,
+                                          unsigned flags, const double* data,
+                                          const double* precision, double* ngal, double* chi2,
+                                          double* dngal, double* dchi2, double* fisher) {
+  const Chi2Host operands{data, precision};
+  return grad_entry(InterpGrad{it}, GradRoute::kHost,
+                    interp_request(it, tc::kGradParamsLeauthaud11, theta, x, n_draws, n_gauss,
+                                   flags, ngal, chi2, dngal, dchi2, fisher),
                     n_theta, &operands, false);
 }
 

@@ -1265,6 +1265,9 @@ int launch_grad_instance(int n_params, int mode, int device, dim3 grid, int lds,
     case tc::kGradParamsAssembias:
       return launch_grad_family<tc::kGradParamsAssembias>(mode, device, grid, lds, stream, k0, k1,
                                                           ga);
+    case tc::kGradParamsLeauthaud11:
+      return launch_grad_family<tc::kGradParamsLeauthaud11>(mode, device, grid, lds, stream, k0,
+                                                            k1, ga);
   }
   return no_grad_family(n_params);
 }

@@ -541,7 +541,8 @@ int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n
   TC_CHECK(n_params == tc::kGradParams || n_params == tc::kGradParamsAssembias || leauthaud,
            "n_params must be %d, %d or %d", tc::kGradParams, tc::kGradParamsAssembias,
            tc::kGradParamsLeauthaud11);
-  TC_CHECK(!leauthaud || kernel <= 1, "the Leauthaud11 family has no interpolator kernels");
+  TC_CHECK(!leauthaud || kernel <= 1,
+           "the Leauthaud11 family's interpolator kernels: see tc_debug_interp_grad_lds_bytes");
   TC_CHECK(n_bins >= n_central && n_central >= 0 && n_r >= 0 && n_dim >= 0, "invalid sizes");
   const size_t sizes[4] = {
       tc::grad_auto_lds_bytes(n_bins, n_central, n_r, chi2 != 0, n_params),
@@ -549,6 +550,27 @@ int tc_debug_grad_lds(int kernel, int n_params, int n_bins, int n_central, int n
       tc::grad_interp_auto_lds_bytes(n_bins, n_central, n_r, n_dim, chi2 != 0, n_params),
       tc::grad_interp_cross_lds_bytes(n_r, n_dim, chi2 != 0, n_params)};
   *bytes = (int64_t)sizes[kernel];
+  return TC_OK;
+}
+
+int tc_debug_interp_grad_lds_bytes(int mode, int n_params, int n_bins, int n_central, int n_r,
+                                   int n_dim, int chi2, int64_t* bytes) {
+  TC_CHECK(bytes != nullptr, "bytes is NULL");
+  TC_CHECK(mode == TC_MODE_AUTO || mode == TC_MODE_CROSS, "mode must be auto or cross");
+  TC_CHECK(n_params == tc::kGradParams || n_params == tc::kGradParamsAssembias ||
+               n_params == tc::kGradParamsLeauthaud11,
+           "n_params must be %d, %d or %d", tc::kGradParams, tc::kGradParamsAssembias,
+           tc::kGradParamsLeauthaud11);
+  TC_CHECK(n_bins >= n_central && n_central >= 0 && n_r >= 0 && n_dim >= 0 &&
+               n_dim <= tc::kGradMaxDim,
+           "invalid sizes");
+  if (n_dim > tc::grad_interp_max_dim(n_params))
+    return fail(TC_ERR_UNSUPPORTED, "gradients of %d parameters serve grids of up to %d dimensions",
+                n_params, tc::grad_interp_max_dim(n_params));
+  *bytes = (int64_t)(mode == TC_MODE_AUTO
+                         ? tc::grad_interp_auto_lds_bytes(n_bins, n_central, n_r, n_dim, chi2 != 0,
+                                                          n_params)
+                         : tc::grad_interp_cross_lds_bytes(n_r, n_dim, chi2 != 0, n_params));
   return TC_OK;
 }
 

@@ -25,7 +25,8 @@ from . import _lib
 from .galtable import GalTypeTable
 from .models import device_spec
 from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _chi2_operands, _flags,
-                      _grad_keys, _grad_spec, _grad_theta, _unbatch)
+                      _grad_keys, _grad_spec, _grad_theta,
+                      _leauthaud11_columns, _unbatch)
 
 OUT_OF_RANGE = ('The x-coordinates are outside of the interpolation ' +
                 'range and extrapolation is turned off.')
@@ -386,11 +387,13 @@ class Interpolator:
 
     # -- analytic gradients ----------------------------------------------------------
 
-    def _grad_inputs(self, theta, x, extrapolate, assembias=False):
+    def _grad_inputs(self, theta, x, extrapolate, assembias=False,
+                     family='zheng07'):
         """``theta (n, 5)`` -- ``(n, 7)`` for the model decorated with
-        assembly bias -- and ``x (n, D)`` of the gradient calls, checked
-        before any device is touched."""
-        theta = _grad_theta(theta, assembias)
+        assembly bias, ``(n, 14)`` for the Leauthaud11 family -- and
+        ``x (n, D)`` of the gradient calls, checked before any device is
+        touched."""
+        theta = _grad_theta(theta, assembias, family)
         x = _lib.contiguous(np.atleast_2d(x))
         if x.shape != (len(theta), len(self.keys)):
             raise ValueError('x must have shape (n_draws, {}).'.format(
@@ -399,7 +402,8 @@ class Interpolator:
         return theta, x
 
     def predict_batch_grad(self, theta, x, n_gauss_prim=10, extrapolate=False,
-                           modulate_with_cenocc=False, assembias=False):
+                           modulate_with_cenocc=False, assembias=False,
+                           family='zheng07'):
         """`predict_batch` together with the exact derivatives of its results
         with respect to the five Zheng07 parameters and the ``D`` extra
         parameters (columns: `ZHENG07_KEYS`, then ``self.keys``), in one
@@ -420,6 +424,13 @@ class Interpolator:
         carry the 7 columns of `ZHENG07_ASSEMBIAS_KEYS` (7 wherever 5 stands
         below), then ``self.keys``.
 
+        ``family='leauthaud11'``: ``theta`` has the 14 columns
+        ``predict_batch(..., family='leauthaud11')`` takes, and the
+        derivatives carry the eleven columns of
+        `tabcorr_amd.models.LEAUTHAUD11_GRAD_KEYS` (threshold, h and h_s are
+        inputs), then ``self.keys``: 11 wherever 5 stands below.  Not
+        together with ``assembias``.
+
         Returns
         -------
         ngal : ``(n_draws, )``
@@ -430,28 +441,29 @@ class Interpolator:
         Raises ``NotImplementedError`` for what the kernel does not serve
         (float32 tables, grids whose rows do not fit the LDS of a workgroup).
         """
-        theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
+        theta, x = self._grad_inputs(theta, x, extrapolate, assembias, family)
         return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
-                               assembias)
+                               assembias, family)
 
     def _grad_call(self, theta, x, n_gauss_prim, modulate_with_cenocc,
-                   assembias, operands=None, want_fisher=False):
+                   assembias, family, operands=None, want_fisher=False):
         """The derivative entry for checked ``(theta, x)``: the family's
         columns, then ``self.keys``."""
         return _grad.call(
-            self.to_device(), 'interp', _grad.family_of(assembias),
+            self.to_device(), 'interp', _grad.family_of(assembias, family),
             [theta, theta.shape[1], x, len(theta), n_gauss_prim,
              _flags(False, modulate_with_cenocc)],
-            theta.shape[1] + len(self.keys), self.tabcorr_list[0].tpcf_shape,
-            operands, want_fisher)
+            len(_grad_keys(assembias, family)) + len(self.keys),
+            self.tabcorr_list[0].tpcf_shape, operands, want_fisher)
 
     def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
                         extrapolate=False, modulate_with_cenocc=False,
-                        assembias=False):
+                        assembias=False, family='zheng07'):
         """`chi2_batch` with its gradient with respect to ``(theta, x)``:
         ``dchi2[:, k] = 2 (xi - data)^T P_sym dxi_k`` with ``P_sym =
         (precision + precision^T) / 2``, finished on the device in the launch
-        that computes ``xi``.  ``assembias=True``: ``7 + D`` columns, as in
+        that computes ``xi``.  ``assembias=True``: ``7 + D`` columns,
+        ``family='leauthaud11'``: ``11 + D`` (of 14 theta columns), as in
         `predict_batch_grad`.
 
         Returns
@@ -459,11 +471,11 @@ class Interpolator:
         ngal, chi2 : ``(n_draws, )``
         dngal, dchi2 : ``(n_draws, 5 + D)``
         """
-        theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
+        theta, x = self._grad_inputs(theta, x, extrapolate, assembias, family)
         operands = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
         return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
-                               assembias, operands)
+                               assembias, family, operands)
 
     def predict_grad(self, model, n_gauss_prim=10, extrapolate=False,
                      check_consistency=True, assembias=False):
@@ -471,7 +483,11 @@ class Interpolator:
         `tabcorr_amd.Zheng07Model` (or the halotools zheng07 composite model)
         whose ``param_dict`` holds the extra parameters; with
         ``assembias=True`` a decorated one, the dicts then keyed by
-        ``ZHENG07_ASSEMBIAS_KEYS + tuple(self.keys)``.
+        ``ZHENG07_ASSEMBIAS_KEYS + tuple(self.keys)``.  A
+        `tabcorr_amd.Leauthaud11Model` is served too: the dicts are then keyed
+        by the sixteen `LEAUTHAUD11_KEYS` of its ``param_dict``, then
+        ``self.keys``, the eleven device columns carried to the sixteen by
+        `Leauthaud11Model.device_jacobian` as in `TabCorr.predict_grad`.
 
         Returns
         -------
@@ -484,7 +500,17 @@ class Interpolator:
         if check_consistency:
             for halotab in self.tabcorr_list:
                 halotab._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'predict_grad')
+        spec = _grad_spec(model, assembias, 'predict_grad', leauthaud11=True)
+        if spec.family == 'leauthaud11':
+            ngal, xi, dngal, dxi = self.predict_batch_grad(
+                spec.theta[np.newaxis], x[np.newaxis],
+                n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
+                modulate_with_cenocc=spec.modulate_with_cenocc,
+                family='leauthaud11')
+            columns = self._leauthaud11_columns(model)
+            return (float(ngal[0]), xi[0],
+                    _grad.keyed(dngal[0], columns=columns),
+                    _grad.keyed(dxi[0], columns=columns))
         model_keys = tuple(_grad_keys(assembias))
         ngal, xi, dngal, dxi = self.predict_batch_grad(
             np.asarray(spec.theta,
@@ -496,11 +522,22 @@ class Interpolator:
         return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], keys),
                 _grad.keyed(dxi[0], keys))
 
+    def _leauthaud11_columns(self, model):
+        """`LEAUTHAUD11_KEYS`, then ``self.keys`` -> (device column, factor)
+        among the ``11 + D`` columns of the Leauthaud11 family's calls: the
+        model's sixteen as `tabcorr._leauthaud11_columns` has them, the extra
+        parameters their own."""
+        columns = _leauthaud11_columns(model)
+        n_model = len(_grad_keys(family='leauthaud11'))
+        for d, key in enumerate(self.keys):
+            columns[key] = (n_model + d, 1.0)
+        return columns
+
     # -- Fisher matrix of the likelihood ------------------------------------------------
 
     def chi2_fisher_batch(self, theta, x, data, precision, n_gauss_prim=10,
                           extrapolate=False, modulate_with_cenocc=False,
-                          assembias=False):
+                          assembias=False, family='zheng07'):
         """`chi2_grad_batch` with the Fisher matrix of the likelihood over
         ``(theta, x)``, from the same launch: with ``dxi_k`` the Jacobian
         column of quantity ``k`` (`ZHENG07_KEYS`, then ``self.keys``),
@@ -514,7 +551,9 @@ class Interpolator:
         ``dngal`` is returned next to ``fisher``, and an outer product
         completes it.  The matrix is symmetric to the bit; a draw's matrix
         does not depend on its batch, and not on ``data``.
-        ``assembias=True``: ``7 + D`` columns, as in `predict_batch_grad`.
+        ``assembias=True``: ``7 + D`` columns, ``family='leauthaud11'``:
+        ``11 + D`` columns and an ``(11 + D, 11 + D)`` matrix, as in
+        `predict_batch_grad`.
 
         Returns
         -------
@@ -523,15 +562,15 @@ class Interpolator:
             for bit
         fisher : ``(n_draws, 5 + D, 5 + D)``
         """
-        theta, x = self._grad_inputs(theta, x, extrapolate, assembias)
+        theta, x = self._grad_inputs(theta, x, extrapolate, assembias, family)
         operands = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
         return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
-                               assembias, operands, True)
+                               assembias, family, operands, True)
 
     def fisher_batch(self, theta, x, precision, n_gauss_prim=10,
                      extrapolate=False, modulate_with_cenocc=False,
-                     assembias=False):
+                     assembias=False, family='zheng07'):
         """The forecast form of `chi2_fisher_batch`, which needs no data: the
         same launch with a zero data vector, without ``chi2`` and ``dchi2``.
         The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal`` part of
@@ -546,7 +585,8 @@ class Interpolator:
         ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
             theta, x, np.zeros(len(self.tabcorr_list[0].tpcf_matrix)),
             precision, n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias)
+            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
+            family=family)
         return ngal, dngal, fisher
 
     def fisher(self, model, precision, n_gauss_prim=10, extrapolate=False,
@@ -557,7 +597,12 @@ class Interpolator:
         takes.  The Gauss-Newton Hessian of chi2 is ``2 fisher``; the ``ngal``
         part of a likelihood is the caller's, from ``dngal`` by an outer
         product.  ``assembias=True``: a decorated model and
-        ``ZHENG07_ASSEMBIAS_KEYS + tuple(self.keys)``.
+        ``ZHENG07_ASSEMBIAS_KEYS + tuple(self.keys)``.  A
+        `tabcorr_amd.Leauthaud11Model`: `LEAUTHAUD11_KEYS`, then
+        ``self.keys``, and the ``(16 + D, 16 + D)`` matrix ``J^T F J`` with
+        ``F`` the ``(11 + D, 11 + D)`` matrix of the device columns and ``J``
+        the block-diagonal matrix of `Leauthaud11Model.device_jacobian` and
+        the identity of the extra parameters.
 
         Returns
         -------
@@ -569,7 +614,22 @@ class Interpolator:
         if check_consistency:
             for halotab in self.tabcorr_list:
                 halotab._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'fisher')
+        spec = _grad_spec(model, assembias, 'fisher', leauthaud11=True)
+        if spec.family == 'leauthaud11':
+            ngal, dngal, fisher = self.fisher_batch(
+                spec.theta[np.newaxis], x[np.newaxis], precision,
+                n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
+                modulate_with_cenocc=spec.modulate_with_cenocc,
+                family='leauthaud11')
+            own = model.device_jacobian()
+            n_dim = len(self.keys)
+            jacobian = np.zeros((own.shape[0] + n_dim, own.shape[1] + n_dim))
+            jacobian[:own.shape[0], :own.shape[1]] = own
+            jacobian[own.shape[0]:, own.shape[1]:] = np.eye(n_dim)
+            return (float(ngal[0]),
+                    _grad.keyed(dngal[0],
+                                columns=self._leauthaud11_columns(model)),
+                    jacobian.T @ fisher[0] @ jacobian)
         model_keys = tuple(_grad_keys(assembias))
         ngal, dngal, fisher = self.fisher_batch(
             np.asarray(spec.theta,
