@@ -134,6 +134,33 @@ struct VjpRequest {
   }
 };
 
+// Which arrays a call at the occupation seam must bring, as a handle kind states it.  The adjoint
+// arrays of a request are g_xi and g_occupation (the likelihood form: g_occupation, there
+// dchi2_docc, alone) and, with_x, g_x (the likelihood form: and dngal_dx).
+struct VjpRule {
+  bool with_x;               // an interpolator: x is required, its adjoints belong to the group
+  bool forward_only;         // the adjoint arrays all NULL is a form of its own (not a table's)
+  const char* together[2];   // what a mixed set is told: the prediction, the likelihood form
+};
+
+// NULL where `request` (operands: the likelihood's are there, or it is the prediction form) is
+// complete under `rule`, else the words of the refusal.
+inline const char* vjp_incomplete(const VjpRule& rule, const VjpRequest& request, bool likelihood,
+                                  bool operands) {
+  const void* value = likelihood ? (const void*)request.chi2 : request.xi;
+  if (!(request.occupation && request.ngal && value && operands && (!rule.with_x || request.x)))
+    return "NULL pointer";
+  const void* group[4];
+  int n = 0, given = 0;
+  if (!likelihood) group[n++] = request.g_xi;
+  group[n++] = request.g_occupation;
+  if (rule.with_x) group[n++] = request.g_x;
+  if (rule.with_x && likelihood) group[n++] = request.dngal_dx;
+  for (int k = 0; k < n; ++k) given += group[k] != nullptr;
+  if (given == n || (given == 0 && rule.forward_only)) return nullptr;
+  return rule.forward_only ? rule.together[likelihood] : "NULL pointer";
+}
+
 // The element offsets that slab `begin` adds to the seven arrays of a request of this shape --
 // theta, x, ngal, dngal, value, dvalue, fisher; -1: the request has no such array -- read off
 // slab() itself (tc_debug_grad_slab; tools/sanitize/host_driver.cpp).
@@ -218,13 +245,13 @@ int grad_slabs(tc_table* t, GradLane request, int64_t n_draws, Run run) {
   return TC_OK;
 }
 
-// A call at the occupation seam on device pointers, on a lane of `t` (a joint: its first table):
-// run(slab, stream) for every slab of the batch, one launch each.
+// A call at the occupation seam on device pointers, on a stream the handle chose itself (an
+// interpolator's lanes; a table's go through grad_slabs): run(slab) for every slab of at most `max`
+// draws.
 template <typename Run>
-int vjp_device(tc_table* t, GradLane lane, const VjpRequest& request, Run run) {
-  return grad_slabs(t, lane, request.n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
-    return run(request.slab(begin, n), stream);
-  });
+int vjp_slabs(const VjpRequest& request, int64_t max, Run run) {
+  return for_each_slab(request.n_draws, max,
+                       [&](int64_t begin, int64_t n) { return run(request.slab(begin, n)); });
 }
 
 // The buffers a host-array call at the occupation seam is staged through, the stream of its
@@ -302,18 +329,6 @@ int vjp_host_arrays(const VjpStaging& stage, const VjpRequest& request, Device d
   });
 }
 
-// ... of a table (a joint: its first table), on its lane 0.
-template <typename Run>
-int vjp_host(tc_table* t, const VjpRequest& request, Run run) {
-  TC_HIP(hipSetDevice(t->device));
-  int stopped = TC_OK;
-  if (t->resident.running && (stopped = resident_stop(t)) != TC_OK) return stopped;
-  const VjpStaging stage{&t->occupation, &t->out_ngal, &t->out_xi, t->stream, max_slab(t)};
-  return vjp_host_arrays(stage, request, [&](const VjpRequest& staged) {
-    return vjp_device(t, GradLane::kPinned, staged, run);
-  });
-}
-
 // The buffers of a handle that a host-array call is staged through, and the stream of its copies.
 struct GradStaging {
   DeviceBuffer* theta;
@@ -372,8 +387,10 @@ int grad_host_arrays(const GradStaging& stage, const GradRequest& request, Devic
 // has a Fisher matrix among its outputs, which then must not be NULL.  A handle kind supplies
 //   check(request, n_theta, likelihood)   what it refuses, the NULL handle first
 //   null_message(likelihood)              the words of its NULL-pointer refusal
-//   device_id(), operands(), drain()      its device; its operand cache and the wait for everything
-//                                         that may still read the cache's old values
+//   device_id(), operands()               its device; its operand cache
+//   upload_chi2(host)                     the operands' way up, behind the wait for everything
+//                                         that may still read the old values (the three in one
+//                                         base per kind: its gradient, seam and forward calls)
 //   staging()                             the buffers and the stream of its host-array calls
 //   device(lane, request)                 the launches of a request on device pointers
 template <typename Adapter>
@@ -391,13 +408,41 @@ int grad_entry(Adapter adapter, GradRoute where, GradRequest request, int n_thet
   TC_CHECK(complete, "%s", adapter.null_message(likelihood));
   TC_HIP(hipSetDevice(adapter.device_id()));
   if (likelihood) {
-    status = adapter.operands().upload(request.n_r, operands->data, operands->precision,
-                                       adapter.staging().stream, [&] { return adapter.drain(); });
-    if (status != TC_OK) return status;
+    if ((status = adapter.upload_chi2(*operands)) != TC_OK) return status;
     request.chi2_data = adapter.operands().device();
   }
   if (where == GradRoute::kDevice) return adapter.device(GradLane::kNext, request);
   return grad_host_arrays(adapter.staging(), request, [&](const GradRequest& staged) {
+    return adapter.device(GradLane::kPinned, staged);
+  });
+}
+
+// Every entry point at the occupation seam, in grad_entry's sequence: `request` as the caller
+// stated it (chi2_data not yet known) and, for the likelihood form, its operands on the host.  A
+// handle kind supplies, next to its base,
+//   check(n_draws, flags)                 what it refuses, the NULL handle first
+//   rule()                                which arrays it needs (VjpRule)
+//   staging()                             the buffers of its host-array calls (VjpStaging)
+//   device(lane, request)                 everything of its own: the resident kernels stop, the
+//                                         gradient tables or the walk are built, the argument block
+//                                         is filled, the lane is chosen, the slabs are launched
+template <typename Adapter>
+int vjp_entry(Adapter adapter, GradRoute where, unsigned flags, VjpRequest request,
+              const Chi2Host* operands) {
+  const bool likelihood = operands != nullptr;
+  int status = adapter.check(request.n_draws, flags);
+  if (status != TC_OK) return status;
+  if (request.n_draws == 0) return TC_OK;
+  const char* missing = vjp_incomplete(adapter.rule(), request, likelihood,
+                                       !likelihood || (operands->data && operands->precision));
+  TC_CHECK(missing == nullptr, "%s", missing);
+  TC_HIP(hipSetDevice(adapter.device_id()));
+  if (likelihood) {
+    if ((status = adapter.upload_chi2(*operands)) != TC_OK) return status;
+    request.chi2_data = adapter.operands().device();
+  }
+  if (where == GradRoute::kDevice) return adapter.device(GradLane::kNext, request);
+  return vjp_host_arrays(adapter.staging(), request, [&](const VjpRequest& staged) {
     return adapter.device(GradLane::kPinned, staged);
   });
 }

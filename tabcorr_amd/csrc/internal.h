@@ -934,3 +934,5 @@ int copy_out(PinnedBuffer* stage, double* ngal, size_t ngal_count, const void* d
 
 // (behind the handles: the request of a derivative call, its staging path and its entry sequence)
 #include "grad_call.h"
+// (... and the forward calls of the two joints)
+#include "joint_forward_call.h"

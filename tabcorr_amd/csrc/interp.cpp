@@ -1032,9 +1032,18 @@ void fill_interp_grid(const tc_interp* it, tc::GradInterpArgs* ga) {
   ga->matrices = (const double* const*)it->grad_walk.matrices;
 }
 
-// An interpolator as grad_entry sees it.
-struct InterpGrad {
+// What the derivative entries of an interpolator share (grad_call.h: grad_entry, vjp_entry).
+struct InterpHandle {
   tc_interp* it;
+  int device_id() const { return it->device; }
+  Chi2Operands& operands() const { return it->chi2; }
+  int upload_chi2(const Chi2Host& host) const {
+    return upload_operands(it, host.data, host.precision);
+  }
+};
+
+// An interpolator as grad_entry sees it.
+struct InterpGrad : InterpHandle {
   // What the table entry points refuse (check_grad_args on the first table: flags, float32, the
   // shape of theta) and a grid that does not fit the LDS of a workgroup.
   int check(const GradRequest& request, int n_theta, bool likelihood) const {
@@ -1057,13 +1066,7 @@ struct InterpGrad {
     return TC_OK;
   }
   const char* null_message(bool) const { return "NULL pointer"; }
-  int device_id() const { return it->device; }
-  Chi2Operands& operands() const { return it->chi2; }
-  // (earlier kernels of any lane may still read the old operands)
-  int drain() const { return tc_interp_synchronize(it); }
-  GradStaging staging() const {
-    return {&it->theta, &it->x, &it->out_ngal, &it->out_xi, it->stream};
-  }
+  GradStaging staging() const { return interp_grad_staging(it); }
   // One launch per slab of draws on a lane of the interpolator's own (it->cur; no table's `prev`
   // is written: nothing chains to these launches); the resident kernels of all its tables stop.
   int device(GradLane lane, const GradRequest& request) const {
@@ -1394,94 +1397,59 @@ int check_interp_vjp(const tc_interp* it, int64_t n_draws, unsigned flags) {
   return check_grad_fit(t0, "interpolator occupation VJP", lds);
 }
 
-// Every entry at the occupation seam: `request` as the caller stated it (chi2_data not yet
-// known) on device pointers (the interpolator's next lane) or host arrays (slab-wise on its lane
-// 0), and, for the likelihood form, its operands on the host.
-int interp_vjp_entry(tc_interp* it, bool host, unsigned flags, VjpRequest request,
-                     const Chi2Host* operands) {
-  int status = check_interp_vjp(it, request.n_draws, flags);
-  if (status != TC_OK) return status;
-  if (request.n_draws == 0) return TC_OK;
-  if (operands != nullptr) {
-    TC_CHECK(request.occupation && request.x && operands->data && operands->precision &&
-                 request.ngal && request.chi2,
-             "NULL pointer");
-    const int given = (request.g_occupation != nullptr) + (request.g_x != nullptr) +
-                      (request.dngal_dx != nullptr);
-    TC_CHECK(given == 0 || given == 3,
-             "dchi2_docc, dchi2_dx and dngal_dx go together: all NULL is the forward-only form");
-  } else {
-    TC_CHECK(request.occupation && request.x && request.ngal && request.xi, "NULL pointer");
-    const int given = (request.g_xi != nullptr) + (request.g_occupation != nullptr) +
-                      (request.g_x != nullptr);
-    TC_CHECK(given == 0 || given == 3,
-             "g_xi, g_occupation and g_x go together: all NULL is the forward-only form");
+// An interpolator as vjp_entry sees it: x is required, and the adjoint arrays go together.
+struct InterpVjp : InterpHandle {
+  int check(int64_t n_draws, unsigned flags) const { return check_interp_vjp(it, n_draws, flags); }
+  VjpRule rule() const {
+    return {true, true,
+            {"g_xi, g_occupation and g_x go together: all NULL is the forward-only form",
+             "dchi2_docc, dchi2_dx and dngal_dx go together: all NULL is the forward-only form"}};
   }
-  tc_table* t0 = it->tables[0];
-  TC_HIP(hipSetDevice(it->device));
-  for (tc_table* t : it->tables)
-    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-  status = build_grad_walk(it, /*with_matrices=*/true);
-  if (status != TC_OK) return status;
-  if (operands != nullptr) {
-    status = upload_operands(it, operands->data, operands->precision);
+  VjpStaging staging() const {
+    return {&it->theta, &it->out_ngal, &it->out_xi, it->stream, max_slab(it->tables[0])};
+  }
+  // One launch per slab of draws on a lane of the interpolator's own (as InterpGrad), timed
+  // through the first table's timer; the resident kernels of all its tables stop, the walk is built.
+  int device(GradLane lane, const VjpRequest& request) const {
+    tc_table* t0 = it->tables[0];
+    int status = TC_OK;
+    for (tc_table* t : it->tables)
+      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+    status = build_grad_walk(it, /*with_matrices=*/true);
     if (status != TC_OK) return status;
-    request.chi2_data = it->chi2.device();
-  }
-  tc::InterpVjpArgs ia{};
-  fill_interp_grid(it, &ia.interp);
-  ia.interp.class_n_h = (const double* const*)it->grad_walk.class_n_h;
-  ia.vjp.n_bins = t0->n_bins;
-  ia.vjp.n_r = t0->n_r;
-  ia.vjp.perm = (const int32_t*)t0->d_perm;
-  ia.vjp.row_tiles = tc::grad_row_tiles(t0->n_bins);
-  ia.vjp.k_steps = tc::grad_k_steps(t0->n_bins);
-  const int lds = (int)interp_vjp_lds(it);
-  // (one launch per slab of at most max_slab(t0) draws, timed through the first table's timer)
-  const auto run = [&](const VjpRequest& slab, hipStream_t stream) {
-    Range range("interpolator occupation VJP (one launch)");
-    slab.arrays(&ia.vjp);
-    ia.interp.table.n_draws = slab.n_draws;
-    ia.interp.x = slab.x;
-    ia.g_x = slab.g_x;
-    ia.dngal_dx = slab.dngal_dx;
-    return launch_grad_batch(t0, slab.n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
-      return launch_vjp_interp_instance(t0->mode, it->device, grid, lds, stream, k0, k1, ia);
-    });
-  };
-  if (host) {
-    const VjpStaging stage{&it->theta, &it->out_ngal, &it->out_xi, it->stream, max_slab(t0)};
-    return vjp_host_arrays(stage, request, [&](const VjpRequest& staged) {
-      return run(staged, interp_grad_stream(it, GradLane::kPinned));
+    tc::InterpVjpArgs ia{};
+    fill_interp_grid(it, &ia.interp);
+    ia.interp.class_n_h = (const double* const*)it->grad_walk.class_n_h;
+    ia.vjp.n_bins = t0->n_bins;
+    ia.vjp.n_r = t0->n_r;
+    ia.vjp.perm = (const int32_t*)t0->d_perm;
+    ia.vjp.row_tiles = tc::grad_row_tiles(t0->n_bins);
+    ia.vjp.k_steps = tc::grad_k_steps(t0->n_bins);
+    const int lds = (int)interp_vjp_lds(it);
+    hipStream_t stream = interp_grad_stream(it, lane);
+    return vjp_slabs(request, max_slab(t0), [&](const VjpRequest& slab) {
+      Range range("interpolator occupation VJP (one launch)");
+      slab.arrays(&ia.vjp);
+      ia.interp.table.n_draws = slab.n_draws;
+      ia.interp.x = slab.x;
+      ia.g_x = slab.g_x;
+      ia.dngal_dx = slab.dngal_dx;
+      return launch_grad_batch(t0, slab.n_draws, lds, [&](dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+        return launch_vjp_interp_instance(t0->mode, it->device, grid, lds, stream, k0, k1, ia);
+      });
     });
   }
-  hipStream_t stream = interp_grad_stream(it, GradLane::kNext);
-  return for_each_slab(request.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
-    return run(request.slab(begin, n), stream);
-  });
-}
+};
 
 // The request of such an entry, in the order of the C arguments.
 VjpRequest interp_vjp_request(const tc_interp* it, const double* occupation, const double* x,
                               int64_t n_draws, const double* g_ngal, const double* g_xi,
                               double* ngal, double* xi, double* chi2, double* g_occupation,
                               double* g_x, double* dngal_dx) {
-  return VjpRequest{n_draws,
-                    it ? it->tables[0]->n_bins : 0,
-                    it ? it->tables[0]->n_r : 0,
-                    occupation,
-                    g_ngal,
-                    g_xi,
-                    nullptr,
-                    ngal,
-                    xi,
-                    chi2,
-                    g_occupation,
-                    it ? (int)it->class_table.size() : 1,
-                    it ? it->n_dim : 0,
-                    x,
-                    g_x,
-                    dngal_dx};
+  const tc_table* t0 = it ? it->tables[0] : nullptr;
+  return VjpRequest{n_draws, t0 ? t0->n_bins : 0, t0 ? t0->n_r : 0, occupation, g_ngal, g_xi,
+                    nullptr, ngal, xi, chi2, g_occupation, it ? (int)it->class_table.size() : 1,
+                    it ? it->n_dim : 0, x, g_x, dngal_dx};
 }
 
 }  // namespace
@@ -1502,10 +1470,10 @@ int tc_interp_predict_occupation_vjp_batch(tc_interp* it, const double* occupati
                                            const double* x, int64_t n_draws, unsigned flags,
                                            const double* g_ngal, const double* g_xi, double* ngal,
                                            double* xi, double* g_occupation, double* g_x) {
-  return interp_vjp_entry(it, true, flags,
-                          interp_vjp_request(it, occupation, x, n_draws, g_ngal, g_xi, ngal, xi,
-                                             nullptr, g_occupation, g_x, nullptr),
-                          nullptr);
+  return vjp_entry(InterpVjp{it}, GradRoute::kHost, flags,
+                   interp_vjp_request(it, occupation, x, n_draws, g_ngal, g_xi, ngal, xi,
+                                      nullptr, g_occupation, g_x, nullptr),
+                   nullptr);
 }
 
 int tc_interp_predict_occupation_vjp_batch_device(tc_interp* it, const double* occupation_device,
@@ -1514,11 +1482,11 @@ int tc_interp_predict_occupation_vjp_batch_device(tc_interp* it, const double* o
                                                   const double* g_xi_device, double* ngal_device,
                                                   double* xi_device, double* g_occupation_device,
                                                   double* g_x_device) {
-  return interp_vjp_entry(it, false, flags,
-                          interp_vjp_request(it, occupation_device, x_device, n_draws,
-                                             g_ngal_device, g_xi_device, ngal_device, xi_device,
-                                             nullptr, g_occupation_device, g_x_device, nullptr),
-                          nullptr);
+  return vjp_entry(InterpVjp{it}, GradRoute::kDevice, flags,
+                   interp_vjp_request(it, occupation_device, x_device, n_draws,
+                                      g_ngal_device, g_xi_device, ngal_device, xi_device,
+                                      nullptr, g_occupation_device, g_x_device, nullptr),
+                   nullptr);
 }
 
 int tc_interp_chi2_occupation_grad_batch(tc_interp* it, const double* occupation, const double* x,
@@ -1526,10 +1494,10 @@ int tc_interp_chi2_occupation_grad_batch(tc_interp* it, const double* occupation
                                          const double* precision, double* ngal, double* chi2,
                                          double* dchi2_docc, double* dchi2_dx, double* dngal_dx) {
   const Chi2Host operands{data, precision};
-  return interp_vjp_entry(it, true, flags,
-                          interp_vjp_request(it, occupation, x, n_draws, nullptr, nullptr, ngal,
-                                             nullptr, chi2, dchi2_docc, dchi2_dx, dngal_dx),
-                          &operands);
+  return vjp_entry(InterpVjp{it}, GradRoute::kHost, flags,
+                   interp_vjp_request(it, occupation, x, n_draws, nullptr, nullptr, ngal,
+                                      nullptr, chi2, dchi2_docc, dchi2_dx, dngal_dx),
+                   &operands);
 }
 
 int tc_interp_chi2_occupation_grad_batch_device(tc_interp* it, const double* occupation_device,
@@ -1540,11 +1508,11 @@ int tc_interp_chi2_occupation_grad_batch_device(tc_interp* it, const double* occ
                                                 double* dchi2_dx_device,
                                                 double* dngal_dx_device) {
   const Chi2Host operands{data, precision};
-  return interp_vjp_entry(it, false, flags,
-                          interp_vjp_request(it, occupation_device, x_device, n_draws, nullptr,
-                                             nullptr, ngal_device, nullptr, chi2_device,
-                                             dchi2_docc_device, dchi2_dx_device, dngal_dx_device),
-                          &operands);
+  return vjp_entry(InterpVjp{it}, GradRoute::kDevice, flags,
+                   interp_vjp_request(it, occupation_device, x_device, n_draws, nullptr,
+                                      nullptr, ngal_device, nullptr, chi2_device,
+                                      dchi2_docc_device, dchi2_dx_device, dngal_dx_device),
+                   &operands);
 }
 
 int tc_debug_interp_vjp_lds_bytes(int mode, int n_bins, int n_r, int n_dim, int64_t* bytes) {

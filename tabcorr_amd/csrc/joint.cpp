@@ -6,10 +6,11 @@
 // first table's, the matrices every table's own (launch.hip: build_grad_table).
 // The forward entries -- the concatenated prediction or chi2 alone -- take ONE launch of
 // joint_forward_kernel (joint_forward_kernels.hip.h) on the mode-auto tables' own forward unit
-// layouts, and the forward call path of the tables (predict_call.h) through the first table.
+// layouts, and the forward call path of the tables (predict_call.h) through the first table, in the
+// entry sequence the two joints share (joint_forward_call.h).
 // The entries at the occupation seam -- any occupation model -- take ONE launch of vjp_joint_kernel
-// (joint_vjp_kernels.hip.h) on the tables' gradient matrices, and the staging path of the tables'
-// own VJP entries (grad_call.h: vjp_host, vjp_device) through the first table.
+// (joint_vjp_kernels.hip.h) on the tables' gradient matrices, in the entry sequence and the staging
+// path of the tables' own VJP entries (grad_call.h: vjp_entry) through the first table.
 #include "internal.h"
 
 using namespace tc::host;
@@ -24,14 +25,40 @@ struct tc_joint {
 
 namespace {
 
-// The family a call's flags select: plain Zheng07, or (TC_FLAG_ASSEMBIAS) the decorated model.
-int joint_params(unsigned flags) {
-  return (flags & TC_FLAG_ASSEMBIAS) ? tc::kGradParamsAssembias : tc::kGradParams;
-}
-
-// A joint as grad_entry sees it: it works through its first table.
-struct JointGrad {
+// What every call of a joint shares (grad_entry, vjp_entry, joint_forward_entry): it works
+// through its first table.
+struct JointHandle {
   tc_joint* joint;
+  tc_table* first() const { return joint->tables[0]; }
+  int device_id() const { return joint->device; }
+  Chi2Operands& operands() const { return joint->chi2; }
+  // (earlier kernels of any lane of the first table may still read the old operands)
+  int upload_chi2(const Chi2Host& host) const {
+    tc_table* t0 = first();
+    return joint->chi2.upload(joint->n_r_total, host.data, host.precision, t0->stream,
+                              [t0] { return tc_table_synchronize(t0); });
+  }
+  // The tables of a derivative kernel's argument block (JointArgs, JointVjpArgs): every table's
+  // resident kernel stops and its gradient matrix is built.
+  template <typename Args>
+  int members(Args* ja) const {
+    ja->n_tables = (int)joint->tables.size();
+    for (int k = 0; k < ja->n_tables; ++k) {
+      tc_table* t = joint->tables[k];
+      int status = TC_OK;
+      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+      if ((status = build_grad_table(t)) != TC_OK) return status;
+      ja->mode[k] = t->mode;
+      ja->n_r[k] = t->n_r;
+      ja->r_offset[k] = joint->r_offset[k];
+      ja->matrix[k] = (const double*)t->grad.d_matrix;
+    }
+    return TC_OK;
+  }
+};
+
+// A joint as grad_entry sees it.
+struct JointGrad : JointHandle {
   // What the table entry points refuse (check_grad_args on the first table, with the family's
   // flag taken out of the flags and without the table's own fit; the tables are float64 and
   // share their bins by construction) and a joint beyond the LDS of a workgroup.
@@ -50,19 +77,14 @@ struct JointGrad {
   const char* null_message(bool likelihood) const {
     return likelihood ? "NULL pointer" : "output pointer is NULL";
   }
-  int device_id() const { return joint->device; }
-  Chi2Operands& operands() const { return joint->chi2; }
-  // (earlier kernels of any lane of the first table may still read the old operands)
-  int drain() const { return tc_table_synchronize(joint->tables[0]); }
   GradStaging staging() const {
-    tc_table* t0 = joint->tables[0];
+    tc_table* t0 = first();
     return {&t0->theta, nullptr, &t0->out_ngal, &t0->out_xi, t0->stream};
   }
-  // One launch per slab of draws on lane 0 (pinned) or the next lane of the first table; the
-  // resident kernels of all the tables stop.
+  // One launch per slab of draws on lane 0 (pinned) or the next lane of the first table.
   int device(GradLane lane, const GradRequest& request) const {
     TC_HIP(hipSetDevice(joint->device));
-    tc_table* t0 = joint->tables[0];
+    tc_table* t0 = first();
     tc::JointArgs ja{};
     fill_grad_shape(t0, request.n_gauss, request.flags, &ja.grad);
     ja.grad.n_r = joint->n_r_total;
@@ -70,17 +92,8 @@ struct JointGrad {
     ja.grad.percentile = request.n_params == tc::kGradParamsAssembias
                              ? (const double*)t0->d_percentile
                              : nullptr;
-    ja.n_tables = (int)joint->tables.size();
-    for (int k = 0; k < ja.n_tables; ++k) {
-      tc_table* t = joint->tables[k];
-      int status = TC_OK;
-      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-      if ((status = build_grad_table(t)) != TC_OK) return status;
-      ja.mode[k] = t->mode;
-      ja.n_r[k] = t->n_r;
-      ja.r_offset[k] = joint->r_offset[k];
-      ja.matrix[k] = (const double*)t->grad.d_matrix;
-    }
+    const int status = members(&ja);
+    if (status != TC_OK) return status;
     return grad_slabs(t0, lane, request.n_draws,
                       [&](int64_t begin, int64_t n, hipStream_t stream) {
                         return run_grad_joint(t0, ja, request.slab(begin, n), stream);
@@ -136,144 +149,113 @@ int joint_forward_fit(int n_bins, int n_tables, const int* mode, const int* n_r,
   return TC_OK;
 }
 
-// The arguments of a forward entry point, the NULL handle first; then what the kernel refuses.
-int check_joint_forward(const tc_joint* joint, const PredictRequest& request) {
-  TC_CHECK(joint != nullptr, "joint handle is NULL");
-  const unsigned flags = request.flags;
-  if (flags & TC_FLAG_SEPARATE_GAL_TYPE)
-    return fail(TC_ERR_UNSUPPORTED, "joint forward calls are implemented for the total "
-                                    "prediction only (not separate_gal_type)");
-  if (flags & TC_FLAG_LEAUTHAUD11)
-    return fail(TC_ERR_UNSUPPORTED, "joint forward calls are implemented for the Zheng07 family "
-                                    "only");
-  const unsigned unserved =
-      flags & ~(unsigned)(TC_FLAG_MODULATE_WITH_CENOCC | TC_FLAG_ASSEMBIAS);
-  if (unserved != 0)
-    return fail(TC_ERR_UNSUPPORTED, "joint forward calls: unknown flags 0x%x", unserved);
-  const tc_table* t0 = joint->tables[0];
-  int status = check_predict_args(t0, request.theta, request.n_theta, request.n_draws,
-                                  request.n_gauss, flags);
-  if (status != TC_OK) return status;
-  const int n_tables = (int)joint->tables.size();
-  int mode[tc::kJointMaxTables], n_r[tc::kJointMaxTables], dtype[tc::kJointMaxTables];
-  for (int k = 0; k < n_tables; ++k) {
-    mode[k] = joint->tables[k]->mode;
-    n_r[k] = joint->tables[k]->n_r;
-    dtype[k] = joint->tables[k]->compute_dtype;
-  }
-  status = joint_forward_fit(t0->n_bins, n_tables, mode, n_r, dtype, nullptr);
-  if (status != TC_OK) return status;
-  for (int k = 0; k < n_tables; ++k) {
-    const tc_table* t = joint->tables[k];
-    if (t->mode != TC_MODE_AUTO) continue;
-    const tc::QuadLayout& layout = t->quad_total.layout;
-    if (!(t->quad && t->quad_total.d_table != nullptr && t->quad_tiling.n_rtiles == 1 &&
-          layout.comps.size() == 1 && layout.comps[0].triangular))
-      return fail(TC_ERR_UNSUPPORTED,
-                  "joint forward calls: table %d (mode auto, %d bins) does not have the unit "
-                  "layout of the one-launch form", k, t->n_bins);
-  }
-  return TC_OK;
-}
-
-// The argument block but for the draws and the outputs: the resident kernels of the tables stop,
-// the mode-cross matrices are built (launch.hip: build_grad_table), the passes are numbered.
-int joint_forward_args(tc_joint* joint, int n_theta, int n_gauss, unsigned flags,
-                       tc::JointForwardArgs* out) {
-  tc_table* t0 = joint->tables[0];
-  tc::JointForwardArgs ja{};
-  ja.n_theta = n_theta;
-  ja.n_bins = t0->n_bins;
-  ja.n_central = t0->plan.n_central;
-  ja.n_gauss = n_gauss;
-  ja.dens_rows = (t0->n_bins + 3) / 4 * 4;
-  ja.n_r = joint->n_r_total;
-  Quadrature* q = nullptr;
-  int status = get_quadrature(t0, n_gauss, &q);
-  if (status != TC_OK) return status;
-  ja.log_m = (const double*)q->log_m;
-  ja.m = (const double*)q->m;
-  ja.weight = (const double*)q->weight;
-  ja.n_h = (const double*)t0->d_n_h;
-  ja.percentile = (const double*)t0->d_percentile;
-  ja.split = 0.5;
-  ja.math_table = (const double*)t0->d_math_table;
-  ja.n_tables = (int)joint->tables.size();
-  const int parts = tc::joint_forward_parts(tc::kJointForwardWaves);
-  bool first_auto = true;
-  for (int k = 0; k < ja.n_tables; ++k) {
-    tc_table* t = joint->tables[k];
-    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-    ja.mode[k] = t->mode;
-    ja.n_rows[k] = t->n_r;
-    ja.r_offset[k] = joint->r_offset[k];
-    ja.job_begin[k + 1] = ja.job_begin[k];
-    if (t->mode == TC_MODE_AUTO) {
-      const tc::QuadComp& comp = t->quad_total.layout.comps[0];
-      const int n_u = t->quad_tiling.n_u;
-      ja.matrix[k] = t->quad_total.d_table;
-      ja.n_u[k] = n_u;
-      ja.table_bytes[k] =
-          (uint32_t)((size_t)t->quad_total.layout.n_units * (size_t)((n_u + 1) / 2) * 1024);
-      ja.job_begin[k + 1] += (n_u + 1) / 2 * 2 * parts;
-      if (first_auto) {
-        tc::triangle_parts(comp.n_rb, parts, ja.part_rb0, ja.part_cb0, ja.part_count);
-        ja.n_cb = comp.n_cb;
-        ja.i_row0 = comp.i_bin0;
-        ja.j_row0 = comp.j_bin0;
-        ja.unit_base = (int)comp.unit_base;
-        first_auto = false;
-      }
-    } else {
-      if ((status = build_grad_table(t)) != TC_OK) return status;
-      ja.matrix[k] = t->grad.d_matrix;
-    }
-  }
-  *out = ja;
-  return TC_OK;
-}
-
-// One launch per slab of the draws of `r` (device pointers) on `stream`, timed and reported
-// through the first table.
-int joint_forward_launches(tc_joint* joint, const tc::JointForwardArgs& shape,
-                           const PredictRequest& r, hipStream_t stream) {
-  Range range("joint forward (one launch)");
-  tc_table* t0 = joint->tables[0];
-  const int lds = (int)tc::joint_forward_lds_bytes(shape.n_bins, shape.n_r,
-                                                   tc::kJointForwardWaves);
-  return for_each_slab(r.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
-    const PredictRequest slab = r.chunk(begin, n);
-    tc::JointForwardArgs ja = shape;
-    ja.theta = slab.theta;
-    ja.n_draws = n;
-    ja.ngal = slab.ngal;
-    ja.xi = r.likelihood ? nullptr : slab.second;
-    ja.chi2_data = r.likelihood ? joint->chi2.device() : nullptr;
-    ja.chi2 = r.likelihood ? slab.second : nullptr;
-    const dim3 grid((unsigned)((n + tc::kJointForwardDraws - 1) / tc::kJointForwardDraws));
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    int status = next_kernel_events(t0, &k0, &k1);
-    if (status != TC_OK) return status;
-    status = launch_joint_forward_instance(
-        shape.n_gauss, (r.flags & TC_FLAG_ASSEMBIAS) != 0,
-        (r.flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0, t0->device, grid, lds, stream, k0, k1, ja);
-    if (status != TC_OK) return status;
-    t0->last_workgroups = (int)grid.x;
-    t0->last_waves = tc::kJointForwardWaves;
-    t0->last_splits = 0;
-    t0->last_lds = lds;
-    return TC_OK;
-  });
-}
-
-// A joint as forward_chunked and forward_zero_copy see it (table.cpp: TableForward): it works
-// through its first table -- the staging areas, the tickets, the lanes and the chunk events are
-// that table's.
-struct JointForward {
+// A joint as joint_forward_entry, forward_chunked and forward_zero_copy see it (table.cpp:
+// TableForward): the staging areas, the tickets, the lanes and the chunk events are the first
+// table's.
+struct JointForward : JointHandle {
   static constexpr bool kThreadedCopyOut = true;
-  tc_joint* joint;
-  const tc::JointForwardArgs* shape;
-  tc_table* handle() const { return joint->tables[0]; }
+  using Args = tc::JointForwardArgs;
+  const Args* shape = nullptr;
+  // The arguments of a forward entry point, the NULL handle first; then what the kernel refuses.
+  int check(const PredictRequest& request) const {
+    TC_CHECK(joint != nullptr, "joint handle is NULL");
+    int status = check_joint_forward_flags("joint forward calls", request.flags);
+    if (status != TC_OK) return status;
+    const tc_table* t0 = first();
+    status = check_predict_args(t0, request.theta, request.n_theta, request.n_draws,
+                                request.n_gauss, request.flags);
+    if (status != TC_OK) return status;
+    const int n_tables = (int)joint->tables.size();
+    int mode[tc::kJointMaxTables], n_r[tc::kJointMaxTables], dtype[tc::kJointMaxTables];
+    for (int k = 0; k < n_tables; ++k) {
+      mode[k] = joint->tables[k]->mode;
+      n_r[k] = joint->tables[k]->n_r;
+      dtype[k] = joint->tables[k]->compute_dtype;
+    }
+    status = joint_forward_fit(t0->n_bins, n_tables, mode, n_r, dtype, nullptr);
+    if (status != TC_OK) return status;
+    for (int k = 0; k < n_tables; ++k) {
+      const tc_table* t = joint->tables[k];
+      if (t->mode == TC_MODE_AUTO && !has_joint_forward_layout(t))
+        return fail(TC_ERR_UNSUPPORTED,
+                    "joint forward calls: table %d (mode auto, %d bins) does not have the unit "
+                    "layout of the one-launch form", k, t->n_bins);
+    }
+    return TC_OK;
+  }
+  // The argument block but for the draws and the outputs: the resident kernels of the tables
+  // stop, the mode-cross matrices are built (launch.hip: build_grad_table), the passes are numbered.
+  int args(const PredictRequest& request, Args* out) const {
+    tc_table* t0 = first();
+    Args ja{};
+    ja.n_theta = request.n_theta;
+    ja.n_bins = t0->n_bins;
+    ja.n_central = t0->plan.n_central;
+    ja.n_gauss = request.n_gauss;
+    ja.dens_rows = (t0->n_bins + 3) / 4 * 4;
+    ja.n_r = joint->n_r_total;
+    Quadrature* q = nullptr;
+    int status = get_quadrature(t0, request.n_gauss, &q);
+    if (status != TC_OK) return status;
+    ja.log_m = (const double*)q->log_m;
+    ja.m = (const double*)q->m;
+    ja.weight = (const double*)q->weight;
+    ja.n_h = (const double*)t0->d_n_h;
+    ja.percentile = (const double*)t0->d_percentile;
+    ja.split = 0.5;
+    ja.math_table = (const double*)t0->d_math_table;
+    ja.n_tables = (int)joint->tables.size();
+    for (int k = 0; k < ja.n_tables; ++k) {
+      tc_table* t = joint->tables[k];
+      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+      if (t->mode != TC_MODE_AUTO && (status = build_grad_table(t)) != TC_OK) return status;
+      ja.matrix[k] = t->mode == TC_MODE_AUTO ? t->quad_total.d_table : t->grad.d_matrix;
+      number_joint_forward_member(&ja, k, t->mode, t->n_r, joint->r_offset[k], t);
+    }
+    *out = ja;
+    return TC_OK;
+  }
+  // One launch per slab of the draws of `r` (device pointers) on `stream`.
+  int launches(const PredictRequest& r, hipStream_t stream) const {
+    Range range("joint forward (one launch)");
+    const int lds = (int)tc::joint_forward_lds_bytes(shape->n_bins, shape->n_r,
+                                                     tc::kJointForwardWaves);
+    return joint_forward_slabs(
+        first(), *shape, joint->chi2.device(), r, lds,
+        [&](const Args& ja, const PredictRequest&, dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+          return launch_joint_forward_instance(
+              shape->n_gauss, (r.flags & TC_FLAG_ASSEMBIAS) != 0,
+              (r.flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0, joint->device, grid, lds, stream, k0,
+              k1, ja);
+        });
+  }
+  // (the first table's next lane, where a call of the table's may chain to it)
+  int device(const PredictRequest& request) const {
+    tc_table* t0 = first();
+    t0->cur = next_lane(false, t0->tuning.pipeline != 0, t0->n_lanes, &t0->device_calls);
+    const int status = launches(request, t0->lanes[t0->cur].stream);
+    if (status == TC_OK) t0->prev = t0->cur;
+    return status;
+  }
+  const char* missing(const PredictRequest& r) const {
+    return r.ngal && r.second ? nullptr : "output pointer is NULL";
+  }
+  tc::SyncChunkPlan plan(const PredictRequest& request) const {
+    return plan_forward_chunks(first(), first()->n_lanes, false, false, request);
+  }
+  // (the draws through the page-locked stage of the first table)
+  int copy_up(const PredictRequest& request, const double** theta, const double**,
+              double** out) const {
+    tc_table* t0 = first();
+    int status = t0->theta.reserve(request.theta_bytes(), t0->stream);
+    if (status == TC_OK) status = t0->out_ngal.reserve(request.out_bytes(), t0->stream);
+    if (status != TC_OK) return status;
+    *theta = (const double*)t0->theta.ptr;
+    *out = (double*)t0->out_ngal.ptr;
+    return copy_in(&t0->h_in, t0->theta.ptr, request.theta, request.theta_bytes(), t0->stream);
+  }
+
+  tc_table* handle() const { return first(); }
   // (one form: a draw's result does not depend on the chunks)
   Call hints(const PredictRequest&, const tc::SyncChunkPlan&) const {
     return probe_call(handle());
@@ -292,8 +274,7 @@ struct JointForward {
                           hipMemcpyHostToDevice, lane.stream));
     if (wait_for != nullptr) TC_HIP(hipStreamWaitEvent(lane.stream, wait_for, 0));
     double* out = (double*)lane.out.ptr;
-    status = joint_forward_launches(
-        joint, *shape,
+    status = launches(
         part.on((const double*)lane.in_theta.ptr, nullptr, out, out + part.ngal_count()),
         lane.stream);
     if (status != TC_OK) return status;
@@ -304,9 +285,7 @@ struct JointForward {
   }
   int synchronize() const { return tc_table_synchronize(handle()); }
   // (the pinned lane of the first table)
-  int run(const PredictRequest& s) const {
-    return joint_forward_launches(joint, *shape, s, handle()->stream);
-  }
+  int run(const PredictRequest& s) const { return launches(s, handle()->stream); }
 };
 
 // The request of a joint forward entry point, in the order of the C arguments.
@@ -317,49 +296,7 @@ PredictRequest joint_forward_request(const tc_joint* joint, const double* theta,
                         1,       theta, nullptr, ngal,   second,    likelihood};
 }
 
-// Every forward entry point of a joint: the checks, the likelihood's operands, then the launches
-// on device pointers (the first table's next lane) or the forward path of host arrays.
-int joint_forward_entry(tc_joint* joint, bool host, const PredictRequest& request,
-                        const Chi2Host* operands) {
-  int status = check_joint_forward(joint, request);
-  if (status != TC_OK) return status;
-  if (request.n_draws == 0) return TC_OK;
-  TC_CHECK(request.ngal && request.second, "output pointer is NULL");
-  TC_CHECK(operands == nullptr || (operands->data && operands->precision), "NULL pointer");
-  tc_table* t0 = joint->tables[0];
-  TC_HIP(hipSetDevice(joint->device));
-  if (operands != nullptr) {
-    status = joint->chi2.upload(joint->n_r_total, operands->data, operands->precision, t0->stream,
-                                [&] { return tc_table_synchronize(t0); });
-    if (status != TC_OK) return status;
-  }
-  tc::JointForwardArgs shape;
-  status = joint_forward_args(joint, request.n_theta, request.n_gauss, request.flags, &shape);
-  if (status != TC_OK) return status;
-  if (!host) {
-    t0->cur = next_lane(false, t0->tuning.pipeline != 0, t0->n_lanes, &t0->device_calls);
-    status = joint_forward_launches(joint, shape, request, t0->lanes[t0->cur].stream);
-    if (status == TC_OK) t0->prev = t0->cur;
-    return status;
-  }
-  const JointForward forward{joint, &shape};
-  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
-  const tc::SyncChunkPlan plan = plan_forward_chunks(t0, t0->n_lanes, false, false, request);
-  if (plan.n_chunks > 0) return forward_chunked(forward, request, plan);
-  status = t0->theta.reserve(request.theta_bytes(), t0->stream);
-  if (status == TC_OK) status = t0->out_ngal.reserve(request.out_bytes(), t0->stream);
-  if (status != TC_OK) return status;
-  status = copy_in(&t0->h_in, t0->theta.ptr, request.theta, request.theta_bytes(), t0->stream);
-  if (status != TC_OK) return status;
-  double* d_ngal = (double*)t0->out_ngal.ptr;
-  double* d_second = d_ngal + request.ngal_count();
-  status = forward.run(request.on((const double*)t0->theta.ptr, nullptr, d_ngal, d_second));
-  if (status != TC_OK) return status;
-  return copy_out(&t0->h_out, request.ngal, request.ngal_count(), d_ngal, request.second,
-                  request.second_count(), d_second, t0->stream);
-}
-
-// ---- the occupation seam (joint_vjp_kernels.hip.h) ----------------------------------------------
+// ---- the occupation seam (joint_vjp_kernels.hip.h; grad_call.h: vjp_entry) ----------------------
 
 int joint_rows_auto(const tc_joint* joint) {
   int rows = 0;
@@ -368,69 +305,50 @@ int joint_rows_auto(const tc_joint* joint) {
   return rows;
 }
 
-// What the entries at the occupation seam refuse, the NULL handle first: flags, a negative number
-// of draws, a workgroup beyond the LDS of a CU (check_grad_fit, for all the tables together).
-int check_joint_vjp(const tc_joint* joint, int64_t n_draws, unsigned flags) {
-  TC_CHECK(joint != nullptr, "joint handle is NULL");
-  TC_CHECK(flags == 0, "joint occupation VJP: flags must be 0, got 0x%x", flags);
-  TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
-  const size_t lds = tc::joint_vjp_lds_bytes(joint->tables[0]->n_bins, joint->n_r_total,
-                                             joint_rows_auto(joint));
-  int status = TC_OK;
-  for (size_t k = 0; status == TC_OK && k < joint->tables.size(); ++k)
-    status = check_grad_fit(joint->tables[k], "joint occupation VJP", lds, joint->n_r_total);
-  return status;
-}
-
-// Every entry at the occupation seam: `request` as the caller stated it (chi2_data not yet
-// known) on device pointers (the first table's next lane) or host arrays (slab-wise on its lane
-// 0), and, for the likelihood form, its operands on the host.
-int joint_vjp_entry(tc_joint* joint, bool host, unsigned flags, VjpRequest request,
-                    const Chi2Host* operands) {
-  int status = check_joint_vjp(joint, request.n_draws, flags);
-  if (status != TC_OK) return status;
-  if (request.n_draws == 0) return TC_OK;
-  if (operands != nullptr) {
-    TC_CHECK(request.occupation && operands->data && operands->precision && request.ngal &&
-                 request.chi2,
-             "NULL pointer");
-  } else {
-    TC_CHECK(request.occupation && request.ngal && request.xi, "NULL pointer");
-    TC_CHECK((request.g_xi == nullptr) == (request.g_occupation == nullptr),
-             "g_xi and g_occupation go together: both NULL is the forward-only form");
+// A joint as vjp_entry sees it: g_xi and g_occupation go together.
+struct JointVjp : JointHandle {
+  // What the entries at the occupation seam refuse, the NULL handle first: flags, a negative
+  // number of draws, a workgroup beyond the LDS of a CU (check_grad_fit, for all the tables
+  // together).
+  int check(int64_t n_draws, unsigned flags) const {
+    TC_CHECK(joint != nullptr, "joint handle is NULL");
+    TC_CHECK(flags == 0, "joint occupation VJP: flags must be 0, got 0x%x", flags);
+    TC_CHECK(n_draws >= 0, "n_draws must be non-negative");
+    const size_t lds = tc::joint_vjp_lds_bytes(first()->n_bins, joint->n_r_total,
+                                               joint_rows_auto(joint));
+    int status = TC_OK;
+    for (size_t k = 0; status == TC_OK && k < joint->tables.size(); ++k)
+      status = check_grad_fit(joint->tables[k], "joint occupation VJP", lds, joint->n_r_total);
+    return status;
   }
-  tc_table* t0 = joint->tables[0];
-  TC_HIP(hipSetDevice(joint->device));
-  if (operands != nullptr) {
-    status = joint->chi2.upload(joint->n_r_total, operands->data, operands->precision, t0->stream,
-                                [&] { return tc_table_synchronize(t0); });
+  VjpRule rule() const {
+    return {false, true,
+            {"g_xi and g_occupation go together: both NULL is the forward-only form", nullptr}};
+  }
+  VjpStaging staging() const {
+    tc_table* t0 = first();
+    return {&t0->occupation, &t0->out_ngal, &t0->out_xi, t0->stream, max_slab(t0)};
+  }
+  // One launch per slab of draws on lane 0 (pinned) or the next lane of the first table.
+  int device(GradLane lane, const VjpRequest& request) const {
+    tc_table* t0 = first();
+    tc::JointVjpArgs ja{};
+    ja.vjp.n_bins = t0->n_bins;
+    ja.vjp.n_r = joint->n_r_total;
+    ja.vjp.perm = (const int32_t*)t0->d_perm;
+    ja.vjp.n_h = (const double*)t0->d_n_h;
+    ja.vjp.row_tiles = tc::grad_row_tiles(t0->n_bins);
+    ja.vjp.k_steps = tc::grad_k_steps(t0->n_bins);
+    const int status = members(&ja);
     if (status != TC_OK) return status;
-    request.chi2_data = joint->chi2.device();
+    ja.n_r_auto = joint_rows_auto(joint);
+    for (const tc_table* t : joint->tables) ja.n_cross += t->mode != TC_MODE_AUTO;
+    return grad_slabs(t0, lane, request.n_draws,
+                      [&](int64_t begin, int64_t n, hipStream_t stream) {
+                        return run_vjp_joint(t0, ja, request.slab(begin, n), stream);
+                      });
   }
-  tc::JointVjpArgs ja{};
-  ja.vjp.n_bins = t0->n_bins;
-  ja.vjp.n_r = joint->n_r_total;
-  ja.vjp.perm = (const int32_t*)t0->d_perm;
-  ja.vjp.n_h = (const double*)t0->d_n_h;
-  ja.vjp.row_tiles = tc::grad_row_tiles(t0->n_bins);
-  ja.vjp.k_steps = tc::grad_k_steps(t0->n_bins);
-  ja.n_tables = (int)joint->tables.size();
-  for (int k = 0; k < ja.n_tables; ++k) {
-    tc_table* t = joint->tables[k];
-    if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-    if ((status = build_grad_table(t)) != TC_OK) return status;
-    ja.mode[k] = t->mode;
-    ja.n_r[k] = t->n_r;
-    ja.r_offset[k] = joint->r_offset[k];
-    ja.matrix[k] = (const double*)t->grad.d_matrix;
-    if (t->mode == TC_MODE_AUTO) ja.n_r_auto += t->n_r;
-    else ja.n_cross += 1;
-  }
-  const auto run = [&](const VjpRequest& slab, hipStream_t stream) {
-    return run_vjp_joint(t0, ja, slab, stream);
-  };
-  return host ? vjp_host(t0, request, run) : vjp_device(t0, GradLane::kNext, request, run);
-}
+};
 
 // The request of such an entry, in the order of the C arguments.
 VjpRequest joint_vjp_request(const tc_joint* joint, const double* occupation, int64_t n_draws,
@@ -449,10 +367,10 @@ int tc_joint_predict_occupation_vjp_batch(tc_joint* joint, const double* occupat
                                           int64_t n_draws, unsigned flags, const double* g_ngal,
                                           const double* g_xi, double* ngal, double* xi,
                                           double* g_occupation) {
-  return joint_vjp_entry(joint, true, flags,
-                         joint_vjp_request(joint, occupation, n_draws, g_ngal, g_xi, ngal, xi,
-                                           nullptr, g_occupation),
-                         nullptr);
+  return vjp_entry(JointVjp{joint}, GradRoute::kHost, flags,
+                   joint_vjp_request(joint, occupation, n_draws, g_ngal, g_xi, ngal, xi,
+                                     nullptr, g_occupation),
+                   nullptr);
 }
 
 int tc_joint_predict_occupation_vjp_batch_device(tc_joint* joint, const double* occupation_device,
@@ -460,11 +378,11 @@ int tc_joint_predict_occupation_vjp_batch_device(tc_joint* joint, const double* 
                                                  const double* g_ngal_device,
                                                  const double* g_xi_device, double* ngal_device,
                                                  double* xi_device, double* g_occupation_device) {
-  return joint_vjp_entry(joint, false, flags,
-                         joint_vjp_request(joint, occupation_device, n_draws, g_ngal_device,
-                                           g_xi_device, ngal_device, xi_device, nullptr,
-                                           g_occupation_device),
-                         nullptr);
+  return vjp_entry(JointVjp{joint}, GradRoute::kDevice, flags,
+                   joint_vjp_request(joint, occupation_device, n_draws, g_ngal_device,
+                                     g_xi_device, ngal_device, xi_device, nullptr,
+                                     g_occupation_device),
+                   nullptr);
 }
 
 int tc_joint_chi2_occupation_grad_batch(tc_joint* joint, const double* occupation,
@@ -472,10 +390,10 @@ int tc_joint_chi2_occupation_grad_batch(tc_joint* joint, const double* occupatio
                                         const double* precision, double* ngal, double* chi2,
                                         double* dchi2_docc) {
   const Chi2Host operands{data, precision};
-  return joint_vjp_entry(joint, true, flags,
-                         joint_vjp_request(joint, occupation, n_draws, nullptr, nullptr, ngal,
-                                           nullptr, chi2, dchi2_docc),
-                         &operands);
+  return vjp_entry(JointVjp{joint}, GradRoute::kHost, flags,
+                   joint_vjp_request(joint, occupation, n_draws, nullptr, nullptr, ngal,
+                                     nullptr, chi2, dchi2_docc),
+                   &operands);
 }
 
 int tc_joint_chi2_occupation_grad_batch_device(tc_joint* joint, const double* occupation_device,
@@ -484,10 +402,10 @@ int tc_joint_chi2_occupation_grad_batch_device(tc_joint* joint, const double* oc
                                                double* ngal_device, double* chi2_device,
                                                double* dchi2_docc_device) {
   const Chi2Host operands{data, precision};
-  return joint_vjp_entry(joint, false, flags,
-                         joint_vjp_request(joint, occupation_device, n_draws, nullptr, nullptr,
-                                           ngal_device, nullptr, chi2_device, dchi2_docc_device),
-                         &operands);
+  return vjp_entry(JointVjp{joint}, GradRoute::kDevice, flags,
+                   joint_vjp_request(joint, occupation_device, n_draws, nullptr, nullptr,
+                                     ngal_device, nullptr, chi2_device, dchi2_docc_device),
+                   &operands);
 }
 
 int tc_debug_joint_vjp_lds_bytes(int n_bins, int n_r_total, int n_r_auto, int64_t* bytes) {
@@ -596,7 +514,7 @@ int tc_joint_chi2_grad_batch(tc_joint* joint, const double* theta, int n_theta, 
 int tc_joint_predict_batch_device(tc_joint* joint, const double* theta_device, int n_theta,
                                   int64_t n_draws, int n_gauss, unsigned flags,
                                   double* ngal_device, double* xi_device) {
-  return joint_forward_entry(joint, false,
+  return joint_forward_entry(JointForward{{joint}}, GradRoute::kDevice,
                              joint_forward_request(joint, theta_device, n_theta, n_draws, n_gauss,
                                                    flags, ngal_device, xi_device, false),
                              nullptr);
@@ -604,7 +522,7 @@ int tc_joint_predict_batch_device(tc_joint* joint, const double* theta_device, i
 
 int tc_joint_predict_batch(tc_joint* joint, const double* theta, int n_theta, int64_t n_draws,
                            int n_gauss, unsigned flags, double* ngal, double* xi) {
-  return joint_forward_entry(joint, true,
+  return joint_forward_entry(JointForward{{joint}}, GradRoute::kHost,
                              joint_forward_request(joint, theta, n_theta, n_draws, n_gauss, flags,
                                                    ngal, xi, false),
                              nullptr);
@@ -615,7 +533,7 @@ int tc_joint_chi2_batch_device(tc_joint* joint, const double* theta_device, int 
                                const double* precision, double* ngal_device,
                                double* chi2_device) {
   const Chi2Host operands{data, precision};
-  return joint_forward_entry(joint, false,
+  return joint_forward_entry(JointForward{{joint}}, GradRoute::kDevice,
                              joint_forward_request(joint, theta_device, n_theta, n_draws, n_gauss,
                                                    flags, ngal_device, chi2_device, true),
                              &operands);
@@ -625,7 +543,7 @@ int tc_joint_chi2_batch(tc_joint* joint, const double* theta, int n_theta, int64
                         int n_gauss, unsigned flags, const double* data, const double* precision,
                         double* ngal, double* chi2) {
   const Chi2Host operands{data, precision};
-  return joint_forward_entry(joint, true,
+  return joint_forward_entry(JointForward{{joint}}, GradRoute::kHost,
                              joint_forward_request(joint, theta, n_theta, n_draws, n_gauss, flags,
                                                    ngal, chi2, true),
                              &operands);

@@ -9,6 +9,8 @@
 // The forward entries -- the concatenated prediction or chi2 alone -- take ONE launch of
 // joint_interp_forward_kernel (joint_interp_forward_kernels.hip.h) on the mode-auto members' own
 // forward unit layouts, and the forward call path of the tables (predict_call.h) through member 0.
+#include <optional>
+
 #include "internal.h"
 
 using namespace tc::host;
@@ -32,10 +34,6 @@ struct tc_joint_interp {
 };
 
 namespace {
-
-int joint_params(unsigned flags) {
-  return (flags & TC_FLAG_ASSEMBIAS) ? tc::kGradParamsAssembias : tc::kGradParams;
-}
 
 tc_table* table_of(const tc_joint_interp* joint, int member) { return joint->tables[member][0]; }
 
@@ -64,9 +62,24 @@ int build_matrices(tc_joint_interp* joint) {
   return TC_OK;
 }
 
-// A joint of interpolators as grad_entry sees it: it works through member 0.
-struct JointInterpGrad {
+// What every call of a joint of interpolators shares (grad_entry, joint_forward_entry): it works
+// through member 0.
+struct JointInterpHandle {
   tc_joint_interp* joint;
+  tc_interp* first() const { return joint->members[0]; }
+  int device_id() const { return joint->device; }
+  Chi2Operands& operands() const { return joint->chi2; }
+  // (the launches go to member 0's lanes: earlier kernels there may still read the old operands)
+  int upload_chi2(const Chi2Host& host) const {
+    tc_interp* it = first();
+    return joint->chi2.upload(joint->n_r_total, host.data, host.precision,
+                              interp_grad_staging(it).stream,
+                              [it] { return tc_interp_synchronize(it); });
+  }
+};
+
+// A joint of interpolators as grad_entry sees it.
+struct JointInterpGrad : JointInterpHandle {
   // What the interpolator entry points refuse (check_grad_args on member 0's first table, the
   // family's flag taken out of the flags; the tables are float64 and share their bins node by
   // node by construction) and a joint beyond the LDS of a workgroup.
@@ -83,11 +96,7 @@ struct JointInterpGrad {
     return status;
   }
   const char* null_message(bool) const { return "NULL pointer"; }
-  int device_id() const { return joint->device; }
-  Chi2Operands& operands() const { return joint->chi2; }
-  // (the launches go to member 0's lanes: earlier kernels there may still read the old operands)
-  int drain() const { return tc_interp_synchronize(joint->members[0]); }
-  GradStaging staging() const { return interp_grad_staging(joint->members[0]); }
+  GradStaging staging() const { return interp_grad_staging(first()); }
   // One launch per slab of draws on lane 0 (pinned) or the next lane of member 0; the resident
   // kernels of every table of every member stop.
   int device(GradLane lane, const GradRequest& request) const {
@@ -188,169 +197,11 @@ int joint_interp_forward_fit(int n_bins, int n_members, const int* mode, const i
   return TC_OK;
 }
 
-// The arguments of a forward entry point, the NULL handle first; then what the kernel refuses.
-int check_joint_interp_forward(const tc_joint_interp* joint, const PredictRequest& request) {
-  TC_CHECK(joint != nullptr, "joint handle is NULL");
-  const unsigned flags = request.flags;
-  if (flags & TC_FLAG_SEPARATE_GAL_TYPE)
-    return fail(TC_ERR_UNSUPPORTED, "joint interpolator forward calls are implemented for the "
-                                    "total prediction only (not separate_gal_type)");
-  if (flags & TC_FLAG_LEAUTHAUD11)
-    return fail(TC_ERR_UNSUPPORTED, "joint interpolator forward calls are implemented for the "
-                                    "Zheng07 family only");
-  const unsigned unserved =
-      flags & ~(unsigned)(TC_FLAG_MODULATE_WITH_CENOCC | TC_FLAG_ASSEMBIAS);
-  if (unserved != 0)
-    return fail(TC_ERR_UNSUPPORTED, "joint interpolator forward calls: unknown flags 0x%x",
-                unserved);
-  const tc_table* t0 = table_of(joint, 0);
-  int status = check_predict_args(t0, request.theta, request.n_theta, request.n_draws,
-                                  request.n_gauss, flags);
-  if (status != TC_OK) return status;
-  const InterpParts first = interp_parts(joint->members[0]);
-  int n_axis[tc::kGradMaxDim];
-  for (int d = 0; d < joint->n_dim; ++d) n_axis[d] = (int)(*first.xp)[d].size();
-  status = joint_interp_forward_fit(t0->n_bins, (int)joint->members.size(), joint->mode.data(),
-                                    joint->n_r.data(), joint->n_dim, n_axis, nullptr, nullptr);
-  if (status != TC_OK) return status;
-  for (size_t m = 0; m < joint->members.size(); ++m) {
-    if (joint->mode[m] != TC_MODE_AUTO) continue;
-    for (const tc_table* t : joint->tables[m]) {
-      const tc::QuadLayout& layout = t->quad_total.layout;
-      if (!(t->quad && t->quad_total.d_table != nullptr && t->quad_tiling.n_rtiles == 1 &&
-            layout.comps.size() == 1 && layout.comps[0].triangular))
-        return fail(TC_ERR_UNSUPPORTED,
-                    "joint interpolator forward calls: a table of member %d (mode auto, %d bins) "
-                    "does not have the unit layout of the one-launch form", (int)m, t->n_bins);
-    }
-  }
-  return TC_OK;
-}
-
-// The argument block but for the draws and the outputs: the resident kernels of every table
-// stop, member 0's walk and classes are built (interp_grad_args, without the gradient matrices:
-// only a mode-cross member's (bins, r) matrices are built here), every member's matrices are
-// matched to the walk, the passes are numbered.
-int joint_interp_forward_args(tc_joint_interp* joint, int n_theta, int n_gauss, unsigned flags,
-                              tc::JointInterpForwardArgs* out) {
-  tc_table* t0 = table_of(joint, 0);
-  GradRequest walk{};
-  walk.n_params = joint_params(flags);
-  walk.n_gauss = n_gauss;
-  walk.flags = flags;
-  tc::GradInterpArgs ia{};
-  // (the walk and the classes alone: no table's gradient matrix is built for a forward call)
-  int status = interp_grad_args(joint->members[0], walk, &ia, /*with_matrices=*/false);
-  if (status != TC_OK) return status;
-  tc::JointInterpForwardArgs ja{};
-  ja.n_theta = n_theta;
-  ja.n_dim = joint->n_dim;
-  ja.n_bins = t0->n_bins;
-  ja.n_central = t0->plan.n_central;
-  ja.n_gauss = n_gauss;
-  ja.dens_rows = (t0->n_bins + 3) / 4 * 4;
-  ja.n_r = joint->n_r_total;
-  ja.split = 0.5;
-  ja.math_table = (const double*)t0->d_math_table;
-  for (int d = 0; d < joint->n_dim; ++d) {
-    ja.n_axis[d] = ia.n_axis[d];
-    ja.axis_offset[d] = ia.axis_offset[d];
-    ja.a_offset[d] = ia.a_offset[d];
-    ja.weight_row[d] = ja.n_weight_rows;
-    ja.n_weight_rows += ia.n_axis[d];
-  }
-  ja.xp = ia.xp;
-  ja.a = ia.a;
-  ja.n_classes = ia.n_classes;
-  ja.class_begin = ia.class_begin;
-  ja.walk_node = ia.walk_node;
-  ja.class_log_m = ia.class_log_m;
-  ja.class_m = ia.class_m;
-  ja.class_weight = ia.class_weight;
-  ja.class_n_h = ia.class_n_h;
-  ja.class_percentile = ia.class_percentile;
-  ja.n_members = (int)joint->members.size();
-  const int parts = tc::joint_forward_parts(tc::kJointForwardWaves);
-  bool first_auto = true;
-  for (int m = 0; m < ja.n_members; ++m) {
-    const std::vector<tc_table*>& tables = joint->tables[m];
-    const bool is_auto = joint->mode[m] == TC_MODE_AUTO;
-    for (tc_table* t : tables) {
-      if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
-      if (!is_auto && (status = build_grad_table(t)) != TC_OK) return status;
-    }
-    if (joint->d_forward_matrices[m] == nullptr) {
-      std::vector<void*> matrices;
-      for (int32_t k : joint->order[m])
-        matrices.push_back(is_auto ? tables[k]->quad_total.d_table : tables[k]->grad.d_matrix);
-      if ((status = upload(matrices, &joint->d_forward_matrices[m])) != TC_OK) return status;
-    }
-    ja.mode[m] = joint->mode[m];
-    ja.n_rows[m] = joint->n_r[m];
-    ja.r_offset[m] = joint->r_offset[m];
-    ja.matrices[m] = (const void* const*)joint->d_forward_matrices[m];
-    ja.job_begin[m + 1] = ja.job_begin[m];
-    if (!is_auto) continue;
-    const tc_table* t = tables[0];
-    const tc::QuadComp& comp = t->quad_total.layout.comps[0];
-    const int n_u = t->quad_tiling.n_u;
-    ja.n_u[m] = n_u;
-    ja.table_bytes[m] =
-        (uint32_t)((size_t)t->quad_total.layout.n_units * (size_t)((n_u + 1) / 2) * 1024);
-    ja.job_begin[m + 1] += (n_u + 1) / 2 * 2 * parts;
-    if (first_auto) {
-      tc::triangle_parts(comp.n_rb, parts, ja.part_rb0, ja.part_cb0, ja.part_count);
-      ja.n_cb = comp.n_cb;
-      ja.i_row0 = comp.i_bin0;
-      ja.j_row0 = comp.j_bin0;
-      ja.unit_base = (int)comp.unit_base;
-      first_auto = false;
-    }
-  }
-  *out = ja;
-  return TC_OK;
-}
-
-// One launch per slab of the draws of `r` (device pointers) on `stream`, timed and reported
-// through member 0's first table.
-int joint_interp_forward_launches(tc_joint_interp* joint, const tc::JointInterpForwardArgs& shape,
-                                  const PredictRequest& r, hipStream_t stream) {
-  Range range("joint interpolator forward (one launch)");
-  tc_table* t0 = table_of(joint, 0);
-  const int lds = (int)tc::joint_interp_forward_lds_bytes(
-      joint->form, shape.n_bins, shape.n_r, shape.n_weight_rows, tc::kJointForwardWaves);
-  return for_each_slab(r.n_draws, max_slab(t0), [&](int64_t begin, int64_t n) {
-    const PredictRequest slab = r.chunk(begin, n);
-    tc::JointInterpForwardArgs ja = shape;
-    ja.theta = slab.theta;
-    ja.x = slab.x;
-    ja.n_draws = n;
-    ja.ngal = slab.ngal;
-    ja.xi = r.likelihood ? nullptr : slab.second;
-    ja.chi2_data = r.likelihood ? joint->chi2.device() : nullptr;
-    ja.chi2 = r.likelihood ? slab.second : nullptr;
-    const dim3 grid((unsigned)((n + tc::kJointForwardDraws - 1) / tc::kJointForwardDraws));
-    hipEvent_t k0 = nullptr, k1 = nullptr;
-    int status = next_kernel_events(t0, &k0, &k1);
-    if (status != TC_OK) return status;
-    status = launch_joint_interp_forward_instance(
-        shape.n_gauss, (r.flags & TC_FLAG_ASSEMBIAS) != 0,
-        (r.flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0, joint->form, joint->device, grid, lds,
-        stream, k0, k1, ja);
-    if (status != TC_OK) return status;
-    t0->last_workgroups = (int)grid.x;
-    t0->last_waves = tc::kJointForwardWaves;
-    t0->last_splits = 0;
-    t0->last_lds = lds;
-    return TC_OK;
-  });
-}
-
-// A joint of interpolators as forward_chunked and forward_zero_copy see it (joint.cpp:
-// JointForward): it works through member 0 -- the staging areas, the tickets and the lanes are
-// that interpolator's.
-struct JointInterpForward {
+// A joint of interpolators as joint_forward_entry, forward_chunked and forward_zero_copy see it
+// (joint.cpp: JointForward): the staging areas, the tickets and the lanes are member 0's.
+struct JointInterpForward : JointInterpHandle {
   static constexpr bool kThreadedCopyOut = true;
+  using Args = tc::JointInterpForwardArgs;
   // member 0's staging areas under the names the forward path reads
   struct Staging {
     PinnedBuffer& h_in;
@@ -358,17 +209,150 @@ struct JointInterpForward {
     Tickets& tickets;
     hipStream_t stream;
   };
-  tc_joint_interp* joint;
-  const tc::JointInterpForwardArgs* shape;
-  Staging areas;
-  const Staging* handle() const { return &areas; }
+  const Args* shape = nullptr;
+  std::optional<Staging> areas;   // (from args() on: the handle is known not to be NULL)
+  // The arguments of a forward entry point, the NULL handle first; then what the kernel refuses.
+  int check(const PredictRequest& request) const {
+    TC_CHECK(joint != nullptr, "joint handle is NULL");
+    int status = check_joint_forward_flags("joint interpolator forward calls", request.flags);
+    if (status != TC_OK) return status;
+    const tc_table* t0 = table_of(joint, 0);
+    status = check_predict_args(t0, request.theta, request.n_theta, request.n_draws,
+                                request.n_gauss, request.flags);
+    if (status != TC_OK) return status;
+    const InterpParts parts = interp_parts(first());
+    int n_axis[tc::kGradMaxDim];
+    for (int d = 0; d < joint->n_dim; ++d) n_axis[d] = (int)(*parts.xp)[d].size();
+    status = joint_interp_forward_fit(t0->n_bins, (int)joint->members.size(), joint->mode.data(),
+                                      joint->n_r.data(), joint->n_dim, n_axis, nullptr, nullptr);
+    if (status != TC_OK) return status;
+    for (size_t m = 0; m < joint->members.size(); ++m) {
+      if (joint->mode[m] != TC_MODE_AUTO) continue;
+      for (const tc_table* t : joint->tables[m])
+        if (!has_joint_forward_layout(t))
+          return fail(TC_ERR_UNSUPPORTED,
+                      "joint interpolator forward calls: a table of member %d (mode auto, %d "
+                      "bins) does not have the unit layout of the one-launch form",
+                      (int)m, t->n_bins);
+    }
+    return TC_OK;
+  }
+  // The argument block but for the draws and the outputs: the resident kernels of every table
+  // stop, member 0's walk and classes are built (interp_grad_args, without the gradient matrices:
+  // only a mode-cross member's (bins, r) matrices are built here), every member's matrices are
+  // matched to the walk, the passes are numbered; member 0's staging areas are taken.
+  int args(const PredictRequest& request, Args* out) {
+    const InterpForwardParts parts = interp_forward_parts(first());
+    areas.emplace(Staging{*parts.h_in, *parts.h_out, *parts.tickets, parts.stream});
+    const tc_table* t0 = table_of(joint, 0);
+    GradRequest walk{};
+    walk.n_params = joint_params(request.flags);
+    walk.n_gauss = request.n_gauss;
+    walk.flags = request.flags;
+    tc::GradInterpArgs ia{};
+    // (the walk and the classes alone: no table's gradient matrix is built for a forward call)
+    int status = interp_grad_args(first(), walk, &ia, /*with_matrices=*/false);
+    if (status != TC_OK) return status;
+    Args ja{};
+    ja.n_theta = request.n_theta;
+    ja.n_dim = joint->n_dim;
+    ja.n_bins = t0->n_bins;
+    ja.n_central = t0->plan.n_central;
+    ja.n_gauss = request.n_gauss;
+    ja.dens_rows = (t0->n_bins + 3) / 4 * 4;
+    ja.n_r = joint->n_r_total;
+    ja.split = 0.5;
+    ja.math_table = (const double*)t0->d_math_table;
+    for (int d = 0; d < joint->n_dim; ++d) {
+      ja.n_axis[d] = ia.n_axis[d];
+      ja.axis_offset[d] = ia.axis_offset[d];
+      ja.a_offset[d] = ia.a_offset[d];
+      ja.weight_row[d] = ja.n_weight_rows;
+      ja.n_weight_rows += ia.n_axis[d];
+    }
+    ja.xp = ia.xp;
+    ja.a = ia.a;
+    ja.n_classes = ia.n_classes;
+    ja.class_begin = ia.class_begin;
+    ja.walk_node = ia.walk_node;
+    ja.class_log_m = ia.class_log_m;
+    ja.class_m = ia.class_m;
+    ja.class_weight = ia.class_weight;
+    ja.class_n_h = ia.class_n_h;
+    ja.class_percentile = ia.class_percentile;
+    ja.n_members = (int)joint->members.size();
+    for (int m = 0; m < ja.n_members; ++m) {
+      const std::vector<tc_table*>& tables = joint->tables[m];
+      const bool is_auto = joint->mode[m] == TC_MODE_AUTO;
+      for (tc_table* t : tables) {
+        if (t->resident.running && (status = resident_stop(t)) != TC_OK) return status;
+        if (!is_auto && (status = build_grad_table(t)) != TC_OK) return status;
+      }
+      if (joint->d_forward_matrices[m] == nullptr) {
+        std::vector<void*> matrices;
+        for (int32_t k : joint->order[m])
+          matrices.push_back(is_auto ? tables[k]->quad_total.d_table : tables[k]->grad.d_matrix);
+        if ((status = upload(matrices, &joint->d_forward_matrices[m])) != TC_OK) return status;
+      }
+      ja.matrices[m] = (const void* const*)joint->d_forward_matrices[m];
+      number_joint_forward_member(&ja, m, joint->mode[m], joint->n_r[m], joint->r_offset[m],
+                                  tables[0]);
+    }
+    *out = ja;
+    return TC_OK;
+  }
+  // One launch per slab of the draws of `r` (device pointers) on `stream`.
+  int launches(const PredictRequest& r, hipStream_t stream) const {
+    Range range("joint interpolator forward (one launch)");
+    const int lds = (int)tc::joint_interp_forward_lds_bytes(
+        joint->form, shape->n_bins, shape->n_r, shape->n_weight_rows, tc::kJointForwardWaves);
+    return joint_forward_slabs(
+        table_of(joint, 0), *shape, joint->chi2.device(), r, lds,
+        [&](Args& ja, const PredictRequest& slab, dim3 grid, hipEvent_t k0, hipEvent_t k1) {
+          ja.x = slab.x;
+          return launch_joint_interp_forward_instance(
+              shape->n_gauss, (r.flags & TC_FLAG_ASSEMBIAS) != 0,
+              (r.flags & TC_FLAG_MODULATE_WITH_CENOCC) != 0, joint->form, joint->device, grid, lds,
+              stream, k0, k1, ja);
+        });
+  }
+  // (member 0's next lane)
+  int device(const PredictRequest& request) const {
+    return launches(request, interp_grad_stream(first(), GradLane::kNext));
+  }
+  const char* missing(const PredictRequest& r) const {
+    return r.x && r.ngal && r.second ? nullptr : "NULL pointer";
+  }
+  tc::SyncChunkPlan plan(const PredictRequest& request) const {
+    return plan_forward_chunks(table_of(joint, 0), interp_forward_parts(first()).n_lanes, false,
+                               false, request);
+  }
+  // (the draws by two copy commands into member 0's buffers)
+  int copy_up(const PredictRequest& request, const double** theta, const double** x,
+              double** out) const {
+    const InterpForwardParts parts = interp_forward_parts(first());
+    int status = parts.theta->reserve(request.theta_bytes(), parts.stream);
+    if (status == TC_OK) status = parts.x->reserve(request.x_bytes(), parts.stream);
+    if (status == TC_OK) status = parts.out->reserve(request.out_bytes(), parts.stream);
+    if (status != TC_OK) return status;
+    TC_HIP(hipMemcpyAsync(parts.theta->ptr, request.theta, request.theta_bytes(),
+                          hipMemcpyHostToDevice, parts.stream));
+    TC_HIP(hipMemcpyAsync(parts.x->ptr, request.x, request.x_bytes(), hipMemcpyHostToDevice,
+                          parts.stream));
+    *theta = (const double*)parts.theta->ptr;
+    *x = (const double*)parts.x->ptr;
+    *out = (double*)parts.out->ptr;
+    return TC_OK;
+  }
+
+  const Staging* handle() const { return &*areas; }
   // (one form: a draw's result does not depend on the chunks)
   Call hints(const PredictRequest&, const tc::SyncChunkPlan&) const { return Call(); }
   std::vector<hipEvent_t>* chunk_events() const { return nullptr; }   // (never staggered)
   // A chunk on member 0's next lane: draws up, the launch, results down, the ticket.
   int enqueue(const PredictRequest& part, const Call&, hipEvent_t, hipEvent_t,
               int64_t* ticket) const {
-    const InterpForwardLane lane = interp_forward_lane(joint->members[0]);
+    const InterpForwardLane lane = interp_forward_lane(first());
     int status = lane.stage_in->reserve(part.in_bytes(), lane.stream);
     if (status == TC_OK) status = lane.stage_out->reserve(part.out_bytes(), lane.stream);
     if (status != TC_OK) return status;
@@ -377,20 +361,17 @@ struct JointInterpForward {
     double* in = (double*)lane.stage_in->ptr;
     double* result = (double*)lane.stage_out->ptr;
     TC_HIP(hipMemcpyAsync(in, part.theta, part.in_bytes(), hipMemcpyHostToDevice, lane.stream));
-    status = joint_interp_forward_launches(
-        joint, *shape,
+    status = launches(
         part.on(in, in + part.n_draws * part.n_theta, result, result + part.ngal_count()),
         lane.stream);
     if (status != TC_OK) return status;
     TC_HIP(hipMemcpyAsync(part.ngal, result, part.out_bytes(), hipMemcpyDeviceToHost,
                           lane.stream));
-    return areas.tickets.issue(lane.stream, ticket);
+    return areas->tickets.issue(lane.stream, ticket);
   }
-  int synchronize() const { return tc_interp_synchronize(joint->members[0]); }
+  int synchronize() const { return tc_interp_synchronize(first()); }
   // (lane 0 of member 0)
-  int run(const PredictRequest& s) const {
-    return joint_interp_forward_launches(joint, *shape, s, areas.stream);
-  }
+  int run(const PredictRequest& s) const { return launches(s, areas->stream); }
 };
 
 // The request of a forward entry point, in the order of the C arguments.
@@ -400,53 +381,6 @@ PredictRequest joint_interp_forward_request(const tc_joint_interp* joint, const 
                                             double* second, bool likelihood) {
   return PredictRequest{n_theta, joint ? joint->n_dim : 0, n_gauss, flags, n_draws,
                         joint ? joint->n_r_total : 0, 1, theta, x, ngal, second, likelihood};
-}
-
-// Every forward entry point: the checks, the likelihood's operands, then the launches on device
-// pointers (member 0's next lane) or the forward path of host arrays.
-int joint_interp_forward_entry(tc_joint_interp* joint, bool host, const PredictRequest& request,
-                               const Chi2Host* operands) {
-  int status = check_joint_interp_forward(joint, request);
-  if (status != TC_OK) return status;
-  if (request.n_draws == 0) return TC_OK;
-  TC_CHECK(request.x && request.ngal && request.second, "NULL pointer");
-  TC_CHECK(operands == nullptr || (operands->data && operands->precision), "NULL pointer");
-  tc_interp* first = joint->members[0];
-  const InterpForwardParts parts = interp_forward_parts(first);
-  TC_HIP(hipSetDevice(joint->device));
-  if (operands != nullptr) {
-    status = joint->chi2.upload(joint->n_r_total, operands->data, operands->precision,
-                                parts.stream, [&] { return tc_interp_synchronize(first); });
-    if (status != TC_OK) return status;
-  }
-  tc::JointInterpForwardArgs shape;
-  status = joint_interp_forward_args(joint, request.n_theta, request.n_gauss, request.flags,
-                                     &shape);
-  if (status != TC_OK) return status;
-  if (!host)
-    return joint_interp_forward_launches(joint, shape, request,
-                                         interp_grad_stream(first, GradLane::kNext));
-  const JointInterpForward forward{joint, &shape,
-                                   {*parts.h_in, *parts.h_out, *parts.tickets, parts.stream}};
-  if (zero_copy_serves(forward, request)) return forward_zero_copy(forward, request);
-  const tc::SyncChunkPlan plan =
-      plan_forward_chunks(table_of(joint, 0), parts.n_lanes, false, false, request);
-  if (plan.n_chunks > 0) return forward_chunked(forward, request, plan);
-  status = parts.theta->reserve(request.theta_bytes(), parts.stream);
-  if (status == TC_OK) status = parts.x->reserve(request.x_bytes(), parts.stream);
-  if (status == TC_OK) status = parts.out->reserve(request.out_bytes(), parts.stream);
-  if (status != TC_OK) return status;
-  TC_HIP(hipMemcpyAsync(parts.theta->ptr, request.theta, request.theta_bytes(),
-                        hipMemcpyHostToDevice, parts.stream));
-  TC_HIP(hipMemcpyAsync(parts.x->ptr, request.x, request.x_bytes(), hipMemcpyHostToDevice,
-                        parts.stream));
-  double* d_ngal = (double*)parts.out->ptr;
-  double* d_second = d_ngal + request.ngal_count();
-  status = forward.run(request.on((const double*)parts.theta->ptr, (const double*)parts.x->ptr,
-                                  d_ngal, d_second));
-  if (status != TC_OK) return status;
-  return copy_out(parts.h_out, request.ngal, request.ngal_count(), d_ngal, request.second,
-                  request.second_count(), d_second, parts.stream);
 }
 
 }  // namespace
@@ -594,8 +528,8 @@ int tc_joint_interp_predict_batch_device(tc_joint_interp* joint, const double* t
                                          int n_theta, const double* x_device, int64_t n_draws,
                                          int n_gauss, unsigned flags, double* ngal_device,
                                          double* xi_device) {
-  return joint_interp_forward_entry(
-      joint, false,
+  return joint_forward_entry(
+      JointInterpForward{{joint}}, GradRoute::kDevice,
       joint_interp_forward_request(joint, theta_device, n_theta, x_device, n_draws, n_gauss, flags,
                                    ngal_device, xi_device, false),
       nullptr);
@@ -604,8 +538,8 @@ int tc_joint_interp_predict_batch_device(tc_joint_interp* joint, const double* t
 int tc_joint_interp_predict_batch(tc_joint_interp* joint, const double* theta, int n_theta,
                                   const double* x, int64_t n_draws, int n_gauss, unsigned flags,
                                   double* ngal, double* xi) {
-  return joint_interp_forward_entry(
-      joint, true,
+  return joint_forward_entry(
+      JointInterpForward{{joint}}, GradRoute::kHost,
       joint_interp_forward_request(joint, theta, n_theta, x, n_draws, n_gauss, flags, ngal, xi,
                                    false),
       nullptr);
@@ -617,8 +551,8 @@ int tc_joint_interp_chi2_batch_device(tc_joint_interp* joint, const double* thet
                                       const double* precision, double* ngal_device,
                                       double* chi2_device) {
   const Chi2Host operands{data, precision};
-  return joint_interp_forward_entry(
-      joint, false,
+  return joint_forward_entry(
+      JointInterpForward{{joint}}, GradRoute::kDevice,
       joint_interp_forward_request(joint, theta_device, n_theta, x_device, n_draws, n_gauss, flags,
                                    ngal_device, chi2_device, true),
       &operands);
@@ -629,8 +563,8 @@ int tc_joint_interp_chi2_batch(tc_joint_interp* joint, const double* theta, int 
                                const double* data, const double* precision, double* ngal,
                                double* chi2) {
   const Chi2Host operands{data, precision};
-  return joint_interp_forward_entry(
-      joint, true,
+  return joint_forward_entry(
+      JointInterpForward{{joint}}, GradRoute::kHost,
       joint_interp_forward_request(joint, theta, n_theta, x, n_draws, n_gauss, flags, ngal, chi2,
                                    true),
       &operands);

@@ -866,18 +866,24 @@ int tc_chi2_zheng07_batch(tc_table* t, const double* theta, int n_theta,
 
 namespace {
 
-// A table as grad_entry sees it.
-struct TableGrad {
+// What the derivative entries of a table share (grad_call.h: grad_entry, vjp_entry).
+struct TableHandle {
   tc_table* t;
+  int device_id() const { return t->device; }
+  Chi2Operands& operands() const { return t->chi2; }
+  int upload_chi2(const Chi2Host& host) const {
+    return upload_operands(t, host.data, host.precision);
+  }
+};
+
+// A table as grad_entry sees it.
+struct TableGrad : TableHandle {
   int check(const GradRequest& request, int n_theta, bool likelihood) const {
     return check_grad_args(t, request, n_theta, likelihood, /*fit=*/true);
   }
   const char* null_message(bool likelihood) const {
     return likelihood ? "NULL pointer" : "output pointer is NULL";
   }
-  int device_id() const { return t->device; }
-  Chi2Operands& operands() const { return t->chi2; }
-  int drain() const { return drain_lanes(t); }      // each lane's stream
   GradStaging staging() const {
     return {&t->theta, nullptr, &t->out_ngal, &t->out_xi, t->stream};
   }
@@ -1068,27 +1074,32 @@ int tc_chi2_grad_leauthaud11_batch(tc_table* t, const double* theta, int n_theta
                     n_theta, &operands, false);
 }
 
-// ---- occupation VJP (launch.hip: run_vjp) -------------------------------------------------
+// ---- occupation VJP (grad_call.h: vjp_entry; launch.hip: run_vjp) -------------------------
 
 namespace {
 
-// The request of a table's entry point at the occupation seam, in the order of the C arguments.
-VjpRequest vjp_request(const tc_table* t, const double* occupation, int64_t n_draws,
-                       const double* g_ngal, const double* g_xi, const double* chi2_data,
-                       double* ngal, double* xi, double* chi2, double* g_occupation) {
-  return VjpRequest{n_draws,   t->n_bins, t->n_r, occupation, g_ngal,       g_xi,
-                    chi2_data, ngal,      xi,     chi2,       g_occupation, 1,
-                    0,         nullptr,   nullptr, nullptr};
-}
-
-// (the launcher of the staging path: one launch of the table's kernel per slab)
-struct VjpLauncher {
-  tc_table* t;
-  int operator()(const VjpRequest& slab, hipStream_t stream) const {
-    return run_vjp(t, slab, stream);
+// A table as vjp_entry sees it: no forward-only form, every adjoint array is required.
+struct TableVjp : TableHandle {
+  int check(int64_t n_draws, unsigned flags) const { return check_vjp_args(t, n_draws, flags); }
+  VjpRule rule() const { return {false, false, {nullptr, nullptr}}; }
+  VjpStaging staging() const {
+    return {&t->occupation, &t->out_ngal, &t->out_xi, t->stream, max_slab(t)};
+  }
+  // (grad_slabs, as TableGrad: one launch of the table's kernel per slab)
+  int device(GradLane lane, const VjpRequest& request) const {
+    return grad_slabs(t, lane, request.n_draws, [&](int64_t begin, int64_t n, hipStream_t stream) {
+      return run_vjp(t, request.slab(begin, n), stream);
+    });
   }
 };
-VjpLauncher vjp_launcher(tc_table* t) { return VjpLauncher{t}; }
+
+// The request of a table's entry point at the occupation seam, in the order of the C arguments.
+VjpRequest vjp_request(const tc_table* t, const double* occupation, int64_t n_draws,
+                       const double* g_ngal, const double* g_xi, double* ngal, double* xi,
+                       double* chi2, double* g_occupation) {
+  return VjpRequest{n_draws, t ? t->n_bins : 0, t ? t->n_r : 0, occupation, g_ngal, g_xi,
+                    nullptr, ngal, xi, chi2, g_occupation, 1, 0, nullptr, nullptr, nullptr};
+}
 
 }  // namespace
 
@@ -1097,63 +1108,40 @@ int tc_predict_occupation_vjp_batch_device(tc_table* t, const double* occupation
                                            const double* g_ngal_device, const double* g_xi_device,
                                            double* ngal_device, double* xi_device,
                                            double* g_occupation_device) {
-  const int status = check_vjp_args(t, n_draws, flags);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(occupation_device && g_xi_device && ngal_device && xi_device && g_occupation_device,
-           "NULL pointer");
-  return vjp_device(t, GradLane::kNext,
-                    vjp_request(t, occupation_device, n_draws, g_ngal_device, g_xi_device, nullptr,
-                                ngal_device, xi_device, nullptr, g_occupation_device),
-                    vjp_launcher(t));
+  return vjp_entry(TableVjp{t}, GradRoute::kDevice, flags,
+                   vjp_request(t, occupation_device, n_draws, g_ngal_device, g_xi_device,
+                               ngal_device, xi_device, nullptr, g_occupation_device),
+                   nullptr);
 }
 
 int tc_predict_occupation_vjp_batch(tc_table* t, const double* occupation, int64_t n_draws,
                                     unsigned flags, const double* g_ngal, const double* g_xi,
                                     double* ngal, double* xi, double* g_occupation) {
-  const int status = check_vjp_args(t, n_draws, flags);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(occupation && g_xi && ngal && xi && g_occupation, "NULL pointer");
-  return vjp_host(t,
-                  vjp_request(t, occupation, n_draws, g_ngal, g_xi, nullptr, ngal, xi, nullptr,
-                              g_occupation),
-                  vjp_launcher(t));
+  return vjp_entry(TableVjp{t}, GradRoute::kHost, flags,
+                   vjp_request(t, occupation, n_draws, g_ngal, g_xi, ngal, xi, nullptr,
+                               g_occupation),
+                   nullptr);
 }
 
 int tc_chi2_occupation_grad_batch_device(tc_table* t, const double* occupation_device,
                                          int64_t n_draws, unsigned flags, const double* data,
                                          const double* precision, double* ngal_device,
                                          double* chi2_device, double* dchi2_docc_device) {
-  int status = check_vjp_args(t, n_draws, flags);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(occupation_device && data && precision && ngal_device && chi2_device &&
-               dchi2_docc_device,
-           "NULL pointer");
-  TC_HIP(hipSetDevice(t->device));
-  status = upload_operands(t, data, precision);
-  if (status != TC_OK) return status;
-  return vjp_device(t, GradLane::kNext,
-                    vjp_request(t, occupation_device, n_draws, nullptr, nullptr, t->chi2.device(),
-                                ngal_device, nullptr, chi2_device, dchi2_docc_device),
-                    vjp_launcher(t));
+  const Chi2Host operands{data, precision};
+  return vjp_entry(TableVjp{t}, GradRoute::kDevice, flags,
+                   vjp_request(t, occupation_device, n_draws, nullptr, nullptr, ngal_device,
+                               nullptr, chi2_device, dchi2_docc_device),
+                   &operands);
 }
 
 int tc_chi2_occupation_grad_batch(tc_table* t, const double* occupation, int64_t n_draws,
                                   unsigned flags, const double* data, const double* precision,
                                   double* ngal, double* chi2, double* dchi2_docc) {
-  int status = check_vjp_args(t, n_draws, flags);
-  if (status != TC_OK) return status;
-  if (n_draws == 0) return TC_OK;
-  TC_CHECK(occupation && data && precision && ngal && chi2 && dchi2_docc, "NULL pointer");
-  TC_HIP(hipSetDevice(t->device));
-  status = upload_operands(t, data, precision);
-  if (status != TC_OK) return status;
-  return vjp_host(t,
-                  vjp_request(t, occupation, n_draws, nullptr, nullptr, t->chi2.device(), ngal,
-                              nullptr, chi2, dchi2_docc),
-                  vjp_launcher(t));
+  const Chi2Host operands{data, precision};
+  return vjp_entry(TableVjp{t}, GradRoute::kHost, flags,
+                   vjp_request(t, occupation, n_draws, nullptr, nullptr, ngal, nullptr, chi2,
+                               dchi2_docc),
+                   &operands);
 }
 
 namespace {

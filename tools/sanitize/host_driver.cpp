@@ -479,6 +479,59 @@ static void check_grad_slabs() {
           }
 }
 
+// The completeness rules of the occupation seam (grad_call.h: vjp_incomplete) on listed cases per
+// handle kind, written out from the entries' documentation and not from the function: the arrays
+// that are there by letter -- o occupation, n ngal, v xi, c chi2, x x, g g_xi, G g_occupation
+// (dchi2_docc), X g_x (dchi2_dx), D dngal_dx -- and what the call is told: nothing (complete), a
+// NULL pointer, or the kind's words for adjoint arrays that go together.
+static void check_vjp_rules() {
+  using tc::host::VjpRequest;
+  using tc::host::VjpRule;
+  static double anchor[1];
+  enum { kTable, kJoint, kInterp };
+  const VjpRule rules[3] = {{false, false, {nullptr, nullptr}},
+                            {false, true, {"pair", nullptr}},
+                            {true, true, {"triple", "chi2 triple"}}};
+  const char* const null = "NULL pointer";
+  const struct Case { int kind; bool likelihood, operands; const char* there; const char* told; }
+  cases[] = {
+      // a table: every adjoint array of the form is required
+      {kTable, false, true, "onvgG", nullptr}, {kTable, false, true, "onvG", null},
+      {kTable, false, true, "onvg", null},     {kTable, false, true, "onv", null},
+      {kTable, false, true, "nvgG", null},     {kTable, false, true, "ovgG", null},
+      {kTable, false, true, "ongG", null},     {kTable, false, true, "oncgG", null},
+      {kTable, true, true, "oncG", nullptr},   {kTable, true, true, "onc", null},
+      {kTable, true, false, "oncG", null},     {kTable, true, true, "onvG", null},
+      // a joint: g_xi and g_occupation together, both NULL the forward-only form; the likelihood
+      // form has dchi2_docc alone, there or not
+      {kJoint, false, true, "onvgG", nullptr}, {kJoint, false, true, "onv", nullptr},
+      {kJoint, false, true, "onvg", "pair"},   {kJoint, false, true, "onvG", "pair"},
+      {kJoint, false, true, "ovgG", null},     {kJoint, false, true, "ong", null},
+      {kJoint, true, true, "oncG", nullptr},   {kJoint, true, true, "onc", nullptr},
+      {kJoint, true, false, "onc", null},      {kJoint, true, true, "ncG", null},
+      // an interpolator: x required; the triples together
+      {kInterp, false, true, "onvxgGX", nullptr},    {kInterp, false, true, "onvx", nullptr},
+      {kInterp, false, true, "onvxgG", "triple"},    {kInterp, false, true, "onvxX", "triple"},
+      {kInterp, false, true, "onvxgX", "triple"},    {kInterp, false, true, "onvxGXD", "triple"},
+      {kInterp, false, true, "onvgGX", null},        {kInterp, false, true, "onxgGX", null},
+      {kInterp, true, true, "oncxGXD", nullptr},     {kInterp, true, true, "oncx", nullptr},
+      {kInterp, true, true, "oncxGX", "chi2 triple"}, {kInterp, true, true, "oncxD", "chi2 triple"},
+      {kInterp, true, true, "oncxgG", "chi2 triple"}, {kInterp, true, true, "oncGXD", null},
+      {kInterp, true, false, "oncxGXD", null},       {kInterp, true, true, "onvxGXD", null},
+  };
+  for (const Case& c : cases) {
+    const auto at = [&](char letter) { return std::strchr(c.there, letter) ? anchor : nullptr; };
+    VjpRequest r{};
+    r.occupation = at('o'), r.ngal = at('n'), r.xi = at('v'), r.chi2 = at('c'), r.x = at('x');
+    r.g_xi = at('g'), r.g_occupation = at('G'), r.g_x = at('X'), r.dngal_dx = at('D');
+    const char* got = tc::host::vjp_incomplete(rules[c.kind], r, c.likelihood, c.operands);
+    EXPECT((got == nullptr) == (c.told == nullptr) &&
+               (got == nullptr || std::strcmp(got, c.told) == 0),
+           "seam rule of kind %d, likelihood %d, arrays %s: %s", c.kind, c.likelihood, c.there,
+           got ? got : "complete");
+  }
+}
+
 // hostmath.h: plan_sync_chunks over the sweep of tests/test_predict_call_cpu.py: boundaries from 0
 // to n_draws, strictly increasing, inner ones multiples of 64, at most 64 chunks, never staggered
 // for an interpolator or a likelihood; and the chunk arithmetic of the forward entry points
@@ -630,6 +683,7 @@ int main() {
   check_joint_interp();
   check_forward_calls();
   check_grad_slabs();
+  check_vjp_rules();
   check_quadrature();
   check_splines();
   check_plans();
