@@ -1000,6 +1000,14 @@ int tc_interp_query(tc_interp* interp, int64_t ticket, int* done);
  *                 zero blocks lie in the later parts.  BASELINE configs[1] 35.9 -> 34.4 us per
  *                 10^4 draws.  3: the parts paired as ever; 2: the draws where they are as
  *                 well; 0: every product.  Same bits all four (profiles/skip_notes.md).
+ *   "fused_share" 1 (default): with "fused_skip" 1, tables of 9-12 or 17-20 correlation
+ *                 function bins (a last r pass of one sub-tile): the waves of a workgroup walk
+ *                 their own parts of the matrix units for all r passes but the last and take the
+ *                 last passes of the workgroup's eight (tile, part) jobs from a counter in LDS,
+ *                 whoever comes first -- the waves whose parts had many zero blocks take more.
+ *                 configs[1] 34.2 -> 33.85 us per 10^4 draws.  2: sixteen items of one group of
+ *                 16 draws each (2.1 us behind); 0: every wave its own part's.  Same bits all
+ *                 three (profiles/share_notes.md).
  *   "cross_wide_min_draws"  default 4096.  Mode cross (tpcf_matrix with one column per halo
  *                 bin), tables or interpolators of up to 16 result rows whose node groups have
  *                 at most two members: undecorated batches of this many draws take the one-launch

@@ -117,4 +117,47 @@ TC_SKIP_FN void skip_consume(bool first, unsigned row_bits, unsigned unit_bits,
   else if (first && !(row_bits & 2u)) clear(SkipGroup<1>());
 }
 
+// ---- sharing the last r pass (option "fused_share", profiles/share_notes.md) ----------------
+// Where the last pass of a wave's part covers ONE r sub-tile (U = 3, 5), its sums meet no other
+// pass's, and the tile's two groups have accumulators of their own: the chain (tile, part, last
+// pass, group) gives the same bits on any wave at any time.  Instead of walking its own part a
+// last time every wave takes ITEMS from a counter in LDS until none is left -- nothing is
+// estimated, nobody waits: the waves whose parts had many zero blocks take more.
+//   share 1   8 items, one per (tile, part), both groups
+//   share 2   16 items, one per (tile, part, group)
+// The list is fixed, the heaviest expected first: the first part (all centrals: no zero
+// blocks) of both tiles, then the parts 3, 2 and 1.
+constexpr int kShareParts = 4;                    // parts per tile (eight waves, 64 draws)
+constexpr int kShareJobs = 2 * kShareParts;       // (tile, part): the slot 4 tile + part
+// LDS of the queue (words of 32 bits): the counter, a word per job that says its masks are
+// there, the jobs' masks (two words of 64 bits each)
+constexpr int kShareCounterWord = 0;
+constexpr int kShareFlagWord = 8;
+constexpr int kShareMaskWord = 16;
+constexpr int kShareWords = kShareMaskWord + 4 * kShareJobs;
+
+struct ShareItem {
+  int tile, part;
+  int select;              // 0 both groups, 1 the even columns' alone, 2 the odd ones'
+};
+
+TC_SKIP_FN int share_item_count(int share) { return share == 1 ? kShareJobs : share == 2 ? 2 * kShareJobs : 0; }
+
+TC_SKIP_FN ShareItem share_item(int share, int index) {
+  const int job = share == 2 ? index >> 1 : index;
+  const int turn = job >> 1;                      // 0: part 0; 1, 2, 3: parts 3, 2, 1
+  ShareItem item;
+  item.tile = job & 1;
+  item.part = turn == 0 ? 0 : kShareParts - turn;
+  item.select = share == 2 ? 1 + (index & 1) : 0;
+  return item;
+}
+
+// What an item ORs into a job's mask words: the bit of the OTHER group in every block, so that
+// skip_consume and the row ends leave that group out altogether.  Selecting is not skipping: it
+// holds where the guard has failed and the zero-block bits are all 0 as well.
+TC_SKIP_FN uint64_t share_select_bits(int select) {
+  return select == 1 ? 0xAAAAAAAAAAAAAAAAull : select == 2 ? 0x5555555555555555ull : 0ull;
+}
+
 }  // namespace tc

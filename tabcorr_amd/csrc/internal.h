@@ -392,6 +392,10 @@ struct Tuning {
                                 // draws of a workgroup in the order of M0, no products of all-zero
                                 // density blocks, the parts (0, 1) / (2, 3) on a SIMD; 3 the parts
                                 // paired as ever; 2 the draws where they are as well; 0 none of it
+  int fused_share = 1;          // ... with fused_skip 1 and U = 3 or 5: the last r pass as items the
+                                // waves take from a counter in LDS, 1 per (tile, part), 2 per
+                                // (tile, part, group); 0 every wave its own part's
+                                // (profiles/share_notes.md: 1 measured ahead, 2 behind)
   int fused_sat_cap = 6;        // ... in place up to 12 + 4 x this many terms (0 .. 5), or
                                 // 6 = series::sat::kShortest: the shortest that serves the bin
   int cross_wide_min_draws = 4096;   // launch.hip: choose_cross_fused (0: never the wide form)

@@ -354,7 +354,9 @@ struct FusedArgs {
   int priority;              // wave priorities: phase 2 | phase 1 << 2 | phase 3 << 4; bits 8 - 10:
                              // developer knobs; bit 11: every entry of the matrix is finite;
                              // bit 13: no products of all-zero density blocks, bit 14: a
-                             // workgroup's draws in the order of M0 (fused_skip.h)
+                             // workgroup's draws in the order of M0, bit 15: the parts (0, 1)
+                             // and (2, 3) on a SIMD, bits 16 - 17: the last r pass shared
+                             // through a queue, by job or by group (fused_skip.h)
   int64_t n_draws;
   const double* log_m;       // quadrature constants as in OccArgs
   const double* m;

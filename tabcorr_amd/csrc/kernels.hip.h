@@ -2388,6 +2388,12 @@ __device__ __forceinline__ void fused_quad_pass40(__amdgpu_buffer_rsrc_t rs_t, u
   }
 }
 
+__device__ __forceinline__ uint64_t wave_uniform(uint64_t value) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)value);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(value >> 32));
+  return ((uint64_t)hi << 32) | lo;
+}
+
 template <int NGAUSS, int U, bool ASSEMBIAS, bool MODULATE, bool LEAUTHAUD = false,
           int W = kFusedWaves, int DL = 64, bool GROUPED = false, int SATDEFER = 0>
 __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 : 2) : 1) void predict_fused_kernel(
@@ -2491,6 +2497,24 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
   // share their groups of 16 -- and, in phase 2, no products of all-zero blocks.  a.priority,
   // bit 13: skip, bit 14: order, bit 15: which parts share a SIMD.
   constexpr bool SKIP = SATDEFER == 2 && DL == 64 && W == 8;
+  // SHARE (fused_skip.h, a.priority bits 16 - 17): the last r pass, where it is a single
+  // sub-tile, as items that the waves take from a counter in LDS -- 1: one per (tile, part), 2:
+  // one per (tile, part, group); only with skipping, order and pairing all on.
+  constexpr bool SHARE = SKIP && (U == 3 || U == 5);
+  static_assert(!SHARE || (PARTS == kShareParts && kShareJobs * 4 * kQuadTile <= fm::kTableDoubles &&
+                           kShareJobs * 4 * kQuadTile <= 20 * (kLanes + 1)),
+                "the shared pass's sums in the place of the math table, below the likelihood's data");
+  int share = 0;
+  // (the queue's words: behind `red` -- the launch adds kShareWords words to the dynamic LDS of
+  // these instances; every word in front of them is in use up to the barrier behind the
+  // pair-weight sums, before which the counter has to be zero)
+  unsigned* const queue = SHARE ? (unsigned*)&red[2][0][0] : nullptr;
+  if constexpr (SHARE) {
+    if (((a.priority >> 13) & 7) == 7 && !(skip & 2)) share = (a.priority >> 16) & 3;
+    if (share > 2) share = 2;
+    // (a group is selected through the mask words: two bits per block)
+    if (share == 2 && a.dens_rows > 4 * kSkipMaxBlocks) share = 1;
+  }
   int at = draw;
   {
     // (every wave sets up its lanes' draws itself: cheaper than a hand-over through LDS)
@@ -2699,6 +2723,10 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     }
     wave_stamp(1);
     stamp(3);
+    if constexpr (SHARE) {
+      // (the counter and the jobs' words "masks are there": zero before anybody can take)
+      if (share != 0 && wave == 0 && lane < kShareMaskWord) queue[lane] = 0u;
+    }
     red[0][wave][lane] = sum_cen;
     red[1][wave][lane] = sum_sat;
     __syncthreads();
@@ -2800,10 +2828,12 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     // every draw's pair-weight sum below 1e280.  Only the blocks the part touches count: a wave
     // with no zero block among them -- the first part, the centrals' rows -- walks as ever.
     uint64_t mask_b = 0, mask_e = 0;
+    bool guard = false;
     if constexpr (SKIP) {
       if (((a.priority >> 11) & 1) && ((a.priority >> 13) & 1) &&
           a.dens_rows <= 4 * kSkipMaxBlocks &&
           __builtin_amdgcn_ballot_w64(!(norm < 1e280)) == 0) {
+        if constexpr (SHARE) guard = true;
         int rb_last = walk.rb0;
         for (int left = walk.count - (walk_row_length(walk, walk.rb0) - walk.cb0); left > 0;
              left -= walk_row_length(walk, rb_last))
@@ -2829,10 +2859,51 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
         }
       }
     }
+    // (the same words for any job of the workgroup -- the rows' straight from their blocks --:
+    // what a wave that takes an item does when the job's own wave has not published them yet)
+    auto job_masks = [&](int of_part, const FusedPart& of_walk, const double* of_b,
+                         const double* of_e, uint64_t& to_b, uint64_t& to_e) {
+      if (of_walk.count <= 0) return;
+      int rb_last = of_walk.rb0;
+      for (int left = of_walk.count - (walk_row_length(of_walk, of_walk.rb0) - of_walk.cb0);
+           left > 0; left -= walk_row_length(of_walk, rb_last))
+        ++rb_last;
+      auto masks = [&](const double* first, int row0, int block0, int block1) {
+        uint64_t mask = 0;
+        const int n_blocks = (a.dens_rows - row0) >> 2;
+        for (int block = block0; block <= block1 && block < n_blocks; ++block) {
+          const f64x2 value = *(const f64x2*)(first + 4 * block * DL);
+          const unsigned bits =
+              (__builtin_amdgcn_ballot_w64(!skip_is_zero(value.x)) == 0 ? 1u : 0u) |
+              (__builtin_amdgcn_ballot_w64(!skip_is_zero(value.y)) == 0 ? 2u : 0u);
+          mask |= (uint64_t)bits << (2 * block);
+        }
+        return mask;
+      };
+      to_b = masks(of_b, a.part_j_row0[of_part], 0,
+                   of_walk.triangular ? rb_last : of_walk.n_cb - 1);
+      to_e = masks(of_e + kq * DL, a.part_i_row0[of_part], of_walk.rb0, rb_last);
+    };
+    if constexpr (SHARE) {
+      // (this job's masks for whoever takes its last pass: the two words, then the word that
+      // says they are there)
+      if (share != 0 && guard) {
+        if (lane == 0) {
+          uint64_t* words = (uint64_t*)(queue + kShareMaskWord) + 2 * slot;
+          words[0] = mask_b;
+          words[1] = mask_e;
+          __hip_atomic_store(queue + kShareFlagWord + slot, 1u, __ATOMIC_RELEASE,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+      }
+    }
 #pragma unroll
     for (int p = 0; p < UP; ++p) {
       F[p][0][0] = F[p][0][1] = F[p][1][0] = F[p][1][1] = 0.0;
       if (skip & 2) continue;
+      if constexpr (SHARE) {
+        if (p == UP - 1 && share != 0) continue;      // (the last pass: items, below)
+      }
       if constexpr (SKIP) {
         if ((mask_b | mask_e) != 0) {
           if (2 * p + 1 < U)
@@ -2848,6 +2919,63 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
         fused_quad_pass<2, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk, F[p]);
       else
         fused_quad_pass<1, DL>(rs_t, off_a + p * 1024, UP * 1024, dens_b, dens_e, walk, F[p]);
+    }
+    if constexpr (SHARE) {
+      if (share != 0) {
+        // The last passes of all eight jobs, an item at a time to whichever wave comes for one:
+        // one lane adds to the counter, the wave goes by what it got back.  Nobody waits for
+        // anybody, and a wave takes at most every item once.  An item's sums go to (job, 4 r, 32
+        // draws) in the place of the math table, which is dead from the barrier behind the
+        // pair-weight sums to phase 3; the job's own wave fetches them behind the next barrier.
+        const int n_items = share_item_count(share);
+        for (int turn = 0; turn < n_items; ++turn) {
+          unsigned ticket = 0;
+          if (lane == 0)
+            ticket = __hip_atomic_fetch_add(queue + kShareCounterWord, 1u, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_WORKGROUP);
+          const int index = __builtin_amdgcn_readfirstlane((int)ticket);
+          if (index >= n_items) break;
+          const ShareItem item = share_item(share, index);
+          const int job = item.tile * PARTS + item.part;
+          const double* item_b = dens + (a.part_j_row0[item.part] + kq) * DL +
+                                 item.tile * kQuadTile + 2 * c;
+          const double* item_e = dens + a.part_i_row0[item.part] * DL + item.tile * kQuadTile + 2 * c;
+          const FusedPart item_walk = {a.part_rb0[item.part],        a.part_cb0[item.part],
+                                       a.part_count[item.part],      a.part_triangular[item.part],
+                                       a.part_n_cb[item.part],
+                                       (unsigned)a.part_unit_base[item.part]};
+          uint64_t item_mask_b = 0, item_mask_e = 0;
+          if (guard) {
+            const unsigned there = __hip_atomic_load(queue + kShareFlagWord + job, __ATOMIC_ACQUIRE,
+                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (__builtin_amdgcn_readfirstlane((int)there) != 0) {
+              const uint64_t* words = (const uint64_t*)(queue + kShareMaskWord) + 2 * job;
+              item_mask_b = wave_uniform(words[0]);
+              item_mask_e = wave_uniform(words[1]);
+            } else {
+              // (its own wave has not come that far: the same words from the same densities)
+              job_masks(item.part, item_walk, item_b, item_e, item_mask_b, item_mask_e);
+            }
+          }
+          const uint64_t leave = share_select_bits(item.select);
+          double sums[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+          if ((item_mask_b | item_mask_e | leave) != 0)
+            fused_quad_pass_skip<1, DL>(rs_t, off_a + (UP - 1) * 1024, UP * 1024, item_b, item_e,
+                                        item_walk, item_mask_b | leave, item_mask_e | leave, sums);
+          else
+            fused_quad_pass<1, DL>(rs_t, off_a + (UP - 1) * 1024, UP * 1024, item_b, item_e,
+                                   item_walk, sums);
+          double* to = table + (job * 4 + kq) * kQuadTile + 2 * c;
+          if (item.select == 0) {
+            const f64x2 value = {sums[0][0], sums[0][1]};
+            *(f64x2*)to = value;
+          } else if (item.select == 1) {
+            to[0] = sums[0][0];
+          } else {
+            to[1] = sums[0][1];
+          }
+        }
+      }
     }
   }
   stamp(5);
@@ -2899,6 +3027,14 @@ __global__ __launch_bounds__(64 * W, DL == 40 ? 2 : W == 8 ? (SATDEFER == 2 ? 4 
     // r = 4 u + l / 16, draws 2 c and 2 c + 1 of the wave's tile
     // (the slot of (tile, part): phase 3 adds a tile's parts in part order)
     double* out = dens + (slot * (4 * U) + kq) * kQuadTile + 2 * c;
+    if constexpr (SHARE) {
+      // (the last pass's sums of this wave's job, whoever formed them)
+      if (share != 0) {
+        const f64x2 value = *(const f64x2*)(table + (slot * 4 + kq) * kQuadTile + 2 * c);
+        F[UP - 1][0][0] = value.x;
+        F[UP - 1][0][1] = value.y;
+      }
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const f64x2 value = {F[u >> 1][u & 1][0], F[u >> 1][u & 1][1]};

@@ -1016,7 +1016,10 @@ int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* t
                 // parts (0, 1) and (2, 3) on a SIMD)
                 (t->tuning.fused_skip != 0 ? 1 << 13 : 0) |
                 (t->tuning.fused_skip == 1 || t->tuning.fused_skip == 3 ? 1 << 14 : 0) |
-                (t->tuning.fused_skip == 1 ? 1 << 15 : 0);
+                (t->tuning.fused_skip == 1 ? 1 << 15 : 0) |
+                // (fused_skip.h: the last r pass shared through a queue in LDS, only with all
+                // three of the above)
+                (t->tuning.fused_skip == 1 ? (t->tuning.fused_share & 3) << 16 : 0);
   fa.n_draws = n_draws;
   fa.n_groups = t->node_groups.n_groups;
   fa.n_central_groups = t->node_groups.n_central_groups;
@@ -1043,7 +1046,7 @@ int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* t
     fa.xi = nullptr;
     *chi2_written = true;
   }
-  const int lds = tc::fused_lds_bytes(fa.dens_rows, waves, draws);
+  int lds = tc::fused_lds_bytes(fa.dens_rows, waves, draws);
   const dim3 grid((unsigned)((n_draws + draws - 1) / draws)), block(64 * waves);
 #ifdef TC_DEVELOPER_KNOBS
   if (fa.chi2 == nullptr && env_int_early("TC_FUSED_STAMPS", 0) != 0) {
@@ -1089,6 +1092,16 @@ int run_fused(tc_table* t, const Call& call, tc::FusedForm form, const double* t
   // bins that share their nodes (Zheng07 family, ten nodes): the GROUPED instances
   instance.grouped = t->grouped && n_gauss == 10 && !(flags & TC_FLAG_LEAUTHAUD11);
   instance.defer = cen_defer ? 2 : sat_defer ? 1 : 0;
+  // (the instances that can share their last r pass keep the queue's words behind everything
+  // else, whatever option "fused_share" says: fused_skip.h.  The 80 KB and 160 KB limits of the
+  // 64 x 8 form leave 2032 bytes behind the last block of four density rows that fits: the bin
+  // limits of choose_fused_form hold as they are.)
+  static_assert(tc::kShareWords * 4 <= (80 * 1024 - tc::fused_scratch_doubles(8) * 8) % 2048 &&
+                    tc::kShareWords * 4 <= (160 * 1024 - tc::fused_scratch_doubles(8) * 8) % 2048,
+                "the queue's words fit behind any table the 64 x 8 form is eligible for");
+  if (instance.defer == 2 && waves == 8 && draws == 64 &&
+      (t->quad_tiling.n_u == 3 || t->quad_tiling.n_u == 5))
+    lds += tc::kShareWords * 4;
   status = launch_fused_instance(instance, t->device, t->quad_tiling.n_u, grid, block, lds, stream,
                                  k0, k1, fa);
   if (status != TC_OK) return status;

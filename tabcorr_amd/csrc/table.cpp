@@ -1576,6 +1576,11 @@ int tc_table_set_option(tc_table* t, const char* name, int value) {
     // A/B and tests: 0 = predict_fused_kernel's matrix phase issues every product (same bits)
     TC_CHECK(value >= 0 && value <= 3, "fused_skip must be 0 .. 3");
     t->tuning.fused_skip = value;
+  } else if (key == "fused_share") {
+    // A/B and tests: the last r pass of the skipping instances with U = 3 or 5 as items of a
+    // queue in LDS (same bits): 0 every wave its own, 1 eight items, 2 sixteen (one per group)
+    TC_CHECK(value >= 0 && value <= 2, "fused_share must be 0, 1 or 2");
+    t->tuning.fused_share = value;
   } else if (key == "fused_sat_cap") {
     TC_CHECK(value >= 0 && value <= 6, "fused_sat_cap must be in [0, 6]");
     t->tuning.fused_sat_cap = value;

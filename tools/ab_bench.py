@@ -19,6 +19,7 @@ def main():
     parser = argparse.ArgumentParser()
     parser.add_argument('--rounds', type=int, default=3)
     parser.add_argument('--args', default='--detail 0 --cpu-seconds 0')
+    parser.add_argument('--run-seconds', type=float, default=300.0, help='limit of one run')
     parser.add_argument('builds', nargs='+')
     args = parser.parse_args()
     results = {}
@@ -33,10 +34,12 @@ def main():
             command = [sys.executable, os.path.join(REPO, 'bench.py')] + args.args.split()
             for option in options:
                 command += ['--option', option]
-            out = subprocess.run(command, env=env, capture_output=True, text=True)
+            out = subprocess.run(command, env=env, capture_output=True, text=True,
+                                 timeout=args.run_seconds)
             if out.returncode != 0:
-                print(name, 'FAILED', out.stderr[-500:], flush=True)
-                continue
+                # (nothing more is started on a device after a run that failed on it)
+                print(name, 'FAILED', out.returncode, out.stderr[-500:], flush=True)
+                sys.exit(1)
             record = json.loads(out.stdout.strip().splitlines()[-1])
             if 'ms_per_step' in record:
                 value = record['ms_per_step'] * 1e3
@@ -45,8 +48,9 @@ def main():
             results.setdefault(name, []).append(value)
             print('%-12s %.2f us' % (name, value), flush=True)
     for name, values in results.items():
-        print('%-12s mean %.2f  min %.2f  (%s)' % (name, sum(values) / len(values), min(values),
-                                                    ' '.join('%.2f' % v for v in values)))
+        print('%-12s median %.2f  range %.2f - %.2f  mean %.2f  (%s)' % (
+            name, sorted(values)[len(values) // 2], min(values), max(values),
+            sum(values) / len(values), ' '.join('%.2f' % v for v in values)))
 
 
 if __name__ == '__main__':
