@@ -314,12 +314,26 @@ FORWARD_ENTRIES.update({
     for _route, _suffix in (('host', ''), ('device', '_device'))})
 
 
+# The occupation seam: (handle kind, form) -> the host-array symbol, `name + '_device'` its
+# twin.  Form 'predict': cotangents (g_ngal, g_xi) in, (ngal, xi, g_occupation) out; 'chi2':
+# (data, precision) in, (ngal, chi2, dchi2_docc) out.  An interpolator takes x behind the
+# occupations and has SEAM_X_OUTPUTS more outputs: g_x, or dchi2_dx and dngal_dx.  A joint and an
+# interpolator take NULL for the derivative outputs (the forward-only form); a table does not.
+SEAM_ENTRIES = {
+    (_kind, _form): 'tc_%s%s_batch' % (_prefix, _entry)
+    for _kind, _prefix in (('table', ''), ('joint', 'joint_'), ('interp', 'interp_'))
+    for _form, _entry in (('predict', 'predict_occupation_vjp'),
+                          ('chi2', 'chi2_occupation_grad'))}
+SEAM_X_OUTPUTS = {'predict': 1, 'chi2': 2}
+
+
 def _derivative_signatures():
     """The argument lists of the derivative entries, composed: the handle, the draws (and an
     interpolator's x), the counts and flags, the likelihood's operands (host pointers in both
-    twins), four outputs and, where the entry has one, the Fisher matrix.  The occupation VJP:
-    the handle, the occupations, n_draws and flags, the cotangents or the operands, three
-    outputs.  A `_device` twin takes device pointers for every array."""
+    twins), four outputs and, where the entry has one, the Fisher matrix.  The occupation seam:
+    the handle, the occupations (and an interpolator's x behind them), n_draws and flags, the
+    cotangents or the operands, three outputs and, for an interpolator, those with respect to x
+    last.  A `_device` twin takes device pointers for every array."""
     out = {}
     for device in (False, True):
         array = ctypes.c_void_p if device else c_double_p
@@ -330,18 +344,11 @@ def _derivative_signatures():
             operands = [c_double_p, c_double_p] * (form != 'predict')
             fisher = [array] * (form == 'fisher' or name in GRAD_OPTIONAL_FISHER)
             out[name + suffix] = head + operands + [array] * 4 + fisher
-        head = [ctypes.c_void_p, array, ctypes.c_int64, ctypes.c_uint]
-        out['tc_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 3
-        out['tc_chi2_occupation_grad_batch' + suffix] = head + [c_double_p] * 2 + [array] * 3
-        # (a joint of tables: the same arguments with N for n_r)
-        out['tc_joint_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 3
-        out['tc_joint_chi2_occupation_grad_batch' + suffix] = (head + [c_double_p] * 2 +
-                                                              [array] * 3)
-        # (an interpolator: x behind the occupations, and the outputs with respect to x last)
-        head = [ctypes.c_void_p, array, array, ctypes.c_int64, ctypes.c_uint]
-        out['tc_interp_predict_occupation_vjp_batch' + suffix] = head + [array] * 2 + [array] * 4
-        out['tc_interp_chi2_occupation_grad_batch' + suffix] = (head + [c_double_p] * 2 +
-                                                               [array] * 5)
+        for (kind, form), name in SEAM_ENTRIES.items():
+            interp = kind == 'interp'
+            head = [ctypes.c_void_p, array] + [array] * interp + [ctypes.c_int64, ctypes.c_uint]
+            middle = [array] * 2 if form == 'predict' else [c_double_p] * 2
+            out[name + suffix] = head + middle + [array] * (3 + interp * SEAM_X_OUTPUTS[form])
     return out
 
 
@@ -352,6 +359,25 @@ _lib = None
 
 class TabCorrHipError(RuntimeError):
     """The HIP backend failed (no device, launch error, RCCL error)."""
+
+
+class Handle:
+    """Owner of a handle of the library: `lib`, `handle`, and its destruction by the symbol
+    `destroy` when the owner goes."""
+
+    def __init__(self, lib, handle, destroy):
+        self.lib = lib
+        self.handle = handle
+        self.destroy = destroy
+
+    def __del__(self):
+        handle = getattr(self, 'handle', None)
+        if handle is not None and handle.value is not None:
+            try:
+                getattr(self.lib, self.destroy)(handle)
+            except Exception:  # interpreter shutdown
+                pass
+            self.handle = None
 
 
 def load():

@@ -22,11 +22,11 @@ import numpy as np
 from . import _forward
 from . import _grad
 from . import _lib
+from . import _seam
 from .galtable import GalTypeTable
 from .models import device_spec
 from .tabcorr import (TabCorr, XI_KEYS, NGAL_KEYS, _chi2_operands, _flags,
-                      _grad_keys, _grad_spec, _grad_theta,
-                      _leauthaud11_columns, _unbatch)
+                      _grad_theta, _unbatch)
 
 OUT_OF_RANGE = ('The x-coordinates are outside of the interpolation ' +
                 'range and extrapolation is turned off.')
@@ -63,7 +63,7 @@ class _HandleLocks:
     def __init__(self, tables):
         unique = {id(t.lock): t.lock for t in tables}
         # (a joint of interpolators takes the two parts of several handles in
-        # this order: joint._MemberLocks)
+        # this order: joint._DeviceJointInterp.ordered_locks)
         self.own = threading.RLock()
         self.of_tables = [unique[k] for k in sorted(unique)]
         self._locks = [self.own] + self.of_tables
@@ -93,7 +93,8 @@ class _HandleLocks:
             lock.release()
 
 
-class _DeviceInterpolator:
+class _DeviceInterpolator(_lib.Handle):
+    """Owner of a ``tc_interp`` handle; keeps its tables' handles alive."""
 
     def __init__(self, interpolator):
         lib = _lib.load()
@@ -105,9 +106,9 @@ class _DeviceInterpolator:
         _lib.check(lib.tc_interp_create(
             ctypes.cast(handles, _lib.c_void_pp), len(devices),
             points.shape[1], _lib.as_double_p(points), ctypes.byref(handle)))
-        self.handle = handle
-        self.lib = lib
+        super().__init__(lib, handle, 'tc_interp_destroy')
         self.tables = devices          # keep the table handles alive
+        self.n_r = devices[0].n_r
         # one host thread at a time per handle (see tabcorr._DeviceTable),
         # the handles of the tables included
         self.lock = _HandleLocks(devices)
@@ -132,15 +133,6 @@ class _DeviceInterpolator:
             if status:
                 _lib.check(status)
             return self._one_ngal[0], self._one_xi.copy()
-
-    def __del__(self):
-        handle = getattr(self, 'handle', None)
-        if handle is not None and handle.value is not None:
-            try:
-                self.lib.tc_interp_destroy(handle)
-            except Exception:
-                pass
-            self.handle = None
 
 
 class Interpolator:
@@ -453,7 +445,7 @@ class Interpolator:
             self.to_device(), 'interp', _grad.family_of(assembias, family),
             [theta, theta.shape[1], x, len(theta), n_gauss_prim,
              _flags(False, modulate_with_cenocc)],
-            len(_grad_keys(assembias, family)) + len(self.keys),
+            len(_grad.keys_of(assembias, family)) + len(self.keys),
             self.tabcorr_list[0].tpcf_shape, operands, want_fisher)
 
     def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
@@ -500,38 +492,13 @@ class Interpolator:
         if check_consistency:
             for halotab in self.tabcorr_list:
                 halotab._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'predict_grad', leauthaud11=True)
-        if spec.family == 'leauthaud11':
-            ngal, xi, dngal, dxi = self.predict_batch_grad(
-                spec.theta[np.newaxis], x[np.newaxis],
-                n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-                modulate_with_cenocc=spec.modulate_with_cenocc,
-                family='leauthaud11')
-            columns = self._leauthaud11_columns(model)
-            return (float(ngal[0]), xi[0],
-                    _grad.keyed(dngal[0], columns=columns),
-                    _grad.keyed(dxi[0], columns=columns))
-        model_keys = tuple(_grad_keys(assembias))
+        theta, options, columns, _ = _grad.model_columns(
+            model, assembias, 'predict_grad', self.keys, leauthaud11=True)
         ngal, xi, dngal, dxi = self.predict_batch_grad(
-            np.asarray(spec.theta,
-                       dtype=np.float64)[np.newaxis, :len(model_keys)],
-            x[np.newaxis], n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        keys = model_keys + tuple(self.keys)
-        return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], keys),
-                _grad.keyed(dxi[0], keys))
-
-    def _leauthaud11_columns(self, model):
-        """`LEAUTHAUD11_KEYS`, then ``self.keys`` -> (device column, factor)
-        among the ``11 + D`` columns of the Leauthaud11 family's calls: the
-        model's sixteen as `tabcorr._leauthaud11_columns` has them, the extra
-        parameters their own."""
-        columns = _leauthaud11_columns(model)
-        n_model = len(_grad_keys(family='leauthaud11'))
-        for d, key in enumerate(self.keys):
-            columns[key] = (n_model + d, 1.0)
-        return columns
+            theta, x[np.newaxis], n_gauss_prim=n_gauss_prim,
+            extrapolate=extrapolate, **options)
+        return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], columns=columns),
+                _grad.keyed(dxi[0], columns=columns))
 
     # -- Fisher matrix of the likelihood ------------------------------------------------
 
@@ -614,32 +581,13 @@ class Interpolator:
         if check_consistency:
             for halotab in self.tabcorr_list:
                 halotab._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'fisher', leauthaud11=True)
-        if spec.family == 'leauthaud11':
-            ngal, dngal, fisher = self.fisher_batch(
-                spec.theta[np.newaxis], x[np.newaxis], precision,
-                n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-                modulate_with_cenocc=spec.modulate_with_cenocc,
-                family='leauthaud11')
-            own = model.device_jacobian()
-            n_dim = len(self.keys)
-            jacobian = np.zeros((own.shape[0] + n_dim, own.shape[1] + n_dim))
-            jacobian[:own.shape[0], :own.shape[1]] = own
-            jacobian[own.shape[0]:, own.shape[1]:] = np.eye(n_dim)
-            return (float(ngal[0]),
-                    _grad.keyed(dngal[0],
-                                columns=self._leauthaud11_columns(model)),
-                    jacobian.T @ fisher[0] @ jacobian)
-        model_keys = tuple(_grad_keys(assembias))
+        theta, options, columns, jacobian = _grad.model_columns(
+            model, assembias, 'fisher', self.keys, leauthaud11=True)
         ngal, dngal, fisher = self.fisher_batch(
-            np.asarray(spec.theta,
-                       dtype=np.float64)[np.newaxis, :len(model_keys)],
-            x[np.newaxis], precision, n_gauss_prim=n_gauss_prim,
-            extrapolate=extrapolate,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        keys = model_keys + tuple(self.keys)
-        return float(ngal[0]), _grad.keyed(dngal[0], keys), fisher[0]
+            theta, x[np.newaxis], precision, n_gauss_prim=n_gauss_prim,
+            extrapolate=extrapolate, **options)
+        return (float(ngal[0]), _grad.keyed(dngal[0], columns=columns),
+                _grad.carried(fisher[0], jacobian))
 
     # -- the occupation seam: any occupation model, one launch ---------------------------
 
@@ -759,37 +707,13 @@ class Interpolator:
 
     def _predict_occupation(self, occupation, x, g_xi, g_ngal, extrapolate):
         occupation, x = self._seam_inputs(occupation, x, extrapolate)
-        n_draws = len(occupation)
         shape = tuple(self.tabcorr_list[0].tpcf_shape)
-        n_r = len(self.tabcorr_list[0].tpcf_matrix)
-        backward = g_xi is not None
-        if backward:
-            g_xi = np.asarray(g_xi, dtype=np.float64)
-            if g_xi.shape != (n_draws, ) + shape:
-                raise ValueError('g_xi must have shape {}, got {}.'.format(
-                    (n_draws, ) + shape, g_xi.shape))
-            g_xi = _lib.contiguous(g_xi.reshape(n_draws, n_r))
-            if g_ngal is not None:
-                g_ngal = np.asarray(g_ngal, dtype=np.float64)
-                if g_ngal.shape != (n_draws, ):
-                    raise ValueError(
-                        'g_ngal must have shape {}, got {}.'.format(
-                            (n_draws, ), g_ngal.shape))
-                g_ngal = _lib.contiguous(g_ngal)
-        device = self._seam_device()
-        ngal = np.empty(n_draws)
-        xi = np.empty((n_draws, n_r))
-        g_occupation = np.empty_like(occupation) if backward else None
-        g_x = np.empty_like(x) if backward else None
-        pointer = _lib.as_double_p
-        with device.lock:
-            _lib.check(device.lib.tc_interp_predict_occupation_vjp_batch(
-                device.handle, pointer(occupation), pointer(x), n_draws, 0,
-                pointer(g_ngal) if backward and g_ngal is not None else None,
-                pointer(g_xi) if backward else None, pointer(ngal),
-                pointer(xi), pointer(g_occupation) if backward else None,
-                pointer(g_x) if backward else None))
-        return ngal, xi.reshape((n_draws, ) + shape), g_occupation, g_x
+        cotangents = None if g_xi is None else _seam.cotangents(
+            g_xi, g_ngal, len(occupation), True, shape)
+        ngal, xi, g_occupation, g_x = _seam.call(
+            self._seam_device(), 'interp', 'predict', occupation, x,
+            cotangents=cotangents)
+        return ngal, xi.reshape((len(ngal), ) + shape), g_occupation, g_x
 
     def predict_occupation(self, occupation, x, extrapolate=False):
         """The interpolated ``predict(occupation)`` for ANY occupation model,
@@ -827,21 +751,10 @@ class Interpolator:
     def _chi2_occupation(self, occupation, x, data, precision, extrapolate,
                          gradient):
         occupation, x = self._seam_inputs(occupation, x, extrapolate)
-        data, precision = _chi2_operands(
+        operands = _chi2_operands(
             data, precision, len(self.tabcorr_list[0].tpcf_matrix))
-        device = self._seam_device()
-        n_draws = len(occupation)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        outputs = [np.empty_like(occupation), np.empty_like(x),
-                   np.empty_like(x)] if gradient else [None] * 3
-        pointer = _lib.as_double_p
-        with device.lock:
-            _lib.check(device.lib.tc_interp_chi2_occupation_grad_batch(
-                device.handle, pointer(occupation), pointer(x), n_draws, 0,
-                pointer(data), pointer(precision), pointer(ngal),
-                pointer(chi2),
-                *[pointer(a) if gradient else None for a in outputs]))
-        return (ngal, chi2) + tuple(outputs)
+        return _seam.call(self._seam_device(), 'interp', 'chi2', occupation,
+                          x, operands=operands, gradient=gradient)
 
     def chi2_occupation(self, occupation, x, data, precision,
                         extrapolate=False):

@@ -23,7 +23,8 @@ import numpy as np
 from . import _forward
 from . import _grad
 from . import _lib
-from .tabcorr import _flags, _grad_keys, _grad_spec, _grad_theta
+from . import _seam
+from .tabcorr import _flags, _grad_theta
 
 MAX_TABLES = 16
 # the gal_type columns the device reads (tabcorr.py: _DeviceTable)
@@ -54,11 +55,12 @@ def _zheng07_only(family):
 
 
 class _Locks:
-    """Every table's lock, taken in one fixed order whatever the order of the
-    tables in the joint (`TabCorr.predict_joint` takes them the same way)."""
+    """The locks of everything a joint works through, taken together in the
+    order of the list: one fixed order whatever the order of the members in
+    the joint (`TabCorr.predict_joint` takes its tables' the same way)."""
 
-    def __init__(self, devices):
-        self.locks = [d.lock for d in sorted(devices, key=id)]
+    def __init__(self, locks):
+        self.locks = locks
 
     def __enter__(self):
         for lock in self.locks:
@@ -69,85 +71,84 @@ class _Locks:
             lock.release()
 
 
-class _DeviceJoint:
+class _DeviceJoint(_lib.Handle):
     """Owner of a ``tc_joint`` handle; keeps its tables' handles alive.  A
     joint works through its tables (``include/tabcorr_amd.h``): every call
-    sits behind `lock`, all of their locks."""
+    sits behind `lock`, all of their locks.  `n_r`: the joint axis."""
+
+    kind = 'joint'
 
     def __init__(self, devices):
-        self.lib = devices[0].lib
-        self.devices = devices
+        lib = devices[0].lib
         handles = (ctypes.c_void_p * len(devices))(
             *[d.handle.value for d in devices])
         handle = ctypes.c_void_p()
-        _lib.check(self.lib.tc_joint_create(handles, len(devices),
-                                            ctypes.byref(handle)))
-        self.handle = handle
-        self.lock = _Locks(devices)
+        _lib.check(getattr(lib, 'tc_%s_create' % self.kind)(
+            handles, len(devices), ctypes.byref(handle)))
+        super().__init__(lib, handle, 'tc_%s_destroy' % self.kind)
+        self.devices = devices
+        self.n_r = sum(d.n_r for d in devices)
+        self.lock = _Locks(self.ordered_locks(devices))
 
-    def __del__(self):
-        handle = getattr(self, 'handle', None)
-        if handle is not None and handle.value is not None:
-            try:
-                self.lib.tc_joint_destroy(handle)
-            except Exception:  # interpreter shutdown
-                pass
-            self.handle = None
+    @staticmethod
+    def ordered_locks(devices):
+        return [d.lock for d in sorted(devices, key=id)]
 
 
-class JointLikelihood:
-    """``JointLikelihood([halotab_wp, halotab_ds])``: 1 to 16 `TabCorr`
-    tables with identical ``gal_type`` tables (mode ``'auto'`` and mode
-    ``'cross'`` may be mixed).  The tables' results are concatenated in list
-    order: table ``k`` owns ``joint.slices[k]`` of the ``joint.n_r_total``
-    entries of ``data`` and of the rows and columns of ``precision``.
+class _DeviceJointInterp(_DeviceJoint):
+    """Owner of a ``tc_joint_interp`` handle; keeps its members' handles
+    alive.  The joint works through its members and their tables: every call
+    sits behind `lock`, all of their locks."""
 
-    Total correlation functions, float64 tables.  Which calls serve which
-    model:
+    kind = 'joint_interp'
 
-    - the calls that take ``theta`` -- `predict_batch`, `chi2_batch`,
-      `predict_batch_grad`, `chi2_grad_batch`, `chi2_fisher_batch`,
-      `fisher_batch` and the un-batched `predict_grad`, `chi2_fisher` --
-      serve plain Zheng07 and, with ``assembias=True``, the model decorated
-      with assembly bias (7 columns wherever 5 stand);
-      ``family='leauthaud11'`` raises ``NotImplementedError``;
-    - the calls that take the occupation array -- `predict_occupation`,
-      `predict_vjp`, `chi2_occupation`, `chi2_grad_occupation` -- serve ANY
-      occupation model, Leauthaud11 and custom ones among them: the caller
-      contracts their results with the model's own ``d<N>/dtheta``.
-    """
+    @staticmethod
+    def ordered_locks(devices):
+        """The interpolator handles' own locks first, then every table's, each
+        group by identity as `interpolator._HandleLocks` orders a handle's."""
+        own = {id(d.lock.own): d.lock.own for d in devices}
+        tables = {id(lock): lock for d in devices for lock in d.lock.of_tables}
+        return ([own[k] for k in sorted(own)] +
+                [tables[k] for k in sorted(tables)])
 
-    def __init__(self, tabcorr_list):
-        self.tabcorr_list = list(tabcorr_list)
-        n_tables = len(self.tabcorr_list)
-        if n_tables < 1 or n_tables > MAX_TABLES:
-            raise ValueError('A joint takes 1 to {} tables, got {}.'.format(
-                MAX_TABLES, n_tables))
-        first = self.tabcorr_list[0]
-        for k, halotab in enumerate(self.tabcorr_list):
-            if any(halotab is other for other in self.tabcorr_list[:k]):
-                raise ValueError(
-                    'Table {} appears twice in the joint.'.format(k))
-            if halotab.compute_dtype != 'float64':
-                raise ValueError('Table {} does not have a float64 compute '
-                                 'dtype.'.format(k))
-            if not _same_bins(halotab.gal_type, first.gal_type):
-                raise ValueError('Table {} does not have the gal_type table '
-                                 'of table 0.'.format(k))
-        sizes = [len(halotab.tpcf_matrix) for halotab in self.tabcorr_list]
+
+class _JointBase:
+    """What a joint of tables and a joint of interpolators share: the parts
+    of the joint axis, the operands of the likelihood, and every call on the
+    draws -- ``(theta, )`` for tables, ``(theta, x)`` for interpolators, in
+    the entries' arguments as the handle kind of `_lib.FORWARD_ENTRIES` and
+    `_lib.GRAD_ENTRIES` has them.  A subclass says the `kind`, the owner of
+    its handle, how draws are checked (`_draws`) and what an un-batched call
+    reads from a model (`_model_draws`)."""
+
+    kind = None
+    _Device = None
+
+    def _set_parts(self, members, part_tables=None, tables=None,
+                   extra_keys=()):
+        """`members`: what the handle is created from; `part_tables`: per
+        member the table whose correlation function bins are its part of the
+        joint axis; `tables`: every table a model must be consistent with
+        (both: the members themselves); `extra_keys`: the parameters
+        differentiated behind the model's."""
+        self._members = members
+        self._part_tables = part_tables or members
+        self._tables = tables or members
+        self._extra_keys = tuple(extra_keys)
+        sizes = [len(halotab.tpcf_matrix) for halotab in self._part_tables]
         offsets = np.concatenate([[0], np.cumsum(sizes)])
         self.slices = [slice(int(offsets[k]), int(offsets[k + 1]))
-                       for k in range(n_tables)]
+                       for k in range(len(members))]
         self.n_r_total = int(offsets[-1])
         self._device = None
 
     def to_device(self):
-        """Upload the tables and create the joint handle (done lazily by the
+        """Upload the members and create the joint handle (done lazily by the
         first call)."""
-        devices = [halotab.to_device() for halotab in self.tabcorr_list]
+        devices = [member.to_device() for member in self._members]
         if self._device is None or any(
                 a is not b for a, b in zip(self._device.devices, devices)):
-            self._device = _DeviceJoint(devices)
+            self._device = self._Device(devices)
         return self._device
 
     # -- arguments ------------------------------------------------------------
@@ -174,30 +175,145 @@ class JointLikelihood:
         return data, precision
 
     def _split(self, array, leading):
-        """The per-table parts of an array whose last axis is the joint one,
+        """The per-member parts of an array whose last axis is the joint one,
         each reshaped to ``leading + tpcf_shape``."""
         return [np.ascontiguousarray(array[..., part]).reshape(
             leading + tuple(halotab.tpcf_shape))
-            for part, halotab in zip(self.slices, self.tabcorr_list)]
+            for part, halotab in zip(self.slices, self._part_tables)]
+
+    def _inputs(self, theta, n_gauss_prim, modulate_with_cenocc, assembias,
+                family, x=None, extrapolate=False):
+        """What follows the handle in an entry's arguments up to the operands
+        -- the draws, checked here before any device is touched, theta's
+        columns behind theta --; the family is in the flags."""
+        _zheng07_only(family)
+        draws = self._draws(theta, assembias, x, extrapolate)
+        theta = draws[0]
+        return (theta, theta.shape[1]) + tuple(draws[1:]) + (
+            len(theta), n_gauss_prim,
+            _flags(False, modulate_with_cenocc, assembias))
 
     # -- batched calls --------------------------------------------------------
 
-    def _forward_call(self, form, theta, n_gauss_prim, modulate_with_cenocc,
-                      assembias, family, operands=()):
-        """The forward entry (``_lib.FORWARD_ENTRIES['joint', form, 'host']``)
-        for draws and operands that are checked here, before any device is
-        touched: the results on the joint axis of ``n_r_total`` entries."""
-        _zheng07_only(family)
-        theta = _grad_theta(theta, assembias)
+    def _forward_call(self, form, inputs, operands=()):
+        """The forward entry (``_lib.FORWARD_ENTRIES[kind, form, 'host']``)
+        for checked `inputs`; the operands are checked here, before any device
+        is touched: the results on the joint axis of ``n_r_total`` entries."""
         if operands:
             operands = self._operands(*operands)
-        n_draws = len(theta)
+        n_draws = len(inputs[0])
         shapes = ((n_draws, ), (n_draws, ) if operands else
                   (n_draws, self.n_r_total))
-        return _forward.call(
-            self.to_device(), 'joint', form,
-            (theta, theta.shape[1], n_draws, n_gauss_prim,
-             _flags(False, modulate_with_cenocc, assembias)), shapes, operands)
+        return _forward.call(self.to_device(), self.kind, form, inputs, shapes,
+                             operands)
+
+    def _predict_batch(self, inputs):
+        ngal, xi = self._forward_call('predict', inputs)
+        return ngal, self._split(xi, (len(ngal), ))
+
+    def _grad_call(self, inputs, operands=None, want_fisher=False):
+        """The derivative entry for checked `inputs` (and operands checked
+        here): the results on the joint axis of ``n_r_total`` entries."""
+        if operands is not None:
+            operands = self._operands(*operands)
+        return _grad.call(
+            self.to_device(), self.kind,
+            _grad.family_of(bool(inputs[-1] & _lib.FLAG_ASSEMBIAS)), inputs,
+            inputs[1] + len(self._extra_keys), (self.n_r_total, ), operands,
+            want_fisher)
+
+    def _predict_batch_grad(self, inputs):
+        ngal, xi, dngal, dxi = self._grad_call(inputs)
+        return (ngal, self._split(xi, dngal.shape[:1]), dngal,
+                self._split(dxi, dngal.shape))
+
+    def _fisher_batch(self, inputs, precision):
+        ngal, _, dngal, _, fisher = self._grad_call(
+            inputs, (np.zeros(self.n_r_total), precision), True)
+        return ngal, dngal, fisher
+
+    # -- un-batched forms -----------------------------------------------------
+
+    def _model_call(self, batched, model, what, n_gauss_prim, extrapolate,
+                    check_consistency, assembias, operands=()):
+        """The public `batched` call for one model object: its results and
+        the ``columns`` of `_grad.model_columns` that name the derivatives."""
+        draws, options = self._model_draws(model, extrapolate)
+        if check_consistency:
+            for halotab in self._tables:
+                halotab._check_consistency_cached(model)
+        theta, model_options, columns, _ = _grad.model_columns(
+            model, assembias, what, self._extra_keys)
+        return batched(theta, *draws, *operands, n_gauss_prim=n_gauss_prim,
+                       **options, **model_options), columns
+
+    def _predict_grad(self, model, *arguments):
+        (ngal, xis, dngal, dxis), columns = self._model_call(
+            self.predict_batch_grad, model, 'predict_grad', *arguments)
+        return (float(ngal[0]), [xi[0] for xi in xis],
+                _grad.keyed(dngal[0], columns),
+                {key: [dxi[0, k] for dxi in dxis]
+                 for key, (k, _) in columns.items()})
+
+    def _chi2_fisher(self, model, data, precision, *arguments):
+        (ngal, chi2, dngal, dchi2, fisher), columns = self._model_call(
+            self.chi2_fisher_batch, model, 'chi2_fisher', *arguments,
+            operands=(data, precision))
+        return (float(ngal[0]), float(chi2[0]), _grad.keyed(dngal[0], columns),
+                _grad.keyed(dchi2[0], columns), fisher[0])
+
+
+class JointLikelihood(_JointBase):
+    """``JointLikelihood([halotab_wp, halotab_ds])``: 1 to 16 `TabCorr`
+    tables with identical ``gal_type`` tables (mode ``'auto'`` and mode
+    ``'cross'`` may be mixed).  The tables' results are concatenated in list
+    order: table ``k`` owns ``joint.slices[k]`` of the ``joint.n_r_total``
+    entries of ``data`` and of the rows and columns of ``precision``.
+
+    Total correlation functions, float64 tables.  Which calls serve which
+    model:
+
+    - the calls that take ``theta`` -- `predict_batch`, `chi2_batch`,
+      `predict_batch_grad`, `chi2_grad_batch`, `chi2_fisher_batch`,
+      `fisher_batch` and the un-batched `predict_grad`, `chi2_fisher` --
+      serve plain Zheng07 and, with ``assembias=True``, the model decorated
+      with assembly bias (7 columns wherever 5 stand);
+      ``family='leauthaud11'`` raises ``NotImplementedError``;
+    - the calls that take the occupation array -- `predict_occupation`,
+      `predict_vjp`, `chi2_occupation`, `chi2_grad_occupation` -- serve ANY
+      occupation model, Leauthaud11 and custom ones among them: the caller
+      contracts their results with the model's own ``d<N>/dtheta``.
+    """
+
+    kind = 'joint'
+    _Device = _DeviceJoint
+
+    def __init__(self, tabcorr_list):
+        self.tabcorr_list = list(tabcorr_list)
+        n_tables = len(self.tabcorr_list)
+        if n_tables < 1 or n_tables > MAX_TABLES:
+            raise ValueError('A joint takes 1 to {} tables, got {}.'.format(
+                MAX_TABLES, n_tables))
+        first = self.tabcorr_list[0]
+        for k, halotab in enumerate(self.tabcorr_list):
+            if any(halotab is other for other in self.tabcorr_list[:k]):
+                raise ValueError(
+                    'Table {} appears twice in the joint.'.format(k))
+            if halotab.compute_dtype != 'float64':
+                raise ValueError('Table {} does not have a float64 compute '
+                                 'dtype.'.format(k))
+            if not _same_bins(halotab.gal_type, first.gal_type):
+                raise ValueError('Table {} does not have the gal_type table '
+                                 'of table 0.'.format(k))
+        self._set_parts(self.tabcorr_list)
+
+    def _draws(self, theta, assembias, x, extrapolate):
+        return (_grad_theta(theta, assembias), )
+
+    def _model_draws(self, model, extrapolate):
+        return (), {}
+
+    # -- batched calls --------------------------------------------------------
 
     def predict_batch(self, theta, n_gauss_prim=10, modulate_with_cenocc=False,
                       assembias=False, family='zheng07'):
@@ -215,9 +331,8 @@ class JointLikelihood:
         ``family='leauthaud11'`` and for a joint the one-launch kernel does
         not serve: a mode ``'auto'`` table of more than 20 correlation
         function bins, or rows beyond the kernel's LDS."""
-        ngal, xi = self._forward_call('predict', theta, n_gauss_prim,
-                                      modulate_with_cenocc, assembias, family)
-        return ngal, self._split(xi, (len(ngal), ))
+        return self._predict_batch(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family))
 
     def chi2_batch(self, theta, data, precision, n_gauss_prim=10,
                    modulate_with_cenocc=False, assembias=False,
@@ -228,9 +343,9 @@ class JointLikelihood:
         an ensemble sampler asks per step.  ``data`` and ``precision`` as
         `chi2_grad_batch` takes them; the signature is the one
         `parallel.chi2_batch_sharded` calls a predictor with."""
-        return self._forward_call('chi2', theta, n_gauss_prim,
-                                  modulate_with_cenocc, assembias, family,
-                                  (data, precision))
+        return self._forward_call('chi2', self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family),
+            (data, precision))
 
     def predict_batch_grad(self, theta, n_gauss_prim=10,
                            modulate_with_cenocc=False, assembias=False,
@@ -247,31 +362,8 @@ class JointLikelihood:
         Raises ``NotImplementedError`` for ``family='leauthaud11'`` and for a
         joint whose rows do not fit the kernel's LDS.
         """
-        _zheng07_only(family)
-        theta = _grad_theta(theta, assembias)
-        n_draws, n_cols = theta.shape
-        ngal, xi, dngal, dxi = self._grad_call(
-            theta, n_gauss_prim, modulate_with_cenocc, assembias)
-        return (ngal, self._split(xi, (n_draws, )), dngal,
-                self._split(dxi, (n_draws, n_cols)))
-
-    def _grad_call(self, theta, n_gauss_prim, modulate_with_cenocc, assembias,
-                   operands=None, want_fisher=False):
-        """The derivative entry for checked draws: the results on the joint
-        axis of ``n_r_total`` entries; the family is in the flags."""
-        return _grad.call(
-            self.to_device(), 'joint', _grad.family_of(assembias),
-            [theta, theta.shape[1], len(theta), n_gauss_prim,
-             _flags(False, modulate_with_cenocc, assembias)],
-            theta.shape[1], (self.n_r_total, ), operands, want_fisher)
-
-    def _chi2(self, theta, data, precision, n_gauss_prim,
-              modulate_with_cenocc, assembias, want_fisher, family):
-        _zheng07_only(family)
-        theta = _grad_theta(theta, assembias)
-        operands = self._operands(data, precision)
-        return self._grad_call(theta, n_gauss_prim, modulate_with_cenocc,
-                               assembias, operands, want_fisher)
+        return self._predict_batch_grad(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family))
 
     def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
                         modulate_with_cenocc=False, assembias=False,
@@ -279,8 +371,9 @@ class JointLikelihood:
         """chi2 of the concatenated data vector and its gradient
         (`TabCorr.chi2_grad_batch` with ``N`` for ``n_r``): ``ngal, chi2``
         ``(n_draws, )``, ``dngal, dchi2`` ``(n_draws, 5)``."""
-        return self._chi2(theta, data, precision, n_gauss_prim,
-                          modulate_with_cenocc, assembias, False, family)
+        return self._grad_call(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family),
+            (data, precision))
 
     def chi2_fisher_batch(self, theta, data, precision, n_gauss_prim=10,
                           modulate_with_cenocc=False, assembias=False,
@@ -289,27 +382,25 @@ class JointLikelihood:
         dxi_k^T P_sym dxi_l`` of the joint data vector, ``(n_draws, 5, 5)``,
         from the same launch (`TabCorr.chi2_fisher_batch`): the off-diagonal
         blocks of ``precision`` couple the tables."""
-        return self._chi2(theta, data, precision, n_gauss_prim,
-                          modulate_with_cenocc, assembias, True, family)
+        return self._grad_call(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family),
+            (data, precision), True)
 
     def fisher_batch(self, theta, precision, n_gauss_prim=10,
                      modulate_with_cenocc=False, assembias=False,
                      family='zheng07'):
         """The forecast form, which needs no data: ``ngal, dngal, fisher``."""
-        ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
-            theta, np.zeros(self.n_r_total), precision,
-            n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
-            family=family)
-        return ngal, dngal, fisher
+        return self._fisher_batch(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family),
+            precision)
 
     # -- the occupation seam: any occupation model -----------------------------
 
-    def _cotangents(self, g_xis, n_draws, batched):
+    def _cotangents(self, g_xis, g_ngal, n_draws, batched):
         """``g_xis`` -- a list with one array per table of shape ``(n_draws, )
         + tpcf_shape``, or one ``(n_draws, N)`` array (without the leading
-        axis when un-batched) -- on the joint axis, contiguous ``(n_draws,
-        N)``, or a ValueError."""
+        axis when un-batched) -- on the joint axis, and ``g_ngal``: the
+        cotangents as `_seam.cotangents` returns them, or a ValueError."""
         leading = (n_draws, ) if batched else ()
         if isinstance(g_xis, (list, tuple)):
             if len(g_xis) != len(self.tabcorr_list):
@@ -324,45 +415,30 @@ class JointLikelihood:
                 if part.shape != shape:
                     raise ValueError('g_xis of table {} must have shape {}, '
                                      'got {}.'.format(k, shape, part.shape))
-                parts.append(part.reshape(n_draws, -1))
-            return _lib.contiguous(np.concatenate(parts, axis=1))
-        g_xi = np.asarray(g_xis, dtype=np.float64)
-        if g_xi.shape != leading + (self.n_r_total, ):
+                parts.append(part.reshape(leading + (-1, )))
+            g_xis = np.concatenate(parts, axis=-1)
+        elif np.shape(g_xis) != leading + (self.n_r_total, ):
             raise ValueError('g_xis must be a list of per-table arrays or '
                              'have shape {}, got {}.'.format(
-                                 leading + (self.n_r_total, ), g_xi.shape))
-        return _lib.contiguous(g_xi.reshape(n_draws, self.n_r_total))
+                                 leading + (self.n_r_total, ),
+                                 np.shape(g_xis)))
+        return _seam.cotangents(g_xis, g_ngal, n_draws, batched,
+                                (self.n_r_total, ))
 
     def _predict_occupation(self, occupation, g_xis, g_ngal):
         """`predict_occupation` (``g_xis`` None) and `predict_vjp`: the
         arguments are checked before any device is touched."""
         occupation, batched = self.tabcorr_list[0]._vjp_occupation(occupation)
         n_draws = len(occupation)
-        g_xi = None
-        if g_xis is not None:
-            g_xi = self._cotangents(g_xis, n_draws, batched)
-            if g_ngal is not None:
-                g_ngal = np.asarray(g_ngal, dtype=np.float64)
-                if g_ngal.shape != ((n_draws, ) if batched else ()):
-                    raise ValueError(
-                        'g_ngal must have shape {}, got {}.'.format(
-                            (n_draws, ) if batched else (), g_ngal.shape))
-                g_ngal = _lib.contiguous(g_ngal.reshape(n_draws))
-        device = self.to_device()
-        ngal = np.empty(n_draws)
-        xi = np.empty((n_draws, self.n_r_total))
-        g_occupation = None if g_xi is None else np.empty_like(occupation)
-        with device.lock:
-            _lib.check(device.lib.tc_joint_predict_occupation_vjp_batch(
-                device.handle, _lib.as_double_p(occupation), n_draws, 0,
-                None if g_ngal is None else _lib.as_double_p(g_ngal),
-                None if g_xi is None else _lib.as_double_p(g_xi),
-                _lib.as_double_p(ngal), _lib.as_double_p(xi),
-                None if g_xi is None else _lib.as_double_p(g_occupation)))
+        cotangents = None if g_xis is None else self._cotangents(
+            g_xis, g_ngal, n_draws, batched)
+        ngal, xi, g_occupation = _seam.call(
+            self.to_device(), 'joint', 'predict', occupation,
+            cotangents=cotangents)
         xis = self._split(xi, (n_draws, ))
         if not batched:
             ngal, xis = ngal[0], [part[0] for part in xis]
-            g_occupation = None if g_xi is None else g_occupation[0]
+            g_occupation = None if g_xis is None else g_occupation[0]
         return ngal, xis, g_occupation
 
     def predict_occupation(self, occupation):
@@ -391,17 +467,10 @@ class JointLikelihood:
 
     def _chi2_occupation(self, occupation, data, precision, gradient):
         occupation, batched = self.tabcorr_list[0]._vjp_occupation(occupation)
-        data, precision = self._operands(data, precision)
-        device = self.to_device()
-        n_draws = len(occupation)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dchi2 = np.empty_like(occupation) if gradient else None
-        with device.lock:
-            _lib.check(device.lib.tc_joint_chi2_occupation_grad_batch(
-                device.handle, _lib.as_double_p(occupation), n_draws, 0,
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                _lib.as_double_p(dchi2) if gradient else None))
+        operands = self._operands(data, precision)
+        ngal, chi2, dchi2 = _seam.call(
+            self.to_device(), 'joint', 'chi2', occupation, operands=operands,
+            gradient=gradient)
         if not batched:
             return ngal[0], chi2[0], dchi2[0] if gradient else None
         return ngal, chi2, dchi2
@@ -427,92 +496,27 @@ class JointLikelihood:
 
     # -- un-batched forms -----------------------------------------------------
 
-    def _model_theta(self, model, check_consistency, assembias, what):
-        if check_consistency:
-            for halotab in self.tabcorr_list:
-                halotab._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, what)
-        keys = _grad_keys(assembias)
-        theta = np.asarray(spec.theta,
-                           dtype=np.float64)[np.newaxis, :len(keys)]
-        return spec, keys, theta
-
     def predict_grad(self, model, n_gauss_prim=10, check_consistency=True,
                      assembias=False):
         """Un-batched `predict_batch_grad` for a model object, as
         `TabCorr.predict_grad`: ``ngal`` (float), ``xis`` (list of arrays of
         each table's ``tpcf_shape``), ``dngal`` (dict by parameter name) and
         ``dxis`` (dict by parameter name of lists)."""
-        spec, keys, theta = self._model_theta(model, check_consistency,
-                                              assembias, 'predict_grad')
-        ngal, xis, dngal, dxis = self.predict_batch_grad(
-            theta, n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        return (float(ngal[0]), [xi[0] for xi in xis],
-                _grad.keyed(dngal[0], keys),
-                {key: [dxi[0, k] for dxi in dxis]
-                 for k, key in enumerate(keys)})
+        return self._predict_grad(model, n_gauss_prim, False,
+                                  check_consistency, assembias)
 
     def chi2_fisher(self, model, data, precision, n_gauss_prim=10,
                     check_consistency=True, assembias=False):
         """Un-batched `chi2_fisher_batch` for a model object: ``ngal``,
         ``chi2`` (floats), ``dngal``, ``dchi2`` (dicts by parameter name) and
         ``fisher`` ``(5, 5)`` in the order of the keys."""
-        spec, keys, theta = self._model_theta(model, check_consistency,
-                                              assembias, 'chi2_fisher')
-        ngal, chi2, dngal, dchi2, fisher = self.chi2_fisher_batch(
-            theta, data, precision, n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        return (float(ngal[0]), float(chi2[0]), _grad.keyed(dngal[0], keys),
-                _grad.keyed(dchi2[0], keys), fisher[0])
+        return self._chi2_fisher(model, data, precision, n_gauss_prim, False,
+                                 check_consistency, assembias)
 
 
 # ---- joint of interpolators ---------------------------------------------------
 
 MAX_MEMBERS = 16
-
-
-class _MemberLocks:
-    """The locks of every member of a joint of interpolators in one fixed
-    order: the interpolator handles' own locks first, then every table's, each
-    group by identity as `interpolator._HandleLocks` orders a handle's."""
-
-    def __init__(self, devices):
-        own = {id(d.lock.own): d.lock.own for d in devices}
-        tables = {id(lock): lock for d in devices for lock in d.lock.of_tables}
-        self.locks = ([own[k] for k in sorted(own)] +
-                      [tables[k] for k in sorted(tables)])
-
-    __enter__ = _Locks.__enter__
-    __exit__ = _Locks.__exit__
-
-
-class _DeviceJointInterp:
-    """Owner of a ``tc_joint_interp`` handle; keeps its members' handles
-    alive.  The joint works through its members and their tables: every call
-    sits behind `lock`, all of their locks."""
-
-    def __init__(self, devices):
-        self.lib = devices[0].lib
-        self.devices = devices
-        handles = (ctypes.c_void_p * len(devices))(
-            *[d.handle.value for d in devices])
-        handle = ctypes.c_void_p()
-        _lib.check(self.lib.tc_joint_interp_create(
-            handles, len(devices), ctypes.byref(handle)))
-        self.handle = handle
-        self.lock = _MemberLocks(devices)
-
-    def __del__(self):
-        handle = getattr(self, 'handle', None)
-        if handle is not None and handle.value is not None:
-            try:
-                self.lib.tc_joint_interp_destroy(handle)
-            except Exception:  # interpreter shutdown
-                pass
-            self.handle = None
 
 
 def _grid_nodes(interpolator):
@@ -522,7 +526,7 @@ def _grid_nodes(interpolator):
             for point in interpolator.points]
 
 
-class JointInterpolator:
+class JointInterpolator(_JointBase):
     """``JointInterpolator([interp_wp, interp_ds])``: 1 to 16 `Interpolator`
     members built over the same grid -- the same ``keys`` in the same order,
     bit-identical abscissae per axis -- whose tables share their ``gal_type``
@@ -546,6 +550,9 @@ class JointInterpolator:
     permuting the members or the list of a member other than member 0 returns
     the same bits.
     """
+
+    kind = 'joint_interp'
+    _Device = _DeviceJointInterp
 
     def __init__(self, interpolators):
         from .interpolator import Interpolator
@@ -589,68 +596,23 @@ class JointInterpolator:
                         'Member {}: table {} does not have the gal_type table '
                         "of member 0's table at its grid node.".format(m, k))
         self.keys = list(first.keys)
-        sizes = [len(member.tabcorr_list[0].tpcf_matrix)
-                 for member in self.interpolators]
-        offsets = np.concatenate([[0], np.cumsum(sizes)])
-        self.slices = [slice(int(offsets[m]), int(offsets[m + 1]))
-                       for m in range(n_members)]
-        self.n_r_total = int(offsets[-1])
-        self._device = None
+        self._set_parts(
+            self.interpolators,
+            [member.tabcorr_list[0] for member in self.interpolators],
+            [halotab for member in self.interpolators
+             for halotab in member.tabcorr_list], self.keys)
 
-    def to_device(self):
-        """Upload the members and create the joint handle (done lazily by the
-        first call)."""
-        devices = [member.to_device() for member in self.interpolators]
-        if self._device is None or any(
-                a is not b for a, b in zip(self._device.devices, devices)):
-            self._device = _DeviceJointInterp(devices)
-        return self._device
-
-    # -- arguments ------------------------------------------------------------
-
-    _operands = JointLikelihood._operands
-
-    def _split(self, array, leading):
-        return [np.ascontiguousarray(array[..., part]).reshape(
-            leading + tuple(member.tabcorr_list[0].tpcf_shape))
-            for part, member in zip(self.slices, self.interpolators)]
-
-    def _inputs(self, theta, x, extrapolate, assembias, family):
+    def _draws(self, theta, assembias, x, extrapolate):
         """``theta (n, 5)`` -- ``(n, 7)`` decorated -- and ``x (n, D)``,
-        checked before any device is touched (`Interpolator._grad_inputs`)."""
-        _zheng07_only(family)
+        checked as `Interpolator._grad_inputs` does."""
         return self.interpolators[0]._grad_inputs(theta, x, extrapolate,
                                                   assembias)
 
-    def _grad_call(self, theta, x, n_gauss_prim, modulate_with_cenocc,
-                   assembias, operands=None, want_fisher=False):
-        """The derivative entry for checked ``(theta, x)``: the results on the
-        joint axis of ``n_r_total`` entries; the family is in the flags."""
-        return _grad.call(
-            self.to_device(), 'joint_interp', _grad.family_of(assembias),
-            [theta, theta.shape[1], x, len(theta), n_gauss_prim,
-             _flags(False, modulate_with_cenocc, assembias)],
-            theta.shape[1] + len(self.keys), (self.n_r_total, ), operands,
-            want_fisher)
+    def _model_draws(self, model, extrapolate):
+        x = self.interpolators[0]._x_model(model)
+        return (x[np.newaxis], ), {'extrapolate': extrapolate}
 
     # -- batched calls --------------------------------------------------------
-
-    def _forward_call(self, form, theta, x, n_gauss_prim, extrapolate,
-                      modulate_with_cenocc, assembias, family, operands=()):
-        """The forward entry (``_lib.FORWARD_ENTRIES['joint_interp', form,
-        'host']``) for ``(theta, x)`` and operands that are checked here,
-        before any device is touched: the results on the joint axis of
-        ``n_r_total`` entries."""
-        theta, x = self._inputs(theta, x, extrapolate, assembias, family)
-        if operands:
-            operands = self._operands(*operands)
-        n_draws = len(theta)
-        shapes = ((n_draws, ), (n_draws, ) if operands else
-                  (n_draws, self.n_r_total))
-        return _forward.call(
-            self.to_device(), 'joint_interp', form,
-            (theta, theta.shape[1], x, n_draws, n_gauss_prim,
-             _flags(False, modulate_with_cenocc, assembias)), shapes, operands)
 
     def predict_batch(self, theta, x, n_gauss_prim=10, extrapolate=False,
                       modulate_with_cenocc=False, assembias=False,
@@ -671,10 +633,9 @@ class JointInterpolator:
         the one-launch kernel does not serve: a mode ``'auto'`` member of more
         than 20 correlation function bins or more than 248 bins, or rows
         beyond the kernel's LDS."""
-        ngal, xi = self._forward_call('predict', theta, x, n_gauss_prim,
-                                      extrapolate, modulate_with_cenocc,
-                                      assembias, family)
-        return ngal, self._split(xi, (len(ngal), ))
+        return self._predict_batch(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family, x,
+            extrapolate))
 
     def chi2_batch(self, theta, x, data, precision, n_gauss_prim=10,
                    extrapolate=False, modulate_with_cenocc=False,
@@ -685,9 +646,9 @@ class JointInterpolator:
         ``(n_draws, )`` -- what an ensemble sampler over the model's and the
         grid's parameters asks per step.  ``data`` and ``precision`` as
         `chi2_grad_batch` takes them."""
-        return self._forward_call('chi2', theta, x, n_gauss_prim, extrapolate,
-                                  modulate_with_cenocc, assembias, family,
-                                  (data, precision))
+        return self._forward_call('chi2', self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family, x,
+            extrapolate), (data, precision))
 
     def predict_batch_grad(self, theta, x, n_gauss_prim=10, extrapolate=False,
                            modulate_with_cenocc=False, assembias=False,
@@ -706,19 +667,9 @@ class JointInterpolator:
         ``family='leauthaud11'`` and for a joint whose rows do not fit the
         kernel's LDS.
         """
-        theta, x = self._inputs(theta, x, extrapolate, assembias, family)
-        n_draws = len(theta)
-        ngal, xi, dngal, dxi = self._grad_call(
-            theta, x, n_gauss_prim, modulate_with_cenocc, assembias)
-        return (ngal, self._split(xi, (n_draws, )), dngal,
-                self._split(dxi, (n_draws, dngal.shape[1])))
-
-    def _chi2(self, theta, x, data, precision, n_gauss_prim, extrapolate,
-              modulate_with_cenocc, assembias, want_fisher, family):
-        theta, x = self._inputs(theta, x, extrapolate, assembias, family)
-        operands = self._operands(data, precision)
-        return self._grad_call(theta, x, n_gauss_prim, modulate_with_cenocc,
-                               assembias, operands, want_fisher)
+        return self._predict_batch_grad(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family, x,
+            extrapolate))
 
     def chi2_grad_batch(self, theta, x, data, precision, n_gauss_prim=10,
                         extrapolate=False, modulate_with_cenocc=False,
@@ -728,8 +679,9 @@ class JointInterpolator:
         ``n_r``): ``ngal, chi2`` ``(n_draws, )``, ``dngal, dchi2``
         ``(n_draws, 5 + D)``.  ``data`` is flat ``(N, )`` or a list of
         per-member arrays, ``precision`` ``(N, N)``."""
-        return self._chi2(theta, x, data, precision, n_gauss_prim, extrapolate,
-                          modulate_with_cenocc, assembias, False, family)
+        return self._grad_call(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family, x,
+            extrapolate), (data, precision))
 
     def chi2_fisher_batch(self, theta, x, data, precision, n_gauss_prim=10,
                           extrapolate=False, modulate_with_cenocc=False,
@@ -738,33 +690,19 @@ class JointInterpolator:
         dxi_k^T P_sym dxi_l`` of the joint data vector over ``(theta, x)``,
         ``(n_draws, 5 + D, 5 + D)``, from the same launch: the off-diagonal
         blocks of ``precision`` couple the members."""
-        return self._chi2(theta, x, data, precision, n_gauss_prim, extrapolate,
-                          modulate_with_cenocc, assembias, True, family)
+        return self._grad_call(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family, x,
+            extrapolate), (data, precision), True)
 
     def fisher_batch(self, theta, x, precision, n_gauss_prim=10,
                      extrapolate=False, modulate_with_cenocc=False,
                      assembias=False, family='zheng07'):
         """The forecast form, which needs no data: ``ngal, dngal, fisher``."""
-        ngal, _, dngal, _, fisher = self.chi2_fisher_batch(
-            theta, x, np.zeros(self.n_r_total), precision,
-            n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-            modulate_with_cenocc=modulate_with_cenocc, assembias=assembias,
-            family=family)
-        return ngal, dngal, fisher
+        return self._fisher_batch(self._inputs(
+            theta, n_gauss_prim, modulate_with_cenocc, assembias, family, x,
+            extrapolate), precision)
 
     # -- un-batched forms -----------------------------------------------------
-
-    def _model_inputs(self, model, check_consistency, assembias, what):
-        x = self.interpolators[0]._x_model(model)
-        if check_consistency:
-            for member in self.interpolators:
-                for halotab in member.tabcorr_list:
-                    halotab._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, what)
-        model_keys = tuple(_grad_keys(assembias))
-        theta = np.asarray(spec.theta,
-                           dtype=np.float64)[np.newaxis, :len(model_keys)]
-        return spec, model_keys + tuple(self.keys), theta, x[np.newaxis]
 
     def predict_grad(self, model, n_gauss_prim=10, extrapolate=False,
                      check_consistency=True, assembias=False):
@@ -773,16 +711,8 @@ class JointInterpolator:
         `Interpolator.predict_grad`: ``ngal`` (float), ``xis`` (list of arrays
         of each member's ``tpcf_shape``), ``dngal`` (dict by the model keys,
         then ``self.keys``) and ``dxis`` (dict by the same keys of lists)."""
-        spec, keys, theta, x = self._model_inputs(
-            model, check_consistency, assembias, 'predict_grad')
-        ngal, xis, dngal, dxis = self.predict_batch_grad(
-            theta, x, n_gauss_prim=n_gauss_prim, extrapolate=extrapolate,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        return (float(ngal[0]), [xi[0] for xi in xis],
-                _grad.keyed(dngal[0], keys),
-                {key: [dxi[0, k] for dxi in dxis]
-                 for k, key in enumerate(keys)})
+        return self._predict_grad(model, n_gauss_prim, extrapolate,
+                                  check_consistency, assembias)
 
     def chi2_fisher(self, model, data, precision, n_gauss_prim=10,
                     extrapolate=False, check_consistency=True,
@@ -790,12 +720,5 @@ class JointInterpolator:
         """Un-batched `chi2_fisher_batch` for a model object: ``ngal``,
         ``chi2`` (floats), ``dngal``, ``dchi2`` (dicts by the model keys, then
         ``self.keys``) and ``fisher`` ``(5 + D, 5 + D)`` in that order."""
-        spec, keys, theta, x = self._model_inputs(
-            model, check_consistency, assembias, 'chi2_fisher')
-        ngal, chi2, dngal, dchi2, fisher = self.chi2_fisher_batch(
-            theta, x, data, precision, n_gauss_prim=n_gauss_prim,
-            extrapolate=extrapolate,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        return (float(ngal[0]), float(chi2[0]), _grad.keyed(dngal[0], keys),
-                _grad.keyed(dchi2[0], keys), fisher[0])
+        return self._chi2_fisher(model, data, precision, n_gauss_prim,
+                                 extrapolate, check_consistency, assembias)

@@ -20,16 +20,17 @@ Extensions beyond the reference (the reason to use a GPU at all):
 import ctypes
 import sys
 import threading
+import weakref
 
 import numpy as np
 
 from . import _forward
 from . import _grad
 from . import _lib
+from . import _seam
 from . import pinned
 from .galtable import GalTypeTable
-from .models import (LEAUTHAUD11_GRAD_KEYS, LEAUTHAUD11_KEYS,
-                     ZHENG07_ASSEMBIAS_KEYS, ZHENG07_KEYS, device_spec)
+from .models import device_spec
 
 ATTR_KEYS = ['tpcf', 'mode', 'simname', 'redshift', 'Num_ptcl_requirement',
              'prim_haloprop_key', 'sec_haloprop_key']
@@ -40,7 +41,7 @@ XI_KEYS = {'auto': ['centrals-centrals', 'centrals-satellites',
 NGAL_KEYS = ['centrals', 'satellites']
 
 
-class _DeviceTable:
+class _DeviceTable(_lib.Handle):
     """Owner of a ``tc_table`` handle."""
 
     def __init__(self, halotab, compute_dtype):
@@ -82,8 +83,7 @@ class _DeviceTable:
             dist_index_p, is_central.ctypes.data_as(_lib.c_uint8_p),
             _lib.DTYPE_F32 if compute_dtype == 'float32' else _lib.DTYPE_F64,
             ctypes.byref(handle)))
-        self.handle = handle
-        self.lib = lib
+        super().__init__(lib, handle, 'tc_table_destroy')
         self.n_bins = len(gal_type)
         self.n_r = matrix.shape[0]
         self.n_components = 3 if mode == 'auto' else 2
@@ -117,15 +117,6 @@ class _DeviceTable:
             if status:
                 _lib.check(status)
             return self._one_ngal[0], self._one_xi.copy()
-
-    def __del__(self):
-        handle = getattr(self, 'handle', None)
-        if handle is not None and handle.value is not None:
-            try:
-                self.lib.tc_table_destroy(handle)
-            except Exception:  # interpreter shutdown
-                pass
-            self.handle = None
 
 
 class TabCorr:
@@ -571,7 +562,9 @@ class TabCorr:
         devices = [halotab.to_device() for halotab in halotabs]
         first = devices[0]
         cache = getattr(first, '_joint', None)
-        if cache is None or cache[0] != [id(d) for d in devices]:
+        # (weak references: the cache hangs on `first`, which is among them)
+        if cache is None or len(cache[0]) != len(devices) or any(
+                ref() is not d for ref, d in zip(cache[0], devices)):
             handles = (ctypes.c_void_p * len(devices))(
                 *[d.handle.value for d in devices])
             theta = np.zeros(16)
@@ -582,11 +575,11 @@ class TabCorr:
             # (every table's lock, in one fixed order whatever the order of
             # the tables in the call)
             locks = [d.lock for d in sorted(devices, key=id)]
-            cache = ([id(d) for d in devices], handles, theta,
+            cache = ([weakref.ref(d) for d in devices], handles, theta,
                      _lib.as_double_p(theta), ngal, _lib.as_double_p(ngal), xi,
-                     xi_p, locks, devices)
+                     xi_p, locks)
             first._joint = cache
-        _, handles, theta, theta_p, ngal, ngal_p, xi, xi_p, locks, _ = cache
+        _, handles, theta, theta_p, ngal, ngal_p, xi, xi_p, locks = cache
         values = spec.values
         flags = _flags(False, spec.modulate_with_cenocc, spec.assembias,
                        spec.family)
@@ -739,7 +732,7 @@ class TabCorr:
             self.to_device(), 'table', _grad.family_of(assembias, family),
             [theta, theta.shape[1], len(theta), n_gauss_prim,
              _flags(False, modulate_with_cenocc)],
-            len(_grad_keys(assembias, family)), self.tpcf_shape)
+            len(_grad.keys_of(assembias, family)), self.tpcf_shape)
 
     def chi2_grad_batch(self, theta, data, precision, n_gauss_prim=10,
                         modulate_with_cenocc=False, assembias=False,
@@ -772,7 +765,7 @@ class TabCorr:
             self.to_device(), 'table', _grad.family_of(assembias, family),
             [theta, theta.shape[1], len(theta), n_gauss_prim,
              _flags(False, modulate_with_cenocc)],
-            len(_grad_keys(assembias, family)), self.tpcf_shape,
+            len(_grad.keys_of(assembias, family)), self.tpcf_shape,
             (data, precision), want_fisher)
 
     def predict_grad(self, model, n_gauss_prim=10, check_consistency=True,
@@ -796,24 +789,12 @@ class TabCorr:
         """
         if check_consistency:
             self._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'predict_grad', leauthaud11=True)
-        if spec.family == 'leauthaud11':
-            ngal, xi, dngal, dxi = self.predict_batch_grad(
-                spec.theta[np.newaxis], n_gauss_prim=n_gauss_prim,
-                modulate_with_cenocc=spec.modulate_with_cenocc,
-                family='leauthaud11')
-            columns = _leauthaud11_columns(model)
-            return (float(ngal[0]), xi[0],
-                    _grad.keyed(dngal[0], columns=columns),
-                    _grad.keyed(dxi[0], columns=columns))
-        keys = _grad_keys(assembias)
+        theta, options, columns, _ = _grad.model_columns(
+            model, assembias, 'predict_grad', leauthaud11=True)
         ngal, xi, dngal, dxi = self.predict_batch_grad(
-            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
-            n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], keys),
-                _grad.keyed(dxi[0], keys))
+            theta, n_gauss_prim=n_gauss_prim, **options)
+        return (float(ngal[0]), xi[0], _grad.keyed(dngal[0], columns=columns),
+                _grad.keyed(dxi[0], columns=columns))
 
     # -- Fisher matrix of the likelihood ---------------------------------------------------
 
@@ -896,24 +877,12 @@ class TabCorr:
         """
         if check_consistency:
             self._check_consistency_cached(model)
-        spec = _grad_spec(model, assembias, 'fisher', leauthaud11=True)
-        if spec.family == 'leauthaud11':
-            ngal, dngal, fisher = self.fisher_batch(
-                spec.theta[np.newaxis], precision, n_gauss_prim=n_gauss_prim,
-                modulate_with_cenocc=spec.modulate_with_cenocc,
-                family='leauthaud11')
-            jacobian = model.device_jacobian()
-            return (float(ngal[0]),
-                    _grad.keyed(dngal[0],
-                                columns=_leauthaud11_columns(model)),
-                    jacobian.T @ fisher[0] @ jacobian)
-        keys = _grad_keys(assembias)
+        theta, options, columns, jacobian = _grad.model_columns(
+            model, assembias, 'fisher', leauthaud11=True)
         ngal, dngal, fisher = self.fisher_batch(
-            np.asarray(spec.theta, dtype=np.float64)[np.newaxis, :len(keys)],
-            precision, n_gauss_prim=n_gauss_prim,
-            modulate_with_cenocc=spec.modulate_with_cenocc,
-            assembias=assembias)
-        return float(ngal[0]), _grad.keyed(dngal[0], keys), fisher[0]
+            theta, precision, n_gauss_prim=n_gauss_prim, **options)
+        return (float(ngal[0]), _grad.keyed(dngal[0], columns=columns),
+                _grad.carried(fisher[0], jacobian))
 
     # -- reverse mode at the occupation seam ---------------------------------------------
 
@@ -960,31 +929,13 @@ class TabCorr:
         tables, very large mode-auto tables).
         """
         occupation, batched = self._vjp_occupation(occupation)
-        n_draws = len(occupation)
-        n_r = len(self.tpcf_matrix)
         shape = tuple(self.tpcf_shape)
-        g_xi = np.asarray(g_xi, dtype=np.float64)
-        if g_xi.shape != ((n_draws, ) if batched else ()) + shape:
-            raise ValueError('g_xi must have shape {}, got {}.'.format(
-                ((n_draws, ) if batched else ()) + shape, g_xi.shape))
-        g_xi = _lib.contiguous(g_xi.reshape(n_draws, n_r))
-        if g_ngal is not None:
-            g_ngal = np.asarray(g_ngal, dtype=np.float64)
-            if g_ngal.shape != ((n_draws, ) if batched else ()):
-                raise ValueError('g_ngal must have shape {}, got {}.'.format(
-                    (n_draws, ) if batched else (), g_ngal.shape))
-            g_ngal = _lib.contiguous(g_ngal.reshape(n_draws))
-        device = self.to_device()
-        ngal = np.empty(n_draws)
-        xi = np.empty((n_draws, n_r))
-        g_occupation = np.empty_like(occupation)
-        with device.lock:
-            _lib.check(device.lib.tc_predict_occupation_vjp_batch(
-                device.handle, _lib.as_double_p(occupation), n_draws, 0,
-                None if g_ngal is None else _lib.as_double_p(g_ngal),
-                _lib.as_double_p(g_xi), _lib.as_double_p(ngal),
-                _lib.as_double_p(xi), _lib.as_double_p(g_occupation)))
-        xi = xi.reshape((n_draws, ) + shape)
+        cotangents = _seam.cotangents(g_xi, g_ngal, len(occupation), batched,
+                                      shape)
+        ngal, xi, g_occupation = _seam.call(
+            self.to_device(), 'table', 'predict', occupation,
+            cotangents=cotangents)
+        xi = xi.reshape((len(ngal), ) + shape)
         if not batched:
             return ngal[0], xi[0], g_occupation[0]
         return ngal, xi, g_occupation
@@ -1004,18 +955,9 @@ class TabCorr:
         dchi2_docc : ``(n_draws, n_bins)``, in the row order of ``gal_type``
         """
         occupation, batched = self._vjp_occupation(occupation)
-        data, precision = _chi2_operands(data, precision,
-                                         len(self.tpcf_matrix))
-        device = self.to_device()
-        n_draws = len(occupation)
-        ngal, chi2 = np.empty(n_draws), np.empty(n_draws)
-        dchi2 = np.empty_like(occupation)
-        with device.lock:
-            _lib.check(device.lib.tc_chi2_occupation_grad_batch(
-                device.handle, _lib.as_double_p(occupation), n_draws, 0,
-                _lib.as_double_p(data), _lib.as_double_p(precision),
-                _lib.as_double_p(ngal), _lib.as_double_p(chi2),
-                _lib.as_double_p(dchi2)))
+        operands = _chi2_operands(data, precision, len(self.tpcf_matrix))
+        ngal, chi2, dchi2 = _seam.call(self.to_device(), 'table', 'chi2',
+                                       occupation, operands=operands)
         if not batched:
             return ngal[0], chi2[0], dchi2[0]
         return ngal, chi2, dchi2
@@ -1074,13 +1016,6 @@ def _flags(separate_gal_type=False, modulate_with_cenocc=False,
             (_lib.FLAG_LEAUTHAUD11 if family == 'leauthaud11' else 0))
 
 
-def _grad_keys(assembias=False, family='zheng07'):
-    """The differentiated model parameters, in column order."""
-    if family == 'leauthaud11':
-        return LEAUTHAUD11_GRAD_KEYS
-    return ZHENG07_ASSEMBIAS_KEYS if assembias else ZHENG07_KEYS
-
-
 def _grad_theta(theta, assembias=False, family='zheng07'):
     """The ``(n_draws, 5)`` parameter array of the gradient calls --
     ``(n_draws, 7)`` for the model decorated with assembly bias,
@@ -1092,45 +1027,11 @@ def _grad_theta(theta, assembias=False, family='zheng07'):
         raise ValueError("family='leauthaud11' has no assembly bias: not "
                          "together with assembias=True.")
     theta = _lib.contiguous(np.atleast_2d(theta))
-    n_cols = 14 if family == 'leauthaud11' else len(_grad_keys(assembias))
+    n_cols = 14 if family == 'leauthaud11' else len(_grad.keys_of(assembias))
     if theta.ndim != 2 or theta.shape[1] != n_cols:
         raise ValueError('theta must have shape (n_draws, {}), got {}.'.format(
             n_cols, theta.shape))
     return theta
-
-
-def _leauthaud11_columns(model):
-    """`LEAUTHAUD11_KEYS` -> (device column, factor): each of the sixteen
-    parameters moves one of the eleven device columns -- ``smhm_X_0`` and
-    ``smhm_X_a`` the relation's X, the other six their own --, by its entry
-    of `Leauthaud11Model.device_jacobian` (zero for ``smhm_X_a`` at
-    redshift 0)."""
-    jacobian = model.device_jacobian()
-    columns = {}
-    for j, key in enumerate(LEAUTHAUD11_KEYS):
-        k = j // 2 if j < 10 else j - 5
-        columns[key] = (k, float(jacobian[k, j]))
-    return columns
-
-
-def _grad_spec(model, assembias, what, leauthaud11=False):
-    """The device spec of the model of an un-batched gradient call: plain
-    Zheng07 -- with ``assembias`` Zheng07 decorated with assembly bias;
-    ``leauthaud11``: the caller serves a `Leauthaud11Model` too."""
-    spec = device_spec(model)
-    if (leauthaud11 and not assembias and spec is not None and
-            spec.family == 'leauthaud11'):
-        return spec
-    if not assembias:
-        if spec is None or spec.family != 'zheng07' or spec.assembias:
-            raise NotImplementedError(
-                '{} needs a plain Zheng07 model (no assembly bias, no other '
-                'family).'.format(what))
-    elif spec is None or spec.family != 'zheng07' or not spec.assembias:
-        raise ValueError(
-            '{} with assembias=True needs a Zheng07 model decorated with '
-            'assembly bias.'.format(what))
-    return spec
 
 
 def _chi2_operands(data, precision, n_r):
